@@ -30,25 +30,25 @@ a)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/${tag}_smoke.log 2>&1; echo "smoke rc=$?"
   trace c2_lz4 --steps 10 --warmup 3
   pmc2 c2 c2_lz4_64k 100000
-  timeout -k 10 900 python bench.py > $out/${tag}_c2_lz4_bench.json 2> $out/c2.err; echo "bench c2 rc=$?"; line c2_lz4 ;;
+  timeout -k 10 900 python bench.py --full > $out/${tag}_c2_lz4_bench.json 2> $out/c2.err; echo "bench c2 rc=$?"; line c2_lz4 ;;
 b)
   trace c3_zstd --workload c3_zstd_256k --steps 3 --warmup 1
   pmc2 c3 c3_zstd_256k 100000 --workload c3_zstd_256k
-  timeout -k 10 900 python bench.py --workload c3_zstd_256k --steps 3 --warmup 1 > $out/${tag}_c3_zstd_bench.json 2> $out/c3.err; echo "bench c3 rc=$?"; line c3_zstd
+  timeout -k 10 900 python bench.py --workload c3_zstd_256k --steps 3 --warmup 1 --full > $out/${tag}_c3_zstd_bench.json 2> $out/c3.err; echo "bench c3 rc=$?"; line c3_zstd
   trace c4_mixed --workload c4_mixed --steps 3 --warmup 1
   pmc2 c4 c4_mixed 125000 --workload c4_mixed
-  timeout -k 10 900 python bench.py --workload c4_mixed --steps 3 --warmup 1 > $out/${tag}_c4_mixed_bench.json 2> $out/c4.err; echo "bench c4 rc=$?"; line c4_mixed
+  timeout -k 10 900 python bench.py --workload c4_mixed --steps 3 --warmup 1 --full > $out/${tag}_c4_mixed_bench.json 2> $out/c4.err; echo "bench c4 rc=$?"; line c4_mixed
   timeout -k 10 600 python bench.py --gpus 4 --workload c4_mixed --entries 40000 --steps 3 --warmup 1 --no-cpu > $out/${tag}_c4_4rank_40000_one_card_rehearsal.json 2> $out/strong.err; echo "4-rank rc=$?"; cut -c1-300 $out/${tag}_c4_4rank_40000_one_card_rehearsal.json
   timeout -k 10 600 python bench.py --gpus 2 --workload c5_zstd1_1m --entries 600 --steps 2 --warmup 1 --no-cpu > $out/${tag}_c5_2rank_one_card_rehearsal.json 2> $out/c5x2.err; echo "c5 2-rank rc=$?" ;;
 b4)   # (only the C4 part of b)
   pmc2 c4 c4_mixed 125000 --workload c4_mixed
-  timeout -k 10 900 python bench.py --workload c4_mixed --steps 3 --warmup 1 > $out/${tag}_c4_mixed_bench.json 2> $out/c4.err; echo "bench c4 rc=$?"; line c4_mixed ;;
+  timeout -k 10 900 python bench.py --workload c4_mixed --steps 3 --warmup 1 --full > $out/${tag}_c4_mixed_bench.json 2> $out/c4.err; echo "bench c4 rc=$?"; line c4_mixed ;;
 c)
   { python3 tools/host_rate.py 20000 2 2>&1 | tail -2; python3 tools/host_rate.py 60000 2 2>&1 | tail -1; python3 tools/host_rate.py 8000 1 2>&1 | tail -1; } | tee $out/${tag}_host_rate.txt
   { python3 tools/host_write_rate.py 4000 1048576 1 1 2>&1 | grep -v amdgpu.ids | tail -3; python3 tools/host_write_rate.py 40000 65536 2 0 2>&1 | grep -v amdgpu.ids | tail -3; } | tee $out/${tag}_host_write_rate.txt
   trace c5_zstd1 --workload c5_zstd1_1m --steps 2 --warmup 1
   pmc2 c5 c5_zstd1_1m 12500 --workload c5_zstd1_1m
-  timeout -k 10 1100 python bench.py --workload c5_zstd1_1m --steps 3 --warmup 1 > $out/${tag}_c5_zstd1_bench.json 2> $out/c5.err; echo "bench c5 rc=$?"; line c5_zstd1
+  timeout -k 10 1100 python bench.py --workload c5_zstd1_1m --steps 3 --warmup 1 --full > $out/${tag}_c5_zstd1_bench.json 2> $out/c5.err; echo "bench c5 rc=$?"; line c5_zstd1
   { timeout -k 10 300 python3 tools/enc_bench.py 4000 1048576 1 2>&1 | grep -E "^(text|records|random|runs) "; timeout -k 10 300 python3 tools/enc_bench.py 2000 1048576 3 2>&1 | grep -E "^(text|records|random|runs) "; } | tee $out/${tag}_enc_classes_levels.txt ;;
 d)
   timeout -k 10 1100 python3 tools/fuzz_gpu.py 400 11 all > $out/${tag}_fuzz_all.log 2>&1; echo "fuzz rc=$?"; tail -8 $out/${tag}_fuzz_all.log ;;

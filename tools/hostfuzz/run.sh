@@ -5,8 +5,10 @@
 # no read outside the entry, and every accepted plan tiles its entry exactly.  tools/hostfuzz/run.sh [iterations]
 set -e
 cd "$(dirname "$0")/../.."
-mkdir -p /tmp/zpk_hostfuzz
-python3 - <<'PY'
+work=$(mktemp -d -t zpk_hostfuzz.XXXXXX)       # private to this run: a directory left by another user cannot block it
+trap 'rm -rf "$work"' EXIT
+WORK=$work python3 - <<'PY'
+import os
 import re
 s = open("zpack_amd/csrc/zpk_codec.hip").read()
 # the walkers as they are in the source (no copy to drift): frame sequences + one LZ4 frame; then one Zstandard frame
@@ -16,7 +18,7 @@ l4 = open("zpack_amd/csrc/lz4_pj.h").read(); zs = open("zpack_amd/csrc/zstd_pj.h
 types = "#define PJ_BLOCK 65536u\n#define ZPJ_BLOCK (128u << 10)\n#define ZPJ_NONE 0xFFFFFFFFu\n#define ZPK_PJ_MIN_BLOCKS 4u\n#define ZPK_ZPJ_MIN_BLOCKS 2u\n"
 types += re.search(r"struct PjBlock \{[^}]*\};", l4).group(0) + "\n" + re.search(r"struct ZpjBlock \{.*?\n\};", zs, re.S).group(0) + "\n"
 t = open("tools/hostfuzz/walk_fuzz_main.cpp.in").read().replace("/*@TYPES@*/", types).replace("/*@WALKERS@*/", s[a:b] + s[c:d])
-open("/tmp/zpk_hostfuzz/walk_fuzz.cpp", "w").write(t)
+open(os.path.join(os.environ["WORK"], "walk_fuzz.cpp"), "w").write(t)
 PY
-g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -std=c++17 -o /tmp/zpk_hostfuzz/walk_fuzz /tmp/zpk_hostfuzz/walk_fuzz.cpp
-/tmp/zpk_hostfuzz/walk_fuzz ${1:-3000000}
+g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -std=c++17 -o "$work/walk_fuzz" "$work/walk_fuzz.cpp"
+"$work/walk_fuzz" ${1:-3000000}

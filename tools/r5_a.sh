@@ -5,7 +5,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_codec.py tests/test_gpu_zpack_
 tail -5 $out/pytest.log
 [ $rc -eq 0 ] || exit $rc
 for mix in 3 0 1 -1; do
-  timeout -k 10 300 python bench.py --mix $mix --steps 8 --warmup 2 --no-cpu > $out/c2_mix$mix.json 2> $out/c2_mix$mix.err || { tail -5 $out/c2_mix$mix.err; exit 1; }
+  timeout -k 10 300 python bench.py --mix $mix --steps 8 --warmup 2 --full --no-cpu > $out/c2_mix$mix.json 2> $out/c2_mix$mix.err || { tail -5 $out/c2_mix$mix.err; exit 1; }
   python3 - <<PY
 import json
 d=json.loads(open("$out/c2_mix$mix.json").read().strip().splitlines()[-1]); r=d["roofline"]

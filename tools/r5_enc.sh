@@ -6,7 +6,7 @@
 out=gpurun_out/r05enc; mkdir -p $out
 for v in head tag head tag; do
   if [ $v = tag ]; then export ZPACK_AMD_CODEC_SO=$PWD/zpack_amd/dev/${ENC_VARIANT_SO:-ab_enctag.so}; else unset ZPACK_AMD_CODEC_SO; fi
-  timeout -k 10 400 python bench.py --workload c5_zstd1_1m --steps 3 --warmup 1 --no-cpu > $out/$v.json 2> $out/$v.err || { echo "$v failed"; tail -3 $out/$v.err; exit 1; }
+  timeout -k 10 400 python bench.py --workload c5_zstd1_1m --steps 3 --warmup 1 --full --no-cpu > $out/$v.json 2> $out/$v.err || { echo "$v failed"; tail -3 $out/$v.err; exit 1; }
   python3 - <<PY
 import json
 d=json.loads(open("$out/$v.json").read().strip().splitlines()[-1]); r=d["roofline"]

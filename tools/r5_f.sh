@@ -7,7 +7,7 @@ tail -5 $out/pytest.log
 [ $rc -eq 0 ] || exit $rc
 one() {  # so label args...
   so=$1; label=$2; shift 2
-  ZPACK_AMD_CODEC_SO=$so timeout -k 10 400 python bench.py "$@" --no-cpu > $out/$label.json 2> $out/$label.err || { tail -5 $out/$label.err; return 1; }
+  ZPACK_AMD_CODEC_SO=$so timeout -k 10 400 python bench.py "$@" --full --no-cpu > $out/$label.json 2> $out/$label.err || { tail -5 $out/$label.err; return 1; }
   python3 - <<PY
 import json
 d=json.loads(open("$out/$label.json").read().strip().splitlines()[-1]); r=d["roofline"]
