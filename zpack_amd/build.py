@@ -96,7 +96,8 @@ def build_codec_dev(force=False, verbose=False):
 def build_zpack(force=False, verbose=False):
     host = os.path.join(HERE, "host")
     csrcs = sorted(os.path.join(host, f) for f in os.listdir(host) if f.endswith(".c"))
-    deps = csrcs + [os.path.join(ROOT, "include", "zpack.h"), os.path.join(ROOT, "include", "zpack_codec.h"), CODEC_SO]
+    deps = csrcs + [os.path.join(host, "internal.h"), os.path.join(ROOT, "include", "zpack.h"), os.path.join(ROOT, "include", "zpack_amd.h"),
+                    os.path.join(ROOT, "include", "zpack_codec.h"), CODEC_SO]
     dig = _stale(ZPACK_SO, deps)
     if not force and dig is None:
         return ZPACK_SO

@@ -22,9 +22,11 @@ static inline void zi_put64(zpack_u8* p, zpack_u64 v) { for (int i = 0; i < 8; i
 #define zi_fseek(fp, off, whence) fseeko((fp), (off_t)(off), (whence))
 #define zi_ftell(fp) ((zpack_u64)ftello(fp))
 
-/* a context = the device codecs a reader / writer / explicit dctx / cctx works with (util.c) */
+/* a context = the device codecs a reader / writer / explicit dctx / cctx works with (util.c), and the read-ahead window of the
+ * in-order zpack_read_file callers that use it (readahead.c) */
 #define ZI_MAX_DEVICES 16
-typedef struct zi_ctx_s { int n; zpk_codec* dev[ZI_MAX_DEVICES]; } zi_ctx;
+struct zi_ra_s;
+typedef struct zi_ctx_s { int n; zpk_codec* dev[ZI_MAX_DEVICES]; struct zi_ra_s* ra; } zi_ctx;
 zi_ctx* zi_ctx_create(void);                 /* NULL when no HIP device is usable: there is no CPU fallback */
 void    zi_ctx_destroy(zi_ctx* x);
 void    zi_ctx_reset(zi_ctx* x);
@@ -36,6 +38,27 @@ void zi_parallel(int parts, void (*fn)(void*, int), void* arg);
 /* name index of reader-owned entry tables (zpack_get_file_entry) */
 void zi_index_register(const zpack_file_entry* table, zpack_u64 count);
 void zi_index_drop(const zpack_file_entry* table);
+
+/* decode entries in one device batch on context `ctx` (reader.c): per-entry verdicts in res[], reader->last_return untouched.
+ * span != NULL: the payloads come from there — archive bytes [span_lo, span_lo + span_size - 1) and one pad byte, covering
+ * entries that all pass the host guards — instead of the reader's memory image or file */
+int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
+                      zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
+                      const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size);
+
+/* read-ahead for in-order zpack_read_file callers (readahead.c) */
+struct zi_ra_s* zi_ra_create(void);          /* reads ZPACK_AMD_READ_AHEAD; NULL when out of memory (read-ahead is then off) */
+void zi_ra_destroy(struct zi_ra_s* ra);
+void zi_ra_drop(struct zi_ra_s* ra);         /* forget the window and free its memory */
+/* 1 when the call was answered from a window (buffer filled, last_return set), 0 when the caller decodes the entry on its own;
+ * called once the host guards of zpack_read_file have passed */
+int  zi_ra_read(zi_ctx* ctx, zpack_reader* reader, const zpack_file_entry* entry, zpack_u8* buffer);
+/* an entry answered before any decode (comp_size 0): still a step of an in-order run of this context */
+void zi_ra_step(zi_ctx* ctx, zpack_reader* reader, const zpack_file_entry* entry);
+/* reader generations: a new one at every parse of a reader, dropped by zpack_close_reader; 0 = a reader never parsed here */
+void      zi_reader_gen_new(const zpack_reader* reader);
+void      zi_reader_gen_drop(const zpack_reader* reader);
+zpack_u64 zi_reader_gen(const zpack_reader* reader);
 
 /* per-stream aggregation state hung off zpack_stream.xxh3_state */
 typedef struct zi_stream_state_s {

@@ -218,6 +218,7 @@ static int reader_load_entries(zpack_reader* reader, const zpack_u8* cdr, size_t
 
 int zpack_read_archive_memory(zpack_reader* reader)
 {
+    zi_reader_gen_new(reader);                            /* no read-ahead window of an earlier parse serves this one */
     if (!reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
     if (reader->file_size < ZPACK_MINIMUM_ARCHIVE_SIZE) return ZPACK_ERROR_FILE_TOO_SMALL;
     const zpack_u8* a = reader->buffer;
@@ -236,6 +237,7 @@ int zpack_read_archive_memory(zpack_reader* reader)
 
 int zpack_read_archive(zpack_reader* reader)
 {
+    zi_reader_gen_new(reader);
     if (!reader->file) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
     if (zi_fseek(reader->file, 0, SEEK_END) != 0) return ZPACK_ERROR_SEEK_FAILED;
     if (!reader->file_size) reader->file_size = (size_t)zi_ftell(reader->file);
@@ -322,31 +324,32 @@ static void read_part(void* arg, int k)
 /* n entries in ONE device batch.  Memory-backed readers hand the codec the archive image itself
  * (zero-copy on the host side, as the reference does at lib/zpack_read.c:345-346); file-backed readers
  * gather the payloads first (the reference mallocs + freads per entry, :336-344). */
-static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
-                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx)
+int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
+                      zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
+                      const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size)
 {
     if (count == 0) return ZPACK_OK;
     if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
-    /* the caller's context, else this reader's own, created on first use (lib/zpack_read.c:17-31) and freed by zpack_close_reader */
-    zi_ctx* ctx = zi_pick_ctx(dctx, &reader->zstd_dctx);
-    if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
-
     zpk_decode_desc* desc = (zpk_decode_desc*)calloc((size_t)count, sizeof(*desc));
-    zpk_decode_result* res = (zpk_decode_result*)calloc((size_t)count, sizeof(*res));
-    if (!desc || !res) { free(desc); free(res); return ZPACK_ERROR_MALLOC_FAILED; }
+    if (!desc) return ZPACK_ERROR_MALLOC_FAILED;
     const zpack_u8* image = reader->buffer;
     zpack_u64 image_size = reader->file_size;
     zpack_u8* gathered = NULL;
     int rc = ZPACK_OK;
 
-    if (reader->file) {
+    if (span) {
+        /* the caller staged archive bytes [span_lo, span_lo + span_size - 1) of entries that all pass the host guards, plus a
+         * 1-byte pad: the same image as the gathered one below, payloads at their distances from each other */
+        for (zpack_u64 i = 0; i < count; i++) fill_desc(&desc[i], entries[i], entries[i]->offset - span_lo, max_sizes[i]);
+        image = span; image_size = span_size;
+    } else if (reader->file) {
         /* pack the payloads of the entries that pass the reference's guards behind a 1-byte pad, so that
          * the device sees the same `offset + comp_size >= file_size` verdicts (lib/zpack_read.c:331) */
         zpack_u64 total = 1;
         for (zpack_u64 i = 0; i < count; i++)
             if (entries[i]->comp_size && entries[i]->offset + entries[i]->comp_size < reader->file_size) total += entries[i]->comp_size;
         gathered = (zpack_u8*)malloc((size_t)total + 1);
-        if (!gathered) { free(desc); free(res); return ZPACK_ERROR_MALLOC_FAILED; }
+        if (!gathered) { free(desc); return ZPACK_ERROR_MALLOC_FAILED; }
         zpack_u64 pos = 0;
         for (zpack_u64 i = 0; i < count && rc == ZPACK_OK; i++) {
             const zpack_file_entry* e = entries[i];
@@ -384,26 +387,49 @@ static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zp
         zi_parallel(parts, read_part, &job);
         for (int k = 0; k < parts; k++) if (job.rc[k] != ZPK_OK) rc = ZPACK_ERROR_NOT_AVAILABLE;
     }
+    free(gathered); free(desc);
+    return rc;
+}
+
+static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx)
+{
+    if (count == 0) return ZPACK_OK;
+    if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
+    /* the caller's context, else this reader's own, created on first use (lib/zpack_read.c:17-31) and freed by zpack_close_reader */
+    zi_ctx* ctx = zi_pick_ctx(dctx, &reader->zstd_dctx);
+    if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
+    zpk_decode_result* res = (zpk_decode_result*)calloc((size_t)count, sizeof(*res));
+    if (!res) return ZPACK_ERROR_MALLOC_FAILED;
+    const int rc = zi_decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0);
     if (rc == ZPACK_OK)
         for (zpack_u64 i = 0; i < count; i++) {
             results[i] = res[i].status;
             if (res[i].status != ZPACK_OK || i + 1 == count) reader->last_return = res[i].status ? (size_t)0 - res[i].detail : 0;
         }
-    free(gathered); free(desc); free(res);
+    free(res);
     return rc;
 }
 
 int zpack_read_file(zpack_reader* reader, zpack_file_entry* entry, zpack_u8* buffer, size_t max_size, void* dctx)
 {
     /* the cheap guards are answered on the host without a device round trip, in the reference's order */
-    if (entry->comp_size == 0) return ZPACK_OK;
+    if (entry->comp_size == 0) {
+        zi_ctx* x = (zi_ctx*)(dctx ? dctx : reader->zstd_dctx);    /* (no context is created for an empty entry) */
+        if (x) zi_ra_step(x, reader, entry);                       /* an empty file does not end an in-order run */
+        return ZPACK_OK;
+    }
     if ((zpack_u64)max_size < entry->uncomp_size) return ZPACK_ERROR_BUFFER_TOO_SMALL;
     if (entry->offset + entry->comp_size >= reader->file_size) return ZPACK_ERROR_FILE_OFFSET_INVALID;
     if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
+    zi_ctx* ctx = zi_pick_ctx(dctx, &reader->zstd_dctx);
+    if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
+    /* an in-order caller is answered from the context's read-ahead window when that decode ended ZPACK_OK (readahead.c) */
+    if (zi_ra_read(ctx, reader, entry, buffer)) return ZPACK_OK;
     int result = ZPACK_OK;
     zpack_file_entry* one = entry;
     zpack_u8* out = buffer;
-    int rc = read_batch(reader, &one, 1, &out, &max_size, &result, dctx);
+    int rc = read_batch(reader, &one, 1, &out, &max_size, &result, ctx);
     return rc ? rc : result;
 }
 
@@ -542,7 +568,9 @@ int zpack_init_reader_memory_shared(zpack_reader* reader, zpack_u8* buffer, size
 
 void zpack_reset_reader_dctx(zpack_reader* reader)
 {
-    zi_ctx_reset((zi_ctx*)reader->zstd_dctx);                   /* lib/zpack_read.c:679-690: after an abandoned stream / error */
+    zi_ctx* x = (zi_ctx*)reader->zstd_dctx;
+    zi_ctx_reset(x);                                            /* lib/zpack_read.c:679-690: after an abandoned stream / error */
+    if (x) zi_ra_drop(x->ra);
 }
 
 void zpack_close_reader(zpack_reader* reader)
@@ -550,6 +578,7 @@ void zpack_close_reader(zpack_reader* reader)
     if (reader->file) fclose(reader->file);
     if (!reader->buffer_shared) free(reader->buffer);
     reader_drop_table(reader);                                 /* names in one arena (reader_load_entries) or one malloc each */
+    zi_reader_gen_drop(reader);
     zi_ctx_destroy((zi_ctx*)reader->zstd_dctx);
     memset(reader, 0, sizeof(*reader));
 }

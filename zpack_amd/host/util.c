@@ -60,12 +60,14 @@ zi_ctx* zi_ctx_create(void)
         }
     }
     if (x->n == 0) { free(x); return NULL; }
+    x->ra = zi_ra_create();                                      /* ZPACK_AMD_READ_AHEAD: bytes of output per window, 0 = off */
     return x;
 }
 
 void zi_ctx_destroy(zi_ctx* x)
 {
     if (!x) return;
+    zi_ra_destroy(x->ra);
     for (int i = 0; i < x->n; i++) zpk_codec_destroy(x->dev[i]);
     free(x);
 }
