@@ -1,11 +1,8 @@
-#include <stdint.h>
-#include <string.h>
+// zpack_amd/csrc/host_walk.h, the header the codec compiles, on mutated frames under ASan + UBSan: built and run by tools/hostfuzz/run.sh
 #include <stdio.h>
 #include <stdlib.h>
-#include <vector>
-typedef uint8_t u8; typedef uint32_t u32; typedef uint64_t u64; typedef int64_t i64;
-/*@TYPES@*/
-/*@WALKERS@*/
+#include "host_walk.h"
+using namespace zpk;
 
 static u64 rng_s = 88172645463325252ull;
 static u64 rnd() { rng_s ^= rng_s << 13; rng_s ^= rng_s >> 7; rng_s ^= rng_s << 17; return rng_s; }
@@ -134,7 +131,53 @@ int main(int argc, char** argv) {
         }
         free(p);
     }
+    // ---- the LZ4 stream step's parsers: the shared frame header and the scan for complete blocks, on mutated single frames cut off at several
+    // lengths (bytes as they arrive); every block reported must lie inside the bytes that were given
+    u64 hdr_ok = 0, blocks_seen = 0, ends = 0;
+    for (u64 it = 0; it < iters; it++) {
+        std::vector<u8> e;
+        u8 h[15] = {0x04,0x22,0x4D,0x18, (u8)(0x40 | ((rnd() & 1) ? 0x20 : 0) | ((rnd() & 1) ? 0x08 : 0)), 0x40};
+        const u32 hl = (h[4] & 0x08) ? 15 : 7;
+        for (u32 i = 6; i + 1 < hl; i++) h[i] = (u8)rnd();
+        h[hl - 1] = (u8)(host_xxh32_small(h + 4, hl - 5) >> 8);
+        e.insert(e.end(), h, h + hl);
+        const int nb = 1 + rnd() % 70;                        // (more than the 64 blocks of a step, now and then)
+        for (int b = 0; b < nb; b++) { u32 n = rnd() % 120; u32 w = n | ((rnd() & 3) == 0 ? 0x80000000u : 0); u8 t[4]; memcpy(t, &w, 4); e.insert(e.end(), t, t + 4); for (u32 i = 0; i < n; i++) e.push_back((u8)rnd()); }
+        u8 z[4] = {0,0,0,0}; e.insert(e.end(), z, z + 4);
+        const int muts = rnd() % 4;
+        for (int m = 0; m < muts; m++) { const int kind = rnd() % 4; if (e.empty()) break;
+            if (kind == 0) e[rnd() % e.size()] ^= (u8)(1u << (rnd() % 8));
+            else if (kind == 1) e[rnd() % e.size()] = (u8)rnd();
+            else if (kind == 2) e.resize(rnd() % (e.size() + 1));
+            else { const size_t n = rnd() % 40; for (size_t i = 0; i < n; i++) e.push_back((u8)rnd()); } }
+        for (int cut = 0; cut < 4; cut++) {
+            const u64 len = cut == 0 ? e.size() : cut == 1 ? rnd() % 20 : rnd() % (e.size() + 1);
+            u8* p = (u8*)malloc(len ? len : 1); memcpy(p, e.data(), len);      // exact-size heap copy of what has "arrived"
+            int indep = -1, has_cs = -1; u64 content = 0;
+            const int hdr = lz4_single_header(p, len, &indep, &has_cs, &content);
+            if (hdr > 0) {
+                hdr_ok++;
+                if ((hdr != 7 && hdr != 15) || (u64)hdr > len || (indep | 1) != 1 || has_cs != (hdr == 15)) { printf("lz4 header: inconsistent answer\n"); return 1; }
+                const u64 avail = len - (u64)hdr; const u32 maxb = 1 + rnd() % 64;
+                u8* r = (u8*)malloc(avail ? avail : 1); memcpy(r, p + hdr, avail);                  // (the stream step drops the header from its pending bytes)
+                PjBlock* tab = (PjBlock*)malloc(maxb * sizeof(PjBlock));                            // exactly max_blocks entries: ASan sees one too many
+                u64 used = 0; bool end = false;
+                const int n = lz4_stream_blocks(r, avail, tab, maxb, &used, &end);
+                if (n >= 0) {
+                    if ((u32)n > maxb || used > avail) { printf("lz4 stream scan: more blocks or bytes than it was given\n"); return 1; }
+                    u64 at = 0;
+                    for (int b = 0; b < n; b++) { const u32 sz = tab[b].comp_size & 0x7FFFFFFFu; if (tab[b].comp_off != at + 4 || sz > PJ_BLOCK || (u64)tab[b].comp_off + sz > avail) { printf("lz4 stream scan: block outside its bytes\n"); return 1; } at = (u64)tab[b].comp_off + sz; }
+                    if (at + (end ? 4 : 0) != used) { printf("lz4 stream scan: consumed bytes disagree with the blocks\n"); return 1; }
+                    blocks_seen += (u64)n; ends += end ? 1 : 0;
+                }
+                free(tab); free(r);
+            } else if (hdr != 0 && hdr != -1) { printf("lz4 header: unknown answer\n"); return 1; }
+            free(p);
+        }
+    }
     printf("%llu mutated single frames walked: %llu LZ4 / %llu Zstandard accepted for the block-parallel readers, every accepted block inside its entry\n", (unsigned long long)iters, (unsigned long long)acc1, (unsigned long long)acc2);
     printf("%llu mutated entries walked, %llu accepted as frame sequences (every accepted plan tiles its entry exactly), %llu intact seeds accepted\n", (unsigned long long)iters, (unsigned long long)accepted, (unsigned long long)intact_ok);
+    printf("%llu mutated LZ4 frames at 4 lengths each through the stream step's header and block scan: %llu headers taken, %llu blocks and %llu EndMarks found, every block inside the bytes given, consumed <= available\n",
+           (unsigned long long)iters, (unsigned long long)hdr_ok, (unsigned long long)blocks_seen, (unsigned long long)ends);
     return 0;
 }

@@ -22,12 +22,11 @@
 // entry is decoded from scratch by the one-wave decoder, which alone gives verdicts.
 #pragma once
 #include "lz4_wave.h"
+#include "pj_types.h"                        // PJ_BLOCK, struct PjBlock
 
 namespace zpk {
 
-#define PJ_BLOCK 65536u                          // LZ4F block size of the frames this path takes (BD = 0x40: what the reference writes)
 #define PJ_LIT 0x80000000u                       // reference: a literal — low 31 bits = byte offset in the compressed entry
-struct PjBlock { u32 comp_off, comp_size /* bit 31: stored */, rec_base, out_size, out_off, nrec; };
 enum { PJ_ERR = 0, PJ_CHANGED = 1, PJ_TOTAL = 2 };      // words of the flags array (PJ_TOTAL: two words)
 
 // record of one sequence: output position in the block | literal length << 16 | literal position in the block << 32 | offset << 48

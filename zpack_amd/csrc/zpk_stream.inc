@@ -291,33 +291,19 @@ static int dstream_fast_lz4(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, ui
     const u8* const P = s->f_pend;
     // ---- the frame header, once ----
     if (!s->f_hdr) {
-        if (s->f_pend_len < 7) return all_in ? ZPK_DS_RESTART : 0;
-        if (hrd32(P) != 0x184D2204u) return ZPK_DS_RESTART;
-        const u32 flg = P[4], bd = P[5];
-        if ((flg >> 6) != 1 || (flg & 0x17) || bd != 0x40) return ZPK_DS_RESTART;      // version; reserved, block / content checksum, dictionary; 64 KiB blocks
-        const u32 hdr = 7 + ((flg & 8) ? 8u : 0u);
-        if (s->f_pend_len < hdr) return all_in ? ZPK_DS_RESTART : 0;
-        if (((host_xxh32_small(P + 4, hdr - 5) >> 8) & 0xFF) != P[hdr - 1]) return ZPK_DS_RESTART;
-        s->f_indep = (flg >> 5) & 1; s->f_has_cs = (flg >> 3) & 1; s->f_content = 0;
-        if (s->f_has_cs) for (int i = 0; i < 8; i++) s->f_content |= (u64)P[6 + i] << (8 * i);
-        s->f_hdr = (int)hdr;
-        memmove(s->f_pend, s->f_pend + hdr, s->f_pend_len - hdr);
-        s->f_pend_len -= hdr;
+        const int hdr = lz4_single_header(P, s->f_pend_len, &s->f_indep, &s->f_has_cs, &s->f_content);
+        if (hdr < 0 || (hdr == 0 && all_in)) return ZPK_DS_RESTART;
+        if (hdr == 0) return 0;
+        s->f_hdr = hdr;
+        memmove(s->f_pend, s->f_pend + hdr, s->f_pend_len - (u64)hdr);
+        s->f_pend_len -= (u64)hdr;
     }
     // ---- the complete blocks among the pending bytes ----
     PjBlock tab[F_BLOCKS];
-    u32 nb = 0; u64 q = 0, recs = 0; bool end = false;
-    while (nb < F_BLOCKS) {
-        if (s->f_pend_len - q < 4) break;
-        const u32 w = hrd32(P + q);
-        if (w == 0) { end = true; q += 4; break; }
-        const u32 n = w & 0x7FFFFFFFu;
-        if (n > PJ_BLOCK) return ZPK_DS_RESTART;
-        if (s->f_pend_len - q - 4 < n) break;
-        PjBlock& B = tab[nb]; B.comp_off = (u32)(q + 4); B.comp_size = w; B.rec_base = (u32)recs; B.out_size = 0; B.out_off = 0; B.nrec = 0;
-        if (!(w >> 31)) recs += n / 3 + 2;
-        nb++; q += 4 + n;
-    }
+    u64 q = 0; bool end = false;
+    const int found = lz4_stream_blocks(P, s->f_pend_len, tab, F_BLOCKS, &q, &end);
+    if (found < 0) return ZPK_DS_RESTART;
+    const u32 nb = (u32)found;
     if (end && !(all_in && q == s->f_pend_len)) return ZPK_DS_RESTART;                   // something follows the EndMark: not one frame
     const bool go = end || nb == F_BLOCKS || (s->f_T == 0 && nb >= 4);
     if (!go) {
@@ -485,12 +471,8 @@ static int dstream_fast_zstd(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, u
             const int pr = zpj_parse_block(P + q, s->f_pend_len - q, in_base + q, B, &last, &total, &tabs);
             if (pr < 0) return ZPK_DS_RESTART;
             if (pr == 0) break;
-            if (B.type == 2) {
-                if (B.lit_type == 2) { tree = tb + nb; new_tree = nb; }
-                if (B.lit_type == 3) { if (tree == ZPJ_NONE) return ZPK_DS_RESTART; B.tree_src = tree; }
-                if (B.lit_type >= 2) { B.lit_base = (u32)lit_total; lit_total += ((u64)B.lit_size + 15) / 16 * 16 + 64; }
-                B.seq_base = (u32)slots; slots += (u64)B.nseq + 1;
-            }
+            if (B.type == 2 && B.lit_type == 2) new_tree = nb;
+            if (!zpj_place_block(B, tb + nb, tree, slots, lit_total)) return ZPK_DS_RESTART;
             tab.push_back(B);
             nb++; q += total;
             if (last) end = true;

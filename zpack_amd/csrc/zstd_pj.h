@@ -25,28 +25,10 @@
 #pragma once
 #include "lz4_pj.h"
 #include "zstd_fse4.h"
+#include "pj_types.h"                        // ZPJ_BLOCK, ZPJ_NONE, ZPJ_TREE_ONLY, struct ZpjBlock
 
 namespace zpk {
 
-#define ZPJ_BLOCK (128u << 10)
-#define ZPJ_NONE 0xFFFFFFFFu
-#define ZPJ_TREE_ONLY 3u                           // ZpjBlock::type of a stream step's first table entry: a block of an earlier step, here only for its Huffman tree
-struct ZpjBlock {
-    u32 hdr_off;             // offset of the 3-byte block header in the compressed entry
-    u32 size;                // Block_Size (Compressed / Raw: bytes of content; RLE: the regenerated size)
-    u32 type;                // 0 Raw, 1 RLE, 2 Compressed
-    u32 lit_type;            // Compressed: 0 Raw, 1 RLE, 2 Compressed, 3 Treeless
-    u32 lit_size;            // ... regenerated literal bytes
-    u32 lit_used;            // ... bytes of the block the literals section takes
-    u32 lit_ref;             // ... reference of literal byte 0: offset in [compressed entry | literal arena]; RLE literals: the byte's offset
-    u32 lit_base;            // ... decoded literals: their offset in the literal arena
-    u32 tree_src;            // ... Treeless: the block whose tree description it uses
-    u32 nseq;                // ... sequences
-    u32 seq_base;            // ... index of its first sequence record (a block owns nseq + 1 slots: the last one stands for the trailing literals)
-    u32 rep_in[3];           // device (k_zpj_reps): repeat offsets at the block's start
-    u32 tab_off[3];          // ... a Repeat_Mode table (LL, OF, ML): where the table it inherits is described (offset in the compressed entry)
-    u32 tab_modes;           // ... and how: 2 bits per kind (0 predefined, 1 RLE, 2 FSE description, 3 nowhere)
-};
 // words of the flags array this path adds (lz4_pj.h: PJ_ERR, PJ_TOTAL, PJ_ROUND0 ..): the counters k_zstd_fse_blocks works with
 #define ZPJ_CNT 40                                 // flags + ZPJ_CNT = its `counters` (ZF_COUNT_WORD 1, ZF_HEAD 8, ZF_WATCHDOG_WORD 11..13)
 
