@@ -39,7 +39,8 @@ extern "C" {
 #endif
 
 #define ZPK_CODEC_ABI_VERSION 3      /* 3: the two-stage LZ4 path of version 2 is gone (options 2..5 are ZPK_E_INVALID again, decode_stats2 out[2] = out[4] = 0,
-                                        out[3] = LZ4 entries that are mostly runs, decoded by k_lz4_left); 2: set_option has options again */
+                                        out[3] = LZ4 entries that are mostly runs, decoded by k_lz4_left); 2: set_option has options again.
+                                        (Additive since 3, no renumbering: decode_stats2 out[8], out[9], which read 0: LZ4 entries the lean kernel handed to the general decoder / not plain frames.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -191,14 +192,17 @@ int zpk_codec_hash_host(zpk_codec* c, const uint8_t* data, uint64_t size, uint64
 /* per-kernel timing of decode batches: when enabled, every decode batch brackets each of its kernels
  * with HIP events on the launch stream; zpk_codec_kernel_ms then returns the duration of kernel
  * `which` (ZPK_K_*) in the most recent batch (synchronises on that batch). */
-enum { ZPK_K_CLASSIFY = 0, ZPK_K_STORED = 1, ZPK_K_LZ4 = 2 /* k_lz4_wave + k_lz4_left + k_lz4_retry */, ZPK_K_ZSTD = 3 /* k_zstd_exec + k_zstd */, ZPK_K_ZSTD_FSE = 4,
+enum { ZPK_K_CLASSIFY = 0, ZPK_K_STORED = 1, ZPK_K_LZ4 = 2 /* k_lz4_wave (plain frames) + k_lz4_left + k_lz4_general + k_lz4_retry */, ZPK_K_ZSTD = 3 /* k_zstd_exec + k_zstd */, ZPK_K_ZSTD_FSE = 4,
        ZPK_K_PACK = 5, ZPK_K_RESERVED6 = 6 /* (was k_lz4_parse) */, ZPK_K_ENCODE = 7, ZPK_K_COUNT = 8 };
 int zpk_codec_set_profiling(zpk_codec* c, int enabled);
 /* out[0], out[1] = LZ4 / Zstandard entries of the most recent decode batch whose first decode ran out of its time budget (a
  * contended or preempted GPU) and that were decoded again, behind the batch, with a 64 x larger one — a slow wave is not a
  * verdict; expected 0 on an idle GPU.  out[3] = LZ4 entries that are mostly runs (compressed to less than 1/8: the classification puts
  * them on the list of k_lz4_left, the build of the one-wave decoder with grouped cooperative copies); out[2] = out[4] = 0; out[5], out[6] = entries of the most recent
- * zpk_codec_decode_batch_host call that were decoded frame-parallel (ZPK_OPT_DEC_SPLIT_MIN) and the frames they had */
+ * zpk_codec_decode_batch_host call that were decoded frame-parallel (ZPK_OPT_DEC_SPLIT_MIN) and the frames they had;
+ * out[8] = LZ4 entries with the header of a plain frame (one frame, no checksums, no dictionary id) that k_lz4_wave, the kernel for such
+ * frames, did not finish cleanly and handed unjudged to the general decoder behind it (damaged, truncated, trailing bytes ...; not part
+ * of out[0]); out[9] = LZ4 entries whose header is not that of a plain frame: the classification sends them to k_lz4_general */
 int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16]);
 /* counters of the most recent decode batch (synchronises): out[0..2] = entries on the stored / zstd / lz4 work
  * lists, out[3] = Zstandard entries finished on pre-decoded sequences (two-stage path), out[4] = by the fused decoder,

@@ -511,4 +511,59 @@ __device__ inline DecodeOut lz4f_decode_wave(Lz4WaveShared& sh, Watchdog& wd, Se
     return r;
 }
 
+// ONE PLAIN FRAME, the hot kernel's walker.  Plain = what the reference writer and this library write: version 01, no block
+// checksum, no content checksum, no dictionary id, no reserved bits, block code >= 4 (content size and linked blocks are allowed),
+// followed by nothing.  true = the end mark was reached with all input consumed and exactly `want` bytes produced.  false = NO
+// VERDICT: the frame is not plain, or the decode ended in any other way (malformed, truncated, output full, trailing bytes or a
+// second frame, time budget) — the caller hands the entry to the general decoder (lz4f_decode_wave), which decodes it from scratch,
+// so every status other than OK / hash mismatch is produced by that code alone.  Nothing is written outside [dst, dst + dst_cap).
+// The point of this walker is what it does NOT carry: the general one keeps the multi-frame loop, the resume state and the checksum
+// flags live across every block decode, and the block decoder has no scalar registers to spare.
+template <int COOP = 0>
+__device__ inline bool lz4f_plain_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& stt, const u8* src, u64 src_size, const u8* src_hi,
+                                       u8* dst, u64 dst_cap, u64 want, int lane)
+{
+    if (src_size < 11) return false;                                   // header + end mark
+    if (uld32(src) != 0x184D2204u) return false;
+    const u32 flg = uld8(src + 4), bd = uld8(src + 5);
+    if ((flg & 0xD7u) != 0x40u || (bd & 0x8Fu) || ((bd >> 4) & 7u) < 4u) return false;
+    const u32 hdr = (flg & 8u) ? 15u : 7u;                             // with or without the content size
+    if (src_size < hdr + 4u) return false;
+    if ((flg & 8u) && uni64(ld64(src + 6)) != want) return false;
+    {
+        u32 h = 0;
+        lane0_guard();
+        if (lane == 0) h = (xxh32_serial(src + 4, hdr - 5, 0) >> 8) & 0xFF;
+        if (uni(h) != uld8(src + hdr - 1)) return false;
+    }
+    const u64 bmax = (u64)1 << (8 + 2 * ((bd >> 4) & 7u));            // 4:64K 5:256K 6:1M 7:4M
+    const bool indep = (flg >> 5) & 1;
+    const u8* ip = src + hdr;
+    const u8* const iend = src + src_size;
+    u8* op = dst;
+    u8* const oend = dst + dst_cap;
+    for (;;) {
+        if (wd.expired() || iend - ip < 4) return false;
+        const u32 bh = uld32(ip);
+        ip += 4;
+        if (bh == 0) break;
+        const u32 bsz = bh & 0x7FFFFFFFu;
+        if (bsz > bmax || (u64)(iend - ip) < bsz) return false;
+        if (bh >> 31) {                                                // stored block: a wave-wide copy, as in the general walker
+            if (bsz > (u64)(oend - op)) return false;
+            for (u32 i = (u32)lane * 16; i < bsz; i += WAVE * 16) gcopy_upto16(op + i, ip + i, bsz - i < 16 ? bsz - i : 16);
+            op += bsz;
+        } else {
+            u8* hist_lo = indep ? op : dst;
+            if ((u64)(op - hist_lo) > 65536) hist_lo = op - 65536;
+            u8* bend = oend;
+            if ((u64)(oend - op) > bmax) bend = op + bmax;
+            if (lz4_block_wave<COOP>(sh, wd, stt, ip, bsz, src_hi, hist_lo, op, bend, lane) != D_OK) return false;
+        }
+        wave_mem_fence();
+        ip += bsz;
+    }
+    return ip == iend && (u64)(op - dst) == want;
+}
+
 }  // namespace zpk

@@ -41,17 +41,27 @@
 using namespace zpk;
 
 // counters layout (u32): [0..3] count per work list, [4..7] dequeue head per list
-enum { L_NONE = 0, L_ZSTD = 1, L_LZ4 = 2, L_COUNT = 4, N_LISTS = 3, L_LZ4_RUNS = 100 /* k_classify only: the LZ4 entries k_lz4_left takes (its list is slot N_LISTS + 2) */ };
+enum { L_NONE = 0, L_ZSTD = 1, L_LZ4 = 2, L_COUNT = 4, N_LISTS = 3, L_LZ4_RUNS = 100 /* k_classify only: the LZ4 entries k_lz4_left takes (its list is slot N_LISTS + 2) */,
+       L_LZ4_GEN = 101 /* k_classify only: LZ4 entries whose frame header is not a plain one (k_lz4_general's: list slot S_LZ4_GEN, length in counters[C_LZ4_GEN]) */ };
 // [8] dequeue head of k_zstd_fse, [9] Zstandard entries finished on pre-decoded sequences, [10] finished by the fused decoder
 enum { C_ZSTD_TWO_STAGE = 9, C_ZSTD_FUSED = 10, C_EXEC_HEAD = 16, C_LEFT_COUNT = 17,
        C_RETRY_LZ4 = 18, C_RETRY_ZSTD = 19,     // entries whose decoder ran out of its time budget: decoded again by the retry launches
        C_RETRY_HEAD = 20,                       // dequeue head of the Zstandard retry launch
        C_LZ4_LEFT = 21, C_LZ4_LEFT_HEAD = 22,   // LZ4 entries that are mostly runs (k_classify: compressed to less than 1/8): k_lz4_left's list, its dequeue head
+       C_LZ4_GEN = 3, C_LZ4_GEN_HEAD = 7,       // LZ4 entries whose header is not that of a plain frame (k_classify): k_lz4_general's list, its dequeue head
+       C_LZ4_HANDED_HEAD = 23, C_LZ4_HANDED = 24, // LZ4 entries k_lz4_wave handed over WITHOUT judging them (a plain header, but no clean end): a list of their own
+       C_LZ4_RETRY_HEAD = 25,                   // dequeue head of k_lz4_retry on the LZ4 retry list (time budgets)
        C_ENC_CLASS = 28,                        // (three words) encode batches: does the batch hold entries for k_encode<12> / <13> / <14> at all
        C_ORDER_SPAN = 26,                       // (two words) largest size class and largest 15 - class among the Zstandard / LZ4 entries
-       C_ORDER = 32,                            // k_order_*: [2 lists][16 classes] entry counts, then the same again as fill cursors
-       N_COUNTERS = 32 + 64 };
-enum { N_LISTS_ALLOC = N_LISTS + 5 };           // + the two retry lists + the LZ4 entries of long runs (k_lz4_left) + the two ordered lists
+       C_ORDER = 32,                            // k_order_*: [3 lists][16 classes] entry counts, then the same again as fill cursors
+       N_COUNTERS = 32 + 96 };
+// list storage behind the three method lists: the two retry lists, the LZ4 entries of long runs (k_lz4_left), the ordered Zstandard / LZ4 lists,
+// the LZ4 hand-overs, the LZ4 entries that are not plain frames and their ordered copy
+enum { S_LZ4_HANDED = N_LISTS + 5, S_LZ4_GEN = N_LISTS + 6, S_LZ4_GEN_ORDERED = N_LISTS + 7, N_LISTS_ALLOC = N_LISTS + 8 };
+#define N_ORDERED 3                              // k_order_*: grid.y = 0 Zstandard, 1 LZ4 (plain), 2 LZ4 (general)
+__device__ __forceinline__ int order_list_slot(int y) { return y == 0 ? (int)L_ZSTD : y == 1 ? (int)L_LZ4 : (int)S_LZ4_GEN; }
+__device__ __forceinline__ int order_count_word(int y) { return y == 0 ? (int)L_ZSTD : y == 1 ? (int)L_LZ4 : (int)C_LZ4_GEN; }
+__device__ __forceinline__ int order_out_slot(int y) { return y == 2 ? (int)S_LZ4_GEN_ORDERED : (int)N_LISTS + 3 + y; }
 
 // ------------------------------------------------------------------------------------ kernels
 
@@ -67,7 +77,15 @@ __device__ __forceinline__ int order_class(u64 size)
 // compressed — go LAST: they are what is left to fill the final round with (C2: +0.75 % over six A/B pairs; on the ragged c4_mixed the
 // same key inside every size class measured -4 % +- noise, so it is not used there).
 __device__ __forceinline__ int order_fast(u64 size, u64 comp) { return comp * 16 >= size * 15 ? 1 : 0; }
-__global__ __launch_bounds__(256) void k_classify(const zpk_decode_desc* __restrict__ desc, u64 n, u64 src_size, u64 dst_size,
+// Does the LZ4 entry begin like a PLAIN frame (what lz4f_plain_wave takes: version 01, no block / content checksum, no dictionary id, no
+// reserved bits, block code >= 4)?  Only the 6 bytes in front of the header checksum are looked at; everything else is the decoder's.
+__device__ __forceinline__ bool lz4_header_is_plain(const u8* __restrict__ p, u64 comp_size)
+{
+    if (comp_size < 11) return false;
+    const u32 magic = (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24), flg = p[4], bd = p[5];
+    return magic == 0x184D2204u && (flg & 0xD7u) == 0x40u && (bd & 0x8Fu) == 0 && ((bd >> 4) & 7u) >= 4u;
+}
+__global__ __launch_bounds__(256) void k_classify(const u8* __restrict__ src, const zpk_decode_desc* __restrict__ desc, u64 n, u64 src_size, u64 dst_size,
                                                   zpk_decode_result* __restrict__ res, u32* __restrict__ lists, u64 list_stride,
                                                   u32* __restrict__ counters)
 {
@@ -89,7 +107,8 @@ __global__ __launch_bounds__(256) void k_classify(const zpk_decode_desc* __restr
         else list = L_NONE;
     }
     else if (d.method == ZPK_METHOD_ZSTD) list = L_ZSTD;
-    else if (d.method == ZPK_METHOD_LZ4) list = d.comp_size < (d.uncomp_size >> 3) ? L_LZ4_RUNS : L_LZ4;      // mostly runs: k_lz4_left's
+    else if (d.method == ZPK_METHOD_LZ4)                                       // mostly runs: k_lz4_left's; not a plain frame: k_lz4_general's
+        list = d.comp_size < (d.uncomp_size >> 3) ? L_LZ4_RUNS : lz4_header_is_plain(src + d.src_offset, d.comp_size) ? L_LZ4 : L_LZ4_GEN;
     else r.status = R_COMP_METHOD_INVALID;                                     // :459
     // an entry that goes on a work list is not decoded yet: until its decoder writes the verdict the slot says so
     // (a decoder that never ran must not read as R_OK)
@@ -98,7 +117,7 @@ __global__ __launch_bounds__(256) void k_classify(const zpk_decode_desc* __restr
     // wave-aggregated append: one atomic per list per wave (a per-lane atomicAdd on three hot words cost 1.1 ms / 100k entries)
     const int lane = lane_id();
     {   // the span of size classes among the entries that go to a decoder (k_order_*)
-        const bool dec = list == L_ZSTD || list == L_LZ4;
+        const bool dec = list == L_ZSTD || list == L_LZ4 || list == L_LZ4_GEN;
         u32 hi = dec ? (u32)order_class(d.uncomp_size) + 1u : 0u, inv = dec ? (u32)(ORD_CLASSES - order_class(d.uncomp_size)) : 0u;   // (+1: 0 = none)
         #pragma unroll
         for (int m = 1; m < 64; m <<= 1) { const u32 a = (u32)__shfl_xor((int)hi, m, 64), b2 = (u32)__shfl_xor((int)inv, m, 64); hi = a > hi ? a : hi; inv = b2 > inv ? b2 : inv; }
@@ -122,6 +141,16 @@ __global__ __launch_bounds__(256) void k_classify(const zpk_decode_desc* __restr
             if (lane == leader) base = atomicAdd(&counters[C_LZ4_LEFT], (u32)__popcll(m));
             base = (u32)__shfl((int)base, leader, 64);
             if (list == L_LZ4_RUNS) lists[(u64)(N_LISTS + 2) * list_stride + base + (u32)__popcll(m & ((1ull << lane) - 1))] = (u32)i;
+        }
+    }
+    {   // k_lz4_general's list
+        const u64 m = __ballot(list == L_LZ4_GEN);
+        if (m != 0) {
+            const int leader = __ffsll((long long)m) - 1;
+            u32 base = 0;
+            if (lane == leader) base = atomicAdd(&counters[C_LZ4_GEN], (u32)__popcll(m));
+            base = (u32)__shfl((int)base, leader, 64);
+            if (list == L_LZ4_GEN) lists[(u64)S_LZ4_GEN * list_stride + base + (u32)__popcll(m & ((1ull << lane) - 1))] = (u32)i;
         }
     }
 }
@@ -151,8 +180,8 @@ __global__ __launch_bounds__(256) void k_order_count(const zpk_decode_desc* __re
                                                      u32* __restrict__ counters, int fast_last)
 {
     __shared__ u32 h[ORD_CLASSES];
-    const int L = blockIdx.y == 0 ? L_ZSTD : L_LZ4;
-    const u32 cnt = counters[L];
+    const int L = order_list_slot(blockIdx.y);
+    const u32 cnt = counters[order_count_word(blockIdx.y)];
     const bool uniform = order_single_class(counters);
     if ((u64)blockIdx.x * 256 >= cnt || (uniform && !fast_last)) return;
     if (threadIdx.x < ORD_CLASSES) h[threadIdx.x] = 0;
@@ -168,15 +197,16 @@ __global__ __launch_bounds__(256) void k_order_count(const zpk_decode_desc* __re
     if (threadIdx.x < ORD_CLASSES && h[threadIdx.x]) atomicAdd(&counters[C_ORDER + blockIdx.y * ORD_CLASSES + threadIdx.x], h[threadIdx.x]);
 }
 __global__ __launch_bounds__(256) void k_order_fill(const zpk_decode_desc* __restrict__ desc, const u32* __restrict__ lists, u64 list_stride,
-                                                    u32* __restrict__ ordered /* two lists of list_stride */, u32* __restrict__ counters, int fast_last)
+                                                    u32* __restrict__ all_lists /* the ordered copies: order_out_slot() */, u32* __restrict__ counters, int fast_last)
 {
     __shared__ u32 wcount[4][ORD_CLASSES], base[ORD_CLASSES];
-    const int L = blockIdx.y == 0 ? L_ZSTD : L_LZ4;
-    const u32 cnt = counters[L];
+    const int L = order_list_slot(blockIdx.y);
+    const u32 cnt = counters[order_count_word(blockIdx.y)];
+    u32* const ordered = all_lists + (u64)order_out_slot(blockIdx.y) * list_stride;
     if ((u64)blockIdx.x * 256 >= cnt) return;
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     const bool uniform = order_single_class(counters);
-    if (uniform && !fast_last) { if (k < cnt) ordered[(u64)blockIdx.y * list_stride + k] = lists[(u64)L * list_stride + k]; return; }
+    if (uniform && !fast_last) { if (k < cnt) ordered[k] = lists[(u64)L * list_stride + k]; return; }
     if (threadIdx.x < 4 * ORD_CLASSES) (&wcount[0][0])[threadIdx.x] = 0;
     __syncthreads();
     const int lane = lane_id(), w = threadIdx.x >> 6;
@@ -192,13 +222,13 @@ __global__ __launch_bounds__(256) void k_order_fill(const zpk_decode_desc* __res
         const u32* const hist = counters + C_ORDER + blockIdx.y * ORD_CLASSES;
         u32 before = 0;
         for (int j = 0; j < c; j++) before += hist[j];
-        base[c] = total ? before + atomicAdd(&counters[C_ORDER + 2 * ORD_CLASSES + blockIdx.y * ORD_CLASSES + c], total) : 0;
+        base[c] = total ? before + atomicAdd(&counters[C_ORDER + N_ORDERED * ORD_CLASSES + blockIdx.y * ORD_CLASSES + c], total) : 0;
     }
     __syncthreads();
     if (b >= 0) {
         u32 at = base[b] + rank;
         for (int j = 0; j < w; j++) at += wcount[j][b];
-        ordered[(u64)blockIdx.y * list_stride + at] = e;
+        ordered[at] = e;
     }
 }
 
@@ -277,9 +307,29 @@ __global__ __launch_bounds__(256) void k_stored(const u8* __restrict__ src, cons
     }
 }
 
-// one LZ4 entry, one wave.  retry_list != nullptr: a decode that ran out of its time budget is not reported — the entry goes on that
-// list (counters[C_RETRY_LZ4]) and k_lz4_retry decodes it again behind the batch with ZPK_WATCHDOG_RETRY_SCALE times the budget.
-// COOP: seq_exec.h — 0 in k_lz4_wave (the round-4 code, one cooperative piece at a time), 2 everywhere else (grouped cooperative copies).
+// developer: the per-phase cycle counters of one entry (ZPK_STATS builds; dbg = 8 words per entry)
+__device__ __forceinline__ void lz4_stats_out(u64* __restrict__ dbg, u32 e, const SeqStats& stt, u64 t_all, int lane)
+{
+#ifdef ZPK_STATS
+    if (dbg && lane == 0) {
+        u64* g = dbg + (u64)e * 8;
+        g[0] = stt.t_parse; g[1] = stt.t_lit; g[2] = stt.t_dep; g[3] = stt.t_rounds;
+        g[4] = ((u64)stt.batches << 32) | stt.rounds; g[5] = ((u64)stt.coops << 32) | stt.asm_batches; g[6] = SEQ_T() - t_all;
+        g[7] = ((u64)stt.fix_iters << 32) | stt.chunks;
+#ifdef ZPK_STATS_PARSE
+        g[0] = stt.t_stage; g[1] = stt.t_walk1; g[2] = stt.t_fix; g[3] = stt.t_emit; g[4] = stt.t_tok;
+        g[5] = ((u64)stt.hops_first << 32) | stt.hops_fix; g[6] = stt.slow_hops;
+#endif
+    }
+#else
+    (void)dbg; (void)e; (void)stt; (void)t_all; (void)lane;
+#endif
+}
+
+// one LZ4 entry, one wave, the GENERAL decoder (every frame shape, every verdict).  retry_list != nullptr: a decode that ran out of
+// its time budget is not reported — the entry goes on that list (counters[C_RETRY_LZ4]) and k_lz4_retry decodes it again behind the
+// batch with ZPK_WATCHDOG_RETRY_SCALE times the budget.
+// COOP: seq_exec.h — 0 = the round-4 code, one cooperative piece at a time (k_lz4_wave), 2 = grouped cooperative copies.
 template <int COOP>
 __device__ __forceinline__ void lz4_entry_wave(Lz4WaveShared& shw, const u8* __restrict__ src, const u8* read_lo, const u8* read_hi,
                                                const zpk_decode_desc* __restrict__ desc, u8* dst, zpk_decode_result* __restrict__ res,
@@ -293,20 +343,7 @@ __device__ __forceinline__ void lz4_entry_wave(Lz4WaveShared& shw, const u8* __r
     SeqStats stt = {};
     const u64 t_all = SEQ_T(); (void)t_all;
     DecodeOut o = lz4f_decode_wave<COOP>(shw, wd, stt, in, uni64(d.comp_size), read_lo, read_hi, out, uni64(d.dst_capacity), lane);
-#ifdef ZPK_STATS
-    if (dbg && lane == 0) {
-        u64* g = dbg + (u64)e * 8;
-        g[0] = stt.t_parse; g[1] = stt.t_lit; g[2] = stt.t_dep; g[3] = stt.t_rounds;
-        g[4] = ((u64)stt.batches << 32) | stt.rounds; g[5] = ((u64)stt.coops << 32) | stt.asm_batches; g[6] = SEQ_T() - t_all;
-        g[7] = ((u64)stt.fix_iters << 32) | stt.chunks;
-#ifdef ZPK_STATS_PARSE
-        g[0] = stt.t_stage; g[1] = stt.t_walk1; g[2] = stt.t_fix; g[3] = stt.t_emit; g[4] = stt.t_tok;
-        g[5] = ((u64)stt.hops_first << 32) | stt.hops_fix; g[6] = stt.slow_hops;
-#endif
-    }
-#else
-    (void)dbg; (void)t_all;
-#endif
+    lz4_stats_out(dbg, e, stt, t_all, lane);
     if (wd.fired && retry_list) {                               // slow is not a verdict: again, later, with the large budget
         lane0_guard();
         if (lane == 0) retry_list[atomicAdd(&counters[C_RETRY_LZ4], 1u)] = e;
@@ -320,37 +357,119 @@ __device__ __forceinline__ void lz4_entry_wave(Lz4WaveShared& shw, const u8* __r
     finish_entry(d, res, e, status, wd.fired ? 0xDEADu : (u32)(-o.rc), o.produced, out, lane);
 }
 
-// one wave per slot of the LZ4 work list: the hardware dispatcher is the load balancer
-__global__ __launch_bounds__(64, 8) void k_lz4_wave(const u8* __restrict__ src, const u8* read_lo, const u8* read_hi,
+// one LZ4 entry, one wave, the LEAN decoder of the hot kernel: one plain frame (lz4f_plain_wave) that decodes to exactly uncomp_size
+// bytes is finished here (OK, or FILE_HASH_MISMATCH from the XXH3 pass).  EVERYTHING else — another frame shape, damage of any kind,
+// a spent time budget — is not judged: the entry goes on the hand-over list (a spent budget: on the retry list) and k_lz4_retry decodes it
+// from scratch with the general decoder, so every other verdict is produced by the code that always produced it.
+__device__ __forceinline__ void lz4_entry_plain(Lz4WaveShared& shw, const u8* __restrict__ src, const u8* read_hi,
+                                                const zpk_decode_desc* __restrict__ desc, u8* dst, zpk_decode_result* __restrict__ res,
+                                                u32 e, u32* __restrict__ counters, u64* __restrict__ dbg, u32* __restrict__ retry_list,
+                                                u32* __restrict__ handed_list, u32 wd_scale, int lane)
+{
+    const zpk_decode_desc& d = desc[e];
+    const u8* in = uni_ptr(src + d.src_offset);
+    u8* out = uni_ptr(dst + d.dst_offset);
+    Watchdog wd; wd.arm(uni64(d.comp_size) + uni64(d.dst_capacity), wd_scale);
+    SeqStats stt = {};
+    const u64 t_all = SEQ_T(); (void)t_all;
+    const bool done = lz4f_plain_wave<0>(shw, wd, stt, in, uni64(d.comp_size), read_hi, out, uni64(d.dst_capacity), uni64(d.uncomp_size), lane);
+    lz4_stats_out(dbg, e, stt, t_all, lane);
+    if (!done) {
+        lane0_guard();
+        if (lane == 0) {                                        // (slow is a retry, like everywhere; anything else a hand-over)
+            if (wd.fired) retry_list[atomicAdd(&counters[C_RETRY_LZ4], 1u)] = e;
+            else handed_list[atomicAdd(&counters[C_LZ4_HANDED], 1u)] = e;
+        }
+        return;
+    }
+    finish_entry(d, res, e, R_OK, 0u, uni64(d.uncomp_size), out, lane);
+}
+
+// one wave per slot of the LZ4 work list: the hardware dispatcher is the load balancer.  (The developer build keeps the phase
+// counters' buffer and the scale of the time budget as arguments; the product kernel carries neither.)
+__global__ __launch_bounds__(64, 8) void k_lz4_wave(const u8* __restrict__ src, const u8* read_hi,
                                                   const zpk_decode_desc* __restrict__ desc, u8* dst,
                                                   zpk_decode_result* __restrict__ res, const u32* __restrict__ list,
-                                                  u32* __restrict__ counters, u64* __restrict__ dbg, u32* __restrict__ retry_list
+                                                  u32* __restrict__ counters, u32* __restrict__ retry_list, u32* __restrict__ handed_list
 #ifdef ZPK_DEVELOPER
-                                                  , u32 wd_scale
+                                                  , u64* __restrict__ dbg, u32 wd_scale
 #endif
                                                   )
 {
 #ifndef ZPK_DEVELOPER
     const u32 wd_scale = 1u;
+    u64* const dbg = nullptr;
 #endif
     const int lane = lane_id();
     __shared__ Lz4WaveShared shw;
     u32 idx;
     if (my_slot(counters, L_LZ4, idx))
-        lz4_entry_wave<0>(shw, src, read_lo, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, retry_list, wd_scale, lane);
+        lz4_entry_plain(shw, src, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, retry_list, handed_list, wd_scale, lane);
 }
 
-// the entries k_lz4_wave gave up on (normally none): a small grid, ZPK_WATCHDOG_RETRY_SCALE times the budget, and now the verdict counts
-__global__ __launch_bounds__(64, 8) void k_lz4_retry(const u8* __restrict__ src, const u8* read_lo, const u8* read_hi,
-                                                   const zpk_decode_desc* __restrict__ desc, u8* dst,
-                                                   zpk_decode_result* __restrict__ res, const u32* __restrict__ list,
-                                                   u32* __restrict__ counters, u64* __restrict__ dbg)
+#ifdef ZPK_DEVELOPER
+// developer hook (ZPK_LZ4_GENERAL=1), launched INSTEAD of k_lz4_wave: every entry of the LZ4 work list goes to the general decoder
+__global__ __launch_bounds__(256) void k_lz4_hand_all(const u32* __restrict__ list, u32* __restrict__ counters, u32* __restrict__ handed_list)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < counters[L_LZ4]) handed_list[atomicAdd(&counters[C_LZ4_HANDED], 1u)] = list[i];
+}
+#endif
+
+// k_lz4_general: the LZ4 entries whose frame header is not that of a plain frame (k_classify reads magic, FLG and BD: checksums on — what
+// the lz4 command line tool writes —, a dictionary id, a skippable frame in front, anything unknown) by the general decoder, the code
+// k_lz4_wave was before it went lean (COOP = 0, the normal time budget, the retry list behind it), from a list of their own in
+// largest-first order.  A persistent grid as wide as the chip's resident waves with an atomic dequeue, beside k_lz4_wave and k_lz4_left;
+// it leaves at once when the list is empty (archives of the reference writer and of this library: always).
+#define LZ4_GENERAL_GRID_MAX 8192u
+__global__ __launch_bounds__(64, 8) void k_lz4_general(const u8* __restrict__ src, const u8* read_lo, const u8* read_hi,
+                                                     const zpk_decode_desc* __restrict__ desc, u8* dst,
+                                                     zpk_decode_result* __restrict__ res, const u32* __restrict__ list,
+                                                     u32* __restrict__ counters, u64* __restrict__ dbg, u32* __restrict__ retry_list, u32 wd_scale)
 {
     const int lane = lane_id();
     __shared__ Lz4WaveShared shw;
-    const u32 n_slots = uni(counters[C_RETRY_LZ4]);
-    for (u32 idx = uni((u32)blockIdx.x); idx < n_slots; idx += gridDim.x)
-        lz4_entry_wave<2>(shw, src, read_lo, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, nullptr, (u32)ZPK_WATCHDOG_RETRY_SCALE, lane);
+    const u32 n_slots = uni(counters[C_LZ4_GEN]);
+    if (n_slots == 0) return;
+    for (;;) {
+        lane0_guard();
+        u32 v = 0;
+        if (lane == 0) v = atomicAdd(&counters[C_LZ4_GEN_HEAD], 1u);
+        const u32 idx = uni(v);
+        lane0_guard();
+        if (idx >= n_slots) break;
+        lz4_entry_wave<0>(shw, src, read_lo, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, retry_list, wd_scale, lane);
+    }
+}
+
+// The general decoder behind all other LZ4 kernels of the batch, a small grid (what it finds is rare: normally nothing, and then every
+// workgroup leaves at once).  It drains, in this order: what is left of k_lz4_general's list (all of it when that kernel was not
+// launched: see decode_launch), the entries k_lz4_wave handed over without judging them (a plain header, but a decode without a clean
+// end: damaged or truncated frames, output full, trailing bytes), and the entries whose decoder ran out of its time budget.
+// ZPK_WATCHDOG_RETRY_SCALE times the budget, and now the verdict counts.
+__global__ __launch_bounds__(64, 8) void k_lz4_retry(const u8* __restrict__ src, const u8* read_lo, const u8* read_hi,
+                                                   const zpk_decode_desc* __restrict__ desc, u8* dst,
+                                                   zpk_decode_result* __restrict__ res, const u32* __restrict__ lists, u64 list_stride,
+                                                   u32* __restrict__ counters, u64* __restrict__ dbg, int gen_slot)
+{
+    const int lane = lane_id();
+    __shared__ Lz4WaveShared shw;
+    for (int k = 0; k < 3; k++) {
+        const int count_word = k == 0 ? (int)C_LZ4_GEN : k == 1 ? (int)C_LZ4_HANDED : (int)C_RETRY_LZ4;
+        const int head_word = k == 0 ? (int)C_LZ4_GEN_HEAD : k == 1 ? (int)C_LZ4_HANDED_HEAD : (int)C_LZ4_RETRY_HEAD;
+        const u32* const list = lists + (u64)(k == 0 ? gen_slot : k == 1 ? (int)S_LZ4_HANDED : (int)N_LISTS) * list_stride;
+        const u32 n_slots = uni(counters[count_word]);
+        if (n_slots == 0 || uni(counters[head_word]) >= n_slots) continue;          // (empty, or drained by an earlier launch)
+        for (;;) {
+            lane0_guard();
+            u32 v = 0;
+            if (lane == 0) v = atomicAdd(&counters[head_word], 1u);
+            const u32 idx = uni(v);
+            lane0_guard();
+            if (idx >= n_slots) break;
+            lz4_entry_wave<2>(shw, src, read_lo, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, nullptr, (u32)ZPK_WATCHDOG_RETRY_SCALE, lane);
+        }
+    }
 }
 
 // k_lz4_left: the LZ4 entries that are mostly RUNS — k_classify puts an entry compressed to less than an eighth of its size on this
@@ -760,7 +879,7 @@ int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
 // the product launch path reads no environment and can neither drop a kernel nor end the host process.
 #ifdef ZPK_DEVELOPER
 #define ZPK_DEV(x) x
-#define ZPK_WD_ARG , wd_scale
+#define ZPK_WD_ARG , c->d_dbg, wd_scale
 #else
 #define ZPK_DEV(x)
 #define ZPK_WD_ARG
@@ -799,6 +918,7 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     u32* const retry_lz4 = c->d_lists + (u64)N_LISTS * stride;
     u32* const retry_zstd = c->d_lists + (u64)(N_LISTS + 1) * stride;
     u32* const left_lz4 = c->d_lists + (u64)(N_LISTS + 2) * stride;
+    u32* const handed_lz4 = c->d_lists + (u64)S_LZ4_HANDED * stride;
     u32 wd_scale = 1; (void)wd_scale;
     ZPK_DEV(static const int wd_env = getenv("ZPK_WD_SCALE") ? atoi(getenv("ZPK_WD_SCALE")) : 1; wd_scale = (u32)wd_env;)
     int skip = 0; (void)skip;
@@ -821,18 +941,20 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     ZPK_TRACE_STEP("memset");
 #define ZPK_KEV(k, j) do { if (c->profiling) (void)hipEventRecord(c->kev[k][j], st); } while (0)
     ZPK_KEV(ZPK_K_CLASSIFY, 0);
-    hipLaunchKernelGGL(k_classify, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, desc, n, src_size, dst_size, res,
+    hipLaunchKernelGGL(k_classify, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, src, desc, n, src_size, dst_size, res,
                        c->d_lists, stride, c->d_counters);
     // largest entries first (see k_order_count); batches that fit the resident waves in one round have nothing to order
     const u32* zstd_list = c->d_lists + L_ZSTD * stride;
     const u32* lz4_list = c->d_lists + L_LZ4 * stride;
+    int gen_slot = S_LZ4_GEN;                                   // the LZ4 entries that are not plain frames
     if (n >= c->order_min) {
-        u32* const ordered = c->d_lists + (u64)(N_LISTS + 3) * stride;
-        const dim3 og((u32)((n + 255) / 256), 2);
+        const dim3 og((u32)((n + 255) / 256), N_ORDERED);
         hipLaunchKernelGGL(k_order_count, og, dim3(256), 0, st, desc, (const u32*)c->d_lists, stride, c->d_counters, c->order_fast_last);
-        hipLaunchKernelGGL(k_order_fill, og, dim3(256), 0, st, desc, (const u32*)c->d_lists, stride, ordered, c->d_counters, c->order_fast_last);
-        zstd_list = ordered; lz4_list = ordered + stride;
+        hipLaunchKernelGGL(k_order_fill, og, dim3(256), 0, st, desc, (const u32*)c->d_lists, stride, c->d_lists, c->d_counters, c->order_fast_last);
+        zstd_list = c->d_lists + (u64)(N_LISTS + 3) * stride; lz4_list = c->d_lists + (u64)(N_LISTS + 4) * stride;
+        gen_slot = S_LZ4_GEN_ORDERED;
     }
+    const u32* const gen_list = c->d_lists + (u64)gen_slot * stride;
     ZPK_KEV(ZPK_K_CLASSIFY, 1);
     ZPK_TRACE_STEP("k_classify");
     const u32 wgrid = (u32)((n + 3) / 4);          // one wave per list slot
@@ -852,8 +974,8 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     // workgroup per entry, and 100 000 EMPTY workgroups trickling through at low priority beside the pre-decode stage cost it 15 ms
     // (71.9 -> 87.6 ms).  So the codec looks at the work-list counts of the batch BEFORE (copied to pinned memory behind every batch,
     // no synchronisation): both methods there, or nothing known yet -> side stream; a codec fed batches of one method stays on one stream.
-    if (!c->h_seen && hipHostMalloc((void**)&c->h_seen, 64, hipHostMallocDefault) == hipSuccess) { c->h_seen[L_NONE] = 0; c->h_seen[L_ZSTD] = 1; c->h_seen[L_LZ4] = 1; c->h_seen[8] = 1; }
-    const bool both_seen = c->zstd_hint >= 0 /* the host path knows */ || (c->h_seen && c->h_seen[L_ZSTD] != 0 && c->h_seen[L_LZ4] != 0);
+    if (!c->h_seen && hipHostMalloc((void**)&c->h_seen, 64, hipHostMallocDefault) == hipSuccess) { c->h_seen[L_NONE] = 0; c->h_seen[L_ZSTD] = 1; c->h_seen[L_LZ4] = 1; c->h_seen[8] = 1; c->h_seen[C_LZ4_GEN] = 1; }
+    const bool both_seen = c->zstd_hint >= 0 /* the host path knows */ || (c->h_seen && c->h_seen[L_ZSTD] != 0 && (c->h_seen[L_LZ4] != 0 || c->h_seen[C_LZ4_GEN] != 0));
     if (maybe_lz4 && maybe_zstd && both_seen && !(skip & 6)) {
         int lo_prio = 0, hi_prio = 0;
         if (!c->s_side) { (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
@@ -882,14 +1004,29 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
             }
             hipLaunchKernelGGL(k_lz4_left, dim3((u32)(n < LZ4_LEFT_GRID_MAX ? n : LZ4_LEFT_GRID_MAX)), dim3(64), 0, sx, src, read_lo, read_hi, desc, dst, res,
                                (const u32*)left_lz4, c->d_counters, c->d_dbg, retry_lz4, wd_scale);
-            hipLaunchKernelGGL(k_lz4_wave, dim3((u32)n), dim3(64), 0, sl, src, read_lo, read_hi, desc, dst, res,
-                               lz4_list, c->d_counters, c->d_dbg, retry_lz4 ZPK_WD_ARG);
+            // the hot kernel: plain frames only; whatever it does not finish cleanly is on its hand-over list
+            bool lean = true;
+#ifdef ZPK_DEVELOPER
+            static const int all_general = getenv("ZPK_LZ4_GENERAL") ? atoi(getenv("ZPK_LZ4_GENERAL")) : 0;      // the general decoder alone (tests compare the two)
+            lean = !all_general;
+            if (!lean) hipLaunchKernelGGL(k_lz4_hand_all, dim3((u32)((n + 255) / 256)), dim3(256), 0, sl, lz4_list, c->d_counters, handed_lz4);
+#endif
+            if (lean) hipLaunchKernelGGL(k_lz4_wave, dim3((u32)n), dim3(64), 0, sl, src, read_hi, desc, dst, res,
+                                         lz4_list, c->d_counters, retry_lz4, handed_lz4 ZPK_WD_ARG);
+            // The entries that are not plain frames (k_classify's third LZ4 list): the general decoder at full width beside the two kernels
+            // above — when the batch BEFORE had such entries, or nothing is known yet.  Otherwise the list is expected to be empty and
+            // is left to k_lz4_retry below, so that archives of plain frames pay for no launch they do not need (a batch that does have
+            // some then runs them on the small grid, once).
+            if (!c->h_seen || c->h_seen[C_LZ4_GEN] != 0)               // (the host-pointer paths do not bring the counts home: always launched there)
+                hipLaunchKernelGGL(k_lz4_general, dim3((u32)(n < LZ4_GENERAL_GRID_MAX ? n : LZ4_GENERAL_GRID_MAX)), dim3(64), 0, sl, src, read_lo, read_hi,
+                                   desc, dst, res, gen_list, c->d_counters, c->d_dbg, retry_lz4, wd_scale);
             if (sx != sl && (hipEventRecord(c->ev_ljoin, sx) != hipSuccess || hipStreamWaitEvent(sl, c->ev_ljoin, 0) != hipSuccess))
                 (void)hipStreamSynchronize(sx);
-            // entries whose decoder ran out of its time budget: again, with ZPK_WATCHDOG_RETRY_SCALE times the budget (a small grid
-            // that leaves at once when the list is empty — the normal case)
+            // whatever is left: k_lz4_general's list if that was not launched, what k_lz4_wave handed over, and the entries whose decoder
+            // ran out of its time budget (ZPK_WATCHDOG_RETRY_SCALE times the budget; a small grid that leaves at once when the lists
+            // are empty — the normal case)
             hipLaunchKernelGGL(k_lz4_retry, dim3((u32)(n < 256 ? n : 256)), dim3(64), 0, sl, src, read_lo, read_hi, desc, dst, res,
-                               (const u32*)retry_lz4, c->d_counters, c->d_dbg);
+                               (const u32*)c->d_lists, stride, c->d_counters, c->d_dbg, gen_slot);
         }
         if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_LZ4][1], sl);
     };
@@ -942,7 +1079,7 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
         }
     }
     ZPK_TRACE_STEP("retry");
-    if (c->h_seen && c->zstd_hint < 0) (void)hipMemcpyAsync((void*)c->h_seen, c->d_counters, N_LISTS * sizeof(u32), hipMemcpyDeviceToHost, st);
+    if (c->h_seen && c->zstd_hint < 0) (void)hipMemcpyAsync((void*)c->h_seen, c->d_counters, (N_LISTS + 1) * sizeof(u32), hipMemcpyDeviceToHost, st);      // (+ 1: C_LZ4_GEN, the LZ4 entries that are not plain frames)
     if (c->h_seen) (void)hipMemcpyAsync((void*)(c->h_seen + 8), c->d_counters + C_LZ4_LEFT, sizeof(u32), hipMemcpyDeviceToHost, st);      // did this batch have LZ4 entries of runs?
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
@@ -1932,7 +2069,7 @@ int zpk_codec_decode_stats(zpk_codec* c, uint32_t out[8])
     u32 h[N_COUNTERS];
     HIPCHK(c, hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
     if (c->totals_valid) memcpy(h, c->host_totals, sizeof(h));          // a pipelined host batch: the sum over its launches
-    out[0] = h[L_NONE]; out[1] = h[L_ZSTD]; out[2] = h[L_LZ4] + h[C_LZ4_LEFT] /* both LZ4 lists */; out[3] = h[C_ZSTD_TWO_STAGE]; out[4] = h[C_ZSTD_FUSED];
+    out[0] = h[L_NONE]; out[1] = h[L_ZSTD]; out[2] = h[L_LZ4] + h[C_LZ4_LEFT] + h[C_LZ4_GEN] /* the three LZ4 lists */; out[3] = h[C_ZSTD_TWO_STAGE]; out[4] = h[C_ZSTD_FUSED];
     out[5] = h[ZF_WATCHDOG_WORD]; out[6] = h[ZF_WATCHDOG_WORD + 1]; out[7] = h[13];
     if (c->fell_back_fused) out[7] |= 0x80000000u;          // the batch could not get its sequence arena: fused decoder only
     ZPK_DEV(if (getenv("ZPK_TRACE")) fprintf(stderr, "[zpk] fse marked %u, pass-0 failures %u, last failure status/rc %08x\n", h[13], h[14], h[15]);)
@@ -1955,6 +2092,8 @@ int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16])
     out[2] = 0; out[3] = h[C_LZ4_LEFT]; out[4] = 0;      // [3]: LZ4 entries that are mostly runs, decoded by k_lz4_left (the two-stage path of round 4 is gone: [2], [4] read 0)
     out[5] = c->big_last[0]; out[6] = c->big_last[1];
     out[7] = c->zpj_last_err;                              // why the most recent large Zstandard frame was NOT finished block-parallel (0: it was, or none came)
+    out[8] = h[C_LZ4_HANDED];                              // LZ4 entries k_lz4_wave handed to the general decoder without judging them
+    out[9] = h[C_LZ4_GEN];                                 // LZ4 entries whose header is not that of a plain frame: k_lz4_general's
     return ZPK_OK;
 }
 
