@@ -16,6 +16,9 @@ lz4_loops() names the loops of k_lz4_wave the decoder's structure defines:
   rounds  the copy-rounds loop inside it: the largest child loop of the batch loop
   hop1/2  the two token-chain walks (first walk, fix-up walk): the loops without children that read three single bytes from LDS
           and shift a 64-bit mask (v_lshlrev_b64 / v_lshrrev_b64), in program order
+
+hash_loop() reports the XXH3 verify pass (xxh3_64_wave, one iteration = 4 KiB): the loop with at least four v_mad_u64_u32 and 16-byte
+global loads; vector instructions, ds_bpermute, v_mov and 16-byte loads per iteration, blocks of inner loops included.
 """
 import re
 import sys
@@ -162,8 +165,26 @@ def lz4_loops(text, name="k_lz4_wave"):
     return res
 
 
+def hash_loop(text, name="k_lz4_wave"):
+    """the XXH3 loop of kernel `name`: static counts per iteration (4 KiB of input)"""
+    body = kernel_body(text, name)
+
+    def has(insts, pat):
+        return sum(1 for s in insts if re.match(pat, s))
+    cands = [lp for lp in loops_of(body) if has(lp.insts(), r"v_mad_u64_u32") >= 4 and has(lp.insts(), r"global_load_dwordx4")]
+    if not cands:
+        raise RuntimeError("%s: no hash loop recognised" % name)
+    lp = min(cands, key=lambda l: len(l.insts()))          # the innermost of them
+    insts = lp.insts()
+    c = count(insts, spill_vgprs(body))
+    return dict(valu=c["valu"], ds_bpermute=has(insts, r"ds_bpermute_b32"), v_mov=c["v_mov"], loads=has(insts, r"global_load_dwordx4"),
+                mad_u64=has(insts, r"v_mad_u64_u32"), permlane_swap=has(insts, r"v_permlane(16|32)_swap"), lds_reads=has(insts, r"ds_read"),
+                waitcnt_vm0=has(insts, r"s_waitcnt vmcnt\(0\)"), v_mov_b64=has(insts, r"v_mov_b64"), total=c["total"])
+
+
 if __name__ == "__main__":
     t = open(sys.argv[1]).read()
     r = lz4_loops(t, sys.argv[2] if len(sys.argv) > 2 else "k_lz4_wave")
     for k in ("meta", "spill_vgprs", "kernel", "batch", "batch_inclusive", "rounds", "hop1", "hop2"):
         print(k, r[k])
+    print("hash", hash_loop(t, sys.argv[2] if len(sys.argv) > 2 else "k_lz4_wave"))

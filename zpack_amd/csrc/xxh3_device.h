@@ -3,11 +3,15 @@
 //
 // Replaces XXH3_64bits of the reference (lib/zpack_read.c:466, lib/zpack_write.c:256).
 //
-// Long inputs (> 240 B): the 8 u64 accumulators are spread over the wave.  Lane l owns the 16-byte
-// slot l of a 1 KiB block = stripe (l >> 2), accumulator pair q = (l & 3).  Within a block the 16
-// stripe contributions to one accumulator only ADD, so they are summed across the 16 lanes that share
-// q with DPP row rotations + v_permlane16/32_swap (no LDS); the per-block scramble then runs redundantly in every lane.  One block
-// costs one 16 B/lane load (1 KiB per wave instruction, fully coalesced) and ~70 VALU/DPP instructions.
+// Long inputs (> 240 B): the 8 u64 accumulators are spread over the wave, pair q = (l & 3) in every lane.
+//   * Xxh3Wave::block() / Xxh3Lite::block(): one 1 KiB block whose bytes are already in registers, lane l = 16-byte slot l = stripe
+//     (l >> 2).  The 16 stripe contributions to one accumulator only ADD: a 16-lane reduction per block (ds_bpermute, or DPP row
+//     rotations + v_permlane16/32_swap), then the scramble redundantly in every lane.  For kernels that hash what they copy or flush
+//     (k_stored, the Zstandard ring, the streams).
+//   * xxh3_64_wave(): a pass over memory, FOUR blocks per step, one DPP row of 16 lanes per block.  A lane sums the four stripes it
+//     takes of its block in its own registers, two DPP rotations finish the block sum inside the row, and only the chain
+//     acc = scramble(acc + S_b) crosses rows: 4 dwords per block instead of a reduction (117 against 213 vector instructions and 16
+//     against 64 ds_bpermute per 4 KiB in k_lz4_wave).
 #pragma once
 #include "zpk_device.h"
 
@@ -120,15 +124,21 @@ struct Xxh3Wave {
     u64 k0, k1;        // secret words of this lane's slot in a full block: secret[8*(l>>2) + 16q (+8)]
     u64 s0, s1;        // scramble keys secret[128 + 16q (+8)]
 
-    __device__ __forceinline__ void init(int lane)
+    // accumulators and scramble keys only: the four-block loop of xxh3_64_wave has keys of its own and loads k0 / k1 behind it
+    __device__ __forceinline__ void init_acc(int lane)
     {
-        const int q = lane & 3, s = lane >> 2;
+        const int q = lane & 3;
         const u64 init[8] = { ZPK_P32_3, ZPK_P64_1, ZPK_P64_2, ZPK_P64_3, ZPK_P64_4, ZPK_P32_2, ZPK_P64_5, ZPK_P32_1 };
         a0 = q == 0 ? init[0] : q == 1 ? init[2] : q == 2 ? init[4] : init[6];
         a1 = q == 0 ? init[1] : q == 1 ? init[3] : q == 2 ? init[5] : init[7];
-        k0 = sec64(8 * s + 16 * q); k1 = sec64(8 * s + 16 * q + 8);
         s0 = sec64(128 + 16 * q);   s1 = sec64(128 + 16 * q + 8);
     }
+    __device__ __forceinline__ void init_keys(int lane)
+    {
+        const int q = lane & 3, s = lane >> 2;
+        k0 = sec64(8 * s + 16 * q); k1 = sec64(8 * s + 16 * q + 8);
+    }
+    __device__ __forceinline__ void init(int lane) { init_acc(lane); init_keys(lane); }
 
     // contribution of one 16-byte slot (d0 = u64 index 2q of its stripe, d1 = index 2q+1)
     static __device__ __forceinline__ void slot(u64 d0, u64 d1, u64 key0, u64 key1, u64& c0, u64& c1)
@@ -142,12 +152,24 @@ struct Xxh3Wave {
     // two rotations (row_ror:4, row_ror:8) add up the four lanes q + 4i; across the four rows v_permlane16_swap / v_permlane32_swap
     // (gfx950) exchange whole rows / halves between a value and its copy, so that value + copy is the sum of the pair.  (Round 2 did
     // this with 16 ds_bpermute per 1 KiB block: ~100 LDS cycles per block on a CU whose LDS pipe the decoders keep 80 % busy.)
-    template <int CTRL>
+    // Two dwords as one 64-bit value the compiler cannot take apart again.  Left to itself it turns a + ((hi << 32) | lo) into
+    // a + lo + (hi << 32): two 64-bit additions and a zeroed register where one addition does (seen in the four-block loop: 8 + 16
+    // extra vector instructions per step).  The empty asm costs nothing and only hides where the halves came from.
+    static __device__ __forceinline__ u64 pair64(u32 lo, u32 hi)
+    {
+        u64 v = ((u64)hi << 32) | lo;
+        asm volatile("" : "+v"(v));
+        return v;
+    }
+    // c + (c rotated inside its DPP row).  LEAN (the four-block loop): every lane of the row is read, so bound_ctrl spares the
+    // zeroed `old` register of each v_mov_dpp, and the rotated value is pinned (pair64).  The Zstandard flush keeps the form it
+    // was measured with.
+    template <int CTRL, bool LEAN = false>
     static __device__ __forceinline__ u64 add_rotated(u64 c)
     {
-        const u32 rl = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)c, CTRL, 0xf, 0xf, false);
-        const u32 rh = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)(c >> 32), CTRL, 0xf, 0xf, false);
-        return c + (((u64)rh << 32) | rl);
+        const u32 rl = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)c, CTRL, 0xf, 0xf, LEAN);
+        const u32 rh = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)(c >> 32), CTRL, 0xf, 0xf, LEAN);
+        return c + (LEAN ? pair64(rl, rh) : (((u64)rh << 32) | rl));
     }
     static __device__ __forceinline__ u64 add_rows(u64 c)
     {
@@ -190,6 +212,62 @@ struct Xxh3Wave {
         reduce16<false>(c0, c1);
         a0 += c0; a1 += c1;
         scramble();
+    }
+
+    // ---- four blocks per step (xxh3_64_wave) -----------------------------------------------------------------------------------------
+    // lane = 16 r + 4 sub + q: DPP row r owns block 4 g + r of group g, q is the slot as above, and in iteration it = 0..3 the lane
+    // takes stripe 4 it + sub of its block.  A lane sums its four contributions in its own registers; the 16 stripes of a block are
+    // then the four lanes of one row that share q (row_sum: two DPP rotations, no LDS, no step across rows).  The block sums do not
+    // depend on the accumulators: only acc = scramble(acc + S_b) is a chain, and it takes the four sums in block order, each
+    // broadcast from its row to the wave (4 dwords per block, against the 16-lane reduction per block of block(): 16 ds_bpermute).
+    static __device__ __forceinline__ void quad_keys(int lane, int it, u64& key0, u64& key1)
+    {
+        const int off = 32 * it + 8 * ((lane >> 2) & 3) + 16 * (lane & 3);        // secret[8 s + 16 q], s = 4 it + sub
+        key0 = sec64(off); key1 = sec64(off + 8);
+    }
+    // ... from a copy of the secret in LDS (stage_secret): one 8-byte-aligned 16-byte read, nothing kept in registers
+    static __device__ __forceinline__ void quad_keys(lds_cp8 sec, int lane, int it, u64& key0, u64& key1)
+    {
+        const ZPK_LDS u64* w = (const ZPK_LDS u64*)(sec + 8 * ((lane >> 2) & 3) + 16 * (lane & 3)) + 4 * it;
+        key0 = w[0]; key1 = w[1];
+    }
+    // the 192-byte secret into LDS at `sec` (16-byte aligned); the wave's earlier LDS traffic there is over (in order per wave)
+    static __device__ __forceinline__ void stage_secret(lds_p8 sec, int lane)
+    {
+        wave_mem_fence();
+        if (lane < 12) lds_st128(sec + 16 * lane, ld128(XXH3_SECRET + 16 * lane));
+        wave_mem_fence();
+    }
+    static __device__ __forceinline__ void quad_slot(u128 d, u64 key0, u64 key1, u64& t0, u64& t1)
+    {
+        u64 c0, c1;
+        slot(d.lo, d.hi, key0, key1, c0, c1);
+        t0 += c0; t1 += c1;
+    }
+    static __device__ __forceinline__ void row_sum(u64& t0, u64& t1)
+    {
+        t0 = add_rotated<0x124, true>(t0); t1 = add_rotated<0x124, true>(t1);   // row_ror:4
+        t0 = add_rotated<0x128, true>(t0); t1 = add_rotated<0x128, true>(t1);   // row_ror:8
+    }
+    // row R of v in every row: one ds_bpermute per dword, the row picked by the instruction's offset field.  (A form without LDS,
+    // three v_permlane32/16_swap per dword for all four rows, compiles to 141 against 117 vector instructions per step and was never
+    // run on a GPU: profiles/r09/.)
+    template <int R>
+    static __device__ __forceinline__ u64 row_bcast_lds(u64 v, int l15x4)
+    {
+        const u32 lo = (u32)__builtin_amdgcn_ds_bpermute(l15x4 + 64 * R, (int)(u32)v);
+        const u32 hi = (u32)__builtin_amdgcn_ds_bpermute(l15x4 + 64 * R, (int)(u32)(v >> 32));
+        return pair64(lo, hi);
+    }
+    __device__ __forceinline__ void fold(u64 S0, u64 S1) { a0 += S0; a1 += S1; scramble(); }
+    // the block sums t0 / t1 of up to four blocks (row r = block r of the group; `n` = 1..4 of them exist, uniform) into the chain
+    __device__ __forceinline__ void fold_rows(u64 t0, u64 t1, u32 n, int lane)
+    {
+        const int l15x4 = 4 * (lane & 15);
+        fold(row_bcast_lds<0>(t0, l15x4), row_bcast_lds<0>(t1, l15x4));
+        if (n > 1) fold(row_bcast_lds<1>(t0, l15x4), row_bcast_lds<1>(t1, l15x4));
+        if (n > 2) fold(row_bcast_lds<2>(t0, l15x4), row_bcast_lds<2>(t1, l15x4));
+        if (n > 3) fold(row_bcast_lds<3>(t0, l15x4), row_bcast_lds<3>(t1, l15x4));
     }
 
     // tail: `nstripes` (0..15) whole stripes at `p`, then the last stripe [end-64, end).
@@ -248,7 +326,10 @@ struct Xxh3Lite {
 
 // XXH3_64bits(p, len) computed by one full wave (all 64 lanes must call; result uniform).
 // `p` may have any alignment.
-__device__ __forceinline__ u64 xxh3_64_wave(const u8* p, u64 len, int lane)
+// LDS_KEYS: the per-lane secret words of the four-block loop are read from a copy of the secret in LDS (`sec`: 192 bytes the
+// caller owns, written here) instead of being kept in 16 registers — for kernels built for 64 VGPRs (k_lz4_wave and its kin).
+template <bool LDS_KEYS = false>
+__device__ __forceinline__ u64 xxh3_64_wave(const u8* p, u64 len, int lane, lds_p8 sec = nullptr)
 {
     if (len <= 240) {
         u64 h = 0;
@@ -257,28 +338,50 @@ __device__ __forceinline__ u64 xxh3_64_wave(const u8* p, u64 len, int lane)
         return uni64(h);
     }
     Xxh3Wave st;
-    st.init(lane);
-    const u64 nblocks = (len - 1) >> 10;
-    const u8* q = p + 16 * lane;
-    // Software prefetch, two pairs of blocks in turn: while one pair is reduced (a block costs ~60 vector instructions) the
-    // loads of the other are in flight.  The loads are UNCONDITIONAL (past the end they re-read the last block) and no loaded
-    // register is ever moved: the compiler counts outstanding loads exactly only then (s_waitcnt vmcnt(2)); with a guarded
-    // load or a register rotation it waits for everything, i.e. for the loads it has just issued — a full memory round trip
-    // per pair, which is what this loop used to cost (18 % of k_lz4_wave).
+    st.init_acc(lane);
+    const u64 nblocks = uni64((len - 1) >> 10);
+    // Four blocks per step (Xxh3Wave, "four blocks per step"): row r = lane >> 4 reads block 4 g + r, 256 contiguous bytes per row
+    // and load.  Software prefetch in two halves: while iterations 0, 1 are multiplied the loads of 2, 3 are in flight, and the next
+    // group's 0, 1 while 2, 3 are multiplied and the group is reduced and folded.  The loads are UNCONDITIONAL (past the end they
+    // re-read the last block) and no loaded register is ever moved: the compiler counts outstanding
+    // loads exactly only then (s_waitcnt vmcnt(2)); with a guarded load or a register rotation it waits for everything, i.e. for
+    // the loads it has just issued — a full memory round trip per half, which is what this loop once cost (18 % of k_lz4_wave).
     if (nblocks > 0) {
-        const u64 last = nblocks - 1;
-        #define XXH3_LD(i) ld128(q + (((i) < last ? (i) : last) << 10))
-        u128 a0 = XXH3_LD(0), a1 = XXH3_LD(1);
-        for (u64 b = 0; b < nblocks; b += 4) {
-            const u128 c0 = XXH3_LD(b + 2), c1 = XXH3_LD(b + 3);
-            st.block(a0);
-            if (b + 1 < nblocks) st.block(a1);
-            a0 = XXH3_LD(b + 4); a1 = XXH3_LD(b + 5);
-            if (b + 2 < nblocks) st.block(c0);
-            if (b + 3 < nblocks) st.block(c1);
+        const u64 lastg = (nblocks - 1) >> 2;                         // the last group: 1..4 blocks
+        const u32 nlast = (((u32)nblocks - 1u) & 3u) + 1u;
+        const u32 row = (u32)lane >> 4, l16 = 16u * ((u32)lane & 15u);
+        u64 kc[4][2] = {};
+        if (LDS_KEYS) Xxh3Wave::stage_secret(sec, lane);
+        else { Xxh3Wave::quad_keys(lane, 0, kc[0][0], kc[0][1]); Xxh3Wave::quad_keys(lane, 1, kc[1][0], kc[1][1]);
+               Xxh3Wave::quad_keys(lane, 2, kc[2][0], kc[2][1]); Xxh3Wave::quad_keys(lane, 3, kc[3][0], kc[3][1]); }
+        #define XXH3_SLOT(d, it) do { u64 k0_ = kc[it][0], k1_ = kc[it][1]; if (LDS_KEYS) Xxh3Wave::quad_keys((lds_cp8)sec, lane, it, k0_, k1_); \
+                                      Xxh3Wave::quad_slot(d, k0_, k1_, t0, t1); } while (0)
+        // byte offset of the lane's row in a full group / in the last one (rows past its last block re-read that block: their sums
+        // stay in their rows and are never folded)
+        const u32 off_full = (row << 10) + l16, off_last = ((row < nlast ? row : nlast - 1u) << 10) + l16;
+        #define XXH3_LD(g, it) ld128(p + ((g) << 12) + ((g) == lastg ? off_last : off_full) + 256u * (it))
+        u128 a0 = XXH3_LD((u64)0, 0), a1 = XXH3_LD((u64)0, 1);
+        #pragma clang loop unroll(disable)                            // (no peeled last step either: its hand-over moves the loaded registers)
+        for (u64 g = 0; g <= lastg; g++) {
+            const u128 c0 = XXH3_LD(g, 2), c1 = XXH3_LD(g, 3);
+            __builtin_amdgcn_sched_barrier(0);                        // (the machine scheduler would issue all four loads up here)
+            u64 t0 = 0, t1 = 0;
+            XXH3_SLOT(a0, 0);
+            XXH3_SLOT(a1, 1);
+            const u64 gn = g < lastg ? g + 1 : lastg;                 // past the end: the last group again
+            asm volatile("" : "+v"(t0), "+v"(t1));                    // (the sums so far are finished here: a0 / a1 are dead, not copied)
+            __builtin_amdgcn_sched_barrier(0);
+            a0 = XXH3_LD(gn, 0); a1 = XXH3_LD(gn, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            XXH3_SLOT(c0, 2);
+            XXH3_SLOT(c1, 3);
+            Xxh3Wave::row_sum(t0, t1);
+            st.fold_rows(t0, t1, g == lastg ? nlast : 4u, lane);
         }
         #undef XXH3_LD
+        #undef XXH3_SLOT
     }
+    st.init_keys(lane);
     const u32 nstripes = (u32)(((len - 1) - (nblocks << 10)) >> 6);
     return st.finish(p + (nblocks << 10), nstripes, p + len, len, lane);
 }

@@ -239,15 +239,17 @@ __device__ __forceinline__ bool my_slot(const u32* counters, int list, u32& idx)
     return idx < uni(counters[list]);
 }
 
+template <bool LDS_KEYS = false>
 __device__ __forceinline__ void finish_entry(const zpk_decode_desc& d, zpk_decode_result* res, u32 e, int status, u32 detail,
-                                             u64 produced, const u8* out, int lane)
+                                             u64 produced, const u8* out, int lane, lds_p8 sec = nullptr)
 {
+    // LDS_KEYS: `sec` = 192 bytes of LDS (16-byte aligned) the caller no longer needs, for the hash loop's keys; else keys in registers
     u64 h = 0;
     lane0_guard();
     if (status == R_OK) {                                                      // (ZPK_DF_SKIP_HASH: the hash is still produced, the status ignores it)
         wave_mem_fence();
 #ifndef ZPK_ABL_NOHASH       // (developer ablation: instruction counters without the hash pass)
-        h = xxh3_64_wave(out, d.uncomp_size, lane);                            // lib/zpack_read.c:466
+        h = xxh3_64_wave<LDS_KEYS>(out, d.uncomp_size, lane, sec);                 // lib/zpack_read.c:466
 #endif
         if (h != d.expect_hash && !(d.flags & ZPK_DF_SKIP_HASH)) status = R_FILE_HASH_MISMATCH;   // :467-468
     }
@@ -354,7 +356,7 @@ __device__ __forceinline__ void lz4_entry_wave(Lz4WaveShared& shw, const u8* __r
     if (o.rc == D_MALFORMED) status = R_DECOMPRESS_FAILED;
     else if (o.rc == D_TRUNCATED) status = o.produced < d.dst_capacity ? R_FILE_INCOMPLETE : R_BUFFER_TOO_SMALL;
     else if (o.rc == D_DST_FULL) status = R_BUFFER_TOO_SMALL;
-    finish_entry(d, res, e, status, wd.fired ? 0xDEADu : (u32)(-o.rc), o.produced, out, lane);
+    finish_entry<true>(d, res, e, status, wd.fired ? 0xDEADu : (u32)(-o.rc), o.produced, out, lane, to_lds_rw(shw.stage));
 }
 
 // one LZ4 entry, one wave, the LEAN decoder of the hot kernel: one plain frame (lz4f_plain_wave) that decodes to exactly uncomp_size
@@ -382,7 +384,7 @@ __device__ __forceinline__ void lz4_entry_plain(Lz4WaveShared& shw, const u8* __
         }
         return;
     }
-    finish_entry(d, res, e, R_OK, 0u, uni64(d.uncomp_size), out, lane);
+    finish_entry<true>(d, res, e, R_OK, 0u, uni64(d.uncomp_size), out, lane, to_lds_rw(shw.stage));
 }
 
 // one wave per slot of the LZ4 work list: the hardware dispatcher is the load balancer.  (The developer build keeps the phase
