@@ -699,3 +699,85 @@ def test_work_lists_largest_first_give_identical_results(codec, lo, hi):
     for i in np.flatnonzero(ok):
         lo = int(desc["dst_offset"][i]); hi = lo + int(desc["uncomp_size"][i])
         assert np.array_equal(o1[lo:hi], o0[lo:hi]), i
+
+
+def test_every_work_list_filled_in_one_batch():
+    """One device batch in which EVERY work list and counter of the decode path is in use at once (zpk_layout.h): 4608 entries of
+    4 KiB — enough for the second stream of k_lz4_left, and with ZPK_OPT_ORDER_MIN = 1024 the counting sort and the ordered list
+    slots — in equal shares stored, Zstandard text, LZ4 plain text, LZ4 byte runs (compressed to less than 1/8), LZ4 frames with a
+    content checksum (not plain: k_lz4_general), plain LZ4 frames with a damaged end mark (handed over by k_lz4_wave unjudged) and
+    Zstandard frames with one flipped byte.  Decoded twice on a fresh codec: the first batch runs on "nothing known yet", the second
+    on what the pinned counts of the first select.  Status, produced, hash and bytes of every entry are the oracle's, and the
+    counters report each list as long as it was constructed."""
+    import torch
+    from tests.test_gpu_lz4_lean import _has_plain_header, _is_plain_and_whole, _with_content_checksum
+    o = oracle()
+    n, size, variants = 4608, 4096, 8
+    kinds = ("stored", "zstd", "lz4", "lz4_runs", "lz4_checksum", "lz4_damaged", "zstd_damaged")
+    rng = np.random.default_rng(2610)
+    pool = {}                                             # (kind, variant) -> (payload, method, XXH3 of the plain bytes)
+    for v in range(variants):
+        text, runs = dg.fill(dg.TEXT, 61, v, size).tobytes(), dg.fill(dg.RUNS, 61, v, size).tobytes()
+        ht, hr = dg.xxh3(text), dg.xxh3(runs)
+        lz, zs, lr = dg.compress(dg.LZ4, 0, text), dg.compress(dg.ZSTD, 3, text), dg.compress(dg.LZ4, 0, runs)
+        assert _is_plain_and_whole(lz) and len(lz) >= size >> 3 and _is_plain_and_whole(lr) and len(lr) < size >> 3
+        ck = _with_content_checksum(o, lz, text)
+        assert not _has_plain_header(ck) and len(ck) >= size >> 3
+        bad_lz = bytearray(lz); bad_lz[len(lz) - 4 + v % 4] ^= (0x01, 0x10, 0x7F)[v % 3]      # the end mark: behind the header, and no clean end
+        assert _has_plain_header(bad_lz) and not _is_plain_and_whole(bad_lz)
+        bad_zs = bytearray(zs); bad_zs[int(rng.integers(0, len(zs)))] ^= int(rng.integers(1, 256))
+        pool.update({("stored", v): (text, dg.NONE, ht), ("zstd", v): (zs, dg.ZSTD, ht), ("lz4", v): (lz, dg.LZ4, ht),
+                     ("lz4_runs", v): (lr, dg.LZ4, hr), ("lz4_checksum", v): (ck, dg.LZ4, ht), ("lz4_damaged", v): (bytes(bad_lz), dg.LZ4, ht),
+                     ("zstd_damaged", v): (bytes(bad_zs), dg.ZSTD, ht)})
+    keys = [(kinds[i % len(kinds)], (i // len(kinds)) % variants) for i in range(n)]
+    count = {k: sum(1 for kk, _ in keys if kk == k) for k in kinds}
+    assert min(count.values()) >= n // len(kinds)
+    frames = [pool[k][0] for k in keys]
+    offs = (10 + np.concatenate([[0], np.cumsum([len(f) for f in frames])])[:-1]).astype(np.uint64)
+    arc = zpk.assemble(frames, [("f%d" % i, int(offs[i]), len(frames[i]), size, pool[keys[i]][2], pool[keys[i]][1]) for i in range(n)])
+    desc = np.zeros(n, dtype=zpack_amd.DECODE_DESC)
+    desc["src_offset"] = offs; desc["comp_size"] = [len(f) for f in frames]; desc["uncomp_size"] = size; desc["dst_capacity"] = size
+    desc["expect_hash"] = [pool[k][2] for k in keys]; desc["method"] = [pool[k][1] for k in keys]
+    desc["dst_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(size + 256)
+    total = n * (size + 256) + 256
+    want = {}                                             # the oracle, once per distinct payload (zero-filled buffer, like the device slot)
+    for i, k in enumerate(keys):
+        if k not in want:
+            want[k] = o.entry_decode(arc, int(offs[i]), len(frames[i]), size, pool[k][2], pool[k][1], size)
+    assert all(want[(k, v)][0] == 0 for k in ("stored", "zstd", "lz4", "lz4_runs", "lz4_checksum") for v in range(variants))
+    assert all(want[("lz4_damaged", v)][0] != 0 for v in range(variants))
+    dev = torch.device("cuda:0")
+    src = torch.from_numpy(np.frombuffer(bytes(arc), dtype=np.uint8).copy()).to(dev)
+    ddesc = torch.from_numpy(desc.view(np.uint8)).to(dev)
+    codec = zpack_amd.Codec(0)
+    codec.set_option(zpack_amd.OPT_ORDER_MIN, 1024)
+    runs_out = []
+    try:
+        for _ in range(2):
+            dst = torch.zeros(total, dtype=torch.uint8, device=dev)
+            dres = torch.zeros(n * zpack_amd.DECODE_RESULT.itemsize, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            codec.decode_batch_device(src, ddesc, n, dst, dres)
+            torch.cuda.synchronize()
+            runs_out.append((dres.cpu().numpy().view(zpack_amd.DECODE_RESULT).copy(), dst.cpu().numpy(), codec.decode_stats()))
+    finally:
+        codec.set_option(zpack_amd.OPT_ORDER_MIN, 8192)
+        codec.close()
+    for run, (r, out, st) in enumerate(runs_out):
+        bad = []
+        for i, k in enumerate(keys):
+            rc, buf, got, h = want[k]
+            a = int(desc["dst_offset"][i])
+            if (int(r[i]["status"]), int(r[i]["produced"]), int(r[i]["hash"])) != (rc, got, h):
+                bad.append((i, k, "record", (int(r[i]["status"]), int(r[i]["produced"]), int(r[i]["hash"])), (rc, got, h)))
+            elif out[a:a + got].tobytes() != buf[:got]:
+                bad.append((i, k, "bytes"))
+        print("run", run, "entries that differ from the oracle:", len(bad), bad[:8], st)
+        assert bad == [], (run, len(bad), bad[:8])
+        assert st["stored"] == count["stored"] and st["zstd"] == count["zstd"] + count["zstd_damaged"], (run, st, count)
+        assert st["lz4"] == count["lz4"] + count["lz4_runs"] + count["lz4_checksum"] + count["lz4_damaged"], (run, st, count)
+        assert st["lz4_long_runs"] == count["lz4_runs"] and st["lz4_general"] == count["lz4_checksum"], (run, st, count)
+        assert st["lz4_handed_over"] == count["lz4_damaged"], (run, st, count)
+        assert st["zstd_two_stage"] + st["zstd_fused"] == count["zstd"] + count["zstd_damaged"], (run, st, count)
+    (r0, o0, _), (r1, o1, _) = runs_out
+    assert np.array_equal(r0, r1) and np.array_equal(o0, o1)

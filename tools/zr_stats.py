@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer: per-phase cycles of the Zstandard RING executor (needs a -DZPK_DEVELOPER -DZSTD_EXEC_RING -DLX_STATS -DLX_STATS_SCAN_ONLY=0
+"""Developer: per-phase cycles of the Zstandard RING executor (needs a -DZPK_DEVELOPER -DLX_STATS -DLX_STATS_SCAN_ONLY=0
 build selected with ZPACK_AMD_CODEC_SO, and ZPK_DEBUG_TIMING=1).  tools/zr_stats.py [entries] [mix]"""
 import os, sys
 import numpy as np

@@ -94,9 +94,6 @@ template <class OT>
 __device__ __forceinline__ u128 lx_load16(const OT& O, u32 s)
 {
     u128 v;
-#ifdef LX_ABL_NOGATHER
-    return lds_ld16_any((lds_cp8)O.ring, (s - O.rb) & (OT::RING - 1));
-#endif
     if (s >= O.rb) v = lds_ld16_any((lds_cp8)O.ring, s - O.rb);
     else v = ld128(O.dst + s);
     return v;
@@ -107,12 +104,8 @@ __device__ __forceinline__ void lx_flush_blocks(OT& O, int lane)
 {
     while (O.fp + 1024u <= O.wp) {
         const u128 v = lds_ld128((lds_cp8)(O.ring + (O.fp - O.rb) + 16u * (u32)lane));
-#ifndef LX_ABL_NOFLUSH
         st128(O.dst + O.fp + 16u * (u32)lane, v);
-#endif
-#ifndef LX_ABL_NOHASH
         if ((O.fp >> 10) < O.hash_blocks) O.xs.block(v, lane, O.sec);
-#endif
         O.fp += 1024u;
     }
 }
@@ -296,10 +289,7 @@ __device__ __forceinline__ int lx_exec_batch(OT& O, u32& cnt, u32 ll, u32 ml, u3
     // (Zstandard literals, far matches) that is one round trip instead of two)
     u128 mv0; mv0.lo = 0; mv0.hi = 0;
     const u128 lv0 = L.load16(0u);
-#ifndef LX_ABL_NOMATCH
     if (early) mv0 = lx_load16(O, sabs);
-#endif
-#ifndef LX_ABL_NOLIT
     {
         // every lane: its first 16 literal bytes (or fewer); the few longer runs go on in 16-byte steps, the last one overlapped
         lds_or_piece(ring, o - O.rb, lv0, ll < 16 ? ll : 16u);
@@ -311,10 +301,8 @@ __device__ __forceinline__ int lx_exec_batch(OT& O, u32& cnt, u32 ll, u32 ml, u3
             bm = __ballot(c + 16 < ll);
         }
     }
-#endif
     LXT(5);
     // ---- matches whose whole source is older than this batch ----
-#ifndef LX_ABL_NOMATCH
     {
         lds_or_piece(ring, ms - O.rb, mv0, !early ? 0u : (ml < 16 ? ml : 16u));
         u64 bm = __ballot(early && ml > 16);
@@ -327,7 +315,6 @@ __device__ __forceinline__ int lx_exec_batch(OT& O, u32& cnt, u32 ll, u32 ml, u3
             bm = __ballot(early && c + 16 < ml);
         }
     }
-#endif
     wave_mem_fence();
     LXT(6);
     // ---- rounds: matches that read this batch's own output ----

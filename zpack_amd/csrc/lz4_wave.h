@@ -370,13 +370,9 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
             // executor assembles the batch there.  The first batch or two of a chunk find too little room and
             // take the direct path.
             const u32 dead = (u32)__builtin_amdgcn_readfirstlane((int)tok_pos) - cpos;
-#ifdef LZ4W_ABL_NOEXEC      // developer ablation (instruction counters only; the output is wrong): parse without the executor
-            (void)dead; const int rc = D_OK; { const u32 xx = wave_scan_add(q.ll + q.ml); op += (u32)__builtin_amdgcn_readlane((int)xx, 63); }
-#else
             int rc;
             if constexpr (EMIT) { (void)dead; rc = emit(q, cnt, (u32)(q.lit - ip)); }
             else rc = seq_exec_batch<true, COOP>(q, cnt, op, oend, dst_lo, -1, lane, stt, B.S, to_lds_rw(sh.stage), dead);
-#endif
             if (rc != D_OK) { op_io = op; return rc; }
         }
         if (fl) return D_MALFORMED;                                            // (not reached: the executor saw the malformed token)

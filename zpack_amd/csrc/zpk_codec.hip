@@ -40,32 +40,13 @@
 
 using namespace zpk;
 
-// counters layout (u32): [0..3] count per work list, [4..7] dequeue head per list
-enum { L_NONE = 0, L_ZSTD = 1, L_LZ4 = 2, L_COUNT = 4, N_LISTS = 3, L_LZ4_RUNS = 100 /* k_classify only: the LZ4 entries k_lz4_left takes (its list is slot N_LISTS + 2) */,
-       L_LZ4_GEN = 101 /* k_classify only: LZ4 entries whose frame header is not a plain one (k_lz4_general's: list slot S_LZ4_GEN, length in counters[C_LZ4_GEN]) */ };
-// [8] dequeue head of k_zstd_fse, [9] Zstandard entries finished on pre-decoded sequences, [10] finished by the fused decoder
-enum { C_ZSTD_TWO_STAGE = 9, C_ZSTD_FUSED = 10, C_EXEC_HEAD = 16, C_LEFT_COUNT = 17,
-       C_RETRY_LZ4 = 18, C_RETRY_ZSTD = 19,     // entries whose decoder ran out of its time budget: decoded again by the retry launches
-       C_RETRY_HEAD = 20,                       // dequeue head of the Zstandard retry launch
-       C_LZ4_LEFT = 21, C_LZ4_LEFT_HEAD = 22,   // LZ4 entries that are mostly runs (k_classify: compressed to less than 1/8): k_lz4_left's list, its dequeue head
-       C_LZ4_GEN = 3, C_LZ4_GEN_HEAD = 7,       // LZ4 entries whose header is not that of a plain frame (k_classify): k_lz4_general's list, its dequeue head
-       C_LZ4_HANDED_HEAD = 23, C_LZ4_HANDED = 24, // LZ4 entries k_lz4_wave handed over WITHOUT judging them (a plain header, but no clean end): a list of their own
-       C_LZ4_RETRY_HEAD = 25,                   // dequeue head of k_lz4_retry on the LZ4 retry list (time budgets)
-       C_ENC_CLASS = 28,                        // (three words) encode batches: does the batch hold entries for k_encode<12> / <13> / <14> at all
-       C_ORDER_SPAN = 26,                       // (two words) largest size class and largest 15 - class among the Zstandard / LZ4 entries
-       C_ORDER = 32,                            // k_order_*: [3 lists][16 classes] entry counts, then the same again as fill cursors
-       N_COUNTERS = 32 + 96 };
-// list storage behind the three method lists: the two retry lists, the LZ4 entries of long runs (k_lz4_left), the ordered Zstandard / LZ4 lists,
-// the LZ4 hand-overs, the LZ4 entries that are not plain frames and their ordered copy
-enum { S_LZ4_HANDED = N_LISTS + 5, S_LZ4_GEN = N_LISTS + 6, S_LZ4_GEN_ORDERED = N_LISTS + 7, N_LISTS_ALLOC = N_LISTS + 8 };
-#define N_ORDERED 3                              // k_order_*: grid.y = 0 Zstandard, 1 LZ4 (plain), 2 LZ4 (general)
-__device__ __forceinline__ int order_list_slot(int y) { return y == 0 ? (int)L_ZSTD : y == 1 ? (int)L_LZ4 : (int)S_LZ4_GEN; }
-__device__ __forceinline__ int order_count_word(int y) { return y == 0 ? (int)L_ZSTD : y == 1 ? (int)L_LZ4 : (int)C_LZ4_GEN; }
-__device__ __forceinline__ int order_out_slot(int y) { return y == 2 ? (int)S_LZ4_GEN_ORDERED : (int)N_LISTS + 3 + y; }
+// the counter block and the list storage: zpk_layout.h
+__device__ __forceinline__ int order_list_slot(int y) { return y == 0 ? (int)S_ZSTD : y == 1 ? (int)S_LZ4 : (int)S_LZ4_GEN; }
+__device__ __forceinline__ int order_count_word(int y) { return y == 0 ? (int)C_ZSTD : y == 1 ? (int)C_LZ4 : (int)C_LZ4_GEN; }
+__device__ __forceinline__ int order_out_slot(int y) { return y == 0 ? (int)S_ZSTD_ORDERED : y == 1 ? (int)S_LZ4_ORDERED : (int)S_LZ4_GEN_ORDERED; }
 
 // ------------------------------------------------------------------------------------ kernels
 
-#define ORD_CLASSES 16
 __device__ __forceinline__ int order_class(u64 size)
 {
     const int lg = 63 - __clzll((long long)(size | 1));
@@ -85,6 +66,19 @@ __device__ __forceinline__ bool lz4_header_is_plain(const u8* __restrict__ p, u6
     const u32 magic = (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24), flg = p[4], bd = p[5];
     return magic == 0x184D2204u && (flg & 0xD7u) == 0x40u && (bd & 0x8Fu) == 0 && ((bd >> 4) & 7u) >= 4u;
 }
+// wave-aggregated append of this wave's entries for list SLOT: one atomic per list per wave (a per-lane atomicAdd on three hot
+// words cost 1.1 ms / 100k entries)
+template <int SLOT>
+__device__ __forceinline__ void classify_append(int list, u64 i, int lane, u32* __restrict__ lists, u64 list_stride, u32* __restrict__ counters)
+{
+    const u64 m = __ballot(list == SLOT);
+    if (m == 0) return;
+    const int leader = __ffsll((long long)m) - 1;
+    u32 base = 0;
+    if (lane == leader) base = atomicAdd(&counters[list_count_word(SLOT)], (u32)__popcll(m));
+    base = (u32)__shfl((int)base, leader, 64);
+    if (list == SLOT) lists[(u64)SLOT * list_stride + base + (u32)__popcll(m & ((1ull << lane) - 1))] = (u32)i;
+}
 __global__ __launch_bounds__(256) void k_classify(const u8* __restrict__ src, const zpk_decode_desc* __restrict__ desc, u64 n, u64 src_size, u64 dst_size,
                                                   zpk_decode_result* __restrict__ res, u32* __restrict__ lists, u64 list_stride,
                                                   u32* __restrict__ counters)
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(256) void k_classify(const u8* __restrict__ src, co
     zpk_decode_desc d; memset(&d, 0, sizeof(d));
     if (live) d = desc[i];
     zpk_decode_result r; r.status = R_OK; r.detail = 0; r.produced = 0; r.hash = 0;
-    int list = -1;
+    int list = -1;                                                             // a ListSlot
     // lib/zpack_read.c:328-332, in this order
     if (!live) list = -1;
     else if (d.comp_size == 0) r.status = R_OK;
@@ -104,55 +98,29 @@ __global__ __launch_bounds__(256) void k_classify(const u8* __restrict__ src, co
     else if (d.dst_offset > dst_size || d.dst_capacity > dst_size - d.dst_offset) { r.status = R_BUFFER_TOO_SMALL; r.detail = 0xBAD0D57u; }
     else if (d.method == ZPK_METHOD_NONE) {
         if (d.uncomp_size > d.comp_size) r.status = R_FILE_SIZE_INVALID;      // :354
-        else list = L_NONE;
+        else list = S_NONE;
     }
-    else if (d.method == ZPK_METHOD_ZSTD) list = L_ZSTD;
+    else if (d.method == ZPK_METHOD_ZSTD) list = S_ZSTD;
     else if (d.method == ZPK_METHOD_LZ4)                                       // mostly runs: k_lz4_left's; not a plain frame: k_lz4_general's
-        list = d.comp_size < (d.uncomp_size >> 3) ? L_LZ4_RUNS : lz4_header_is_plain(src + d.src_offset, d.comp_size) ? L_LZ4 : L_LZ4_GEN;
+        list = d.comp_size < (d.uncomp_size >> 3) ? S_LZ4_RUNS : lz4_header_is_plain(src + d.src_offset, d.comp_size) ? S_LZ4 : S_LZ4_GEN;
     else r.status = R_COMP_METHOD_INVALID;                                     // :459
     // an entry that goes on a work list is not decoded yet: until its decoder writes the verdict the slot says so
     // (a decoder that never ran must not read as R_OK)
     if (list >= 0) { r.status = R_DECOMPRESS_FAILED; r.detail = 0xFFFFFFFFu; }
     if (live) res[i] = r;
-    // wave-aggregated append: one atomic per list per wave (a per-lane atomicAdd on three hot words cost 1.1 ms / 100k entries)
     const int lane = lane_id();
     {   // the span of size classes among the entries that go to a decoder (k_order_*)
-        const bool dec = list == L_ZSTD || list == L_LZ4 || list == L_LZ4_GEN;
+        const bool dec = list == S_ZSTD || list == S_LZ4 || list == S_LZ4_GEN;
         u32 hi = dec ? (u32)order_class(d.uncomp_size) + 1u : 0u, inv = dec ? (u32)(ORD_CLASSES - order_class(d.uncomp_size)) : 0u;   // (+1: 0 = none)
         #pragma unroll
         for (int m = 1; m < 64; m <<= 1) { const u32 a = (u32)__shfl_xor((int)hi, m, 64), b2 = (u32)__shfl_xor((int)inv, m, 64); hi = a > hi ? a : hi; inv = b2 > inv ? b2 : inv; }
-        if (lane == 0 && hi) { atomicMax(&counters[C_ORDER_SPAN], hi - 1u); atomicMax(&counters[C_ORDER_SPAN + 1], inv - 1u); }
+        if (lane == 0 && hi) { atomicMax(&counters[C_ORDER_SPAN], hi - 1u); atomicMax(&counters[C_ORDER_SPAN_INV], inv - 1u); }
     }
-    #pragma unroll
-    for (int L = 0; L < N_LISTS; L++) {
-        const u64 m = __ballot(list == L);
-        if (m == 0) continue;
-        const int leader = __ffsll((long long)m) - 1;
-        u32 base = 0;
-        if (lane == leader) base = atomicAdd(&counters[L], (u32)__popcll(m));
-        base = (u32)__shfl((int)base, leader, 64);
-        if (list == L) lists[(u64)L * list_stride + base + (u32)__popcll(m & ((1ull << lane) - 1))] = (u32)i;
-    }
-    {   // k_lz4_left's list: storage slot N_LISTS + 2, length in counters[C_LZ4_LEFT]
-        const u64 m = __ballot(list == L_LZ4_RUNS);
-        if (m != 0) {
-            const int leader = __ffsll((long long)m) - 1;
-            u32 base = 0;
-            if (lane == leader) base = atomicAdd(&counters[C_LZ4_LEFT], (u32)__popcll(m));
-            base = (u32)__shfl((int)base, leader, 64);
-            if (list == L_LZ4_RUNS) lists[(u64)(N_LISTS + 2) * list_stride + base + (u32)__popcll(m & ((1ull << lane) - 1))] = (u32)i;
-        }
-    }
-    {   // k_lz4_general's list
-        const u64 m = __ballot(list == L_LZ4_GEN);
-        if (m != 0) {
-            const int leader = __ffsll((long long)m) - 1;
-            u32 base = 0;
-            if (lane == leader) base = atomicAdd(&counters[C_LZ4_GEN], (u32)__popcll(m));
-            base = (u32)__shfl((int)base, leader, 64);
-            if (list == L_LZ4_GEN) lists[(u64)S_LZ4_GEN * list_stride + base + (u32)__popcll(m & ((1ull << lane) - 1))] = (u32)i;
-        }
-    }
+    classify_append<S_NONE>(list, i, lane, lists, list_stride, counters);
+    classify_append<S_ZSTD>(list, i, lane, lists, list_stride, counters);
+    classify_append<S_LZ4>(list, i, lane, lists, list_stride, counters);
+    classify_append<S_LZ4_RUNS>(list, i, lane, lists, list_stride, counters);
+    classify_append<S_LZ4_GEN>(list, i, lane, lists, list_stride, counters);
 }
 
 // ---- largest entries first -----------------------------------------------------------------------------------------------------
@@ -161,9 +129,9 @@ __global__ __launch_bounds__(256) void k_classify(const u8* __restrict__ src, co
 // The Zstandard and LZ4 work lists are therefore re-ordered by size class (floor(log2 uncomp_size), largest first: longest
 // processing time first) with a two-kernel counting sort — per-workgroup LDS histograms, one global atomic per class and
 // workgroup; entries of one class keep their neighbourhood.  (Uniform batches come out in nearly the order they went in.)
-// (k_classify leaves the largest class and the largest 15 - class it saw in counters[C_ORDER_SPAN], [C_ORDER_SPAN + 1]: a batch of ONE
+// (k_classify leaves the largest class and the largest 15 - class it saw in counters[C_ORDER_SPAN], [C_ORDER_SPAN_INV]: a batch of ONE
 // class — the uniform workloads — is copied through in its own order.)
-__device__ __forceinline__ bool order_single_class(const u32* counters) { return counters[C_ORDER_SPAN] + counters[C_ORDER_SPAN + 1] == ORD_CLASSES - 1; }
+__device__ __forceinline__ bool order_single_class(const u32* counters) { return counters[C_ORDER_SPAN] + counters[C_ORDER_SPAN_INV] == ORD_CLASSES - 1; }
 // rank of this lane among the lanes of its wave with the same class (in lane order), and how many there are
 __device__ __forceinline__ void order_wave_rank(int b, int lane, u32& rank, u32& count)
 {
@@ -194,7 +162,7 @@ __global__ __launch_bounds__(256) void k_order_count(const zpk_decode_desc* __re
     order_wave_rank(b, lane, rank, count);
     if (b >= 0 && rank == 0) atomicAdd(&h[b], count);
     __syncthreads();
-    if (threadIdx.x < ORD_CLASSES && h[threadIdx.x]) atomicAdd(&counters[C_ORDER + blockIdx.y * ORD_CLASSES + threadIdx.x], h[threadIdx.x]);
+    if (threadIdx.x < ORD_CLASSES && h[threadIdx.x]) atomicAdd(&counters[C_ORDER_HIST + blockIdx.y * ORD_CLASSES + threadIdx.x], h[threadIdx.x]);
 }
 __global__ __launch_bounds__(256) void k_order_fill(const zpk_decode_desc* __restrict__ desc, const u32* __restrict__ lists, u64 list_stride,
                                                     u32* __restrict__ all_lists /* the ordered copies: order_out_slot() */, u32* __restrict__ counters, int fast_last)
@@ -219,10 +187,10 @@ __global__ __launch_bounds__(256) void k_order_fill(const zpk_decode_desc* __res
     if (threadIdx.x < ORD_CLASSES) {                                                   // this workgroup's range of the class: entries stay in list order inside it
         const int c = threadIdx.x;
         const u32 total = wcount[0][c] + wcount[1][c] + wcount[2][c] + wcount[3][c];
-        const u32* const hist = counters + C_ORDER + blockIdx.y * ORD_CLASSES;
+        const u32* const hist = counters + C_ORDER_HIST + blockIdx.y * ORD_CLASSES;
         u32 before = 0;
         for (int j = 0; j < c; j++) before += hist[j];
-        base[c] = total ? before + atomicAdd(&counters[C_ORDER + N_ORDERED * ORD_CLASSES + blockIdx.y * ORD_CLASSES + c], total) : 0;
+        base[c] = total ? before + atomicAdd(&counters[C_ORDER_FILL + blockIdx.y * ORD_CLASSES + c], total) : 0;
     }
     __syncthreads();
     if (b >= 0) {
@@ -233,10 +201,10 @@ __global__ __launch_bounds__(256) void k_order_fill(const zpk_decode_desc* __res
 }
 
 // one wave per work-list slot: the hardware dispatcher is the load balancer
-__device__ __forceinline__ bool my_slot(const u32* counters, int list, u32& idx)
+__device__ __forceinline__ bool my_slot(const u32* counters, int count_word, u32& idx)
 {
     idx = uni((u32)(((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6));           // 64-bit: n blocks x 64 threads passes 2^32 at n = 2^26
-    return idx < uni(counters[list]);
+    return idx < uni(counters[count_word]);
 }
 
 template <bool LDS_KEYS = false>
@@ -248,9 +216,7 @@ __device__ __forceinline__ void finish_entry(const zpk_decode_desc& d, zpk_decod
     lane0_guard();
     if (status == R_OK) {                                                      // (ZPK_DF_SKIP_HASH: the hash is still produced, the status ignores it)
         wave_mem_fence();
-#ifndef ZPK_ABL_NOHASH       // (developer ablation: instruction counters without the hash pass)
         h = xxh3_64_wave<LDS_KEYS>(out, d.uncomp_size, lane, sec);                 // lib/zpack_read.c:466
-#endif
         if (h != d.expect_hash && !(d.flags & ZPK_DF_SKIP_HASH)) status = R_FILE_HASH_MISMATCH;   // :467-468
     }
     lane0_guard();
@@ -267,7 +233,7 @@ __global__ __launch_bounds__(256) void k_stored(const u8* __restrict__ src, cons
 {
     const int lane = lane_id();
     u32 idx;
-    if (my_slot(counters, L_NONE, idx)) {
+    if (my_slot(counters, C_NONE, idx)) {
         const u32 e = uni(list[idx]);
         const zpk_decode_desc d = desc[e];
         const u8* in = uni_ptr(src + d.src_offset);
@@ -405,7 +371,7 @@ __global__ __launch_bounds__(64, 8) void k_lz4_wave(const u8* __restrict__ src, 
     const int lane = lane_id();
     __shared__ Lz4WaveShared shw;
     u32 idx;
-    if (my_slot(counters, L_LZ4, idx))
+    if (my_slot(counters, C_LZ4, idx))
         lz4_entry_plain(shw, src, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, retry_list, handed_list, wd_scale, lane);
 }
 
@@ -414,7 +380,7 @@ __global__ __launch_bounds__(64, 8) void k_lz4_wave(const u8* __restrict__ src, 
 __global__ __launch_bounds__(256) void k_lz4_hand_all(const u32* __restrict__ list, u32* __restrict__ counters, u32* __restrict__ handed_list)
 {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < counters[L_LZ4]) handed_list[atomicAdd(&counters[C_LZ4_HANDED], 1u)] = list[i];
+    if (i < counters[C_LZ4]) handed_list[atomicAdd(&counters[C_LZ4_HANDED], 1u)] = list[i];
 }
 #endif
 
@@ -433,15 +399,8 @@ __global__ __launch_bounds__(64, 8) void k_lz4_general(const u8* __restrict__ sr
     __shared__ Lz4WaveShared shw;
     const u32 n_slots = uni(counters[C_LZ4_GEN]);
     if (n_slots == 0) return;
-    for (;;) {
-        lane0_guard();
-        u32 v = 0;
-        if (lane == 0) v = atomicAdd(&counters[C_LZ4_GEN_HEAD], 1u);
-        const u32 idx = uni(v);
-        lane0_guard();
-        if (idx >= n_slots) break;
+    for (u32 idx; dequeue(counters, C_LZ4_GEN_HEAD, n_slots, lane, idx); )
         lz4_entry_wave<0>(shw, src, read_lo, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, retry_list, wd_scale, lane);
-    }
 }
 
 // The general decoder behind all other LZ4 kernels of the batch, a small grid (what it finds is rare: normally nothing, and then every
@@ -459,18 +418,11 @@ __global__ __launch_bounds__(64, 8) void k_lz4_retry(const u8* __restrict__ src,
     for (int k = 0; k < 3; k++) {
         const int count_word = k == 0 ? (int)C_LZ4_GEN : k == 1 ? (int)C_LZ4_HANDED : (int)C_RETRY_LZ4;
         const int head_word = k == 0 ? (int)C_LZ4_GEN_HEAD : k == 1 ? (int)C_LZ4_HANDED_HEAD : (int)C_LZ4_RETRY_HEAD;
-        const u32* const list = lists + (u64)(k == 0 ? gen_slot : k == 1 ? (int)S_LZ4_HANDED : (int)N_LISTS) * list_stride;
+        const u32* const list = lists + (u64)(k == 0 ? gen_slot : k == 1 ? (int)S_LZ4_HANDED : (int)S_RETRY_LZ4) * list_stride;
         const u32 n_slots = uni(counters[count_word]);
         if (n_slots == 0 || uni(counters[head_word]) >= n_slots) continue;          // (empty, or drained by an earlier launch)
-        for (;;) {
-            lane0_guard();
-            u32 v = 0;
-            if (lane == 0) v = atomicAdd(&counters[head_word], 1u);
-            const u32 idx = uni(v);
-            lane0_guard();
-            if (idx >= n_slots) break;
+        for (u32 idx; dequeue(counters, head_word, n_slots, lane, idx); )
             lz4_entry_wave<2>(shw, src, read_lo, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, nullptr, (u32)ZPK_WATCHDOG_RETRY_SCALE, lane);
-        }
     }
 }
 
@@ -490,17 +442,10 @@ __global__ __launch_bounds__(64, LZ4_LEFT_WAVES) void k_lz4_left(const u8* __res
 {
     const int lane = lane_id();
     __shared__ Lz4WaveShared shw;
-    const u32 n_slots = uni(counters[C_LZ4_LEFT]);
+    const u32 n_slots = uni(counters[C_LZ4_RUNS]);
     if (n_slots == 0) return;                      // (text, records: always — 8192 dequeues on one word are 0.1 ms by themselves)
-    for (;;) {
-        lane0_guard();
-        u32 v = 0;
-        if (lane == 0) v = atomicAdd(&counters[C_LZ4_LEFT_HEAD], 1u);
-        const u32 idx = uni(v);
-        lane0_guard();
-        if (idx >= n_slots) break;
+    for (u32 idx; dequeue(counters, C_LZ4_RUNS_HEAD, n_slots, lane, idx); )
         lz4_entry_wave<2>(shw, src, read_lo, read_hi, desc, dst, res, uni(list[idx]), counters, dbg, retry_list, wd_scale, lane);
-    }
 }
 
 // Stage 2 of the two-stage Zstandard path: entries whose sequences k_zstd_fse left in the arena (zstate == 1) are run
@@ -513,13 +458,9 @@ __global__ __launch_bounds__(64, LZ4_LEFT_WAVES) void k_lz4_left(const u8* __res
 #define ZSTD_EXEC_WAVES 4
 #endif
 // The execute stage runs through the LDS output ring (zstd_ring.h): aligned LDS accesses, near matches served from LDS, whole 1 KiB
-// lines flushed with the XXH3 accumulators fed on the way out.  Against the direct executor (zstd_sequences_pre + seq_exec_batch,
-// every sequence written to and gathered from HBM with exact-tail accesses, hash by re-reading; -DZSTD_EXEC_DIRECT keeps it) it moves
-// 34 % fewer bytes in and 27 % fewer out of HBM at the same speed (profiles/r02: text, 8192 x 256 KiB: FETCH 13.8 -> 9.1 GB raw,
-// WRITE 4.5 -> 3.3 GB; C3 62.4 vs 61.3 ms, C4 equal).
-#ifndef ZSTD_EXEC_DIRECT
-#define ZSTD_EXEC_RING 1
-#endif
+// lines flushed with the XXH3 accumulators fed on the way out.  Against the direct executor of round 1 (every sequence written to and
+// gathered from HBM with exact-tail accesses, hash by re-reading) it moves 34 % fewer bytes in and 27 % fewer out of HBM at the same
+// speed (profiles/r02: text, 8192 x 256 KiB: FETCH 13.8 -> 9.1 GB raw, WRITE 4.5 -> 3.3 GB; C3 62.4 vs 61.3 ms, C4 equal).
 __global__ __launch_bounds__(ZSTD_WG_THREADS, ZSTD_EXEC_WAVES) void k_zstd_exec(const u8* __restrict__ src, const zpk_decode_desc* __restrict__ desc,
                                                                u8* dst, zpk_decode_result* __restrict__ res,
                                                                const u32* __restrict__ list, u32* __restrict__ counters,
@@ -527,29 +468,17 @@ __global__ __launch_bounds__(ZSTD_WG_THREADS, ZSTD_EXEC_WAVES) void k_zstd_exec(
                                                                u32* __restrict__ zstate, u32* __restrict__ leftover, u64* __restrict__ dbg)
 {
     const int lane = lane_id();
-    const u32 nz = uni(counters[L_ZSTD]);
+    const u32 nz = uni(counters[C_ZSTD]);
     if (nz == 0) return;
-#ifndef ZSTD_EXEC_RING
-    __shared__ __attribute__((aligned(16))) u8 sh_raw[ZSTD_SHARED_EXEC_BYTES];
-    ZstdShared& sh = *(ZstdShared*)sh_raw;
-    if (threadIdx.x == 0) { sh.defaults_built = 0; sh.huf_valid = 0; }
-#else
     __shared__ ZstdRingShared sh;
     if (threadIdx.x == 0) sh.huf_valid = 0;
-#endif
     __syncthreads();
     u8* lit = lit_scratch + (u64)blockIdx.x * ZSTD_LIT_SCRATCH;
-    for (;;) {
-        lane0_guard();
-        u32 v = 0;
-        if (lane == 0) v = atomicAdd(&counters[C_EXEC_HEAD], 1u);
-        const u32 idx = uni(v);
-        lane0_guard();
-        if (idx >= nz) break;
+    for (u32 idx; dequeue(counters, C_EXEC_HEAD, nz, lane, idx); ) {
         const u32 e = uni(list[idx]);
         if (uni(zstate[e]) != 1u) {                     // not pre-decoded: straight to the full decoder's list
             lane0_guard();
-            if (lane == 0) leftover[atomicAdd(&counters[C_LEFT_COUNT], 1u)] = e;
+            if (lane == 0) leftover[atomicAdd(&counters[C_ZSTD_LEFT], 1u)] = e;
             lane0_guard();
             continue;
         }
@@ -558,34 +487,6 @@ __global__ __launch_bounds__(ZSTD_WG_THREADS, ZSTD_EXEC_WAVES) void k_zstd_exec(
         u8* out = uni_ptr(dst + d.dst_offset);
         const u64* const pre = arena + (((u64)d.dst_offset + 7) >> 3);
         Watchdog wd; wd.arm(uni64(d.comp_size) + uni64(d.dst_capacity));
-#ifndef ZSTD_EXEC_RING
-#ifdef ZPK_STATS
-        ZstdStats zs = {};
-        const u64 t_all = SEQ_T();
-        DecodeOut o = zstd_decode_wave<true>(sh, wd, in, uni64(d.comp_size), out, uni64(d.dst_capacity), lit, lane, &zs, pre);
-        const u64 t_dec = SEQ_T();
-#else
-        (void)dbg;
-        DecodeOut o = zstd_decode_wave<true>(sh, wd, in, uni64(d.comp_size), out, uni64(d.dst_capacity), lit, lane, nullptr, pre);
-#endif
-        bool ok = o.rc == D_OK;
-        u64 h = 0;
-        lane0_guard();
-        if (ok) {
-            wave_mem_fence();
-    #ifndef ZPK_ABL_NOHASH       // (developer ablation: instruction counters without the hash pass)
-        h = xxh3_64_wave(out, d.uncomp_size, lane);                            // lib/zpack_read.c:466
-#endif
-            ok = h == d.expect_hash || (d.flags & ZPK_DF_SKIP_HASH);
-        }
-        const int ok_status = R_OK;
-#ifdef ZPK_STATS
-        if (dbg && lane == 0) {
-            u64* g = dbg + (u64)e * 16;
-            g[0] = zs.t_lit; g[1] = zs.t_tab; g[2] = zs.t_fse; g[3] = zs.t_exec; g[4] = zs.nseq; g[5] = zs.nblk; g[6] = t_dec - t_all; g[7] = SEQ_T() - t_dec;
-        }
-#endif
-#else
         (void)dbg;
         // through the LDS output ring (zstd_ring.h): the hash comes out of the flushes
         struct { int rc; u64 produced; } o;
@@ -598,7 +499,6 @@ __global__ __launch_bounds__(ZSTD_WG_THREADS, ZSTD_EXEC_WAVES) void k_zstd_exec(
         // (the set of frames this path accepts equals the oracle's on 18 000 damaged frames: profiles/r02/r02_fuzz_ring_executor.log)
         const bool ok = xr.rc == LX_OK && xr.produced == uni64(d.uncomp_size);
         const int ok_status = (h == d.expect_hash || (d.flags & ZPK_DF_SKIP_HASH)) ? R_OK : R_FILE_HASH_MISMATCH;
-#endif
         lane0_guard();
         if (lane == 0) {
             if (ok) {
@@ -607,8 +507,8 @@ __global__ __launch_bounds__(ZSTD_WG_THREADS, ZSTD_EXEC_WAVES) void k_zstd_exec(
                 zstate[e] = 2u;
                 atomicAdd(&counters[C_ZSTD_TWO_STAGE], 1u);
             } else {
-                leftover[atomicAdd(&counters[C_LEFT_COUNT], 1u)] = e;
-                atomicAdd(&counters[14], 1u); counters[15] = ((u32)(-o.rc) & 0xFFFFu);
+                leftover[atomicAdd(&counters[C_ZSTD_LEFT], 1u)] = e;
+                atomicAdd(&counters[C_EXEC_FAILED], 1u); counters[C_EXEC_LAST_RC] = ((u32)(-o.rc) & 0xFFFFu);
             }
         }
     }
@@ -630,13 +530,7 @@ __global__ __launch_bounds__(ZSTD_WG_THREADS, 3) void k_zstd(const u8* __restric
     if (threadIdx.x == 0) { sh.defaults_built = 0; sh.huf_valid = 0; }
     __syncthreads();
     u8* lit = lit_scratch + (u64)blockIdx.x * ZSTD_LIT_SCRATCH;
-    for (;;) {
-        lane0_guard();
-        u32 v = 0;
-        if (lane == 0) v = atomicAdd(&counters[head_word], 1u);
-        const u32 idx = uni(v);
-        lane0_guard();
-        if (idx >= nz) break;
+    for (u32 idx; dequeue(counters, head_word, nz, lane, idx); ) {
         const u32 e = uni(list[idx]);
         const zpk_decode_desc d = desc[e];
         const u8* in = uni_ptr(src + d.src_offset);
@@ -688,6 +582,16 @@ __global__ __launch_bounds__(256) void k_hash(const u8* __restrict__ src, const 
 #define ZPK_PJ_CHUNK_BLOCKS 512u                   // lz4_pj.h: blocks per chunk = 32 MiB of output, 128 MiB of byte references (the Infinity Cache holds 256)
 #endif
 #define ZPK_PJ_MAX_CHUNKS 64u
+// One device buffer the codec owns (pointer + capacity in bytes).  grow() enlarges it; every one is a member of zpk_codec and is
+// listed in zpk_codec::bufs, which is what zpk_codec_destroy frees.
+struct DevBufBase { void* p = nullptr; u64 cap = 0; };
+template <class T> struct DevBuf : DevBufBase {
+    operator T*() const { return (T*)p; }
+    template <class U> explicit operator U*() const { return (U*)p; }
+};
+// A second stream beside the batch's own (created on first use) with the event pair that forks work onto it and joins it back
+struct SideStream { hipStream_t s = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+
 struct zpk_codec {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -697,40 +601,32 @@ struct zpk_codec {
     // take it only while they enqueue: batches on ONE stream are ordered by the stream; a codec must not be driven
     // from two streams at once (create one codec per stream — contexts are cheap).
     pthread_mutex_t mu;
-    u32* d_counters = nullptr;
-    u32* d_lists = nullptr;      u64 list_cap = 0;
-    u8*  d_lit = nullptr;        u64 lit_cap = 0;
+    DevBuf<u32> d_counters;                      // N_COUNTERS words (zpk_layout.h)
+    DevBuf<u32> d_lists;                         // N_LIST_SLOTS work lists (zpk_layout.h)
+    DevBuf<u8>  d_lit;
     // host-API staging
-    u8*  d_src = nullptr;        u64 src_cap = 0;
+    DevBuf<u8>  d_src;
     u8*  h_pin[2] = {nullptr, nullptr};          // pinned staging of the host-pointer paths (ZPK_PIN_CHUNK bytes each), created on first use
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     hipStream_t s_up = nullptr, s_dn = nullptr;  // host-pointer decode pipeline: upload / download streams beside `stream` (created on first use)
-    hipStream_t s_side = nullptr;                // decode batches: the LZ4 kernel beside the Zstandard stages (low priority, created on first use)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    void* d_pj_blocks = nullptr; u64 pj_blocks_cap = 0; // large single LZ4 frames (lz4_pj.h): block table, sequence records, start masks, byte references, flags
-    void* d_pj_recs = nullptr;   u64 pj_recs_cap = 0;
-    void* d_pj_masks = nullptr;  u64 pj_masks_cap = 0;
-    void* d_pj_S = nullptr;      u64 pj_S_cap = 0;
-    u32*  d_pj_flags = nullptr;
+    SideStream side;                             // decode batches: the LZ4 kernels beside the Zstandard stages (low priority)
+    DevBuf<void> d_pj_blocks, d_pj_recs, d_pj_masks, d_pj_S;   // large single LZ4 frames (lz4_pj.h): block table, sequence records, start masks, byte references
+    DevBuf<u32>  d_pj_flags;                     // ... and flags (256 bytes)
     u8*   h_bigsrc = nullptr; u64 h_bigsrc_cap = 0;  // pinned: the compressed bytes of one large device-resident entry, for the host's block walk (zpk_codec_decode_big_device)
-    u8*   d_big1 = nullptr;                          // device: one descriptor + one result (the same call's one-wave fallback)
+    DevBuf<u8> d_big1;                               // device: one descriptor + one result (the same call's one-wave fallback)
     u32   zpj_last_err = 0;                          // developer: the flag word of the most recent large Zstandard frame (why it went to the one-wave decoder)
-    void* d_zpj_blocks = nullptr; u64 zpj_blocks_cap = 0; // large single Zstandard frames (zstd_pj.h): block table; work items, states, final histories; sequence positions
-    void* d_zpj_aux = nullptr;    u64 zpj_aux_cap = 0;
-    void* d_zpj_pos = nullptr;    u64 zpj_pos_cap = 0;
-    hipStream_t s_left = nullptr;                // decode batches: k_lz4_left (the LZ4 entries that are mostly runs) beside k_lz4_wave
-    hipEvent_t ev_lfork = nullptr, ev_ljoin = nullptr;
-    volatile u32* h_seen = nullptr;              // pinned: the work-list counts of an earlier device batch (what the next one probably holds)
+    DevBuf<void> d_zpj_blocks, d_zpj_aux, d_zpj_pos; // large single Zstandard frames (zstd_pj.h): block table; work items, states, final histories; sequence positions
+    SideStream left;                             // decode batches: k_lz4_left (the LZ4 entries that are mostly runs) beside k_lz4_wave
+    volatile SeenCounts* h_seen = nullptr;       // pinned: the work-list counts of an earlier device batch (what the next one probably holds)
     hipEvent_t pipe_ev[2 * 64] = {};             // per piece: uploaded, decoded
-    u8*  d_dst = nullptr;        u64 dst_cap = 0;
-    void* d_desc = nullptr;      u64 desc_cap = 0;
-    void* d_res = nullptr;       u64 res_cap = 0;
-    u64* d_dbg = nullptr;        u64 dbg_cap = 0;
-    u64* d_seq = nullptr;        u64 seq_cap = 0;      // encoder: sequence lists, one per workgroup
-    u8*  d_pack = nullptr;       u64 pack_cap = 0;     // K7: block sums + span index of the compaction
-    u8*  d_packed = nullptr;     u64 packed_cap = 0;   // host encode path: packed payload stream
-    u8*  d_packoff = nullptr;    u64 packoff_cap = 0;  // host encode path: payload offsets
-    u8*  d_xpart = nullptr;      u64 xpart_cap = 0;    // host encode path, split entries: span list | 64 bytes of XXH3 partial sums per 1 KiB block | hashes
+    DevBuf<u8>  d_dst;
+    DevBuf<void> d_desc, d_res;
+    DevBuf<u64> d_dbg;
+    DevBuf<u64> d_seq;                                 // encoder: sequence lists, one per workgroup
+    DevBuf<u8>  d_pack;                                // K7: block sums + span index of the compaction
+    DevBuf<u8>  d_packed;                              // host encode path: packed payload stream
+    DevBuf<u8>  d_packoff;                             // host encode path: payload offsets
+    DevBuf<u8>  d_xpart;                               // host encode path, split entries: span list | 64 bytes of XXH3 partial sums per 1 KiB block | hashes
     u64  enc_order_min = 4608;                         // ... and encode batches their ticket queue (the encoder's resident waves: 18 per CU)
     int  order_fast_last = 1;                          // ZPK_OPT_ORDER_FAST_LAST: a batch of one size class runs its incompressible entries last
     u64  order_min = 8192;                             // ZPK_OPT_ORDER_MIN: decode batches of at least this many entries run their work lists largest entries first
@@ -738,8 +634,8 @@ struct zpk_codec {
     hipEvent_t pj_ev[ZPK_PJ_MAX_CHUNKS] = {};           // lz4_pj.h: one event behind every chunk of a large LZ4 frame (its bytes may go home)
     u32  big_last[2] = {0, 0};                         // host decode path, most recent call: entries decoded frame-parallel, their frames
     u64  enc_split_min = ZPK_ENC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_ENC_SPLIT_MIN: entries of at least this many bytes are written as a sequence of frames
-    u64* d_zarena = nullptr;     u64 zarena_cap = 0;   // decoder: pre-decoded Zstandard sequences, laid out like dst (zstd_fse4.h)
-    u32* d_zstate = nullptr;     u64 zstate_cap = 0;   // decoder: per entry, 1 = its sequences are in the arena
+    DevBuf<u64> d_zarena;                              // decoder: pre-decoded Zstandard sequences, laid out like dst (zstd_fse4.h)
+    DevBuf<u32> d_zstate;                              // decoder: per entry, 1 = its sequences are in the arena
     int lz4_hint = -1;           // host path: does the batch hold an LZ4 entry?  -1 = unknown (device path)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t kev[ZPK_K_COUNT][2] = {};
@@ -753,6 +649,9 @@ struct zpk_codec {
     u32 host_totals[N_COUNTERS] = {};
     int totals_valid = 0;
     char err[256] = {0};
+    DevBufBase* const bufs[24] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_big1,
+                                   &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
+                                   &d_xpart, &d_zarena, &d_zstate };
 };
 
 struct CodecLock {
@@ -766,21 +665,22 @@ struct CodecLock {
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     snprintf((c)->err, sizeof((c)->err), "%s: %s", #call, hipGetErrorString(e_)); return ZPK_E_LAUNCH; } } while (0)
 
-static int grow(zpk_codec* c, void** p, u64* cap, u64 need)
+static void release(DevBufBase& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+static int grow(zpk_codec* c, DevBufBase& b, u64 need)
 {
-    if (need <= *cap) return ZPK_OK;
+    if (need <= b.cap) return ZPK_OK;
     // the buffer may still be in use by work enqueued earlier on the codec's stream or the caller's
-    if (*p) { (void)hipDeviceSynchronize(); (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    if (b.p) { (void)hipDeviceSynchronize(); release(b); }
     u64 want = need + need / 4 + 4096;
-    if (hipMalloc(p, want) != hipSuccess) {
+    if (hipMalloc(&b.p, want) != hipSuccess) {
         (void)hipGetLastError();
         want = need + 256;                                                          // the slack was a convenience, not a need
-        if (hipMalloc(p, want) != hipSuccess) {
+        if (hipMalloc(&b.p, want) != hipSuccess) {
             (void)hipGetLastError();
             snprintf(c->err, sizeof(c->err), "hipMalloc(%llu) failed", (unsigned long long)want); return ZPK_E_NOMEM;
         }
     }
-    *cap = want;
+    b.cap = want;
     return ZPK_OK;
 }
 
@@ -816,7 +716,7 @@ int zpk_codec_create(zpk_codec** out, int device)
         pthread_mutex_init(&c->mu, &at); pthread_mutexattr_destroy(&at);
     }
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void**)&c->d_counters, N_COUNTERS * sizeof(u32)) != hipSuccess ||
+        hipMalloc(&c->d_counters.p, N_COUNTERS * sizeof(u32)) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
         zpk_codec_destroy(c);
         return ZPK_E_NO_DEVICE;
@@ -830,26 +730,21 @@ void zpk_codec_destroy(zpk_codec* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    (void)hipFree(c->d_counters); (void)hipFree(c->d_lists); (void)hipFree(c->d_lit);
-    (void)hipFree(c->d_src); (void)hipFree(c->d_dst); (void)hipFree(c->d_desc); (void)hipFree(c->d_res);
+    for (DevBufBase* b : c->bufs) release(*b);
     for (int k = 0; k < 2; k++) { if (c->h_pin[k]) (void)hipHostFree(c->h_pin[k]); if (c->pin_ev[k]) (void)hipEventDestroy(c->pin_ev[k]); }
     if (c->piece_counters) (void)hipHostFree(c->piece_counters);
     if (c->h_pj) (void)hipHostFree(c->h_pj);
     if (c->h_seen) (void)hipHostFree((void*)c->h_seen);
-    if (c->s_side) (void)hipStreamDestroy(c->s_side);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (u32 k = 0; k < ZPK_PJ_MAX_CHUNKS; k++) if (c->pj_ev[k]) (void)hipEventDestroy(c->pj_ev[k]);
-    (void)hipFree(c->d_zpj_blocks); (void)hipFree(c->d_zpj_aux); (void)hipFree(c->d_zpj_pos); (void)hipFree(c->d_big1);
     if (c->h_bigsrc) (void)hipHostFree(c->h_bigsrc);
-    (void)hipFree(c->d_pj_blocks); (void)hipFree(c->d_pj_recs); (void)hipFree(c->d_pj_masks); (void)hipFree(c->d_pj_S); (void)hipFree(c->d_pj_flags);
-    if (c->s_left) (void)hipStreamDestroy(c->s_left);
-    if (c->ev_lfork) (void)hipEventDestroy(c->ev_lfork);
-    if (c->ev_ljoin) (void)hipEventDestroy(c->ev_ljoin);
+    for (SideStream* x : { &c->side, &c->left }) {
+        if (x->s) (void)hipStreamDestroy(x->s);
+        if (x->fork) (void)hipEventDestroy(x->fork);
+        if (x->join) (void)hipEventDestroy(x->join);
+    }
+    for (u32 k = 0; k < ZPK_PJ_MAX_CHUNKS; k++) if (c->pj_ev[k]) (void)hipEventDestroy(c->pj_ev[k]);
     if (c->s_up) (void)hipStreamDestroy(c->s_up);
     if (c->s_dn) (void)hipStreamDestroy(c->s_dn);
     for (int k = 0; k < 2 * 64; k++) if (c->pipe_ev[k]) (void)hipEventDestroy(c->pipe_ev[k]);
-    (void)hipFree(c->d_dbg); (void)hipFree(c->d_seq); (void)hipFree(c->d_zarena); (void)hipFree(c->d_zstate); (void)hipFree(c->d_pack); (void)hipFree(c->d_packed); (void)hipFree(c->d_packoff); (void)hipFree(c->d_xpart);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < ZPK_K_COUNT; i++) for (int j = 0; j < 2; j++) if (c->kev[i][j]) (void)hipEventDestroy(c->kev[i][j]);
@@ -870,9 +765,7 @@ void zpk_codec_reset(zpk_codec* c)
     // a context keeps its grown staging between batches (the next batch of that size starts at once); a reset gives the large pieces
     // back — a process that holds many readers can bound what each one retains (zpack_reset_reader_dctx / zpack_reset_writer_cctx)
     const u64 keep = 64ull << 20;
-    void** bufs[] = { (void**)&c->d_src, (void**)&c->d_dst, (void**)&c->d_zarena, (void**)&c->d_lit };
-    u64* caps[] = { &c->src_cap, &c->dst_cap, &c->zarena_cap, &c->lit_cap };
-    for (int i = 0; i < 5; i++) if (*bufs[i] && *caps[i] > keep) { (void)hipFree(*bufs[i]); *bufs[i] = nullptr; *caps[i] = 0; }
+    for (DevBufBase* b : { (DevBufBase*)&c->d_src, (DevBufBase*)&c->d_dst, (DevBufBase*)&c->d_zarena, (DevBufBase*)&c->d_lit }) if (b->cap > keep) release(*b);
 }
 const char* zpk_codec_last_error(const zpk_codec* c) { return c ? c->err : "no codec"; }
 int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
@@ -894,7 +787,7 @@ static int xxh3_spans_launch(zpk_codec* c, const u8* base, const zpk_span* h_spa
     if (nspans > 0x7FFFFFFFull) return ZPK_E_INVALID;
     const u64 span_bytes = (nspans * sizeof(zpk_span) + 255) & ~255ull, part_bytes = part_blocks * 64;
     int rc;
-    if ((rc = grow(c, (void**)&c->d_xpart, &c->xpart_cap, span_bytes + part_bytes + nspans * 8 + 64))) return rc;
+    if ((rc = grow(c, c->d_xpart, span_bytes + part_bytes + nspans * 8 + 64))) return rc;
     zpk_span* d_spans = (zpk_span*)c->d_xpart;
     u64* d_part = (u64*)(c->d_xpart + span_bytes);
     u64* d_hash = (u64*)(c->d_xpart + span_bytes + part_bytes);
@@ -908,6 +801,25 @@ static int xxh3_spans_launch(zpk_codec* c, const u8* base, const zpk_span* h_spa
 }
 static inline u64 xxh3_span_blocks(u64 len) { return (((len - 1) >> 10) + XS_GROUP - 1) / XS_GROUP * XS_GROUP; }   // partial-sum slots of one span
 
+// Fork: work enqueued on x.s from here on runs beside `from`, behind everything `from` holds now.  The stream (low_priority: at
+// the device's lowest) and the two events are created on first use; false = no second stream, the caller stays on `from`.
+static bool fork_stream(SideStream& x, hipStream_t from, bool low_priority)
+{
+    if (!x.s) {
+        int lo_prio = 0, hi_prio = 0;
+        if (low_priority) (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
+        if ((low_priority ? hipStreamCreateWithPriority(&x.s, hipStreamNonBlocking, lo_prio) : hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking)) != hipSuccess) x.s = nullptr;
+    }
+    if (!x.fork && hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess) x.fork = nullptr;
+    if (!x.join && hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess) x.join = nullptr;
+    return x.s && x.fork && x.join && hipEventRecord(x.fork, from) == hipSuccess && hipStreamWaitEvent(x.s, x.fork, 0) == hipSuccess;
+}
+// Join: `into` goes on behind what x.s holds; when that cannot be enqueued the host waits for x.s instead.
+static void join_stream(SideStream& x, hipStream_t into)
+{
+    if (hipEventRecord(x.join, x.s) != hipSuccess || hipStreamWaitEvent(into, x.join, 0) != hipSuccess) (void)hipStreamSynchronize(x.s);
+}
+
 static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* read_lo, const u8* read_hi,
                          const zpk_decode_desc* desc, u64 n, u8* dst, u64 dst_size, zpk_decode_result* res, hipStream_t st)
 {
@@ -915,18 +827,19 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;               // one workgroup per LZ4 entry: the grid's x limit
     c->totals_valid = 0;                                        // (the pipeline sets it again once it has summed its pieces)
     int rc;
-    if ((rc = grow(c, (void**)&c->d_lists, &c->list_cap, N_LISTS_ALLOC * n * sizeof(u32)))) return rc;
-    const u64 stride = c->list_cap / (N_LISTS_ALLOC * sizeof(u32));
-    u32* const retry_lz4 = c->d_lists + (u64)N_LISTS * stride;
-    u32* const retry_zstd = c->d_lists + (u64)(N_LISTS + 1) * stride;
-    u32* const left_lz4 = c->d_lists + (u64)(N_LISTS + 2) * stride;
-    u32* const handed_lz4 = c->d_lists + (u64)S_LZ4_HANDED * stride;
+    if ((rc = grow(c, c->d_lists, N_LIST_SLOTS * n * sizeof(u32)))) return rc;
+    const u64 stride = c->d_lists.cap / (N_LIST_SLOTS * sizeof(u32));
+    auto list_at = [&](int slot) { return c->d_lists + (u64)slot * stride; };
+    u32* const retry_lz4 = list_at(S_RETRY_LZ4);
+    u32* const retry_zstd = list_at(S_RETRY_ZSTD);
+    u32* const left_lz4 = list_at(S_LZ4_RUNS);
+    u32* const handed_lz4 = list_at(S_LZ4_HANDED);
     u32 wd_scale = 1; (void)wd_scale;
     ZPK_DEV(static const int wd_env = getenv("ZPK_WD_SCALE") ? atoi(getenv("ZPK_WD_SCALE")) : 1; wd_scale = (u32)wd_env;)
     int skip = 0; (void)skip;
 #ifdef ZPK_DEVELOPER
     static const int want_dbg = getenv("ZPK_DEBUG_TIMING") ? atoi(getenv("ZPK_DEBUG_TIMING")) : 0;
-    if (want_dbg) { if ((rc = grow(c, (void**)&c->d_dbg, &c->dbg_cap, n * 128))) return rc; }
+    if (want_dbg) { if ((rc = grow(c, c->d_dbg, n * 128))) return rc; }
     static const int trace = getenv("ZPK_TRACE") ? atoi(getenv("ZPK_TRACE")) : 0;
     static const int skip_env = getenv("ZPK_SKIP") ? atoi(getenv("ZPK_SKIP")) : 0;      // bitmask: 1 stored, 2 lz4, 4 zstd
     skip = skip_env;
@@ -938,7 +851,7 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     const u32 zstd_grid = (u32)(n < ZSTD_GRID_MAX ? n : ZSTD_GRID_MAX);
     const u32 exec_grid = (u32)(n < ZSTD_EXEC_GRID_MAX ? n : ZSTD_EXEC_GRID_MAX);
     const bool maybe_zstd = c->zstd_hint != 0;                  // the host path knows its methods; device batches may hold any
-    if (maybe_zstd && (rc = grow(c, (void**)&c->d_lit, &c->lit_cap, (u64)(exec_grid > zstd_grid ? exec_grid : zstd_grid) * ZSTD_LIT_SCRATCH))) return rc;
+    if (maybe_zstd && (rc = grow(c, c->d_lit, (u64)(exec_grid > zstd_grid ? exec_grid : zstd_grid) * ZSTD_LIT_SCRATCH))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), st));
     ZPK_TRACE_STEP("memset");
 #define ZPK_KEV(k, j) do { if (c->profiling) (void)hipEventRecord(c->kev[k][j], st); } while (0)
@@ -946,22 +859,22 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     hipLaunchKernelGGL(k_classify, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, src, desc, n, src_size, dst_size, res,
                        c->d_lists, stride, c->d_counters);
     // largest entries first (see k_order_count); batches that fit the resident waves in one round have nothing to order
-    const u32* zstd_list = c->d_lists + L_ZSTD * stride;
-    const u32* lz4_list = c->d_lists + L_LZ4 * stride;
+    const u32* zstd_list = list_at(S_ZSTD);
+    const u32* lz4_list = list_at(S_LZ4);
     int gen_slot = S_LZ4_GEN;                                   // the LZ4 entries that are not plain frames
     if (n >= c->order_min) {
         const dim3 og((u32)((n + 255) / 256), N_ORDERED);
         hipLaunchKernelGGL(k_order_count, og, dim3(256), 0, st, desc, (const u32*)c->d_lists, stride, c->d_counters, c->order_fast_last);
         hipLaunchKernelGGL(k_order_fill, og, dim3(256), 0, st, desc, (const u32*)c->d_lists, stride, c->d_lists, c->d_counters, c->order_fast_last);
-        zstd_list = c->d_lists + (u64)(N_LISTS + 3) * stride; lz4_list = c->d_lists + (u64)(N_LISTS + 4) * stride;
+        zstd_list = list_at(S_ZSTD_ORDERED); lz4_list = list_at(S_LZ4_ORDERED);
         gen_slot = S_LZ4_GEN_ORDERED;
     }
-    const u32* const gen_list = c->d_lists + (u64)gen_slot * stride;
+    const u32* const gen_list = list_at(gen_slot);
     ZPK_KEV(ZPK_K_CLASSIFY, 1);
     ZPK_TRACE_STEP("k_classify");
     const u32 wgrid = (u32)((n + 3) / 4);          // one wave per list slot
     ZPK_KEV(ZPK_K_STORED, 0);
-    if (!(skip & 1)) hipLaunchKernelGGL(k_stored, dim3(wgrid), dim3(256), 0, st, src, desc, dst, res, c->d_lists + L_NONE * stride, c->d_counters);
+    if (!(skip & 1)) hipLaunchKernelGGL(k_stored, dim3(wgrid), dim3(256), 0, st, src, desc, dst, res, list_at(S_NONE), c->d_counters);
     ZPK_KEV(ZPK_K_STORED, 1);
     ZPK_TRACE_STEP("k_stored");
     // LZ4: one wave per work-list slot (lz4_wave.h).  A batch that may hold both methods runs the LZ4 kernels on a SIDE stream of
@@ -969,25 +882,17 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     // 16 workgroups per CU leave 3-8 KiB of LDS and most of the vector issue slots idle), so LZ4 waves fill what they leave.
     const bool maybe_lz4 = c->lz4_hint != 0;
     hipStream_t sl = st;
-#ifndef ZPK_NO_SIDE_STREAM
     // (measured, 125 000 mixed entries: 112.0 -> 90.9 ms per batch, the LZ4 kernel's 25 ms disappear inside the Zstandard stages, which
     // get 1-3 ms longer; a pure LZ4 batch — the Zstandard kernels find empty lists — is unchanged within noise: 618.4 vs 618.2 GiB/s.)
     // A device batch does not say which methods it holds, and a pure Zstandard batch must NOT take the side stream: k_lz4_wave is one
     // workgroup per entry, and 100 000 EMPTY workgroups trickling through at low priority beside the pre-decode stage cost it 15 ms
     // (71.9 -> 87.6 ms).  So the codec looks at the work-list counts of the batch BEFORE (copied to pinned memory behind every batch,
     // no synchronisation): both methods there, or nothing known yet -> side stream; a codec fed batches of one method stays on one stream.
-    if (!c->h_seen && hipHostMalloc((void**)&c->h_seen, 64, hipHostMallocDefault) == hipSuccess) { c->h_seen[L_NONE] = 0; c->h_seen[L_ZSTD] = 1; c->h_seen[L_LZ4] = 1; c->h_seen[8] = 1; c->h_seen[C_LZ4_GEN] = 1; }
-    const bool both_seen = c->zstd_hint >= 0 /* the host path knows */ || (c->h_seen && c->h_seen[L_ZSTD] != 0 && (c->h_seen[L_LZ4] != 0 || c->h_seen[C_LZ4_GEN] != 0));
-    if (maybe_lz4 && maybe_zstd && both_seen && !(skip & 6)) {
-        int lo_prio = 0, hi_prio = 0;
-        if (!c->s_side) { (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
-                          if (hipStreamCreateWithPriority(&c->s_side, hipStreamNonBlocking, lo_prio) != hipSuccess) c->s_side = nullptr; }
-        if (!c->ev_fork && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess) c->ev_fork = nullptr;
-        if (!c->ev_join && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) c->ev_join = nullptr;
-        if (c->s_side && c->ev_fork && c->ev_join && hipEventRecord(c->ev_fork, st) == hipSuccess &&
-            hipStreamWaitEvent(c->s_side, c->ev_fork, 0) == hipSuccess) sl = c->s_side;
+    if (!c->h_seen && hipHostMalloc((void**)&c->h_seen, 64, hipHostMallocDefault) == hipSuccess) {
+        c->h_seen->none = 0; c->h_seen->zstd = 1; c->h_seen->lz4 = 1; c->h_seen->lz4_gen = 1; c->h_seen->lz4_runs = 1;      // nothing known yet
     }
-#endif
+    const bool both_seen = c->zstd_hint >= 0 /* the host path knows */ || (c->h_seen && c->h_seen->zstd != 0 && (c->h_seen->lz4 != 0 || c->h_seen->lz4_gen != 0));
+    if (maybe_lz4 && maybe_zstd && both_seen && !(skip & 6) && fork_stream(c->side, st, true)) sl = c->side.s;
     auto launch_lz4 = [&]() {
         if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_LZ4][0], sl);
         if (!(skip & 2) && maybe_lz4) {
@@ -997,13 +902,7 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
             hipStream_t sx = sl;
             // (a small batch is latency, not throughput: no second stream; neither when the batch BEFORE had no such entry — then the launch
             // is an empty grid in front of k_lz4_wave, and a batch that does have some pays the serial stretch once)
-            if (n >= 4096 && c->h_seen && c->h_seen[8] != 0) {
-            if (!c->s_left && hipStreamCreateWithFlags(&c->s_left, hipStreamNonBlocking) != hipSuccess) c->s_left = nullptr;
-            if (!c->ev_lfork && hipEventCreateWithFlags(&c->ev_lfork, hipEventDisableTiming) != hipSuccess) c->ev_lfork = nullptr;
-            if (!c->ev_ljoin && hipEventCreateWithFlags(&c->ev_ljoin, hipEventDisableTiming) != hipSuccess) c->ev_ljoin = nullptr;
-            if (c->s_left && c->ev_lfork && c->ev_ljoin && hipEventRecord(c->ev_lfork, sl) == hipSuccess &&
-                hipStreamWaitEvent(c->s_left, c->ev_lfork, 0) == hipSuccess) sx = c->s_left;
-            }
+            if (n >= 4096 && c->h_seen && c->h_seen->lz4_runs != 0 && fork_stream(c->left, sl, false)) sx = c->left.s;
             hipLaunchKernelGGL(k_lz4_left, dim3((u32)(n < LZ4_LEFT_GRID_MAX ? n : LZ4_LEFT_GRID_MAX)), dim3(64), 0, sx, src, read_lo, read_hi, desc, dst, res,
                                (const u32*)left_lz4, c->d_counters, c->d_dbg, retry_lz4, wd_scale);
             // the hot kernel: plain frames only; whatever it does not finish cleanly is on its hand-over list
@@ -1019,11 +918,10 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
             // above — when the batch BEFORE had such entries, or nothing is known yet.  Otherwise the list is expected to be empty and
             // is left to k_lz4_retry below, so that archives of plain frames pay for no launch they do not need (a batch that does have
             // some then runs them on the small grid, once).
-            if (!c->h_seen || c->h_seen[C_LZ4_GEN] != 0)               // (the host-pointer paths do not bring the counts home: always launched there)
+            if (!c->h_seen || c->h_seen->lz4_gen != 0)               // (the host-pointer paths do not bring the counts home: always launched there)
                 hipLaunchKernelGGL(k_lz4_general, dim3((u32)(n < LZ4_GENERAL_GRID_MAX ? n : LZ4_GENERAL_GRID_MAX)), dim3(64), 0, sl, src, read_lo, read_hi,
                                    desc, dst, res, gen_list, c->d_counters, c->d_dbg, retry_lz4, wd_scale);
-            if (sx != sl && (hipEventRecord(c->ev_ljoin, sx) != hipSuccess || hipStreamWaitEvent(sl, c->ev_ljoin, 0) != hipSuccess))
-                (void)hipStreamSynchronize(sx);
+            if (sx != sl) join_stream(c->left, sl);
             // whatever is left: k_lz4_general's list if that was not launched, what k_lz4_wave handed over, and the entries whose decoder
             // ran out of its time budget (ZPK_WATCHDOG_RETRY_SCALE times the budget; a small grid that leaves at once when the lists
             // are empty — the normal case)
@@ -1041,8 +939,8 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     bool two_stage = maybe_zstd && dst_size >= 64;
     ZPK_DEV(static const int fused_only = getenv("ZPK_ZSTD_FUSED") ? atoi(getenv("ZPK_ZSTD_FUSED")) : 0; if (fused_only) two_stage = false;)
     c->fell_back_fused = 0;
-    if (two_stage && (grow(c, (void**)&c->d_zarena, &c->zarena_cap, dst_size + 64) != ZPK_OK ||
-                      grow(c, (void**)&c->d_zstate, &c->zstate_cap, 2 * n * sizeof(u32)) != ZPK_OK)) {
+    if (two_stage && (grow(c, c->d_zarena, dst_size + 64) != ZPK_OK ||
+                      grow(c, c->d_zstate, 2 * n * sizeof(u32)) != ZPK_OK)) {
         two_stage = false; c->fell_back_fused = 1;
         snprintf(c->err, sizeof(c->err), "note: no memory for the %llu-byte Zstandard sequence arena; this batch ran the fused decoder",
                  (unsigned long long)dst_size + 64);
@@ -1064,7 +962,7 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     if (!(skip & 4) && maybe_zstd)
         hipLaunchKernelGGL(k_zstd, dim3(zstd_grid), dim3(ZSTD_WG_THREADS), 0, st, src, desc, dst, res,
                        two_stage ? (const u32*)leftover : zstd_list, c->d_counters, c->d_lit, c->d_dbg,
-                       two_stage ? (int)C_LEFT_COUNT : (int)L_ZSTD, (int)(L_COUNT + L_ZSTD), retry_zstd, (int)C_RETRY_ZSTD, wd_scale);
+                       two_stage ? (int)C_ZSTD_LEFT : (int)C_ZSTD, (int)C_ZSTD_HEAD, retry_zstd, (int)C_RETRY_ZSTD, wd_scale);
     ZPK_KEV(ZPK_K_ZSTD, 1);
     ZPK_TRACE_STEP("k_zstd");
     // Entries whose decoder ran out of its time budget (a preempted or contended GPU, not the entry's fault) are decoded again
@@ -1072,17 +970,16 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     // when their list is empty (the normal case).
     if (!(skip & 4) && maybe_zstd)
         hipLaunchKernelGGL(k_zstd, dim3(zstd_grid < 128 ? zstd_grid : 128), dim3(ZSTD_WG_THREADS), 0, st, src, desc, dst, res,
-                           (const u32*)retry_zstd, c->d_counters, c->d_lit, c->d_dbg, (int)C_RETRY_ZSTD, (int)C_RETRY_HEAD,
+                           (const u32*)retry_zstd, c->d_counters, c->d_lit, c->d_dbg, (int)C_RETRY_ZSTD, (int)C_ZSTD_RETRY_HEAD,
                            (u32*)nullptr, 0, (u32)ZPK_WATCHDOG_RETRY_SCALE);
     if (sl != st) {                                 // the LZ4 kernels, beside the above; the batch is done when both streams are
         launch_lz4();
-        if (hipEventRecord(c->ev_join, sl) != hipSuccess || hipStreamWaitEvent(st, c->ev_join, 0) != hipSuccess) {
-            (void)hipStreamSynchronize(sl);
-        }
+        join_stream(c->side, st);
     }
     ZPK_TRACE_STEP("retry");
-    if (c->h_seen && c->zstd_hint < 0) (void)hipMemcpyAsync((void*)c->h_seen, c->d_counters, (N_LISTS + 1) * sizeof(u32), hipMemcpyDeviceToHost, st);      // (+ 1: C_LZ4_GEN, the LZ4 entries that are not plain frames)
-    if (c->h_seen) (void)hipMemcpyAsync((void*)(c->h_seen + 8), c->d_counters + C_LZ4_LEFT, sizeof(u32), hipMemcpyDeviceToHost, st);      // did this batch have LZ4 entries of runs?
+    // what this batch held, for the next one: none / zstd / lz4 / lz4_gen (adjacent counter words: zpk_layout.h) in one copy; did it have LZ4 entries of runs?
+    if (c->h_seen && c->zstd_hint < 0) (void)hipMemcpyAsync((void*)&c->h_seen->none, c->d_counters + C_NONE, 4 * sizeof(u32), hipMemcpyDeviceToHost, st);
+    if (c->h_seen) (void)hipMemcpyAsync((void*)&c->h_seen->lz4_runs, c->d_counters + C_LZ4_RUNS, sizeof(u32), hipMemcpyDeviceToHost, st);
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
 }
@@ -1110,7 +1007,7 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
         if ((r.status != 0 && r.status != 15) || r.produced >= desc[i].uncomp_size || desc[i].uncomp_size > desc[i].dst_capacity ||
             desc[i].comp_size == 0 /* :328: OK before anything is read */ || desc[i].method == ZPK_METHOD_NONE) continue;
         int rc;
-        if ((rc = grow(c, (void**)&c->d_xpart, &c->xpart_cap, 64))) return rc;
+        if ((rc = grow(c, c->d_xpart, 64))) return rc;
         const u64 tail = desc[i].uncomp_size - r.produced;
         u64 meta[3] = { hd[i].dst_offset, desc[i].uncomp_size, 0 };
         HIPCHK(c, hipMemcpyAsync(c->d_dst + hd[i].dst_offset + r.produced, dst_ptrs[i] + r.produced, tail, hipMemcpyHostToDevice, c->stream));
@@ -1309,9 +1206,9 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
                              const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results)
 {
     int rc;
-    if ((rc = grow(c, (void**)&c->d_src, &c->src_cap, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, (void**)&c->d_dst, &c->dst_cap, out_total + 16)) ||
-        (rc = grow(c, &c->d_desc, &c->desc_cap, n * sizeof(zpk_decode_desc))) ||
-        (rc = grow(c, &c->d_res, &c->res_cap, n * sizeof(zpk_decode_result)))) return rc;
+    if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
+        (rc = grow(c, c->d_desc, n * sizeof(zpk_decode_desc))) ||
+        (rc = grow(c, c->d_res, n * sizeof(zpk_decode_result)))) return rc;
     hipError_t e = hipSuccess;
     if (hi > lo) e = hipMemcpyAsync(c->d_src, image + lo, hi - lo, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_desc, hd, n * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
@@ -1392,9 +1289,9 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     }
     if (np < 3 || span_sum > (hi - lo) + (hi - lo) / 4 + (1u << 20)) return ZPK_OK;      // entries not in archive order: the spans would be uploaded many times over
     int rc;
-    if ((rc = grow(c, (void**)&c->d_src, &c->src_cap, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, (void**)&c->d_dst, &c->dst_cap, out_total + 16)) ||
-        (rc = grow(c, &c->d_desc, &c->desc_cap, n * sizeof(zpk_decode_desc))) ||
-        (rc = grow(c, &c->d_res, &c->res_cap, n * sizeof(zpk_decode_result))) || (rc = pin_ready(c))) return rc;
+    if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
+        (rc = grow(c, c->d_desc, n * sizeof(zpk_decode_desc))) ||
+        (rc = grow(c, c->d_res, n * sizeof(zpk_decode_result))) || (rc = pin_ready(c))) return rc;
     if (!c->s_up && hipStreamCreateWithFlags(&c->s_up, hipStreamNonBlocking) != hipSuccess) { c->s_up = nullptr; return ZPK_OK; }
     if (!c->s_dn && hipStreamCreateWithFlags(&c->s_dn, hipStreamNonBlocking) != hipSuccess) { c->s_dn = nullptr; return ZPK_OK; }
     for (int k = 0; k < 2 * np; k++)
@@ -1506,10 +1403,10 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
     // the XXH3 of the output runs BESIDE all this on its own stream, section by section as the chunks become final (xxh3_span.h: the
     // partial sums of a section's blocks side by side, then the one-wave chain over them — 14 ms for 256 MiB, as long as everything else
     // together, which is why it must not come behind)
-    if (!c->s_left && hipStreamCreateWithFlags(&c->s_left, hipStreamNonBlocking) != hipSuccess) { c->s_left = nullptr; return ZPK_OK; }
-    hipStream_t sh = c->s_left;
+    if (!c->left.s && hipStreamCreateWithFlags(&c->left.s, hipStreamNonBlocking) != hipSuccess) { c->left.s = nullptr; return ZPK_OK; }
+    hipStream_t sh = c->left.s;
     const u64 part_blocks = xxh3_span_blocks(n), ngroups = part_blocks / XS_GROUP;
-    if ((rc = grow(c, (void**)&c->d_xpart, &c->xpart_cap, 256 + part_blocks * 64 + 256))) return rc;
+    if ((rc = grow(c, c->d_xpart, 256 + part_blocks * 64 + 256))) return rc;
     zpk_span* const d_span = (zpk_span*)c->d_xpart;
     u64* const d_part = (u64*)(c->d_xpart + 256);
     u64* const d_hash = (u64*)(c->d_xpart + 256 + part_blocks * 64);
@@ -1604,10 +1501,10 @@ static int decode_big_lz4_single(zpk_codec* c, const u8* archive, const zpk_deco
     const u64 nb = blocks.size(), n = d.uncomp_size;
     const u64 total_recs = (u64)blocks.back().rec_base + ((blocks.back().comp_size >> 31) ? 0 : (blocks.back().comp_size / 3 + 2));
     int rc;
-    if ((rc = grow(c, (void**)&c->d_src, &c->src_cap, d.comp_size + ZPK_SRC_SLACK)) || (!d_out && (rc = grow(c, (void**)&c->d_dst, &c->dst_cap, n + 16))) ||
-        (rc = grow(c, &c->d_pj_blocks, &c->pj_blocks_cap, nb * sizeof(PjBlock))) || (rc = grow(c, &c->d_pj_recs, &c->pj_recs_cap, (total_recs + 64) * 8)) ||
-        (rc = grow(c, &c->d_pj_masks, &c->pj_masks_cap, nb * (PJ_BLOCK / 8))) || (rc = grow(c, &c->d_pj_S, &c->pj_S_cap, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }     // no memory for the scratch: the one-wave decoder
-    if (!c->d_pj_flags && hipMalloc((void**)&c->d_pj_flags, 256) != hipSuccess) { c->d_pj_flags = nullptr; (void)hipGetLastError(); return ZPK_OK; }
+    if ((rc = grow(c, c->d_src, d.comp_size + ZPK_SRC_SLACK)) || (!d_out && (rc = grow(c, c->d_dst, n + 16))) ||
+        (rc = grow(c, c->d_pj_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->d_pj_recs, (total_recs + 64) * 8)) ||
+        (rc = grow(c, c->d_pj_masks, nb * (PJ_BLOCK / 8))) || (rc = grow(c, c->d_pj_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }     // no memory for the scratch: the one-wave decoder
+    if (!c->d_pj_flags && hipMalloc(&c->d_pj_flags.p, 256) != hipSuccess) { c->d_pj_flags.p = nullptr; (void)hipGetLastError(); return ZPK_OK; }
     hipStream_t st = c->stream;
     hipError_t e = d_archive ? hipMemcpyAsync(c->d_src, d_archive + d.src_offset, d.comp_size, hipMemcpyDeviceToDevice, st)
                              : hipMemcpyAsync(c->d_src, archive + d.src_offset, d.comp_size, hipMemcpyHostToDevice, st);
@@ -1656,16 +1553,16 @@ static int decode_big_zstd_single(zpk_codec* c, const u8* archive, const zpk_dec
     const u64 aux_desc = 0, aux_list = (nb * sizeof(zpk_decode_desc) + 255) & ~255ull, aux_state = aux_list + ((nb * 4 + 255) & ~255ull),
               aux_rep = aux_state + ((nb * 4 + 255) & ~255ull), aux_size = aux_rep + nb * 12 + 256;
     int rc;
-    if ((rc = grow(c, (void**)&c->d_src, &c->src_cap, arena_off + lit_total + ZPK_SRC_SLACK)) || (!d_out && (rc = grow(c, (void**)&c->d_dst, &c->dst_cap, n + 16))) ||
-        (rc = grow(c, &c->d_pj_blocks, &c->pj_blocks_cap, nb * sizeof(PjBlock))) || (rc = grow(c, &c->d_zpj_blocks, &c->zpj_blocks_cap, nb * sizeof(ZpjBlock))) ||
-        (rc = grow(c, &c->d_zpj_aux, &c->zpj_aux_cap, aux_size)) || (rc = grow(c, &c->d_pj_recs, &c->pj_recs_cap, (slots + 64) * 8)) ||
-        (rc = grow(c, &c->d_zpj_pos, &c->zpj_pos_cap, (slots + 64) * 8)) || (rc = grow(c, &c->d_pj_masks, &c->pj_masks_cap, nb * (ZPJ_BLOCK / 8))) ||
-        (rc = grow(c, &c->d_pj_S, &c->pj_S_cap, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }        // no memory for the scratch: the one-wave decoder
-    if (!c->d_pj_flags && hipMalloc((void**)&c->d_pj_flags, 256) != hipSuccess) { c->d_pj_flags = nullptr; (void)hipGetLastError(); return ZPK_OK; }
+    if ((rc = grow(c, c->d_src, arena_off + lit_total + ZPK_SRC_SLACK)) || (!d_out && (rc = grow(c, c->d_dst, n + 16))) ||
+        (rc = grow(c, c->d_pj_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->d_zpj_blocks, nb * sizeof(ZpjBlock))) ||
+        (rc = grow(c, c->d_zpj_aux, aux_size)) || (rc = grow(c, c->d_pj_recs, (slots + 64) * 8)) ||
+        (rc = grow(c, c->d_zpj_pos, (slots + 64) * 8)) || (rc = grow(c, c->d_pj_masks, nb * (ZPJ_BLOCK / 8))) ||
+        (rc = grow(c, c->d_pj_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }        // no memory for the scratch: the one-wave decoder
+    if (!c->d_pj_flags && hipMalloc(&c->d_pj_flags.p, 256) != hipSuccess) { c->d_pj_flags.p = nullptr; (void)hipGetLastError(); return ZPK_OK; }
     hipStream_t st = c->stream;
     u8* const aux = (u8*)c->d_zpj_aux;
-    u32 hflags[64]; memset(hflags, 0, sizeof(hflags));
-    hflags[ZPJ_CNT + ZF_COUNT_WORD] = (u32)list.size();
+    u32 hflags[ZPJ_FLAG_WORDS]; memset(hflags, 0, sizeof(hflags));
+    hflags[ZPJ_CNT + C_ZSTD] = (u32)list.size();
     std::vector<PjBlock> hb(nb);
     memset(hb.data(), 0, nb * sizeof(PjBlock));
     hipError_t e = d_archive ? hipMemcpyAsync(c->d_src, d_archive + d.src_offset, d.comp_size, hipMemcpyDeviceToDevice, st)
@@ -1739,9 +1636,9 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     }
     coff[ng] = ct; ooff[ng] = ot;
     int rc;
-    if ((rc = grow(c, (void**)&c->d_src, &c->src_cap, ct + ZPK_SRC_SLACK)) || (rc = grow(c, (void**)&c->d_dst, &c->dst_cap, ot + 16)) ||
-        (rc = grow(c, &c->d_desc, &c->desc_cap, nsub * sizeof(zpk_decode_desc))) ||
-        (rc = grow(c, &c->d_res, &c->res_cap, nsub * sizeof(zpk_decode_result)))) return rc;
+    if ((rc = grow(c, c->d_src, ct + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, ot + 16)) ||
+        (rc = grow(c, c->d_desc, nsub * sizeof(zpk_decode_desc))) ||
+        (rc = grow(c, c->d_res, nsub * sizeof(zpk_decode_result)))) return rc;
     hipError_t e = hipSuccess;
     if (ng == 1) e = hipMemcpyAsync(c->d_src, cptr[0], desc[be[g0].idx].comp_size, hipMemcpyHostToDevice, c->stream);
     else {
@@ -2009,7 +1906,7 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
         }
     }
     // ---- the one-wave kernels (every verdict is theirs) ----
-    if (!c->d_big1 && hipMalloc((void**)&c->d_big1, 512) != hipSuccess) { c->d_big1 = nullptr; (void)hipGetLastError(); return ZPK_E_NOMEM; }
+    if (!c->d_big1 && hipMalloc(&c->d_big1.p, 512) != hipSuccess) { c->d_big1.p = nullptr; (void)hipGetLastError(); return ZPK_E_NOMEM; }
     zpk_decode_desc* const dd = (zpk_decode_desc*)c->d_big1;
     zpk_decode_result* const dr = (zpk_decode_result*)(c->d_big1 + 256);
     HIPCHK(c, hipMemcpyAsync(dd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
@@ -2041,7 +1938,7 @@ int zpk_codec_hash_host(zpk_codec* c, const uint8_t* data, uint64_t size, uint64
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = grow(c, (void**)&c->d_src, &c->src_cap, size + 16)) || (rc = grow(c, &c->d_res, &c->res_cap, 64))) return rc;
+    if ((rc = grow(c, c->d_src, size + 16)) || (rc = grow(c, c->d_res, 64))) return rc;
     u64 meta[3] = { 0, size, 0 };
     if (size) HIPCHK(c, hipMemcpyAsync(c->d_src, data, size, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_res, meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
@@ -2055,7 +1952,7 @@ int zpk_codec_hash_host(zpk_codec* c, const uint8_t* data, uint64_t size, uint64
 // debugging: copy the per-entry phase timing words (8 x u64 per entry; needs ZPK_DEBUG_TIMING=1) to the host
 int zpk_codec_debug_read(zpk_codec* c, void* host, uint64_t bytes)
 {
-    if (!c || !c->d_dbg || bytes > c->dbg_cap) return ZPK_E_INVALID;      // d_dbg exists only in a -DZPK_DEVELOPER build
+    if (!c || !c->d_dbg || bytes > c->d_dbg.cap) return ZPK_E_INVALID;      // d_dbg exists only in a -DZPK_DEVELOPER build
     HIPCHK(c, hipDeviceSynchronize());
     HIPCHK(c, hipMemcpy(host, c->d_dbg, bytes, hipMemcpyDeviceToHost));
     return ZPK_OK;
@@ -2071,10 +1968,10 @@ int zpk_codec_decode_stats(zpk_codec* c, uint32_t out[8])
     u32 h[N_COUNTERS];
     HIPCHK(c, hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
     if (c->totals_valid) memcpy(h, c->host_totals, sizeof(h));          // a pipelined host batch: the sum over its launches
-    out[0] = h[L_NONE]; out[1] = h[L_ZSTD]; out[2] = h[L_LZ4] + h[C_LZ4_LEFT] + h[C_LZ4_GEN] /* the three LZ4 lists */; out[3] = h[C_ZSTD_TWO_STAGE]; out[4] = h[C_ZSTD_FUSED];
-    out[5] = h[ZF_WATCHDOG_WORD]; out[6] = h[ZF_WATCHDOG_WORD + 1]; out[7] = h[13];
+    out[0] = h[C_NONE]; out[1] = h[C_ZSTD]; out[2] = h[C_LZ4] + h[C_LZ4_RUNS] + h[C_LZ4_GEN] /* the three LZ4 lists */; out[3] = h[C_ZSTD_TWO_STAGE]; out[4] = h[C_ZSTD_FUSED];
+    out[5] = h[C_FSE_WATCHDOG]; out[6] = h[C_FSE_BUDGET]; out[7] = h[C_FSE_MARKED];
     if (c->fell_back_fused) out[7] |= 0x80000000u;          // the batch could not get its sequence arena: fused decoder only
-    ZPK_DEV(if (getenv("ZPK_TRACE")) fprintf(stderr, "[zpk] fse marked %u, pass-0 failures %u, last failure status/rc %08x\n", h[13], h[14], h[15]);)
+    ZPK_DEV(if (getenv("ZPK_TRACE")) fprintf(stderr, "[zpk] fse marked %u, pass-0 failures %u, last failure status/rc %08x\n", h[C_FSE_MARKED], h[C_EXEC_FAILED], h[C_EXEC_LAST_RC]);)
     return ZPK_OK;
 }
 
@@ -2091,7 +1988,7 @@ int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16])
     if (c->totals_valid) memcpy(h, c->host_totals, sizeof(h));
     memset(out, 0, 16 * sizeof(uint32_t));
     out[0] = h[C_RETRY_LZ4]; out[1] = h[C_RETRY_ZSTD];
-    out[2] = 0; out[3] = h[C_LZ4_LEFT]; out[4] = 0;      // [3]: LZ4 entries that are mostly runs, decoded by k_lz4_left (the two-stage path of round 4 is gone: [2], [4] read 0)
+    out[2] = 0; out[3] = h[C_LZ4_RUNS]; out[4] = 0;      // [3]: LZ4 entries that are mostly runs, decoded by k_lz4_left (the two-stage path of round 4 is gone: [2], [4] read 0)
     out[5] = c->big_last[0]; out[6] = c->big_last[1];
     out[7] = c->zpj_last_err;                              // why the most recent large Zstandard frame was NOT finished block-parallel (0: it was, or none came)
     out[8] = h[C_LZ4_HANDED];                              // LZ4 entries k_lz4_wave handed to the general decoder without judging them
@@ -2105,7 +2002,7 @@ int zpk_codec_debug_fetch(zpk_codec* c, int what, uint64_t offset, void* host, u
 {
     if (!c || !host) return ZPK_E_INVALID;
     const u8* base = what == 0 ? (const u8*)c->d_zarena : (const u8*)c->d_zstate;
-    const u64 cap = what == 0 ? c->zarena_cap : c->zstate_cap;
+    const u64 cap = what == 0 ? c->d_zarena.cap : c->d_zstate.cap;
     if (!base || offset > cap || bytes > cap - offset) return ZPK_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());

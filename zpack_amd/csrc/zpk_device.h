@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/zpack_codec.h"
+#include "zpk_layout.h"
 
 namespace zpk {
 
@@ -49,7 +50,20 @@ template <typename T> __device__ __forceinline__ T* uni_ptr(T* p) { return (T*)u
 // then runs per-lane-class and a following readfirstlane no longer sees lane 0 (the wave re-processes
 // stale data forever).  Every lane-0 region whose result is broadcast starts behind lane0_guard(): the
 // wave barrier is a convergent no-op, and LLVM never duplicates a block that holds one.
+// The loop this bit — the atomic dequeue of a persistent grid — is written ONCE, in dequeue() below: kernels call that.
 __device__ __forceinline__ void lane0_guard() { __builtin_amdgcn_wave_barrier(); }
+
+// One wave of a persistent grid takes the next slot of a work list of `count` slots: lane 0 bumps counters[head_word], every lane
+// gets the slot in `idx` (an SGPR).  false: the list is drained.
+__device__ __forceinline__ bool dequeue(u32* __restrict__ counters, int head_word, u32 count, int lane, u32& idx)
+{
+    lane0_guard();
+    u32 v = 0;
+    if (lane == 0) v = atomicAdd(&counters[head_word], 1u);
+    idx = uni(v);
+    lane0_guard();
+    return idx < count;
+}
 
 // Address spaces.  A `const u8*` that went through readfirstlane (uni_ptr) or a pointer select is a
 // GENERIC pointer to the compiler, and every access through it becomes a FLAT instruction — an order of
@@ -127,12 +141,6 @@ __device__ __forceinline__ u64 shfl_xor64(u64 v, int mask)
 // no LDS traffic — a ds_bpermute ladder costs ~5x the instructions
 __device__ __forceinline__ u32 wave_scan_add(u32 v)
 {
-#ifdef ZPK_NO_DPP
-    const int lane_ = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { u32 y = (u32)__shfl_up((int)v, d, 64); if (lane_ >= d) v += y; }
-    return v;
-#endif
     v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
     v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
     v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4

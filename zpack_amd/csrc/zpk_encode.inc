@@ -226,7 +226,6 @@ __device__ inline u32 lz4e_block(Lz4EncSharedT<HLOG>& sh, const u8* src, u32 n, 
         u32 l2 = C.l2; bool diff = C.diff;
         const u8* const cp = src + P.p - C.d;
         const u32 pp = P.p;
-#ifndef ENC_ABL_NOEXT       // developer ablation (instruction counters only; the output is wrong)
         // 32 bytes per memory round trip first (the wave waits for its longest match: eight bytes per trip made a 40-byte match
         // five dependent round trips for all 64 lanes), then 8, then single bytes up to the block's match limit
         while (!diff && pp + l2 + 32 <= mend) {
@@ -245,7 +244,6 @@ __device__ inline u32 lz4e_block(Lz4EncSharedT<HLOG>& sh, const u8* src, u32 n, 
             l2 += 8;
         }
         if (!diff && pp + l2 + 8 > mend) while (pp + l2 < mend && ld8(cp + l2) == ld8(src + pp + l2)) l2++;
-#endif
         return l2;
     };
     auto extend = [&](const Pos& P, const Cand& C, u32& len, u32& off) { const u32 l2 = extend_len(P, C); if (l2 > len) { len = l2; off = C.d; } };
@@ -257,7 +255,6 @@ __device__ inline u32 lz4e_block(Lz4EncSharedT<HLOG>& sh, const u8* src, u32 n, 
     // (extend_picked): the wave compares 1 KiB per round trip (16 bytes per lane, contiguous), the last bytes before the block's match
     // limit one byte per lane.  (Tried for every block: text lost 3 % to the extra code in the chain loop — it has few long matches.)
     auto step32 = [&](const Pos& P, Cand& C) {
-#ifndef ENC_ABL_NOEXT
         const bool more = C.ok && !C.diff && P.p + C.l2 + 32u <= mend;
         if (__ballot(more) == 0) return;
         if (more) {
@@ -270,14 +267,12 @@ __device__ inline u32 lz4e_block(Lz4EncSharedT<HLOG>& sh, const u8* src, u32 n, 
             else if (x3) { C.l2 += 24u + ((u32)(__ffsll((long long)x3) - 1) >> 3); C.diff = true; }
             else C.l2 += 32;
         }
-#endif
     };
     // the better of two candidates by what is known of them (an OPEN one is at least as long as its known part)
     auto take = [&](const Cand& C, u32& len, u32& off, bool& open) { if (C.ok && C.l2 > len) { len = C.l2; off = C.d; open = !C.diff; } };
     // the repeat-offset candidate wins unless the table's match is longer by two bytes or more (its sequence is about a byte cheaper)
     auto take_rep = [&](const Cand& C, u32& len, u32& off, bool& open) { if (C.ok && C.l2 >= 4u && C.l2 + 1u >= len) { len = C.l2; off = C.d; open = !C.diff; } };
     auto extend_picked = [&](u32 dL, u32 q) -> u32 {                            // the match at distance dL holds up to q: its end (uniform)
-#ifndef ENC_ABL_NOEXT
         for (;;) {
             const u32 at = q + 16u * (u32)lane;
             const bool valid = at + 16u <= mend;
@@ -296,18 +291,12 @@ __device__ inline u32 lz4e_block(Lz4EncSharedT<HLOG>& sh, const u8* src, u32 n, 
         const bool ne = (u32)lane < r && ld8(src + q + (u32)lane - dL) != ld8(src + q + (u32)lane);
         const u64 nm = __ballot(ne);
         return nm ? q + (u32)(__ffsll((long long)nm) - 1) : mend;
-#else
-        return q;
-#endif
     };
     // the parse of one chunk whose lanes hold (len, off) of their best candidate
     auto parse_chunk = [&](u32 base, u32 pp, u32 len, u32 off, bool open, auto rep) {
         constexpr bool REP = decltype(rep)::value;               // (compile time: the repeat-offset search costs registers the other path has no use for)
         u64 openm = REP ? __ballot(open && len != 0u) : 0ull;     // (binary blocks) matches known only up to `len` so far
         u64 mask = __ballot(len >= minmatch) | openm;             // (an open match below the minimum length is tested when it is picked)
-#ifdef ENC_ABL_NOPARSE      // developer ablation (instruction counters only; the output is wrong)
-        mask = 0;
-#endif
         {
             // The sequence list (both formats).  The greedy chain through the chunk (first usable match at or after the cursor wins, the
             // cursor jumps behind it) is the only serial part: a scalar loop of a dozen instructions per emitted match that
@@ -347,9 +336,6 @@ __device__ inline u32 lz4e_block(Lz4EncSharedT<HLOG>& sh, const u8* src, u32 n, 
                 cur = (u32)l + (u32)__builtin_amdgcn_readlane((int)len, l);
                 pe = base + cur;
             }
-#ifdef ENC_ABL_NOEMIT       // developer ablation (the output is wrong): the greedy chain runs, nothing is emitted
-            emit = 0;
-#endif
             if (emit) {
                 const u32 slot = __builtin_amdgcn_mbcnt_hi((u32)(emit >> 32), __builtin_amdgcn_mbcnt_lo((u32)emit, 0u));     // emitted matches before this lane's
                 if ((emit >> lane) & 1) {
@@ -886,9 +872,6 @@ __device__ inline u32 zstde_block_inner(Lz4EncSharedT<HLOG>& she, ZstdEncShared&
     const u32 tail = lz4e_block(she, src, n, nullptr, lane, seqs, &nseq, binary ? 4u : ZE_MINMATCH, effort, abs_base, binary ? &rep_in : nullptr);
     wave_mem_fence();
     const u32 last_off = nseq ? (u32)(uni64(((const ZPK_GLOBAL u64*)seqs)[nseq - 1]) >> 40) & 0x7FFFFFu : 0u;      // what repeat offset 1 is behind this block, if it goes out compressed
-#ifdef ENC_ABL_NOBLOCK      // developer ablation (instruction counters only; the output is wrong): match finder alone
-    return 0;
-#endif
     if (nseq == 0 || n < 16) return 0;
     {   // the Huffman / FSE scratch below overlays the first ZE_TABLE_SAVE bytes of the hash table, which the NEXT block of the entry
         // still wants (matches into the previous block): that part goes to the workgroup's HBM scratch and comes back afterwards
@@ -1247,10 +1230,12 @@ __global__ __launch_bounds__(64, HLOG == LZ4E_HASH_LOG ? ZE_WAVES_PER_SIMD : (HL
     }
     // entries are pulled from a counter, not dealt out by stride: an entry is ~100 ms of one wave, a batch is only a few rounds of the
     // resident workgroups, and the classes differ by 5x — whoever is free takes the next one
+    // (not dequeue() of zpk_device.h: the ticket is looked up in `order` between the compare and the second guard, and this kernel's
+    // instruction stream is left as it was measured)
     for (;;) {
     lane0_guard();
     u32 ticket = 0;
-    if (lane == 0) ticket = atomicAdd(&queue[HLOG - LZ4E_HASH_LOG], 1u);
+    if (lane == 0) ticket = atomicAdd(&queue[C_ENC_HEAD + (HLOG - LZ4E_HASH_LOG)], 1u);
     if (uni(ticket) >= n) break;
     const u64 w = order ? uni(order[uni(ticket)]) : uni(ticket);                  // largest entries first (k_enc_order_*)
     lane0_guard();
@@ -1469,7 +1454,7 @@ static int pack_launch(zpk_codec* c, const uint8_t* slots, const zpk_encode_desc
     if (n > 0x7FFFFFFFull) return ZPK_E_INVALID;
     const u64 nblocks = (n + PK_BLOCK - 1) / PK_BLOCK;
     int rc;
-    if ((rc = grow(c, (void**)&c->d_pack, &c->pack_cap, 2 * nblocks * sizeof(u64) + (n + 1) * sizeof(u64) + 64))) return rc;
+    if ((rc = grow(c, c->d_pack, 2 * nblocks * sizeof(u64) + (n + 1) * sizeof(u64) + 64))) return rc;
     u64* const block_sums = (u64*)c->d_pack;
     u64* const span_blocks = block_sums + nblocks;
     u64* const span_first = span_blocks + nblocks;
@@ -1541,8 +1526,8 @@ __global__ __launch_bounds__(256) void k_enc_order_count(const zpk_encode_desc* 
     if (b >= 0 && rank == 0) atomicAdd(&h[b], count);
     __syncthreads();
     if (threadIdx.x < ORD_CLASSES && h[threadIdx.x]) {
-        atomicAdd(&counters[C_ORDER + threadIdx.x], h[threadIdx.x]);
-        atomicMax(&counters[C_ORDER_SPAN], (u32)threadIdx.x); atomicMax(&counters[C_ORDER_SPAN + 1], (u32)(ORD_CLASSES - 1 - threadIdx.x));
+        atomicAdd(&counters[C_ORDER_HIST + threadIdx.x], h[threadIdx.x]);
+        atomicMax(&counters[C_ORDER_SPAN], (u32)threadIdx.x); atomicMax(&counters[C_ORDER_SPAN_INV], (u32)(ORD_CLASSES - 1 - threadIdx.x));
     }
 }
 __global__ __launch_bounds__(256) void k_enc_order_fill(const zpk_encode_desc* __restrict__ desc, u64 n, u32* __restrict__ order, u32* __restrict__ counters)
@@ -1562,8 +1547,8 @@ __global__ __launch_bounds__(256) void k_enc_order_fill(const zpk_encode_desc* _
         const int cl = threadIdx.x;
         const u32 total = wcount[0][cl] + wcount[1][cl] + wcount[2][cl] + wcount[3][cl];
         u32 before = 0;
-        for (int j = 0; j < cl; j++) before += counters[C_ORDER + j];
-        base[cl] = total ? before + atomicAdd(&counters[C_ORDER + 2 * ORD_CLASSES + cl], total) : 0;
+        for (int j = 0; j < cl; j++) before += counters[C_ORDER_HIST + j];
+        base[cl] = total ? before + atomicAdd(&counters[C_ORDER_FILL + cl], total) : 0;
     }
     __syncthreads();
     if (b >= 0) {
@@ -1581,12 +1566,12 @@ static int encode_launch(zpk_codec* c, const uint8_t* src, const zpk_encode_desc
     int rc;
     // (one scratch region per WORKGROUP of the launch: a batch of a few entries — the streaming writer's steps — takes a few MB, not
     // the 1.8 GB of a full grid)
-    if ((rc = grow(c, (void**)&c->d_seq, &c->seq_cap, (u64)grid * ZE_WG_SCRATCH * sizeof(u64)))) return rc;
+    if ((rc = grow(c, c->d_seq, (u64)grid * ZE_WG_SCRATCH * sizeof(u64)))) return rc;
     if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_ENCODE][0], st);
     HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), st));   // the two kernels' dequeue heads, the order histogram
     const u32* order = nullptr;
     if (n >= c->enc_order_min) {
-        if ((rc = grow(c, (void**)&c->d_lists, &c->list_cap, (u64)N_LISTS_ALLOC * n * sizeof(u32)))) return rc;     // (sized like the decode lists)
+        if ((rc = grow(c, c->d_lists, (u64)N_LIST_SLOTS * n * sizeof(u32)))) return rc;     // (sized like the decode lists)
         hipLaunchKernelGGL(k_enc_order_count, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, desc, n, c->d_counters);
         hipLaunchKernelGGL(k_enc_order_fill, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, desc, n, c->d_lists, c->d_counters);
         order = c->d_lists;
@@ -1683,9 +1668,9 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
     }
     first[n] = k;
     int rc;
-    if ((rc = grow(c, (void**)&c->d_src, &c->src_cap, in_total + 64)) || (rc = grow(c, (void**)&c->d_dst, &c->dst_cap, out_total + 64)) ||
-        (rc = grow(c, &c->d_desc, &c->desc_cap, np * sizeof(zpk_encode_desc))) ||
-        (rc = grow(c, &c->d_res, &c->res_cap, np * sizeof(zpk_encode_result)))) return rc;
+    if ((rc = grow(c, c->d_src, in_total + 64)) || (rc = grow(c, c->d_dst, out_total + 64)) ||
+        (rc = grow(c, c->d_desc, np * sizeof(zpk_encode_desc))) ||
+        (rc = grow(c, c->d_res, np * sizeof(zpk_encode_result)))) return rc;
     hipError_t e = hipSuccess;
     // the sources go up through the pinned staging buffers, gathered piece by piece (zpk_codec.hip, h2d_gather); a single large entry
     // goes as it is
@@ -1702,8 +1687,8 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
     // the hashes of the split entries
     if ((rc = xxh3_spans_launch(c, c->d_src, spans, nsplit, part_blocks, h_hash, c->stream))) return rc;
     // the payloads come back as ONE packed stream (device scan + compaction), not as n small copies out of bound-sized slots
-    if ((rc = grow(c, (void**)&c->d_packed, &c->packed_cap, out_total + 64)) ||
-        (rc = grow(c, (void**)&c->d_packoff, &c->packoff_cap, (np + 1) * sizeof(u64))) ||
+    if ((rc = grow(c, c->d_packed, out_total + 64)) ||
+        (rc = grow(c, c->d_packoff, (np + 1) * sizeof(u64))) ||
         (rc = zpk_codec_pack_batch_device(c, c->d_dst, (const zpk_encode_desc*)c->d_desc, (const zpk_encode_result*)c->d_res, np,
                                           c->d_packed, out_total, (u64*)c->d_packoff, max_cap, c->stream))) return rc;
     e = hipMemcpyAsync(hr, c->d_res, np * sizeof(zpk_encode_result), hipMemcpyDeviceToHost, c->stream);

@@ -528,7 +528,7 @@ static int dstream_fast_zstd(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, u
         }
     } catch (...) { return 10; }
     u32 hflags[64]; memset(hflags, 0, sizeof(hflags));
-    hflags[ZPJ_CNT + ZF_COUNT_WORD] = (u32)list.size();
+    hflags[ZPJ_CNT + C_ZSTD] = (u32)list.size();
     hipError_t e = hipSuccess;
     e = hipMemcpyAsync(d_in, s->f_tab_desc, 3 * FZ_TABDESC, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && s->f_tree_len) e = hipMemcpyAsync(d_in + tree_at, s->f_tree, s->f_tree_len, hipMemcpyHostToDevice, st);

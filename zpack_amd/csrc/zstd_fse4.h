@@ -35,9 +35,8 @@ namespace zpk {
 #define ZF_WG_PER_CU 12u                           // LDS: 12 452 B per workgroup = ten 1280-byte allocation units; 12 x 10 of the CU's 128
 #endif
 #define ZF_GRID_MAX (256u * ZF_WG_PER_CU)
-#define ZF_HEAD 8                                  // counters[] word used as this kernel's dequeue head
-#define ZF_WATCHDOG_WORD 11                        // counters[11]: entries given up by the row watchdog, [12]: header-loop budget hits
-#define ZF_COUNT_WORD 1                            // counters[] word holding the length of the Zstandard work list (L_ZSTD)
+// counters[] words of this kernel (zpk_layout.h): C_ZSTD the length of its work list, C_FSE_HEAD its dequeue head, C_FSE_WATCHDOG rows
+// given up by the row watchdog, C_FSE_BUDGET header-loop budget hits, C_FSE_MARKED entries whose sequences it left in the arena
 
 // LDS is what bounds the number of streams in flight, and the stage's throughput is proportional to that number (measured, round 2:
 // 4 / 6 / 8 workgroups per CU -> 34.7 / 25.7 / 19.2 ms on 16 384 text entries).  So a decode-table cell is TWO bytes here:
@@ -259,7 +258,7 @@ __device__ __forceinline__ void zstd_fse_rows(ZfShared& sh, const u8* __restrict
     const u32 tmask = chain ? 511u : 0u;                 // idle lanes read cell 0
     u32 badv = 0;
     u32 acc_lo = 0, acc_hi = 0;                          // per lane: lane j of a row holds packed sequence (seq_n - 1 - j) of the row's entry
-    const u32 nz = counters[ZF_COUNT_WORD];
+    const u32 nz = counters[C_ZSTD];
     // A row must never hold the GPU: an entry gets the size-proportional budget of zpk_device.h (like the fused decoder), and the header
     // loop a fixed budget of steps per wave; either limit just hands the entry (or the rest of the list) to k_zstd.
     u64 row_deadline = 0;
@@ -269,7 +268,7 @@ __device__ __forceinline__ void zstd_fse_rows(ZfShared& sh, const u8* __restrict
         if (phase != ZF_DONE && phase != ZF_NEED_ENTRY && __builtin_amdgcn_s_memrealtime() > row_deadline) {
             bad = true; ip = iend; phase = ZF_NEED_FRAME;
             lane0_guard();
-            if (sub == 0) atomicAdd(&counters[ZF_WATCHDOG_WORD], 1u);
+            if (sub == 0) atomicAdd(&counters[C_FSE_WATCHDOG], 1u);
             lane0_guard();
         }
         // =================== between blocks: headers, tables, stream start (divergent, rare) ===================
@@ -277,14 +276,16 @@ __device__ __forceinline__ void zstd_fse_rows(ZfShared& sh, const u8* __restrict
             for (;;) {
                 if (++setup_steps > (1u << 24)) {                      // cannot happen: every step consumes input or finishes an entry
                     lane0_guard();
-                    if (sub == 0) atomicAdd(&counters[ZF_WATCHDOG_WORD + 1], 1u);
+                    if (sub == 0) atomicAdd(&counters[C_FSE_BUDGET], 1u);
                     lane0_guard();
                     phase = ZF_DONE; break;
                 }
                 if (phase == ZF_NEED_ENTRY) {
+                    // (not dequeue() of zpk_device.h: here every 16-lane ROW takes an entry of its own — four atomics per wave, the
+                    // broadcast is per row and the rows of a wave are in different phases)
                     lane0_guard();
                     u32 v = 0;
-                    if (sub == 0) v = atomicAdd(&counters[ZF_HEAD], 1u);
+                    if (sub == 0) v = atomicAdd(&counters[C_FSE_HEAD], 1u);
                     lane0_guard();
                     v = (u32)__shfl((int)v, lane & ~15, 64);
                     if (v >= nz) { phase = ZF_DONE; break; }
@@ -312,7 +313,7 @@ __device__ __forceinline__ void zstd_fse_rows(ZfShared& sh, const u8* __restrict
                         lane0_guard();
                         if (sub == 0) {
                             if constexpr (BLOCKS) { rep_out[3u * e] = rep0; rep_out[3u * e + 1u] = rep1; rep_out[3u * e + 2u] = rep2; }
-                            state[e] = bad ? 0u : 1u; if (!bad) atomicAdd(&counters[ZF_WATCHDOG_WORD + 2], 1u);
+                            state[e] = bad ? 0u : 1u; if (!bad) atomicAdd(&counters[C_FSE_MARKED], 1u);
                         }
                         lane0_guard();
                         phase = ZF_NEED_ENTRY;
@@ -589,7 +590,7 @@ __global__ __launch_bounds__(64, 3) void k_zstd_fse(const u8* __restrict__ src, 
                                                  const u32* __restrict__ list, u32* __restrict__ counters,
                                                  u64* __restrict__ arena, u32* __restrict__ state)
 {
-    if (counters[ZF_COUNT_WORD] == 0) return;        // no Zstandard entry in the batch
+    if (counters[C_ZSTD] == 0) return;        // no Zstandard entry in the batch
     __shared__ ZfShared sh;
     zstd_fse_rows<false>(sh, src, desc, list, counters, arena, state, nullptr, 0);
 }
@@ -597,7 +598,7 @@ __global__ __launch_bounds__(64, 3) void k_zstd_fse_blocks(const u8* __restrict_
                                                         const u32* __restrict__ list, u32* __restrict__ counters,
                                                         u64* __restrict__ arena, u32* __restrict__ state, u32* __restrict__ rep_out, u64 src_size)
 {
-    if (counters[ZF_COUNT_WORD] == 0) return;
+    if (counters[C_ZSTD] == 0) return;
     __shared__ ZfShared sh;
     zstd_fse_rows<true>(sh, src, desc, list, counters, arena, state, rep_out, src_size);
 }

@@ -30,7 +30,10 @@
 namespace zpk {
 
 // words of the flags array this path adds (lz4_pj.h: PJ_ERR, PJ_TOTAL, PJ_ROUND0 ..): the counters k_zstd_fse_blocks works with
-#define ZPJ_CNT 40                                 // flags + ZPJ_CNT = its `counters` (ZF_COUNT_WORD 1, ZF_HEAD 8, ZF_WATCHDOG_WORD 11..13)
+#define ZPJ_CNT 40                                 // flags + ZPJ_CNT = its `counters` (C_ZSTD, C_FSE_HEAD, C_FSE_WATCHDOG .. C_FSE_MARKED)
+#define ZPJ_FLAG_WORDS 64                          // the whole flags array
+static_assert(ZPJ_CNT + C_ZSTD < ZPJ_FLAG_WORDS && ZPJ_CNT + C_FSE_HEAD < ZPJ_FLAG_WORDS && ZPJ_CNT + C_FSE_MARKED < ZPJ_FLAG_WORDS && C_FSE_WATCHDOG < C_FSE_MARKED,
+              "k_zstd_fse_blocks' counter words lie inside the flags array");
 
 struct ZpjLitHdr { u32 type, hl, streams, regen, csize; bool ok; };
 __device__ __forceinline__ ZpjLitHdr zpj_lit_hdr(const u8* p, u64 size)

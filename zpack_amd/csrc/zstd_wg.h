@@ -416,14 +416,8 @@ struct HufBits {
     i32 cb;               // container covers stream bits [cb*8, cb*8 + 128)
     u64 c_lo, c_hi, pre, pre2;  // pre / pre2 = the 8 + 8 bytes below c_lo, loaded two steps ahead: with 8-bit codes a step is
                                 // only 8 symbols, less than a memory round trip under load
-#ifdef HUF_PRE4
-    u64 pre3, pre4;
-#define HUF_SHIFT_DOWN() do { c_hi = c_lo; c_lo = pre; pre = pre2; pre2 = pre3; pre3 = pre4; cb -= 8; pre4 = fetch(cb - 32); } while (0)
-#define HUF_SEEK_PRE() do { pre = fetch(cb - 8); pre2 = fetch(cb - 16); pre3 = fetch(cb - 24); pre4 = fetch(cb - 32); } while (0)
-#else
 #define HUF_SHIFT_DOWN() do { c_hi = c_lo; c_lo = pre; pre = pre2; cb -= 8; pre2 = fetch(cb - 16); } while (0)
 #define HUF_SEEK_PRE() do { pre = fetch(cb - 8); pre2 = fetch(cb - 16); } while (0)
-#endif
 
     __device__ __forceinline__ u64 fetch(i32 byte) const
     {
@@ -1066,6 +1060,11 @@ __device__ inline int zstd_literals(SH& sh, ZFrameState& fs, const u8* src, u64 
     return D_OK;
 }
 
+// EXEC_ONLY = true, zstd_sequences_pre and the pre / pre_idx / work_bytes plumbing are the direct executor of round 1: k_zstd_exec runs
+// through the ring (zstd_ring.h) and nothing instantiates <true> any more.  They are still here on purpose: with them deleted (round 10)
+// k_zstd_stream answered DECOMPRESS_FAILED on entries of several frames that it decodes correctly with them present, although the
+// deletion changes no statement that runs — something in the resumable decode depends on how this file compiles, and that has to be
+// found before the dead path can go (profiles/r10/README.md).
 template <bool EXEC_ONLY>
 __device__ inline int zstd_block(ZstdShared& sh, ZFrameState& fs, const u8* src, u64 size, const u8* rd_hi,
                                  u8* dst, u64 dst_cap, u8* frame_lo, u8* lit_buf, u64& produced, int lane)
