@@ -661,6 +661,79 @@ def test_stream_steps_agree_with_one_shot_on_foreign_and_damaged_frames(codec, g
             assert got == outs[0][:min(produced, usize)].tobytes(), label
 
 
+_RESUME_CHUNKS = (262144, 300001)
+
+
+@pytest.fixture(scope="module")
+def resume_entry():
+    """One Zstandard entry of 786434 compressed bytes, laid out so that the launch boundaries of _RESUME_CHUNKS (the stream launches
+    once per chunk of >= 256 KiB) fall inside a skippable frame, inside a frame header, inside blocks and inside a content checksum:
+      frame 1    TEXT, 700000 bytes, level 3: six blocks, four of them with Treeless literals
+      skippable  ends at 299999, so 262144 lies inside it and 300001 two bytes into the header of frame 2
+      frame 2    RECORDS, 500000 bytes, level 3: four blocks; 524288 lies inside one of them
+      skippable  padding that puts the entry's last byte at 786433
+      frame 3    TEXT, 700000 bytes, level 9 (level 3 emits no Repeat_Mode tables on this data, level 9 one), Content_Checksum_Flag
+                 set and the 4 checksum bytes appended: 600002 lies inside a block, 786432 two bytes into the checksum
+    -> (entry, plain, offset of frame 2, its length, offset of frame 3, its length)"""
+    import struct
+    o = oracle()
+    p1, p2, p3 = dg.fill(dg.TEXT, 71, 0, 700000), dg.fill(dg.RECORDS, 71, 1, 500000), dg.fill(dg.TEXT, 73, 2, 700000)
+    f1, f2 = dg.compress(dg.ZSTD, 3, p1), dg.compress(dg.ZSTD, 3, p2)
+    f3 = bytearray(dg.compress(dg.ZSTD, 9, p3))
+    assert f3[:4] == b"\x28\xb5\x2f\xfd" and not f3[4] & 4
+    f3[4] |= 4                                                                              # RFC 8878 3.1.1.1.1: Content_Checksum_Flag
+    f3 = bytes(f3) + struct.pack("<I", o.xxh64(p3) & 0xFFFFFFFF)
+    total = 3 * 262144 + 2
+
+    def skippable(n):
+        assert 0 <= n < 1 << 20, n
+        return struct.pack("<II", 0x184D2A50, n) + bytes(n)
+
+    at2 = 300001 - 2
+    sk1 = skippable(at2 - len(f1) - 8)
+    at3 = total - len(f3)
+    sk2 = skippable(at3 - at2 - len(f2) - 8)
+    entry = f1 + sk1 + f2 + sk2 + f3
+    assert len(entry) == total and len(f1) + 8 < 262144 < at2 and at2 + len(f2) > 524288 and at3 < 600002
+    plain = np.concatenate([p1, p2, p3])
+    rc, out = o.zstd_decode(entry, len(plain))
+    assert rc == 0 and out == plain.tobytes()
+    return entry, plain, at2, len(f2), at3, len(f3)
+
+
+@pytest.mark.parametrize("damage", ["intact", "flip in frame 2", "cut inside frame 3"])
+def test_stream_resumes_across_launches_on_a_multi_frame_entry(codec, resume_entry, damage):
+    """The windowless Zstandard resume path — park(0) in a skippable frame and in a frame header, park(1) inside frames whose blocks use
+    Treeless literals and a Repeat_Mode table, park(2) in front of a content checksum, the LDS image saved and restored — on an entry
+    too large for one launch and not one plain frame (so not the bounded fast path): more than one launch (zpk_dstream_counters), and
+    the status and the bytes of the one-shot decode of the same bytes, also with a byte flipped in the second frame and with the entry
+    cut inside the third."""
+    entry, plain, at2, len2, at3, len3 = resume_entry
+    usize, h = len(plain), dg.xxh3(plain)
+    fr = bytearray(entry)
+    if damage == "flip in frame 2":
+        fr[at2 + len2 // 2] ^= 1
+    elif damage == "cut inside frame 3":
+        fr = fr[:at3 + len3 // 2]
+    fr = bytes(fr)
+    e = dict(offset=10, comp_size=len(fr), uncomp_size=usize, hash=h, method=dg.ZSTD)
+    arc = zpk.assemble([fr], [("f", 10, len(fr), usize, h, dg.ZSTD)])
+    res, outs = codec.decode_batch_host(arc, _desc([e], [usize]))
+    want_rc, produced = int(res[0]["status"]), int(res[0]["produced"])
+    if damage == "intact":
+        assert want_rc == 0 and produced == usize and outs[0][:usize].tobytes() == plain.tobytes()
+    if want_rc == 0 and produced < usize:
+        want_rc = 15              # (as in test_stream_steps_agree_with_one_shot_on_foreign_and_damaged_frames)
+    for chunk in _RESUME_CHUNKS:
+        status, got, _ = _stream_decode(codec, fr, dg.ZSTD, usize, h, chunk, 1 << 20)
+        stats = _stream_decode.stats
+        print(damage, "chunk", chunk, "one-shot", want_rc, "stream", status, stats)
+        assert stats["restarts"] == 0 and stats["steps"] >= 2, (damage, chunk, stats)           # more than one launch
+        assert status == want_rc, (damage, chunk, "one-shot", want_rc, "stream", status)
+        if want_rc in (0, 15):
+            assert got == outs[0][:min(produced, usize)].tobytes(), (damage, chunk)
+
+
 @pytest.mark.parametrize("lo,hi", [(200, 300000), (3000, 3000)])
 def test_work_lists_largest_first_give_identical_results(codec, lo, hi):
     """A ragged batch (200 B ... 300 KiB; and a batch of ONE size, which is ordered by "did it compress" instead: both methods, all four
