@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer: per-phase cycles of the general LZ4 decoder k_lz4_wave (needs a -DZPK_DEVELOPER -DZPK_STATS build selected with
-ZPACK_AMD_CODEC_SO, and ZPK_DEBUG_TIMING=1).  tools/lw_stats.py [entries] [mix]"""
+ZPACK_AMD_CODEC_SO, and ZPK_DEBUG_TIMING=1).  tools/lw_stats.py [entries] [mix]
+LW_ASM=1 with a -DZPK_STATS_ASM build: which batches the executor assembles in LDS, why it refuses the others, ticks of both kinds."""
 import os, sys
 import numpy as np
 os.environ["ZPK_DEBUG_TIMING"] = "1"
@@ -21,6 +22,19 @@ for _ in range(3):
 torch.cuda.synchronize()
 a = np.zeros((n, 8), dtype=np.uint64)
 codec._chk(codec.L.zpk_codec_debug_read(codec.h, a.ctypes.data, a.nbytes), "debug_read")
+if os.environ.get("LW_ASM"):        # a -DZPK_STATS_ASM build: the eight words are the assembly counters (zpk_codec.hip, lz4_stats_out)
+    hi, lo = (a >> 32).sum(0).astype(np.float64), (a & 0xFFFFFFFF).sum(0).astype(np.float64)
+    nb, t_asm, t_dir = hi[0], float(a[:, 5].sum()), float(a[:, 6].sum())
+    print("assembly of batches (mix %d, %d entries): %.0f batches, %.1f per entry" % (mix, n, nb, nb / n))
+    for k, v in (("assembled", lo[0]), ("direct: no room only", hi[1]), ("direct: a long piece only", lo[1]), ("direct: both", hi[2]),
+                 ("direct: straddle only", lo[2])):
+        print("  %-28s %6.2f %%" % (k, 100 * v / nb))
+    print("  of the batches with room, share of ALL batches that hold: literal run > 32 %.2f %%, plain match > 32 %.2f %%, "
+          "self-overlap offset >= 16 %.2f %%, self-overlap offset < 16 %.2f %%" % tuple(100 * v / nb for v in (hi[3], lo[3], hi[4], lo[4])))
+    n_dir = nb - lo[0]
+    print("  ticks per batch: assembled %.0f, direct %.0f; per output byte: assembled %.3f (mean %.0f B), direct %.3f (mean %.0f B)" % (
+        t_asm / max(lo[0], 1), t_dir / max(n_dir, 1), t_asm / max(hi[7], 1), hi[7] / max(lo[0], 1), t_dir / max(lo[7], 1), lo[7] / max(n_dir, 1)))
+    sys.exit(0)
 m = a.astype(np.float64).mean(0)
 print("mean memtime ticks per entry (mix %d, %d entries): total %.0f" % (mix, n, m[6]))
 for k, v in zip(["parse", "literals", "deps", "rounds"], m[:4]):

@@ -76,6 +76,9 @@ static_assert(LZ4W_SEG <= 64u, "the visited-position mask of a segment is one 64
 #define LZ4W_RUNIN LZ4W_SEG                       // bytes of run-in before a segment's speculative walk
 #endif
 
+#ifndef LZ4W_SPLIT_FIRST
+#define LZ4W_SPLIT_FIRST 0
+#endif
 #ifndef LZ4W_NREC
 #define LZ4W_NREC 576u                           // token-position list: 9 batches of 64 sequences.  Measured: total LDS <= 5 KiB
                                                  // per wave keeps the waves the register budget allows (32 per CU at 64 VGPRs; 5.5 KiB loses waves: 451 vs 482 GiB/s in round 1)
@@ -328,8 +331,12 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
         // numbers in LDS — a short loop over the set bits of its mask — so that a batch lane finds its token with
         // one ds_read.  The list holds LZ4W_NREC entries; a chunk with more sequences is listed in windows.
         ZPK_LDS u16* const rec = (ZPK_LDS u16*)sh.rec;
-        for (u32 b0 = 0; b0 < nseq; b0 += WAVE) {
-            if (b0 % LZ4W_NREC == 0) {
+        // (LZ4W_SPLIT_FIRST, developer A/B: a chunk's first 64 sequences go as two batches of 32, so that the second half finds the
+        // room the whole batch does not — measured and left off, profiles/r12)
+        for (u32 b0 = 0, bstep; b0 < nseq; b0 += bstep) {
+            bstep = LZ4W_SPLIT_FIRST && b0 < WAVE ? WAVE / 2 : WAVE;
+            const u32 bw = b0 % LZ4W_NREC;                                     // a multiple of 32, of 64 behind the first: a batch never wraps the window
+            if (bw == 0) {
                 wave_mem_fence();
                 u64 m = w.m;
                 u32 k = x - my_nseq;                                           // number of this lane's first sequence
@@ -340,15 +347,19 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
                     if (k - b0 < LZ4W_NREC) rec[k - b0] = (u16)(rel + b);      // k < b0 wraps to a huge value
                     k++;
                 }
+                // behind the chunk's last sequence: where the chain leaves the chunk (the room of the last batch, see below).  Written
+                // by the lane of the last sequence and the active lanes behind it: at the fixed point they all hold the chain's exit
+                // (chain_exit > cpos; whatever it is, the room stays inside the stage)
+                if (active && x == nseq && nseq - b0 < LZ4W_NREC)
+                    rec[nseq - b0] = (u16)(w.exit - cpos < LZ4W_CHUNK + LZ4W_SLACK ? w.exit - cpos : LZ4W_CHUNK + LZ4W_SLACK);
                 wave_mem_fence();                                              // LDS is in order within a wave
             }
-            const int cnt = (int)(nseq - b0 < WAVE ? nseq - b0 : WAVE);
+            const int cnt = (int)(nseq - b0 < bstep ? nseq - b0 : bstep);
             const u64 tq0 = SEQ_T(); (void)tq0;
             SeqBatch q; q.lit = ip; q.lit_lds = SEQ_NO_LDS; q.ll = 0; q.ml = 0; q.off = 1; q.bad = 0;
-            const u32 sq = b0 + (u32)lane;
             u32 tok_pos = cpos;
             if (lane < cnt) {
-                const u32 p = cpos + (u32)rec[sq % LZ4W_NREC];
+                const u32 p = cpos + (u32)rec[bw + (u32)lane];
                 tok_pos = p;
                 const Lz4Quick t = lz4_quick(B.S, B.cbase, p, lim);
                 if (!t.slow) {                                                               // straight-line common case
@@ -366,13 +377,35 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
                 if (q.ll <= SEQ_OWN_MAX && lp + q.ll <= B.cend) q.lit_lds = lp - B.cbase;
             }
             SEQ_STAT({ u64 t2 = SEQ_T(); stt.t_parse += t2 - tq0; stt.t_tok += t2 - tq0; });
-            // Input this chunk has already consumed (everything before the batch's first token) is dead: the
-            // executor assembles the batch there.  The first batch or two of a chunk find too little room and
-            // take the direct path.
-            const u32 dead = (u32)__builtin_amdgcn_readfirstlane((int)tok_pos) - cpos;
+            // Input this chunk has already consumed is dead: the executor assembles the batch there.  By the time the executor
+            // issues its first LDS store, this batch's own input is consumed too — its tokens are decoded into q above (the
+            // out-of-line lz4_token_at calls included) and the executor reads its literals (two lds_ld128 per lane) ahead of every
+            // lds_store_wide32 and of the copies of long runs, which come from memory; stage and assembly buffer are the same array
+            // and neither pointer is __restrict__, so the compiler keeps that order, and the LDS operations of one wave complete in
+            // order.  (Only the 32 history bytes at the front of the buffer are written before the literals are read.  No assembled
+            // batch has input there: a chunk's first batch never fits — a match is at least a byte longer than its token, offset
+            // and extension bytes, a literal run at most a byte per 255 shorter than its own, so a batch's output + 48 is more than
+            // its input — and every later batch begins at least 64 x 3 bytes into the chunk.)  So the dead bytes run up to the NEXT
+            // batch's first token: the list entry behind this batch's last one (behind the chunk's last sequence: the chain's
+            // exit).  At a window boundary of the list that entry is not written yet — entry 0 still holds the window's first
+            // token — and the room ends at this batch's first token, as it did for every batch before.  A chunk's first
+            // batch or two still find too little room and take the direct path.
+            u32 dead = 0;
+            if constexpr (!EMIT) {
+                const u32 nx = bw + (u32)cnt;
+                const u32 own = tok_pos - cpos;                                            // (lane 0 holds the batch's first token)
+#ifdef LZ4W_ROOM_OWN_TOKEN                                                             // developer A/B: the room as it was before this rule
+                (void)nx; const u32 nxt = 0u;
+#else
+                const u32 nxt = (u32)rec[nx == LZ4W_NREC ? 0u : nx];
+#endif
+                // INVARIANT the executor relies on (its history store, seq_exec.h 3a, comes before it reads the literals): a batch
+                // that is assembled has own >= SEQ_ASM_PRE, i.e. none of its input in the first 32 bytes of the stage (see above)
+                dead = (u32)__builtin_amdgcn_readfirstlane((int)(nxt > own ? nxt : own));
+            }
             int rc;
             if constexpr (EMIT) { (void)dead; rc = emit(q, cnt, (u32)(q.lit - ip)); }
-            else rc = seq_exec_batch<true, COOP>(q, cnt, op, oend, dst_lo, -1, lane, stt, B.S, to_lds_rw(sh.stage), dead);
+            else rc = seq_exec_batch<true, COOP, SEQ_ASM_LONG_LIT != 0>(q, cnt, op, oend, dst_lo, -1, lane, stt, B.S, to_lds_rw(sh.stage), dead);
             if (rc != D_OK) { op_io = op; return rc; }
         }
         if (fl) return D_MALFORMED;                                            // (not reached: the executor saw the malformed token)

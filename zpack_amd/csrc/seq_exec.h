@@ -236,7 +236,11 @@ __device__ __forceinline__ void seq_coop_round(u64 cm, u32 ml, u32 off, u8* ms, 
 // developer aid: cycle accounting of the executor (kept in registers; written out only when asked)
 // compiled in only with -DZPK_STATS (the counters cost ~10 registers, i.e. a wave of occupancy per SIMD)
 #ifdef ZPK_STATS
-struct SeqStats { u64 t_parse, t_lit, t_dep, t_rounds; u32 rounds, batches, coops, redirects; u64 t_stage, t_walk1, t_fix, t_emit, t_tok; u32 fix_iters, chunks, asm_batches, hops_first, hops_fix, slow_hops; };
+struct SeqStats { u64 t_parse, t_lit, t_dep, t_rounds; u32 rounds, batches, coops, redirects; u64 t_stage, t_walk1, t_fix, t_emit, t_tok; u32 fix_iters, chunks, asm_batches, hops_first, hops_fix, slow_hops;
+    // why a batch was not assembled (ZPK_STATS_ASM, tools/lw_stats.py): no room only / a long piece only / both / straddle only; of the batches
+    // that had the room, those with a literal run > SEQ_OWN_MAX, a plain match > SEQ_OWN_MAX, a self-overlapping match of offset >= 16, < 16
+    // (a batch counts once per kind); ticks and output bytes of assembled against direct batches
+    u32 r_room, r_piece, r_both, r_straddle, k_lit, k_match, k_so16, k_so1; u64 t_asm, t_dir; u32 b_asm, b_dir; };
 #define SEQ_T() __builtin_amdgcn_s_memtime()
 #define SEQ_STAT(x) do { x; } while (0)
 #else
@@ -254,6 +258,11 @@ struct SeqStats { };
 #endif
 
 #define SEQ_NO_LDS 0xFFFFFFFFu
+// LONG_LIT of seq_exec_batch as the LZ4 decoder sets it: an assembled batch may hold literal runs longer than SEQ_OWN_MAX (0 = such a
+// batch takes the direct path, as it did before: developer A/B).  The Zstandard callers leave LONG_LIT off.
+#ifndef SEQ_ASM_LONG_LIT
+#define SEQ_ASM_LONG_LIT 1
+#endif
 // Batch assembly buffer (optional, LDS, per wave): SEQ_ASM_PRE bytes of history, the batch output, 16 bytes of
 // read slack.
 #define SEQ_ASM_PRE 32u
@@ -335,12 +344,15 @@ __device__ __forceinline__ u64 seq_dependencies(bool has_match, u32 r_ms, u32 r_
 // oend = end of the output slot, dst_lo = lowest address a match may read.  lit_rle >= 0: every literal
 // byte equals that value (Zstandard RLE literals).  Returns D_OK / D_MALFORMED / D_DST_FULL.
 // lit_stage: LDS buffer q.lit_lds indexes (16 readable bytes past every literal run it is used for), or null.
-// asm_buf/asm_cap: per-wave LDS scratch of asm_cap bytes (0 = none) that does not overlap this batch's
-// literals.  A batch whose output fits (SEQ_ASM_PRE + total + SEQ_ASM_SLACK <= asm_cap) and that has no long or
-// self-overlapping piece is ASSEMBLED IN LDS: literals and matches are written there, in-batch sources are
+// asm_buf/asm_cap: per-wave LDS scratch of asm_cap bytes (0 = none).  From byte SEQ_ASM_PRE on it MAY overlap this
+// batch's literals in lit_stage (the LZ4 caller hands over everything before the next batch's first token): the
+// literals are read before the first store there.  Its first SEQ_ASM_PRE bytes must not (lz4_wave.h says why they
+// never do).  A batch whose output fits (SEQ_ASM_PRE + total + SEQ_ASM_SLACK <= asm_cap) and that has no long or
+// self-overlapping piece (LONG_LIT: match) is ASSEMBLED IN LDS: literals and matches are written there, in-batch sources are
 // read back from there at LDS latency instead of a store->load round trip through L2, and the finished batch
 // goes to memory as one contiguous 16-bytes-per-lane stream — one or two full store instructions instead of
 // ~17 partially filled ones.
+// LONG_LIT: a batch with literal runs longer than SEQ_OWN_MAX may be assembled too (each run is copied from memory by its own lane).
 // NARROW_ONLY: the caller guarantees 31-bit positions and offsets (LZ4: 16-bit offsets, lengths clamped to 2^23), so only
 // the 32-bit dependency analysis is instantiated.
 // COOP (round 5): what a batch does with its cooperative pieces (matches longer than SEQ_OWN_MAX or feeding themselves, literal runs
@@ -350,11 +362,12 @@ __device__ __forceinline__ u64 seq_dependencies(bool has_match, u32 r_ms, u32 r_
 // path changes: +3.7 % vector instructions, +18 % wait cycles; instruction-cache misses are nil), as a real call (__noinline__) 31 %:
 // profiles/r05/r05_coop_variants_ab.txt.  So k_classify sends the LZ4 entries that are mostly runs (compressed to less than an eighth)
 // to k_lz4_left, built with COOP = 2, and k_lz4_wave is the code it was.
-template <bool NARROW_ONLY = false, int COOP = 2>
+template <bool NARROW_ONLY = false, int COOP = 2, bool LONG_LIT = false>
 __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& op, u8* oend, const u8* dst_lo, int lit_rle, int lane,
                                               SeqStats& stt, lds_cp8 lit_stage = nullptr, lds_p8 asm_buf = nullptr, u32 asm_cap = 0)
 {
     u64 t0 = SEQ_T(); (void)t0; (void)stt;
+    const u64 tb = t0; (void)tb;
     SEQ_STAT(stt.batches++);
     const bool act = lane < cnt;
     const u32 ll = act ? q.ll : 0u, ml = act ? q.ml : 0u;
@@ -399,22 +412,48 @@ __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& o
     const bool early = has_match && !coop && src + (i64)need_len <= 0;
     SEQ_STAT({ u64 t1 = SEQ_T(); stt.t_dep += t1 - t0; t0 = t1; });
 
+#ifdef ZPK_STATS
+        if (lit_rle < 0 && NARROW_ONLY) {            // (the LZ4 decoder: its assembly buffer is the stage, LDS address 0)
+            const bool fits = total + (SEQ_ASM_PRE + SEQ_ASM_SLACK) <= (u64)asm_cap;
+            const u64 kl = __ballot(ll > SEQ_OWN_MAX), km = __ballot(has_match && !self_overlap && ml > SEQ_OWN_MAX);
+            const u64 k16 = __ballot(has_match && self_overlap && q.off >= 16u), k1 = __ballot(has_match && self_overlap && q.off < 16u);
+            const bool piece = ((LONG_LIT ? 0ull : kl) | km | k16 | k1) != 0;
+            if (!fits) { if (piece) stt.r_both++; else stt.r_room++; }
+            else {
+                if (piece) stt.r_piece++;
+                else if (__ballot(has_match && !early && src < 0) != 0 && (u64)(op - dst_lo) < SEQ_ASM_PRE) stt.r_straddle++;
+                stt.k_lit += kl != 0; stt.k_match += km != 0; stt.k_so16 += k16 != 0; stt.k_so1 += k1 != 0;
+            }
+        }
+#endif
     // ---- 3a. assembly in LDS ----
     if (lit_rle < 0 && total + (SEQ_ASM_PRE + SEQ_ASM_SLACK) <= (u64)asm_cap) {
         const bool straddle = has_match && !early && src < 0;                       // source begins before the batch, ends inside
         const u64 sm = __ballot(straddle);
-        if (__ballot(coop || ll > SEQ_OWN_MAX) == 0 && (sm == 0 || (u64)(op - dst_lo) >= SEQ_ASM_PRE)) {
+        if (__ballot(coop || (!LONG_LIT && ll > SEQ_OWN_MAX)) == 0 && (sm == 0 || (u64)(op - dst_lo) >= SEQ_ASM_PRE)) {
             SEQ_STAT(stt.asm_batches++);
             const lds_p8 ob = asm_buf + SEQ_ASM_PRE;                                // batch position 0
+            // (asm_buf may cover this batch's own literals in lit_stage from byte SEQ_ASM_PRE on — the history bytes in front of
+            // that belong to the caller's dead space in any case: the literals are read below, ahead of every store behind the history)
+            // INVARIANT (caller): none of this batch's literals lie in asm_buf[0, SEQ_ASM_PRE) — this store comes before they are read
             if (sm != 0 && lane < 2) lds_st128(asm_buf + 16 * lane, ld128(op - SEQ_ASM_PRE + 16 * lane));
+            // a literal run longer than SEQ_OWN_MAX (q.lit_lds is SEQ_NO_LDS for it) is copied below from memory
+            const u32 ln = LONG_LIT && ll > SEQ_OWN_MAX ? 0u : ll;
             Copy32 ca;
             if (q.lit_lds != SEQ_NO_LDS) {
                 ca.lo.lo = ca.lo.hi = ca.hi.lo = ca.hi.hi = 0;
-                if (ll) { ca.lo = lds_ld128(lit_stage + q.lit_lds); if (ll > 16) ca.hi = lds_ld128(lit_stage + q.lit_lds + (ll - 16)); }
-            } else ca = gload_wide32(q.lit, ll, false);
+                if (ln) { ca.lo = lds_ld128(lit_stage + q.lit_lds); if (ln > 16) ca.hi = lds_ld128(lit_stage + q.lit_lds + (ln - 16)); }
+            } else ca = gload_wide32(q.lit, ln, false);
+            if (LONG_LIT && ll > SEQ_OWN_MAX) {                                      // long runs: memory -> LDS by their own lanes, 16 B a step
+                const lds_p8 p = ob + (r_ms - ll);
+                for (u32 c = 0; c < ll; c += 16) {                                   // (the last piece overlaps the one before it)
+                    const u32 at = c + 16 <= ll ? c : ll - 16;
+                    lds_st128(p + at, ld128(q.lit + at));
+                }
+            }
             const u32 mn = early ? ml : 0u;
             const Copy32 cb = gload_wide32(srcp, mn, srcp + 16 <= oend);
-            lds_store_wide32(ob + (r_ms - ll), ca, ll);
+            lds_store_wide32(ob + (r_ms - ll), ca, ln);
             lds_store_wide32(ob + r_ms, cb, mn);
             wave_mem_fence();
             u64 done = ~pending | __ballot(early);
@@ -444,6 +483,7 @@ __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& o
                 else gstore_upto16(op + c, v, tot - c);
             }
             wave_mem_fence();
+            SEQ_STAT({ stt.t_asm += SEQ_T() - tb; stt.b_asm += (u32)total; });
             op += total;
             return D_OK;
         }
@@ -537,7 +577,7 @@ __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& o
         done |= rmask;
         pending &= ~rmask;
     }
-    SEQ_STAT({ u64 t1 = SEQ_T(); stt.t_rounds += t1 - t0; });
+    SEQ_STAT({ u64 t1 = SEQ_T(); stt.t_rounds += t1 - t0; stt.t_dir += t1 - tb; stt.b_dir += (u32)total; });
     op += total;
     return D_OK;
 }

@@ -288,6 +288,11 @@ __device__ __forceinline__ void lz4_stats_out(u64* __restrict__ dbg, u32 e, cons
         g[0] = stt.t_stage; g[1] = stt.t_walk1; g[2] = stt.t_fix; g[3] = stt.t_emit; g[4] = stt.t_tok;
         g[5] = ((u64)stt.hops_first << 32) | stt.hops_fix; g[6] = stt.slow_hops;
 #endif
+#ifdef ZPK_STATS_ASM
+        g[0] = ((u64)stt.batches << 32) | stt.asm_batches; g[1] = ((u64)stt.r_room << 32) | stt.r_piece; g[2] = ((u64)stt.r_both << 32) | stt.r_straddle;
+        g[3] = ((u64)stt.k_lit << 32) | stt.k_match; g[4] = ((u64)stt.k_so16 << 32) | stt.k_so1; g[5] = stt.t_asm; g[6] = stt.t_dir;
+        g[7] = ((u64)stt.b_asm << 32) | stt.b_dir;
+#endif
     }
 #else
     (void)dbg; (void)e; (void)stt; (void)t_all; (void)lane;
