@@ -40,7 +40,8 @@ extern "C" {
 
 #define ZPK_CODEC_ABI_VERSION 3      /* 3: the two-stage LZ4 path of version 2 is gone (options 2..5 are ZPK_E_INVALID again, decode_stats2 out[2] = out[4] = 0,
                                         out[3] = LZ4 entries that are mostly runs, decoded by k_lz4_left); 2: set_option has options again.
-                                        (Additive since 3, no renumbering: decode_stats2 out[8], out[9], which read 0: LZ4 entries the lean kernel handed to the general decoder / not plain frames.) */
+                                        (Additive since 3, no renumbering: decode_stats2 out[8], out[9], which read 0: LZ4 entries the lean kernel handed to the general decoder / not plain frames.
+                                        zpk_codec_encode_big_device, zpk_codec_encode_stats: large entries in device memory written in pieces.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -168,6 +169,28 @@ int zpk_codec_encode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
 int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs,
                                 const zpk_encode_desc* desc, uint64_t n,
                                 uint8_t* const* dst_ptrs, zpk_encode_result* results);
+
+/* zpk_codec_encode_batch_device for batches that hold LARGE entries: d_src, d_dst and d_results are DEVICE pointers, `desc` is HOST memory
+ * (consumed before the call returns).  An entry with size >= ZPK_OPT_ENC_SPLIT_MIN, size > 512 KiB and a valid method is compressed as
+ * 512 KiB pieces, one wave each, and its frame is assembled ON THE DEVICE: its slot d_dst + dst_offset and d_results[i] end up holding
+ * exactly what zpk_codec_encode_batch_host writes for that entry (frame header, the pieces' blocks in order, the end of the frame;
+ * ZPK_METHOD_NONE: the plain copy; status / detail of the first failing piece; a frame that does not fit dst_capacity is
+ * COMPRESS_FAILED — BUFFER_TOO_SMALL for a stored entry; comp_size = hash = 0 on any failure), hash = XXH3-64 of the whole plaintext by
+ * the whole chip.  Every other entry gets byte for byte what zpk_codec_encode_batch_device gives it.  Nothing outside an entry's
+ * [dst_offset, dst_offset + dst_capacity) is written, whatever its verdict; a failed entry's slot may hold part of its blocks.
+ * Work is enqueued on `stream` (NULL = the codec's own) and the call returns without waiting for it; the results compose with
+ * zpk_codec_pack_batch_device unchanged (the caller uploads `desc` for it).  A third call in a row waits until the first one's tables
+ * have gone up.  ZPK_E_INVALID: an entry's source or slot does not lie inside [0, src_size) / [0, dst_size).
+ * SOURCE SLACK (this call and zpk_codec_encode_batch_device): the kernels load 16 bytes per lane.  The match finder, the literal
+ * copies and the XXH3 passes take a narrower load or the last block again where 16 bytes would pass the end of an entry, but the
+ * contract is that of the host path's staging: the allocation extends at least 16 bytes behind the last source byte of the batch. */
+int zpk_codec_encode_big_device(zpk_codec* c, const uint8_t* d_src, uint64_t src_size,
+                                const zpk_encode_desc* desc /* HOST memory */, uint64_t n,
+                                uint8_t* d_dst, uint64_t dst_size,
+                                zpk_encode_result* d_results /* DEVICE memory */, void* stream);
+/* the most recent zpk_codec_encode_big_device call: out[0] = entries written in pieces, out[1] = their pieces; out[2..7] = 0.  Known when
+ * the call is enqueued: does not synchronise. */
+int zpk_codec_encode_stats(zpk_codec* c, uint32_t out[8]);
 
 /* ---- compressed-size scan + compaction (the serial `write_offset += comp_size` of lib/zpack_write.c:338, for a batch)
  * After an encode batch: offsets[i] = start of entry i's payload in the packed stream (exclusive prefix sum of the

@@ -142,6 +142,25 @@ class Codec:
                                                        dst.data_ptr(), dst.numel(), results_dev.data_ptr(), st),
                   "zpk_codec_encode_batch_device")
 
+    def encode_big_device(self, src, desc, dst, results_dev, stream=None):
+        """A batch that holds large entries: src / dst / results_dev are uint8 CUDA tensors, desc an np array of ENCODE_DESC (host, consumed
+        before the call returns).  Entries of at least OPT_ENC_SPLIT_MIN bytes are compressed in 512 KiB pieces and their frames assembled
+        on the device; asynchronous like encode_batch_device."""
+        self._settle(stream)
+        st = C.c_void_p(stream) if stream else None
+        desc = np.ascontiguousarray(desc, dtype=ENCODE_DESC)
+        self.L.zpk_codec_encode_big_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        self._chk(self.L.zpk_codec_encode_big_device(self.h, src.data_ptr(), src.numel(), desc.ctypes.data, len(desc),
+                                                     dst.data_ptr(), dst.numel(), results_dev.data_ptr(), st),
+                  "zpk_codec_encode_big_device")
+
+    def encode_stats(self):
+        """The last encode_big_device call: entries written in pieces, and their pieces."""
+        a = (C.c_uint32 * 8)()
+        self.L.zpk_codec_encode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        self._chk(self.L.zpk_codec_encode_stats(self.h, a), "encode_stats")
+        return dict(split_entries=a[0], pieces=a[1])
+
     def pack_batch_device(self, slots, desc_dev, results_dev, n, packed, offsets_dev, max_entry_size, stream=None):
         """offsets_dev: int64 CUDA tensor of n + 1; packed: uint8 CUDA tensor or None (sizes only)."""
         self._settle(stream)

@@ -639,6 +639,10 @@ struct zpk_codec {
     hipEvent_t pj_ev[ZPK_PJ_MAX_CHUNKS] = {};           // lz4_pj.h: one event behind every chunk of a large LZ4 frame (its bytes may go home)
     u32  big_last[2] = {0, 0};                         // host decode path, most recent call: entries decoded frame-parallel, their frames
     u64  enc_split_min = ZPK_ENC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_ENC_SPLIT_MIN: entries of at least this many bytes are written as a sequence of frames
+    // zpk_codec_encode_big_device: the tables of one call (descriptors, pieces, entry table, spans) go up from pinned memory behind
+    // whatever the stream still holds; two blocks take turns, the event says that a block's upload has run
+    u8*  h_bigenc[2] = {nullptr, nullptr}; u64 h_bigenc_cap[2] = {0, 0}; hipEvent_t bigenc_ev[2] = {nullptr, nullptr}; u32 bigenc_turn = 0;
+    u32  enc_big_last[2] = {0, 0};                     // ... most recent call: entries written in pieces, their pieces
     DevBuf<u64> d_zarena;                              // decoder: pre-decoded Zstandard sequences, laid out like dst (zstd_fse4.h)
     DevBuf<u32> d_zstate;                              // decoder: per entry, 1 = its sequences are in the arena
     int lz4_hint = -1;           // host path: does the batch hold an LZ4 entry?  -1 = unknown (device path)
@@ -741,6 +745,7 @@ void zpk_codec_destroy(zpk_codec* c)
     if (c->h_pj) (void)hipHostFree(c->h_pj);
     if (c->h_seen) (void)hipHostFree((void*)c->h_seen);
     if (c->h_bigsrc) (void)hipHostFree(c->h_bigsrc);
+    for (int k = 0; k < 2; k++) { if (c->h_bigenc[k]) (void)hipHostFree(c->h_bigenc[k]); if (c->bigenc_ev[k]) (void)hipEventDestroy(c->bigenc_ev[k]); }
     for (SideStream* x : { &c->side, &c->left }) {
         if (x->s) (void)hipStreamDestroy(x->s);
         if (x->fork) (void)hipEventDestroy(x->fork);
@@ -785,9 +790,12 @@ int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
 #define ZPK_WD_ARG
 #endif
 
-// XXH3-64 of `nspans` long spans of `base` (xxh3_span.h): enqueues the two kernels and the copy of the hashes to `h_hash`
-static int xxh3_spans_launch(zpk_codec* c, const u8* base, const zpk_span* h_spans, u64 nspans, u64 part_blocks, u64* h_hash, hipStream_t st)
+// XXH3-64 of `nspans` long spans of `base` (xxh3_span.h): enqueues the upload of the span list and the two kernels; the hashes stay on
+// the device, *d_hash_out says where (inside c->d_xpart, valid until the next call that hashes spans).  `h_spans` must stay as it is
+// until the upload has run: the caller synchronises, or hands pinned memory it keeps.
+static int xxh3_spans_enqueue(zpk_codec* c, const u8* base, const zpk_span* h_spans, u64 nspans, u64 part_blocks, u64** d_hash_out, hipStream_t st)
 {
+    *d_hash_out = nullptr;
     if (nspans == 0) return ZPK_OK;
     if (nspans > 0x7FFFFFFFull) return ZPK_E_INVALID;
     const u64 span_bytes = (nspans * sizeof(zpk_span) + 255) & ~255ull, part_bytes = part_blocks * 64;
@@ -801,6 +809,15 @@ static int xxh3_spans_launch(zpk_codec* c, const u8* base, const zpk_span* h_spa
     if (ngroups) hipLaunchKernelGGL(k_xxh3_partials, dim3((u32)((ngroups + 3) / 4)), dim3(256), 0, st, base, (const zpk_span*)d_spans, (u32)nspans, (u64)0, ngroups, d_part);
     hipLaunchKernelGGL(k_xxh3_chain, dim3((u32)nspans), dim3(64), 0, st, base, (const zpk_span*)d_spans, (const u64*)d_part, d_hash, (u64*)nullptr, (u64)0, ~(u64)0, 1);
     HIPCHK(c, hipGetLastError());
+    *d_hash_out = d_hash;
+    return ZPK_OK;
+}
+// ... and the copy of the hashes to `h_hash`
+static int xxh3_spans_launch(zpk_codec* c, const u8* base, const zpk_span* h_spans, u64 nspans, u64 part_blocks, u64* h_hash, hipStream_t st)
+{
+    u64* d_hash = nullptr;
+    const int rc = xxh3_spans_enqueue(c, base, h_spans, nspans, part_blocks, &d_hash, st);
+    if (rc || !d_hash) return rc;
     HIPCHK(c, hipMemcpyAsync(h_hash, d_hash, nspans * 8, hipMemcpyDeviceToHost, st));
     return ZPK_OK;
 }

@@ -1739,3 +1739,193 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
 }
 
 }  // extern "C"
+
+// ---- large entries that are ALREADY in device memory (zpk_codec_encode_big_device): the pieces of the host path above, and the frame put
+// together on the device — no host between the encode and the finished frame.  The pieces are compressed into the codec's staging
+// (slots of zpk_codec_compress_bound bytes), one scan over their sizes says where each lands, k_big_gather moves them into the caller's
+// slot behind the frame header, k_big_close writes header, end of frame and the entry's result.
+struct BigEncEntry {                                   // one entry written in pieces
+    u64 dst_offset, dst_capacity;                  // its slot
+    u32 entry, first, npieces, method;             // index among the call's entries; its pieces are [first, first + npieces)
+    u32 hl, tl;                                    // bytes of frame header / end of frame (stored: 0, 0)
+    u8  hdr[16], trl[8];                           // big_frame_header / big_frame_trailer
+};
+
+// work item = (piece, span of PK_SPAN bytes of its slot); a piece has at most `spans_per_piece` of them (its bound), those behind its
+// compressed size leave at once.  Piece j of entry i lands at slot_i + hl_i + (offsets[j] - offsets[first_i]); what would land behind
+// dst_capacity - tl (a frame that does not fit: k_big_close says so) is not written.  16 bytes per lane at any alignment, four loads in
+// flight; every byte is read once and written once.
+__global__ __launch_bounds__(256) void k_big_gather(const u8* __restrict__ slots, const zpk_encode_desc* __restrict__ pdesc,
+                                                    const zpk_encode_result* __restrict__ pres, u32 np, const u64* __restrict__ offsets,
+                                                    const u32* __restrict__ piece_entry, const BigEncEntry* __restrict__ big, u32 spans_per_piece,
+                                                    u8* __restrict__ dst)
+{
+    const u32 w = uni((u32)(((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int lane = lane_id();
+    const u32 p = w / spans_per_piece;
+    if (p >= np) return;
+    const u64 size = pk_size(pres, p, np);
+    const u64 from = (u64)(w - p * spans_per_piece) * PK_SPAN;
+    if (from >= size) return;
+    const BigEncEntry* const B = big + piece_entry[p];
+    const u64 cap = B->dst_capacity, limit = cap > B->tl ? cap - B->tl : 0;          // end of what the blocks may use, from the slot's start
+    const u64 at = B->hl + (offsets[p] - offsets[B->first]) + from;
+    if (at >= limit) return;
+    u32 len = (u32)(size - from < PK_SPAN ? size - from : PK_SPAN);
+    if (len > limit - at) len = (u32)(limit - at);
+    const u8* const s = uni_ptr(slots + pdesc[p].dst_offset + from);
+    u8* const d = uni_ptr(dst + B->dst_offset + at);
+    u32 i = (u32)lane * 16u;
+    for (; i + 3u * WAVE * 16u + 16u <= len; i += 4u * WAVE * 16u) {
+        u128 v[4];
+        #pragma unroll
+        for (u32 t = 0; t < 4; t++) v[t] = ld128(s + i + t * WAVE * 16u);
+        #pragma unroll
+        for (u32 t = 0; t < 4; t++) st128(d + i + t * WAVE * 16u, v[t]);
+    }
+    for (; i < len; i += WAVE * 16u) gcopy_upto16(d + i, s + i, len - i < 16u ? len - i : 16u);
+}
+
+// one wave per entry written in pieces: the verdict of its first failing piece, else the frame's length against the slot (the semantics
+// of zpk_codec_encode_batch_host above); header and end of frame go around the blocks k_big_gather has placed
+__global__ __launch_bounds__(64) void k_big_close(const zpk_encode_result* __restrict__ pres, const u64* __restrict__ offsets,
+                                                  const BigEncEntry* __restrict__ big, const u64* __restrict__ hashes, u8* __restrict__ dst,
+                                                  zpk_encode_result* __restrict__ results)
+{
+    const int lane = lane_id();
+    const BigEncEntry* const B = big + blockIdx.x;
+    const u32 first = B->first, npieces = B->npieces, hl = B->hl, tl = B->tl;
+    u32 bad = ~0u;                                                                     // first failing piece among this lane's
+    for (u32 j = (u32)lane; j < npieces && bad == ~0u; j += WAVE) if (pres[first + j].status != R_OK) bad = j;
+    #pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) { const u32 o = (u32)__shfl_xor((int)bad, k, 64); bad = o < bad ? o : bad; }
+    bad = uni(bad);
+    const u64 blocks = uni64(offsets[first + npieces] - offsets[first]);
+    zpk_encode_result r; r.status = R_OK; r.detail = 0; r.comp_size = 0; r.hash = 0;
+    if (bad != ~0u) { const zpk_encode_result f = pres[first + bad]; r.status = f.status; r.detail = f.detail; }
+    else if (hl + blocks + tl > B->dst_capacity) r.status = B->method == ZPK_METHOD_NONE ? R_BUFFER_TOO_SMALL : R_COMPRESS_FAILED;
+    else {
+        u8* const out = uni_ptr(dst + B->dst_offset);
+        if ((u32)lane < hl) st8(out + lane, B->hdr[lane]);
+        if ((u32)lane < tl) st8(out + hl + blocks + lane, B->trl[lane]);
+        r.comp_size = hl + blocks + tl;
+        r.hash = hashes[blockIdx.x];
+    }
+    lane0_guard();
+    if (lane == 0) results[B->entry] = r;
+}
+
+// a pinned block of `need` bytes for one call's tables: the two blocks take turns, and a block is handed out again only when the upload
+// that read it last has run (the caller records c->bigenc_ev[*slot] behind its uploads)
+static int big_tables_block(zpk_codec* c, u64 need, u8** out, int* slot)
+{
+    const int k = (int)(c->bigenc_turn++ & 1u);
+    if (!c->bigenc_ev[k]) HIPCHK(c, hipEventCreateWithFlags(&c->bigenc_ev[k], hipEventDisableTiming));
+    else HIPCHK(c, hipEventSynchronize(c->bigenc_ev[k]));
+    if (c->h_bigenc_cap[k] < need) {
+        if (c->h_bigenc[k]) (void)hipHostFree(c->h_bigenc[k]);
+        c->h_bigenc[k] = nullptr; c->h_bigenc_cap[k] = 0;
+        const u64 want = need + need / 4 + 4096;
+        if (hipHostMalloc((void**)&c->h_bigenc[k], want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); c->h_bigenc[k] = nullptr;
+            snprintf(c->err, sizeof(c->err), "pinned tables: out of memory"); return ZPK_E_NOMEM;
+        }
+        c->h_bigenc_cap[k] = want;
+    }
+    *out = c->h_bigenc[k]; *slot = k;
+    return ZPK_OK;
+}
+
+extern "C" {
+
+int zpk_codec_encode_big_device(zpk_codec* c, const uint8_t* d_src, uint64_t src_size, const zpk_encode_desc* desc, uint64_t n,
+                                uint8_t* d_dst, uint64_t dst_size, zpk_encode_result* d_results, void* stream)
+{
+    if (!c || (n && (!desc || !d_results))) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    c->enc_big_last[0] = c->enc_big_last[1] = 0;
+    if (n == 0) return ZPK_OK;
+    if (n > 0x7FFFFFFFull) return ZPK_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    auto is_split = [&](u64 i) { return desc[i].size >= c->enc_split_min && desc[i].size > ZPK_ENC_PIECE && desc[i].method <= ZPK_METHOD_LZ4; };
+    u64 np = 0, ns = 0;
+    for (u64 i = 0; i < n; i++) {
+        if (desc[i].src_offset > src_size || desc[i].size > src_size - desc[i].src_offset ||
+            desc[i].dst_offset > dst_size || desc[i].dst_capacity > dst_size - desc[i].dst_offset) return ZPK_E_INVALID;
+        if (is_split(i)) { np += (desc[i].size + ZPK_ENC_PIECE - 1) / ZPK_ENC_PIECE; ns++; }
+    }
+    if (np > 0x7FFFFFFFull) return ZPK_E_INVALID;
+    // the tables, in the order they lie in the pinned block and (all but the spans) in c->d_desc: the call's descriptors — an entry
+    // written in pieces stands there as an EMPTY STORED entry, which the one-wave launch passes over without writing a byte of its slot
+    // (k_big_close writes its result later) —, the pieces, the entry table, piece -> entry, the spans to hash
+    const u64 o_piece = n * sizeof(zpk_encode_desc), o_big = o_piece + np * sizeof(zpk_encode_desc), o_pe = o_big + ns * sizeof(BigEncEntry);
+    const u64 up_bytes = (o_pe + np * sizeof(u32) + 7) & ~7ull, all_bytes = up_bytes + ns * sizeof(zpk_span);
+    u8* h = nullptr; int slot = 0, rc;
+    if ((rc = big_tables_block(c, all_bytes, &h, &slot))) return rc;
+    zpk_encode_desc* const hd = (zpk_encode_desc*)h; zpk_encode_desc* const hp = (zpk_encode_desc*)(h + o_piece);
+    BigEncEntry* const hb = (BigEncEntry*)(h + o_big); u32* const hpe = (u32*)(h + o_pe); zpk_span* const spans = (zpk_span*)(h + up_bytes);
+    u64 k = 0, e = 0, out_total = 0, part_blocks = 0, max_cap = 0;
+    for (u64 i = 0; i < n; i++) {
+        hd[i] = desc[i];
+        if (!is_split(i)) continue;
+        hd[i].method = ZPK_METHOD_NONE; hd[i].size = 0; hd[i].dst_capacity = 0; hd[i].level = 0;
+        const u64 pieces = (desc[i].size + ZPK_ENC_PIECE - 1) / ZPK_ENC_PIECE;
+        BigEncEntry& B = hb[e];
+        memset(&B, 0, sizeof(B));
+        B.dst_offset = desc[i].dst_offset; B.dst_capacity = desc[i].dst_capacity;
+        B.entry = (u32)i; B.first = (u32)k; B.npieces = (u32)pieces; B.method = desc[i].method;
+        if (desc[i].method != ZPK_METHOD_NONE) { B.hl = big_frame_header(desc[i].method, desc[i].size, B.hdr); B.tl = big_frame_trailer(desc[i].method, B.trl); }
+        for (u64 j = 0; j < pieces; j++, k++) {
+            hp[k] = desc[i];
+            hp[k].src_offset = desc[i].src_offset + j * ZPK_ENC_PIECE;
+            hp[k].size = j + 1 == pieces ? desc[i].size - j * ZPK_ENC_PIECE : (u64)ZPK_ENC_PIECE;
+            hp[k].dst_capacity = zpk_codec_compress_bound(desc[i].method, hp[k].size);
+            hp[k].method |= ZPK_EF_PIECE;
+            hp[k].dst_offset = out_total; out_total += (hp[k].dst_capacity + 255) & ~255ull;
+            if (hp[k].dst_capacity > max_cap) max_cap = hp[k].dst_capacity;
+            hpe[k] = (u32)e;
+        }
+        spans[e].off = desc[i].src_offset; spans[e].len = desc[i].size; spans[e].part_base = part_blocks;
+        part_blocks += xxh3_span_blocks(desc[i].size);
+        e++;
+    }
+    const u32 spans_per_piece = (u32)((max_cap + PK_SPAN - 1) / PK_SPAN);
+    const u64 gather_waves = np * spans_per_piece;
+    if (gather_waves > 0x3FFFFFFFull) return ZPK_E_INVALID;
+    if ((rc = grow(c, c->d_desc, up_bytes))) return rc;
+    if (ns && ((rc = grow(c, c->d_dst, out_total + 64)) || (rc = grow(c, c->d_res, np * sizeof(zpk_encode_result))) ||
+               (rc = grow(c, c->d_packoff, (np + 1) * sizeof(u64))))) return rc;
+    u8* const dt = (u8*)c->d_desc;
+    HIPCHK(c, hipMemcpyAsync(dt, h, up_bytes, hipMemcpyHostToDevice, st));
+    u64* d_hash = nullptr;
+    rc = xxh3_spans_enqueue(c, d_src, spans, ns, part_blocks, &d_hash, st);           // the hashes of the entries in pieces: by the whole chip, over the plaintext where it lies
+    HIPCHK(c, hipEventRecord(c->bigenc_ev[slot], st));                                 // (behind the last upload out of the block, whatever rc says)
+    if (rc) return rc;
+    if (ns < n && (rc = encode_launch(c, d_src, (const zpk_encode_desc*)dt, n, d_dst, d_results, st))) return rc;      // the others: as zpk_codec_encode_batch_device does them
+    if (ns == 0) return ZPK_OK;
+    const zpk_encode_desc* const dp = (const zpk_encode_desc*)(dt + o_piece);
+    const zpk_encode_result* const dr = (const zpk_encode_result*)c->d_res;
+    u64* const doff = (u64*)c->d_packoff;
+    if ((rc = encode_launch(c, d_src, dp, np, c->d_dst, (zpk_encode_result*)c->d_res, st)) ||
+        (rc = pack_launch(c, nullptr, dp, dr, np, nullptr, 0, doff, 0, st))) return rc;
+    if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_PACK][0], st);
+    hipLaunchKernelGGL(k_big_gather, dim3((u32)((gather_waves + 3) / 4)), dim3(256), 0, st, (const u8*)c->d_dst, dp, dr, (u32)np, (const u64*)doff,
+                       (const u32*)(dt + o_pe), (const BigEncEntry*)(dt + o_big), spans_per_piece, d_dst);
+    if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_PACK][1], st);
+    hipLaunchKernelGGL(k_big_close, dim3((u32)ns), dim3(64), 0, st, dr, (const u64*)doff, (const BigEncEntry*)(dt + o_big), (const u64*)d_hash, d_dst, d_results);
+    HIPCHK(c, hipGetLastError());
+    c->enc_big_last[0] = (u32)ns; c->enc_big_last[1] = (u32)np;
+    return ZPK_OK;
+}
+
+int zpk_codec_encode_stats(zpk_codec* c, uint32_t out[8])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    memset(out, 0, 8 * sizeof(uint32_t));
+    out[0] = c->enc_big_last[0]; out[1] = c->enc_big_last[1];
+    return ZPK_OK;
+}
+
+}  // extern "C"
