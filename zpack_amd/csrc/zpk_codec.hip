@@ -37,6 +37,7 @@
 #include "lz4_pj.h"
 #include "zstd_pj.h"
 #include "host_walk.h"                           // the host parsers of untrusted frame / block headers (plain C++, built under sanitizers by tools/hostfuzz)
+#include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
 
 using namespace zpk;
 
@@ -582,7 +583,6 @@ __global__ __launch_bounds__(256) void k_hash(const u8* __restrict__ src, const 
 
 #define ZPK_DEC_SPLIT_MIN_DEFAULT (256ull << 10)     // (round 5: a single 512 KiB LZ4 entry is 0.66 ms block-parallel against 3.3 ms by one wave, 1 MiB of Zstandard 4.3 against 31.7: tools/mid_entry_rate.py)
 #define ZPK_ENC_SPLIT_MIN_DEFAULT (2ull << 20)
-#define ZPK_ENC_PIECE (512u << 10)                 // = ZPK_CS_PIECE of the streaming writer
 #ifndef ZPK_PJ_CHUNK_BLOCKS
 #define ZPK_PJ_CHUNK_BLOCKS 512u                   // lz4_pj.h: blocks per chunk = 32 MiB of output, 128 MiB of byte references (the Infinity Cache holds 256)
 #endif
@@ -1070,9 +1070,46 @@ static int pin_ready(zpk_codec* c)
     return ZPK_OK;
 }
 
+// One piece [p0, p1) of a staged range, moved between its pinned buffer and the buffers of those of the n entries that reach into it (entry
+// i owns bytes [off(i), off(i) + len(i)) of the range, ascending in i; ei: the first that may, kept from piece to piece) by a few host
+// threads: one thread copies at ~22 GB/s, the bus brings ~50.
+// move(i, in_entry, in_piece, bytes) copies `bytes` bytes, at in_entry of entry i and at in_piece of the piece, whichever way the caller goes.
+// Eight entries or more are dealt out by count; of a few large entries the piece's BYTES are cut among the threads (one entry of 256 MiB
+// came home at one thread's rate).  A piece below 4 MiB is one thread's.
+extern "C++" {
+template <class OffFn, class LenFn, class MoveFn>
+static void staged_piece_copy(u64 p0, u64 p1, u64 n, u64& ei, OffFn off, LenFn len, MoveFn move)
+{
+    while (ei < n && off(ei) + len(ei) <= p0) ei++;
+    u64 ej = ei;
+    while (ej < n && off(ej) < p1) ej++;
+    const u64 cnt = ej - ei, span = p1 - p0;
+    const unsigned T = span >= (4u << 20) ? ZPK_SCATTER_THREADS : 1u;
+    auto cut = [&](unsigned t) { return t >= T ? p1 : p0 + ((span * t / T) & ~(u64)4095); };
+    // share t of T: entries [lo_i, hi_i), of each what lies in bytes [lo_b, hi_b)
+    auto share = [&](unsigned t) {
+        const bool by_bytes = cnt < 8;
+        const u64 lo_i = by_bytes ? ei : ei + cnt * t / T, hi_i = by_bytes ? ej : ei + cnt * (t + 1) / T;
+        const u64 lo_b = by_bytes ? cut(t) : p0, hi_b = by_bytes ? cut(t + 1) : p1;
+        for (u64 i = lo_i; i < hi_i; i++) {
+            const u64 o = off(i), l = len(i);
+            const u64 a = o > lo_b ? o : lo_b, z = o + l < hi_b ? o + l : hi_b;
+            if (z > a) move(i, a - o, a - p0, z - a);
+        }
+    };
+    // (a thread that cannot be started must not unwind through the C ABI: its share is copied inline instead)
+    std::thread th[ZPK_SCATTER_THREADS - 1];
+    bool started[ZPK_SCATTER_THREADS - 1] = {};
+    for (unsigned t = 1; t < T; t++) {
+        try { th[t - 1] = std::thread(share, t); started[t - 1] = true; }
+        catch (...) { started[t - 1] = false; }
+    }
+    share(0);
+    for (unsigned t = 1; t < T; t++) { if (started[t - 1]) th[t - 1].join(); else share(t); }
+}
+
 // Device range [d_base, d_base + total) back to the host in pieces of ZPK_PIN_CHUNK bytes through the two pinned buffers; piece j + 1 is
 // on the bus while piece j is scattered: entry i owns bytes [off(i), off(i) + len(i)) of the range (ascending in i) and goes to dst_ptrs[i].
-extern "C++" {
 struct NoPre { hipError_t operator()(u64) const { return hipSuccess; } };
 // pre(q1): called before bytes below q1 of the range are copied (the pipeline makes the download stream wait for their decode there)
 template <class OffFn, class LenFn, class PreFn = NoPre>
@@ -1100,50 +1137,7 @@ static int d2h_scatter(zpk_codec* c, const u8* d_base, u64 total, u64 n, uint8_t
         }
         e = hipEventSynchronize(c->pin_ev[k]);
         if (e != hipSuccess) break;
-        while (ei < n && off(ei) + len(ei) <= p0) ei++;
-        u64 ej = ei;
-        while (ej < n && off(ej) < p1) ej++;
-        // the scatter of one piece, split over a few host threads by entry count (one thread copies at ~22 GB/s, the bus brings ~50)
-        auto part = [&](u64 lo_i, u64 hi_i) {
-            for (u64 i = lo_i; i < hi_i; i++) {
-                const u64 o = off(i), l = len(i);
-                const u64 a = o > p0 ? o : p0, z = o + l < p1 ? o + l : p1;
-                if (z > a) memcpy(dst_ptrs[i] + (a - o), c->h_pin[k] + (a - p0), z - a);
-            }
-        };
-        const u64 cnt = ej - ei;
-        const unsigned T = p1 - p0 >= (4u << 20) ? ZPK_SCATTER_THREADS : 1u;
-        if (T <= 1) part(ei, ej);
-        else if (cnt < 8) {
-            // a few large entries: the piece's BYTES are split over the threads (one entry of 256 MiB came home at one thread's rate)
-            auto bytes = [&](u64 lo_b, u64 hi_b) {
-                for (u64 i = ei; i < ej; i++) {
-                    const u64 o = off(i), l = len(i);
-                    const u64 a = o > lo_b ? o : lo_b, z = o + l < hi_b ? o + l : hi_b;
-                    if (z > a) memcpy(dst_ptrs[i] + (a - o), c->h_pin[k] + (a - p0), z - a);
-                }
-            };
-            const u64 span = p1 - p0;
-            auto cut = [&](unsigned t) { return t >= T ? p1 : p0 + ((span * t / T) & ~(u64)4095); };
-            std::thread th[ZPK_SCATTER_THREADS - 1];
-            bool started[ZPK_SCATTER_THREADS - 1] = {};
-            for (unsigned t = 1; t < T; t++) {
-                try { th[t - 1] = std::thread(bytes, cut(t), cut(t + 1)); started[t - 1] = true; }
-                catch (...) { started[t - 1] = false; }
-            }
-            bytes(p0, cut(1));
-            for (unsigned t = 1; t < T; t++) { if (started[t - 1]) th[t - 1].join(); else bytes(cut(t), cut(t + 1)); }
-        } else {
-            // (a thread that cannot be started must not unwind through the C ABI: its share is copied inline instead)
-            std::thread th[ZPK_SCATTER_THREADS - 1];
-            bool started[ZPK_SCATTER_THREADS - 1] = {};
-            for (unsigned t = 1; t < T; t++) {
-                try { th[t - 1] = std::thread(part, ei + cnt * t / T, ei + cnt * (t + 1) / T); started[t - 1] = true; }
-                catch (...) { started[t - 1] = false; }
-            }
-            part(ei, ei + cnt / T);
-            for (unsigned t = 1; t < T; t++) { if (started[t - 1]) th[t - 1].join(); else part(ei + cnt * t / T, ei + cnt * (t + 1) / T); }
-        }
+        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(dst_ptrs[i] + in_entry, c->h_pin[k] + in_piece, bytes); });
     }
     return ZPK_OK;
 }
@@ -1168,48 +1162,7 @@ static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t*
         const int k = (int)(j & 1);
         const u64 p0 = j * ZPK_PIN_CHUNK, p1 = p0 + ZPK_PIN_CHUNK < total ? p0 + ZPK_PIN_CHUNK : total;
         if (used[k]) { e = hipEventSynchronize(evs[k]); if (e != hipSuccess) break; }      // the buffer's previous piece has left
-        while (ei < n && off(ei) + len(ei) <= p0) ei++;
-        u64 ej = ei;
-        while (ej < n && off(ej) < p1) ej++;
-        auto part = [&](u64 lo_i, u64 hi_i) {
-            for (u64 i = lo_i; i < hi_i; i++) {
-                const u64 o = off(i), l = len(i);
-                const u64 a = o > p0 ? o : p0, z = o + l < p1 ? o + l : p1;
-                if (z > a) memcpy(pins[k] + (a - p0), src_ptrs[i] + (a - o), z - a);
-            }
-        };
-        const u64 cnt = ej - ei;
-        const unsigned T = p1 - p0 >= (4u << 20) ? ZPK_SCATTER_THREADS : 1u;
-        if (T <= 1) part(ei, ej);
-        else if (cnt < 8) {
-            // a few large entries: the piece's BYTES are split over the threads (as in d2h_scatter)
-            auto bytes = [&](u64 lo_b, u64 hi_b) {
-                for (u64 i = ei; i < ej; i++) {
-                    const u64 o = off(i), l = len(i);
-                    const u64 a = o > lo_b ? o : lo_b, z = o + l < hi_b ? o + l : hi_b;
-                    if (z > a) memcpy(pins[k] + (a - p0), src_ptrs[i] + (a - o), z - a);
-                }
-            };
-            const u64 span = p1 - p0;
-            auto cut = [&](unsigned t) { return t >= T ? p1 : p0 + ((span * t / T) & ~(u64)4095); };
-            std::thread th[ZPK_SCATTER_THREADS - 1];
-            bool started[ZPK_SCATTER_THREADS - 1] = {};
-            for (unsigned t = 1; t < T; t++) {
-                try { th[t - 1] = std::thread(bytes, cut(t), cut(t + 1)); started[t - 1] = true; }
-                catch (...) { started[t - 1] = false; }
-            }
-            bytes(p0, cut(1));
-            for (unsigned t = 1; t < T; t++) { if (started[t - 1]) th[t - 1].join(); else bytes(cut(t), cut(t + 1)); }
-        } else {
-            std::thread th[ZPK_SCATTER_THREADS - 1];
-            bool started[ZPK_SCATTER_THREADS - 1] = {};
-            for (unsigned t = 1; t < T; t++) {
-                try { th[t - 1] = std::thread(part, ei + cnt * t / T, ei + cnt * (t + 1) / T); started[t - 1] = true; }
-                catch (...) { started[t - 1] = false; }
-            }
-            part(ei, ei + cnt / T);
-            for (unsigned t = 1; t < T; t++) { if (started[t - 1]) th[t - 1].join(); else part(ei + cnt * t / T, ei + cnt * (t + 1) / T); }
-        }
+        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(pins[k] + in_piece, src_ptrs[i] + in_entry, bytes); });
         e = hipMemcpyAsync(d_base + p0, pins[k], p1 - p0, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipEventRecord(evs[k], st);
         used[k] = true;

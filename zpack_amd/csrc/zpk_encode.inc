@@ -1486,23 +1486,7 @@ int zpk_codec_pack_batch_device(zpk_codec* c, const uint8_t* slots, const zpk_en
     return pack_launch(c, slots, desc, results, n, packed, packed_cap, offsets, max_entry_size, stream ? (hipStream_t)stream : c->stream);
 }
 
-size_t zpk_codec_compress_bound(uint32_t method, size_t n)
-{
-    switch (method) {
-    case ZPK_METHOD_NONE: return n;
-    case ZPK_METHOD_ZSTD: {                                                        // >= ZSTD_COMPRESSBOUND(n), room for raw blocks
-        size_t zb = n + (n >> 8) + (n < (128u << 10) ? (((128u << 10) - n) >> 11) : 0);
-        size_t raw = n + 13 + 3 * (n / (128u << 10) + 1);
-        return zb > raw ? zb : raw;
-    }
-    case ZPK_METHOD_LZ4: {                                                          // LZ4F_compressBound(n, NULL) of lz4 1.9.x
-        size_t max_src = n + 65535, full = max_src / 65536, part = max_src & 65535;
-        size_t last = n == 0 ? part : 0;
-        return 8 * (full + (last > 0)) + 65536 * full + last + 8;
-    }
-    default: return 0;
-    }
-}
+size_t zpk_codec_compress_bound(uint32_t method, size_t n) { return enc_compress_bound(method, n); }       // (enc_plan.h)
 
 }  // extern "C"
 // ---- largest entries first: an entry is tens of ms of ONE wave and a batch is a few rounds of the resident waves, so a 1 MiB entry that
@@ -1602,27 +1586,9 @@ int zpk_codec_encode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
 // each other they slow each other down by more than the overlap gains.  Removed; the stages run one after the other.)
 
 extern "C" {
-// Entries of at least c->enc_split_min bytes go to the device as 512 KiB pieces, one wave each.  Round 4 made every piece a frame of its
-// own; since round 5 a piece is a run of BLOCKS and the entry is ONE frame — what the reference writer produces (lib/zpack_write.c:179,
-// :204-210): the host puts the frame header in front of the first piece's blocks and closes the frame behind the last one (LZ4: the
-// EndMark; Zstandard: an empty last block), the packed stream keeps the pieces in order.  A piece's first block has no match into the
-// piece before it (its table starts empty): 0.1 % of ratio.  The entry's hash is that of the whole plaintext (the two kernels above).
-static u32 big_frame_header(u32 method, u64 len, u8* h)
-{
-    if (method == ZPK_METHOD_LZ4) { const u8 b[7] = {0x04, 0x22, 0x4D, 0x18, 0x40, 0x40, 0xC0}; memcpy(h, b, 7); return 7; }
-    // Zstandard: magic, Frame_Header_Descriptor (content size of 4 or 8 bytes, not single-segment), Window_Descriptor 64 KiB (no match of
-    // this encoder reaches further, and its blocks are <= 64 KiB), Frame_Content_Size
-    const u32 fcs = len <= 0xFFFFFFFFull ? 4u : 8u;
-    const u8 b[6] = {0x28, 0xB5, 0x2F, 0xFD, (u8)((fcs == 4 ? 2u : 3u) << 6), 0x30};
-    memcpy(h, b, 6);
-    for (u32 i = 0; i < fcs; i++) h[6 + i] = (u8)(len >> (8 * i));
-    return 6 + fcs;
-}
-static u32 big_frame_trailer(u32 method, u8* t)
-{
-    if (method == ZPK_METHOD_LZ4) { memset(t, 0, 4); return 4; }               // EndMark
-    t[0] = 0x01; t[1] = 0x00; t[2] = 0x00; return 3;                             // Last_Block, Raw_Block, Block_Size 0
-}
+// Entries of at least c->enc_split_min bytes go to the device as 512 KiB pieces, one wave each, and come back as ONE frame (enc_plan.h: which
+// entries, their pieces, the frame's header and end, the entry's verdict); the packed stream keeps the pieces in order.  The entry's hash
+// is that of the whole plaintext (the two kernels of xxh3_span.h).
 int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, const zpk_encode_desc* desc, uint64_t n,
                                 uint8_t* const* dst_ptrs, zpk_encode_result* results)
 {
@@ -1630,40 +1596,31 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    // pieces: entry i is pieces [first[i], first[i + 1])
+    const u64 split_min = c->enc_split_min;
     u64 np = 0, nsplit = 0;
-    for (u64 i = 0; i < n; i++) {
-        const bool split = desc[i].size >= c->enc_split_min && desc[i].size > ZPK_ENC_PIECE && desc[i].method <= ZPK_METHOD_LZ4;
-        np += split ? (desc[i].size + ZPK_ENC_PIECE - 1) / ZPK_ENC_PIECE : 1;
-        nsplit += split;
-    }
+    for (u64 i = 0; i < n; i++) { np += enc_piece_count(split_min, desc[i]); nsplit += enc_is_split(split_min, desc[i]); }
     if (np > 0x7FFFFFFFull) return ZPK_E_INVALID;
-    zpk_encode_desc* hd = (zpk_encode_desc*)malloc(np * sizeof(zpk_encode_desc));
-    u64* first = (u64*)malloc((n + 1) * sizeof(u64));
-    zpk_encode_result* hr = np != n ? (zpk_encode_result*)malloc(np * sizeof(zpk_encode_result)) : results;
-    u64* h_off = (u64*)malloc((np + 1) * sizeof(u64));
-    zpk_span* spans = nsplit ? (zpk_span*)malloc(nsplit * sizeof(zpk_span)) : nullptr;
-    u64* h_hash = nsplit ? (u64*)malloc(nsplit * sizeof(u64)) : nullptr;
-    struct Free { void* p[6]; ~Free() { for (void* x : p) free(x); } } guard = { { hd, first, np != n ? hr : nullptr, h_off, spans, h_hash } };
-    if (!hd || !first || !hr || !h_off || (nsplit && (!spans || !h_hash))) return ZPK_E_NOMEM;
+    // the call's tables, one block: the pieces (entry i is pieces [first[i], first[i + 1])), their results and packed offsets; per entry
+    // where its payload goes; per entry in pieces its span and hash
+    const bool framed = np != n;
+    u8* at = (u8*)malloc(np * (sizeof(zpk_encode_desc) + 8) + (n + 2) * 8 + (framed ? np * sizeof(zpk_encode_result) + n * sizeof(u8*) : 0) +
+                         nsplit * (sizeof(zpk_span) + 8));
+    struct Free { void* p; ~Free() { free(p); } } guard = { at };
+    if (!at) return ZPK_E_NOMEM;
+    auto take = [&](u64 bytes) { u8* const p = at; at += bytes; return p; };                  // (every size a multiple of 8)
+    zpk_encode_desc* const hd = (zpk_encode_desc*)take(np * sizeof(zpk_encode_desc));
+    u64* const first = (u64*)take((n + 1) * 8);
+    u64* const h_off = (u64*)take((np + 1) * 8);
+    zpk_encode_result* const hr = framed ? (zpk_encode_result*)take(np * sizeof(zpk_encode_result)) : results;
+    u8** const payload = framed ? (u8**)take(n * sizeof(u8*)) : nullptr;
+    zpk_span* const spans = (zpk_span*)take(nsplit * sizeof(zpk_span));
+    u64* const h_hash = (u64*)take(nsplit * 8);
     u64 in_total = 0, out_total = 0, k = 0, ns = 0, part_blocks = 0, max_cap = 0;
     for (u64 i = 0; i < n; i++) {
         first[i] = k;
-        const bool split = desc[i].size >= c->enc_split_min && desc[i].size > ZPK_ENC_PIECE && desc[i].method <= ZPK_METHOD_LZ4;
-        const u64 pieces = split ? (desc[i].size + ZPK_ENC_PIECE - 1) / ZPK_ENC_PIECE : 1;
-        for (u64 j = 0; j < pieces; j++, k++) {
-            hd[k] = desc[i];
-            hd[k].src_offset = in_total + j * ZPK_ENC_PIECE;
-            hd[k].size = split ? (j + 1 == pieces ? desc[i].size - j * ZPK_ENC_PIECE : (u64)ZPK_ENC_PIECE) : desc[i].size;
-            hd[k].dst_capacity = split ? zpk_codec_compress_bound(desc[i].method, hd[k].size) : desc[i].dst_capacity;
-            if (split) hd[k].method |= ZPK_EF_PIECE;
-            hd[k].dst_offset = out_total; out_total += (hd[k].dst_capacity + 255) & ~255ull;
-            if (hd[k].dst_capacity > max_cap) max_cap = hd[k].dst_capacity;
-        }
-        if (split) {
-            spans[ns].off = in_total; spans[ns].len = desc[i].size; spans[ns].part_base = part_blocks; ns++;
-            part_blocks += xxh3_span_blocks(desc[i].size);
-        }
+        const EncSpan sp = enc_emit_entry(split_min, desc[i], in_total, hd + k, out_total, max_cap);
+        k += enc_piece_count(split_min, desc[i]);
+        if (enc_is_split(split_min, desc[i])) { spans[ns++] = zpk_span{ sp.off, sp.len, part_blocks }; part_blocks += xxh3_span_blocks(sp.len); }
         in_total += (desc[i].size + 255 + 16) & ~255ull;
     }
     first[n] = k;
@@ -1694,45 +1651,30 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
     e = hipMemcpyAsync(hr, c->d_res, np * sizeof(zpk_encode_result), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h_off, c->d_packoff, (np + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && np != n) {
-        // an entry's verdict is that of its first failing piece; its size the sum of its frames, which must fit what the caller gave
+    if (e == hipSuccess && framed) {
+        // an entry in pieces: its verdict (enc_verdict: that of its first failing piece, else its frame against what the caller gave),
+        // and where its blocks go: behind its frame header, which — like the end of the frame — the host writes itself, here
         ns = 0;
         for (u64 i = 0; i < n; i++) {
             const u64 a = first[i], b = first[i + 1];
-            zpk_encode_result r = hr[a];
-            if (b - a > 1) {
-                r.comp_size = 0;
-                for (u64 j = a; j < b && r.status == 0; j++) { if (hr[j].status) { r.status = hr[j].status; r.detail = hr[j].detail; } else r.comp_size += hr[j].comp_size; }
-                r.hash = h_hash[ns++];
-                if (desc[i].method != ZPK_METHOD_NONE) { u8 tmp[16]; r.comp_size += big_frame_header(desc[i].method, desc[i].size, tmp) + big_frame_trailer(desc[i].method, tmp); }
-                if (r.status == 0 && r.comp_size > desc[i].dst_capacity) { r.status = desc[i].method == ZPK_METHOD_NONE ? R_BUFFER_TOO_SMALL : R_COMPRESS_FAILED; r.detail = 0; }
-                if (r.status) { r.comp_size = 0; r.hash = 0; }
-            }
-            results[i] = r;
+            payload[i] = dst_ptrs[i];
+            if (b - a == 1) { results[i] = hr[a]; continue; }
+            const zpk_encode_result* failed = nullptr;
+            for (u64 j = a; j < b && !failed; j++) if (hr[j].status) failed = &hr[j];
+            const EncEnvelope E = enc_envelope(desc[i].method, desc[i].size);
+            const u64 blocks = h_off[b] - h_off[a];
+            results[i] = enc_verdict(failed, blocks, E.hl, E.tl, desc[i].dst_capacity, desc[i].method, h_hash[ns++]);
+            if (results[i].status != 0 || E.hl == 0) continue;                         // (a stored entry has no envelope)
+            memcpy(dst_ptrs[i], E.hdr, E.hl);
+            memcpy(dst_ptrs[i] + E.hl + blocks, E.trl, E.tl);
+            payload[i] += E.hl;
         }
     }
     if (e == hipSuccess && h_off[np]) {
-        // the packed stream comes back through the pinned staging buffers, scattered piece by piece (zpk_codec.hip, d2h_scatter); the
-        // blocks of a split entry land behind its frame header, which — like the end of the frame — the host writes itself
-        std::vector<uint8_t*> payload_ptr;
-        const bool framed = np != n;
-        auto is_framed = [&](u64 i) { return first[i + 1] - first[i] > 1 && desc[i].method != ZPK_METHOD_NONE && results[i].status == 0; };
-        if (framed) {
-            try { payload_ptr.resize(n); } catch (...) { return ZPK_E_NOMEM; }
-            for (u64 i = 0; i < n; i++) { u8 tmp[16]; payload_ptr[i] = dst_ptrs[i] + (is_framed(i) ? big_frame_header(desc[i].method, desc[i].size, tmp) : 0u); }
-        }
-        auto payload_len = [&](u64 i) -> u64 {
-            if (results[i].status != 0) return 0ull;
-            if (!framed || !is_framed(i)) return (u64)results[i].comp_size;
-            return h_off[first[i + 1]] - h_off[first[i]];
-        };
-        const int src = d2h_scatter(c, c->d_packed, h_off[np], n, framed ? payload_ptr.data() : dst_ptrs, [&](u64 i) { return h_off[first[i]]; }, payload_len, e);
+        // the packed stream comes back through the pinned staging buffers, scattered piece by piece (zpk_codec.hip, d2h_scatter)
+        auto payload_len = [&](u64 i) -> u64 { return results[i].status != 0 ? 0ull : h_off[first[i + 1]] - h_off[first[i]]; };
+        const int src = d2h_scatter(c, c->d_packed, h_off[np], n, framed ? payload : dst_ptrs, [&](u64 i) { return h_off[first[i]]; }, payload_len, e);
         if (src) return src;
-        if (framed && e == hipSuccess)
-            for (u64 i = 0; i < n; i++) if (is_framed(i)) {
-                const u32 hl = big_frame_header(desc[i].method, desc[i].size, dst_ptrs[i]);
-                (void)big_frame_trailer(desc[i].method, dst_ptrs[i] + hl + payload_len(i));
-            }
     }
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "encode: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     return ZPK_OK;
@@ -1747,9 +1689,9 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
 struct BigEncEntry {                                   // one entry written in pieces
     u64 dst_offset, dst_capacity;                  // its slot
     u32 entry, first, npieces, method;             // index among the call's entries; its pieces are [first, first + npieces)
-    u32 hl, tl;                                    // bytes of frame header / end of frame (stored: 0, 0)
-    u8  hdr[16], trl[8];                           // big_frame_header / big_frame_trailer
+    EncEnvelope env;                               // its frame header and end of frame (enc_plan.h)
 };
+static_assert(ENC_R_OK == R_OK && ENC_R_BUFFER_TOO_SMALL == R_BUFFER_TOO_SMALL && ENC_R_COMPRESS_FAILED == R_COMPRESS_FAILED, "enc_plan.h states zpack_result's values itself");
 
 // work item = (piece, span of PK_SPAN bytes of its slot); a piece has at most `spans_per_piece` of them (its bound), those behind its
 // compressed size leave at once.  Piece j of entry i lands at slot_i + hl_i + (offsets[j] - offsets[first_i]); what would land behind
@@ -1768,8 +1710,8 @@ __global__ __launch_bounds__(256) void k_big_gather(const u8* __restrict__ slots
     const u64 from = (u64)(w - p * spans_per_piece) * PK_SPAN;
     if (from >= size) return;
     const BigEncEntry* const B = big + piece_entry[p];
-    const u64 cap = B->dst_capacity, limit = cap > B->tl ? cap - B->tl : 0;          // end of what the blocks may use, from the slot's start
-    const u64 at = B->hl + (offsets[p] - offsets[B->first]) + from;
+    const u64 cap = B->dst_capacity, limit = cap > B->env.tl ? cap - B->env.tl : 0;          // end of what the blocks may use, from the slot's start
+    const u64 at = B->env.hl + (offsets[p] - offsets[B->first]) + from;
     if (at >= limit) return;
     u32 len = (u32)(size - from < PK_SPAN ? size - from : PK_SPAN);
     if (len > limit - at) len = (u32)(limit - at);
@@ -1786,30 +1728,26 @@ __global__ __launch_bounds__(256) void k_big_gather(const u8* __restrict__ slots
     for (; i < len; i += WAVE * 16u) gcopy_upto16(d + i, s + i, len - i < 16u ? len - i : 16u);
 }
 
-// one wave per entry written in pieces: the verdict of its first failing piece, else the frame's length against the slot (the semantics
-// of zpk_codec_encode_batch_host above); header and end of frame go around the blocks k_big_gather has placed
+// one wave per entry written in pieces: its verdict (enc_verdict, the one zpk_codec_encode_batch_host above gives); header and end of
+// frame go around the blocks k_big_gather has placed
 __global__ __launch_bounds__(64) void k_big_close(const zpk_encode_result* __restrict__ pres, const u64* __restrict__ offsets,
                                                   const BigEncEntry* __restrict__ big, const u64* __restrict__ hashes, u8* __restrict__ dst,
                                                   zpk_encode_result* __restrict__ results)
 {
     const int lane = lane_id();
     const BigEncEntry* const B = big + blockIdx.x;
-    const u32 first = B->first, npieces = B->npieces, hl = B->hl, tl = B->tl;
+    const u32 first = B->first, npieces = B->npieces, hl = B->env.hl, tl = B->env.tl;
     u32 bad = ~0u;                                                                     // first failing piece among this lane's
     for (u32 j = (u32)lane; j < npieces && bad == ~0u; j += WAVE) if (pres[first + j].status != R_OK) bad = j;
     #pragma unroll
     for (int k = 32; k >= 1; k >>= 1) { const u32 o = (u32)__shfl_xor((int)bad, k, 64); bad = o < bad ? o : bad; }
     bad = uni(bad);
     const u64 blocks = uni64(offsets[first + npieces] - offsets[first]);
-    zpk_encode_result r; r.status = R_OK; r.detail = 0; r.comp_size = 0; r.hash = 0;
-    if (bad != ~0u) { const zpk_encode_result f = pres[first + bad]; r.status = f.status; r.detail = f.detail; }
-    else if (hl + blocks + tl > B->dst_capacity) r.status = B->method == ZPK_METHOD_NONE ? R_BUFFER_TOO_SMALL : R_COMPRESS_FAILED;
-    else {
+    const zpk_encode_result r = enc_verdict(bad != ~0u ? pres + first + bad : nullptr, blocks, hl, tl, B->dst_capacity, B->method, hashes[blockIdx.x]);
+    if (r.status == R_OK) {
         u8* const out = uni_ptr(dst + B->dst_offset);
-        if ((u32)lane < hl) st8(out + lane, B->hdr[lane]);
-        if ((u32)lane < tl) st8(out + hl + blocks + lane, B->trl[lane]);
-        r.comp_size = hl + blocks + tl;
-        r.hash = hashes[blockIdx.x];
+        if ((u32)lane < hl) st8(out + lane, B->env.hdr[lane]);
+        if ((u32)lane < tl) st8(out + hl + blocks + lane, B->env.trl[lane]);
     }
     lane0_guard();
     if (lane == 0) results[B->entry] = r;
@@ -1848,12 +1786,12 @@ int zpk_codec_encode_big_device(zpk_codec* c, const uint8_t* d_src, uint64_t src
     if (n > 0x7FFFFFFFull) return ZPK_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    auto is_split = [&](u64 i) { return desc[i].size >= c->enc_split_min && desc[i].size > ZPK_ENC_PIECE && desc[i].method <= ZPK_METHOD_LZ4; };
+    const u64 split_min = c->enc_split_min;
     u64 np = 0, ns = 0;
     for (u64 i = 0; i < n; i++) {
         if (desc[i].src_offset > src_size || desc[i].size > src_size - desc[i].src_offset ||
             desc[i].dst_offset > dst_size || desc[i].dst_capacity > dst_size - desc[i].dst_offset) return ZPK_E_INVALID;
-        if (is_split(i)) { np += (desc[i].size + ZPK_ENC_PIECE - 1) / ZPK_ENC_PIECE; ns++; }
+        if (enc_is_split(split_min, desc[i])) { np += enc_piece_count(split_min, desc[i]); ns++; }
     }
     if (np > 0x7FFFFFFFull) return ZPK_E_INVALID;
     // the tables, in the order they lie in the pinned block and (all but the spans) in c->d_desc: the call's descriptors — an entry
@@ -1868,27 +1806,15 @@ int zpk_codec_encode_big_device(zpk_codec* c, const uint8_t* d_src, uint64_t src
     u64 k = 0, e = 0, out_total = 0, part_blocks = 0, max_cap = 0;
     for (u64 i = 0; i < n; i++) {
         hd[i] = desc[i];
-        if (!is_split(i)) continue;
+        if (!enc_is_split(split_min, desc[i])) continue;
         hd[i].method = ZPK_METHOD_NONE; hd[i].size = 0; hd[i].dst_capacity = 0; hd[i].level = 0;
-        const u64 pieces = (desc[i].size + ZPK_ENC_PIECE - 1) / ZPK_ENC_PIECE;
         BigEncEntry& B = hb[e];
-        memset(&B, 0, sizeof(B));
         B.dst_offset = desc[i].dst_offset; B.dst_capacity = desc[i].dst_capacity;
-        B.entry = (u32)i; B.first = (u32)k; B.npieces = (u32)pieces; B.method = desc[i].method;
-        if (desc[i].method != ZPK_METHOD_NONE) { B.hl = big_frame_header(desc[i].method, desc[i].size, B.hdr); B.tl = big_frame_trailer(desc[i].method, B.trl); }
-        for (u64 j = 0; j < pieces; j++, k++) {
-            hp[k] = desc[i];
-            hp[k].src_offset = desc[i].src_offset + j * ZPK_ENC_PIECE;
-            hp[k].size = j + 1 == pieces ? desc[i].size - j * ZPK_ENC_PIECE : (u64)ZPK_ENC_PIECE;
-            hp[k].dst_capacity = zpk_codec_compress_bound(desc[i].method, hp[k].size);
-            hp[k].method |= ZPK_EF_PIECE;
-            hp[k].dst_offset = out_total; out_total += (hp[k].dst_capacity + 255) & ~255ull;
-            if (hp[k].dst_capacity > max_cap) max_cap = hp[k].dst_capacity;
-            hpe[k] = (u32)e;
-        }
-        spans[e].off = desc[i].src_offset; spans[e].len = desc[i].size; spans[e].part_base = part_blocks;
-        part_blocks += xxh3_span_blocks(desc[i].size);
-        e++;
+        B.entry = (u32)i; B.first = (u32)k; B.npieces = (u32)enc_piece_count(split_min, desc[i]); B.method = desc[i].method;
+        B.env = enc_envelope(desc[i].method, desc[i].size);
+        const EncSpan sp = enc_emit_entry(split_min, desc[i], desc[i].src_offset, hp + k, out_total, max_cap);
+        for (u32 j = 0; j < B.npieces; j++) hpe[k++] = (u32)e;
+        spans[e++] = zpk_span{ sp.off, sp.len, part_blocks }; part_blocks += xxh3_span_blocks(sp.len);
     }
     const u32 spans_per_piece = (u32)((max_cap + PK_SPAN - 1) / PK_SPAN);
     const u64 gather_waves = np * spans_per_piece;

@@ -132,7 +132,6 @@ __global__ __launch_bounds__(64) void k_xxh3s_finish(zpk_cs_state* __restrict__ 
     if (lane == 0) st->hash = h;
 }
 
-#define ZPK_CS_PIECE (512u << 10)                // a piece: what one wave compresses, a run of blocks of the entry's frame
 #define ZPK_CS_PIECES 8u                         // pieces compressed side by side in one step
 #define ZPK_CS_CARRY 64u                         // bytes kept in front of the buffered plaintext (the XXH3's last stripe may reach back)
 struct zpk_cstream {
@@ -857,7 +856,7 @@ static int cstream_append(zpk_cstream* s, const u8* bytes, u32 n)
     return 0;
 }
 
-// compress the first `npieces` pieces of the buffered plaintext (`last_len` = length of the last one; the others ZPK_CS_PIECE) into
+// compress the first `npieces` pieces of the buffered plaintext (`last_len` = length of the last one; the others ZPK_ENC_PIECE) into
 // frames appended to d_out; `hash_blocks`: whole 1 KiB blocks of those bytes to feed to the running XXH3
 static int cstream_step(zpk_cstream* s, u32 npieces, u64 last_len, u64 hash_blocks, u64 src_off = 0, bool sequence = true)
 {
@@ -865,27 +864,28 @@ static int cstream_step(zpk_cstream* s, u32 npieces, u64 last_len, u64 hash_bloc
     u8* const plain = s->d_in + ZPK_CS_CARRY + src_off;
     zpk_cs_state* const st = (zpk_cs_state*)(s->d_aux + ZPK_CS_AUX_STATE);
     if (hash_blocks) hipLaunchKernelGGL(k_xxh3s_blocks, dim3(1), dim3(64), 0, c->stream, st, (const u8*)plain, hash_blocks);
-    const u64 bytes = (u64)(npieces - 1) * ZPK_CS_PIECE + last_len;
+    const u64 bytes = (u64)(npieces - 1) * ZPK_ENC_PIECE + last_len;
     if (s->method == ZPK_METHOD_NONE) {
         if (dgrow_keep(c, &s->d_out, &s->out_cap, s->out_len + bytes + 64, s->out_len) != ZPK_OK) return 10;
         if (bytes && hipMemcpyAsync(s->d_out + s->out_len, plain, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return 24;
         s->out_len += bytes; s->total_out += bytes; s->steps++;
         return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : 24;
     }
-    const u64 bound = zpk_codec_compress_bound(s->method, ZPK_CS_PIECE), slot = (bound + 255) & ~255ull;
+    const u64 bound = zpk_codec_compress_bound(s->method, ZPK_ENC_PIECE), slot = (bound + 255) & ~255ull;
     if (dgrow_keep(c, &s->d_slots, &s->slots_cap, slot * ZPK_CS_PIECES + 64, 0) != ZPK_OK) return 10;
     if (sequence && !s->framed) {
         // an entry that goes out in pieces is ONE frame (round 5; what the reference's streaming writer keeps open across calls,
         // lib/zpack_write.c:477-574): its header now — no content size, it is not known yet —, the pieces as runs of blocks, the end of
         // the frame in zpk_cstream_finish
-        const u8 l4[7] = {0x04, 0x22, 0x4D, 0x18, 0x40, 0x40, 0xC0}, zs[6] = {0x28, 0xB5, 0x2F, 0xFD, 0x00, 0x30};
-        const int hrc = s->method == ZPK_METHOD_LZ4 ? cstream_append(s, l4, 7) : cstream_append(s, zs, 6);
+        const EncEnvelope E = enc_envelope(s->method, ZPK_ENC_SIZE_UNKNOWN);
+        const int hrc = cstream_append(s, E.hdr, E.hl);
         if (hrc) return hrc;
         s->framed = 1;
     }
+    // (not enc_emit_entry's slots: every piece of a step, a short last one too, has a full piece's bound: the array is laid out once)
     zpk_encode_desc hd[ZPK_CS_PIECES]; memset(hd, 0, sizeof(hd));
     for (u32 k = 0; k < npieces; k++) {
-        hd[k].src_offset = (u64)k * ZPK_CS_PIECE; hd[k].size = k + 1 == npieces ? last_len : (u64)ZPK_CS_PIECE;
+        hd[k].src_offset = (u64)k * ZPK_ENC_PIECE; hd[k].size = k + 1 == npieces ? last_len : (u64)ZPK_ENC_PIECE;
         hd[k].dst_offset = (u64)k * slot; hd[k].dst_capacity = bound; hd[k].method = s->method | (sequence ? ZPK_EF_PIECE : 0u); hd[k].level = s->level;   // (an entry of ONE frame is written exactly as the batch writer writes it)
     }
     zpk_encode_desc* const dd = (zpk_encode_desc*)(s->d_aux + ZPK_CS_AUX_DESC);
@@ -925,16 +925,16 @@ int zpk_cstream_update(zpk_cstream* s, const uint8_t* in, size_t in_size)
         // take what fits under the next step's threshold + 1 byte: a piece is compressed only when a byte FOLLOWS it, so that none of its
         // 1 KiB blocks is the input's last (XXH3 treats that one differently).  First step after 512 KiB (first output early), then
         // eight pieces at a time.
-        const u64 thr = !s->configured ? ~0ull >> 2 : (s->steps == 0 ? (u64)ZPK_CS_PIECE : (u64)ZPK_CS_PIECE * ZPK_CS_PIECES);
+        const u64 thr = !s->configured ? ~0ull >> 2 : (s->steps == 0 ? (u64)ZPK_ENC_PIECE : (u64)ZPK_ENC_PIECE * ZPK_CS_PIECES);
         const u64 room = thr + 1 - s->in_len;                               // (in_len <= thr here: a step leaves at most one piece behind)
         const u64 take = in_size < room ? in_size : room;
         if (dgrow_keep(c, &s->d_in, &s->in_cap, ZPK_CS_CARRY + s->in_len + take + 64, ZPK_CS_CARRY + s->in_len) != ZPK_OK) return 10;
         if (hipMemcpyAsync(s->d_in + ZPK_CS_CARRY + s->in_len, in, take, hipMemcpyHostToDevice, c->stream) != hipSuccess) return 24;
         s->in_len += take; s->total_in += take; in += take; in_size -= take;
         if (s->in_len > thr) {
-            const u32 np = (u32)((s->in_len - 1) / ZPK_CS_PIECE);                       // >= 1 whole pieces with a byte behind them
-            const u64 bytes = (u64)np * ZPK_CS_PIECE;
-            const int rc = cstream_step(s, np, ZPK_CS_PIECE, bytes >> 10);
+            const u32 np = (u32)((s->in_len - 1) / ZPK_ENC_PIECE);                       // >= 1 whole pieces with a byte behind them
+            const u64 bytes = (u64)np * ZPK_ENC_PIECE;
+            const int rc = cstream_step(s, np, ZPK_ENC_PIECE, bytes >> 10);
             if (rc) return rc;
             // what is left moves to the front, behind the 64 bytes that precede it
             const u64 rest = s->in_len - bytes;
@@ -963,19 +963,19 @@ int zpk_cstream_finish(zpk_cstream* s, uint32_t method, int32_t level, uint64_t*
     // the remaining pieces (an entry that never stepped may hold more than eight: unconfigured callers); an empty entry is one empty frame
     u64 left = s->in_len, at = 0;
     bool any = s->steps == 0;
-    const bool sequence = s->steps > 0 || left > ZPK_CS_PIECE;
+    const bool sequence = s->steps > 0 || left > ZPK_ENC_PIECE;
     while (left || any) {
         any = false;
-        u32 np = (u32)((left + ZPK_CS_PIECE - 1) / ZPK_CS_PIECE); if (np == 0) np = 1; if (np > ZPK_CS_PIECES) np = ZPK_CS_PIECES;
-        const u64 bytes = (u64)np * ZPK_CS_PIECE < left ? (u64)np * ZPK_CS_PIECE : left;
-        const u64 last_len = bytes - (u64)(np - 1) * ZPK_CS_PIECE;
+        u32 np = (u32)((left + ZPK_ENC_PIECE - 1) / ZPK_ENC_PIECE); if (np == 0) np = 1; if (np > ZPK_CS_PIECES) np = ZPK_CS_PIECES;
+        const u64 bytes = (u64)np * ZPK_ENC_PIECE < left ? (u64)np * ZPK_ENC_PIECE : left;
+        const u64 last_len = bytes - (u64)(np - 1) * ZPK_ENC_PIECE;
         const int rc = cstream_step(s, np, last_len, 0, at, sequence);
         if (rc) return rc;
         left -= bytes; at += bytes;
     }
     if (s->framed) {                                                         // the end of the frame: LZ4 EndMark / an empty last Zstandard block
-        const u8 l4[4] = {0, 0, 0, 0}, zs[3] = {0x01, 0x00, 0x00};
-        const int trc = s->method == ZPK_METHOD_LZ4 ? cstream_append(s, l4, 4) : cstream_append(s, zs, 3);
+        const EncEnvelope E = enc_envelope(s->method, ZPK_ENC_SIZE_UNKNOWN);
+        const int trc = cstream_append(s, E.trl, E.tl);
         if (trc) return trc;
     }
     zpk_cs_state hs;
