@@ -10,6 +10,8 @@
  *   lib/zpack_read.c:350-468   switch(comp_method){memcpy |            zpk_codec_decode_batch_device
  *        ZSTD_decompressDCtx :380 | LZ4F_decompress loop :414-439}      zpk_codec_decode_batch_host
  *        + XXH3_64bits verify :466-468, guards :328-332                 (one descriptor per entry)
+ *                                                                       zpk_codec_decode_big_device / _big_batch_device
+ *                                                                       (large entries in device memory, block-parallel)
  *   lib/zpack_write.c:161-224  zpack_compress_file {memcpy |            zpk_codec_encode_batch_device
  *        ZSTD_compressCCtx :179 | LZ4F_compressBegin/Update/End         zpk_codec_encode_batch_host
  *        :204-210} + XXH3_64bits :256
@@ -41,7 +43,9 @@ extern "C" {
 #define ZPK_CODEC_ABI_VERSION 3      /* 3: the two-stage LZ4 path of version 2 is gone (options 2..5 are ZPK_E_INVALID again, decode_stats2 out[2] = out[4] = 0,
                                         out[3] = LZ4 entries that are mostly runs, decoded by k_lz4_left); 2: set_option has options again.
                                         (Additive since 3, no renumbering: decode_stats2 out[8], out[9], which read 0: LZ4 entries the lean kernel handed to the general decoder / not plain frames.
-                                        zpk_codec_encode_big_device, zpk_codec_encode_stats: large entries in device memory written in pieces.) */
+                                        zpk_codec_encode_big_device, zpk_codec_encode_stats: large entries in device memory written in pieces.
+                                        zpk_codec_decode_big_batch_device: a device-resident batch with large entries, their block headers walked on the device;
+                                        decode_stats2 out[10], out[11], which read 0: entries walked there / those the walk accepted.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -152,6 +156,23 @@ int zpk_codec_decode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
  * kernels of zpk_codec_decode_batch_device.  Same verdicts either way (what zpack_read_file would return, lib/zpack_read.c:326-471). */
 int  zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc,
                                  uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* result);
+
+/* A BATCH in device memory that holds large entries (the batch form of zpk_codec_decode_big_device): d_archive and d_dst are DEVICE
+ * pointers, desc and results HOST memory; synchronous — returns when every entry is decoded and verified and results[0, n) are filled.
+ * The compressed bytes never leave the device: one kernel (k_big_walk) walks the block headers of every candidate side by side — an LZ4 or
+ * Zstandard entry of ZPK_OPT_DEC_SPLIT_MIN .. 4 GiB that passes the guards of lib/zpack_read.c:328-348 and whose slot lies inside dst_size —
+ * and only its records and block tables (24 / 72 bytes per block, at most 2 * blocks-of-full-size + 8 blocks per entry: a frame with more
+ * is declined) come to the host.  Of the frames the walk accepts, those worth a turn of the whole chip — by the estimate
+ * zpk_codec_decode_batch_host uses — are decoded block-parallel, one after the other; every other entry, and every entry the block-parallel
+ * path does not finish, goes through ONE launch of the kernels of zpk_codec_decode_batch_device.  Same verdicts as that call, entry by
+ * entry; nothing outside [dst_offset, dst_offset + dst_capacity) of an entry is written.  n == 0: ZPK_OK; a NULL pointer with n > 0:
+ * ZPK_E_INVALID.  zpk_codec_decode_stats2: out[5] / out[6] block-parallel entries / their blocks, out[10] entries walked on the device,
+ * out[11] those the walk accepted.
+ * Not in this call: large STORED entries and entries that are sequences of frames (round 4 archives) stay one wave per entry; the
+ * block-parallel entries are not overlapped with one another or with the one-wave launch; zpk_codec_decode_big_device still walks on the
+ * host; libzpack_amd.so and zpk-batch do not use it. */
+int  zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                       uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results);
 
 /* Host form: host pointers, synchronous.  Stages [min src_offset, max src_offset+comp_size) of
  * `archive` to the device, decodes, and copies each slot back to dst_ptrs[i] (desc[i].dst_offset is

@@ -135,6 +135,19 @@ class Codec:
                   "zpk_codec_decode_big_device")
         return res[0]
 
+    def decode_big_batch_device(self, src, desc, dst):
+        """A batch that holds large entries: src / dst are uint8 CUDA tensors, desc an np array of DECODE_DESC (host) -> np array of
+        DECODE_RESULT (host, after every entry is decoded and verified).  The block headers of the large LZ4 / Zstandard entries are walked
+        on the device, so their compressed bytes stay there; the ones worth it are decoded block-parallel, the rest one wave each."""
+        self._settle(None)
+        desc = np.ascontiguousarray(desc, dtype=DECODE_DESC)
+        res = np.zeros(len(desc), dtype=DECODE_RESULT)
+        self.L.zpk_codec_decode_big_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        self._chk(self.L.zpk_codec_decode_big_batch_device(self.h, src.data_ptr(), src.numel(), desc.ctypes.data, len(desc),
+                                                           dst.data_ptr(), dst.numel(), res.ctypes.data),
+                  "zpk_codec_decode_big_batch_device")
+        return res
+
     def encode_batch_device(self, src, desc_dev, n, dst, results_dev, stream=None):
         self._settle(stream)
         st = C.c_void_p(stream) if stream else None
@@ -198,7 +211,8 @@ class Codec:
         return dict(stored=a[0], zstd=a[1], lz4=a[2], zstd_two_stage=a[3], zstd_fused=a[4], fse_watchdog=a[5], fse_budget=a[6],
                     zstd_arena_refused=bool(a[7] >> 31), retried_lz4=b[0], retried_zstd=b[1],
                     lz4_long_runs=b[3], lz4_handed_over=b[8], lz4_general=b[9],
-                    frame_parallel_entries=b[5], frame_parallel_frames=b[6], zstd_blocks_flags=b[7])
+                    frame_parallel_entries=b[5], frame_parallel_frames=b[6], zstd_blocks_flags=b[7],
+                    device_walked=b[10], device_walk_accepted=b[11])
 
     def debug_fetch(self, what, offset, count, dtype):
         a = np.zeros(count, dtype=dtype)

@@ -1,11 +1,20 @@
 // host_walk.h — the host code that parses UNTRUSTED archive bytes for the frame-parallel and block-parallel readers (zpk_codec.hip) and
 // for the bounded stream steps (zpk_stream.inc): frame headers, block headers, block tables.
 // Plain C++17, standard headers only: tools/hostfuzz builds this file with g++ under ASan + UBSan (g++ knows no HIP), which keeps it so.
+// The walk over ONE large frame is also device code (k_big_walk, big_walk.h): ZPK_HD is empty on a CPU build, so the rules exist once.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 #include <vector>
 #include "pj_types.h"
+
+#ifndef ZPK_HD
+#ifdef __HIPCC__
+#define ZPK_HD __host__ __device__
+#else
+#define ZPK_HD
+#endif
+#endif
 
 namespace zpk {
 
@@ -19,8 +28,8 @@ namespace zpk {
 // frame, a frame without content size, skippable frames, trailing bytes, a guard of lib/zpack_read.c:328-348 that would fire — stays
 // with the one-wave decoders, and so does every entry one of whose frames fails here: verdicts come from one place only.
 struct BigSub { u64 src_off, comp, out_off, size; };                  // a frame: byte ranges relative to its entry
-static inline u32 hrd32(const u8* p) { u32 v; memcpy(&v, p, 4); return v; }
-static inline u64 hrd64(const u8* p) { u64 v; memcpy(&v, p, 8); return v; }
+ZPK_HD static inline u32 hrd32(const u8* p) { u32 v; memcpy(&v, p, 4); return v; }
+ZPK_HD static inline u64 hrd64(const u8* p) { u64 v; memcpy(&v, p, 8); return v; }
 
 static bool walk_lz4_frames(const u8* p, u64 comp, u64 uncomp, std::vector<BigSub>& subs)
 {
@@ -95,7 +104,7 @@ other:
 
 // ---- ONE LARGE LZ4 FRAME (what the reference writer produces for any large entry: lib/zpack_write.c:204-210), block-parallel: lz4_pj.h ----
 // XXH32 of a frame descriptor (2 .. 14 bytes; xxHash specification, inputs shorter than 16 bytes): the header checksum byte is (h >> 8) & 0xFF
-static u32 host_xxh32_small(const u8* p, u32 len)
+ZPK_HD static u32 host_xxh32_small(const u8* p, u32 len)
 {
     const u32 P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
     (void)P1; (void)P2;
@@ -113,7 +122,7 @@ static u32 host_xxh32_small(const u8* p, u32 len)
 // The header of ONE LZ4 frame as the block-parallel readers take it: version 01; no reserved bit, block / content checksum or dictionary;
 // 64 KiB blocks; a header checksum byte that is right.  -> its size, 7 or 15 (0: the bytes end inside it, -1: not this path's);
 // *independent = the blocks do not reach into each other, *has_content_size / *content_size = what the frame says about its output.
-static int lz4_single_header(const u8* p, u64 avail, int* independent, int* has_content_size, u64* content_size)
+ZPK_HD static int lz4_single_header(const u8* p, u64 avail, int* independent, int* has_content_size, u64* content_size)
 {
     if (avail < 7) return 0;
     if (hrd32(p) != 0x184D2204u) return -1;
@@ -149,11 +158,29 @@ static int lz4_stream_blocks(const u8* p, u64 avail, PjBlock* tab, u32 max_block
     return (int)nb;
 }
 
+// ---- where a walk over ONE frame puts its block table ------------------------------------------------------------------------------------
+// The host readers grow a std::vector; the walk on the device (k_big_walk) and its CPU harness fill a table of FIXED capacity that the
+// caller sized from descriptor fields alone.  A frame with more blocks than the table holds is declined, like any other irregular frame:
+// push() refuses the block behind the last slot and nothing is written there, so a walk makes at most capacity + 1 turns of its loop
+// (every turn takes at least 3 bytes of the entry).
+template <class T> struct WalkVec {                                   // host only
+    std::vector<T>& v;
+    bool push(const T& b) { v.push_back(b); return true; }
+    u64 size() const { return v.size(); }
+};
+template <class T> struct WalkTab {
+    T* tab; u32 cap, n;
+    ZPK_HD bool push(const T& b) { if (n >= cap) return false; tab[n++] = b; return true; }
+    ZPK_HD u64 size() const { return n; }
+};
+// Table capacities of the fixed form: twice the blocks a frame of full blocks has, + 8 (a writer may close blocks early)
+ZPK_HD static inline u64 walk_lz4_capacity(u64 uncomp) { return 2 * ((uncomp + PJ_BLOCK - 1) / PJ_BLOCK) + 8; }
+ZPK_HD static inline u64 walk_zstd_capacity(u64 uncomp) { return 2 * ((uncomp + ZPJ_BLOCK - 1) / ZPJ_BLOCK) + 8; }
+
 // The entry is ONE frame of 64 KiB blocks, nothing optional but a content size that agrees with the entry, nothing behind its EndMark:
 // its block table (offsets relative to the entry).  Anything else: false (the one-wave decoder's).
-static bool walk_lz4_single(const u8* p, u64 comp, u64 uncomp, std::vector<PjBlock>& blocks, int& independent)
+template <class Sink> ZPK_HD static bool walk_lz4_single_to(const u8* p, u64 comp, u64 uncomp, Sink& blocks, int& independent)
 {
-    blocks.clear();
     if (comp >= 0x7FFF0000ull || uncomp >= 0x7FFF0000ull) return false;
     int has_cs = 0; u64 content = 0;
     const int hdr = lz4_single_header(p, comp, &independent, &has_cs, &content);
@@ -168,14 +195,29 @@ static bool walk_lz4_single(const u8* p, u64 comp, u64 uncomp, std::vector<PjBlo
         PjBlock B; B.comp_off = (u32)q; B.comp_size = w; B.rec_base = (u32)recs; B.out_size = 0; B.out_off = 0; B.nrec = 0;
         if (!(w >> 31)) recs += n / 3 + 2;
         if (recs > 0xFFFFFF00ull) return false;
-        blocks.push_back(B);
+        if (!blocks.push(B)) return false;
         q += n;
     }
     return q == comp && blocks.size() >= ZPK_PJ_MIN_BLOCKS;
 }
+static bool walk_lz4_single(const u8* p, u64 comp, u64 uncomp, std::vector<PjBlock>& blocks, int& independent)
+{
+    blocks.clear();
+    WalkVec<PjBlock> sink{ blocks };
+    return walk_lz4_single_to(p, comp, uncomp, sink, independent);
+}
+// ... into tab[0, capacity): *nblocks = the blocks it holds (0 when the frame is declined; slots behind *nblocks may have been written)
+ZPK_HD static bool walk_lz4_single_into(const u8* p, u64 comp, u64 uncomp, PjBlock* tab, u32 capacity, u32* nblocks, int* independent)
+{
+    WalkTab<PjBlock> sink{ tab, capacity, 0 };
+    int indep = 0;
+    const bool ok = walk_lz4_single_to(p, comp, uncomp, sink, indep);
+    *nblocks = ok ? sink.n : 0; *independent = indep;
+    return ok;
+}
 
 // Bytes an FSE table description (RFC 8878 4.1.1) takes, or -1 (malformed / beyond `avail` / more symbols or accuracy than its kind allows)
-static int zpj_ncount_len(const u8* p, u64 avail, int max_sym, int max_al)
+ZPK_HD static int zpj_ncount_len(const u8* p, u64 avail, int max_sym, int max_al)
 {
     u64 bit = 0;
     auto rd = [&](u32 n) -> i64 {                                   // n <= 16 bits from the LSB-first stream; -1 beyond the bytes
@@ -223,7 +265,7 @@ struct ZpjTabs { u32 mode[3], off[3]; };
 // about trees or slots), 0 = the bytes end inside it, -1 = not a block this path takes (reserved type, Repeat_Mode table, sizes that
 // disagree).  *last = its Last_Block bit, *total = 3 + the bytes of its body.
 // tabs != nullptr: Repeat_Mode tables are taken — resolved against *tabs, which is updated with what this block defines.
-static int zpj_parse_block(const u8* p, u64 avail, u64 at, ZpjBlock& B, u32* last, u64* total, ZpjTabs* tabs = nullptr)
+ZPK_HD static int zpj_parse_block(const u8* p, u64 avail, u64 at, ZpjBlock& B, u32* last, u64* total, ZpjTabs* tabs = nullptr)
 {
     if (avail < 3) return 0;
     const u32 bh = (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16);
@@ -292,7 +334,7 @@ static int zpj_parse_block(const u8* p, u64 avail, u64 at, ZpjBlock& B, u32* las
 
 // The header of a Zstandard frame as ZSTD_compressCCtx writes it (lib/zpack_write.c:179): no dictionary, no checksum, a window of at
 // most 2^max_wlog bytes.  -> its size (0: the bytes end inside it, -1: not this path's); *window = Window_Size, *fcs = content size or ~0.
-static int zpj_parse_frame_header(const u8* p, u64 avail, u32 max_wlog, u64* window, u64* fcs)
+ZPK_HD static int zpj_parse_frame_header(const u8* p, u64 avail, u32 max_wlog, u64* window, u64* fcs)
 {
     if (avail < 6) return 0;
     if (hrd32(p) != 0xFD2FB528u) return -1;
@@ -317,7 +359,7 @@ static int zpj_parse_frame_header(const u8* p, u64 avail, u32 max_wlog, u64* win
 // The place of a parsed block in its block table, where it becomes entry `index`: a compressed block gets its sequence slots (nseq + 1
 // from `slots` on), its room in the literal arena (`lit_total`) and, Treeless, the block whose tree it uses.  tree = the last table entry
 // whose literals carry a Huffman tree so far (ZPJ_NONE: none), kept up to date here.  false: a Treeless block with no tree in front of it.
-static inline bool zpj_place_block(ZpjBlock& B, u32 index, u32& tree, u64& slots, u64& lit_total)
+ZPK_HD static inline bool zpj_place_block(ZpjBlock& B, u32 index, u32& tree, u64& slots, u64& lit_total)
 {
     if (B.type != 2) return true;
     if (B.lit_type == 2) tree = index;
@@ -332,9 +374,9 @@ static inline bool zpj_place_block(ZpjBlock& B, u32 index, u32& tree, u64& slots
 // entry's, a window of at most 128 MiB, no Repeat_Mode table, every Treeless block behind a block with a tree, >= ZPK_PJ_MIN_BLOCKS
 // blocks, nothing behind the last block -> the block table of zstd_pj.h.  slots = sequence slots (a block owns nseq + 1), lit_total =
 // bytes of the literal arena.
-static bool walk_zstd_single(const u8* p, u64 comp, u64 uncomp, std::vector<ZpjBlock>& blocks, u64& slots, u64& lit_total)
+template <class Sink> ZPK_HD static bool walk_zstd_single_to(const u8* p, u64 comp, u64 uncomp, Sink& blocks, u64& slots, u64& lit_total)
 {
-    blocks.clear(); slots = 0; lit_total = 0;
+    slots = 0; lit_total = 0;
     u64 window = 0, fcs = ~0ull;
     const int hdr = zpj_parse_frame_header(p, comp, 27, &window, &fcs);
     if (hdr <= 0 || (fcs != ~0ull && fcs != uncomp)) return false;
@@ -345,13 +387,28 @@ static bool walk_zstd_single(const u8* p, u64 comp, u64 uncomp, std::vector<ZpjB
         ZpjBlock B; u32 last = 0; u64 total = 0;
         if (zpj_parse_block(p + q, comp - q, q, B, &last, &total, &tabs) != 1) return false;
         if (!zpj_place_block(B, (u32)blocks.size(), tree, slots, lit_total)) return false;
-        blocks.push_back(B);
+        if (!blocks.push(B)) return false;
         q += total;
         if (last) break;
         if (slots > 0x7FFFFF00ull || lit_total > 0x70000000ull) return false;
     }
     if (q != comp || blocks.size() < ZPK_ZPJ_MIN_BLOCKS) return false;
     return comp + lit_total + 1024 < 0x7FFFFF00ull;
+}
+static bool walk_zstd_single(const u8* p, u64 comp, u64 uncomp, std::vector<ZpjBlock>& blocks, u64& slots, u64& lit_total)
+{
+    blocks.clear();
+    WalkVec<ZpjBlock> sink{ blocks };
+    return walk_zstd_single_to(p, comp, uncomp, sink, slots, lit_total);
+}
+// ... into tab[0, capacity), like walk_lz4_single_into
+ZPK_HD static bool walk_zstd_single_into(const u8* p, u64 comp, u64 uncomp, ZpjBlock* tab, u32 capacity, u32* nblocks, u64* slots, u64* lit_total)
+{
+    WalkTab<ZpjBlock> sink{ tab, capacity, 0 };
+    u64 sl = 0, lt = 0;
+    const bool ok = walk_zstd_single_to(p, comp, uncomp, sink, sl, lt);
+    *nblocks = ok ? sink.n : 0; *slots = sl; *lit_total = lt;
+    return ok;
 }
 
 }  // namespace zpk

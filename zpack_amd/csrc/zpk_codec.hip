@@ -37,6 +37,7 @@
 #include "lz4_pj.h"
 #include "zstd_pj.h"
 #include "host_walk.h"                           // the host parsers of untrusted frame / block headers (plain C++, built under sanitizers by tools/hostfuzz)
+#include "big_walk.h"                            // k_big_walk: that walk over one large frame, on the device, for every large entry of a device-resident batch
 #include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
 
 using namespace zpk;
@@ -619,6 +620,9 @@ struct zpk_codec {
     DevBuf<u32>  d_pj_flags;                     // ... and flags (256 bytes)
     u8*   h_bigsrc = nullptr; u64 h_bigsrc_cap = 0;  // pinned: the compressed bytes of one large device-resident entry, for the host's block walk (zpk_codec_decode_big_device)
     DevBuf<u8> d_big1;                               // device: one descriptor + one result (the same call's one-wave fallback)
+    DevBuf<u8> d_bigwalk;                            // zpk_codec_decode_big_batch_device: candidates | records | block tables (k_big_walk)
+    u8*   h_bigwalk = nullptr; u64 h_bigwalk_cap = 0;    // ... pinned: the candidates going up, the records and tables coming home
+    u32   walk_last[2] = {0, 0};                     // ... most recent call: entries walked on the device, those the walk accepted
     u32   zpj_last_err = 0;                          // developer: the flag word of the most recent large Zstandard frame (why it went to the one-wave decoder)
     DevBuf<void> d_zpj_blocks, d_zpj_aux, d_zpj_pos; // large single Zstandard frames (zstd_pj.h): block table; work items, states, final histories; sequence positions
     SideStream left;                             // decode batches: k_lz4_left (the LZ4 entries that are mostly runs) beside k_lz4_wave
@@ -658,7 +662,7 @@ struct zpk_codec {
     u32 host_totals[N_COUNTERS] = {};
     int totals_valid = 0;
     char err[256] = {0};
-    DevBufBase* const bufs[24] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_big1,
+    DevBufBase* const bufs[25] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_big1, &d_bigwalk,
                                    &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
                                    &d_xpart, &d_zarena, &d_zstate };
 };
@@ -745,6 +749,7 @@ void zpk_codec_destroy(zpk_codec* c)
     if (c->h_pj) (void)hipHostFree(c->h_pj);
     if (c->h_seen) (void)hipHostFree((void*)c->h_seen);
     if (c->h_bigsrc) (void)hipHostFree(c->h_bigsrc);
+    if (c->h_bigwalk) (void)hipHostFree(c->h_bigwalk);
     for (int k = 0; k < 2; k++) { if (c->h_bigenc[k]) (void)hipHostFree(c->h_bigenc[k]); if (c->bigenc_ev[k]) (void)hipEventDestroy(c->bigenc_ev[k]); }
     for (SideStream* x : { &c->side, &c->left }) {
         if (x->s) (void)hipStreamDestroy(x->s);
@@ -1652,6 +1657,43 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     return ZPK_OK;
 }
 
+// a large single frame that the walk (host_walk.h, on the host or by k_big_walk) accepted: entry idx of its batch and its block table
+struct PjEntry { u64 idx; std::vector<PjBlock> blocks; int independent; std::vector<ZpjBlock> zblocks; u64 slots, lit_total; };
+
+// Which single frames go block-parallel.  One at a time, each fills the chip: a fixed cost + its bytes at ~12 GiB/s — while the
+// entries of the usual batch all run side by side, one wave each: a batch of a hundred 3 MiB entries is done in the time of ONE
+// of them there.  The batch's time is (the block-parallel entries, one after the
+// other) + (the longest one-wave entry left): the largest entries go block-parallel as long as that sum shrinks.
+// (zpk_codec_decode_batch_host and zpk_codec_decode_big_batch_device: `pj` = the accepted frames of the batch desc[0, n); those that stay, in
+// the order they are to run, are the block-parallel ones)
+static void pj_choose(const zpk_decode_desc* desc, u64 n, std::vector<PjEntry>& pj)
+{
+    if (pj.empty()) return;
+    // (measured, tools/mid_entry_rate.py + big_frame_rate.py: one wave 0.15 GiB/s LZ4 — ~1 GiB/s when the entry did not compress —,
+    // 0.031 GiB/s Zstandard; block-parallel 0.6 ms + 12 GiB/s LZ4, 4.2 ms + 12 GiB/s Zstandard)
+    auto wave_ms = [&](u64 i) {
+        const double mib = (double)desc[i].uncomp_size / (1 << 20);
+        const bool stored_like = desc[i].comp_size >= desc[i].uncomp_size - desc[i].uncomp_size / 16;
+        return mib / 1.024 / (desc[i].method == ZPK_METHOD_LZ4 ? (stored_like ? 1.0 : 0.15) : (stored_like ? 0.9 : 0.031));
+    };
+    auto pj_ms = [&](u64 i) { return (desc[i].method == ZPK_METHOD_LZ4 ? 0.6 : 4.2) + (double)desc[i].uncomp_size / (1 << 20) / 12.0 / 1.024; };
+    std::sort(pj.begin(), pj.end(), [&](const PjEntry& a, const PjEntry& b) { return wave_ms(a.idx) > wave_ms(b.idx); });
+    double other = 0;                                                         // the longest entry that is not a candidate at all
+    { std::vector<u8> cand(n, 0); for (auto& P : pj) cand[P.idx] = 1;
+      for (u64 i = 0; i < n; i++) if (!cand[i] && desc[i].method != ZPK_METHOD_NONE && desc[i].uncomp_size >= (64u << 10)) { const double t = wave_ms(i); if (t > other) other = t; } }
+    std::vector<double> tk(pj.size() + 1);
+    double best = 1e300, acc = 0;
+    for (size_t k = 0; k <= pj.size(); k++) {                                 // the first k block-parallel
+        const double rest_ms = k < pj.size() ? wave_ms(pj[k].idx) : 0.0;
+        tk[k] = acc + (rest_ms > other ? rest_ms : other);
+        if (tk[k] < best) best = tk[k];
+        if (k < pj.size()) acc += pj_ms(pj[k].idx);
+    }
+    size_t keep = pj.size();                                                  // (the estimates are rough: as many as come within 10 % of the best)
+    while (keep > 0 && tk[keep] > 1.1 * best) keep--;
+    pj.resize(keep);
+}
+
 static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                    uint8_t* const* dst_ptrs, zpk_decode_result* results)
 {
@@ -1722,11 +1764,10 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0;
+    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0;
     // ---- which entries are sequences of frames worth decoding frame-parallel ----
     std::vector<BigEntry> be;
     std::vector<BigSub> subs;
-    struct PjEntry { u64 idx; std::vector<PjBlock> blocks; int independent; std::vector<ZpjBlock> zblocks; u64 slots, lit_total; };
     std::vector<PjEntry> pj;                                                          // large single frames (lz4_pj.h, zstd_pj.h)
     if (archive && c->dec_split_min != ~0ull) {
         try {
@@ -1779,35 +1820,7 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
         }
         // ---- everything else, and the entries a frame of which did not decode, through the usual path ----
         for (u64 k = 0; k < be.size(); k++) if (!redo[k]) is_big[be[k].idx] = 1;
-        // Which single frames go block-parallel.  One at a time, each fills the chip: a fixed cost + its bytes at ~12 GiB/s — while the
-        // entries of the usual batch all run side by side, one wave each: a batch of a hundred 3 MiB entries is done in the time of ONE
-        // of them there.  The batch's time is (the block-parallel entries, one after the
-        // other) + (the longest one-wave entry left): the largest entries go block-parallel as long as that sum shrinks.
-        if (!pj.empty()) {
-            // (measured, tools/mid_entry_rate.py + big_frame_rate.py: one wave 0.15 GiB/s LZ4 — ~1 GiB/s when the entry did not compress —,
-            // 0.031 GiB/s Zstandard; block-parallel 0.6 ms + 12 GiB/s LZ4, 4.2 ms + 12 GiB/s Zstandard)
-            auto wave_ms = [&](u64 i) {
-                const double mib = (double)desc[i].uncomp_size / (1 << 20);
-                const bool stored_like = desc[i].comp_size >= desc[i].uncomp_size - desc[i].uncomp_size / 16;
-                return mib / 1.024 / (desc[i].method == ZPK_METHOD_LZ4 ? (stored_like ? 1.0 : 0.15) : (stored_like ? 0.9 : 0.031));
-            };
-            auto pj_ms = [&](u64 i) { return (desc[i].method == ZPK_METHOD_LZ4 ? 0.6 : 4.2) + (double)desc[i].uncomp_size / (1 << 20) / 12.0 / 1.024; };
-            std::sort(pj.begin(), pj.end(), [&](const PjEntry& a, const PjEntry& b) { return wave_ms(a.idx) > wave_ms(b.idx); });
-            double other = 0;                                                         // the longest entry that is not a candidate at all
-            { std::vector<u8> cand(n, 0); for (auto& P : pj) cand[P.idx] = 1;
-              for (u64 i = 0; i < n; i++) if (!cand[i] && desc[i].method != ZPK_METHOD_NONE && desc[i].uncomp_size >= (64u << 10)) { const double t = wave_ms(i); if (t > other) other = t; } }
-            std::vector<double> tk(pj.size() + 1);
-            double best = 1e300, acc = 0;
-            for (size_t k = 0; k <= pj.size(); k++) {                                 // the first k block-parallel
-                const double rest_ms = k < pj.size() ? wave_ms(pj[k].idx) : 0.0;
-                tk[k] = acc + (rest_ms > other ? rest_ms : other);
-                if (tk[k] < best) best = tk[k];
-                if (k < pj.size()) acc += pj_ms(pj[k].idx);
-            }
-            size_t keep = pj.size();                                                  // (the estimates are rough: as many as come within 10 % of the best)
-            while (keep > 0 && tk[keep] > 1.1 * best) keep--;
-            pj.resize(keep);
-        }
+        pj_choose(desc, n, pj);
         for (u64 k = 0; k < pj.size() && rc == ZPK_OK; k++) {                         // one large frame at a time: each fills the chip
             u8 again = 1;
             if (desc[pj[k].idx].method == ZPK_METHOD_LZ4)
@@ -1836,8 +1849,9 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
 // ONE entry whose compressed bytes are ON THE DEVICE, decoded into device memory (round 5; the device-pointer form of what
 // zpk_codec_decode_batch_host does for a large single frame).  desc and result are HOST memory; the call returns when the entry is
 // decoded and verified.  A large entry that is one frame of the reference writer is decoded block-parallel (lz4_pj.h / zstd_pj.h): its
-// compressed bytes come to the host once, into a pinned buffer, for the walk over the block headers (2.6 ms for 130 MiB; a walk on
-// the device is a chain of dependent loads of about the same length), everything else stays on the device.  Any other entry — and any
+// compressed bytes come to the host once, into a pinned buffer, for the walk over the block headers (2.6 ms for 130 MiB; the walk on
+// the device, k_big_walk, measured 1.77 ms for such an LZ4 entry but 77.6 ms for a Zstandard one: profiles/r15), everything else stays
+// on the device.  Any other entry — and any
 // entry the block-parallel path does not finish — is decoded by the one-wave kernels, exactly as zpk_codec_decode_batch_device would.
 int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc,
                                 uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* result)
@@ -1845,7 +1859,7 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
     if (!c || !desc || !result || !d_archive) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0;
+    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0;
     const zpk_decode_desc d = *desc;
     u8 redo = 1;
     int rc = ZPK_OK;
@@ -1892,6 +1906,119 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
     HIPCHK(c, hipMemcpyAsync(result, dr, sizeof(*result), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ZPK_OK;
+}
+
+// A BATCH whose compressed bytes are ON THE DEVICE and whose output stays there, with large entries in it (the batch form of
+// zpk_codec_decode_big_device, the read-side mirror of zpk_codec_encode_big_device).  desc and results are HOST memory; the call returns
+// when every entry is decoded and verified.  The compressed bytes never leave the device: k_big_walk (big_walk.h) walks the block headers
+// of every candidate — an LZ4 / Zstandard entry of at least ZPK_OPT_DEC_SPLIT_MIN bytes that passes the guards of lib/zpack_read.c:328-348,
+// the conditions zpk_codec_decode_big_device tests — side by side where they lie, and the records and block tables come home in one copy.
+// Of the frames the walk accepted, pj_choose picks those worth a turn of the whole chip (lz4_pj.h / zstd_pj.h, one after the other);
+// every other entry — and every entry the block-parallel path does not finish — is decoded by the one-wave kernels in ONE launch over
+// their descriptors, exactly as zpk_codec_decode_batch_device would: every verdict other than OK / hash mismatch is theirs.
+int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                      uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results)
+{
+    if (!c || (n && (!desc || !results || !d_archive || !d_dst))) return ZPK_E_INVALID;
+    if (n == 0) return ZPK_OK;
+    if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0;
+    int rc = ZPK_OK;
+    try {
+        // ---- the candidates and where their tables go: [ items | records | tables ], the same layout on the device and in pinned host memory ----
+        std::vector<u64> cand;
+        if (c->dec_split_min != ~0ull)
+            for (u64 i = 0; i < n; i++) {
+                const zpk_decode_desc& d = desc[i];
+                const bool guards = d.comp_size && d.src_offset <= archive_size && d.comp_size < archive_size - d.src_offset && d.dst_capacity >= d.uncomp_size &&
+                                    d.dst_offset <= dst_size && d.uncomp_size <= dst_size - d.dst_offset;
+                if (guards && d.uncomp_size >= c->dec_split_min && d.uncomp_size <= ZPK_HOST_CHUNK_BYTES &&
+                    (d.method == ZPK_METHOD_LZ4 || d.method == ZPK_METHOD_ZSTD)) cand.push_back(i);
+            }
+        const u64 nc = cand.size();
+        const u64 rec_off = (nc * sizeof(BigWalkItem) + 255) & ~255ull, tab0 = rec_off + ((nc * sizeof(BigWalkRec) + 255) & ~255ull);
+        u64 total = tab0;
+        std::vector<u64> tab_off(nc);
+        for (u64 k = 0; k < nc; k++) {
+            const zpk_decode_desc& d = desc[cand[k]];
+            const u64 cap = d.method == ZPK_METHOD_LZ4 ? walk_lz4_capacity(d.uncomp_size) : walk_zstd_capacity(d.uncomp_size);
+            tab_off[k] = total;
+            total += (cap * (d.method == ZPK_METHOD_LZ4 ? sizeof(PjBlock) : sizeof(ZpjBlock)) + 15) & ~15ull;
+        }
+        bool walk = nc > 0;
+        if (walk && c->h_bigwalk_cap < total) {
+            if (c->h_bigwalk) { (void)hipHostFree(c->h_bigwalk); c->h_bigwalk = nullptr; c->h_bigwalk_cap = 0; }
+            const u64 want = total + total / 4 + 4096;
+            if (hipHostMalloc((void**)&c->h_bigwalk, want, hipHostMallocDefault) == hipSuccess) c->h_bigwalk_cap = want;
+            else { (void)hipGetLastError(); c->h_bigwalk = nullptr; walk = false; }       // no memory for the tables: one wave per entry
+        }
+        if (walk && grow(c, c->d_bigwalk, total)) { c->err[0] = 0; walk = false; }
+        std::vector<PjEntry> pj;
+        if (walk) {
+            BigWalkItem* const items = (BigWalkItem*)c->h_bigwalk;
+            for (u64 k = 0; k < nc; k++) {
+                const zpk_decode_desc& d = desc[cand[k]];
+                BigWalkItem& it = items[k];
+                it.src_off = d.src_offset; it.comp = d.comp_size; it.uncomp = d.uncomp_size; it.tab_off = tab_off[k]; it.method = d.method;
+                it.cap = (u32)(d.method == ZPK_METHOD_LZ4 ? walk_lz4_capacity(d.uncomp_size) : walk_zstd_capacity(d.uncomp_size));
+            }
+            // ---- one launch over all candidates, one copy home (records + tables), one synchronisation ----
+            HIPCHK(c, hipMemcpyAsync(c->d_bigwalk, items, nc * sizeof(BigWalkItem), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_big_walk, dim3((u32)nc), dim3(64), 0, c->stream, d_archive, (const BigWalkItem*)(u8*)c->d_bigwalk, (u32)nc,
+                               (u8*)c->d_bigwalk, (BigWalkRec*)(c->d_bigwalk + rec_off));
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(c->h_bigwalk + rec_off, c->d_bigwalk + rec_off, total - rec_off, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            const BigWalkRec* const recs = (const BigWalkRec*)(c->h_bigwalk + rec_off);
+            c->walk_last[0] = (u32)nc;
+            for (u64 k = 0; k < nc; k++) {
+                const BigWalkRec& r = recs[k];
+                const zpk_decode_desc& d = desc[cand[k]];
+                const u64 cap = d.method == ZPK_METHOD_LZ4 ? walk_lz4_capacity(d.uncomp_size) : walk_zstd_capacity(d.uncomp_size);
+                if (r.accepted != 1 || r.nblocks == 0 || r.nblocks > cap) continue;
+                c->walk_last[1]++;
+                PjEntry P; P.idx = cand[k]; P.independent = (int)(r.independent & 1); P.slots = r.slots; P.lit_total = r.lit_total;
+                if (d.method == ZPK_METHOD_LZ4) { const PjBlock* t = (const PjBlock*)(c->h_bigwalk + tab_off[k]); P.blocks.assign(t, t + r.nblocks); }
+                else { const ZpjBlock* t = (const ZpjBlock*)(c->h_bigwalk + tab_off[k]); P.zblocks.assign(t, t + r.nblocks); }
+                pj.push_back(std::move(P));
+            }
+        }
+        pj_choose(desc, n, pj);
+        std::vector<u8> is_big(n, 0);
+        for (u64 k = 0; k < pj.size(); k++) {                                         // one large frame at a time: each fills the chip
+            const zpk_decode_desc& d = desc[pj[k].idx];
+            zpk_decode_result r; memset(&r, 0, sizeof(r));
+            u8 again = 1;
+            if (d.method == ZPK_METHOD_LZ4)
+                rc = decode_big_lz4_single(c, nullptr, d, pj[k].blocks, pj[k].independent, nullptr, r, again, d_archive, d_dst + d.dst_offset);
+            else
+                rc = decode_big_zstd_single(c, nullptr, d, pj[k].zblocks, pj[k].slots, pj[k].lit_total, nullptr, r, again, d_archive, d_dst + d.dst_offset);
+            if (rc != ZPK_OK) return rc;
+            if (!again) { results[pj[k].idx] = r; is_big[pj[k].idx] = 1; }
+        }
+        // ---- everything else through the one-wave kernels, one launch (every verdict is theirs) ----
+        std::vector<u64> rest;
+        for (u64 i = 0; i < n; i++) if (!is_big[i]) rest.push_back(i);
+        if (!rest.empty()) {
+            const u64 nr = rest.size();
+            std::vector<zpk_decode_desc> rd(nr);
+            std::vector<zpk_decode_result> rr(nr);
+            for (u64 k = 0; k < nr; k++) rd[k] = desc[rest[k]];
+            if ((rc = grow(c, c->d_desc, nr * sizeof(zpk_decode_desc))) || (rc = grow(c, c->d_res, nr * sizeof(zpk_decode_result)))) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->d_desc, rd.data(), nr * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream));
+            c->zstd_hint = -1; c->lz4_hint = -1;
+            const u32 keep0 = c->big_last[0], keep1 = c->big_last[1];
+            if ((rc = decode_launch(c, d_archive, archive_size, d_archive, d_archive + archive_size, (const zpk_decode_desc*)c->d_desc, nr,
+                                    d_dst, dst_size, (zpk_decode_result*)c->d_res, c->stream))) return rc;
+            c->big_last[0] = keep0; c->big_last[1] = keep1;
+            HIPCHK(c, hipMemcpyAsync(rr.data(), c->d_res, nr * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (u64 k = 0; k < nr; k++) results[rest[k]] = rr[k];
+        }
+    } catch (...) { rc = ZPK_E_NOMEM; }
+    return rc;
 }
 
 int zpk_codec_hash_batch_device(zpk_codec* c, const uint8_t* src, const uint64_t* offsets, const uint64_t* sizes, uint64_t n,
@@ -1968,6 +2095,7 @@ int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16])
     out[7] = c->zpj_last_err;                              // why the most recent large Zstandard frame was NOT finished block-parallel (0: it was, or none came)
     out[8] = h[C_LZ4_HANDED];                              // LZ4 entries k_lz4_wave handed to the general decoder without judging them
     out[9] = h[C_LZ4_GEN];                                 // LZ4 entries whose header is not that of a plain frame: k_lz4_general's
+    out[10] = c->walk_last[0]; out[11] = c->walk_last[1];  // zpk_codec_decode_big_batch_device: entries walked on the device (k_big_walk), those the walk accepted
     return ZPK_OK;
 }
 
