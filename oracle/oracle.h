@@ -91,6 +91,13 @@ typedef struct orc_zstd_stats_s {
     uint32_t repcode_uses;
     uint64_t window_size;
     uint32_t single_segment, has_fcs, has_checksum;
+    uint32_t huf_max_bits;          /* of the last Huffman description read */
+    uint32_t lit_small_fmt[4];      /* Raw / RLE literals sections per Size_Format: [0] 5 bits, [1] 12 bits, [3] 20 bits */
+    uint32_t lit_huf_fmt[4];        /* Compressed / Treeless literals sections per Size_Format */
+    uint32_t nseq_form[4];          /* Number_of_Sequences: the one-byte 0, then the 1-, 2- and 3-byte forms */
+    uint32_t fcs_bytes, dict_id_bytes;
+    uint32_t block_max_regen;       /* the most one compressed block regenerated */
+    uint32_t ncount_on_byte;        /* FSE table descriptions whose last bit is the last bit of a byte */
 } orc_zstd_stats;
 const orc_zstd_stats* orc_zstd_last_stats(void);
 /* trace of the sequences orc_zstd_decode executes, packed offset | match length << 29 | literal length << 47 (the

@@ -116,6 +116,7 @@ static int fse_read_ncount(const uint8_t* src, size_t size, int max_sym, int max
     if (remaining != 0) return -1;
     size_t used = (b.bit + 7) >> 3;
     if (used > size) return -1;
+    if ((b.bit & 7) == 0) g_stats.ncount_on_byte++;
     *nsym = s;
     *al_out = al;
     return (int)used;
@@ -179,6 +180,7 @@ static int huf_build(huf_table* h, const uint8_t* weights, int n)     /* n inclu
     /* libzstd HUF_readStats: "by construction: at least 2 elts of rank 1, must be even" */
     if (rank_count[1] < 2 || (rank_count[1] & 1)) return -1;
     h->max_bits = max_bits;
+    g_stats.huf_max_bits = (uint32_t)max_bits;
     /* weight w => code length max_bits+1-w, 2^(w-1) table slots; lowest weights first, natural order inside a weight */
     uint32_t start[14];
     uint32_t pos = 0;
@@ -326,6 +328,7 @@ static int decode_literals(frame_ctx* c, const uint8_t* src, size_t size, size_t
         else if (fmt == 1)  { hl = 2; if (size < 2) return -1; n = (src[0] >> 4) | ((size_t)src[1] << 4); }
         else                { hl = 3; if (size < 3) return -1; n = (src[0] >> 4) | ((size_t)src[1] << 4) | ((size_t)src[2] << 12); }
         if (n > BLOCK_MAX) return -1;
+        g_stats.lit_small_fmt[(fmt & 1) ? fmt : 0]++;     /* 00 and 10 are one format: a single flag bit, the size in 5 bits */
         if (type == 0) {
             if (hl + n > size) return -1;
             memcpy(c->lit, src + hl, n);
@@ -351,6 +354,7 @@ static int decode_literals(frame_ctx* c, const uint8_t* src, size_t size, size_t
     default: hl = 5; streams = 4; regen = (v >> 4) & 0x3FFFF; csize = (v >> 22) | ((size_t)src[4] << 10); break;
     }
     if (regen > BLOCK_MAX || hl + csize > size) return -1;
+    g_stats.lit_huf_fmt[fmt]++;
     const uint8_t* p = src + hl;
     size_t left = csize;
     if (type == 2) {
@@ -403,23 +407,32 @@ static int decode_block(frame_ctx* c, const uint8_t* src, size_t size, uint8_t* 
 
     if (left < 1) return E_CORRUPT;
     size_t nseq = p[0];
+    int one_byte_zero = 0;
     if (nseq == 0) {
         if (left != 1) return E_CORRUPT;          /* libzstd ZSTD_decodeSeqHeaders: srcSize_wrong */
         p += 1; left -= 1;
+        one_byte_zero = 1;
+        g_stats.nseq_form[0]++;
     } else if (nseq < 128) {
         p += 1; left -= 1;
+        g_stats.nseq_form[1]++;
     } else if (nseq < 255) {
         if (left < 2) return E_CORRUPT;
         nseq = ((nseq - 128) << 8) + p[1];
         p += 2; left -= 2;
+        g_stats.nseq_form[2]++;
     } else {
         if (left < 3) return E_CORRUPT;
         nseq = (size_t)p[1] + ((size_t)p[2] << 8) + 0x7F00;
         p += 3; left -= 3;
+        g_stats.nseq_form[3]++;
     }
 
     size_t op = 0, lit_pos = 0;
-    if (nseq > 0) {
+    /* libzstd ZSTD_decodeSeqHeaders returns early only for the ONE-byte zero: a count of 0 in the two-byte form (0x80 0x00) is
+     * followed by the modes byte and the table descriptions like any other, the tables replace the ones a later Repeat_Mode block
+     * repeats (but do not by themselves make Repeat_Mode legal, see below), and the bytes behind them are never looked at (ZSTD_decompressSequences does nothing for nbSeq == 0) */
+    if (!one_byte_zero) {
         if (left < 1) return E_CORRUPT;
         unsigned modes = p[0];
         p += 1; left -= 1;
@@ -433,8 +446,9 @@ static int decode_block(frame_ctx* c, const uint8_t* src, size_t size, uint8_t* 
         r = read_seq_table(&c->ml, (modes >> 2) & 3, 2, p, left, 52, 9, ML_DEFAULT, 53, 6, c->seq_tables_valid);
         if (r < 0) return E_CORRUPT;
         p += r; left -= (size_t)r;
-        c->seq_tables_valid = 1;
-
+    }
+    if (nseq > 0) {
+        c->seq_tables_valid = 1;                  /* libzstd sets dctx->fseEntropy only where it decodes sequences */
         bwd_bits b;
         if (bwd_init(&b, p, left) < 0) return E_CORRUPT;
         uint32_t sll = (uint32_t)bwd_read(&b, c->ll.al);
@@ -490,7 +504,9 @@ static int decode_block(frame_ctx* c, const uint8_t* src, size_t size, uint8_t* 
     if (rest > dst_cap - op) return E_DST_FULL;
     memcpy(dst + op, c->lit + lit_pos, rest);
     op += rest;
-    if (op > BLOCK_MAX) return E_CORRUPT;
+    /* no check of op against Block_Maximum_Size: libzstd 1.4.9 has none in ZSTD_decompressFrame (a block whose lengths add up to
+     * more than 128 KiB is bounded by the destination alone) */
+    if (op > g_stats.block_max_regen) g_stats.block_max_regen = (uint32_t)op;
     *produced = op;
     return E_OK;
 }
@@ -530,6 +546,7 @@ static int decode_frame(frame_ctx* c, const uint8_t* src, size_t size, size_t* i
     if (single) window = fcs;
     g_stats.frames++; g_stats.window_size = window; g_stats.single_segment = single;
     g_stats.has_fcs = fn != 0; g_stats.has_checksum = cksum;
+    g_stats.fcs_bytes = fn; g_stats.dict_id_bytes = dn;
 
     c->huf.valid = 0;
     c->seq_tables_valid = 0;

@@ -140,7 +140,9 @@ class ZstdStats(C.Structure):
                                           "lit_huf_4stream", "huf_fse_weights", "huf_direct_weights")] + \
                [("seq_mode", (C.c_uint32 * 4) * 3), ("sequences", C.c_uint64), ("repcode_uses", C.c_uint32),
                 ("window_size", C.c_uint64), ("single_segment", C.c_uint32), ("has_fcs", C.c_uint32),
-                ("has_checksum", C.c_uint32)]
+                ("has_checksum", C.c_uint32), ("huf_max_bits", C.c_uint32), ("lit_small_fmt", C.c_uint32 * 4),
+                ("lit_huf_fmt", C.c_uint32 * 4), ("nseq_form", C.c_uint32 * 4), ("fcs_bytes", C.c_uint32),
+                ("dict_id_bytes", C.c_uint32), ("block_max_regen", C.c_uint32), ("ncount_on_byte", C.c_uint32)]
 
 
 # ----------------------------------------------------------------------------- zpack.h ABI view

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer aid: a larger round of tests/test_gpu_codec.py::test_corrupted_frames_* — thousands of damaged frames per
 method / level in one device batch (XXH3 verify off), verdict + bytes against the oracle.  usage: fuzz_gpu.py [per_base] [seed] [lz4|all] [level]
-(third argument "lz4": only the LZ4 configurations)"""
+(third argument "lz4": only the LZ4 configurations)
+Frames built by hand at the edges of the format and of the kernels' own limits are tests/zstd_asm.py + tests/test_gpu_zstd_asm.py."""
 import os
 import sys
 import time

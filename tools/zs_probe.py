@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer probe: one small Zstandard batch through the two-stage decode, with the counters printed.
-   zs_probe.py N SIZE LEVEL [MIX]      (run with ZPK_TRACE=1 to see which kernel a hang is in)"""
+   zs_probe.py N SIZE LEVEL [MIX]      (run with ZPK_TRACE=1 to see which kernel a hang is in)
+   The arena-against-oracle check below is a test now: tests/test_gpu_zstd_asm.py::test_the_sequence_arena_equals_the_oracles_trace."""
 import os
 import sys
 import time

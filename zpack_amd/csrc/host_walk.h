@@ -303,7 +303,7 @@ ZPK_HD static int zpj_parse_block(const u8* p, u64 avail, u64 at, ZpjBlock& B, u
     if (nseq == 0) { if (bs - o != 1) return -1; }
     else {
         if (nseq < 128) o += 1;
-        else if (nseq < 255) { if (bs - o < 2) return -1; nseq = ((nseq - 128) << 8) + b[o + 1]; o += 2; }
+        else if (nseq < 255) { if (bs - o < 2) return -1; nseq = ((nseq - 128) << 8) + b[o + 1]; o += 2; if (nseq == 0) return -1; /* tables without sequences */ }
         else { if (bs - o < 3) return -1; nseq = (u64)b[o + 1] + ((u64)b[o + 2] << 8) + 0x7F00; o += 3; }
         if (bs - o < 1) return -1;
         const u32 modes = b[o];

@@ -400,7 +400,7 @@ __device__ __forceinline__ void zstd_fse_rows(ZfShared& sh, const u8* __restrict
                         nseq = ld8(p);
                         if (nseq == 0) { if (left != 1) ok = false; p += 1; left -= 1; }
                         else if (nseq < 128) { p += 1; left -= 1; }
-                        else if (nseq < 255) { if (left < 2) ok = false; else { nseq = ((nseq - 128) << 8) + ld8(p + 1); p += 2; left -= 2; } }
+                        else if (nseq < 255) { if (left < 2) ok = false; else { nseq = ((nseq - 128) << 8) + ld8(p + 1); p += 2; left -= 2; } if (nseq == 0) ok = false; /* tables without sequences: the fused decoder's (zstd_block) */ }
                         else { if (left < 3) ok = false; else { nseq = (u64)ld8(p + 1) + ((u64)ld8(p + 2) << 8) + 0x7F00; p += 3; left -= 3; } }
                     }
                     if (ok && nseq > 0) {

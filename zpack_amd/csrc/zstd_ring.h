@@ -102,7 +102,7 @@ __device__ inline int zr_block(ZstdRingShared& sh, ZFrameState& fs, LxOut& O, co
     u64 nseq = uld8(p);
     if (nseq == 0) { if (left != 1) return LX_E_FRAME; }
     else if (nseq < 128) { left -= 1; }
-    else if (nseq < 255) { if (left < 2) return LX_E_FRAME; nseq = ((nseq - 128) << 8) + uld8(p + 1); left -= 2; }
+    else if (nseq < 255) { if (left < 2) return LX_E_FRAME; nseq = ((nseq - 128) << 8) + uld8(p + 1); left -= 2; if (nseq == 0) return LX_E_FRAME; /* tables without sequences: zstd_block's */ }
     else { if (left < 3) return LX_E_FRAME; nseq = (u64)uld8(p + 1) + ((u64)uld8(p + 2) << 8) + 0x7F00; left -= 3; }
     const u32 block_out = O.wp;
     u64 lit_pos = 0;

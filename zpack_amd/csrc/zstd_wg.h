@@ -1083,6 +1083,10 @@ __device__ inline int zstd_block(ZstdShared& sh, ZFrameState& fs, const u8* src,
     u64 left = size - used;
     if (left < 1) return D_MALFORMED;
     u64 nseq = uld8(p);
+    // Only the ONE-byte 0 ends the section (libzstd ZSTD_decodeSeqHeaders).  A count of 0 in the two-byte form (0x80 0x00) is followed by
+    // the modes byte and the table descriptions like any other count: they are read, must be well-formed and REPLACE the tables a later
+    // Repeat_Mode block repeats; they do not make Repeat_Mode legal (that takes a block with sequences), and what follows them is ignored.
+    const bool tables_follow = nseq != 0;
     if (nseq == 0) { if (left != 1) return D_MALFORMED; p += 1; left -= 1; }
     else if (nseq < 128) { p += 1; left -= 1; }
     else if (nseq < 255) { if (left < 2) return D_MALFORMED; nseq = ((nseq - 128) << 8) + uld8(p + 1); p += 2; left -= 2; }
@@ -1090,7 +1094,7 @@ __device__ inline int zstd_block(ZstdShared& sh, ZFrameState& fs, const u8* src,
 
     u8* op = dst; u8* oend = dst + dst_cap;
     u64 lit_pos = 0;
-    if (nseq > 0) {
+    if (tables_follow) {
         if (left < 1) return D_MALFORMED;
         ZSeqArgs sa;
         sa.pre = nullptr;
@@ -1130,10 +1134,11 @@ __device__ inline int zstd_block(ZstdShared& sh, ZFrameState& fs, const u8* src,
             if (__ballot(!ok) != 0) return D_MALFORMED;
         }
         __syncthreads();
-        fs.seq_tables_valid = true;
+        if (nseq > 0) fs.seq_tables_valid = true;
         ZST({ u64 t = SEQ_T(); fs.zs->t_tab += t - zt0; zt0 = t; fs.zs->nseq += nseq; });
         }
 
+        if (nseq > 0) {
         sa.p = p; sa.left = left; sa.nseq = nseq;
         sa.al_ll = fs.al_ll; sa.al_of = fs.al_of; sa.al_ml = fs.al_ml;
         sa.rep0 = (u32)fs.rep0; sa.rep1 = (u32)fs.rep1; sa.rep2 = (u32)fs.rep2;
@@ -1148,6 +1153,7 @@ __device__ inline int zstd_block(ZstdShared& sh, ZFrameState& fs, const u8* src,
         if (src_rc != D_OK) { produced = (u64)(op - dst); return src_rc; }
         if (!sa.pre) { fs.rep0 = sa.rep0; fs.rep1 = sa.rep1; fs.rep2 = sa.rep2; }
         lit_pos = sa.lit_pos;
+        }
     }
     const u64 rest = lit_size - lit_pos;
     if (rest > (u64)(oend - op)) { produced = (u64)(op - dst); return D_DST_FULL; }
@@ -1157,7 +1163,7 @@ __device__ inline int zstd_block(ZstdShared& sh, ZFrameState& fs, const u8* src,
     } else for (u64 i = (u64)lane * 16; i < rest; i += WAVE * 16) gcopy_upto16(op + i, lit + lit_pos + i, (u32)(rest - i < 16 ? rest - i : 16));
     op += rest;
     wave_mem_fence();
-    if ((u64)(op - dst) > ZSTD_BLOCK_MAX) return D_MALFORMED;
+    // (no check against Block_Maximum_Size: libzstd has none — lengths that add up to more than 128 KiB are bounded by the destination)
     produced = (u64)(op - dst);
     return D_OK;
 }
