@@ -45,7 +45,8 @@ extern "C" {
                                         (Additive since 3, no renumbering: decode_stats2 out[8], out[9], which read 0: LZ4 entries the lean kernel handed to the general decoder / not plain frames.
                                         zpk_codec_encode_big_device, zpk_codec_encode_stats: large entries in device memory written in pieces.
                                         zpk_codec_decode_big_batch_device: a device-resident batch with large entries, their block headers walked on the device;
-                                        decode_stats2 out[10], out[11], which read 0: entries walked there / those the walk accepted.) */
+                                        decode_stats2 out[10], out[11], which read 0: entries walked there / those the walk accepted.
+                                        ZPK_OPT_STORED_SPAN_MIN, decode_stats2 out[12], out[13], which read 0: large stored entries in device memory copied chip-wide / their groups.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -136,9 +137,15 @@ int         zpk_codec_device(const zpk_codec* c);
  *   ZPK_OPT_ORDER_MIN               decode batches of at least `value` entries run their Zstandard and LZ4 work lists LARGEST ENTRIES
  *                                   FIRST (size classes by powers of two; a device counting sort behind the classification): one
  *                                   wave works on one entry, so a large entry that starts last runs on alone; encode batches order
- *                                   their ticket queue the same way.  Default 8192 (decode), 4608 (encode); 0 = never. */
+ *                                   their ticket queue the same way.  Default 8192 (decode), 4608 (encode); 0 = never.
+ *   ZPK_OPT_STORED_SPAN_MIN         zpk_codec_decode_big_batch_device, zpk_codec_decode_big_device: a STORED entry (method none) of at least
+ *                                   `value` bytes that passes the guards of lib/zpack_read.c:328-354 is copied to its slot and hashed by the
+ *                                   whole chip — one wave per 64 KiB, then one short chain per entry — instead of by one wave; anything
+ *                                   else, and any entry that fails a guard, goes through the one-wave kernels (verdicts other than OK /
+ *                                   hash mismatch come from there only).  Default 256 KiB; the least size taken is 1025; 0 = never. */
 /* (2..5 were the opt-in two-stage LZ4 path of round 4 and its measurement aids: measured slower than the one-kernel decoder, removed in round 5) */
 enum { ZPK_OPT_ENC_SPLIT_MIN = 6, ZPK_OPT_DEC_SPLIT_MIN = 7, ZPK_OPT_ORDER_MIN = 8, ZPK_OPT_ORDER_FAST_LAST = 9 /* a batch of ONE size class runs the entries that did not compress (a copy to decode) last: 1 (default) / 0 */ };
+#define ZPK_OPT_STORED_SPAN_MIN 10
 int         zpk_codec_set_option(zpk_codec* c, int option, int value);
 
 /* ---- batch decode + verify ----------------------------------------------------------------
@@ -153,7 +160,9 @@ int zpk_codec_decode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
 /* ONE entry whose compressed bytes are in DEVICE memory, decoded into device memory (d_dst + desc->dst_offset); desc and result are host
  * memory; returns when the entry is decoded and verified.  A large entry that is one frame of the reference writer
  * (lib/zpack_write.c:179, :204-210) is decoded block-parallel — 13-17 GiB/s instead of one wave's 0.03-0.14; anything else runs through the
- * kernels of zpk_codec_decode_batch_device.  Same verdicts either way (what zpack_read_file would return, lib/zpack_read.c:326-471). */
+ * kernels of zpk_codec_decode_batch_device.  A large STORED entry (ZPK_OPT_STORED_SPAN_MIN) is copied and hashed by the whole chip
+ * (k_stored_span + the XXH3 chain); decode_stats2 out[12] / out[13] count it and its groups of 64 KiB.  Same verdicts either way (what
+ * zpack_read_file would return, lib/zpack_read.c:326-471). */
 int  zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc,
                                  uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* result);
 
@@ -168,7 +177,13 @@ int  zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_
  * entry; nothing outside [dst_offset, dst_offset + dst_capacity) of an entry is written.  n == 0: ZPK_OK; a NULL pointer with n > 0:
  * ZPK_E_INVALID.  zpk_codec_decode_stats2: out[5] / out[6] block-parallel entries / their blocks, out[10] entries walked on the device,
  * out[11] those the walk accepted.
- * Not in this call: large STORED entries and entries that are sequences of frames (round 4 archives) stay one wave per entry; the
+ * Large STORED entries (round 17): an entry with method none of at least ZPK_OPT_STORED_SPAN_MIN bytes that passes the same guards is
+ * copied to its slot and hashed by the whole chip on a second stream of the codec, beside everything else of the call — ONE launch of
+ * k_stored_span for all of them (one wave per 64 KiB: each 1 KiB block is loaded once, stored and folded into its XXH3 partial sum), one
+ * XXH3 chain wave per entry, the hashes come home in one copy; the call waits for that stream on every way out.  Status 0 or FILE_HASH_MISMATCH (ZPK_DF_SKIP_HASH honoured), detail 0, produced = uncomp_size: what the one-wave
+ * kernel writes; nothing outside [dst_offset, dst_offset + uncomp_size) is written.  out[12] / out[13]: such entries / their groups of
+ * 64 KiB; they are not part of out[0] of zpk_codec_decode_stats (no work list held them) nor of out[5] / out[6].
+ * Not in this call: entries that are sequences of frames (round 4 archives) stay one wave per entry; the
  * block-parallel entries are not overlapped with one another or with the one-wave launch; zpk_codec_decode_big_device still walks on the
  * host; libzpack_amd.so and zpk-batch do not use it. */
 int  zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
@@ -246,7 +261,10 @@ int zpk_codec_set_profiling(zpk_codec* c, int enabled);
  * zpk_codec_decode_batch_host call that were decoded frame-parallel (ZPK_OPT_DEC_SPLIT_MIN) and the frames they had;
  * out[8] = LZ4 entries with the header of a plain frame (one frame, no checksums, no dictionary id) that k_lz4_wave, the kernel for such
  * frames, did not finish cleanly and handed unjudged to the general decoder behind it (damaged, truncated, trailing bytes ...; not part
- * of out[0]); out[9] = LZ4 entries whose header is not that of a plain frame: the classification sends them to k_lz4_general */
+ * of out[0]); out[9] = LZ4 entries whose header is not that of a plain frame: the classification sends them to k_lz4_general;
+ * out[10], out[11] = entries of the most recent zpk_codec_decode_big_batch_device call walked on the device / those the walk accepted;
+ * out[12], out[13] = stored entries the most recent zpk_codec_decode_big_batch_device / zpk_codec_decode_big_device call copied chip-wide
+ * (ZPK_OPT_STORED_SPAN_MIN) / their groups of 64 KiB */
 int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16]);
 /* counters of the most recent decode batch (synchronises): out[0..2] = entries on the stored / zstd / lz4 work
  * lists, out[3] = Zstandard entries finished on pre-decoded sequences (two-stage path), out[4] = by the fused decoder,

@@ -19,6 +19,7 @@ DF_SKIP_HASH = 1
 DF_GENERAL = 2
 K_CLASSIFY, K_STORED, K_LZ4, K_ZSTD, K_ZSTD_FSE, K_PACK, K_ENCODE = 0, 1, 2, 3, 4, 5, 7
 OPT_ENC_SPLIT_MIN, OPT_DEC_SPLIT_MIN, OPT_ORDER_MIN, OPT_ORDER_FAST_LAST = 6, 7, 8, 9      # zpk_codec_set_option (include/zpack_codec.h)
+OPT_STORED_SPAN_MIN = 10
 
 # zpk_decode_desc / zpk_decode_result / zpk_encode_desc / zpk_encode_result (include/zpack_codec.h)
 DECODE_DESC = np.dtype([("src_offset", "<u8"), ("comp_size", "<u8"), ("uncomp_size", "<u8"), ("expect_hash", "<u8"),
@@ -138,7 +139,8 @@ class Codec:
     def decode_big_batch_device(self, src, desc, dst):
         """A batch that holds large entries: src / dst are uint8 CUDA tensors, desc an np array of DECODE_DESC (host) -> np array of
         DECODE_RESULT (host, after every entry is decoded and verified).  The block headers of the large LZ4 / Zstandard entries are walked
-        on the device, so their compressed bytes stay there; the ones worth it are decoded block-parallel, the rest one wave each."""
+        on the device, so their compressed bytes stay there; the ones worth it are decoded block-parallel, large stored entries
+        (OPT_STORED_SPAN_MIN) are copied and hashed chip-wide, the rest one wave each."""
         self._settle(None)
         desc = np.ascontiguousarray(desc, dtype=DECODE_DESC)
         res = np.zeros(len(desc), dtype=DECODE_RESULT)
@@ -212,7 +214,7 @@ class Codec:
                     zstd_arena_refused=bool(a[7] >> 31), retried_lz4=b[0], retried_zstd=b[1],
                     lz4_long_runs=b[3], lz4_handed_over=b[8], lz4_general=b[9],
                     frame_parallel_entries=b[5], frame_parallel_frames=b[6], zstd_blocks_flags=b[7],
-                    device_walked=b[10], device_walk_accepted=b[11])
+                    device_walked=b[10], device_walk_accepted=b[11], stored_span_entries=b[12], stored_span_groups=b[13])
 
     def debug_fetch(self, what, offset, count, dtype):
         a = np.zeros(count, dtype=dtype)

@@ -39,6 +39,8 @@
 #include "host_walk.h"                           // the host parsers of untrusted frame / block headers (plain C++, built under sanitizers by tools/hostfuzz)
 #include "big_walk.h"                            // k_big_walk: that walk over one large frame, on the device, for every large entry of a device-resident batch
 #include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
+#include "stored_plan.h"                         // the large stored entries of a device-resident batch: which are taken, their span table, the verdict (plain C++, likewise)
+#include "stored_span.h"                         // k_stored_span: their copy fused with the XXH3 partial sums, across the chip
 
 using namespace zpk;
 
@@ -584,6 +586,11 @@ __global__ __launch_bounds__(256) void k_hash(const u8* __restrict__ src, const 
 
 #define ZPK_DEC_SPLIT_MIN_DEFAULT (256ull << 10)     // (round 5: a single 512 KiB LZ4 entry is 0.66 ms block-parallel against 3.3 ms by one wave, 1 MiB of Zstandard 4.3 against 31.7: tools/mid_entry_rate.py)
 #define ZPK_ENC_SPLIT_MIN_DEFAULT (2ull << 20)
+#define ZPK_STORED_SPAN_MIN_DEFAULT (256ull << 10) // (round 17: tools/big_batch_device_rate.py --stored, profiles/r17)
+#ifndef ZPK_STORED_SPAN_FORK
+#define ZPK_STORED_SPAN_FORK 1                     // zpk_codec_decode_big_batch_device runs the stored spans on a second stream beside the rest of the call; 0: on its own stream, in front of the walk
+                                                   // (256 MiB stored + 256 MiB LZ4 text in one call: 14.9-15.2 ms forked against 23.6-23.9 ms serial, every forked run ahead: profiles/r17/r17_fork_ab.txt)
+#endif
 #ifndef ZPK_PJ_CHUNK_BLOCKS
 #define ZPK_PJ_CHUNK_BLOCKS 512u                   // lz4_pj.h: blocks per chunk = 32 MiB of output, 128 MiB of byte references (the Infinity Cache holds 256)
 #endif
@@ -623,6 +630,13 @@ struct zpk_codec {
     DevBuf<u8> d_bigwalk;                            // zpk_codec_decode_big_batch_device: candidates | records | block tables (k_big_walk)
     u8*   h_bigwalk = nullptr; u64 h_bigwalk_cap = 0;    // ... pinned: the candidates going up, the records and tables coming home
     u32   walk_last[2] = {0, 0};                     // ... most recent call: entries walked on the device, those the walk accepted
+    // large stored entries of a device-resident call (stored_plan.h / stored_span.h): span table | destination offsets | 64 bytes of XXH3
+    // partial sums per 1 KiB block | hashes — a buffer of its own, d_xpart belongs to the block-parallel readers of the same call
+    DevBuf<u8> d_sspan;
+    u8*   h_sspan = nullptr; u64 h_sspan_cap = 0;        // ... pinned: the table going up, the hashes coming home
+    SideStream span;                                     // ... the second stream of the forked form (created on first use)
+    u64   stored_span_min = ZPK_STORED_SPAN_MIN_DEFAULT; // ZPK_OPT_STORED_SPAN_MIN: stored entries of at least this many bytes go chip-wide
+    u32   span_last[2] = {0, 0};                         // ... most recent call: entries copied chip-wide, their groups
     u32   zpj_last_err = 0;                          // developer: the flag word of the most recent large Zstandard frame (why it went to the one-wave decoder)
     DevBuf<void> d_zpj_blocks, d_zpj_aux, d_zpj_pos; // large single Zstandard frames (zstd_pj.h): block table; work items, states, final histories; sequence positions
     SideStream left;                             // decode batches: k_lz4_left (the LZ4 entries that are mostly runs) beside k_lz4_wave
@@ -662,7 +676,7 @@ struct zpk_codec {
     u32 host_totals[N_COUNTERS] = {};
     int totals_valid = 0;
     char err[256] = {0};
-    DevBufBase* const bufs[25] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_big1, &d_bigwalk,
+    DevBufBase* const bufs[26] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_big1, &d_bigwalk, &d_sspan,
                                    &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
                                    &d_xpart, &d_zarena, &d_zstate };
 };
@@ -750,8 +764,9 @@ void zpk_codec_destroy(zpk_codec* c)
     if (c->h_seen) (void)hipHostFree((void*)c->h_seen);
     if (c->h_bigsrc) (void)hipHostFree(c->h_bigsrc);
     if (c->h_bigwalk) (void)hipHostFree(c->h_bigwalk);
+    if (c->h_sspan) (void)hipHostFree(c->h_sspan);
     for (int k = 0; k < 2; k++) { if (c->h_bigenc[k]) (void)hipHostFree(c->h_bigenc[k]); if (c->bigenc_ev[k]) (void)hipEventDestroy(c->bigenc_ev[k]); }
-    for (SideStream* x : { &c->side, &c->left }) {
+    for (SideStream* x : { &c->side, &c->left, &c->span }) {
         if (x->s) (void)hipStreamDestroy(x->s);
         if (x->fork) (void)hipEventDestroy(x->fork);
         if (x->join) (void)hipEventDestroy(x->join);
@@ -826,7 +841,7 @@ static int xxh3_spans_launch(zpk_codec* c, const u8* base, const zpk_span* h_spa
     HIPCHK(c, hipMemcpyAsync(h_hash, d_hash, nspans * 8, hipMemcpyDeviceToHost, st));
     return ZPK_OK;
 }
-static inline u64 xxh3_span_blocks(u64 len) { return (((len - 1) >> 10) + XS_GROUP - 1) / XS_GROUP * XS_GROUP; }   // partial-sum slots of one span
+// (xxh3_span_blocks, the partial-sum slots of one span: stored_plan.h)
 
 // Fork: work enqueued on x.s from here on runs beside `from`, behind everything `from` holds now.  The stream (low_priority: at
 // the device's lowest) and the two events are created on first use; false = no second stream, the caller stays on `from`.
@@ -1764,7 +1779,7 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0;
+    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0;
     // ---- which entries are sequences of frames worth decoding frame-parallel ----
     std::vector<BigEntry> be;
     std::vector<BigSub> subs;
@@ -1846,6 +1861,67 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
     return rc;
 }
 
+// ---- large STORED entries of a device-resident call, copied and hashed by the whole chip (round 17; stored_plan.h, stored_span.h) ----
+// The entries of desc[0, n) that stored_span_takes, in one k_stored_span (the copy fused with the XXH3 partial sums, any number of spans),
+// one k_xxh3_chain with one wave per span — on the SOURCE, so it does not wait for the copy's bytes — and the copy home of the hashes,
+// all enqueued on `st`.  The table goes up from pinned memory the codec owns and the hashes land there: both calls that use this wait
+// for `st` before they return, so one block suffices.  run.idx = the entries taken (none when the option is off, nothing qualifies or
+// there is no memory for the tables: those stay with the one-wave launch); their results are composed by stored_span_finish once `st`
+// has drained.
+struct StoredSpanRun { std::vector<u64> idx; const u64* h_hash = nullptr; };
+static int stored_span_enqueue(zpk_codec* c, const u8* d_archive, u64 archive_size, const zpk_decode_desc* desc, u64 n, u8* d_dst, u64 dst_size,
+                               hipStream_t st, StoredSpanRun& run)
+{
+    run.idx.clear(); run.h_hash = nullptr;
+    if (c->stored_span_min == ~0ull) return ZPK_OK;
+    u64 k = 0;
+    for (u64 i = 0; i < n; i++) k += stored_span_takes(desc[i], archive_size, dst_size, c->stored_span_min) ? 1 : 0;
+    if (k == 0) return ZPK_OK;
+    const u64 dst_at = (k * sizeof(StoredSpanRow) + 255) & ~255ull, up_bytes = dst_at + ((k * 8 + 255) & ~255ull), h_total = up_bytes + k * 8;
+    if (c->h_sspan_cap < h_total) {
+        if (c->h_sspan) { (void)hipHostFree(c->h_sspan); c->h_sspan = nullptr; c->h_sspan_cap = 0; }
+        const u64 want = h_total + h_total / 4 + 4096;
+        if (hipHostMalloc((void**)&c->h_sspan, want, hipHostMallocDefault) == hipSuccess) c->h_sspan_cap = want;
+        else { (void)hipGetLastError(); c->h_sspan = nullptr; return ZPK_OK; }
+    }
+    StoredSpanRow* const rows = (StoredSpanRow*)c->h_sspan;
+    u64* const dst_off = (u64*)(c->h_sspan + dst_at);
+    StoredPlan plan = { 0, 0, 0 };
+    run.idx.reserve(k);
+    for (u64 i = 0; i < n; i++)
+        if (stored_span_takes(desc[i], archive_size, dst_size, c->stored_span_min)) {
+            if (!stored_span_emit(desc[i], rows, dst_off, plan)) break;              // the launch is full: the rest stays one wave per entry
+            run.idx.push_back(i);
+        }
+    if (plan.nspans == 0) return ZPK_OK;
+    const u64 part_at = up_bytes, hash_at = part_at + plan.part_blocks * 64;
+    if (grow(c, c->d_sspan, hash_at + plan.nspans * 8 + 64)) { c->err[0] = 0; run.idx.clear(); return ZPK_OK; }
+    const zpk_span* const d_spans = (const zpk_span*)(u8*)c->d_sspan;
+    u64* const d_part = (u64*)(c->d_sspan + part_at);
+    u64* const d_hash = (u64*)(c->d_sspan + hash_at);
+    u64* const h_hash = (u64*)(c->h_sspan + up_bytes);
+    HIPCHK(c, hipMemcpyAsync(c->d_sspan, c->h_sspan, up_bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_stored_span, dim3((u32)((plan.groups + 3) / 4)), dim3(256), 0, st, d_archive, d_dst, d_spans,
+                       (const u64*)(c->d_sspan + dst_at), (u32)plan.nspans, plan.groups, d_part);
+    hipLaunchKernelGGL(k_xxh3_chain, dim3((u32)plan.nspans), dim3(64), 0, st, d_archive, d_spans, (const u64*)d_part, d_hash, (u64*)nullptr, (u64)0, ~(u64)0, 1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_hash, d_hash, plan.nspans * 8, hipMemcpyDeviceToHost, st));
+    run.h_hash = h_hash;
+    c->span_last[0] = (u32)plan.nspans; c->span_last[1] = (u32)(plan.groups > 0xFFFFFFFFull ? 0xFFFFFFFFull : plan.groups);
+    return ZPK_OK;
+}
+// ... and their results, once the stream of stored_span_enqueue has drained
+static void stored_span_finish(const StoredSpanRun& run, const zpk_decode_desc* desc, zpk_decode_result* results)
+{
+    for (u64 k = 0; k < run.idx.size(); k++) results[run.idx[k]] = stored_span_verdict(desc[run.idx[k]], run.h_hash[k]);
+}
+// Waits for a stream when it goes out of scope: every return path behind a fork — the error paths too — leaves nothing in flight that
+// reads the codec's pinned block or writes the caller's slots.
+struct StreamDrain {
+    hipStream_t s = nullptr;
+    ~StreamDrain() { if (s) (void)hipStreamSynchronize(s); }
+};
+
 // ONE entry whose compressed bytes are ON THE DEVICE, decoded into device memory (round 5; the device-pointer form of what
 // zpk_codec_decode_batch_host does for a large single frame).  desc and result are HOST memory; the call returns when the entry is
 // decoded and verified.  A large entry that is one frame of the reference writer is decoded block-parallel (lz4_pj.h / zstd_pj.h): its
@@ -1859,10 +1935,25 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
     if (!c || !desc || !result || !d_archive) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0;
+    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0;
     const zpk_decode_desc d = *desc;
     u8 redo = 1;
     int rc = ZPK_OK;
+    if (d_dst && stored_span_takes(d, archive_size, dst_size, c->stored_span_min)) {   // a large stored entry: copied and hashed chip-wide (serial form)
+        try {
+            StoredSpanRun run;
+            StreamDrain drain; drain.s = c->stream;
+            if ((rc = stored_span_enqueue(c, d_archive, archive_size, &d, 1, d_dst, dst_size, c->stream, run))) return rc;
+            if (!run.idx.empty()) {
+                drain.s = nullptr;
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                stored_span_finish(run, &d, result);
+                (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->totals_valid = 0;   // no work list held an entry in this call
+                return ZPK_OK;
+            }
+            drain.s = nullptr;
+        } catch (...) { c->span_last[0] = c->span_last[1] = 0; }
+    }
     const bool guards = d.comp_size && d.src_offset <= archive_size && d.comp_size < archive_size - d.src_offset && d.dst_capacity >= d.uncomp_size &&
                         d.dst_offset <= dst_size && d.uncomp_size <= dst_size - d.dst_offset;
     if (guards && c->dec_split_min != ~0ull && d.uncomp_size >= c->dec_split_min && d.uncomp_size <= ZPK_HOST_CHUNK_BYTES &&
@@ -1924,9 +2015,25 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
     if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0;
+    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0;
     int rc = ZPK_OK;
+    StoredSpanRun span;
+    StreamDrain drain;                                                                // (declared in front of the try: it waits on every way out)
     try {
+        // ---- the large stored entries: copy + XXH3 across the chip.  Serial form: on c->stream, in front of the walk.  Forked form: on a
+        // second stream beside the walk, the block-parallel entries and the one-wave launch — the slots are disjoint, and the chain is one
+        // wave per span, so the rest of the chip is free while it runs.
+        {
+            bool any = false;
+            if (c->stored_span_min != ~0ull) for (u64 i = 0; i < n && !any; i++) any = stored_span_takes(desc[i], archive_size, dst_size, c->stored_span_min);
+            if (any) {
+                hipStream_t ss = c->stream;
+                if (ZPK_STORED_SPAN_FORK && fork_stream(c->span, c->stream, false)) ss = c->span.s;
+                drain.s = ss;
+                if ((rc = stored_span_enqueue(c, d_archive, archive_size, desc, n, d_dst, dst_size, ss, span))) return rc;
+                if (span.idx.empty()) drain.s = nullptr;
+            }
+        }
         // ---- the candidates and where their tables go: [ items | records | tables ], the same layout on the device and in pinned host memory ----
         std::vector<u64> cand;
         if (c->dec_split_min != ~0ull)
@@ -1987,6 +2094,7 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
         }
         pj_choose(desc, n, pj);
         std::vector<u8> is_big(n, 0);
+        for (u64 i : span.idx) is_big[i] = 1;                                         // (composed behind the join, below)
         for (u64 k = 0; k < pj.size(); k++) {                                         // one large frame at a time: each fills the chip
             const zpk_decode_desc& d = desc[pj[k].idx];
             zpk_decode_result r; memset(&r, 0, sizeof(r));
@@ -2016,6 +2124,15 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
             HIPCHK(c, hipMemcpyAsync(rr.data(), c->d_res, nr * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             for (u64 k = 0; k < nr; k++) results[rest[k]] = rr[k];
+        } else if (!span.idx.empty()) {
+            (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->totals_valid = 0;       // no work list held an entry in this call
+        }
+        // ---- the join: the stored spans' stream has drained -> their hashes are in the pinned block ----
+        if (!span.idx.empty()) {
+            const hipStream_t ss = drain.s;
+            drain.s = nullptr;
+            HIPCHK(c, hipStreamSynchronize(ss));
+            stored_span_finish(span, desc, results);
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
     return rc;
@@ -2096,6 +2213,7 @@ int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16])
     out[8] = h[C_LZ4_HANDED];                              // LZ4 entries k_lz4_wave handed to the general decoder without judging them
     out[9] = h[C_LZ4_GEN];                                 // LZ4 entries whose header is not that of a plain frame: k_lz4_general's
     out[10] = c->walk_last[0]; out[11] = c->walk_last[1];  // zpk_codec_decode_big_batch_device: entries walked on the device (k_big_walk), those the walk accepted
+    out[12] = c->span_last[0]; out[13] = c->span_last[1];  // ... and zpk_codec_decode_big_device: stored entries copied chip-wide (k_stored_span), their groups
     return ZPK_OK;
 }
 
@@ -2121,6 +2239,7 @@ int zpk_codec_set_option(zpk_codec* c, int option, int value)
     if (option == ZPK_OPT_ORDER_MIN) { if (value < 0) return ZPK_E_INVALID; c->order_min = c->enc_order_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     if (option == ZPK_OPT_DEC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->dec_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     if (option == ZPK_OPT_ENC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->enc_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
+    if (option == ZPK_OPT_STORED_SPAN_MIN) { if (value < 0) return ZPK_E_INVALID; c->stored_span_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     return ZPK_E_INVALID;
 }
 
