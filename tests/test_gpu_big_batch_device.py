@@ -11,7 +11,7 @@ import pytest
 
 import zpack_amd
 from benchdata import datagen as dg
-from zpack_amd import METHOD_NONE, METHOD_ZSTD, METHOD_LZ4, OPT_ENC_SPLIT_MIN, OPT_DEC_SPLIT_MIN
+from zpack_amd import METHOD_NONE, METHOD_ZSTD, METHOD_LZ4, OPT_ENC_SPLIT_MIN, OPT_DEC_SPLIT_MIN, OPT_STORED_SPAN_MIN
 
 pytestmark = pytest.mark.gpu
 K = 1 << 10
@@ -297,3 +297,63 @@ def test_arguments_and_a_batch_without_candidates(codec, entries):
     assert L.zpk_codec_decode_big_batch_device(None, src.data_ptr(), src.numel(), d.ctypes.data, len(d), dst.data_ptr(), dst.numel(), res.ctypes.data) == -2
     torch.cuda.synchronize()
     assert bool((dst.cpu().numpy() == GUARD).all())
+
+
+def test_pinned_blocks_grow_and_are_reused_at_a_smaller_need():
+    """The codec's three read-side pinned blocks — the walk's tables, the stored spans' table, the bytes of one entry for the host's walk —
+    each grown, grown again and then used at a smaller need, on ONE codec with both thresholds at 64 KiB: decode_big_batch_device with 1,
+    48 and 1 entries of 96 KiB (LZ4 text, Zstandard text, stored in turn), then decode_big_device with a 96 KiB LZ4 entry, a 1 MiB one, the
+    96 KiB one again and a 96 KiB stored one.  After every call: status, produced, hash and bytes are decode_batch_device's on the same
+    descriptors, the guards stand, and the counters are the counts of the call's own descriptors."""
+    import torch
+    dev = torch.device("cuda:0")
+    n = 96 * K
+    kinds = [(METHOD_LZ4, 0), (METHOD_ZSTD, 1), (METHOD_NONE, 0)]
+
+    def item(i, size=n):
+        m, lv = kinds[i % 3]
+        plain = dg.fill(dg.TEXT, 505, i, size)
+        pay = plain if m == METHOD_NONE else np.array(np.frombuffer(dg.compress(m, lv, plain), dtype=np.uint8))
+        return (m, pay, len(pay), size, dg.xxh3(plain), size), plain
+
+    def accepted(m, pay):                                  # host_walk.h: a frame of at least 4 LZ4 blocks / 2 Zstandard blocks
+        return m != METHOD_NONE and _block_count(pay, m) >= (4 if m == METHOD_LZ4 else 2)
+
+    made = [item(i) for i in range(48)]
+    big, big_plain = item(48, 1 * M)                       # (48 % 3 == 0: LZ4)
+    c = zpack_amd.Codec(0)
+    try:
+        c.set_option(OPT_DEC_SPLIT_MIN, 64 * K)
+        c.set_option(OPT_STORED_SPAN_MIN, 64 * K)
+        for count in (1, 48, 1):
+            items, plains = [x[0] for x in made[:count]], [x[1] for x in made[:count]]
+            arc, d, total = _batch(items)
+            r1, st, out1, r0, out0 = _run_both(c, arc, d, total)
+            print(count, st)
+            _same_verdicts(r1, r0, d, out1, out0, ["%d of %d" % (i, count) for i in range(count)])
+            for i, plain in enumerate(plains):
+                o = int(d["dst_offset"][i])
+                assert int(r1["status"][i]) == 0 and int(r1["produced"][i]) == n and int(r1["hash"][i]) == items[i][4], (count, i, r1[i])
+                assert np.array_equal(out1[o:o + n], plain), (count, i)
+            assert _guards_intact(out1, d) and _guards_intact(out0, d)
+            walked = sum(1 for it in items if it[0] != METHOD_NONE)
+            assert st["device_walked"] == walked and st["device_walk_accepted"] == sum(1 for it in items if accepted(it[0], it[1])), (count, st)
+            assert st["stored_span_entries"] == count - walked, (count, st)
+        singles = [(made[0][0], made[0][1]), (big, big_plain), (made[0][0], made[0][1]), (made[2][0], made[2][1])]
+        for k, (it, plain) in enumerate(singles):
+            arc, d, total = _batch([it])
+            src = torch.from_numpy(arc).to(dev)
+            dst = torch.full((total,), GUARD, dtype=torch.uint8, device=dev)
+            r = c.decode_big_device(src, d, dst)
+            st = c.decode_stats()
+            out1 = dst.cpu().numpy()
+            print(k, st)
+            _, _, _, r0, out0 = _run_both(c, arc, d, total)
+            _same_verdicts(np.array([r], dtype=zpack_amd.DECODE_RESULT), r0, d, out1, out0, ["single %d" % k])
+            assert int(r["status"]) == 0 and int(r["produced"]) == len(plain) and int(r["hash"]) == it[4], (k, r)
+            assert np.array_equal(out1[256:256 + len(plain)], plain) and _guards_intact(out1, d) and _guards_intact(out0, d), k
+            assert (st["device_walked"], st["device_walk_accepted"]) == (0, 0), (k, st)              # this call walks on the host
+            assert st["stored_span_entries"] == (1 if it[0] == METHOD_NONE else 0), (k, st)
+            assert st["frame_parallel_entries"] == (1 if accepted(it[0], it[1]) else 0), (k, st)
+    finally:
+        c.close()

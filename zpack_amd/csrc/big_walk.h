@@ -9,21 +9,11 @@
 //   - stores: plain C++ assignments by lane 0 = vector stores, table entries first, the record last;
 //   - no LDS, no barrier, no atomics: a wave needs only its registers, so as many candidates are resident as the chip has wave slots.
 #pragma once
-#include "../../include/zpack_codec.h"
-#include "host_walk.h"
+#include "dec_plan.h"                            // (the public header, host_walk.h)
 
 namespace zpk {
 
-struct BigWalkItem {                     // host -> device, one per candidate
-    u64 src_off, comp, uncomp;           // the entry: d_archive + src_off, comp bytes (inside the archive: the caller's guards passed), its stated size
-    u64 tab_off;                         // its table in the staging buffer (byte offset, 8-aligned)
-    u32 cap, method;                     // table capacity in blocks (walk_*_capacity: a function of uncomp alone); ZPK_METHOD_LZ4 / _ZSTD
-};
-struct BigWalkRec {                      // device -> host, one per candidate
-    u32 accepted, nblocks;               // 1: the frame is the block-parallel readers' and tab[0, nblocks) is its table; 0: the one-wave decoder's
-    u32 independent, pad;                // LZ4: the blocks do not reach into each other
-    u64 slots, lit_total;                // Zstandard: sequence slots, bytes of the literal arena
-};
+// BigWalkItem (one per candidate, host -> device), BigWalkRec (device -> host) and the staging layout [ items | records | tables ]: dec_plan.h
 
 __global__ __launch_bounds__(64) void k_big_walk(const u8* __restrict__ archive, const BigWalkItem* __restrict__ items, u32 n,
                                                  u8* __restrict__ staging, BigWalkRec* __restrict__ recs)

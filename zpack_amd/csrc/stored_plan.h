@@ -1,25 +1,12 @@
 // stored_plan.h — the large STORED entries of a device-resident batch, copied and hashed by the whole chip (k_stored_span, stored_span.h),
 // decided in one place for zpk_codec_decode_big_batch_device and zpk_codec_decode_big_device: which entries are taken, the span table the
-// two kernels read, the verdict of a finished entry.
-// Plain C++17, the public header and standard headers only: tools/hostfuzz builds this file with g++ under ASan + UBSan (g++ knows no HIP),
-// which keeps it so.
+// two kernels read.  The guards and the verdict of a finished entry are dec_plan.h's, shared with the compressed entries of the same calls.
+// Plain C++17, the public header, dec_plan.h and standard headers only: tools/hostfuzz builds this file with g++ under ASan + UBSan (g++
+// knows no HIP), which keeps it so.
 #pragma once
-#include <stdint.h>
-#include "../../include/zpack_codec.h"
-
-#ifndef ZPK_HD
-#ifdef __HIPCC__
-#define ZPK_HD __host__ __device__
-#else
-#define ZPK_HD
-#endif
-#endif
+#include "dec_plan.h"                            // (the public header, the typedefs, ZPK_HD)
 
 namespace zpk {
-
-typedef uint8_t  u8;                             // (the typedefs of zpk_device.h)
-typedef uint32_t u32;
-typedef uint64_t u64;
 
 // ---- the layout of the partial sums (xxh3_span.h) -------------------------------------------------------------------------------------
 // A span of `len` bytes has (len - 1) >> 10 full 1 KiB blocks in front of the block with its last byte; a GROUP is 64 of them, one wave's
@@ -28,18 +15,16 @@ typedef uint64_t u64;
 ZPK_HD static inline u64 xxh3_span_blocks(u64 len) { return (((len - 1) >> 10) + ZPK_SPAN_GROUP - 1) / ZPK_SPAN_GROUP * ZPK_SPAN_GROUP; }   // partial-sum slots of one span
 
 // ---- which entries are taken ------------------------------------------------------------------------------------------------------------
-// The guards are those of k_classify (lib/zpack_read.c:328-354) with the answers that lead to k_stored: an entry that fails one stays with
-// the one-wave launch, whose k_classify alone says BUFFER_TOO_SMALL / FILE_OFFSET_INVALID / FILE_SIZE_INVALID, in the reference's order.
+// The guards are dec_plan.h's (lib/zpack_read.c:328-348) and :354, with the answers that lead to k_stored: an entry that fails one stays
+// with the one-wave launch, whose k_classify alone says BUFFER_TOO_SMALL / FILE_OFFSET_INVALID / FILE_SIZE_INVALID, in the reference's order.
 // A span without a full block has no group to carry its tail: 1025 bytes is the least.  threshold: zpk_codec::stored_span_min (~0: never).
 #define ZPK_STORED_SPAN_LEAST 1025ull
 ZPK_HD static inline bool stored_span_takes(const zpk_decode_desc& d, u64 archive_size, u64 dst_size, u64 threshold)
 {
     if (d.method != ZPK_METHOD_NONE) return false;
-    if (d.comp_size == 0) return false;                                              // :328 — OK, nothing produced
-    if (d.dst_capacity < d.uncomp_size) return false;                                // :329
-    if (d.src_offset > archive_size || d.comp_size >= archive_size - d.src_offset) return false;   // :331 (offset + comp_size < file_size)
+    if (!dec_guards_pass(d, archive_size)) return false;                             // :328 (OK, nothing produced), :329, :331
     if (d.uncomp_size > d.comp_size) return false;                                   // :354
-    if (d.dst_offset > dst_size || d.uncomp_size > dst_size - d.dst_offset) return false;          // the slot lies inside dst
+    if (!dec_slot_in_dst(d, dst_size)) return false;
     return d.uncomp_size >= (threshold > ZPK_STORED_SPAN_LEAST ? threshold : ZPK_STORED_SPAN_LEAST);
 }
 
@@ -63,15 +48,7 @@ static inline bool stored_span_emit(const zpk_decode_desc& d, StoredSpanRow* row
     return true;
 }
 
-// ---- the verdict ------------------------------------------------------------------------------------------------------------------------
-// Field for field what k_stored writes (lib/zpack_read.c:466-468): the hash is always produced, ZPK_DF_SKIP_HASH keeps it out of the status.
-enum : int { STORED_R_OK = 0, STORED_R_FILE_HASH_MISMATCH = 15 };
-ZPK_HD static inline zpk_decode_result stored_span_verdict(const zpk_decode_desc& d, u64 hash)
-{
-    zpk_decode_result r;
-    r.status = (!(d.flags & ZPK_DF_SKIP_HASH) && hash != d.expect_hash) ? STORED_R_FILE_HASH_MISMATCH : STORED_R_OK;
-    r.detail = 0; r.produced = d.uncomp_size; r.hash = hash;
-    return r;
-}
+// ---- the verdict: dec_hash_verdict (dec_plan.h), field for field what k_stored writes (lib/zpack_read.c:466-468) --------------------------
+ZPK_HD static inline zpk_decode_result stored_span_verdict(const zpk_decode_desc& d, u64 hash) { return dec_hash_verdict(d, hash); }
 
 }  // namespace zpk

@@ -37,6 +37,7 @@
 #include "lz4_pj.h"
 #include "zstd_pj.h"
 #include "host_walk.h"                           // the host parsers of untrusted frame / block headers (plain C++, built under sanitizers by tools/hostfuzz)
+#include "dec_plan.h"                            // a large entry's route on the read side: guards, candidates, chooser, walk layout, verdict (plain C++, likewise)
 #include "big_walk.h"                            // k_big_walk: that walk over one large frame, on the device, for every large entry of a device-resident batch
 #include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
 #include "stored_plan.h"                         // the large stored entries of a device-resident batch: which are taken, their span table, the verdict (plain C++, likewise)
@@ -584,7 +585,6 @@ __global__ __launch_bounds__(256) void k_hash(const u8* __restrict__ src, const 
 
 // ------------------------------------------------------------------------------------ host side
 
-#define ZPK_DEC_SPLIT_MIN_DEFAULT (256ull << 10)     // (round 5: a single 512 KiB LZ4 entry is 0.66 ms block-parallel against 3.3 ms by one wave, 1 MiB of Zstandard 4.3 against 31.7: tools/mid_entry_rate.py)
 #define ZPK_ENC_SPLIT_MIN_DEFAULT (2ull << 20)
 #define ZPK_STORED_SPAN_MIN_DEFAULT (256ull << 10) // (round 17: tools/big_batch_device_rate.py --stored, profiles/r17)
 #ifndef ZPK_STORED_SPAN_FORK
@@ -602,6 +602,23 @@ template <class T> struct DevBuf : DevBufBase {
     operator T*() const { return (T*)p; }
     template <class U> explicit operator U*() const { return (U*)p; }
 };
+// One block of pinned host memory the codec owns, for tables and bytes that travel in one copy; every one is listed in zpk_codec::pins,
+// which is what zpk_codec_destroy frees.  grow_pinned -> the block holds `need` bytes; false: no pinned memory (the HIP error is cleared,
+// the block is empty) — what then is the caller's policy.  A block is regrown only while nothing on a stream still reads or writes it: a
+// call that uses one drains the stream it put the copies on before it returns (h_bigsrc, h_bigwalk: hipStreamSynchronize behind the copy
+// home; h_sspan: the run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the
+// block's next turn (h_bigenc).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
+struct PinBuf { u8* p = nullptr; u64 cap = 0; };
+static bool grow_pinned(PinBuf& b, u64 need)
+{
+    if (need <= b.cap) return true;
+    if (b.p) (void)hipHostFree(b.p);
+    b.p = nullptr; b.cap = 0;
+    const u64 want = need + need / 4 + 4096;
+    if (hipHostMalloc((void**)&b.p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
+    b.cap = want;
+    return true;
+}
 // A second stream beside the batch's own (created on first use) with the event pair that forks work onto it and joins it back
 struct SideStream { hipStream_t s = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
 
@@ -625,15 +642,14 @@ struct zpk_codec {
     SideStream side;                             // decode batches: the LZ4 kernels beside the Zstandard stages (low priority)
     DevBuf<void> d_pj_blocks, d_pj_recs, d_pj_masks, d_pj_S;   // large single LZ4 frames (lz4_pj.h): block table, sequence records, start masks, byte references
     DevBuf<u32>  d_pj_flags;                     // ... and flags (256 bytes)
-    u8*   h_bigsrc = nullptr; u64 h_bigsrc_cap = 0;  // pinned: the compressed bytes of one large device-resident entry, for the host's block walk (zpk_codec_decode_big_device)
-    DevBuf<u8> d_big1;                               // device: one descriptor + one result (the same call's one-wave fallback)
+    PinBuf h_bigsrc;                                 // pinned: the compressed bytes of one large device-resident entry, for the host's block walk (zpk_codec_decode_big_device)
     DevBuf<u8> d_bigwalk;                            // zpk_codec_decode_big_batch_device: candidates | records | block tables (k_big_walk)
-    u8*   h_bigwalk = nullptr; u64 h_bigwalk_cap = 0;    // ... pinned: the candidates going up, the records and tables coming home
+    PinBuf h_bigwalk;                                // ... pinned: the candidates going up, the records and tables coming home
     u32   walk_last[2] = {0, 0};                     // ... most recent call: entries walked on the device, those the walk accepted
     // large stored entries of a device-resident call (stored_plan.h / stored_span.h): span table | destination offsets | 64 bytes of XXH3
     // partial sums per 1 KiB block | hashes — a buffer of its own, d_xpart belongs to the block-parallel readers of the same call
     DevBuf<u8> d_sspan;
-    u8*   h_sspan = nullptr; u64 h_sspan_cap = 0;        // ... pinned: the table going up, the hashes coming home
+    PinBuf h_sspan;                                      // ... pinned: the table going up, the hashes coming home
     SideStream span;                                     // ... the second stream of the forked form (created on first use)
     u64   stored_span_min = ZPK_STORED_SPAN_MIN_DEFAULT; // ZPK_OPT_STORED_SPAN_MIN: stored entries of at least this many bytes go chip-wide
     u32   span_last[2] = {0, 0};                         // ... most recent call: entries copied chip-wide, their groups
@@ -659,7 +675,7 @@ struct zpk_codec {
     u64  enc_split_min = ZPK_ENC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_ENC_SPLIT_MIN: entries of at least this many bytes are written as a sequence of frames
     // zpk_codec_encode_big_device: the tables of one call (descriptors, pieces, entry table, spans) go up from pinned memory behind
     // whatever the stream still holds; two blocks take turns, the event says that a block's upload has run
-    u8*  h_bigenc[2] = {nullptr, nullptr}; u64 h_bigenc_cap[2] = {0, 0}; hipEvent_t bigenc_ev[2] = {nullptr, nullptr}; u32 bigenc_turn = 0;
+    PinBuf h_bigenc[2]; hipEvent_t bigenc_ev[2] = {nullptr, nullptr}; u32 bigenc_turn = 0;
     u32  enc_big_last[2] = {0, 0};                     // ... most recent call: entries written in pieces, their pieces
     DevBuf<u64> d_zarena;                              // decoder: pre-decoded Zstandard sequences, laid out like dst (zstd_fse4.h)
     DevBuf<u32> d_zstate;                              // decoder: per entry, 1 = its sequences are in the arena
@@ -676,9 +692,10 @@ struct zpk_codec {
     u32 host_totals[N_COUNTERS] = {};
     int totals_valid = 0;
     char err[256] = {0};
-    DevBufBase* const bufs[26] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_big1, &d_bigwalk, &d_sspan,
+    DevBufBase* const bufs[25] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_bigwalk, &d_sspan,
                                    &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
                                    &d_xpart, &d_zarena, &d_zstate };
+    PinBuf* const pins[5] = { &h_bigsrc, &h_bigwalk, &h_sspan, &h_bigenc[0], &h_bigenc[1] };
 };
 
 struct CodecLock {
@@ -762,10 +779,8 @@ void zpk_codec_destroy(zpk_codec* c)
     if (c->piece_counters) (void)hipHostFree(c->piece_counters);
     if (c->h_pj) (void)hipHostFree(c->h_pj);
     if (c->h_seen) (void)hipHostFree((void*)c->h_seen);
-    if (c->h_bigsrc) (void)hipHostFree(c->h_bigsrc);
-    if (c->h_bigwalk) (void)hipHostFree(c->h_bigwalk);
-    if (c->h_sspan) (void)hipHostFree(c->h_sspan);
-    for (int k = 0; k < 2; k++) { if (c->h_bigenc[k]) (void)hipHostFree(c->h_bigenc[k]); if (c->bigenc_ev[k]) (void)hipEventDestroy(c->bigenc_ev[k]); }
+    for (PinBuf* b : c->pins) if (b->p) (void)hipHostFree(b->p);
+    for (int k = 0; k < 2; k++) if (c->bigenc_ev[k]) (void)hipEventDestroy(c->bigenc_ev[k]);
     for (SideStream* x : { &c->side, &c->left, &c->span }) {
         if (x->s) (void)hipStreamDestroy(x->s);
         if (x->fork) (void)hipEventDestroy(x->fork);
@@ -1367,10 +1382,6 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     return rc;
 }
 
-#ifndef ZPK_HOST_CHUNK_BYTES
-#define ZPK_HOST_CHUNK_BYTES (4ull << 30)        // output slots of one device sub-batch of the host path (an entry larger than this goes alone)
-#endif
-
 // ---- entries that are SEQUENCES OF FRAMES, decoded frame-parallel (host path): host_walk.h finds the frames (walk_lz4_frames, walk_zstd_frames) ----
 struct BigEntry { u64 idx, first_sub, nsub; };
 
@@ -1475,11 +1486,9 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
     if (e == hipSuccess) e = e2 != hipSuccess ? e2 : e3;
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large frame: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     if ((u32)c->h_pj[1] != 0) return ZPK_OK;                                                       // PJ_ERR: something was irregular after all
-    const u64 h = c->h_pj[0];
-    result.hash = h; result.produced = n; result.detail = 0;
-    const bool hash_ok = (d.flags & ZPK_DF_SKIP_HASH) || h == d.expect_hash;
-    if (!hash_ok && !accept_mismatch) return ZPK_OK;                                               // (the one-wave decoder gives this entry's verdict)
-    result.status = hash_ok ? 0 : 15;                                                              // ZPACK_ERROR_FILE_HASH_MISMATCH, lib/zpack_read.c:467
+    const zpk_decode_result v = dec_hash_verdict(d, c->h_pj[0]);
+    if (v.status != DEC_R_OK && !accept_mismatch) return ZPK_OK;                                   // (the one-wave decoder gives this entry's verdict)
+    result = v;
     c->big_last[0]++; c->big_last[1] += (u32)nb;
     redo = 0;
     return ZPK_OK;
@@ -1487,22 +1496,25 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
 
 }   // extern "C++"
 
+// The two ends of a block-parallel entry: the archive its bytes are read from (archive + src_offset) and where ITS output goes, each
+// either host or device memory.  Output on the device stays where it is written; a host destination gets it through c->d_dst.
+struct BigSrc { const u8* archive; bool on_device; };
+struct BigDst { u8* p; bool on_device; };
+
 // -> ZPK_OK with redo = 0: the entry is decoded, hashed and delivered; redo = 1: not this path's (the one-wave decoder decides)
-// (d_archive != nullptr: the entry's bytes are on the device already; d_out != nullptr: that is where the output goes, on the device)
-static int decode_big_lz4_single(zpk_codec* c, const u8* archive, const zpk_decode_desc& d, const std::vector<PjBlock>& blocks, int independent,
-                                 uint8_t* dst_ptr, zpk_decode_result& result, u8& redo, const u8* d_archive = nullptr, u8* d_out = nullptr)
+static int decode_big_lz4_single(zpk_codec* c, const BigSrc& src, const zpk_decode_desc& d, const std::vector<PjBlock>& blocks, int independent,
+                                 const BigDst& dst, zpk_decode_result& result, u8& redo)
 {
     redo = 1;
     const u64 nb = blocks.size(), n = d.uncomp_size;
     const u64 total_recs = (u64)blocks.back().rec_base + ((blocks.back().comp_size >> 31) ? 0 : (blocks.back().comp_size / 3 + 2));
     int rc;
-    if ((rc = grow(c, c->d_src, d.comp_size + ZPK_SRC_SLACK)) || (!d_out && (rc = grow(c, c->d_dst, n + 16))) ||
+    if ((rc = grow(c, c->d_src, d.comp_size + ZPK_SRC_SLACK)) || (!dst.on_device && (rc = grow(c, c->d_dst, n + 16))) ||
         (rc = grow(c, c->d_pj_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->d_pj_recs, (total_recs + 64) * 8)) ||
         (rc = grow(c, c->d_pj_masks, nb * (PJ_BLOCK / 8))) || (rc = grow(c, c->d_pj_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }     // no memory for the scratch: the one-wave decoder
     if (!c->d_pj_flags && hipMalloc(&c->d_pj_flags.p, 256) != hipSuccess) { c->d_pj_flags.p = nullptr; (void)hipGetLastError(); return ZPK_OK; }
     hipStream_t st = c->stream;
-    hipError_t e = d_archive ? hipMemcpyAsync(c->d_src, d_archive + d.src_offset, d.comp_size, hipMemcpyDeviceToDevice, st)
-                             : hipMemcpyAsync(c->d_src, archive + d.src_offset, d.comp_size, hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(c->d_src, src.archive + d.src_offset, d.comp_size, src.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_pj_blocks, blocks.data(), nb * sizeof(PjBlock), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(c->d_pj_flags, 0, 256, st);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
@@ -1522,12 +1534,12 @@ static int decode_big_lz4_single(zpk_codec* c, const u8* archive, const zpk_deco
     auto init = [&](u32 b0, u32 b1, hipStream_t s2) {
         hipLaunchKernelGGL(k_pj_init, dim3(b1 - b0), dim3(256), 0, s2, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->d_pj_recs, (const u32*)c->d_pj_masks, S, n, c->d_pj_flags, independent);
     };
-    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS, d.comp_size, init, true, d_out ? d_out : c->d_dst, dst_ptr, result, redo);
+    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS, d.comp_size, init, true, dst.on_device ? dst.p : (u8*)c->d_dst, dst.on_device ? nullptr : dst.p, result, redo);
 }
 
 // -> ZPK_OK with redo = 0: the entry is decoded, its XXH3 is the expected one, the bytes are delivered; redo = 1: not this path's
-static int decode_big_zstd_single(zpk_codec* c, const u8* archive, const zpk_decode_desc& d, std::vector<ZpjBlock>& blocks, u64 slots, u64 lit_total,
-                                  uint8_t* dst_ptr, zpk_decode_result& result, u8& redo, const u8* d_archive = nullptr, u8* d_out = nullptr)
+static int decode_big_zstd_single(zpk_codec* c, const BigSrc& src, const zpk_decode_desc& d, std::vector<ZpjBlock>& blocks, u64 slots, u64 lit_total,
+                                  const BigDst& dst, zpk_decode_result& result, u8& redo)
 {
     redo = 1;
     const u64 nb = blocks.size(), n = d.uncomp_size;
@@ -1548,7 +1560,7 @@ static int decode_big_zstd_single(zpk_codec* c, const u8* archive, const zpk_dec
     const u64 aux_desc = 0, aux_list = (nb * sizeof(zpk_decode_desc) + 255) & ~255ull, aux_state = aux_list + ((nb * 4 + 255) & ~255ull),
               aux_rep = aux_state + ((nb * 4 + 255) & ~255ull), aux_size = aux_rep + nb * 12 + 256;
     int rc;
-    if ((rc = grow(c, c->d_src, arena_off + lit_total + ZPK_SRC_SLACK)) || (!d_out && (rc = grow(c, c->d_dst, n + 16))) ||
+    if ((rc = grow(c, c->d_src, arena_off + lit_total + ZPK_SRC_SLACK)) || (!dst.on_device && (rc = grow(c, c->d_dst, n + 16))) ||
         (rc = grow(c, c->d_pj_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->d_zpj_blocks, nb * sizeof(ZpjBlock))) ||
         (rc = grow(c, c->d_zpj_aux, aux_size)) || (rc = grow(c, c->d_pj_recs, (slots + 64) * 8)) ||
         (rc = grow(c, c->d_zpj_pos, (slots + 64) * 8)) || (rc = grow(c, c->d_pj_masks, nb * (ZPJ_BLOCK / 8))) ||
@@ -1560,8 +1572,7 @@ static int decode_big_zstd_single(zpk_codec* c, const u8* archive, const zpk_dec
     hflags[ZPJ_CNT + C_ZSTD] = (u32)list.size();
     std::vector<PjBlock> hb(nb);
     memset(hb.data(), 0, nb * sizeof(PjBlock));
-    hipError_t e = d_archive ? hipMemcpyAsync(c->d_src, d_archive + d.src_offset, d.comp_size, hipMemcpyDeviceToDevice, st)
-                             : hipMemcpyAsync(c->d_src, archive + d.src_offset, d.comp_size, hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(c->d_src, src.archive + d.src_offset, d.comp_size, src.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_zpj_blocks, blocks.data(), nb * sizeof(ZpjBlock), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_pj_blocks, hb.data(), nb * sizeof(PjBlock), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(aux + aux_desc, items.data(), nb * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, st);
@@ -1595,7 +1606,7 @@ static int decode_big_zstd_single(zpk_codec* c, const u8* archive, const zpk_dec
         hipLaunchKernelGGL(k_zpj_init, dim3(b1 - b0), dim3(256), 0, s2, (const ZpjBlock*)ZB, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->d_pj_recs, (const u64*)c->d_zpj_pos,
                            (const u32*)c->d_pj_masks, S, n, c->d_pj_flags);
     };
-    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS * PJ_BLOCK / ZPJ_BLOCK, arena_off + lit_total, init, false, d_out ? d_out : c->d_dst, dst_ptr, result, redo);
+    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS * PJ_BLOCK / ZPJ_BLOCK, arena_off + lit_total, init, false, dst.on_device ? dst.p : (u8*)c->d_dst, dst.on_device ? nullptr : dst.p, result, redo);
 }
 
 // the frames of entries [g0, g1) of `be` as one device batch; redo[k] = 1: entry k takes the serial path after all
@@ -1659,9 +1670,7 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         for (u64 f = 0; f < E.nsub; f++, j++) if (hr[j].status != 0 || hr[j].produced != subs[E.first_sub + f].size) ok = false;
         redo[g0 + k] = ok ? 0 : 1;
         if (!ok) continue;
-        zpk_decode_result& r = results[E.idx];
-        r.hash = h_hash[k]; r.produced = d.uncomp_size; r.detail = 0;
-        r.status = ((d.flags & ZPK_DF_SKIP_HASH) || r.hash == d.expect_hash) ? 0 : 15;          // ZPACK_ERROR_FILE_HASH_MISMATCH, lib/zpack_read.c:467
+        results[E.idx] = dec_hash_verdict(d, h_hash[k]);
         c->big_last[0]++; c->big_last[1] += (u32)E.nsub;
     }
     std::vector<uint8_t*> optr(ng);
@@ -1674,40 +1683,35 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
 
 // a large single frame that the walk (host_walk.h, on the host or by k_big_walk) accepted: entry idx of its batch and its block table
 struct PjEntry { u64 idx; std::vector<PjBlock> blocks; int independent; std::vector<ZpjBlock> zblocks; u64 slots, lit_total; };
+// ... the walk on the host over entry d (LZ4 or Zstandard) whose bytes are at p: true = accepted, P is its PjEntry
+static bool walk_single(const u8* p, const zpk_decode_desc& d, u64 idx, PjEntry& P)
+{
+    P.idx = idx; P.independent = 0; P.slots = P.lit_total = 0;
+    return d.method == ZPK_METHOD_LZ4 ? walk_lz4_single(p, d.comp_size, d.uncomp_size, P.blocks, P.independent)
+                                      : walk_zstd_single(p, d.comp_size, d.uncomp_size, P.zblocks, P.slots, P.lit_total);
+}
 
-// Which single frames go block-parallel.  One at a time, each fills the chip: a fixed cost + its bytes at ~12 GiB/s — while the
-// entries of the usual batch all run side by side, one wave each: a batch of a hundred 3 MiB entries is done in the time of ONE
-// of them there.  The batch's time is (the block-parallel entries, one after the
-// other) + (the longest one-wave entry left): the largest entries go block-parallel as long as that sum shrinks.
-// (zpk_codec_decode_batch_host and zpk_codec_decode_big_batch_device: `pj` = the accepted frames of the batch desc[0, n); those that stay, in
-// the order they are to run, are the block-parallel ones)
+// Which single frames go block-parallel: dec_choose (dec_plan.h).  `pj` = the accepted frames of the batch desc[0, n); those that stay, in
+// the order they are to run, are the block-parallel ones (zpk_codec_decode_batch_host and zpk_codec_decode_big_batch_device)
 static void pj_choose(const zpk_decode_desc* desc, u64 n, std::vector<PjEntry>& pj)
 {
-    if (pj.empty()) return;
-    // (measured, tools/mid_entry_rate.py + big_frame_rate.py: one wave 0.15 GiB/s LZ4 — ~1 GiB/s when the entry did not compress —,
-    // 0.031 GiB/s Zstandard; block-parallel 0.6 ms + 12 GiB/s LZ4, 4.2 ms + 12 GiB/s Zstandard)
-    auto wave_ms = [&](u64 i) {
-        const double mib = (double)desc[i].uncomp_size / (1 << 20);
-        const bool stored_like = desc[i].comp_size >= desc[i].uncomp_size - desc[i].uncomp_size / 16;
-        return mib / 1.024 / (desc[i].method == ZPK_METHOD_LZ4 ? (stored_like ? 1.0 : 0.15) : (stored_like ? 0.9 : 0.031));
-    };
-    auto pj_ms = [&](u64 i) { return (desc[i].method == ZPK_METHOD_LZ4 ? 0.6 : 4.2) + (double)desc[i].uncomp_size / (1 << 20) / 12.0 / 1.024; };
-    std::sort(pj.begin(), pj.end(), [&](const PjEntry& a, const PjEntry& b) { return wave_ms(a.idx) > wave_ms(b.idx); });
-    double other = 0;                                                         // the longest entry that is not a candidate at all
-    { std::vector<u8> cand(n, 0); for (auto& P : pj) cand[P.idx] = 1;
-      for (u64 i = 0; i < n; i++) if (!cand[i] && desc[i].method != ZPK_METHOD_NONE && desc[i].uncomp_size >= (64u << 10)) { const double t = wave_ms(i); if (t > other) other = t; } }
-    std::vector<double> tk(pj.size() + 1);
-    double best = 1e300, acc = 0;
-    for (size_t k = 0; k <= pj.size(); k++) {                                 // the first k block-parallel
-        const double rest_ms = k < pj.size() ? wave_ms(pj[k].idx) : 0.0;
-        tk[k] = acc + (rest_ms > other ? rest_ms : other);
-        if (tk[k] < best) best = tk[k];
-        if (k < pj.size()) acc += pj_ms(pj[k].idx);
-    }
-    size_t keep = pj.size();                                                  // (the estimates are rough: as many as come within 10 % of the best)
-    while (keep > 0 && tk[keep] > 1.1 * best) keep--;
-    pj.resize(keep);
+    std::vector<u64> cand(pj.size());
+    for (size_t k = 0; k < pj.size(); k++) cand[k] = pj[k].idx;
+    std::vector<PjEntry> chosen;
+    for (u64 k : dec_choose(desc, n, cand.data(), cand.size())) chosen.push_back(std::move(pj[k]));
+    pj.swap(chosen);
 }
+
+// One accepted frame through the block-parallel reader of its method.  -> ZPK_OK with redo = 0: decoded, hashed, delivered, `result` is
+// its verdict; redo = 1: not this path's, `result` is to be ignored (the one-wave decoder decides)
+static int decode_big_single(zpk_codec* c, PjEntry& P, const zpk_decode_desc& d, const BigSrc& src, const BigDst& dst, zpk_decode_result& result, u8& redo)
+{
+    if (d.method == ZPK_METHOD_LZ4) return decode_big_lz4_single(c, src, d, P.blocks, P.independent, dst, result, redo);
+    return decode_big_zstd_single(c, src, d, P.zblocks, P.slots, P.lit_total, dst, result, redo);
+}
+
+// the counts decode_stats2 reports of the most recent decode call: none yet
+static void begin_decode_call(zpk_codec* c) { c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0; }
 
 static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                    uint8_t* const* dst_ptrs, zpk_decode_result* results)
@@ -1733,8 +1737,7 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
             // except for stored entries, whose slot is the smaller of the two and whose guard passed or failed on the host values)
             if (d.method == ZPK_METHOD_NONE && d.dst_capacity >= d.uncomp_size) hd[first + cnt].dst_capacity = slot_bytes;
             out_total += slot;
-            const bool ok = d.comp_size && d.src_offset <= archive_size && d.comp_size <= archive_size - d.src_offset;
-            if (ok) { if (d.src_offset < lo) lo = d.src_offset; if (d.src_offset + d.comp_size > hi) hi = d.src_offset + d.comp_size; comp_sum += d.comp_size; }
+            if (dec_has_payload(d) && dec_src_in_image(d, archive_size)) { if (d.src_offset < lo) lo = d.src_offset; if (d.src_offset + d.comp_size > hi) hi = d.src_offset + d.comp_size; comp_sum += d.comp_size; }
             if (d.method == ZPK_METHOD_ZSTD) has_zstd = 1;
             if (d.method == ZPK_METHOD_LZ4) has_lz4 = 1;
             cnt++;
@@ -1752,9 +1755,7 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
             u64 pos = 0;
             for (u64 i = first; i < first + cnt; i++) {
                 const zpk_decode_desc& d = desc[i];
-                const bool in_image = d.comp_size && d.src_offset <= archive_size && d.comp_size <= archive_size - d.src_offset;
-                const bool passes = in_image && d.src_offset + d.comp_size < archive_size;
-                if (passes) { memcpy(gathered + pos, archive + d.src_offset, d.comp_size); hd[i].src_offset = pos; pos += d.comp_size; }
+                if (dec_has_payload(d) && dec_src_passes(d, archive_size)) { memcpy(gathered + pos, archive + d.src_offset, d.comp_size); hd[i].src_offset = pos; pos += d.comp_size; }
                 else hd[i].src_offset = total + 1;
             }
             gathered[pos] = 0;
@@ -1779,7 +1780,7 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0;
+    begin_decode_call(c);
     // ---- which entries are sequences of frames worth decoding frame-parallel ----
     std::vector<BigEntry> be;
     std::vector<BigSub> subs;
@@ -1788,9 +1789,7 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
         try {
             for (u64 i = 0; i < n; i++) {
                 const zpk_decode_desc& d = desc[i];
-                if (d.uncomp_size < c->dec_split_min || d.uncomp_size > ZPK_HOST_CHUNK_BYTES || d.method > ZPK_METHOD_LZ4) continue;
-                // every guard of lib/zpack_read.c:328-348 must pass: an entry that earns a verdict there gets it from the usual path
-                if (!d.comp_size || d.src_offset > archive_size || d.comp_size >= archive_size - d.src_offset || d.dst_capacity < d.uncomp_size) continue;
+                if (!dec_big_candidate(d, archive_size, c->dec_split_min)) continue;      // (an entry that earns a verdict from a guard gets it from the usual path)
                 const size_t s0 = subs.size();
                 bool ok = false;
                 if (d.method == ZPK_METHOD_NONE) {
@@ -1801,29 +1800,17 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
                         }
                         ok = true;
                     }
-                } else if (d.method == ZPK_METHOD_LZ4) {
-                    ok = walk_lz4_frames(archive + d.src_offset, d.comp_size, d.uncomp_size, subs);
-                    if (!ok) {                                                        // ONE frame (what the reference writes): block-parallel
-                        PjEntry P; P.idx = i; P.independent = 0; P.slots = P.lit_total = 0;
-                        if (walk_lz4_single(archive + d.src_offset, d.comp_size, d.uncomp_size, P.blocks, P.independent)) pj.push_back(std::move(P));
-                    }
-                }
-                else {
-                    ok = walk_zstd_frames(archive + d.src_offset, d.comp_size, d.uncomp_size, subs);
-                    if (!ok) {                                                        // ONE frame (what the reference writes): block-parallel
-                        PjEntry P; P.idx = i; P.independent = 0; P.slots = P.lit_total = 0;
-                        if (walk_zstd_single(archive + d.src_offset, d.comp_size, d.uncomp_size, P.zblocks, P.slots, P.lit_total)) pj.push_back(std::move(P));
-                    }
+                } else {
+                    const u8* const p = archive + d.src_offset;
+                    ok = d.method == ZPK_METHOD_LZ4 ? walk_lz4_frames(p, d.comp_size, d.uncomp_size, subs) : walk_zstd_frames(p, d.comp_size, d.uncomp_size, subs);
+                    PjEntry P;                                                        // ONE frame (what the reference writes): block-parallel
+                    if (!ok && walk_single(p, d, i, P)) pj.push_back(std::move(P));
                 }
                 if (ok) be.push_back(BigEntry{ i, (u64)s0, (u64)(subs.size() - s0) });
             }
         } catch (...) { be.clear(); subs.clear(); pj.clear(); }                       // out of host memory for the plan: the usual path
     }
-    if (be.empty() && pj.empty()) {
-        const int rc = decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results);
-        c->zstd_hint = -1; c->lz4_hint = -1;
-        return rc;
-    }
+    if (be.empty() && pj.empty()) return decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results);
     int rc = ZPK_OK;
     try {
         std::vector<u8> redo(be.size(), 0), is_big(n, 0);
@@ -1838,10 +1825,7 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
         pj_choose(desc, n, pj);
         for (u64 k = 0; k < pj.size() && rc == ZPK_OK; k++) {                         // one large frame at a time: each fills the chip
             u8 again = 1;
-            if (desc[pj[k].idx].method == ZPK_METHOD_LZ4)
-                rc = decode_big_lz4_single(c, archive, desc[pj[k].idx], pj[k].blocks, pj[k].independent, dst_ptrs[pj[k].idx], results[pj[k].idx], again);
-            else
-                rc = decode_big_zstd_single(c, archive, desc[pj[k].idx], pj[k].zblocks, pj[k].slots, pj[k].lit_total, dst_ptrs[pj[k].idx], results[pj[k].idx], again);
+            rc = decode_big_single(c, pj[k], desc[pj[k].idx], BigSrc{ archive, false }, BigDst{ dst_ptrs[pj[k].idx], false }, results[pj[k].idx], again);
             if (rc == ZPK_OK && !again) is_big[pj[k].idx] = 1;
         }
         std::vector<u64> rest;
@@ -1851,9 +1835,7 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
             std::vector<uint8_t*> rp(rest.size());
             std::vector<zpk_decode_result> rr(rest.size());
             for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = dst_ptrs[rest[k]]; }
-            const u32 keep0 = c->big_last[0], keep1 = c->big_last[1];
             rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data());
-            c->big_last[0] = keep0; c->big_last[1] = keep1;
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
@@ -1864,28 +1846,28 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
 // ---- large STORED entries of a device-resident call, copied and hashed by the whole chip (round 17; stored_plan.h, stored_span.h) ----
 // The entries of desc[0, n) that stored_span_takes, in one k_stored_span (the copy fused with the XXH3 partial sums, any number of spans),
 // one k_xxh3_chain with one wave per span — on the SOURCE, so it does not wait for the copy's bytes — and the copy home of the hashes,
-// all enqueued on `st`.  The table goes up from pinned memory the codec owns and the hashes land there: both calls that use this wait
-// for `st` before they return, so one block suffices.  run.idx = the entries taken (none when the option is off, nothing qualifies or
-// there is no memory for the tables: those stay with the one-wave launch); their results are composed by stored_span_finish once `st`
-// has drained.
-struct StoredSpanRun { std::vector<u64> idx; const u64* h_hash = nullptr; };
+// all enqueued on run.st: the codec's stream or, `fork`, a second stream beside it (the slots are disjoint, and the chain is one wave per
+// span, so the rest of the chip is free while it runs).  The table goes up from pinned memory the codec owns and the hashes land there.
+// run.idx = the entries taken (none when the option is off, nothing qualifies or there is no memory for the tables: those stay with the
+// one-wave launch); stored_span_finish waits for run.st and composes their results.  A run that goes out of scope unfinished — every
+// error path of its call — waits too: nothing stays in flight that reads the pinned block or writes the caller's slots.
+struct StoredSpanRun {
+    std::vector<u64> idx; const u64* h_hash = nullptr; hipStream_t st = nullptr;
+    ~StoredSpanRun() { if (st) (void)hipStreamSynchronize(st); }
+};
 static int stored_span_enqueue(zpk_codec* c, const u8* d_archive, u64 archive_size, const zpk_decode_desc* desc, u64 n, u8* d_dst, u64 dst_size,
-                               hipStream_t st, StoredSpanRun& run)
+                               bool fork, StoredSpanRun& run)
 {
-    run.idx.clear(); run.h_hash = nullptr;
     if (c->stored_span_min == ~0ull) return ZPK_OK;
     u64 k = 0;
     for (u64 i = 0; i < n; i++) k += stored_span_takes(desc[i], archive_size, dst_size, c->stored_span_min) ? 1 : 0;
     if (k == 0) return ZPK_OK;
+    const hipStream_t st = fork && fork_stream(c->span, c->stream, false) ? c->span.s : c->stream;
     const u64 dst_at = (k * sizeof(StoredSpanRow) + 255) & ~255ull, up_bytes = dst_at + ((k * 8 + 255) & ~255ull), h_total = up_bytes + k * 8;
-    if (c->h_sspan_cap < h_total) {
-        if (c->h_sspan) { (void)hipHostFree(c->h_sspan); c->h_sspan = nullptr; c->h_sspan_cap = 0; }
-        const u64 want = h_total + h_total / 4 + 4096;
-        if (hipHostMalloc((void**)&c->h_sspan, want, hipHostMallocDefault) == hipSuccess) c->h_sspan_cap = want;
-        else { (void)hipGetLastError(); c->h_sspan = nullptr; return ZPK_OK; }
-    }
-    StoredSpanRow* const rows = (StoredSpanRow*)c->h_sspan;
-    u64* const dst_off = (u64*)(c->h_sspan + dst_at);
+    if (!grow_pinned(c->h_sspan, h_total)) return ZPK_OK;                            // no pinned memory for the table: one wave per entry
+    u8* const h_sspan = c->h_sspan.p;
+    StoredSpanRow* const rows = (StoredSpanRow*)h_sspan;
+    u64* const dst_off = (u64*)(h_sspan + dst_at);
     StoredPlan plan = { 0, 0, 0 };
     run.idx.reserve(k);
     for (u64 i = 0; i < n; i++)
@@ -1899,35 +1881,60 @@ static int stored_span_enqueue(zpk_codec* c, const u8* d_archive, u64 archive_si
     const zpk_span* const d_spans = (const zpk_span*)(u8*)c->d_sspan;
     u64* const d_part = (u64*)(c->d_sspan + part_at);
     u64* const d_hash = (u64*)(c->d_sspan + hash_at);
-    u64* const h_hash = (u64*)(c->h_sspan + up_bytes);
-    HIPCHK(c, hipMemcpyAsync(c->d_sspan, c->h_sspan, up_bytes, hipMemcpyHostToDevice, st));
+    run.h_hash = (const u64*)(h_sspan + up_bytes);
+    run.st = st;
+    HIPCHK(c, hipMemcpyAsync(c->d_sspan, h_sspan, up_bytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_stored_span, dim3((u32)((plan.groups + 3) / 4)), dim3(256), 0, st, d_archive, d_dst, d_spans,
                        (const u64*)(c->d_sspan + dst_at), (u32)plan.nspans, plan.groups, d_part);
     hipLaunchKernelGGL(k_xxh3_chain, dim3((u32)plan.nspans), dim3(64), 0, st, d_archive, d_spans, (const u64*)d_part, d_hash, (u64*)nullptr, (u64)0, ~(u64)0, 1);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_hash, d_hash, plan.nspans * 8, hipMemcpyDeviceToHost, st));
-    run.h_hash = h_hash;
+    HIPCHK(c, hipMemcpyAsync(h_sspan + up_bytes, d_hash, plan.nspans * 8, hipMemcpyDeviceToHost, st));
     c->span_last[0] = (u32)plan.nspans; c->span_last[1] = (u32)(plan.groups > 0xFFFFFFFFull ? 0xFFFFFFFFull : plan.groups);
     return ZPK_OK;
 }
-// ... and their results, once the stream of stored_span_enqueue has drained
-static void stored_span_finish(const StoredSpanRun& run, const zpk_decode_desc* desc, zpk_decode_result* results)
+// ... the join: their stream has drained -> their hashes are in the pinned block, their results are composed
+static int stored_span_finish(zpk_codec* c, StoredSpanRun& run, const zpk_decode_desc* desc, zpk_decode_result* results)
 {
-    for (u64 k = 0; k < run.idx.size(); k++) results[run.idx[k]] = stored_span_verdict(desc[run.idx[k]], run.h_hash[k]);
+    if (run.idx.empty()) return ZPK_OK;
+    const hipStream_t st = run.st;
+    run.st = nullptr;
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (u64 k = 0; k < run.idx.size(); k++) results[run.idx[k]] = dec_hash_verdict(desc[run.idx[k]], run.h_hash[k]);
+    return ZPK_OK;
 }
-// Waits for a stream when it goes out of scope: every return path behind a fork — the error paths too — leaves nothing in flight that
-// reads the codec's pinned block or writes the caller's slots.
-struct StreamDrain {
-    hipStream_t s = nullptr;
-    ~StreamDrain() { if (s) (void)hipStreamSynchronize(s); }
-};
+
+// The one-wave tail of the device-resident calls: entries desc[rest[0, nr)] through the one-wave kernels in ONE launch over their
+// descriptors, exactly as zpk_codec_decode_batch_device would (every verdict other than OK / hash mismatch is theirs), their results
+// scattered to results[rest[k]]; returns when they are home.  No entry left while the stored spans took some: no work list held an entry
+// in this call, the counters say so.
+static int decode_rest_device(zpk_codec* c, const u8* d_archive, u64 archive_size, const zpk_decode_desc* desc, const u64* rest, u64 nr,
+                              u8* d_dst, u64 dst_size, zpk_decode_result* results)
+{
+    if (nr == 0) {
+        if (c->span_last[0]) { (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->totals_valid = 0; }
+        return ZPK_OK;
+    }
+    std::vector<zpk_decode_desc> rd(nr);
+    std::vector<zpk_decode_result> rr(nr);
+    for (u64 k = 0; k < nr; k++) rd[k] = desc[rest[k]];
+    int rc;
+    if ((rc = grow(c, c->d_desc, nr * sizeof(zpk_decode_desc))) || (rc = grow(c, c->d_res, nr * sizeof(zpk_decode_result)))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_desc, rd.data(), nr * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream));
+    c->zstd_hint = -1; c->lz4_hint = -1;
+    if ((rc = decode_launch(c, d_archive, archive_size, d_archive, d_archive + archive_size, (const zpk_decode_desc*)c->d_desc, nr,
+                            d_dst, dst_size, (zpk_decode_result*)c->d_res, c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(rr.data(), c->d_res, nr * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (u64 k = 0; k < nr; k++) results[rest[k]] = rr[k];
+    return ZPK_OK;
+}
 
 // ONE entry whose compressed bytes are ON THE DEVICE, decoded into device memory (round 5; the device-pointer form of what
 // zpk_codec_decode_batch_host does for a large single frame).  desc and result are HOST memory; the call returns when the entry is
 // decoded and verified.  A large entry that is one frame of the reference writer is decoded block-parallel (lz4_pj.h / zstd_pj.h): its
 // compressed bytes come to the host once, into a pinned buffer, for the walk over the block headers (2.6 ms for 130 MiB; the walk on
 // the device, k_big_walk, measured 1.77 ms for such an LZ4 entry but 77.6 ms for a Zstandard one: profiles/r15), everything else stays
-// on the device.  Any other entry — and any
+// on the device — a sole candidate always goes block-parallel, the chooser (dec_choose) is the batch call's.  Any other entry — and any
 // entry the block-parallel path does not finish — is decoded by the one-wave kernels, exactly as zpk_codec_decode_batch_device would.
 int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc,
                                 uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* result)
@@ -1935,75 +1942,38 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
     if (!c || !desc || !result || !d_archive) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0;
+    begin_decode_call(c);
     const zpk_decode_desc d = *desc;
-    u8 redo = 1;
     int rc = ZPK_OK;
-    if (d_dst && stored_span_takes(d, archive_size, dst_size, c->stored_span_min)) {   // a large stored entry: copied and hashed chip-wide (serial form)
-        try {
+    bool done = false;                                                                // a chip-wide path has finished the entry
+    try {
+        if (d_dst && stored_span_takes(d, archive_size, dst_size, c->stored_span_min)) {   // a large stored entry: copied and hashed chip-wide (serial form)
             StoredSpanRun run;
-            StreamDrain drain; drain.s = c->stream;
-            if ((rc = stored_span_enqueue(c, d_archive, archive_size, &d, 1, d_dst, dst_size, c->stream, run))) return rc;
-            if (!run.idx.empty()) {
-                drain.s = nullptr;
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                stored_span_finish(run, &d, result);
-                (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->totals_valid = 0;   // no work list held an entry in this call
-                return ZPK_OK;
-            }
-            drain.s = nullptr;
-        } catch (...) { c->span_last[0] = c->span_last[1] = 0; }
-    }
-    const bool guards = d.comp_size && d.src_offset <= archive_size && d.comp_size < archive_size - d.src_offset && d.dst_capacity >= d.uncomp_size &&
-                        d.dst_offset <= dst_size && d.uncomp_size <= dst_size - d.dst_offset;
-    if (guards && c->dec_split_min != ~0ull && d.uncomp_size >= c->dec_split_min && d.uncomp_size <= ZPK_HOST_CHUNK_BYTES &&
-        (d.method == ZPK_METHOD_LZ4 || d.method == ZPK_METHOD_ZSTD) && d_dst) {
-        bool have = c->h_bigsrc_cap >= d.comp_size;
-        if (!have) {
-            if (c->h_bigsrc) { (void)hipHostFree(c->h_bigsrc); c->h_bigsrc = nullptr; c->h_bigsrc_cap = 0; }
-            const u64 want = d.comp_size + d.comp_size / 4 + 4096;
-            if (hipHostMalloc((void**)&c->h_bigsrc, want, hipHostMallocDefault) == hipSuccess) { c->h_bigsrc_cap = want; have = true; }
-            else { (void)hipGetLastError(); c->h_bigsrc = nullptr; }
-        }
-        if (have) {
-            hipError_t e = hipMemcpyAsync(c->h_bigsrc, d_archive + d.src_offset, d.comp_size, hipMemcpyDeviceToHost, c->stream);
+            if ((rc = stored_span_enqueue(c, d_archive, archive_size, &d, 1, d_dst, dst_size, false, run)) || (rc = stored_span_finish(c, run, &d, result))) return rc;
+            done = !run.idx.empty();
+        } else if (d_dst && dec_big_candidate_device(d, archive_size, dst_size, c->dec_split_min) && grow_pinned(c->h_bigsrc, d.comp_size)) {
+            u8* const h_src = c->h_bigsrc.p;                                          // (no pinned memory for the entry's bytes: one wave)
+            hipError_t e = hipMemcpyAsync(h_src, d_archive + d.src_offset, d.comp_size, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large entry: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-            try {
+            PjEntry P;
+            if (walk_single(h_src, d, 0, P)) {
                 zpk_decode_result r; memset(&r, 0, sizeof(r));
-                if (d.method == ZPK_METHOD_LZ4) {
-                    std::vector<PjBlock> blocks; int independent = 0;
-                    if (walk_lz4_single(c->h_bigsrc, d.comp_size, d.uncomp_size, blocks, independent))
-                        rc = decode_big_lz4_single(c, nullptr, d, blocks, independent, nullptr, r, redo, d_archive, d_dst + d.dst_offset);
-                } else {
-                    std::vector<ZpjBlock> zb; u64 slots = 0, lit_total = 0;
-                    if (walk_zstd_single(c->h_bigsrc, d.comp_size, d.uncomp_size, zb, slots, lit_total))
-                        rc = decode_big_zstd_single(c, nullptr, d, zb, slots, lit_total, nullptr, r, redo, d_archive, d_dst + d.dst_offset);
-                }
-                if (rc != ZPK_OK) return rc;
-                if (!redo) { *result = r; return ZPK_OK; }
-            } catch (...) { redo = 1; }
+                u8 redo = 1;
+                if ((rc = decode_big_single(c, P, d, BigSrc{ d_archive, true }, BigDst{ d_dst + d.dst_offset, true }, r, redo))) return rc;
+                if (!redo) { *result = r; done = true; }
+            }
         }
-    }
-    // ---- the one-wave kernels (every verdict is theirs) ----
-    if (!c->d_big1 && hipMalloc(&c->d_big1.p, 512) != hipSuccess) { c->d_big1.p = nullptr; (void)hipGetLastError(); return ZPK_E_NOMEM; }
-    zpk_decode_desc* const dd = (zpk_decode_desc*)c->d_big1;
-    zpk_decode_result* const dr = (zpk_decode_result*)(c->d_big1 + 256);
-    HIPCHK(c, hipMemcpyAsync(dd, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
-    c->zstd_hint = -1; c->lz4_hint = -1;
-    const u32 keep0 = c->big_last[0], keep1 = c->big_last[1];
-    if ((rc = decode_launch(c, d_archive, archive_size, d_archive, d_archive + archive_size, dd, 1, d_dst, dst_size, dr, c->stream))) return rc;
-    c->big_last[0] = keep0; c->big_last[1] = keep1;
-    HIPCHK(c, hipMemcpyAsync(result, dr, sizeof(*result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZPK_OK;
+    } catch (...) { c->span_last[0] = c->span_last[1] = 0; }                          // out of host memory for a table: one wave
+    const u64 self = 0;
+    try { rc = decode_rest_device(c, d_archive, archive_size, &d, &self, done ? 0 : 1, d_dst, dst_size, result); } catch (...) { rc = ZPK_E_NOMEM; }
+    return rc;
 }
 
 // A BATCH whose compressed bytes are ON THE DEVICE and whose output stays there, with large entries in it (the batch form of
 // zpk_codec_decode_big_device, the read-side mirror of zpk_codec_encode_big_device).  desc and results are HOST memory; the call returns
 // when every entry is decoded and verified.  The compressed bytes never leave the device: k_big_walk (big_walk.h) walks the block headers
-// of every candidate — an LZ4 / Zstandard entry of at least ZPK_OPT_DEC_SPLIT_MIN bytes that passes the guards of lib/zpack_read.c:328-348,
-// the conditions zpk_codec_decode_big_device tests — side by side where they lie, and the records and block tables come home in one copy.
+// of every candidate (dec_big_candidate_device, as in zpk_codec_decode_big_device) side by side where they lie, one copy brings the tables home.
 // Of the frames the walk accepted, pj_choose picks those worth a turn of the whole chip (lz4_pj.h / zstd_pj.h, one after the other);
 // every other entry — and every entry the block-parallel path does not finish — is decoded by the one-wave kernels in ONE launch over
 // their descriptors, exactly as zpk_codec_decode_batch_device would: every verdict other than OK / hash mismatch is theirs.
@@ -2015,80 +1985,40 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
     if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0;
+    begin_decode_call(c);
     int rc = ZPK_OK;
-    StoredSpanRun span;
-    StreamDrain drain;                                                                // (declared in front of the try: it waits on every way out)
+    StoredSpanRun span;                                                               // (declared in front of the try: it waits on every way out)
     try {
         // ---- the large stored entries: copy + XXH3 across the chip.  Serial form: on c->stream, in front of the walk.  Forked form: on a
-        // second stream beside the walk, the block-parallel entries and the one-wave launch — the slots are disjoint, and the chain is one
-        // wave per span, so the rest of the chip is free while it runs.
-        {
-            bool any = false;
-            if (c->stored_span_min != ~0ull) for (u64 i = 0; i < n && !any; i++) any = stored_span_takes(desc[i], archive_size, dst_size, c->stored_span_min);
-            if (any) {
-                hipStream_t ss = c->stream;
-                if (ZPK_STORED_SPAN_FORK && fork_stream(c->span, c->stream, false)) ss = c->span.s;
-                drain.s = ss;
-                if ((rc = stored_span_enqueue(c, d_archive, archive_size, desc, n, d_dst, dst_size, ss, span))) return rc;
-                if (span.idx.empty()) drain.s = nullptr;
-            }
-        }
-        // ---- the candidates and where their tables go: [ items | records | tables ], the same layout on the device and in pinned host memory ----
+        // second stream beside the walk, the block-parallel entries and the one-wave launch.
+        if ((rc = stored_span_enqueue(c, d_archive, archive_size, desc, n, d_dst, dst_size, ZPK_STORED_SPAN_FORK != 0, span))) return rc;
+        // ---- the candidates, walked where they lie: one launch over all of them, one copy home (records + tables), one synchronisation ----
         std::vector<u64> cand;
-        if (c->dec_split_min != ~0ull)
-            for (u64 i = 0; i < n; i++) {
-                const zpk_decode_desc& d = desc[i];
-                const bool guards = d.comp_size && d.src_offset <= archive_size && d.comp_size < archive_size - d.src_offset && d.dst_capacity >= d.uncomp_size &&
-                                    d.dst_offset <= dst_size && d.uncomp_size <= dst_size - d.dst_offset;
-                if (guards && d.uncomp_size >= c->dec_split_min && d.uncomp_size <= ZPK_HOST_CHUNK_BYTES &&
-                    (d.method == ZPK_METHOD_LZ4 || d.method == ZPK_METHOD_ZSTD)) cand.push_back(i);
-            }
+        for (u64 i = 0; i < n; i++) if (dec_big_candidate_device(desc[i], archive_size, dst_size, c->dec_split_min)) cand.push_back(i);
         const u64 nc = cand.size();
-        const u64 rec_off = (nc * sizeof(BigWalkItem) + 255) & ~255ull, tab0 = rec_off + ((nc * sizeof(BigWalkRec) + 255) & ~255ull);
-        u64 total = tab0;
-        std::vector<u64> tab_off(nc);
-        for (u64 k = 0; k < nc; k++) {
-            const zpk_decode_desc& d = desc[cand[k]];
-            const u64 cap = d.method == ZPK_METHOD_LZ4 ? walk_lz4_capacity(d.uncomp_size) : walk_zstd_capacity(d.uncomp_size);
-            tab_off[k] = total;
-            total += (cap * (d.method == ZPK_METHOD_LZ4 ? sizeof(PjBlock) : sizeof(ZpjBlock)) + 15) & ~15ull;
-        }
-        bool walk = nc > 0;
-        if (walk && c->h_bigwalk_cap < total) {
-            if (c->h_bigwalk) { (void)hipHostFree(c->h_bigwalk); c->h_bigwalk = nullptr; c->h_bigwalk_cap = 0; }
-            const u64 want = total + total / 4 + 4096;
-            if (hipHostMalloc((void**)&c->h_bigwalk, want, hipHostMallocDefault) == hipSuccess) c->h_bigwalk_cap = want;
-            else { (void)hipGetLastError(); c->h_bigwalk = nullptr; walk = false; }       // no memory for the tables: one wave per entry
-        }
-        if (walk && grow(c, c->d_bigwalk, total)) { c->err[0] = 0; walk = false; }
+        std::vector<BigWalkItem> items;
+        const BigWalkLayout L = dec_walk_layout(desc, cand.data(), nc, items);
         std::vector<PjEntry> pj;
+        bool walk = nc > 0 && grow_pinned(c->h_bigwalk, L.total);
+        if (walk && grow(c, c->d_bigwalk, L.total)) { c->err[0] = 0; walk = false; }  // no memory for the tables, pinned or on the device: one wave per entry
         if (walk) {
-            BigWalkItem* const items = (BigWalkItem*)c->h_bigwalk;
-            for (u64 k = 0; k < nc; k++) {
-                const zpk_decode_desc& d = desc[cand[k]];
-                BigWalkItem& it = items[k];
-                it.src_off = d.src_offset; it.comp = d.comp_size; it.uncomp = d.uncomp_size; it.tab_off = tab_off[k]; it.method = d.method;
-                it.cap = (u32)(d.method == ZPK_METHOD_LZ4 ? walk_lz4_capacity(d.uncomp_size) : walk_zstd_capacity(d.uncomp_size));
-            }
-            // ---- one launch over all candidates, one copy home (records + tables), one synchronisation ----
-            HIPCHK(c, hipMemcpyAsync(c->d_bigwalk, items, nc * sizeof(BigWalkItem), hipMemcpyHostToDevice, c->stream));
+            u8* const h_walk = c->h_bigwalk.p;
+            memcpy(h_walk, items.data(), nc * sizeof(BigWalkItem));
+            HIPCHK(c, hipMemcpyAsync(c->d_bigwalk, h_walk, nc * sizeof(BigWalkItem), hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(k_big_walk, dim3((u32)nc), dim3(64), 0, c->stream, d_archive, (const BigWalkItem*)(u8*)c->d_bigwalk, (u32)nc,
-                               (u8*)c->d_bigwalk, (BigWalkRec*)(c->d_bigwalk + rec_off));
+                               (u8*)c->d_bigwalk, (BigWalkRec*)(c->d_bigwalk + L.rec_off));
             HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(c->h_bigwalk + rec_off, c->d_bigwalk + rec_off, total - rec_off, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h_walk + L.rec_off, c->d_bigwalk + L.rec_off, L.total - L.rec_off, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            const BigWalkRec* const recs = (const BigWalkRec*)(c->h_bigwalk + rec_off);
+            const BigWalkRec* const recs = (const BigWalkRec*)(h_walk + L.rec_off);
             c->walk_last[0] = (u32)nc;
             for (u64 k = 0; k < nc; k++) {
                 const BigWalkRec& r = recs[k];
-                const zpk_decode_desc& d = desc[cand[k]];
-                const u64 cap = d.method == ZPK_METHOD_LZ4 ? walk_lz4_capacity(d.uncomp_size) : walk_zstd_capacity(d.uncomp_size);
-                if (r.accepted != 1 || r.nblocks == 0 || r.nblocks > cap) continue;
+                if (r.accepted != 1 || r.nblocks == 0 || r.nblocks > items[k].cap) continue;
                 c->walk_last[1]++;
                 PjEntry P; P.idx = cand[k]; P.independent = (int)(r.independent & 1); P.slots = r.slots; P.lit_total = r.lit_total;
-                if (d.method == ZPK_METHOD_LZ4) { const PjBlock* t = (const PjBlock*)(c->h_bigwalk + tab_off[k]); P.blocks.assign(t, t + r.nblocks); }
-                else { const ZpjBlock* t = (const ZpjBlock*)(c->h_bigwalk + tab_off[k]); P.zblocks.assign(t, t + r.nblocks); }
+                if (items[k].method == ZPK_METHOD_LZ4) { const PjBlock* t = (const PjBlock*)(h_walk + items[k].tab_off); P.blocks.assign(t, t + r.nblocks); }
+                else { const ZpjBlock* t = (const ZpjBlock*)(h_walk + items[k].tab_off); P.zblocks.assign(t, t + r.nblocks); }
                 pj.push_back(std::move(P));
             }
         }
@@ -2099,41 +2029,14 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
             const zpk_decode_desc& d = desc[pj[k].idx];
             zpk_decode_result r; memset(&r, 0, sizeof(r));
             u8 again = 1;
-            if (d.method == ZPK_METHOD_LZ4)
-                rc = decode_big_lz4_single(c, nullptr, d, pj[k].blocks, pj[k].independent, nullptr, r, again, d_archive, d_dst + d.dst_offset);
-            else
-                rc = decode_big_zstd_single(c, nullptr, d, pj[k].zblocks, pj[k].slots, pj[k].lit_total, nullptr, r, again, d_archive, d_dst + d.dst_offset);
-            if (rc != ZPK_OK) return rc;
+            if ((rc = decode_big_single(c, pj[k], d, BigSrc{ d_archive, true }, BigDst{ d_dst + d.dst_offset, true }, r, again))) return rc;
             if (!again) { results[pj[k].idx] = r; is_big[pj[k].idx] = 1; }
         }
         // ---- everything else through the one-wave kernels, one launch (every verdict is theirs) ----
         std::vector<u64> rest;
         for (u64 i = 0; i < n; i++) if (!is_big[i]) rest.push_back(i);
-        if (!rest.empty()) {
-            const u64 nr = rest.size();
-            std::vector<zpk_decode_desc> rd(nr);
-            std::vector<zpk_decode_result> rr(nr);
-            for (u64 k = 0; k < nr; k++) rd[k] = desc[rest[k]];
-            if ((rc = grow(c, c->d_desc, nr * sizeof(zpk_decode_desc))) || (rc = grow(c, c->d_res, nr * sizeof(zpk_decode_result)))) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->d_desc, rd.data(), nr * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream));
-            c->zstd_hint = -1; c->lz4_hint = -1;
-            const u32 keep0 = c->big_last[0], keep1 = c->big_last[1];
-            if ((rc = decode_launch(c, d_archive, archive_size, d_archive, d_archive + archive_size, (const zpk_decode_desc*)c->d_desc, nr,
-                                    d_dst, dst_size, (zpk_decode_result*)c->d_res, c->stream))) return rc;
-            c->big_last[0] = keep0; c->big_last[1] = keep1;
-            HIPCHK(c, hipMemcpyAsync(rr.data(), c->d_res, nr * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (u64 k = 0; k < nr; k++) results[rest[k]] = rr[k];
-        } else if (!span.idx.empty()) {
-            (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->totals_valid = 0;       // no work list held an entry in this call
-        }
-        // ---- the join: the stored spans' stream has drained -> their hashes are in the pinned block ----
-        if (!span.idx.empty()) {
-            const hipStream_t ss = drain.s;
-            drain.s = nullptr;
-            HIPCHK(c, hipStreamSynchronize(ss));
-            stored_span_finish(span, desc, results);
-        }
+        if ((rc = decode_rest_device(c, d_archive, archive_size, desc, rest.data(), rest.size(), d_dst, dst_size, results))) return rc;
+        rc = stored_span_finish(c, span, desc, results);
     } catch (...) { rc = ZPK_E_NOMEM; }
     return rc;
 }

@@ -1760,17 +1760,8 @@ static int big_tables_block(zpk_codec* c, u64 need, u8** out, int* slot)
     const int k = (int)(c->bigenc_turn++ & 1u);
     if (!c->bigenc_ev[k]) HIPCHK(c, hipEventCreateWithFlags(&c->bigenc_ev[k], hipEventDisableTiming));
     else HIPCHK(c, hipEventSynchronize(c->bigenc_ev[k]));
-    if (c->h_bigenc_cap[k] < need) {
-        if (c->h_bigenc[k]) (void)hipHostFree(c->h_bigenc[k]);
-        c->h_bigenc[k] = nullptr; c->h_bigenc_cap[k] = 0;
-        const u64 want = need + need / 4 + 4096;
-        if (hipHostMalloc((void**)&c->h_bigenc[k], want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); c->h_bigenc[k] = nullptr;
-            snprintf(c->err, sizeof(c->err), "pinned tables: out of memory"); return ZPK_E_NOMEM;
-        }
-        c->h_bigenc_cap[k] = want;
-    }
-    *out = c->h_bigenc[k]; *slot = k;
+    if (!grow_pinned(c->h_bigenc[k], need)) { snprintf(c->err, sizeof(c->err), "pinned tables: out of memory"); return ZPK_E_NOMEM; }
+    *out = c->h_bigenc[k].p; *slot = k;
     return ZPK_OK;
 }
 
