@@ -482,8 +482,9 @@ def test_host_batch_takes_the_upload_decode_download_pipeline(codec, method, lev
         assert rc == 0 and outs[i][:k].tobytes() == want
 
 
-def _stream_decode(codec, frame, method, uncomp_size, want_hash, chunk, out_chunk=4096):
-    """zpk_dstream_* directly (include/zpack_codec.h): feed `chunk` bytes per step -> (final status, bytes, input offset at the first output)"""
+def _stream_decode(codec, frame, method, uncomp_size, want_hash, chunk, out_chunk=4096, trace=None):
+    """zpk_dstream_* directly (include/zpack_codec.h): feed `chunk` bytes per step -> (final status, bytes, input offset at the first output);
+    trace(rc, consumed, produced, done, wants_input (-1: a replay), launches, device_bytes) is called after every call"""
     import ctypes as C
     L = codec.L
     L.zpk_dstream_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -501,13 +502,23 @@ def _stream_decode(codec, frame, method, uncomp_size, want_hash, chunk, out_chun
     pos, first, status = 0, None, 0
     consumed, produced, done = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
     stats = _stream_decode.stats = dict(restarts=0, device_peak=0, steps=0)
+    la, ca = C.c_uint64(0), C.c_uint64(0)
+    L.zpk_dstream_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+
+    def report(rc, wants):
+        if trace is not None:
+            L.zpk_dstream_counters(s, C.byref(la), C.byref(ca))
+            trace(rc, consumed.value, produced.value, done.value, wants, la.value, int(L.zpk_dstream_device_bytes(s)))
     for _ in range(1000000):
-        take = min(chunk, len(src) - pos) if L.zpk_dstream_wants_input(s) else 0
+        wants = L.zpk_dstream_wants_input(s)
+        take = min(chunk, len(src) - pos) if wants else 0
         rc = L.zpk_dstream_step(s, method, len(src), uncomp_size, want_hash, src[pos:].ctypes.data if take else None, take, C.byref(consumed),
                                 ob.ctypes.data, out_chunk, C.byref(produced), C.byref(done))
+        report(rc, wants)
         if rc == 1001:                           # ZPK_DS_RESTART (include/zpack_codec.h): the bytes given so far once more, then on
             stats["restarts"] += 1
             rc = L.zpk_dstream_replay(s, method, len(src), uncomp_size, want_hash, src.ctypes.data if pos else None, pos, 1)
+            report(rc, -1)
             if rc == 0:
                 continue
         stats["device_peak"] = max(stats["device_peak"], int(L.zpk_dstream_device_bytes(s)))
@@ -520,8 +531,6 @@ def _stream_decode(codec, frame, method, uncomp_size, want_hash, chunk, out_chun
         if rc not in (0,) or done.value:
             break
         assert consumed.value or produced.value, "a step that neither consumes nor produces"
-    la, ca = C.c_uint64(0), C.c_uint64(0)
-    L.zpk_dstream_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.zpk_dstream_counters(s, C.byref(la), C.byref(ca))
     stats["steps"] = la.value
     L.zpk_dstream_destroy(s)

@@ -13,7 +13,9 @@ typedef int16_t  i16;
 typedef int32_t  i32;
 typedef int64_t  i64;
 
-#define PJ_BLOCK 65536u                          // LZ4F block size of the frames this path takes (BD = 0x40: what the reference writes)
+#define XS_GROUP 64u                             // xxh3_span.h: 1 KiB blocks per wave of the partial pass (the stream steps plan their hash sections in these groups: stream_plan.h)
+
+#define PJ_BLOCK 65536u                         // LZ4F block size of the frames this path takes (BD = 0x40: what the reference writes)
 struct PjBlock { u32 comp_off, comp_size /* bit 31: stored */, rec_base, out_size, out_off, nrec; };
 
 #define ZPJ_BLOCK (128u << 10)

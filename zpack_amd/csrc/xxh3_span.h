@@ -5,6 +5,7 @@
 #pragma once
 #include "zpk_device.h"
 #include "xxh3_device.h"
+#include "pj_types.h"                            // XS_GROUP
 
 namespace zpk {
 
@@ -17,7 +18,7 @@ __device__ __forceinline__ u64 shfl64(u64 v, int from)
     return ((u64)hi << 32) | lo;
 }
 struct zpk_span { u64 off, len, part_base; };    // part_base: index of the span's first block among the partial sums (a multiple of 64)
-#define XS_GROUP 64u                             // blocks per wave of the partial pass
+// XS_GROUP (pj_types.h): blocks per wave of the partial pass
 // groups [g_first, ngroups) of 64 blocks (a caller whose span becomes final piece by piece launches a range of groups per piece)
 __global__ __launch_bounds__(256) void k_xxh3_partials(const u8* __restrict__ src, const zpk_span* __restrict__ spans, u32 nspans,
                                                        u64 g_first, u64 ngroups, u64* __restrict__ partial)

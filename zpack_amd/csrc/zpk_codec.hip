@@ -42,6 +42,7 @@
 #include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
 #include "stored_plan.h"                         // the large stored entries of a device-resident batch: which are taken, their span table, the verdict (plain C++, likewise)
 #include "stored_span.h"                         // k_stored_span: their copy fused with the XXH3 partial sums, across the chip
+#include "stream_plan.h"                         // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
 
 using namespace zpk;
 

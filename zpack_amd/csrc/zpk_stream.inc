@@ -62,7 +62,27 @@ __global__ __launch_bounds__(64) void k_stream_hash(const u8* __restrict__ out, 
     if (lane == 0) rec->hash = h;
 }
 
-#define FZ_TABDESC 192u                            // bytes kept of an FSE table description (53 symbols at accuracy 9 take < 100)
+// What ONLY the bounded block-parallel steps use (round 5; dstream_fast_* below).  DsFastEntry is the state of the entry being read: cleared
+// as a whole between entries (dstream_clear); DsFast adds the buffers, which stay.
+struct DsFastEntry {
+    u64 pend_len;                                // bytes in DsFast::pend
+    u64 in_total;                                // compressed bytes taken so far
+    int hdr, indep, has_cs; u64 content;         // the frame header is parsed (its size); LZ4: independent blocks; content size
+    u64 T, hist, ghashed;                        // output bytes of the finished steps; history bytes in front of the device window; 64 KiB groups hashed
+    u64 avail, given, delivered;                 // the size of the last step's output, what the caller has of it; output bytes handed out in all
+    // Zstandard steps: the window, the repeat offsets and the last block with a Huffman tree travel from step to step
+    u64 window, fcs, hist_cap;
+    u32 reps[3];
+    u32 tree_len;                                // bytes in DsFast::tree
+    u32 tab_mode[3], tab_len[3]; u8 tab_desc[3][FZ_TABDESC];   // host: what governs the three sequence tables (Repeat_Mode blocks of later steps build them again)
+};
+struct DsFast : DsFastEntry {
+    u8* pend; u64 pend_cap;                      // host: compressed bytes that are not decoded yet (from a block boundary on)
+    u8* d_f; u64 f_cap;                          // device: everything an LZ4 step needs (a fixed ~40 MiB, dstream_fast_layout); the scratch of a Zstandard step
+    u8* d_fo; u64 fo_cap;                        // device, Zstandard: [history | a step's output] + what persists between steps (XXH3 state)
+    u8* h_out;                                   // host, pinned: the output of the last step
+    u8* tree;                                    // host: the most recent block whose literals section carries a tree (Treeless blocks of later steps read it)
+};
 struct zpk_dstream {
     zpk_codec* c;                                // the codec of the CURRENT call (a stream outlives codecs: never touched by reset / destroy)
     int device;                                  // where the buffers below live
@@ -77,25 +97,9 @@ struct zpk_dstream {
     // bounded host memory (ZPK_DS_GATHER), at most one launch per ZPK_DS_GATHER bytes of input.
     u8* h_in; u64 h_len;                         // host: compressed bytes taken from the caller, not yet on the device
     u64 launches, calls;                         // (diagnostics: decode steps launched / calls served)
-    // ---- block-parallel steps in bounded memory (round 5; dstream_fast_* below) ----
-    int fast;                                    // 0 undecided, 1 running, -1 not for this entry (the windowless path above)
-    u8* f_pend; u64 f_pend_len, f_pend_cap;      // host: compressed bytes that are not decoded yet (from a block boundary on)
-    u64 f_in_total;                              // compressed bytes taken so far
-    int f_hdr, f_indep, f_has_cs; u64 f_content; // the frame header is parsed (its size); independent blocks; content size
-    u64 f_T, f_hist, f_ghashed;                  // output bytes of the finished steps; history bytes in front of the device window; 64 KiB groups hashed
-    u8* d_f; u64 f_cap;                          // device: everything a step needs (a fixed ~40 MiB, dstream_fast_layout)
-    u8* h_fout;                                  // host, pinned: the output of the last step
-    u64 f_avail, f_given, f_delivered;           // ... its size, what the caller has of it; output bytes handed out in all
-    u64 f_steps;                                 // (diagnostics)
-    // Zstandard steps (dstream_fast_zstd): the window, the repeat offsets and the last block with a Huffman tree travel from step to step
-    u8* d_fo; u64 fo_cap;                        // device: [history | a step's output] + what persists between steps (XXH3 state); d_f is scratch here
-    u64 f_window, f_fcs, f_hist_cap;
-    u32 f_reps[3];
-    u8* f_tree; u32 f_tree_len;                  // host: the most recent block whose literals section carries a tree (Treeless blocks of later steps read it)
-    u32 f_tab_mode[3], f_tab_len[3]; u8 f_tab_desc[3][FZ_TABDESC];   // host: what governs the three sequence tables (Repeat_Mode blocks of later steps build them again)
-    int f_last;                                  // the frame's last block has been decoded
+    int fast;                                    // 0 undecided, 1 the bounded steps are running, -1 not for this entry (the windowless step)
+    DsFast f;
 };
-#define ZPK_DS_GATHER (256u << 10)
 
 // ---- streaming XXH3 of the plaintext: the accumulators of the long-input path between steps ----
 struct zpk_cs_state { u64 acc[8]; u64 hash; };
@@ -151,7 +155,6 @@ static void dfree(u8** p, u64* cap) { if (*p) { (void)hipFree(*p); *p = nullptr;
 
 // device buffer of at least `need` bytes that keeps its first `keep` bytes.  Sizes here derive from what the caller says about the
 // entry: nothing may wrap (a wrapped size would allocate a few bytes and hand the kernels a huge capacity).
-#define ZPK_STREAM_MAX_BYTES (1ull << 46)
 static int dgrow_keep(zpk_codec* c, u8** p, u64* cap, u64 need, u64 keep)
 {
     if (need <= *cap) return ZPK_OK;
@@ -180,15 +183,28 @@ int zpk_dstream_create(zpk_codec* c, zpk_dstream** out)
 static void dstream_release(zpk_dstream* s)
 {
     if (s && s->h_in) { free(s->h_in); s->h_in = nullptr; s->h_len = 0; }
-    if (s && s->f_pend) { free(s->f_pend); s->f_pend = nullptr; s->f_pend_len = s->f_pend_cap = 0; }
-    if (s && s->f_tree) { free(s->f_tree); s->f_tree = nullptr; s->f_tree_len = 0; }
-    if (!s || !(s->d_in || s->d_out || s->d_aux || s->d_f || s->h_fout || s->d_fo)) return;
+    if (s && s->f.pend) { free(s->f.pend); s->f.pend = nullptr; s->f.pend_len = s->f.pend_cap = 0; }
+    if (s && s->f.tree) { free(s->f.tree); s->f.tree = nullptr; s->f.tree_len = 0; }
+    if (!s || !(s->d_in || s->d_out || s->d_aux || s->f.d_f || s->f.h_out || s->f.d_fo)) return;
     if (hipSetDevice(s->device) != hipSuccess) return;
-    if (s->h_fout) { (void)hipHostFree(s->h_fout); s->h_fout = nullptr; }
-    dfree(&s->d_f, &s->f_cap); dfree(&s->d_fo, &s->fo_cap);
+    if (s->f.h_out) { (void)hipHostFree(s->f.h_out); s->f.h_out = nullptr; }
+    dfree(&s->f.d_f, &s->f.f_cap); dfree(&s->f.d_fo, &s->f.fo_cap);
     // (every step ends with a synchronisation of the stream it ran on, so nothing is in flight on these buffers: no device-wide wait —
     // hipFree itself orders the release behind outstanding work)
     dfree(&s->d_in, &s->in_cap); dfree(&s->d_out, &s->out_cap); dfree(&s->d_aux, &s->aux_cap);
+}
+
+// The state of the entry being read, cleared in one place.  A replay (the entry's bytes once more through the windowless step, after
+// ZPK_DS_RESTART) keeps what the caller already has of the entry — f.delivered, the count of calls — and leaves the bounded steps
+// (fast = -1); a reset drops those too and leaves the route undecided.  Every buffer stays either way.
+static void dstream_clear(zpk_dstream* s, bool replay)
+{
+    const u64 delivered = replay ? s->f.delivered : 0;
+    s->in_len = 0; s->avail = 0; s->out_pos = 0; s->complete = 0; s->status = 0; s->h_len = 0; s->launches = 0;
+    if (!replay) s->calls = 0;
+    static_cast<DsFastEntry&>(s->f) = DsFastEntry();
+    s->f.delivered = delivered;
+    s->fast = replay ? -1 : 0;
 }
 
 // the codec the NEXT step decodes with (a stream may outlive codecs): device memory belongs to a device — moving on releases it
@@ -202,17 +218,15 @@ void zpk_dstream_bind(zpk_dstream* s, zpk_codec* c)
 void zpk_dstream_reset(zpk_dstream* s)
 {
     if (!s) return;
-    s->in_len = 0; s->avail = 0; s->out_pos = 0; s->complete = 0; s->status = 0; s->h_len = 0; s->launches = 0; s->calls = 0;
-    s->f_tree_len = 0; s->f_last = 0; s->f_window = 0; s->f_fcs = 0;
-    s->fast = 0; s->f_pend_len = 0; s->f_in_total = 0; s->f_hdr = 0; s->f_T = s->f_hist = s->f_ghashed = 0; s->f_avail = s->f_given = s->f_delivered = 0; s->f_steps = 0;
+    dstream_clear(s, false);
     // a stream that has carried a large entry gives the device memory back between entries
-    if (s->in_cap + s->out_cap + s->f_cap + s->fo_cap > (64ull << 20)) dstream_release(s);
+    if (s->in_cap + s->out_cap + s->f.f_cap + s->f.fo_cap > (64ull << 20)) dstream_release(s);
 }
 
 void zpk_dstream_destroy(zpk_dstream* s) { if (s) { dstream_release(s); free(s); } }
 
 // diagnostics: bytes of device memory the stream holds right now
-uint64_t zpk_dstream_device_bytes(const zpk_dstream* s) { return s ? s->in_cap + s->out_cap + s->aux_cap + s->f_cap + s->fo_cap : 0; }
+uint64_t zpk_dstream_device_bytes(const zpk_dstream* s) { return s ? s->in_cap + s->out_cap + s->aux_cap + s->f.f_cap + s->f.fo_cap : 0; }
 
 // diagnostics: decode steps launched / calls served since the last reset
 void zpk_dstream_counters(const zpk_dstream* s, uint64_t* launches, uint64_t* calls)
@@ -233,241 +247,265 @@ void zpk_dstream_counters(const zpk_dstream* s, uint64_t* launches, uint64_t* ca
 // (zpk_dstream_wants_input).  ANYTHING else — another header flavour, a second frame, a skippable frame, a damaged or truncated
 // block, sizes that disagree — is not decided here: the step answers ZPK_DS_RESTART, the caller feeds the entry's bytes so far again
 // (zpk_dstream_replay) and the stream goes on above, where the verdicts are; the bytes handed out so far are not handed out again.
-#define ZPK_DS_FAST_MIN (1ull << 20)
-#ifndef ZPK_DS_RESTART
-#define ZPK_DS_RESTART 1001
-#endif
-#define F_BLOCKS 64u
-#define F_HIST (128u << 10)
-#define F_OUT (F_BLOCKS * PJ_BLOCK)
-#define F_IN (F_BLOCKS * (PJ_BLOCK + 4u) + 256u)
-#define F_HOST_OUT (8ull << 20)                    // the pinned buffer a step's output comes home in (the larger of the two step sizes)
-struct FastLayout { u64 in, out, tmp, S, recs, masks, blocks, flags, part, span, hash, state, rec, size; };
-static FastLayout dstream_fast_layout()
-{
-    FastLayout L; u64 o = 0;
-    auto take = [&](u64 n) { const u64 at = o; o += (n + 255) & ~255ull; return at; };
-    L.in = take(F_IN + ZPK_SRC_SLACK); L.out = take(F_HIST + F_OUT + 64); L.tmp = take(F_HIST); L.S = take(((u64)F_HIST + F_OUT) * 4 + 64);
-    L.recs = take((u64)F_BLOCKS * (PJ_BLOCK / 3 + 2 + 8) * 8); L.masks = take((u64)F_BLOCKS * (PJ_BLOCK / 8)); L.blocks = take(F_BLOCKS * sizeof(PjBlock));
-    L.flags = take(256); L.part = take((((u64)F_HIST + F_OUT) / 65536 + 4) * 4096); L.span = take(sizeof(zpk_span)); L.hash = take(64); L.state = take(64);
-    L.rec = take(sizeof(zpk_stream_rec)); L.size = o;
-    return L;
-}
+//
+// A step (stream_plan.h has every rule that is not a launch): intake of the caller's bytes — header, once — the complete blocks among
+// the pending bytes — go / wait / RESTART — buffers (the first step allocates) — upload and the kernel pipeline up to the gather (what
+// the two codecs differ in) — the XXH3 so far — the output home and the history carry — ONE synchronisation — commit and hand-out.
+static_assert(sizeof(zpk_span) <= FS_SMALL && sizeof(zpk_stream_rec) <= FS_SMALL && sizeof(zpk_decode_desc) == FZ_DESC_BYTES && FS_SRC_SLACK == ZPK_SRC_SLACK,
+              "stream_plan.h lays the steps' device blocks out with these sizes");
+static_assert(F_FIRST_MIN == ZPK_PJ_MIN_BLOCKS && FZ_FIRST_MIN == ZPK_ZPJ_MIN_BLOCKS, "the first step's minimum is the block-parallel readers'");
 
 static int dstream_fast_deliver(zpk_dstream* s, uint8_t* out, size_t out_cap, size_t* produced, int* done)
 {
-    const u64 left = s->f_avail - s->f_given;
+    const u64 left = s->f.avail - s->f.given;
     const u64 give = out_cap < left ? out_cap : left;
-    if (give) memcpy(out, s->h_fout + s->f_given, give);
-    s->f_given += give; s->f_delivered += give; *produced = give;
-    if (s->complete && s->f_given == s->f_avail) { *done = 1; return s->status; }
+    if (give) memcpy(out, s->f.h_out + s->f.given, give);
+    s->f.given += give; s->f.delivered += give; *produced = give;
+    if (s->complete && s->f.given == s->f.avail) { *done = 1; return s->status; }
     return 0;
+}
+
+// The caller's bytes join the pending ones; a call that finds output waiting (or the entry complete) only hands out.
+// -> true: *rc is the call's answer; false: the step goes on
+static bool dstream_fast_intake(zpk_dstream* s, uint64_t comp_size, const uint8_t* in, size_t in_size, size_t* consumed,
+                                uint8_t* out, size_t out_cap, size_t* produced, int* done, int* rc)
+{
+    const StreamIntake it = stream_intake(comp_size, s->f.in_total, in_size);
+    if ((*rc = it.rc) != 0) return true;
+    *consumed = it.take;
+    if (it.take) {
+        const u64 cap = stream_pend_cap(s->f.pend_len, s->f.pend_cap, it.take);
+        if (cap != s->f.pend_cap) {
+            u8* nb = (u8*)realloc(s->f.pend, cap);
+            if (!nb) { *rc = 10; return true; }
+            s->f.pend = nb; s->f.pend_cap = cap;
+        }
+        memcpy(s->f.pend + s->f.pend_len, in, it.take);
+        s->f.pend_len += it.take; s->f.in_total += it.take;
+    }
+    s->calls++;
+    if (s->f.given < s->f.avail || s->complete) { *rc = dstream_fast_deliver(s, out, out_cap, produced, done); return true; }
+    return false;
+}
+
+// the frame header is parsed: its `hdr` bytes leave the pending ones
+static void dstream_fast_header_done(zpk_dstream* s, int hdr)
+{
+    s->f.hdr = hdr;
+    memmove(s->f.pend, s->f.pend + hdr, s->f.pend_len - (u64)hdr);
+    s->f.pend_len -= (u64)hdr;
+}
+
+// the device block `need` bytes large and the pinned output buffer: nothing of this entry lives there before its first step, which allocates
+static int dstream_fast_buffers(zpk_dstream* s, u8** dev, u64* cap, u64 need)
+{
+    if (*cap < need) {
+        if (s->f.T != 0) return ZPK_DS_RESTART;
+        dfree(dev, cap);
+        if (hipMalloc((void**)dev, need) != hipSuccess) { (void)hipGetLastError(); *dev = nullptr; return ZPK_DS_RESTART; }
+        *cap = need;
+    }
+    if (!s->f.h_out && hipHostMalloc((void**)&s->f.h_out, F_HOST_OUT, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s->f.h_out = nullptr; return ZPK_DS_RESTART; }
+    return 0;
+}
+
+// What the shared parts of a step work on, and the step's scope guard: the asynchronous copies of a step name host memory of the step —
+// hf, hh, span here, the block tables of its function — so from the first enqueue (arm) to the step's own synchronisation (sync) every
+// way out waits for the stream.  Declared BEHIND every local a copy names: it leaves first.  Costs nothing where a step succeeds.
+struct FastStep {
+    hipStream_t st; bool armed;
+    u8* d_out; u8* d_tmp; u64 hist_cap;          // the window [history | step output], the temporary of the carry, the history's capacity
+    u64* d_part; zpk_span* d_span; u64* d_hash; u64* d_state; zpk_stream_rec* rec; u32* flags;
+    zpk_span span; u64 hh; u32 hf[64];           // host ends of the step's small copies
+    explicit FastStep(hipStream_t stream) : st(stream), armed(false), hh(0) {}
+    FastStep(const FastStep&) = delete;
+    void arm() { armed = true; }
+    hipError_t sync() { armed = false; return hipStreamSynchronize(st); }
+    ~FastStep() { if (armed) (void)hipStreamSynchronize(st); }
+};
+
+// Pointer doubling over blocks [b0, b1) of nt: `look` rounds, then a look whether the last one still moved anything (LZ4 looks every
+// F_LOOK rounds, Zstandard every FZ_LOOK: launch counts and synchronisation points of the two steps as they were measured).
+// -> 0, 24, or ZPK_DS_RESTART (a damaged block; rounds that never settle)
+static int dstream_jump_rounds(FastStep& F, u32* S, const PjBlock* B, u32 b0, u32 b1, u32 nt, u32 jgrid, u32 look)
+{
+    for (u32 r0 = 0; r0 < PJ_MAX_ROUNDS; r0 += look) {
+        const u32 r1 = r0 + look < PJ_MAX_ROUNDS ? r0 + look : PJ_MAX_ROUNDS;
+        for (u32 r = r0; r < r1; r++) hipLaunchKernelGGL(k_pj_jump, dim3(jgrid), dim3(256), 0, F.st, S, B, b0, b1, nt, F.flags, r);
+        hipError_t e = hipMemcpyAsync(F.hf, F.flags, (PJ_ROUND0 + PJ_MAX_ROUNDS) * 4, hipMemcpyDeviceToHost, F.st);
+        if (e == hipSuccess) e = hipStreamSynchronize(F.st);
+        if (e != hipSuccess) return 24;
+        if (F.hf[PJ_ERR]) return ZPK_DS_RESTART;
+        if (!F.hf[PJ_ROUND0 + r1 - 1]) break;
+        if (r1 == PJ_MAX_ROUNDS) return ZPK_DS_RESTART;
+    }
+    return 0;
+}
+
+// XXH3 of everything produced so far (stream_hash_plan): whole 64 KiB groups as they become final, the rest with the end; an entry that
+// ends in its first step is hashed in one launch.  With the end the hash is on its way to F.hh.
+static hipError_t dstream_hash_so_far(zpk_dstream* s, FastStep& F, u64 T_new, bool end)
+{
+    const StreamHash h = stream_hash_plan(s->f.T, s->f.hist, T_new, s->f.ghashed, end);
+    if (h.one_shot) {
+        hipLaunchKernelGGL(k_stream_hash, dim3(1), dim3(64), 0, F.st, (const u8*)F.d_out, T_new, F.rec);
+        return hipMemcpyAsync(&F.hh, &F.rec->hash, 8, hipMemcpyDeviceToHost, F.st);
+    }
+    if (h.chain) {
+        const u8* const virt = F.d_out - h.virt_back;                                    // position p of the output lies at virt + p
+        u64* const part_v = F.d_part - h.part_back;
+        F.span.off = 0; F.span.len = T_new; F.span.part_base = 0;
+        const hipError_t e = hipMemcpyAsync(F.d_span, &F.span, sizeof(F.span), hipMemcpyHostToDevice, F.st);
+        if (e != hipSuccess) return e;
+        if (h.partials)
+            hipLaunchKernelGGL(k_xxh3_partials, dim3((u32)((h.g_to - h.g_from + 3) / 4)), dim3(256), 0, F.st, virt, (const zpk_span*)F.d_span, 1u, h.g_from, h.g_to, part_v);
+        hipLaunchKernelGGL(k_xxh3_chain, dim3(1), dim3(64), 0, F.st, virt, (const zpk_span*)F.d_span, (const u64*)part_v, F.d_hash, F.d_state, h.b_from, h.b_to, h.last);
+        s->f.ghashed = h.ghashed_new;
+    }
+    return end ? hipMemcpyAsync(&F.hh, F.d_hash, 8, hipMemcpyDeviceToHost, F.st) : hipSuccess;
+}
+
+// The step's output home, `flag_bytes` of the flags with it; the last hist_cap bytes stay as the next step's history (stream_carry);
+// then the step's ONE synchronisation.  e: what the enqueues before have answered.  -> 0 or 24
+static int dstream_home_and_carry(zpk_dstream* s, zpk_codec* c, FastStep& F, hipError_t e, u64 step_out, bool end, u64 flag_bytes)
+{
+    if (e == hipSuccess && step_out) e = hipMemcpyAsync(s->f.h_out, F.d_out + s->f.hist, step_out, hipMemcpyDeviceToHost, F.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(F.hf, F.flags, flag_bytes, hipMemcpyDeviceToHost, F.st);
+    if (e == hipSuccess) {
+        const StreamCarry k = stream_carry(s->f.hist, step_out, F.hist_cap, end);
+        if (k.move) {
+            e = hipMemcpyAsync(F.d_tmp, F.d_out + k.from, k.keep, hipMemcpyDeviceToDevice, F.st);
+            if (e == hipSuccess) e = hipMemcpyAsync(F.d_out, F.d_tmp, k.keep, hipMemcpyDeviceToDevice, F.st);
+        }
+        s->f.hist = k.hist_new;
+    }
+    if (e == hipSuccess) e = F.sync();
+    if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "stream step: %s", hipGetErrorString(e)); return 24; }
+    return 0;
+}
+
+// the step is final: its `q` compressed bytes leave the pending ones, its output waits in the pinned buffer; the verdict with the end
+// (lib/zpack_read.c:631-637: it arrives with the last byte)
+static int dstream_commit_and_deliver(zpk_dstream* s, const FastStep& F, u64 T_new, u64 step_out, u64 q, bool end, uint64_t hash,
+                                      uint8_t* out, size_t out_cap, size_t* produced, int* done)
+{
+    s->f.T = T_new; s->f.avail = step_out; s->f.given = 0; s->launches++;
+    memmove(s->f.pend, s->f.pend + q, s->f.pend_len - q);
+    s->f.pend_len -= q;
+    if (end) { s->complete = 1; s->status = stream_verdict(F.hh, hash); }
+    return dstream_fast_deliver(s, out, out_cap, produced, done);
 }
 
 // -> a zpack_result, or ZPK_DS_RESTART
 static int dstream_fast_lz4(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, uint64_t uncomp_size, uint64_t hash,
                             const uint8_t* in, size_t in_size, size_t* consumed, uint8_t* out, size_t out_cap, size_t* produced, int* done)
 {
-    if (comp_size < s->f_in_total) return 21;
-    if (comp_size > ZPK_STREAM_MAX_BYTES) return 10; /* ZPACK_ERROR_MALLOC_FAILED: as the windowless path answers a size no device holds */
-    // ---- the caller's bytes (never more than the entry still has) ----
-    const u64 want = comp_size - s->f_in_total;
-    const u64 take = in_size < want ? in_size : want;
-    *consumed = take;
-    if (take) {
-        if (s->f_pend_len + take > s->f_pend_cap) {
-            const u64 cap = s->f_pend_len + take + (1u << 20);
-            u8* nb = (u8*)realloc(s->f_pend, cap);
-            if (!nb) return 10;
-            s->f_pend = nb; s->f_pend_cap = cap;
-        }
-        memcpy(s->f_pend + s->f_pend_len, in, take);
-        s->f_pend_len += take; s->f_in_total += take;
-    }
-    s->calls++;
-    if (s->f_given < s->f_avail || s->complete) return dstream_fast_deliver(s, out, out_cap, produced, done);
-    const bool all_in = s->f_in_total == comp_size;
-    const u8* const P = s->f_pend;
+    int rc = 0;
+    if (dstream_fast_intake(s, comp_size, in, in_size, consumed, out, out_cap, produced, done, &rc)) return rc;
+    const bool all_in = s->f.in_total == comp_size;
+    const u8* const P = s->f.pend;
     // ---- the frame header, once ----
-    if (!s->f_hdr) {
-        const int hdr = lz4_single_header(P, s->f_pend_len, &s->f_indep, &s->f_has_cs, &s->f_content);
+    if (!s->f.hdr) {
+        const int hdr = lz4_single_header(P, s->f.pend_len, &s->f.indep, &s->f.has_cs, &s->f.content);
         if (hdr < 0 || (hdr == 0 && all_in)) return ZPK_DS_RESTART;
         if (hdr == 0) return 0;
-        s->f_hdr = hdr;
-        memmove(s->f_pend, s->f_pend + hdr, s->f_pend_len - (u64)hdr);
-        s->f_pend_len -= (u64)hdr;
+        dstream_fast_header_done(s, hdr);
     }
     // ---- the complete blocks among the pending bytes ----
     PjBlock tab[F_BLOCKS];
     u64 q = 0; bool end = false;
-    const int found = lz4_stream_blocks(P, s->f_pend_len, tab, F_BLOCKS, &q, &end);
+    const int found = lz4_stream_blocks(P, s->f.pend_len, tab, F_BLOCKS, &q, &end);
     if (found < 0) return ZPK_DS_RESTART;
     const u32 nb = (u32)found;
-    if (end && !(all_in && q == s->f_pend_len)) return ZPK_DS_RESTART;                   // something follows the EndMark: not one frame
-    const bool go = end || nb == F_BLOCKS || (s->f_T == 0 && nb >= 4);
-    if (!go) {
-        if (all_in) return ZPK_DS_RESTART;                                               // the entry ends inside a frame: the verdict is not ours
-        return 0;
-    }
+    const StreamGo go = stream_go(end, nb, F_BLOCKS, F_FIRST_MIN, s->f.T, all_in, q == s->f.pend_len);
+    if (go != STREAM_RUN) return go == STREAM_RESTART ? ZPK_DS_RESTART : 0;
     // ---- one step ----
     if (hipSetDevice(c->device) != hipSuccess) return 24;
     const FastLayout L = dstream_fast_layout();
-    if (s->f_cap < L.size) {                                                             // (nothing of this entry lives there yet: the first step allocates)
-        if (s->f_T != 0) return ZPK_DS_RESTART;
-        dfree(&s->d_f, &s->f_cap);
-        if (hipMalloc((void**)&s->d_f, L.size) != hipSuccess) { (void)hipGetLastError(); s->d_f = nullptr; return ZPK_DS_RESTART; }
-        s->f_cap = L.size;
-    }
-    if (!s->h_fout && hipHostMalloc((void**)&s->h_fout, F_HOST_OUT, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s->h_fout = nullptr; return ZPK_DS_RESTART; }
-    hipStream_t st = c->stream;
-    u8* const d_in = s->d_f + L.in; u8* const d_out = s->d_f + L.out; u32* const S = (u32*)(s->d_f + L.S); u32* const flags = (u32*)(s->d_f + L.flags);
-    PjBlock* const B = (PjBlock*)(s->d_f + L.blocks);
+    if ((rc = dstream_fast_buffers(s, &s->f.d_f, &s->f.f_cap, L.size)) != 0) return rc;
+    u8* const d_f = s->f.d_f;
+    u8* const d_in = d_f + L.in; u32* const S = (u32*)(d_f + L.S); PjBlock* const B = (PjBlock*)(d_f + L.blocks);
+    FastStep F(c->stream);
+    F.d_out = d_f + L.out; F.d_tmp = d_f + L.tmp; F.hist_cap = F_HIST; F.d_part = (u64*)(d_f + L.part); F.d_span = (zpk_span*)(d_f + L.span);
+    F.d_hash = (u64*)(d_f + L.hash); F.d_state = (u64*)(d_f + L.state); F.rec = (zpk_stream_rec*)(d_f + L.rec); F.flags = (u32*)(d_f + L.flags);
+    hipStream_t st = F.st;
     u64 step_out = 0;
-    u32 hf[PJ_ROUND0 + PJ_MAX_ROUNDS];
     hipError_t e = hipSuccess;
     if (nb) {
+        F.arm();
         e = hipMemcpyAsync(d_in, P, q, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(B, tab, nb * sizeof(PjBlock), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 256, st);
+        if (e == hipSuccess) e = hipMemsetAsync(F.flags, 0, 256, st);
         if (e != hipSuccess) return 24;
-        hipLaunchKernelGGL(k_pj_parse, dim3(nb), dim3(64), 0, st, (const u8*)d_in, q, B, nb, (u64*)(s->d_f + L.recs), (u32*)(s->d_f + L.masks), flags);
-        hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, nb, flags, (u32)s->f_hist);
-        e = hipMemcpyAsync(hf, flags, 16, hipMemcpyDeviceToHost, st);
+        hipLaunchKernelGGL(k_pj_parse, dim3(nb), dim3(64), 0, st, (const u8*)d_in, q, B, nb, (u64*)(d_f + L.recs), (u32*)(d_f + L.masks), F.flags);
+        hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, nb, F.flags, (u32)s->f.hist);
+        e = hipMemcpyAsync(F.hf, F.flags, 16, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return 24;
-        const u64 total = ((u64)hf[PJ_TOTAL + 1] << 32) | hf[PJ_TOTAL];
-        if (hf[PJ_ERR] || total < s->f_hist || total - s->f_hist > F_OUT) return ZPK_DS_RESTART;
-        step_out = total - s->f_hist;
-        if (s->f_T + step_out > uncomp_size) return ZPK_DS_RESTART;                      // more than the entry may hold: BUFFER_TOO_SMALL is not ours to say
-        hipLaunchKernelGGL(k_pj_init, dim3(nb), dim3(256), 0, st, (const PjBlock*)B, 0u, nb, (const u64*)(s->d_f + L.recs), (const u32*)(s->d_f + L.masks), S, total, flags, s->f_indep);
+        const u64 total = ((u64)F.hf[PJ_TOTAL + 1] << 32) | F.hf[PJ_TOTAL];
+        if (F.hf[PJ_ERR] || total < s->f.hist || total - s->f.hist > F_OUT) return ZPK_DS_RESTART;
+        step_out = total - s->f.hist;
+        if (s->f.T + step_out > uncomp_size) return ZPK_DS_RESTART;                      // more than the entry may hold: BUFFER_TOO_SMALL is not ours to say
+        hipLaunchKernelGGL(k_pj_init, dim3(nb), dim3(256), 0, st, (const PjBlock*)B, 0u, nb, (const u64*)(d_f + L.recs), (const u32*)(d_f + L.masks), S, total, F.flags, s->f.indep);
         if (step_out) {
-            const u32 jgrid = (u32)((step_out + 1023) / 1024), ggrid = (u32)((total - (s->f_hist & ~3ull) + 1023) / 1024);
-            for (u32 r0 = 0; r0 < PJ_MAX_ROUNDS; r0 += 12) {                             // twelve rounds, then a look whether the last one still moved anything
-                const u32 r1 = r0 + 12 < PJ_MAX_ROUNDS ? r0 + 12 : PJ_MAX_ROUNDS;
-                for (u32 r = r0; r < r1; r++) hipLaunchKernelGGL(k_pj_jump, dim3(jgrid), dim3(256), 0, st, S, (const PjBlock*)B, 0u, nb, nb, flags, r);
-                e = hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, st);
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-                if (e != hipSuccess) return 24;
-                if (hf[PJ_ERR]) return ZPK_DS_RESTART;
-                if (!hf[PJ_ROUND0 + r1 - 1]) break;
-                if (r1 == PJ_MAX_ROUNDS) return ZPK_DS_RESTART;
-            }
-            hipLaunchKernelGGL(k_pj_gather, dim3(ggrid), dim3(256), 0, st, (const u32*)S, (const PjBlock*)B, 0u, nb, nb, (const u8*)d_in, q, d_out, flags);
+            const u32 jgrid = (u32)((step_out + 1023) / 1024), ggrid = (u32)((total - (s->f.hist & ~3ull) + 1023) / 1024);
+            if ((rc = dstream_jump_rounds(F, S, B, 0u, nb, nb, jgrid, F_LOOK)) != 0) return rc;
+            hipLaunchKernelGGL(k_pj_gather, dim3(ggrid), dim3(256), 0, st, (const u32*)S, (const PjBlock*)B, 0u, nb, nb, (const u8*)d_in, q, F.d_out, F.flags);
         }
     }
-    const u64 T_new = s->f_T + step_out;
-    if (end && s->f_has_cs && s->f_content != T_new) return ZPK_DS_RESTART;
-    // ---- XXH3 of everything produced so far, in sections of whole 64 KiB groups; position p of the output lies at virt + p ----
-    const u8* const virt = d_out - (s->f_T - s->f_hist);
-    u64* const d_part = (u64*)(s->d_f + L.part);
-    zpk_span* const d_span = (zpk_span*)(s->d_f + L.span);
-    u64* const d_hash = (u64*)(s->d_f + L.hash); u64* const d_state = (u64*)(s->d_f + L.state);
-    zpk_stream_rec* const rec = (zpk_stream_rec*)(s->d_f + L.rec);
-    u64 hh[2] = {0, 0};
-    if (end && s->f_ghashed == 0 && s->f_T == 0) {
-        hipLaunchKernelGGL(k_stream_hash, dim3(1), dim3(64), 0, st, (const u8*)d_out, T_new, rec);
-        e = hipMemcpyAsync(&hh[0], &rec->hash, 8, hipMemcpyDeviceToHost, st);
-    } else {
-        const u64 nblk = T_new ? (T_new - 1) >> 10 : 0;
-        const u64 g_to = end ? (nblk + XS_GROUP - 1) / XS_GROUP : nblk / XS_GROUP;
-        zpk_span span; span.off = 0; span.len = T_new; span.part_base = 0;
-        if (g_to > s->f_ghashed || end) {
-            e = hipMemcpyAsync(d_span, &span, sizeof(span), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) return 24;
-            u64* const part_v = d_part - s->f_ghashed * (XS_GROUP * 8);
-            if (g_to > s->f_ghashed)
-                hipLaunchKernelGGL(k_xxh3_partials, dim3((u32)((g_to - s->f_ghashed + 3) / 4)), dim3(256), 0, st, virt, (const zpk_span*)d_span, 1u, s->f_ghashed, g_to, part_v);
-            hipLaunchKernelGGL(k_xxh3_chain, dim3(1), dim3(64), 0, st, virt, (const zpk_span*)d_span, (const u64*)part_v, d_hash, d_state, s->f_ghashed * XS_GROUP, g_to * XS_GROUP, end ? 1 : 0);
-            if (!end) s->f_ghashed = g_to;
-        }
-        if (end) e = hipMemcpyAsync(&hh[0], d_hash, 8, hipMemcpyDeviceToHost, st);
-    }
-    // ---- the step's output home; the last 128 KiB stay as the next step's history ----
-    if (e == hipSuccess && step_out) e = hipMemcpyAsync(s->h_fout, d_out + s->f_hist, step_out, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(hf, flags, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !end && step_out) {
-        const u64 have = s->f_hist + step_out, keep = have < F_HIST ? have : (u64)F_HIST;
-        if (have > keep) {
-            e = hipMemcpyAsync(s->d_f + L.tmp, d_out + (have - keep), keep, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_out, s->d_f + L.tmp, keep, hipMemcpyDeviceToDevice, st);
-        }
-        s->f_hist = keep;
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "stream step: %s", hipGetErrorString(e)); return 24; }
-    if (nb && hf[PJ_ERR]) return ZPK_DS_RESTART;                                         // (the history was moved: harmless, the replay starts over)
-    s->f_T = T_new; s->f_avail = step_out; s->f_given = 0; s->f_steps++; s->launches++;
-    memmove(s->f_pend, s->f_pend + q, s->f_pend_len - q);
-    s->f_pend_len -= q;
-    if (end) { s->complete = 1; s->status = hh[0] == hash ? 0 : 15; }                    // lib/zpack_read.c:631-637: the verdict arrives with the last byte
-    return dstream_fast_deliver(s, out, out_cap, produced, done);
+    const u64 T_new = s->f.T + step_out;
+    if (end && s->f.has_cs && s->f.content != T_new) return ZPK_DS_RESTART;
+    F.arm();
+    e = dstream_hash_so_far(s, F, T_new, end);
+    if ((rc = dstream_home_and_carry(s, c, F, e, step_out, end, 4)) != 0) return rc;
+    if (nb && F.hf[PJ_ERR]) return ZPK_DS_RESTART;                                       // (the history was moved: harmless, the replay starts over)
+    return dstream_commit_and_deliver(s, F, T_new, step_out, q, end, hash, out, out_cap, produced, done);
 }
 
 // The same for ONE plain Zstandard frame (ZSTD_compressCCtx: no checksum, no dictionary; a window of at most 8 MiB): steps of up to 64
 // blocks (zstd_pj.h: sequences and literals of all blocks side by side, then references / pointer doubling / gather in chunks of 16
 // blocks) behind the frame's window of output, which stays on the device as history.  From step to step travel: the window, the three
 // repeat offsets, the running XXH3 and — on the host — the last block whose literals carry a Huffman tree (Treeless blocks of later
-// steps read its description: it goes up again in front of the step's blocks).
-#define FZ_BLOCKS 64u
-#define FZ_CHUNK 16u
-#define FZ_OUT ((u64)FZ_BLOCKS * ZPJ_BLOCK)
-#define FZ_MAX_WLOG 23u
-static_assert(FZ_OUT <= F_HOST_OUT && F_OUT <= F_HOST_OUT, "a step's output fits the pinned buffer");
+// steps read its description: it goes up again in front of the step's blocks) and the table descriptions in force.
 static int dstream_fast_zstd(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, uint64_t uncomp_size, uint64_t hash,
                              const uint8_t* in, size_t in_size, size_t* consumed, uint8_t* out, size_t out_cap, size_t* produced, int* done)
 {
-    if (comp_size < s->f_in_total) return 21;
-    if (comp_size > ZPK_STREAM_MAX_BYTES) return 10;
-    const u64 want = comp_size - s->f_in_total;
-    const u64 take = in_size < want ? in_size : want;
-    *consumed = take;
-    if (take) {
-        if (s->f_pend_len + take > s->f_pend_cap) {
-            const u64 cap = s->f_pend_len + take + (1u << 20);
-            u8* nbuf = (u8*)realloc(s->f_pend, cap);
-            if (!nbuf) return 10;
-            s->f_pend = nbuf; s->f_pend_cap = cap;
-        }
-        memcpy(s->f_pend + s->f_pend_len, in, take);
-        s->f_pend_len += take; s->f_in_total += take;
-    }
-    s->calls++;
-    if (s->f_given < s->f_avail || s->complete) return dstream_fast_deliver(s, out, out_cap, produced, done);
-    const bool all_in = s->f_in_total == comp_size;
-    const u8* const P = s->f_pend;
-    if (!s->f_hdr) {
+    int rc = 0;
+    if (dstream_fast_intake(s, comp_size, in, in_size, consumed, out, out_cap, produced, done, &rc)) return rc;
+    const bool all_in = s->f.in_total == comp_size;
+    const u8* const P = s->f.pend;
+    // ---- the frame header, once ----
+    if (!s->f.hdr) {
         u64 window = 0, fcs = ~0ull;
-        const int hdr = zpj_parse_frame_header(P, s->f_pend_len, FZ_MAX_WLOG, &window, &fcs);
+        const int hdr = zpj_parse_frame_header(P, s->f.pend_len, FZ_MAX_WLOG, &window, &fcs);
         if (hdr < 0 || (hdr == 0 && all_in)) return ZPK_DS_RESTART;
         if (hdr == 0) return 0;
-        if (window > (1ull << FZ_MAX_WLOG) + (1ull << (FZ_MAX_WLOG - 3)) * 7) return ZPK_DS_RESTART;       // (a single-segment frame: its window is its content size)
-        s->f_window = window; s->f_fcs = fcs; s->f_hdr = hdr;
-        s->f_hist_cap = (window < F_HIST ? (u64)F_HIST : window + 255) & ~255ull;
-        s->f_reps[0] = 1; s->f_reps[1] = 4; s->f_reps[2] = 8; s->f_tree_len = 0; s->f_last = 0;
-        for (int k = 0; k < 3; k++) { s->f_tab_mode[k] = 3; s->f_tab_len[k] = 0; }
-        memmove(s->f_pend, s->f_pend + hdr, s->f_pend_len - (u64)hdr);
-        s->f_pend_len -= (u64)hdr;
+        if (!fz_window_ok(window)) return ZPK_DS_RESTART;
+        s->f.window = window; s->f.fcs = fcs; s->f.hist_cap = fz_hist_cap(window);
+        s->f.reps[0] = 1; s->f.reps[1] = 4; s->f.reps[2] = 8; s->f.tree_len = 0;
+        for (int k = 0; k < 3; k++) { s->f.tab_mode[k] = 3; s->f.tab_len[k] = 0; }
+        dstream_fast_header_done(s, hdr);
     }
     // ---- the complete blocks among the pending bytes; table entry 0 = the inherited tree block (if any) ----
     std::vector<ZpjBlock> tab;
-    const u32 tb = s->f_tree_len ? 1u : 0u;                    // table index of the step's first block
+    const u32 tb = s->f.tree_len ? 1u : 0u;                    // table index of the step's first block
     // the device copy of a step: [3 x FZ_TABDESC: the table descriptions earlier steps left in force][the tree block][the step's blocks]
     const u64 tree_at = 3ull * FZ_TABDESC;
-    const u64 in_base = tree_at + (s->f_tree_len ? (((u64)s->f_tree_len + 63) & ~63ull) : 0);
-    ZpjTabs tabs; for (int k = 0; k < 3; k++) { tabs.mode[k] = s->f_tab_mode[k]; tabs.off[k] = (u32)(k * FZ_TABDESC); }
+    const u64 in_base = tree_at + (s->f.tree_len ? (((u64)s->f.tree_len + 63) & ~63ull) : 0);
+    ZpjTabs tabs; for (int k = 0; k < 3; k++) { tabs.mode[k] = s->f.tab_mode[k]; tabs.off[k] = (u32)(k * FZ_TABDESC); }
     u64 q = 0, slots = 0, lit_total = 0;
-    u32 nb = 0, tree = s->f_tree_len ? 0u : ZPJ_NONE, new_tree = ZPJ_NONE;
+    u32 nb = 0, tree = s->f.tree_len ? 0u : ZPJ_NONE, new_tree = ZPJ_NONE;
     bool end = false;
     try {
-        if (s->f_tree_len) {
+        if (s->f.tree_len) {
             ZpjBlock T; u32 tl = 0; u64 tt = 0;
-            if (zpj_parse_block(s->f_tree, s->f_tree_len, tree_at, T, &tl, &tt) != 1 || T.type != 2 || T.lit_type != 2) return ZPK_DS_RESTART;
+            if (zpj_parse_block(s->f.tree, s->f.tree_len, tree_at, T, &tl, &tt) != 1 || T.type != 2 || T.lit_type != 2) return ZPK_DS_RESTART;
             T.type = ZPJ_TREE_ONLY; T.nseq = 0;
             tab.push_back(T);
         }
         while (nb < FZ_BLOCKS && !end) {
             ZpjBlock B; u32 last = 0; u64 total = 0;
-            const int pr = zpj_parse_block(P + q, s->f_pend_len - q, in_base + q, B, &last, &total, &tabs);
+            const int pr = zpj_parse_block(P + q, s->f.pend_len - q, in_base + q, B, &last, &total, &tabs);
             if (pr < 0) return ZPK_DS_RESTART;
             if (pr == 0) break;
             if (B.type == 2 && B.lit_type == 2) new_tree = nb;
@@ -477,41 +515,23 @@ static int dstream_fast_zstd(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, u
             if (last) end = true;
         }
     } catch (...) { return 10; }
-    if (end && !(all_in && q == s->f_pend_len)) return ZPK_DS_RESTART;                   // something follows the last block: not one frame
-    const bool go = end || nb == FZ_BLOCKS || (s->f_T == 0 && nb >= 2);
-    if (!go) return all_in ? ZPK_DS_RESTART : 0;
+    const StreamGo go = stream_go(end, nb, FZ_BLOCKS, FZ_FIRST_MIN, s->f.T, all_in, q == s->f.pend_len);
+    if (go != STREAM_RUN) return go == STREAM_RESTART ? ZPK_DS_RESTART : 0;
     // ---- one step ----
     if (hipSetDevice(c->device) != hipSuccess) return 24;
-    const u64 HC = s->f_hist_cap;
-    const u64 fo_need = HC + FZ_OUT + 64 + HC + 1024;
-    if (s->fo_cap < fo_need) {
-        if (s->f_T != 0) return ZPK_DS_RESTART;
-        dfree(&s->d_fo, &s->fo_cap);
-        if (hipMalloc((void**)&s->d_fo, fo_need) != hipSuccess) { (void)hipGetLastError(); s->d_fo = nullptr; return ZPK_DS_RESTART; }
-        s->fo_cap = fo_need;
-    }
-    if (!s->h_fout && hipHostMalloc((void**)&s->h_fout, F_HOST_OUT, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s->h_fout = nullptr; return ZPK_DS_RESTART; }
     const u32 nt = tb + nb;                                     // table entries
     const u64 in_len = in_base + q, arena_off = (in_len + 64 + 255) & ~255ull, src_total = arena_off + lit_total;
-    u64 o = 0;
-    auto carve = [&](u64 n) { const u64 at = o; o += (n + 255) & ~255ull; return at; };
-    const u64 o_in = carve(src_total + ZPK_SRC_SLACK), o_zb = carve((u64)nt * sizeof(ZpjBlock)), o_pb = carve((u64)nt * sizeof(PjBlock)),
-              o_desc = carve((u64)nt * sizeof(zpk_decode_desc)), o_list = carve((u64)nt * 4), o_state = carve((u64)nt * 4), o_rep = carve((u64)nt * 12),
-              o_recs = carve((slots + 64) * 8), o_pos = carve((slots + 64) * 8), o_masks = carve((u64)nt * (ZPJ_BLOCK / 8)),
-              o_S = carve((u64)FZ_CHUNK * ZPJ_BLOCK * 4 + 64), o_part = carve(((HC + FZ_OUT) / 65536 + 4) * 4096);
-    if (s->f_cap < o) {
-        dfree(&s->d_f, &s->f_cap);
-        const u64 want_cap = o + o / 4;
-        if (hipMalloc((void**)&s->d_f, want_cap) != hipSuccess) { (void)hipGetLastError(); s->d_f = nullptr; return ZPK_DS_RESTART; }
-        s->f_cap = want_cap;
+    const FzLayout L = dstream_fz_layout(nt, slots, src_total, s->f.hist_cap);
+    if ((rc = dstream_fast_buffers(s, &s->f.d_fo, &s->f.fo_cap, L.fo_need)) != 0) return rc;
+    if (s->f.f_cap < L.size) {                                  // the scratch holds nothing between steps: any step may grow it
+        dfree(&s->f.d_f, &s->f.f_cap);
+        const u64 want_cap = fz_scratch_alloc(L.size);
+        if (hipMalloc((void**)&s->f.d_f, want_cap) != hipSuccess) { (void)hipGetLastError(); s->f.d_f = nullptr; return ZPK_DS_RESTART; }
+        s->f.f_cap = want_cap;
     }
-    hipStream_t st = c->stream;
-    u8* const d_in = s->d_f + o_in; u8* const d_out = s->d_fo;
-    u8* const d_tmp = s->d_fo + HC + FZ_OUT + 64;
-    u8* const d_small = d_tmp + HC;                             // state 64 | hash 64 | span 64 | rec 256 | flags 256
-    u64* const d_state = (u64*)d_small; u64* const d_hash = (u64*)(d_small + 64); zpk_span* const d_span = (zpk_span*)(d_small + 128);
-    zpk_stream_rec* const rec = (zpk_stream_rec*)(d_small + 256); u32* const flags = (u32*)(d_small + 512);
-    ZpjBlock* const ZB = (ZpjBlock*)(s->d_f + o_zb); PjBlock* const B = (PjBlock*)(s->d_f + o_pb);
+    u8* const d_f = s->f.d_f; u8* const d_fo = s->f.d_fo;
+    u8* const d_in = d_f + L.in;
+    ZpjBlock* const ZB = (ZpjBlock*)(d_f + L.zb); PjBlock* const B = (PjBlock*)(d_f + L.pb);
     std::vector<zpk_decode_desc> items; std::vector<u32> list; std::vector<PjBlock> hb;
     try {
         items.assign(nt, zpk_decode_desc()); hb.assign(nt, PjBlock());
@@ -528,158 +548,105 @@ static int dstream_fast_zstd(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, u
     } catch (...) { return 10; }
     u32 hflags[64]; memset(hflags, 0, sizeof(hflags));
     hflags[ZPJ_CNT + C_ZSTD] = (u32)list.size();
-    hipError_t e = hipSuccess;
-    e = hipMemcpyAsync(d_in, s->f_tab_desc, 3 * FZ_TABDESC, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && s->f_tree_len) e = hipMemcpyAsync(d_in + tree_at, s->f_tree, s->f_tree_len, hipMemcpyHostToDevice, st);
+    FastStep F(c->stream);
+    F.d_out = d_fo + L.out; F.d_tmp = d_fo + L.tmp; F.hist_cap = s->f.hist_cap; F.d_part = (u64*)(d_f + L.part); F.d_span = (zpk_span*)(d_fo + L.p_span);
+    F.d_hash = (u64*)(d_fo + L.p_hash); F.d_state = (u64*)(d_fo + L.p_state); F.rec = (zpk_stream_rec*)(d_fo + L.p_rec); F.flags = (u32*)(d_fo + L.p_flags);
+    hipStream_t st = F.st;
+    u32* const flags = F.flags;
+    F.arm();
+    hipError_t e = hipMemcpyAsync(d_in, s->f.tab_desc, 3 * FZ_TABDESC, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && s->f.tree_len) e = hipMemcpyAsync(d_in + tree_at, s->f.tree, s->f.tree_len, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && q) e = hipMemcpyAsync(d_in + in_base, P, q, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(ZB, tab.data(), nt * sizeof(ZpjBlock), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(B, hb.data(), nt * sizeof(PjBlock), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_f + o_desc, items.data(), nt * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && !list.empty()) e = hipMemcpyAsync(s->d_f + o_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_f + o_state, 0, (o_recs - o_state), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_f + L.desc, items.data(), nt * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !list.empty()) e = hipMemcpyAsync(d_f + L.list, list.data(), list.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_f + L.state, 0, (L.recs - L.state), st);
     if (e == hipSuccess) e = hipMemcpyAsync(flags, hflags, sizeof(hflags), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return 24;
-    u32* const state = (u32*)(s->d_f + o_state); u32* const rep_out = (u32*)(s->d_f + o_rep);
+    u32* const state = (u32*)(d_f + L.state); u32* const rep_out = (u32*)(d_f + L.rep);
     if (!list.empty()) {
         const u32 rows = (u32)list.size();
         const u32 grid = (rows + ZF_ROWS - 1) / ZF_ROWS < ZF_GRID_MAX ? (rows + ZF_ROWS - 1) / ZF_ROWS : ZF_GRID_MAX;
-        hipLaunchKernelGGL(k_zstd_fse_blocks, dim3(grid), dim3(64), 0, st, (const u8*)d_in, (const zpk_decode_desc*)(s->d_f + o_desc), (const u32*)(s->d_f + o_list),
-                           flags + ZPJ_CNT, (u64*)(s->d_f + o_recs), state, rep_out, in_len);
+        hipLaunchKernelGGL(k_zstd_fse_blocks, dim3(grid), dim3(64), 0, st, (const u8*)d_in, (const zpk_decode_desc*)(d_f + L.desc), (const u32*)(d_f + L.list),
+                           flags + ZPJ_CNT, (u64*)(d_f + L.recs), state, rep_out, in_len);
     }
     hipLaunchKernelGGL(k_zpj_lit, dim3(nt), dim3(64), 0, st, d_in, src_total, arena_off, (const ZpjBlock*)ZB, nt, flags);
-    hipLaunchKernelGGL(k_zpj_reps, dim3(1), dim3(64), 0, st, ZB, nt, (const u32*)state, (const u32*)rep_out, flags, s->f_reps[0], s->f_reps[1], s->f_reps[2]);
-    hipLaunchKernelGGL(k_zpj_pos, dim3(nt), dim3(256), 0, st, (const ZpjBlock*)ZB, B, nt, (const u64*)(s->d_f + o_recs), (u64*)(s->d_f + o_pos), (u32*)(s->d_f + o_masks), flags);
-    hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, nt, flags, (u32)s->f_hist);
-    u32 hf[64];
-    e = hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, st);
+    hipLaunchKernelGGL(k_zpj_reps, dim3(1), dim3(64), 0, st, ZB, nt, (const u32*)state, (const u32*)rep_out, flags, s->f.reps[0], s->f.reps[1], s->f.reps[2]);
+    hipLaunchKernelGGL(k_zpj_pos, dim3(nt), dim3(256), 0, st, (const ZpjBlock*)ZB, B, nt, (const u64*)(d_f + L.recs), (u64*)(d_f + L.pos), (u32*)(d_f + L.masks), flags);
+    hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, nt, flags, (u32)s->f.hist);
+    e = hipMemcpyAsync(F.hf, flags, sizeof(F.hf), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), B, nt * sizeof(PjBlock), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return 24;
-    const u64 total = ((u64)hf[PJ_TOTAL + 1] << 32) | hf[PJ_TOTAL];
-    if (hf[PJ_ERR] || total < s->f_hist || total - s->f_hist > FZ_OUT) return ZPK_DS_RESTART;
-    const u64 step_out = total - s->f_hist;
-    if (s->f_T + step_out > uncomp_size) return ZPK_DS_RESTART;
+    const u64 total = ((u64)F.hf[PJ_TOTAL + 1] << 32) | F.hf[PJ_TOTAL];
+    if (F.hf[PJ_ERR] || total < s->f.hist || total - s->f.hist > FZ_OUT) return ZPK_DS_RESTART;
+    const u64 step_out = total - s->f.hist;
+    if (s->f.T + step_out > uncomp_size) return ZPK_DS_RESTART;
     // references, pointer doubling, gather: FZ_CHUNK blocks at a time (the references of a chunk are all the scratch this takes)
     for (u32 b0 = tb; b0 < nt; b0 += FZ_CHUNK) {
         const u32 b1 = b0 + FZ_CHUNK < nt ? b0 + FZ_CHUNK : nt;
         const u64 lo = hb[b0].out_off, hi = b1 < nt ? hb[b1].out_off : total;
         if (hi == lo) continue;
-        u32* const Sv = (u32*)(s->d_f + o_S) - lo;            // S[i] for the chunk's positions only
+        u32* const Sv = (u32*)(d_f + L.S) - lo;               // S[i] for the chunk's positions only
         e = hipMemsetAsync(flags + PJ_ROUND0, 0, PJ_MAX_ROUNDS * 4, st);
         if (e != hipSuccess) return 24;
-        hipLaunchKernelGGL(k_zpj_init, dim3(b1 - b0), dim3(256), 0, st, (const ZpjBlock*)ZB, (const PjBlock*)B, b0, nt, (const u64*)(s->d_f + o_recs), (const u64*)(s->d_f + o_pos),
-                           (const u32*)(s->d_f + o_masks), Sv, total, flags);
+        hipLaunchKernelGGL(k_zpj_init, dim3(b1 - b0), dim3(256), 0, st, (const ZpjBlock*)ZB, (const PjBlock*)B, b0, nt, (const u64*)(d_f + L.recs), (const u64*)(d_f + L.pos),
+                           (const u32*)(d_f + L.masks), Sv, total, flags);
         const u32 jgrid = (u32)((hi - lo + 1023) / 1024), ggrid = (u32)((hi - (lo & ~3ull) + 1023) / 1024);
-        for (u32 r0 = 0; r0 < PJ_MAX_ROUNDS; r0 += 14) {
-            const u32 r1 = r0 + 14 < PJ_MAX_ROUNDS ? r0 + 14 : PJ_MAX_ROUNDS;
-            for (u32 r = r0; r < r1; r++) hipLaunchKernelGGL(k_pj_jump, dim3(jgrid), dim3(256), 0, st, Sv, (const PjBlock*)B, b0, b1, nt, flags, r);
-            e = hipMemcpyAsync(hf, flags, (PJ_ROUND0 + PJ_MAX_ROUNDS) * 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return 24;
-            if (hf[PJ_ERR]) return ZPK_DS_RESTART;
-            if (!hf[PJ_ROUND0 + r1 - 1]) break;
-            if (r1 == PJ_MAX_ROUNDS) return ZPK_DS_RESTART;
-        }
-        hipLaunchKernelGGL(k_pj_gather, dim3(ggrid), dim3(256), 0, st, (const u32*)Sv, (const PjBlock*)B, b0, b1, nt, (const u8*)d_in, src_total, d_out, flags);
+        if ((rc = dstream_jump_rounds(F, Sv, B, b0, b1, nt, jgrid, FZ_LOOK)) != 0) return rc;
+        hipLaunchKernelGGL(k_pj_gather, dim3(ggrid), dim3(256), 0, st, (const u32*)Sv, (const PjBlock*)B, b0, b1, nt, (const u8*)d_in, src_total, F.d_out, flags);
     }
-    const u64 T_new = s->f_T + step_out;
-    if (end && s->f_fcs != ~0ull && s->f_fcs != T_new) return ZPK_DS_RESTART;
-    // ---- XXH3 so far (dstream_fast_lz4) ----
-    const u8* const virt = d_out - (s->f_T - s->f_hist);
-    u64* const d_part = (u64*)(s->d_f + o_part);
-    u64 hh[2] = {0, 0};
-    if (end && s->f_ghashed == 0 && s->f_T == 0) {
-        hipLaunchKernelGGL(k_stream_hash, dim3(1), dim3(64), 0, st, (const u8*)d_out, T_new, rec);
-        e = hipMemcpyAsync(&hh[0], &rec->hash, 8, hipMemcpyDeviceToHost, st);
-    } else {
-        const u64 nblk = T_new ? (T_new - 1) >> 10 : 0;
-        const u64 g_to = end ? (nblk + XS_GROUP - 1) / XS_GROUP : nblk / XS_GROUP;
-        zpk_span span; span.off = 0; span.len = T_new; span.part_base = 0;
-        if (g_to > s->f_ghashed || end) {
-            e = hipMemcpyAsync(d_span, &span, sizeof(span), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) return 24;
-            u64* const part_v = d_part - s->f_ghashed * (XS_GROUP * 8);
-            if (g_to > s->f_ghashed)
-                hipLaunchKernelGGL(k_xxh3_partials, dim3((u32)((g_to - s->f_ghashed + 3) / 4)), dim3(256), 0, st, virt, (const zpk_span*)d_span, 1u, s->f_ghashed, g_to, part_v);
-            hipLaunchKernelGGL(k_xxh3_chain, dim3(1), dim3(64), 0, st, virt, (const zpk_span*)d_span, (const u64*)part_v, d_hash, d_state, s->f_ghashed * XS_GROUP, g_to * XS_GROUP, end ? 1 : 0);
-            if (!end) s->f_ghashed = g_to;
-        }
-        if (end) e = hipMemcpyAsync(&hh[0], d_hash, 8, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess && step_out) e = hipMemcpyAsync(s->h_fout, d_out + s->f_hist, step_out, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(hf, flags, 64 * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !end && step_out) {
-        const u64 have = s->f_hist + step_out, keep = have < HC ? have : HC;
-        if (have > keep) {
-            e = hipMemcpyAsync(d_tmp, d_out + (have - keep), keep, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_out, d_tmp, keep, hipMemcpyDeviceToDevice, st);
-        }
-        s->f_hist = keep;
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "stream step: %s", hipGetErrorString(e)); return 24; }
-    if (hf[PJ_ERR]) return ZPK_DS_RESTART;
-    s->f_reps[0] = hf[ZPJ_REPS]; s->f_reps[1] = hf[ZPJ_REPS + 1]; s->f_reps[2] = hf[ZPJ_REPS + 2];
+    const u64 T_new = s->f.T + step_out;
+    if (end && s->f.fcs != ~0ull && s->f.fcs != T_new) return ZPK_DS_RESTART;
+    e = dstream_hash_so_far(s, F, T_new, end);
+    if ((rc = dstream_home_and_carry(s, c, F, e, step_out, end, sizeof(F.hf))) != 0) return rc;
+    if (F.hf[PJ_ERR]) return ZPK_DS_RESTART;
+    // ---- what travels on the host ----
+    s->f.reps[0] = F.hf[ZPJ_REPS]; s->f.reps[1] = F.hf[ZPJ_REPS + 1]; s->f.reps[2] = F.hf[ZPJ_REPS + 2];
     for (int k = 0; k < 3; k++) {                                // table descriptions this step put in force: kept for Repeat_Mode blocks to come
-        s->f_tab_mode[k] = tabs.mode[k];
+        s->f.tab_mode[k] = tabs.mode[k];
         if (tabs.mode[k] != 3 && tabs.off[k] >= in_base) {
             const u64 at = tabs.off[k] - in_base, n = q - at < FZ_TABDESC ? q - at : (u64)FZ_TABDESC;
-            memcpy(s->f_tab_desc[k], P + at, n); s->f_tab_len[k] = (u32)n;
+            memcpy(s->f.tab_desc[k], P + at, n); s->f.tab_len[k] = (u32)n;
         }
     }
     if (new_tree != ZPJ_NONE) {                                  // the step's last block with a tree: kept for the Treeless blocks to come
         const ZpjBlock& TB = tab[tb + new_tree];
         const u64 at = TB.hdr_off - in_base, len = 3ull + TB.size;
-        if (!s->f_tree && !(s->f_tree = (u8*)malloc(ZPJ_BLOCK + 64))) return 10;
-        memcpy(s->f_tree, P + at, len); s->f_tree_len = (u32)len;
+        if (!s->f.tree && !(s->f.tree = (u8*)malloc(ZPJ_BLOCK + 64))) return 10;
+        memcpy(s->f.tree, P + at, len); s->f.tree_len = (u32)len;
     }
-    s->f_T = T_new; s->f_avail = step_out; s->f_given = 0; s->f_steps++; s->launches++;
-    memmove(s->f_pend, s->f_pend + q, s->f_pend_len - q);
-    s->f_pend_len -= q;
-    if (end) { s->complete = 1; s->f_last = 1; s->status = hh[0] == hash ? 0 : 15; }
-    return dstream_fast_deliver(s, out, out_cap, produced, done);
+    return dstream_commit_and_deliver(s, F, T_new, step_out, q, end, hash, out, out_cap, produced, done);
 }
 
 // 1: the next step wants input; 0: it only has output to hand out (bounded memory: the reader pulls nothing meanwhile)
 int zpk_dstream_wants_input(const zpk_dstream* s)
 {
     if (!s || s->fast != 1) return 1;
-    return (s->f_given < s->f_avail || s->complete) ? 0 : 1;
+    return (s->f.given < s->f.avail || s->complete) ? 0 : 1;
 }
 
-// after ZPK_DS_RESTART: the entry's first bytes again (first = 1 with the first piece), through the windowless path, nothing handed out;
+// after ZPK_DS_RESTART: the entry's first bytes again (first = 1 with the first piece), through the windowless step, nothing handed out;
 // when all bytes the stream had taken are back the stream goes on where the caller is.  Returns a zpack_result (a verdict may come up here).
 int zpk_dstream_replay(zpk_dstream* s, uint32_t method, uint64_t comp_size, uint64_t uncomp_size, uint64_t hash, const uint8_t* in, size_t in_size, int first)
 {
     if (!s) return 21;
-    if (first) {
-        s->fast = -1;
-        s->in_len = 0; s->avail = 0; s->out_pos = 0; s->complete = 0; s->status = 0; s->h_len = 0; s->launches = 0;
-        s->f_pend_len = 0; s->f_avail = s->f_given = 0;
-    }
+    if (first) dstream_clear(s, true);
     size_t consumed = 0, produced = 0; int done = 0;
-    // what the caller already has is not handed out again (hand_out above skips f_delivered bytes; they are the same bytes: blocks the
+    // what the caller already has is not handed out again (dstream_hand_out skips f.delivered bytes; they are the same bytes: blocks the
     // bounded steps decoded are regular)
     return zpk_dstream_step(s, method, comp_size, uncomp_size, hash, in, in_size, &consumed, nullptr, 0, &produced, &done);
 }
 
-int zpk_dstream_step(zpk_dstream* s, uint32_t method, uint64_t comp_size, uint64_t uncomp_size, uint64_t hash,
-                     const uint8_t* in, size_t in_size, size_t* consumed, uint8_t* out, size_t out_cap, size_t* produced, int* done)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The windowless step: the caller's chunk joins the entry's bytes on the device (small ones are gathered on the host until a step is
+// worth a launch), one resumable decode step over everything that is there, the verdict once everything that can be known is known;
+// nothing to do once the entry is complete.
+// -> 0: go on to the hand-out; anything else is the call's answer
+static int dstream_windowless_step(zpk_dstream* s, zpk_codec* c, uint32_t method, uint64_t comp_size, uint64_t uncomp_size, uint64_t hash,
+                                   const uint8_t* in, size_t in_size, size_t* consumed)
 {
-    if (!s || !consumed || !produced || !done) return 21; /* ZPACK_ERROR_STREAM_INVALID */
-    *consumed = 0; *produced = 0; *done = 0;
-    zpk_codec* c = s->c;
-    if (!c) return 24;
-    if (method != ZPK_METHOD_NONE && method != ZPK_METHOD_ZSTD && method != ZPK_METHOD_LZ4) return 19; /* ZPACK_ERROR_COMP_METHOD_INVALID */
-    CodecLock lk(c);
-    if (hipSetDevice(c->device) != hipSuccess) return 24; /* ZPACK_ERROR_NOT_AVAILABLE: never a CPU fallback */
-    if (s->fast == 0) s->fast = ((method == ZPK_METHOD_LZ4 || method == ZPK_METHOD_ZSTD) && comp_size >= ZPK_DS_FAST_MIN && c->dec_split_min != ~0ull) ? 1 : -1;
-    if (s->fast == 1) {
-        const int frc = method == ZPK_METHOD_LZ4 ? dstream_fast_lz4(s, c, comp_size, uncomp_size, hash, in, in_size, consumed, out, out_cap, produced, done)
-                                                 : dstream_fast_zstd(s, c, comp_size, uncomp_size, hash, in, in_size, consumed, out, out_cap, produced, done);
-        if (frc == ZPK_DS_RESTART) { *consumed = 0; *produced = 0; *done = 0; }
-        return frc;
-    }
     const u64 aux_need = 256 + sizeof(ZstdResume) + ZSTD_LIT_SCRATCH;
     if (!s->complete) {
         // comp_size / uncomp_size come from the archive's CDR, unverified: every size below is derived from bytes that have actually
@@ -707,7 +674,7 @@ int zpk_dstream_step(zpk_dstream* s, uint32_t method, uint64_t comp_size, uint64
             if (!s->h_in && !(s->h_in = (u8*)malloc(2 * ZPK_DS_GATHER))) return 10;
             memcpy(s->h_in + s->h_len, in, take_all);                        // (h_len < ZPK_DS_GATHER here, take_all < ZPK_DS_GATHER: fits)
             s->h_len += take_all;
-            if (s->h_len < ZPK_DS_GATHER && !last_byte_here) goto hand_out;  // not worth a launch yet: the bytes are kept
+            if (s->h_len < ZPK_DS_GATHER && !last_byte_here) return 0;       // not worth a launch yet: the bytes are kept
             up = s->h_in; up_len = s->h_len;
         }
         const u64 take = up_len;
@@ -781,13 +748,17 @@ int zpk_dstream_step(zpk_dstream* s, uint32_t method, uint64_t comp_size, uint64
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) return 24;
             s->complete = 1;
-            s->status = h.hash == hash ? 0 : 15; /* ZPACK_ERROR_FILE_HASH_MISMATCH: with the last byte, the data stays */
+            s->status = stream_verdict(h.hash, hash); /* ZPACK_ERROR_FILE_HASH_MISMATCH: with the last byte, the data stays */
         }
     }
-hand_out:
-    // ---- whatever output exists beyond what the caller has ----
-    // (after a restart out of the bounded steps the caller already has f_delivered bytes: they are skipped as they come into being)
-    if (s->out_pos < s->f_delivered) s->out_pos = s->f_delivered < s->avail ? s->f_delivered : s->avail;
+    return 0;
+}
+
+// whatever output of the windowless step exists beyond what the caller has
+// (after a restart out of the bounded steps the caller already has f.delivered bytes: they are skipped as they come into being)
+static int dstream_hand_out(zpk_dstream* s, uint32_t method, uint8_t* out, size_t out_cap, size_t* produced, int* done)
+{
+    if (s->out_pos < s->f.delivered) s->out_pos = s->f.delivered < s->avail ? s->f.delivered : s->avail;
     const u8* const body = method == ZPK_METHOD_NONE ? s->d_in : s->d_out;
     const u64 left = s->avail - s->out_pos;
     const u64 give = out_cap < left ? out_cap : left;
@@ -797,6 +768,28 @@ hand_out:
     s->out_pos += give; *produced = give;
     if (s->complete && s->out_pos == s->avail) { *done = 1; return s->status; }   /* hash verdict arrives with the last byte */
     return 0;
+}
+
+int zpk_dstream_step(zpk_dstream* s, uint32_t method, uint64_t comp_size, uint64_t uncomp_size, uint64_t hash,
+                     const uint8_t* in, size_t in_size, size_t* consumed, uint8_t* out, size_t out_cap, size_t* produced, int* done)
+{
+    if (!s || !consumed || !produced || !done) return 21; /* ZPACK_ERROR_STREAM_INVALID */
+    *consumed = 0; *produced = 0; *done = 0;
+    zpk_codec* c = s->c;
+    if (!c) return 24;
+    if (method != ZPK_METHOD_NONE && method != ZPK_METHOD_ZSTD && method != ZPK_METHOD_LZ4) return 19; /* ZPACK_ERROR_COMP_METHOD_INVALID */
+    CodecLock lk(c);
+    if (hipSetDevice(c->device) != hipSuccess) return 24; /* ZPACK_ERROR_NOT_AVAILABLE: never a CPU fallback */
+    if (s->fast == 0) s->fast = ((method == ZPK_METHOD_LZ4 || method == ZPK_METHOD_ZSTD) && comp_size >= ZPK_DS_FAST_MIN && c->dec_split_min != ~0ull) ? 1 : -1;
+    if (s->fast == 1) {
+        const int frc = method == ZPK_METHOD_LZ4 ? dstream_fast_lz4(s, c, comp_size, uncomp_size, hash, in, in_size, consumed, out, out_cap, produced, done)
+                                                 : dstream_fast_zstd(s, c, comp_size, uncomp_size, hash, in, in_size, consumed, out, out_cap, produced, done);
+        if (frc == ZPK_DS_RESTART) { *consumed = 0; *produced = 0; *done = 0; }
+        return frc;
+    }
+    const int rc = dstream_windowless_step(s, c, method, comp_size, uncomp_size, hash, in, in_size, consumed);
+    if (rc) return rc;
+    return dstream_hand_out(s, method, out, out_cap, produced, done);
 }
 
 int zpk_cstream_create(zpk_codec* c, zpk_cstream** out)
