@@ -46,7 +46,10 @@ extern "C" {
                                         zpk_codec_encode_big_device, zpk_codec_encode_stats: large entries in device memory written in pieces.
                                         zpk_codec_decode_big_batch_device: a device-resident batch with large entries, their block headers walked on the device;
                                         decode_stats2 out[10], out[11], which read 0: entries walked there / those the walk accepted.
-                                        ZPK_OPT_STORED_SPAN_MIN, decode_stats2 out[12], out[13], which read 0: large stored entries in device memory copied chip-wide / their groups.) */
+                                        ZPK_OPT_STORED_SPAN_MIN, decode_stats2 out[12], out[13], which read 0: large stored entries in device memory copied chip-wide / their groups.
+                                        zpk_codec_decode_batch_host_dptr, zpk_codec_encode_batch_dsrc, zpk_codec_copy_spans_device, zpk_codec_pointer_device,
+                                        zpk_codec_packed_stride: the host-pointer paths with the PLAINTEXT in the caller's device memory, and the kernel that moves it;
+                                        decode_stats2 out[14], out[15], which read 0: sub-batches through the host path's pipeline / k_span_copy launches.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -185,7 +188,9 @@ int  zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_
  * 64 KiB; they are not part of out[0] of zpk_codec_decode_stats (no work list held them) nor of out[5] / out[6].
  * Not in this call: entries that are sequences of frames (round 4 archives) stay one wave per entry; the
  * block-parallel entries are not overlapped with one another or with the one-wave launch; zpk_codec_decode_big_device still walks on the
- * host; libzpack_amd.so and zpk-batch do not use it. */
+ * host; libzpack_amd.so and zpk-batch do not use it: this call wants the ARCHIVE in device memory, and a reader's image is host memory or a
+ * file.  What libzpack_amd.so does use for plaintext in device memory (zpack_amd.h: zpack_amd_read_files_device, _packed,
+ * zpack_amd_write_files_device) is zpk_codec_decode_batch_host_dptr / zpk_codec_encode_batch_dsrc below; zpk-batch uses neither. */
 int  zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                        uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results);
 
@@ -196,6 +201,34 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
                                 const zpk_decode_desc* desc, uint64_t n,
                                 uint8_t* const* dst_ptrs, zpk_decode_result* results);
 
+/* zpk_codec_decode_batch_host with DEVICE destinations: archive, desc and results are host memory, d_dst_ptrs is a HOST array of n DEVICE
+ * pointers on the codec's device (desc[i].dst_capacity bytes each); synchronous.  The routing is that call's — the sub-batches by
+ * ZPK_HOST_CHUNK_BYTES, the sparse-pick gather, the frame-parallel and block-parallel routes of large entries (a block-parallel entry is
+ * decoded straight into its pointer) — and so are results[i].  Where the host call copies a sub-batch's staging home and scatters it on
+ * the host, this one issues ONE launch of k_span_copy that moves every slot to its pointer: exactly the bytes the host call copies to
+ * dst_ptrs[i] — [0, produced) — and nothing outside [ptr, ptr + dst_capacity).  A sub-batch large enough for the three-stage pipeline keeps
+ * its pipelined upload; the third stage is then one k_span_copy per piece, behind the piece's decode, in place of the download.
+ * decode_stats2 out[14], out[15] (which read 0): sub-batches of the most recent host decode call that took the pipeline (either kind of
+ * destination) / the k_span_copy launches of the most recent call of this kind.
+ * POINTER CHECK, on the host before anything is enqueued: every [d_dst_ptrs[i], + dst_capacity) with dst_capacity > 0 must lie inside ONE
+ * allocation on the codec's device (hipMemGetAddressRange; the last range is remembered, so a batch into one buffer costs one query),
+ * else ZPK_E_INVALID and nothing has run — a wrong pointer is a return code, not a fault.
+ * The caller's earlier work on those buffers must have completed: the codec runs on its own stream. */
+int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
+                                     const zpk_decode_desc* desc, uint64_t n,
+                                     uint8_t* const* d_dst_ptrs, zpk_decode_result* results);
+
+/* ---- spans of device memory, copied by one kernel (k_span_copy) ----------------------------------
+ * rows[0, n) is HOST memory, consumed before the call returns; src and dst are DEVICE addresses on the codec's device, any alignment;
+ * spans must not overlap each other's destinations or their own source.  Every span goes through the pointer check above (source and
+ * destination; len 0 passes and copies nothing): ZPK_E_INVALID and nothing has run.  Asynchronous on `stream` (NULL = the codec's own). */
+typedef struct zpk_span_copy { uint64_t src, dst, len; } zpk_span_copy;
+int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_t n, void* stream);
+/* the HIP ordinal of the device whose memory `ptr` points into, -1 when it is not device memory (host memory, NULL, no device) */
+int zpk_codec_pointer_device(const void* ptr);
+/* what an entry of uncomp_size bytes takes of a packed device read (zpack_amd_read_files_device_packed): uncomp_size rounded up to 256 */
+uint64_t zpk_codec_packed_stride(uint64_t uncomp_size);
+
 /* ---- batch encode + hash ------------------------------------------------------------------ */
 size_t zpk_codec_compress_bound(uint32_t method, size_t src_size);
 int zpk_codec_encode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src_size,
@@ -203,6 +236,14 @@ int zpk_codec_encode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
                                   uint8_t* dst, uint64_t dst_size,
                                   zpk_encode_result* results, void* stream);
 int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs,
+                                const zpk_encode_desc* desc, uint64_t n,
+                                uint8_t* const* dst_ptrs, zpk_encode_result* results);
+/* zpk_codec_encode_batch_host with DEVICE sources: d_src_ptrs is a HOST array of n DEVICE pointers on the codec's device (desc[i].size
+ * bytes each), dst_ptrs and results stay host memory; synchronous.  The upload of the sources becomes ONE launch of k_span_copy that
+ * gathers them into the same staging — which provides the 16 bytes of source slack the encode kernels ask for; a caller's tensor cannot
+ * promise them — and everything behind it is the host call's code: dst_ptrs[i] and results[i] are byte for byte what that call gives
+ * for host copies of the same bytes.  The pointer check of zpk_codec_decode_batch_host_dptr, on [d_src_ptrs[i], + size). */
+int zpk_codec_encode_batch_dsrc(zpk_codec* c, const uint8_t* const* d_src_ptrs,
                                 const zpk_encode_desc* desc, uint64_t n,
                                 uint8_t* const* dst_ptrs, zpk_encode_result* results);
 
@@ -264,7 +305,9 @@ int zpk_codec_set_profiling(zpk_codec* c, int enabled);
  * of out[0]); out[9] = LZ4 entries whose header is not that of a plain frame: the classification sends them to k_lz4_general;
  * out[10], out[11] = entries of the most recent zpk_codec_decode_big_batch_device call walked on the device / those the walk accepted;
  * out[12], out[13] = stored entries the most recent zpk_codec_decode_big_batch_device / zpk_codec_decode_big_device call copied chip-wide
- * (ZPK_OPT_STORED_SPAN_MIN) / their groups of 64 KiB */
+ * (ZPK_OPT_STORED_SPAN_MIN) / their groups of 64 KiB;
+ * out[14] = sub-batches of the most recent zpk_codec_decode_batch_host / _dptr call that took the three-stage pipeline; out[15] = k_span_copy
+ * launches of the most recent zpk_codec_decode_batch_host_dptr call */
 int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16]);
 /* counters of the most recent decode batch (synchronises): out[0..2] = entries on the stored / zstd / lz4 work
  * lists, out[3] = Zstandard entries finished on pre-decoded sequences (two-stage path), out[4] = by the fused decoder,

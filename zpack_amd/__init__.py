@@ -63,6 +63,13 @@ def lib():
         L.zpk_codec_decode_batch_host.argtypes = [vp, u8p, u64, vp, u64, vp, vp]
         L.zpk_codec_encode_batch_device.argtypes = [vp, u8p, u64, vp, u64, u8p, u64, vp, vp]
         L.zpk_codec_encode_batch_host.argtypes = [vp, vp, vp, u64, vp, vp]
+        if hasattr(L, "zpk_codec_copy_spans_device"):         # (an A/B build from before the device-memory calls has none of them: using one raises)
+            L.zpk_codec_decode_batch_host_dptr.argtypes = [vp, u8p, u64, vp, u64, vp, vp]
+            L.zpk_codec_encode_batch_dsrc.argtypes = [vp, vp, vp, u64, vp, vp]
+            L.zpk_codec_copy_spans_device.argtypes = [vp, vp, u64, vp]
+            L.zpk_codec_pointer_device.argtypes = [vp]
+            L.zpk_codec_packed_stride.argtypes = [u64]
+            L.zpk_codec_packed_stride.restype = u64
         L.zpk_codec_pack_batch_device.argtypes = [vp, u8p, vp, vp, u64, u8p, u64, vp, u64, vp]
         L.zpk_codec_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
         L.zpk_codec_compress_bound.restype = C.c_size_t
@@ -214,7 +221,8 @@ class Codec:
                     zstd_arena_refused=bool(a[7] >> 31), retried_lz4=b[0], retried_zstd=b[1],
                     lz4_long_runs=b[3], lz4_handed_over=b[8], lz4_general=b[9],
                     frame_parallel_entries=b[5], frame_parallel_frames=b[6], zstd_blocks_flags=b[7],
-                    device_walked=b[10], device_walk_accepted=b[11], stored_span_entries=b[12], stored_span_groups=b[13])
+                    device_walked=b[10], device_walk_accepted=b[11], stored_span_entries=b[12], stored_span_groups=b[13],
+                    pipelined_sub_batches=b[14], span_copy_launches=b[15])
 
     def debug_fetch(self, what, offset, count, dtype):
         a = np.zeros(count, dtype=dtype)
@@ -246,6 +254,28 @@ class Codec:
         self._chk(self.L.zpk_codec_decode_batch_host(self.h, arc.ctypes.data, arc.size, desc.ctypes.data, n, ptrs,
                                                      res.ctypes.data), "zpk_codec_decode_batch_host")
         return res, [o[:int(d["dst_capacity"])] for o, d in zip(outs, desc)]
+
+    # ---- the plaintext in the caller's DEVICE memory (torch tensors; archive and tables host memory) ----
+    def decode_batch_host_dptr(self, archive, desc, dst_ptrs):
+        """decode_batch_host with device destinations: dst_ptrs[i] = device address of desc[i].dst_capacity bytes on this codec's device.
+        Returns the results; raises on ZPK_E_INVALID (a pointer the check turned down: nothing has run)."""
+        self._settle(None)
+        arc = np.ascontiguousarray(np.frombuffer(archive, dtype=np.uint8) if not isinstance(archive, np.ndarray) else archive)
+        desc = np.ascontiguousarray(desc, dtype=DECODE_DESC)
+        n = len(desc)
+        ptrs = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in dst_ptrs])
+        res = np.zeros(n, dtype=DECODE_RESULT)
+        self._chk(self.L.zpk_codec_decode_batch_host_dptr(self.h, arc.ctypes.data, arc.size, desc.ctypes.data, n, ptrs, res.ctypes.data),
+                  "zpk_codec_decode_batch_host_dptr")
+        return res
+
+    def copy_spans_device(self, rows, stream=None):
+        """rows: (n, 3) uint64 array of (src address, dst address, len): one k_span_copy launch, asynchronous on `stream` (None: the
+        codec's own; synchronise the device before reading the destinations)."""
+        self._settle(stream)
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 3)
+        self._chk(self.L.zpk_codec_copy_spans_device(self.h, rows.ctypes.data, len(rows), C.c_void_p(stream) if stream else None),
+                  "zpk_codec_copy_spans_device")
 
     def hash_host(self, data):
         a = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))

@@ -42,6 +42,10 @@
 #include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
 #include "stored_plan.h"                         // the large stored entries of a device-resident batch: which are taken, their span table, the verdict (plain C++, likewise)
 #include "stored_span.h"                         // k_stored_span: their copy fused with the XXH3 partial sums, across the chip
+#include "span_copy_plan.h"                      // plaintext in the caller's DEVICE memory: the row table, items and launches of k_span_copy, the staging slots, the pointer test (plain C++, likewise)
+// k_span_copy (span_copy.h) is compiled in a file of its own, span_copy.hip: this file's code object stays the one it was, kernel for
+// kernel at the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
+namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
 #include "stream_plan.h"                         // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
 
 using namespace zpk;
@@ -693,10 +697,15 @@ struct zpk_codec {
     u32 host_totals[N_COUNTERS] = {};
     int totals_valid = 0;
     char err[256] = {0};
-    DevBufBase* const bufs[25] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_bigwalk, &d_sspan,
+    // plaintext in the caller's device memory (span_copy_plan.h / span_copy.h): the row table of k_span_copy, pinned going up — the event
+    // says that the upload has run, the block is written again only behind it — and the allocation the pointer check saw last
+    DevBuf<u8> d_sc; PinBuf h_sc; hipEvent_t sc_ev = nullptr; bool sc_pending = false;
+    u64   sc_base = 0, sc_size = 0;
+    u32   pipe_last = 0, sc_last = 0;                // most recent host decode call: sub-batches that took the three-stage pipeline; k_span_copy launches
+    DevBufBase* const bufs[26] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_bigwalk, &d_sspan, &d_sc,
                                    &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
                                    &d_xpart, &d_zarena, &d_zstate };
-    PinBuf* const pins[5] = { &h_bigsrc, &h_bigwalk, &h_sspan, &h_bigenc[0], &h_bigenc[1] };
+    PinBuf* const pins[6] = { &h_bigsrc, &h_bigwalk, &h_sspan, &h_bigenc[0], &h_bigenc[1], &h_sc };
 };
 
 struct CodecLock {
@@ -782,6 +791,7 @@ void zpk_codec_destroy(zpk_codec* c)
     if (c->h_seen) (void)hipHostFree((void*)c->h_seen);
     for (PinBuf* b : c->pins) if (b->p) (void)hipHostFree(b->p);
     for (int k = 0; k < 2; k++) if (c->bigenc_ev[k]) (void)hipEventDestroy(c->bigenc_ev[k]);
+    if (c->sc_ev) (void)hipEventDestroy(c->sc_ev);
     for (SideStream* x : { &c->side, &c->left, &c->span }) {
         if (x->s) (void)hipStreamDestroy(x->s);
         if (x->fork) (void)hipEventDestroy(x->fork);
@@ -825,6 +835,53 @@ int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
 #define ZPK_DEV(x)
 #define ZPK_WD_ARG
 #endif
+
+// ---- plaintext in the caller's DEVICE memory (span_copy_plan.h, span_copy.h) -------------------------------------------------------------
+// The pointer check, on the host: [ptr, ptr + len) lies inside ONE allocation on the codec's device.  The last allocation seen is kept for
+// the duration of one call (span_check_begin forgets it: the caller may have freed the buffer since), so a batch into one buffer is one query.
+static void span_check_begin(zpk_codec* c) { c->sc_base = 0; c->sc_size = 0; }
+static bool span_ptr_ok(zpk_codec* c, const void* ptr, u64 len)
+{
+    if (len == 0) return true;
+    if (!ptr) return false;
+    if (c->sc_size && span_copy_in_range((u64)ptr, len, c->sc_base, c->sc_size)) return true;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }      // (host memory HIP has not seen)
+    if (at.type != hipMemoryTypeDevice || at.device != c->device) return false;
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
+    c->sc_base = (u64)base; c->sc_size = size;
+    return span_copy_in_range((u64)ptr, len, c->sc_base, c->sc_size);
+}
+
+// in[0, n) in ONE k_span_copy on `st` (a table past one grid: several, over the same table); returns when the table's upload and the
+// kernel are enqueued.  The pointers have been checked by the caller, or are the codec's own.
+static int span_copy_enqueue(zpk_codec* c, const zpk_span_copy* in, u64 n, hipStream_t st)
+{
+    u64 nz = 0;
+    for (u64 i = 0; i < n; i++) nz += in[i].len != 0;
+    if (nz == 0) return ZPK_OK;
+    if (nz > ZPK_SC_MAX_ROWS) return ZPK_E_INVALID;
+    if (c->sc_pending) { HIPCHK(c, hipEventSynchronize(c->sc_ev)); c->sc_pending = false; }             // the pinned block's last upload has run
+    if (!c->sc_ev && hipEventCreateWithFlags(&c->sc_ev, hipEventDisableTiming) != hipSuccess) { c->sc_ev = nullptr; (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "span copy: no event"); return ZPK_E_LAUNCH; }
+    if (!grow_pinned(c->h_sc, nz * sizeof(SpanCopyRow))) { snprintf(c->err, sizeof(c->err), "span copy: out of pinned memory"); return ZPK_E_NOMEM; }
+    int rc;
+    if ((rc = grow(c, c->d_sc, nz * sizeof(SpanCopyRow)))) return rc;
+    SpanCopyRow* const rows = (SpanCopyRow*)c->h_sc.p;
+    SpanCopyPlan p = { 0, 0 };
+    for (u64 i = 0; i < n; i++) (void)span_copy_emit(in[i].src, in[i].dst, in[i].len, rows, p);
+    HIPCHK(c, hipMemcpyAsync(c->d_sc, rows, p.nrows * sizeof(SpanCopyRow), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->sc_ev, st));
+    c->sc_pending = true;
+    const u64 nl = span_copy_launches(p.items);
+    for (u64 j = 0; j < nl; j++) {
+        const SpanCopyLaunch L = span_copy_launch(p.items, j);
+        span_copy_launch((const SpanCopyRow*)(const u8*)c->d_sc, (u32)p.nrows, L.item0, L.items, L.grid, st);
+        c->sc_last++;
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZPK_OK;
+}
 
 // XXH3-64 of `nspans` long spans of `base` (xxh3_span.h): enqueues the upload of the span list and the two kernels; the hashes stay on
 // the device, *d_hash_out says where (inside c->d_xpart, valid until the next call that hashes spans).  `h_spans` must stay as it is
@@ -1057,8 +1114,9 @@ int zpk_codec_decode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
 // hashes buffer[0, uncomp_size) all the same — the decoded bytes followed by whatever the CALLER'S buffer held.  The device slot holds
 // something else there (an earlier batch's output), so for these rare entries the caller's bytes are brought up behind the decoded
 // ones and the slot is hashed again: the verdict is the one the reference reaches on this caller's buffer.
+// (ddst: dst_ptrs are DEVICE pointers — zpk_codec_decode_batch_host_dptr — and the caller's bytes come over from there)
 static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, uint8_t* const* dst_ptrs,
-                                zpk_decode_result* results)
+                                zpk_decode_result* results, bool ddst = false)
 {
     for (u64 i = 0; i < n; i++) {
         zpk_decode_result& r = results[i];
@@ -1068,7 +1126,7 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
         if ((rc = grow(c, c->d_xpart, 64))) return rc;
         const u64 tail = desc[i].uncomp_size - r.produced;
         u64 meta[3] = { hd[i].dst_offset, desc[i].uncomp_size, 0 };
-        HIPCHK(c, hipMemcpyAsync(c->d_dst + hd[i].dst_offset + r.produced, dst_ptrs[i] + r.produced, tail, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_dst + hd[i].dst_offset + r.produced, dst_ptrs[i] + r.produced, tail, ddst ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_xpart, meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
         u64* m = (u64*)c->d_xpart;
         hipLaunchKernelGGL(k_hash, dim3(1), dim3(64), 0, c->stream, (const u8*)c->d_dst, (const u64*)m, (const u64*)(m + 1), (u64)1, m + 2);
@@ -1214,7 +1272,7 @@ static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t*
 #define ZPK_SRC_SLACK 192u
 #define ZPK_SRC_READ_SLACK 128u
 static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
-                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results)
+                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst = false)
 {
     int rc;
     if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
@@ -1239,7 +1297,14 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
         if (results[i].produced > desc[i].dst_capacity) results[i].produced = desc[i].dst_capacity;     // (cannot happen)
         produced_total += results[i].produced;
     }
-    if (n > 1 && produced_total && produced_total * 2 >= out_total) {
+    if (ddst) {
+        // DEVICE destinations: the same bytes — [slot, slot + produced) of every entry — by ONE launch of k_span_copy, no host in between
+        std::vector<zpk_span_copy> sp;
+        try { sp.reserve(n); } catch (...) { return ZPK_E_NOMEM; }
+        for (u64 i = 0; i < n; i++) if (results[i].produced) sp.push_back(zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], results[i].produced });
+        if ((rc = span_copy_enqueue(c, sp.data(), sp.size(), c->stream))) return rc;
+        e = hipStreamSynchronize(c->stream);
+    } else if (n > 1 && produced_total && produced_total * 2 >= out_total) {
         // dense: the slots come back in pieces of ZPK_PIN_CHUNK bytes through two PINNED staging buffers — piece j + 1 is on the bus
         // while piece j is scattered into the caller's (pageable) buffers.  (One hipMemcpy of everything into a fresh malloc, then
         // the scatter, ran at 6.7 GB/s: page faults + the driver's own staging of pageable memory.)
@@ -1250,7 +1315,7 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
             if (results[i].produced) e = hipMemcpy(dst_ptrs[i], c->d_dst + hd[i].dst_offset, results[i].produced, hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "D2H: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    return rehash_short_entries(c, hd, desc, n, dst_ptrs, results);
+    return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, ddst);
 }
 
 // ---- the same chunk as a three-stage pipeline (round 3) ------------------------------------------------------------------------
@@ -1270,7 +1335,7 @@ struct HostPiece { u64 e0, e1, clo, chi, olo, ohi; };
 
 static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
                                  const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results,
-                                 bool& taken)
+                                 bool& taken, bool ddst = false)
 {
     taken = false;
     const u64 min_entries = c->zstd_hint ? 12288 : 4096;
@@ -1308,6 +1373,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     for (int k = 0; k < 2 * np; k++)
         if (!c->pipe_ev[k] && hipEventCreateWithFlags(&c->pipe_ev[k], hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) { c->pipe_ev[k] = nullptr; return ZPK_OK; }
     taken = true;
+    c->pipe_last++;
     hipError_t e = hipMemcpyAsync(c->d_desc, hd, n * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     std::atomic<int> uploaded(0), launched(0);   // pieces whose upload / decode has been ENQUEUED with its event recorded (-1: failed)
@@ -1364,11 +1430,35 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         }
         return hipSuccess;
     };
+    if (ddst) {
+        // DEVICE destinations (zpk_codec_decode_batch_host_dptr): there is no download.  Piece by piece, as soon as its decode has run: the
+        // verdicts come home and ONE k_span_copy on the download stream moves the piece's slots to their pointers — [slot, slot + produced),
+        // the bytes the scatter below copies — while the upload and the decode of the pieces behind it go on.
+        std::vector<zpk_span_copy> sp;
+        for (int k = 0; k < np && rc == ZPK_OK && e == hipSuccess; k++) {
+            int l;
+            while ((l = launched.load()) >= 0 && l <= k) std::this_thread::yield();
+            if (l < 0) { e = hipErrorUnknown; break; }
+            const HostPiece& P = pc[k];
+            e = hipStreamWaitEvent(c->s_dn, c->pipe_ev[2 * k + 1], 0);
+            if (e == hipSuccess) e = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->s_dn);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->s_dn);
+            if (e != hipSuccess) break;
+            try {
+                sp.clear();
+                for (u64 i = P.e0; i < P.e1; i++) {
+                    const u64 p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
+                    if (p) sp.push_back(zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], p });
+                }
+            } catch (...) { rc = ZPK_E_NOMEM; break; }
+            rc = span_copy_enqueue(c, sp.data(), sp.size(), c->s_dn);
+        }
+    } else
     rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; },
                      [&](u64 i) { const u64 p = results[i].produced; return p > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : p; }, e, c->s_dn, pre);
     if (up_threaded) t_up.join();
     if (launch_threaded) t_launch.join();
-    if (rc == ZPK_OK && e == hipSuccess) e = pre(out_total + 1);       // (pieces with no output bytes: their results still come back)
+    if (!ddst && rc == ZPK_OK && e == hipSuccess) e = pre(out_total + 1);       // (pieces with no output bytes: their results still come back)
     if (rc == ZPK_OK && e == hipSuccess) e = hipStreamSynchronize(c->s_dn);
     if (launch_rc.load() != ZPK_OK) rc = launch_rc.load();
     else if (rc == ZPK_OK && e != hipSuccess) { snprintf(c->err, sizeof(c->err), "host decode pipeline: %s", hipGetErrorString(e)); rc = ZPK_E_LAUNCH; }
@@ -1379,7 +1469,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         for (int k = 0; k < np; k++) for (int w = 0; w < N_COUNTERS; w++) c->host_totals[w] += c->piece_counters[k][w];
         c->totals_valid = 1;
     }
-    if (rc == ZPK_OK) rc = rehash_short_entries(c, hd, desc, n, dst_ptrs, results);
+    if (rc == ZPK_OK) rc = rehash_short_entries(c, hd, desc, n, dst_ptrs, results, ddst);
     return rc;
 }
 
@@ -1612,7 +1702,7 @@ static int decode_big_zstd_single(zpk_codec* c, const BigSrc& src, const zpk_dec
 
 // the frames of entries [g0, g1) of `be` as one device batch; redo[k] = 1: entry k takes the serial path after all
 static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_desc* desc, const BigEntry* be, u64 g0, u64 g1,
-                            const std::vector<BigSub>& subs, uint8_t* const* dst_ptrs, zpk_decode_result* results, u8* redo)
+                            const std::vector<BigSub>& subs, uint8_t* const* dst_ptrs, zpk_decode_result* results, u8* redo, bool ddst = false)
 {
     const u64 ng = g1 - g0;
     u64 nsub = 0;
@@ -1674,6 +1764,13 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         results[E.idx] = dec_hash_verdict(d, h_hash[k]);
         c->big_last[0]++; c->big_last[1] += (u32)E.nsub;
     }
+    if (ddst) {                                                                        // DEVICE destinations: one launch of k_span_copy
+        std::vector<zpk_span_copy> sp;
+        for (u64 k = 0; k < ng; k++) if (!redo[g0 + k]) sp.push_back(zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], desc[be[g0 + k].idx].uncomp_size });
+        if ((rc = span_copy_enqueue(c, sp.data(), sp.size(), c->stream))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return ZPK_OK;
+    }
     std::vector<uint8_t*> optr(ng);
     for (u64 k = 0; k < ng; k++) optr[k] = dst_ptrs[be[g0 + k].idx];
     rc = d2h_scatter(c, c->d_dst, ot, ng, optr.data(), [&](u64 k) { return ooff[k]; }, [&](u64 k) { return redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size; }, e);
@@ -1712,10 +1809,10 @@ static int decode_big_single(zpk_codec* c, PjEntry& P, const zpk_decode_desc& d,
 }
 
 // the counts decode_stats2 reports of the most recent decode call: none yet
-static void begin_decode_call(zpk_codec* c) { c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0; }
+static void begin_decode_call(zpk_codec* c) { c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0; c->pipe_last = c->sc_last = 0; }
 
 static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                   uint8_t* const* dst_ptrs, zpk_decode_result* results)
+                                   uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst = false)
 {
     if (n == 0) return ZPK_OK;
     zpk_decode_desc* hd = (zpk_decode_desc*)malloc(n * sizeof(zpk_decode_desc));
@@ -1729,8 +1826,8 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
         while (first + cnt < n) {
             const zpk_decode_desc& d = desc[first + cnt];
             // stored entries copy exactly uncomp_size bytes (lib/zpack_read.c:366); the decoders may fill all of max_size
-            const u64 slot_bytes = d.method == ZPK_METHOD_NONE && d.uncomp_size < d.dst_capacity ? d.uncomp_size : d.dst_capacity;
-            const u64 slot = (slot_bytes + 255) & ~255ull;
+            const u64 slot_bytes = span_copy_read_slot_bytes(d.method == ZPK_METHOD_NONE, d.uncomp_size, d.dst_capacity);
+            const u64 slot = span_copy_read_slot(d.method == ZPK_METHOD_NONE, d.uncomp_size, d.dst_capacity);      // (span_copy_plan.h states the layout for both kinds of destination)
             if (cnt && (out_total + slot > ZPK_HOST_CHUNK_BYTES || cnt >= 0x7FFFFFF0ull)) break;
             hd[first + cnt] = d;
             hd[first + cnt].dst_offset = out_total;
@@ -1763,9 +1860,9 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
             image = gathered; image_size = total; lo = 0; hi = pos;
         }
         bool piped = false;
-        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, piped);
+        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, piped, ddst);
         if (rc == ZPK_OK && !piped)
-            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first);
+            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, ddst);
         first += cnt;
     }
     c->zstd_hint = -1; c->lz4_hint = -1;
@@ -1774,13 +1871,19 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
     return rc;
 }
 
-int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                uint8_t* const* dst_ptrs, zpk_decode_result* results)
+// zpk_codec_decode_batch_host and, ddst, zpk_codec_decode_batch_host_dptr: one routing, the destinations host or device memory
+static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                 uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst)
 {
     if (!c || (n && (!desc || !results || !dst_ptrs))) return ZPK_E_INVALID;
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
+    if (ddst) {                                                                       // the pointer check: before anything is enqueued
+        span_check_begin(c);
+        for (u64 i = 0; i < n; i++)
+            if (!span_ptr_ok(c, dst_ptrs[i], desc[i].dst_capacity)) { snprintf(c->err, sizeof(c->err), "destination %llu is not %llu bytes of one allocation on device %d", (unsigned long long)i, (unsigned long long)desc[i].dst_capacity, c->device); return ZPK_E_INVALID; }
+    }
     begin_decode_call(c);
     // ---- which entries are sequences of frames worth decoding frame-parallel ----
     std::vector<BigEntry> be;
@@ -1811,14 +1914,14 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
             }
         } catch (...) { be.clear(); subs.clear(); pj.clear(); }                       // out of host memory for the plan: the usual path
     }
-    if (be.empty() && pj.empty()) return decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results);
+    if (be.empty() && pj.empty()) return decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results, ddst);
     int rc = ZPK_OK;
     try {
         std::vector<u8> redo(be.size(), 0), is_big(n, 0);
         for (u64 g0 = 0; g0 < be.size() && rc == ZPK_OK; ) {                          // groups by the size of their output
             u64 g1 = g0, out = 0;
             while (g1 < be.size() && (g1 == g0 || out + desc[be[g1].idx].uncomp_size <= ZPK_HOST_CHUNK_BYTES)) { out += (desc[be[g1].idx].uncomp_size + 255) & ~255ull; g1++; }
-            rc = decode_big_group(c, archive, desc, be.data(), g0, g1, subs, dst_ptrs, results, redo.data());
+            rc = decode_big_group(c, archive, desc, be.data(), g0, g1, subs, dst_ptrs, results, redo.data(), ddst);
             g0 = g1;
         }
         // ---- everything else, and the entries a frame of which did not decode, through the usual path ----
@@ -1826,7 +1929,7 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
         pj_choose(desc, n, pj);
         for (u64 k = 0; k < pj.size() && rc == ZPK_OK; k++) {                         // one large frame at a time: each fills the chip
             u8 again = 1;
-            rc = decode_big_single(c, pj[k], desc[pj[k].idx], BigSrc{ archive, false }, BigDst{ dst_ptrs[pj[k].idx], false }, results[pj[k].idx], again);
+            rc = decode_big_single(c, pj[k], desc[pj[k].idx], BigSrc{ archive, false }, BigDst{ dst_ptrs[pj[k].idx], ddst }, results[pj[k].idx], again);
             if (rc == ZPK_OK && !again) is_big[pj[k].idx] = 1;
         }
         std::vector<u64> rest;
@@ -1836,13 +1939,48 @@ int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t a
             std::vector<uint8_t*> rp(rest.size());
             std::vector<zpk_decode_result> rr(rest.size());
             for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = dst_ptrs[rest[k]]; }
-            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data());
+            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), ddst);
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
     c->zstd_hint = -1; c->lz4_hint = -1;
     return rc;
 }
+
+int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                uint8_t* const* dst_ptrs, zpk_decode_result* results)
+{
+    return decode_batch_host_any(c, archive, archive_size, desc, n, dst_ptrs, results, false);
+}
+
+int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                     uint8_t* const* d_dst_ptrs, zpk_decode_result* results)
+{
+    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, true);
+}
+
+int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_t n, void* stream)
+{
+    if (!c || (n && !rows)) return ZPK_E_INVALID;
+    if (n == 0) return ZPK_OK;
+    CodecLock lk(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    span_check_begin(c);
+    for (u64 i = 0; i < n; i++)
+        if (!span_ptr_ok(c, (const void*)rows[i].src, rows[i].len) || !span_ptr_ok(c, (const void*)rows[i].dst, rows[i].len)) {
+            snprintf(c->err, sizeof(c->err), "span %llu does not lie inside one allocation on device %d", (unsigned long long)i, c->device); return ZPK_E_INVALID;
+        }
+    return span_copy_enqueue(c, rows, n, stream ? (hipStream_t)stream : c->stream);
+}
+
+int zpk_codec_pointer_device(const void* ptr)
+{
+    hipPointerAttribute_t at;
+    if (!ptr || hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return at.type == hipMemoryTypeDevice ? at.device : -1;
+}
+
+uint64_t zpk_codec_packed_stride(uint64_t uncomp_size) { return span_copy_packed_stride(uncomp_size); }
 
 // ---- large STORED entries of a device-resident call, copied and hashed by the whole chip (round 17; stored_plan.h, stored_span.h) ----
 // The entries of desc[0, n) that stored_span_takes, in one k_stored_span (the copy fused with the XXH3 partial sums, any number of spans),
@@ -2118,6 +2256,7 @@ int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16])
     out[9] = h[C_LZ4_GEN];                                 // LZ4 entries whose header is not that of a plain frame: k_lz4_general's
     out[10] = c->walk_last[0]; out[11] = c->walk_last[1];  // zpk_codec_decode_big_batch_device: entries walked on the device (k_big_walk), those the walk accepted
     out[12] = c->span_last[0]; out[13] = c->span_last[1];  // ... and zpk_codec_decode_big_device: stored entries copied chip-wide (k_stored_span), their groups
+    out[14] = c->pipe_last; out[15] = c->sc_last;          // zpk_codec_decode_batch_host / _dptr: sub-batches through the three-stage pipeline; k_span_copy launches (_dptr)
     return ZPK_OK;
 }
 

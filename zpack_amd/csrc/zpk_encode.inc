@@ -1589,13 +1589,19 @@ extern "C" {
 // Entries of at least c->enc_split_min bytes go to the device as 512 KiB pieces, one wave each, and come back as ONE frame (enc_plan.h: which
 // entries, their pieces, the frame's header and end, the entry's verdict); the packed stream keeps the pieces in order.  The entry's hash
 // is that of the whole plaintext (the two kernels of xxh3_span.h).
-int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, const zpk_encode_desc* desc, uint64_t n,
-                                uint8_t* const* dst_ptrs, zpk_encode_result* results)
+// (dsrc: zpk_codec_encode_batch_dsrc — src_ptrs are DEVICE pointers, gathered into the same staging by one launch of k_span_copy)
+static int encode_batch_host_any(zpk_codec* c, const uint8_t* const* src_ptrs, const zpk_encode_desc* desc, uint64_t n,
+                                 uint8_t* const* dst_ptrs, zpk_encode_result* results, bool dsrc)
 {
     if (!c || (n && (!desc || !results || !src_ptrs || !dst_ptrs))) return ZPK_E_INVALID;
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
+    if (dsrc) {                                                                       // the pointer check: before anything is enqueued
+        span_check_begin(c);
+        for (u64 i = 0; i < n; i++)
+            if (!span_ptr_ok(c, src_ptrs[i], desc[i].size)) { snprintf(c->err, sizeof(c->err), "source %llu is not %llu bytes of one allocation on device %d", (unsigned long long)i, (unsigned long long)desc[i].size, c->device); return ZPK_E_INVALID; }
+    }
     const u64 split_min = c->enc_split_min;
     u64 np = 0, nsplit = 0;
     for (u64 i = 0; i < n; i++) { np += enc_piece_count(split_min, desc[i]); nsplit += enc_is_split(split_min, desc[i]); }
@@ -1621,7 +1627,7 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
         const EncSpan sp = enc_emit_entry(split_min, desc[i], in_total, hd + k, out_total, max_cap);
         k += enc_piece_count(split_min, desc[i]);
         if (enc_is_split(split_min, desc[i])) { spans[ns++] = zpk_span{ sp.off, sp.len, part_blocks }; part_blocks += xxh3_span_blocks(sp.len); }
-        in_total += (desc[i].size + 255 + 16) & ~255ull;
+        in_total += span_copy_write_slot(desc[i].size);                               // (span_copy_plan.h states the layout for both kinds of source)
     }
     first[n] = k;
     int rc;
@@ -1631,7 +1637,14 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
     hipError_t e = hipSuccess;
     // the sources go up through the pinned staging buffers, gathered piece by piece (zpk_codec.hip, h2d_gather); a single large entry
     // goes as it is
-    if (n == 1) { if (desc[0].size) e = hipMemcpyAsync(c->d_src, src_ptrs[0], desc[0].size, hipMemcpyHostToDevice, c->stream); }
+    if (dsrc) {
+        // DEVICE sources: entry i to its place in the staging, hd[first[i]].src_offset, all of them by ONE launch of k_span_copy
+        std::vector<zpk_span_copy> sp;
+        try { sp.reserve(n); } catch (...) { return ZPK_E_NOMEM; }
+        for (u64 i = 0; i < n; i++) if (desc[i].size) sp.push_back(zpk_span_copy{ (u64)src_ptrs[i], (u64)(c->d_src + hd[first[i]].src_offset), desc[i].size });
+        if ((rc = span_copy_enqueue(c, sp.data(), sp.size(), c->stream))) return rc;
+    }
+    else if (n == 1) { if (desc[0].size) e = hipMemcpyAsync(c->d_src, src_ptrs[0], desc[0].size, hipMemcpyHostToDevice, c->stream); }
     else {
         const int grc = h2d_gather(c, c->d_src, in_total, n, src_ptrs, [&](u64 i) { return (u64)hd[first[i]].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, e, c->stream);
         if (grc) return grc;
@@ -1678,6 +1691,18 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, co
     }
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "encode: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     return ZPK_OK;
+}
+
+int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs, const zpk_encode_desc* desc, uint64_t n,
+                                uint8_t* const* dst_ptrs, zpk_encode_result* results)
+{
+    return encode_batch_host_any(c, src_ptrs, desc, n, dst_ptrs, results, false);
+}
+
+int zpk_codec_encode_batch_dsrc(zpk_codec* c, const uint8_t* const* d_src_ptrs, const zpk_encode_desc* desc, uint64_t n,
+                                uint8_t* const* dst_ptrs, zpk_encode_result* results)
+{
+    return encode_batch_host_any(c, d_src_ptrs, desc, n, dst_ptrs, results, true);
 }
 
 }  // extern "C"

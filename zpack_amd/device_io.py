@@ -1,0 +1,172 @@
+"""Archives read into and written from CUDA tensors: the plaintext stays in device memory, only compressed bytes cross the bus.
+
+A thin ctypes view of the three device-memory calls of libzpack_amd.so (include/zpack_amd.h: zpack_amd_read_files_device,
+zpack_amd_read_files_device_packed, zpack_amd_write_files_device), with torch for the memory.  There is no CPU fallback: without a HIP
+device the calls return ZPACK_ERROR_NOT_AVAILABLE and these functions raise.
+
+    tensors, statuses = read_files_device("weights.zpk")                  # every entry, in archive order
+    write_files_device("weights.zpk", {"layer0": t0, "layer1": t1}, method=METHOD_LZ4, level=0)
+
+The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
+are ZPACK_ERROR_NOT_AVAILABLE.
+"""
+import ctypes as C
+import os
+
+from . import ZPACK_SO, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4            # noqa: F401  (the methods are part of this module's interface)
+
+OK, BUFFER_TOO_SMALL, STREAM_INVALID, NOT_AVAILABLE = 0, 12, 21, 24     # enum zpack_result (include/zpack.h)
+
+
+class FileEntry(C.Structure):                # zpack_file_entry (include/zpack.h)
+    _fields_ = [("filename", C.c_char_p), ("offset", C.c_uint64), ("comp_size", C.c_uint64),
+                ("uncomp_size", C.c_uint64), ("hash", C.c_uint64), ("comp_method", C.c_uint8)]
+
+
+class Reader(C.Structure):                   # zpack_reader
+    _fields_ = [("version", C.c_uint16), ("file_entries", C.POINTER(FileEntry)), ("file_count", C.c_uint64),
+                ("comp_size", C.c_uint64), ("uncomp_size", C.c_uint64), ("file_size", C.c_size_t),
+                ("zstd_dctx", C.c_void_p), ("lz4f_dctx", C.c_void_p), ("last_return", C.c_size_t),
+                ("cdr_offset", C.c_uint64), ("eocdr_offset", C.c_uint64), ("buffer", C.c_void_p),
+                ("buffer_shared", C.c_uint8), ("file", C.c_void_p)]
+
+
+class CompressOptions(C.Structure):          # zpack_compress_options
+    _fields_ = [("method", C.c_int), ("level", C.c_int)]
+
+
+class File(C.Structure):                     # zpack_file; `buffer` is a DEVICE address here
+    _fields_ = [("filename", C.c_char_p), ("buffer", C.c_void_p), ("size", C.c_uint64),
+                ("options", C.POINTER(CompressOptions)), ("cctx", C.c_void_p)]
+
+
+class Writer(C.Structure):                   # zpack_writer
+    _fields_ = [("buffer", C.c_void_p), ("buffer_capacity", C.c_size_t), ("file", C.c_void_p), ("file_size", C.c_size_t),
+                ("write_offset", C.c_size_t), ("file_entries", C.POINTER(FileEntry)), ("fe_capacity", C.c_uint64),
+                ("file_count", C.c_uint64), ("zstd_cctx", C.c_void_p), ("lz4f_cctx", C.c_void_p),
+                ("last_return", C.c_size_t), ("cdr_offset", C.c_uint64), ("eocdr_offset", C.c_uint64)]
+
+
+assert C.sizeof(FileEntry) == 48 and C.sizeof(Reader) == 112 and C.sizeof(File) == 40 and C.sizeof(Writer) == 104
+
+_lib = None
+
+
+def lib():
+    """libzpack_amd.so with the prototypes this module uses; raises when the library is missing (there is no fallback)"""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(ZPACK_SO):
+            raise RuntimeError("%s is missing: run `python -m zpack_amd.build`; there is no CPU fallback" % ZPACK_SO)
+        import torch  # noqa: F401  (one HIP runtime per process: torch's comes up first, see zpack_amd.lib)
+        L = C.CDLL(ZPACK_SO)
+        R, W, vp, u64 = C.POINTER(Reader), C.POINTER(Writer), C.c_void_p, C.c_uint64
+        L.zpack_init_reader.argtypes = [R, C.c_char_p]
+        L.zpack_init_reader_memory.argtypes = [R, vp, C.c_size_t]
+        L.zpack_close_reader.argtypes = [R]
+        L.zpack_close_reader.restype = None
+        L.zpack_amd_read_files_device.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]
+        L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
+        L.zpack_init_writer.argtypes = [W, C.c_char_p]
+        L.zpack_init_writer_heap.argtypes = [W, C.c_size_t]
+        L.zpack_write_header.argtypes = [W]
+        L.zpack_write_data_header.argtypes = [W]
+        L.zpack_amd_write_files_device.argtypes = [W, C.POINTER(File), u64]
+        L.zpack_write_cdr.argtypes = [W]
+        L.zpack_write_eocdr.argtypes = [W]
+        L.zpack_close_writer.argtypes = [W]
+        L.zpack_close_writer.restype = None
+        _lib = L
+    return _lib
+
+
+def _settle(device):
+    """The library's codec runs on a stream of its own: what torch has enqueued for these tensors on its current stream — the fill that
+    made a source, the last use of a block the allocator hands out again — has to have finished (Codec._settle documents the same)."""
+    import torch
+    torch.cuda.current_stream(device).synchronize()
+
+
+def _check(rc, what):
+    if rc != OK:
+        raise RuntimeError("%s -> %d%s" % (what, rc, " (no usable HIP device, or tensors on a device outside ZPACK_AMD_DEVICES: there is no CPU fallback)"
+                                                 if rc == NOT_AVAILABLE else ""))
+
+
+def read_files_device(archive, names=None, device=0):
+    """`archive`: a path, or the archive's bytes.  `names`: the entries to read, in that order (None: all, in archive order).
+    Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
+    a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
+    import torch
+    L = lib()
+    r = Reader()
+    if isinstance(archive, (str, os.PathLike)):
+        _check(L.zpack_init_reader(C.byref(r), os.fsencode(archive)), "zpack_init_reader")
+    else:
+        raw = bytes(archive)
+        _check(L.zpack_init_reader_memory(C.byref(r), raw, len(raw)), "zpack_init_reader_memory")
+    try:
+        if names is None:
+            picks = list(range(r.file_count))
+        else:
+            first = {}
+            for i in range(r.file_count):
+                first.setdefault(r.file_entries[i].filename.decode(), i)
+            picks = [first[n] for n in names]                                       # KeyError: no such entry
+        n = len(picks)
+        sizes = [int(r.file_entries[i].uncomp_size) for i in picks]
+        starts, total = [], 0
+        for s in sizes:
+            starts.append(total)
+            total += (s + 255) & ~255
+        dev = torch.device("cuda", device)
+        backing = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        tensors = [backing[a:a + s] for a, s in zip(starts, sizes)]
+        ents = (C.POINTER(FileEntry) * max(n, 1))(*[C.pointer(r.file_entries[i]) for i in picks])
+        bufs = (C.c_void_p * max(n, 1))(*[t.data_ptr() if s else None for t, s in zip(tensors, sizes)])
+        caps = (C.c_size_t * max(n, 1))(*sizes)
+        res = (C.c_int * max(n, 1))()
+        _settle(dev)
+        _check(L.zpack_amd_read_files_device(C.byref(r), ents, n, bufs, caps, res, None), "zpack_amd_read_files_device")
+        return tensors, [int(res[i]) for i in range(n)]
+    finally:
+        L.zpack_close_reader(C.byref(r))
+
+
+def write_files_device(path, tensors, method=METHOD_LZ4, level=0):
+    """Writes the archive `path` with one entry per item of `tensors` ({name: CUDA tensor}, all on one device; any dtype: an entry is the
+    tensor's bytes in memory order).  path None: the archive is built on the heap and returned as bytes."""
+    L = lib()
+    items = list(tensors.items())
+    flat = [t.contiguous().reshape(-1).view(dtype=_u8()) for _, t in items]
+    for t in flat:
+        if not t.is_cuda:
+            raise ValueError("write_files_device takes CUDA tensors (zpack_write_files is the call for host memory)")
+    w = Writer()
+    _check(L.zpack_init_writer(C.byref(w), os.fsencode(path)) if path is not None else L.zpack_init_writer_heap(C.byref(w), 0), "zpack_init_writer")
+    try:
+        opts = CompressOptions(int(method), int(level))
+        arr = (File * max(len(items), 1))()
+        for i, ((name, _), t) in enumerate(zip(items, flat)):
+            arr[i].filename = name.encode()
+            arr[i].buffer = t.data_ptr() if t.numel() else None
+            arr[i].size = t.numel()
+            arr[i].options = C.pointer(opts)
+            arr[i].cctx = None
+        if flat:
+            _settle(flat[0].device)
+        _check(L.zpack_write_header(C.byref(w)), "zpack_write_header")
+        _check(L.zpack_write_data_header(C.byref(w)), "zpack_write_data_header")
+        _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
+        _check(L.zpack_write_cdr(C.byref(w)), "zpack_write_cdr")
+        _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
+        if path is None:
+            return C.string_at(w.buffer, w.file_size)
+        return None
+    finally:
+        L.zpack_close_writer(C.byref(w))
+
+
+def _u8():
+    import torch
+    return torch.uint8

@@ -45,6 +45,15 @@ void zi_index_drop(const zpack_file_entry* table);
 int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                       zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                       const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size);
+/* ... with the PLAINTEXT IN DEVICE MEMORY (zpack_amd.h: zpack_amd_read_files_device): buffers[i] are device pointers, the batch runs on
+ * the one codec of `ctx` whose device they belong to (ZPACK_ERROR_NOT_AVAILABLE when it has none; ZPACK_ERROR_STREAM_INVALID when
+ * the codec's pointer check turns a buffer down) */
+int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
+                             zpack_u8* const* d_buffers, const size_t* max_sizes, zpk_decode_result* res);
+/* the codec of `ctx` on the device that the first device pointer among ptrs[0, n) with sizes[i] != 0 belongs to (stride: bytes from one
+ * pointer / size to the next, the arrays may be fields of structs).  *rc = ZPACK_OK with NULL: no entry has bytes, any codec serves;
+ * ZPACK_ERROR_STREAM_INVALID: bytes, but no device pointer; ZPACK_ERROR_NOT_AVAILABLE: a device the context does not hold */
+zpk_codec* zi_ctx_codec_of(zi_ctx* ctx, const void* ptrs, size_t ptr_stride, const void* sizes, size_t size_stride, int size_is_u64, zpack_u64 n, int* rc);
 
 /* read-ahead for in-order zpack_read_file callers (readahead.c) */
 struct zi_ra_s* zi_ra_create(void);          /* reads ZPACK_AMD_READ_AHEAD; NULL when out of memory (read-ahead is then off) */

@@ -7,6 +7,7 @@
  * (zpk_codec_decode_batch_host); zpack_read_file is a batch of one, zpack_read_files a batch of n.
  */
 #include "internal.h"
+#include "zpack_amd.h"
 
 /* ------------------------------------------------------------------ container parsing */
 
@@ -324,9 +325,28 @@ static void read_part(void* arg, int k)
 /* n entries in ONE device batch.  Memory-backed readers hand the codec the archive image itself
  * (zero-copy on the host side, as the reference does at lib/zpack_read.c:345-346); file-backed readers
  * gather the payloads first (the reference mallocs + freads per entry, :336-344). */
+static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
+                          zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
+                          const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int on_device);
+
 int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                       zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                       const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size)
+{
+    return decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, span, span_lo, span_size, 0);
+}
+
+int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
+                             zpack_u8* const* d_buffers, const size_t* max_sizes, zpk_decode_result* res)
+{
+    return decode_entries(reader, ctx, entries, count, d_buffers, max_sizes, res, NULL, 0, 0, 1);
+}
+
+/* on_device: buffers[i] are DEVICE pointers — the plaintext stays there, only the compressed bytes cross the bus: the batch is one
+ * zpk_codec_decode_batch_host_dptr call on the codec of the pointers' device (no shard: one call's pointers belong to one device) */
+static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
+                          zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
+                          const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int on_device)
 {
     if (count == 0) return ZPACK_OK;
     if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
@@ -368,7 +388,14 @@ int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const
     } else {
         for (zpack_u64 i = 0; i < count; i++) fill_desc(&desc[i], entries[i], entries[i]->offset, max_sizes[i]);
     }
-    if (rc == ZPACK_OK) {
+    if (rc == ZPACK_OK && on_device) {
+        zpk_codec* codec = zi_ctx_codec_of(ctx, buffers, sizeof(*buffers), max_sizes, sizeof(*max_sizes), sizeof(size_t) == 8, count, &rc);
+        if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: verdicts only) */
+        if (codec) {
+            const int crc = zpk_codec_decode_batch_host_dptr(codec, image, image_size, desc, count, buffers, res);
+            if (crc != ZPK_OK) rc = crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
+        }
+    } else if (rc == ZPACK_OK) {
         read_job job = { ctx, image, image_size, desc, buffers, res, {0}, {0} };
         int parts = ctx->n;
         if ((zpack_u64)parts > count) parts = (int)count;
@@ -392,7 +419,7 @@ int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const
 }
 
 static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
-                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx)
+                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int on_device)
 {
     if (count == 0) return ZPACK_OK;
     if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
@@ -401,7 +428,7 @@ static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zp
     if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
     zpk_decode_result* res = (zpk_decode_result*)calloc((size_t)count, sizeof(*res));
     if (!res) return ZPACK_ERROR_MALLOC_FAILED;
-    const int rc = zi_decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0);
+    const int rc = decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0, on_device);
     if (rc == ZPACK_OK)
         for (zpack_u64 i = 0; i < count; i++) {
             results[i] = res[i].status;
@@ -429,7 +456,7 @@ int zpack_read_file(zpack_reader* reader, zpack_file_entry* entry, zpack_u8* buf
     int result = ZPACK_OK;
     zpack_file_entry* one = entry;
     zpack_u8* out = buffer;
-    int rc = read_batch(reader, &one, 1, &out, &max_size, &result, ctx);
+    int rc = read_batch(reader, &one, 1, &out, &max_size, &result, ctx, 0);
     return rc ? rc : result;
 }
 
@@ -437,7 +464,7 @@ int zpack_read_files(zpack_reader* reader, zpack_file_entry* const* entries, zpa
                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx)
 {
     if (!reader || (count && (!entries || !buffers || !max_sizes || !results))) return ZPACK_ERROR_STREAM_INVALID;
-    return read_batch(reader, entries, count, buffers, max_sizes, results, dctx);
+    return read_batch(reader, entries, count, buffers, max_sizes, results, dctx, 0);
 }
 
 int zpack_read_files_packed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
@@ -455,7 +482,39 @@ int zpack_read_files_packed(zpack_reader* reader, zpack_file_entry* const* entri
         bufs[i] = buffer + (pos <= buffer_size ? pos : buffer_size);
         pos += entries[i]->uncomp_size;
     }
-    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx);
+    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx, 0);
+    free(bufs); free(caps);
+    return rc;
+}
+
+/* ---- zpack_amd.h: the same reads with the plaintext in DEVICE memory — thin fronts for read_batch's on_device mode.  They neither use
+ * nor feed the read-ahead windows (those hold host copies for zpack_read_file callers). */
+int zpack_amd_read_files_device(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                void* const* d_buffers, const size_t* max_sizes, int* results, void* dctx)
+{
+    if (!reader || (count && (!entries || !d_buffers || !max_sizes || !results))) return ZPACK_ERROR_STREAM_INVALID;
+    if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
+    return read_batch(reader, entries, count, (zpack_u8* const*)d_buffers, max_sizes, results, dctx, 1);
+}
+
+int zpack_amd_read_files_device_packed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                       void* d_buffer, size_t buffer_size, zpack_u64* out_offsets, int* results, void* dctx)
+{
+    if (!reader || (count && (!entries || !d_buffer || !out_offsets || !results))) return ZPACK_ERROR_STREAM_INVALID;
+    if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;
+    zpack_u8** bufs = (zpack_u8**)malloc(sizeof(zpack_u8*) * (size_t)(count ? count : 1));
+    size_t* caps = (size_t*)malloc(sizeof(size_t) * (size_t)(count ? count : 1));
+    if (!bufs || !caps) { free(bufs); free(caps); return ZPACK_ERROR_MALLOC_FAILED; }
+    zpack_u64 pos = 0;
+    for (zpack_u64 i = 0; i < count; i++) {
+        out_offsets[i] = pos;
+        const zpack_u64 room = pos <= buffer_size ? buffer_size - pos : 0;
+        caps[i] = (size_t)(entries[i]->uncomp_size <= room ? entries[i]->uncomp_size : room);   /* too little room => BUFFER_TOO_SMALL */
+        bufs[i] = (zpack_u8*)d_buffer + (pos <= buffer_size ? pos : buffer_size);
+        const zpack_u64 stride = zpk_codec_packed_stride(entries[i]->uncomp_size);  /* every entry starts at a multiple of 256 */
+        pos = stride > ~(zpack_u64)0 - pos ? ~(zpack_u64)0 : pos + stride;
+    }
+    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx, 1);
     free(bufs); free(caps);
     return rc;
 }

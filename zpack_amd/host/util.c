@@ -89,6 +89,25 @@ zi_ctx* zi_pick_ctx(void* explicit_ctx, void** owner_slot)
     return x;
 }
 
+zpk_codec* zi_ctx_codec_of(zi_ctx* ctx, const void* ptrs, size_t ptr_stride, const void* sizes, size_t size_stride, int size_is_u64, zpack_u64 n, int* rc)
+{
+    int any_bytes = 0;
+    *rc = ZPACK_OK;
+    for (zpack_u64 i = 0; i < n; i++) {
+        const void* const sp = (const char*)sizes + i * size_stride;
+        const zpack_u64 bytes = size_is_u64 ? *(const zpack_u64*)sp : (zpack_u64)*(const size_t*)sp;
+        if (!bytes) continue;
+        any_bytes = 1;
+        const int ordinal = zpk_codec_pointer_device(*(void* const*)((const char*)ptrs + i * ptr_stride));
+        if (ordinal < 0) continue;
+        for (int k = 0; k < ctx->n; k++) if (zpk_codec_device(ctx->dev[k]) == ordinal) return ctx->dev[k];
+        *rc = ZPACK_ERROR_NOT_AVAILABLE;
+        return NULL;
+    }
+    if (any_bytes) *rc = ZPACK_ERROR_STREAM_INVALID;
+    return NULL;
+}
+
 /* split `count` items with weights w[] into x->n contiguous ranges of about equal weight: cut[k] .. cut[k+1] */
 void zi_split(const zpack_u64* w, zpack_u64 count, int parts, zpack_u64* cut)
 {

@@ -7,6 +7,7 @@
  * `write_offset += comp_size` of :338 becomes a prefix sum over the batch's compressed sizes.
  */
 #include "internal.h"
+#include "zpack_amd.h"
 
 /* ------------------------------------------------------------------ sink + entry table */
 
@@ -162,7 +163,10 @@ static void write_part(void* arg, int k)
     j->rc[k] = n ? zpk_codec_encode_batch_host(j->ctx->dev[k], j->srcs + lo, j->desc + lo, n, j->dsts + lo, j->res + lo) : ZPK_OK;
 }
 
-int zpack_write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count)
+/* on_device: files[i].buffer are DEVICE pointers (zpack_amd_write_files_device) — the plaintext is compressed where it lies, only the
+ * compressed bytes cross the bus: one zpk_codec_encode_batch_dsrc call on the codec of the pointers' device (no shard: one call's
+ * pointers belong to one device).  Everything behind the codec call is the same code, so the archive is the same bytes. */
+static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, int on_device)
 {
     if (file_count == 0) return ZPACK_OK;
     if (!writer->file && !writer->buffer) return ZPACK_ERROR_WRITER_NOT_OPENED;
@@ -196,6 +200,15 @@ int zpack_write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_co
     if (rc == ZPACK_OK) {
         zpack_u64 pos = 0;
         for (zpack_u64 i = 0; i < file_count; i++) { dsts[i] = scratch + pos; pos += desc[i].dst_capacity + 16; }
+    }
+    if (rc == ZPACK_OK && on_device) {
+        zpk_codec* codec = zi_ctx_codec_of(ctx, &files[0].buffer, sizeof(files[0]), &files[0].size, sizeof(files[0]), 1, file_count, &rc);
+        if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: empty entries only) */
+        if (codec) {
+            const int crc = zpk_codec_encode_batch_dsrc(codec, srcs, desc, file_count, dsts, res);
+            if (crc != ZPK_OK) rc = crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
+        }
+    } else if (rc == ZPACK_OK) {
         write_job job = { ctx, srcs, desc, dsts, res, {0}, {0} };
         int parts = ctx->n;
         if ((zpack_u64)parts > file_count) parts = (int)file_count;
@@ -224,6 +237,16 @@ int zpack_write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_co
     }
     free(scratch); free(desc); free(res); free(srcs); free(dsts);
     return rc;
+}
+
+int zpack_write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count) { return write_files(writer, files, file_count, 0); }
+
+int zpack_amd_write_files_device(zpack_writer* writer, zpack_file* files, zpack_u64 file_count)
+{
+    if (!writer || (file_count && !files)) return ZPACK_ERROR_STREAM_INVALID;
+    for (zpack_u64 i = 0; i < file_count; i++) if (!files[i].options || !files[i].filename) return ZPACK_ERROR_STREAM_INVALID;
+    if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
+    return write_files(writer, files, file_count, 1);
 }
 
 /* raw entry copy between archives: no codec involved (lib/zpack_write.c:345-428) */
