@@ -24,8 +24,8 @@ ZPACK_EXPORT int zpack_amd_read_ahead_stats(const zpack_reader* reader, void* dc
  * then up again).
  *
  * Call model.  Synchronous: a call returns when the buffers hold the plaintext / the archive holds the entries.  `entries`, `results`,
- *   `max_sizes`, `out_offsets` and the zpack_file array (its filenames and options) are host memory; the reader is memory-backed or
- *   file-backed and the writer heap- or file-backed, as for the host forms.
+ *   `max_sizes`, `out_offsets` and the zpack_file array (its filenames and options) are host memory; the reader is memory-backed,
+ *   file-backed or over an image in device memory (zpack_amd_init_reader_device, below) and the writer heap- or file-backed.
  * results[i], the bytes, last_return.  results[i] and the bytes in d_buffers[i] are what zpack_read_files gives for the same arguments
  *   with host buffers; reader->last_return is set by the same rule (the last entry's, or the last failing one's).  One bad entry does
  *   not stop the others.
@@ -53,6 +53,45 @@ ZPACK_EXPORT int zpack_amd_read_files_device_packed(zpack_reader* reader, zpack_
                                                     int* results, void* dctx);
 /* zpack_write_files where files[i].buffer is a DEVICE pointer (files[i].size bytes) */
 ZPACK_EXPORT int zpack_amd_write_files_device(zpack_writer* writer, zpack_file* files, zpack_u64 file_count);
+
+/* ---- the archive IMAGE in DEVICE memory -------------------------------------------------------------------------------------------
+ * A third kind of reader beside the memory-backed and the file-backed one: the archive lies in device memory — a data set or checkpoint
+ * kept compressed in HBM, an archive that arrived by a device-to-device transfer — and its compressed bytes never cross the bus.
+ *
+ * After a successful init.  version, file_entries, file_count, comp_size, uncomp_size, file_size, cdr_offset and eocdr_offset are what
+ *   zpack_init_reader_memory gives for the same bytes; the names are reader-owned.  buffer == NULL and file == NULL: where the image
+ *   lives is kept beside the reader (zpack_reader has the reference's fixed layout), zpack_amd_reader_device_image tells.  The image is
+ *   BORROWED, as in zpack_init_reader_memory_shared: the caller keeps it alive and unmodified until zpack_close_reader, which does not
+ *   free it.  zpack_close_reader and a failed init drop the record: the struct then reads ZPACK_ERROR_ARCHIVE_NOT_LOADED like any reader
+ *   that was never opened, and can be opened again, as any kind.
+ * Return codes of the init.  A NULL reader or d_image is ZPACK_ERROR_STREAM_INVALID.  No HIP device: ZPACK_ERROR_NOT_AVAILABLE.  A
+ *   pointer that is not device memory, or a range [d_image, d_image + size) that leaves its allocation, is ZPACK_ERROR_STREAM_INVALID,
+ *   checked on the host before anything is copied.  For a valid range every container error is the code zpack_init_reader_memory
+ *   returns for the same bytes (too small, a bad signature, a CDR that lies about its size ...).  Only the header, the EOCDR and the
+ *   CDR are fetched to the host.
+ * Which read calls work, and their results.  zpack_read_file, zpack_read_files, zpack_read_files_packed, zpack_amd_read_files_device,
+ *   zpack_amd_read_files_device_packed, zpack_read_raw_file, zpack_read_raw_file_stream, zpack_read_file_stream, and
+ *   zpack_write_files_from_archive with it as the source.  results[i], the bytes [0, produced) of every buffer, the return value and
+ *   reader->last_return are exactly what the same call gives on a memory reader over a host copy of the image; nothing outside
+ *   [buffer, buffer + max_size) is written.  The batch reads decode where the image lies: large frames block-parallel, large stored
+ *   entries chip-wide, everything else one wave per entry, into the codec's staging; one kernel (device destinations) or one copy home
+ *   (host destinations) hands the plaintext over.
+ * Raw and stream reads fetch the bytes they need with a device-to-host copy; nothing else about them changes.
+ * Read-ahead.  In-order zpack_read_file loops keep their read-ahead; its windows decode on the device like any batch.
+ * Which device.  The image's device must be one of the context's (dctx, else the reader's own: ZPACK_AMD_DEVICES), else
+ *   ZPACK_ERROR_NOT_AVAILABLE; device destinations must be on the image's device, else ZPACK_ERROR_STREAM_INVALID.  The batch runs on
+ *   that device's codec alone, with no shard.
+ * Stream ordering.  The caller's earlier work on the image (the copy that filled it ...) must have completed; the image is read-only to
+ *   the library.
+ * Calls that do not apply.  zpack_read_archive_memory and zpack_read_archive on such a reader return ZPACK_ERROR_ARCHIVE_NOT_LOADED: it
+ *   has no host image and no file. */
+
+/* A reader over an archive image in DEVICE memory: [d_image, d_image + size) on one HIP device.  The image is BORROWED
+ * (as in zpack_init_reader_memory_shared): the caller keeps it alive and unmodified until zpack_close_reader, which
+ * does not free it.  Parses header, EOCDR and CDR by fetching only those bytes to the host. */
+ZPACK_EXPORT int zpack_amd_init_reader_device(zpack_reader* reader, const void* d_image, size_t size);
+/* *d_image / *device of a reader opened by the call above (NULL / -1 for any other reader). */
+ZPACK_EXPORT int zpack_amd_reader_device_image(const zpack_reader* reader, const void** d_image, int* device);
 
 #ifdef __cplusplus
 }

@@ -49,7 +49,9 @@ extern "C" {
                                         ZPK_OPT_STORED_SPAN_MIN, decode_stats2 out[12], out[13], which read 0: large stored entries in device memory copied chip-wide / their groups.
                                         zpk_codec_decode_batch_host_dptr, zpk_codec_encode_batch_dsrc, zpk_codec_copy_spans_device, zpk_codec_pointer_device,
                                         zpk_codec_packed_stride: the host-pointer paths with the PLAINTEXT in the caller's device memory, and the kernel that moves it;
-                                        decode_stats2 out[14], out[15], which read 0: sub-batches through the host path's pipeline / k_span_copy launches.) */
+                                        decode_stats2 out[14], out[15], which read 0: sub-batches through the host path's pipeline / k_span_copy launches.
+                                        zpk_codec_fetch_device, zpk_codec_decode_batch_dimage, ZPK_OPT_DIMAGE_CHUNK, zpk_codec_dimage_stats: the host-pointer paths
+                                        with the ARCHIVE IMAGE in the caller's device memory.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -145,10 +147,13 @@ int         zpk_codec_device(const zpk_codec* c);
  *                                   `value` bytes that passes the guards of lib/zpack_read.c:328-354 is copied to its slot and hashed by the
  *                                   whole chip — one wave per 64 KiB, then one short chain per entry — instead of by one wave; anything
  *                                   else, and any entry that fails a guard, goes through the one-wave kernels (verdicts other than OK /
- *                                   hash mismatch come from there only).  Default 256 KiB; the least size taken is 1025; 0 = never. */
+ *                                   hash mismatch come from there only).  Default 256 KiB; the least size taken is 1025; 0 = never.
+ *   ZPK_OPT_DIMAGE_CHUNK            zpk_codec_decode_batch_dimage: bytes of staging slots per sub-batch (an entry whose slot is larger goes
+ *                                   alone).  0 = the default, ZPK_HOST_CHUNK_BYTES (4 GiB): what zpk_codec_decode_batch_host cuts by. */
 /* (2..5 were the opt-in two-stage LZ4 path of round 4 and its measurement aids: measured slower than the one-kernel decoder, removed in round 5) */
 enum { ZPK_OPT_ENC_SPLIT_MIN = 6, ZPK_OPT_DEC_SPLIT_MIN = 7, ZPK_OPT_ORDER_MIN = 8, ZPK_OPT_ORDER_FAST_LAST = 9 /* a batch of ONE size class runs the entries that did not compress (a copy to decode) last: 1 (default) / 0 */ };
 #define ZPK_OPT_STORED_SPAN_MIN 10
+#define ZPK_OPT_DIMAGE_CHUNK 11
 int         zpk_codec_set_option(zpk_codec* c, int option, int value);
 
 /* ---- batch decode + verify ----------------------------------------------------------------
@@ -188,9 +193,10 @@ int  zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_
  * 64 KiB; they are not part of out[0] of zpk_codec_decode_stats (no work list held them) nor of out[5] / out[6].
  * Not in this call: entries that are sequences of frames (round 4 archives) stay one wave per entry; the
  * block-parallel entries are not overlapped with one another or with the one-wave launch; zpk_codec_decode_big_device still walks on the
- * host; libzpack_amd.so and zpk-batch do not use it: this call wants the ARCHIVE in device memory, and a reader's image is host memory or a
- * file.  What libzpack_amd.so does use for plaintext in device memory (zpack_amd.h: zpack_amd_read_files_device, _packed,
- * zpack_amd_write_files_device) is zpk_codec_decode_batch_host_dptr / zpk_codec_encode_batch_dsrc below; zpk-batch uses neither. */
+ * host.  libzpack_amd.so reaches this call's routing through zpk_codec_decode_batch_dimage below, for a reader whose image lies in device
+ * memory (zpack_amd.h: zpack_amd_init_reader_device); a reader over host memory or a file, with the plaintext in device memory
+ * (zpack_amd_read_files_device, _packed, zpack_amd_write_files_device), uses zpk_codec_decode_batch_host_dptr / zpk_codec_encode_batch_dsrc.
+ * zpk-batch uses none of them. */
 int  zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                        uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results);
 
@@ -228,6 +234,32 @@ int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_
 int zpk_codec_pointer_device(const void* ptr);
 /* what an entry of uncomp_size bytes takes of a packed device read (zpack_amd_read_files_device_packed): uncomp_size rounded up to 256 */
 uint64_t zpk_codec_packed_stride(uint64_t uncomp_size);
+
+/* ---- the ARCHIVE IMAGE in the caller's device memory ------------------------------------------------
+ * instance-free: copies [d_src, d_src + bytes) home, synchronously.  ZPK_E_INVALID when it is not `bytes` bytes of one allocation in
+ * device memory (checked first, nothing copied); ZPK_E_NO_DEVICE without a runtime.  host_dst NULL: the check alone, nothing is copied
+ * (how a caller validates a whole image before it fetches the few bytes it parses).  bytes 0: ZPK_OK wherever the pointers point. */
+int zpk_codec_fetch_device(const void* d_src, void* host_dst, uint64_t bytes);
+
+/* zpk_codec_decode_batch_host / _host_dptr with the ARCHIVE in device memory: desc and results are host memory, dst_ptrs a HOST array of
+ * n host pointers (dst_on_device == 0) or n device pointers on the codec's device (1); synchronous.  The compressed bytes stay where
+ * they are.  The batch is cut into sub-batches in the order given: a sub-batch closes when the next slot would take it past
+ * ZPK_OPT_DIMAGE_CHUNK, an entry whose slot is larger goes alone; the slots are the host path's — what the entry may produce (a stored
+ * entry: uncomp_size), at multiples of 256, in the codec's staging (the block-parallel readers want outputs on 256-byte boundaries, so
+ * nothing is decoded straight into a caller's pointer).  Each sub-batch runs the routing of zpk_codec_decode_big_batch_device into that
+ * staging — the walk on the device, the chooser, the chip-wide stored copies, one one-wave launch for everything else; results[i] are
+ * that call's — and then the slots are handed over as the host calls do: ONE launch of k_span_copy with [slot, slot + produced) ->
+ * pointer (device destinations), or the copy home and the host path's scatter (host destinations).  Nothing outside
+ * [dst_ptrs[i], + dst_capacity) is written.
+ * POINTER CHECK, on the host before anything is enqueued: [d_archive, + archive_size) and, with device destinations, every
+ * [dst_ptrs[i], + dst_capacity) pass the check of zpk_codec_decode_batch_host_dptr, else ZPK_E_INVALID and nothing has run.
+ * The caller's earlier work on the image and the buffers must have completed: the codec runs on its own stream.
+ * decode_stats2 describes the call as it does zpk_codec_decode_big_batch_device (out[5], [6], [10]..[13] summed over the sub-batches). */
+int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size,
+                                  const zpk_decode_desc* desc, uint64_t n,
+                                  uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results);
+/* the most recent such call: out[0] sub-batches, out[1] k_span_copy launches, out[2] bytes copied home (saturating), out[3] 0 */
+int zpk_codec_dimage_stats(zpk_codec* c, uint32_t out[4]);
 
 /* ---- batch encode + hash ------------------------------------------------------------------ */
 size_t zpk_codec_compress_bound(uint32_t method, size_t src_size);

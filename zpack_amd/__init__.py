@@ -20,6 +20,7 @@ DF_GENERAL = 2
 K_CLASSIFY, K_STORED, K_LZ4, K_ZSTD, K_ZSTD_FSE, K_PACK, K_ENCODE = 0, 1, 2, 3, 4, 5, 7
 OPT_ENC_SPLIT_MIN, OPT_DEC_SPLIT_MIN, OPT_ORDER_MIN, OPT_ORDER_FAST_LAST = 6, 7, 8, 9      # zpk_codec_set_option (include/zpack_codec.h)
 OPT_STORED_SPAN_MIN = 10
+OPT_DIMAGE_CHUNK = 11
 
 # zpk_decode_desc / zpk_decode_result / zpk_encode_desc / zpk_encode_result (include/zpack_codec.h)
 DECODE_DESC = np.dtype([("src_offset", "<u8"), ("comp_size", "<u8"), ("uncomp_size", "<u8"), ("expect_hash", "<u8"),
@@ -268,6 +269,34 @@ class Codec:
         self._chk(self.L.zpk_codec_decode_batch_host_dptr(self.h, arc.ctypes.data, arc.size, desc.ctypes.data, n, ptrs, res.ctypes.data),
                   "zpk_codec_decode_batch_host_dptr")
         return res
+
+    # ---- the ARCHIVE IMAGE in the caller's device memory (a uint8 CUDA tensor; the tables host memory) ----
+    def decode_batch_dimage(self, image, desc, dst_ptrs=None):
+        """decode_batch_host / decode_batch_host_dptr with the archive in device memory.  dst_ptrs None: host destinations — returns
+        (results, [output bytes]) like decode_batch_host; else dst_ptrs[i] = device address of desc[i].dst_capacity bytes on this codec's
+        device — returns the results.  Raises on ZPK_E_INVALID (a pointer the check turned down: nothing has run)."""
+        self._settle(None)
+        desc = np.ascontiguousarray(desc, dtype=DECODE_DESC)
+        n = len(desc)
+        res = np.zeros(n, dtype=DECODE_RESULT)
+        self.L.zpk_codec_decode_batch_dimage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
+        if dst_ptrs is None:
+            outs = [np.zeros(max(1, int(d["dst_capacity"])), dtype=np.uint8) for d in desc]
+            ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        else:
+            ptrs = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in dst_ptrs])
+        self._chk(self.L.zpk_codec_decode_batch_dimage(self.h, image.data_ptr(), image.numel(), desc.ctypes.data, n, ptrs,
+                                                       0 if dst_ptrs is None else 1, res.ctypes.data), "zpk_codec_decode_batch_dimage")
+        if dst_ptrs is None:
+            return res, [o[:int(d["dst_capacity"])] for o, d in zip(outs, desc)]
+        return res
+
+    def dimage_stats(self):
+        """The last decode_batch_dimage call: its sub-batches (OPT_DIMAGE_CHUNK), k_span_copy launches and the bytes it copied home."""
+        a = (C.c_uint32 * 4)()
+        self.L.zpk_codec_dimage_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        self._chk(self.L.zpk_codec_dimage_stats(self.h, a), "zpk_codec_dimage_stats")
+        return dict(sub_batches=a[0], span_copy_launches=a[1], bytes_copied_home=a[2])
 
     def copy_spans_device(self, rows, stream=None):
         """rows: (n, 3) uint64 array of (src address, dst address, len): one k_span_copy launch, asynchronous on `stream` (None: the

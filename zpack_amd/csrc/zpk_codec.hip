@@ -46,7 +46,8 @@
 // k_span_copy (span_copy.h) is compiled in a file of its own, span_copy.hip: this file's code object stays the one it was, kernel for
 // kernel at the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
 namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
-#include "stream_plan.h"                         // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
+#include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
+#include "stream_plan.h"                        // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
 
 using namespace zpk;
 
@@ -702,6 +703,10 @@ struct zpk_codec {
     DevBuf<u8> d_sc; PinBuf h_sc; hipEvent_t sc_ev = nullptr; bool sc_pending = false;
     u64   sc_base = 0, sc_size = 0;
     u32   pipe_last = 0, sc_last = 0;                // most recent host decode call: sub-batches that took the three-stage pipeline; k_span_copy launches
+    // the archive image in the caller's device memory (dimage_plan.h): ZPK_OPT_DIMAGE_CHUNK (0 = the default) and, of the most recent
+    // zpk_codec_decode_batch_dimage call, its sub-batches, k_span_copy launches and the bytes it copied home (saturating)
+    u64   dimage_chunk = 0;
+    u32   dimage_last[3] = {0, 0, 0};
     DevBufBase* const bufs[26] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_bigwalk, &d_sspan, &d_sc,
                                    &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
                                    &d_xpart, &d_zarena, &d_zstate };
@@ -1271,6 +1276,8 @@ static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t*
 // logical end (wide loads next to an entry's last byte; the two-stage LZ4 parser fetches whole 64-byte groups) — never interpret them
 #define ZPK_SRC_SLACK 192u
 #define ZPK_SRC_READ_SLACK 128u
+static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
+                         zpk_decode_result* results, bool ddst, u64* home = nullptr);
 static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
                              const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst = false)
 {
@@ -1290,9 +1297,20 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
     e = hipMemcpyAsync(results, c->d_res, n * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "decode: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    // hand the bytes back: everything the codec produced (a hash mismatch leaves the data in the buffer, like the
-    // reference), and only that — a generous max_size costs device address space, not PCIe time
+    return deliver_slots(c, hd, desc, n, out_total, dst_ptrs, results, ddst);
+}
+
+// The slots of a decoded sub-batch, c->d_dst + hd[i].dst_offset, handed to the caller (decode_host_chunk; zpk_codec_decode_batch_dimage):
+// everything the codec produced (a hash mismatch leaves the data in the buffer, like the reference), and only that — a generous
+// max_size costs device address space, not PCIe time.  results[0, n) are home and the decode has completed.  *home: the bytes that
+// crossed the bus for it.
+static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
+                         zpk_decode_result* results, bool ddst, u64* home)
+{
+    int rc;
+    hipError_t e = hipSuccess;
     u64 produced_total = 0;
+    if (home) *home = 0;
     for (u64 i = 0; i < n; i++) {
         if (results[i].produced > desc[i].dst_capacity) results[i].produced = desc[i].dst_capacity;     // (cannot happen)
         produced_total += results[i].produced;
@@ -1310,9 +1328,11 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
         // the scatter, ran at 6.7 GB/s: page faults + the driver's own staging of pageable memory.)
         rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; }, [&](u64 i) { return (u64)results[i].produced; }, e);
         if (rc) return rc;
+        if (home) *home = out_total;
     } else {
         for (u64 i = 0; i < n && e == hipSuccess; i++)
             if (results[i].produced) e = hipMemcpy(dst_ptrs[i], c->d_dst + hd[i].dst_offset, results[i].produced, hipMemcpyDeviceToHost);
+        if (home) *home = produced_total;
     }
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "D2H: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, ddst);
@@ -2028,7 +2048,7 @@ static int stored_span_enqueue(zpk_codec* c, const u8* d_archive, u64 archive_si
     hipLaunchKernelGGL(k_xxh3_chain, dim3((u32)plan.nspans), dim3(64), 0, st, d_archive, d_spans, (const u64*)d_part, d_hash, (u64*)nullptr, (u64)0, ~(u64)0, 1);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_sspan + up_bytes, d_hash, plan.nspans * 8, hipMemcpyDeviceToHost, st));
-    c->span_last[0] = (u32)plan.nspans; c->span_last[1] = (u32)(plan.groups > 0xFFFFFFFFull ? 0xFFFFFFFFull : plan.groups);
+    c->span_last[0] += (u32)plan.nspans; c->span_last[1] += (u32)(plan.groups > 0xFFFFFFFFull ? 0xFFFFFFFFull : plan.groups);      // (+=: as walk_last)
     return ZPK_OK;
 }
 // ... the join: their stream has drained -> their hashes are in the pinned block, their results are composed
@@ -2116,15 +2136,11 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
 // Of the frames the walk accepted, pj_choose picks those worth a turn of the whole chip (lz4_pj.h / zstd_pj.h, one after the other);
 // every other entry — and every entry the block-parallel path does not finish — is decoded by the one-wave kernels in ONE launch over
 // their descriptors, exactly as zpk_codec_decode_batch_device would: every verdict other than OK / hash mismatch is theirs.
-int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                      uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results)
+// (the body: the caller holds the lock, has set the device and called begin_decode_call — zpk_codec_decode_batch_dimage runs it once per
+// sub-batch, with d_dst = the codec's own staging)
+static int decode_big_batch_body(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                 uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results)
 {
-    if (!c || (n && (!desc || !results || !d_archive || !d_dst))) return ZPK_E_INVALID;
-    if (n == 0) return ZPK_OK;
-    if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;
-    CodecLock lk(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    begin_decode_call(c);
     int rc = ZPK_OK;
     StoredSpanRun span;                                                               // (declared in front of the try: it waits on every way out)
     try {
@@ -2150,7 +2166,7 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
             HIPCHK(c, hipMemcpyAsync(h_walk + L.rec_off, c->d_bigwalk + L.rec_off, L.total - L.rec_off, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             const BigWalkRec* const recs = (const BigWalkRec*)(h_walk + L.rec_off);
-            c->walk_last[0] = (u32)nc;
+            c->walk_last[0] += (u32)nc;                                                // (+=: begin_decode_call zeroed it; the sub-batches of zpk_codec_decode_batch_dimage add up)
             for (u64 k = 0; k < nc; k++) {
                 const BigWalkRec& r = recs[k];
                 if (r.accepted != 1 || r.nblocks == 0 || r.nblocks > items[k].cap) continue;
@@ -2177,6 +2193,100 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
         if ((rc = decode_rest_device(c, d_archive, archive_size, desc, rest.data(), rest.size(), d_dst, dst_size, results))) return rc;
         rc = stored_span_finish(c, span, desc, results);
     } catch (...) { rc = ZPK_E_NOMEM; }
+    return rc;
+}
+
+int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                      uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results)
+{
+    if (!c || (n && (!desc || !results || !d_archive || !d_dst))) return ZPK_E_INVALID;
+    if (n == 0) return ZPK_OK;
+    if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_decode_call(c);
+    return decode_big_batch_body(c, d_archive, archive_size, desc, n, d_dst, dst_size, results);
+}
+
+// ---- the ARCHIVE IMAGE in the caller's device memory, the destinations host or device pointers (dimage_plan.h) ----------------------------
+// zpk_codec_decode_batch_host / _host_dptr for a reader whose image lies in device memory: the batch is cut into sub-batches by the size
+// of their staging slots (dimage_cut), each runs the body of zpk_codec_decode_big_batch_device with d_dst = c->d_dst — the walk on the
+// device, dec_choose, the stored spans, one one-wave launch for the rest: the verdicts come from where they always came from — and
+// deliver_slots hands the slots over as the host path does: one k_span_copy to device pointers; the copy home and the scatter to host
+// pointers.  The compressed bytes never cross the bus.
+int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                  uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results)
+{
+    if (!c || (n && (!desc || !results || !dst_ptrs || !d_archive))) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    c->dimage_last[0] = c->dimage_last[1] = c->dimage_last[2] = 0;
+    if (n == 0) return ZPK_OK;
+    const bool ddst = dst_on_device != 0;
+    span_check_begin(c);                                                              // the pointer checks: before anything is enqueued
+    if (!span_ptr_ok(c, d_archive, archive_size)) { snprintf(c->err, sizeof(c->err), "the archive is not %llu bytes of one allocation on device %d", (unsigned long long)archive_size, c->device); return ZPK_E_INVALID; }
+    if (ddst)
+        for (u64 i = 0; i < n; i++)
+            if (!span_ptr_ok(c, dst_ptrs[i], desc[i].dst_capacity)) { snprintf(c->err, sizeof(c->err), "destination %llu is not %llu bytes of one allocation on device %d", (unsigned long long)i, (unsigned long long)desc[i].dst_capacity, c->device); return ZPK_E_INVALID; }
+    begin_decode_call(c);
+    const u64 chunk = dimage_chunk(c->dimage_chunk);
+    auto slot = [&](u64 i) { return dimage_slot(desc[i].method == ZPK_METHOD_NONE, desc[i].uncomp_size, desc[i].dst_capacity); };
+    int rc = ZPK_OK;
+    u64 home_total = 0;
+    try {
+        std::vector<zpk_decode_desc> hd;
+        std::vector<u64> at(n);                                                       // entry i lies at at[i] of ITS sub-batch's staging
+        for (u64 first = 0; first < n && rc == ZPK_OK; ) {
+            const DimageCut cut = dimage_cut(first, n, chunk, slot, at.data() + first);
+            hd.resize(cut.count);
+            for (u64 k = 0; k < cut.count; k++) {
+                const zpk_decode_desc& d = desc[first + k];
+                hd[k] = d;
+                hd[k].dst_offset = at[first + k];
+                // (as in the host path: the device judges `max_size < uncomp_size` on the caller's capacity, a stored entry that passes
+                // it writes uncomp_size bytes and its slot is that long)
+                if (d.method == ZPK_METHOD_NONE && d.dst_capacity >= d.uncomp_size) hd[k].dst_capacity = span_copy_read_slot_bytes(true, d.uncomp_size, d.dst_capacity);
+            }
+            if (cut.out_total > ~0ull - 16) { snprintf(c->err, sizeof(c->err), "a staging slot of %llu bytes", (unsigned long long)cut.out_total); rc = ZPK_E_NOMEM; break; }
+            if ((rc = grow(c, c->d_dst, cut.out_total + 16))) break;
+            if ((rc = decode_big_batch_body(c, d_archive, archive_size, hd.data(), cut.count, c->d_dst, cut.out_total, results + first))) break;
+            u64 home = 0;
+            if ((rc = deliver_slots(c, hd.data(), desc + first, cut.count, cut.out_total, dst_ptrs + first, results + first, ddst, &home))) break;
+            home_total = home > ~0ull - home_total ? ~0ull : home_total + home;
+            c->dimage_last[0]++;
+            first += cut.count;
+        }
+    } catch (...) { rc = ZPK_E_NOMEM; }
+    c->dimage_last[1] = c->sc_last;
+    c->dimage_last[2] = home_total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)home_total;
+    return rc;
+}
+
+int zpk_codec_dimage_stats(zpk_codec* c, uint32_t out[4])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    out[0] = c->dimage_last[0]; out[1] = c->dimage_last[1]; out[2] = c->dimage_last[2]; out[3] = 0;
+    return ZPK_OK;
+}
+
+// instance-free: [d_src, d_src + bytes) home, when it is that many bytes of one allocation in device memory (span_copy_in_range)
+int zpk_codec_fetch_device(const void* d_src, void* host_dst, uint64_t bytes)
+{
+    if (zpk_codec_device_count() <= 0) return ZPK_E_NO_DEVICE;
+    if (bytes == 0) return ZPK_OK;
+    hipPointerAttribute_t at;
+    if (!d_src || hipPointerGetAttributes(&at, d_src) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_INVALID; }
+    if (at.type != hipMemoryTypeDevice) return ZPK_E_INVALID;
+    int was = -1;
+    if (hipGetDevice(&was) != hipSuccess) { (void)hipGetLastError(); was = -1; }
+    if (was != at.device && hipSetDevice(at.device) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_LAUNCH; }
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    int rc = ZPK_OK;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_src) != hipSuccess) { (void)hipGetLastError(); rc = ZPK_E_INVALID; }
+    else if (!span_copy_in_range((u64)d_src, bytes, (u64)base, size)) rc = ZPK_E_INVALID;
+    else if (host_dst && hipMemcpy(host_dst, d_src, bytes, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = ZPK_E_LAUNCH; }
+    if (was >= 0 && was != at.device) (void)hipSetDevice(was);
     return rc;
 }
 
@@ -2283,6 +2393,7 @@ int zpk_codec_set_option(zpk_codec* c, int option, int value)
     if (option == ZPK_OPT_DEC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->dec_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     if (option == ZPK_OPT_ENC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->enc_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     if (option == ZPK_OPT_STORED_SPAN_MIN) { if (value < 0) return ZPK_E_INVALID; c->stored_span_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
+    if (option == ZPK_OPT_DIMAGE_CHUNK) { if (value < 0) return ZPK_E_INVALID; c->dimage_chunk = (u64)value; return ZPK_OK; }       // (0 = the default: dimage_chunk())
     return ZPK_E_INVALID;
 }
 

@@ -1,10 +1,12 @@
 """Archives read into and written from CUDA tensors: the plaintext stays in device memory, only compressed bytes cross the bus.
 
 A thin ctypes view of the three device-memory calls of libzpack_amd.so (include/zpack_amd.h: zpack_amd_read_files_device,
-zpack_amd_read_files_device_packed, zpack_amd_write_files_device), with torch for the memory.  There is no CPU fallback: without a HIP
-device the calls return ZPACK_ERROR_NOT_AVAILABLE and these functions raise.
+zpack_amd_read_files_device_packed, zpack_amd_write_files_device) and of the reader over an archive image in device memory
+(zpack_amd_init_reader_device), with torch for the memory.  There is no CPU fallback: without a HIP device the calls return
+ZPACK_ERROR_NOT_AVAILABLE and these functions raise.
 
     tensors, statuses = read_files_device("weights.zpk")                  # every entry, in archive order
+    tensors, statuses = read_files_device(image)                          # ... of an archive that lies in a uint8 CUDA tensor
     write_files_device("weights.zpk", {"layer0": t0, "layer1": t1}, method=METHOD_LZ4, level=0)
 
 The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
@@ -63,6 +65,7 @@ def lib():
         R, W, vp, u64 = C.POINTER(Reader), C.POINTER(Writer), C.c_void_p, C.c_uint64
         L.zpack_init_reader.argtypes = [R, C.c_char_p]
         L.zpack_init_reader_memory.argtypes = [R, vp, C.c_size_t]
+        L.zpack_amd_init_reader_device.argtypes = [R, vp, C.c_size_t]
         L.zpack_close_reader.argtypes = [R]
         L.zpack_close_reader.restype = None
         L.zpack_amd_read_files_device.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]
@@ -94,13 +97,21 @@ def _check(rc, what):
 
 
 def read_files_device(archive, names=None, device=0):
-    """`archive`: a path, or the archive's bytes.  `names`: the entries to read, in that order (None: all, in archive order).
+    """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
+    compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
+    in that order (None: all, in archive order).
     Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
     a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
     import torch
     L = lib()
     r = Reader()
-    if isinstance(archive, (str, os.PathLike)):
+    if isinstance(archive, torch.Tensor):
+        if not (archive.is_cuda and archive.dtype == torch.uint8 and archive.dim() == 1 and archive.is_contiguous()):
+            raise ValueError("an archive image in device memory is a contiguous one-dimensional uint8 CUDA tensor")
+        device = archive.device.index
+        _settle(archive.device)                                                     # whatever filled the image has finished
+        _check(L.zpack_amd_init_reader_device(C.byref(r), archive.data_ptr(), archive.numel()), "zpack_amd_init_reader_device")
+    elif isinstance(archive, (str, os.PathLike)):
         _check(L.zpack_init_reader(C.byref(r), os.fsencode(archive)), "zpack_init_reader")
     else:
         raw = bytes(archive)

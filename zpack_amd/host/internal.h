@@ -68,6 +68,18 @@ void zi_ra_step(zi_ctx* ctx, zpack_reader* reader, const zpack_file_entry* entry
 void      zi_reader_gen_new(const zpack_reader* reader);
 void      zi_reader_gen_drop(const zpack_reader* reader);
 zpack_u64 zi_reader_gen(const zpack_reader* reader);
+/* ... and, in the same record, the image of a reader opened by zpack_amd_init_reader_device (zpack_reader has a fixed layout and no field
+ * for it): set -> 1, 0 when there is no memory for the record; get -> the image (*device: its HIP ordinal), NULL for any other reader.
+ * zi_reader_gen_drop forgets it with the record. */
+int         zi_reader_dimage_set(const zpack_reader* reader, const void* d_image, int device);
+const void* zi_reader_dimage(const zpack_reader* reader, int* device);
+
+/* Is a reader loaded, and from where: its FILE, its host image, or an image in device memory (*d_image, *device; both may be NULL).
+ * The side table is only asked when the reader has neither a file nor a buffer. */
+typedef enum { ZI_SRC_NONE = 0, ZI_SRC_FILE, ZI_SRC_MEMORY, ZI_SRC_DEVICE } zi_source;
+zi_source zi_reader_source(const zpack_reader* reader, const zpack_u8** d_image, int* device);
+/* bytes [at, at + n) of a device image brought home (zpk_codec_fetch_device): ZPACK_OK, or ZPACK_ERROR_READ_FAILED */
+int zi_dimage_fetch(const zpack_u8* d_image, zpack_u64 at, zpack_u8* dst, size_t n);
 
 /* per-stream aggregation state hung off zpack_stream.xxh3_state */
 typedef struct zi_stream_state_s {

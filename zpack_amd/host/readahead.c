@@ -54,7 +54,7 @@ typedef struct zi_ra_s {
 /* ------------------------------------------------------------------ reader generations
  * zpack_reader has the reference's fixed layout: the generation of a reader lives in a side table keyed by its address. */
 
-typedef struct zi_gen_s { const zpack_reader* reader; zpack_u64 gen; struct zi_gen_s* next; } zi_gen;
+typedef struct zi_gen_s { const zpack_reader* reader; zpack_u64 gen; const void* d_image; int device; struct zi_gen_s* next; } zi_gen;   /* d_image: zpack_amd_init_reader_device */
 #define ZI_GEN_BUCKETS 64
 static pthread_rwlock_t g_gen_mu = PTHREAD_RWLOCK_INITIALIZER;     /* every zpack_read_file reads it: shared */
 static zi_gen* g_gen[ZI_GEN_BUCKETS];
@@ -91,6 +91,27 @@ zpack_u64 zi_reader_gen(const zpack_reader* reader)
     const zpack_u64 g = *pp ? (*pp)->gen : 0;
     pthread_rwlock_unlock(&g_gen_mu);
     return g;
+}
+
+int zi_reader_dimage_set(const zpack_reader* reader, const void* d_image, int device)
+{
+    pthread_rwlock_wrlock(&g_gen_mu);
+    zi_gen** pp = gen_slot(reader);
+    if (!*pp && (*pp = (zi_gen*)calloc(1, sizeof(zi_gen))) != NULL) (*pp)->reader = reader;
+    if (*pp) { (*pp)->d_image = d_image; (*pp)->device = device; }
+    const int ok = *pp != NULL;
+    pthread_rwlock_unlock(&g_gen_mu);
+    return ok;
+}
+
+const void* zi_reader_dimage(const zpack_reader* reader, int* device)
+{
+    pthread_rwlock_rdlock(&g_gen_mu);
+    zi_gen** pp = gen_slot(reader);
+    const void* p = *pp ? (*pp)->d_image : NULL;
+    if (device) *device = p ? (*pp)->device : -1;
+    pthread_rwlock_unlock(&g_gen_mu);
+    return p;
 }
 
 /* ------------------------------------------------------------------ the window */

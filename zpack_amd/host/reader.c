@@ -217,23 +217,97 @@ static int reader_load_entries(zpack_reader* reader, const zpack_u8* cdr, size_t
     return ZPACK_OK;
 }
 
+/* The parse of an image of reader->file_size bytes (at least ZPACK_MINIMUM_ARCHIVE_SIZE) in two steps, so that an image in device memory
+ * brings home only what each step reads.  The ends: `head` = the header and the data signature behind it, `eocdr` = the last
+ * ZPACK_EOCDR_SIZE bytes -> version, eocdr_offset, cdr_offset ... */
+static int image_parse_ends(zpack_reader* reader, const zpack_u8* head, const zpack_u8* eocdr)
+{
+    int rc;
+    if ((rc = zpack_read_header_memory(head, &reader->version))) return rc;
+    if ((rc = zpack_read_data_header_memory(head + ZPACK_HEADER_SIZE))) return rc;
+    reader->eocdr_offset = reader->file_size - ZPACK_EOCDR_SIZE;
+    if ((rc = zpack_read_eocdr_memory(eocdr, &reader->cdr_offset))) return rc;
+    if (reader->cdr_offset >= reader->file_size) return ZPACK_ERROR_READ_FAILED;
+    return ZPACK_OK;
+}
+
+/* ... and the table: `cdr` = the bytes [cdr_offset, file_size) */
+static int image_parse_table(zpack_reader* reader, const zpack_u8* cdr)
+{
+    const size_t size_left = reader->file_size - (size_t)reader->cdr_offset;
+    if (reader->lz4f_dctx) reader_drop_table(reader);     /* an arena table from an earlier parse of this reader: start over */
+    if (reader->file_entries)                             /* a table the caller put there (public-API parse): keep its contract */
+        return zpack_read_cdr_memory(cdr, size_left, &reader->file_entries, &reader->file_count, &reader->comp_size, &reader->uncomp_size);
+    return reader_load_entries(reader, cdr, size_left);
+}
+
 int zpack_read_archive_memory(zpack_reader* reader)
 {
     zi_reader_gen_new(reader);                            /* no read-ahead window of an earlier parse serves this one */
     if (!reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
     if (reader->file_size < ZPACK_MINIMUM_ARCHIVE_SIZE) return ZPACK_ERROR_FILE_TOO_SMALL;
     const zpack_u8* a = reader->buffer;
+    int rc = image_parse_ends(reader, a, a + reader->file_size - ZPACK_EOCDR_SIZE);
+    return rc ? rc : image_parse_table(reader, a + reader->cdr_offset);
+}
+
+/* ---- zpack_amd.h: a reader over an image in DEVICE memory.  Where the image lives is kept beside the reader (zi_reader_dimage_set: the
+ * record of its generation); the parse above runs on host copies of the bytes it reads — the two ends, then [cdr_offset, file_size). */
+zi_source zi_reader_source(const zpack_reader* reader, const zpack_u8** d_image, int* device)
+{
+    if (d_image) *d_image = NULL;
+    if (device) *device = -1;
+    if (reader->file) return ZI_SRC_FILE;
+    if (reader->buffer) return ZI_SRC_MEMORY;
+    const zpack_u8* p = (const zpack_u8*)zi_reader_dimage(reader, device);
+    if (d_image) *d_image = p;
+    return p ? ZI_SRC_DEVICE : ZI_SRC_NONE;
+}
+
+int zi_dimage_fetch(const zpack_u8* d_image, zpack_u64 at, zpack_u8* dst, size_t n)
+{
+    return zpk_codec_fetch_device(d_image + at, dst, n) == ZPK_OK ? ZPACK_OK : ZPACK_ERROR_READ_FAILED;
+}
+
+static int read_archive_device(zpack_reader* reader, const zpack_u8* d_image)
+{
+    if (reader->file_size < ZPACK_MINIMUM_ARCHIVE_SIZE) return ZPACK_ERROR_FILE_TOO_SMALL;
+    zpack_u8 head[ZPACK_HEADER_SIZE + ZPACK_SIGNATURE_SIZE], eocdr[ZPACK_EOCDR_SIZE];
     int rc;
-    if ((rc = zpack_read_header_memory(a, &reader->version))) return rc;
-    if ((rc = zpack_read_data_header_memory(a + ZPACK_HEADER_SIZE))) return rc;
-    reader->eocdr_offset = reader->file_size - ZPACK_EOCDR_SIZE;
-    if ((rc = zpack_read_eocdr_memory(a + reader->eocdr_offset, &reader->cdr_offset))) return rc;
-    if (reader->cdr_offset >= reader->file_size) return ZPACK_ERROR_READ_FAILED;
-    if (reader->lz4f_dctx) reader_drop_table(reader);     /* an arena table from an earlier parse of this reader: start over */
-    if (reader->file_entries)                             /* a table the caller put there (public-API parse): keep its contract */
-        return zpack_read_cdr_memory(a + reader->cdr_offset, reader->file_size - (size_t)reader->cdr_offset, &reader->file_entries,
-                                     &reader->file_count, &reader->comp_size, &reader->uncomp_size);
-    return reader_load_entries(reader, a + reader->cdr_offset, reader->file_size - (size_t)reader->cdr_offset);
+    if ((rc = zi_dimage_fetch(d_image, 0, head, sizeof(head)))) return rc;
+    if ((rc = zi_dimage_fetch(d_image, reader->file_size - ZPACK_EOCDR_SIZE, eocdr, sizeof(eocdr)))) return rc;
+    if ((rc = image_parse_ends(reader, head, eocdr))) return rc;
+    const size_t size_left = reader->file_size - (size_t)reader->cdr_offset;
+    zpack_u8* cdr = (zpack_u8*)malloc(size_left);
+    if (!cdr) return ZPACK_ERROR_MALLOC_FAILED;
+    if ((rc = zi_dimage_fetch(d_image, reader->cdr_offset, cdr, size_left)) == ZPACK_OK) rc = image_parse_table(reader, cdr);
+    free(cdr);
+    return rc;
+}
+
+int zpack_amd_init_reader_device(zpack_reader* reader, const void* d_image, size_t size)
+{
+    if (!reader || !d_image) return ZPACK_ERROR_STREAM_INVALID;
+    if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
+    /* the whole range is checked against its allocation before a byte is copied; size 0 passes any check and is too small below */
+    const int device = zpk_codec_pointer_device(d_image);
+    if (device < 0 || zpk_codec_fetch_device(d_image, NULL, size) != ZPK_OK) return ZPACK_ERROR_STREAM_INVALID;
+    reader->file_size = size;
+    zi_reader_gen_new(reader);
+    int rc = zi_reader_dimage_set(reader, d_image, device) ? read_archive_device(reader, (const zpack_u8*)d_image) : ZPACK_ERROR_MALLOC_FAILED;
+    if (rc != ZPACK_OK) zi_reader_gen_drop(reader);                                 /* a failed init leaves no record: ARCHIVE_NOT_LOADED from here on */
+    return rc;
+}
+
+int zpack_amd_reader_device_image(const zpack_reader* reader, const void** d_image, int* device)
+{
+    if (!reader) return ZPACK_ERROR_STREAM_INVALID;
+    const zpack_u8* p = NULL;
+    int dev = -1;
+    if (zi_reader_source(reader, &p, &dev) != ZI_SRC_DEVICE) { p = NULL; dev = -1; }
+    if (d_image) *d_image = p;
+    if (device) *device = dev;
+    return ZPACK_OK;
 }
 
 int zpack_read_archive(zpack_reader* reader)
@@ -277,6 +351,8 @@ int zpack_read_raw_file(zpack_reader* reader, zpack_file_entry* entry, zpack_u8*
     const size_t n = (zpack_u64)max_size < entry->comp_size ? max_size : (size_t)entry->comp_size;
     if (reader->file) return read_at(reader->file, entry->offset, buffer, n);
     if (reader->buffer) { memcpy(buffer, reader->buffer + entry->offset, n); return ZPACK_OK; }
+    const zpack_u8* d_image = NULL;
+    if (zi_reader_source(reader, &d_image, NULL) == ZI_SRC_DEVICE) return zi_dimage_fetch(d_image, entry->offset, buffer, n);
     return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
 }
 
@@ -291,7 +367,12 @@ int zpack_read_raw_file_stream(zpack_reader* reader, zpack_file_entry* entry, zp
     const zpack_u64 at = entry->offset + stream->total_in;
     if (reader->file) { int rc = read_at(reader->file, at, stream->next_in, n); if (rc) return rc; }
     else if (reader->buffer) memcpy(stream->next_in, reader->buffer + at, n);
-    else return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
+    else {
+        const zpack_u8* d_image = NULL;
+        if (zi_reader_source(reader, &d_image, NULL) != ZI_SRC_DEVICE) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
+        int rc = zi_dimage_fetch(d_image, at, stream->next_in, n);
+        if (rc) return rc;
+    }
     stream->next_in += n; stream->avail_in -= n; stream->total_in += n;
     *in_size = n;
     return ZPACK_OK;
@@ -349,7 +430,10 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
                           const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int on_device)
 {
     if (count == 0) return ZPACK_OK;
-    if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
+    const zpack_u8* d_image = NULL;
+    int d_device = -1;
+    const zi_source from = zi_reader_source(reader, &d_image, &d_device);
+    if (from == ZI_SRC_NONE) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
     zpk_decode_desc* desc = (zpk_decode_desc*)calloc((size_t)count, sizeof(*desc));
     if (!desc) return ZPACK_ERROR_MALLOC_FAILED;
     const zpack_u8* image = reader->buffer;
@@ -386,9 +470,20 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
         /* entries that the reference would reject with BUFFER_TOO_SMALL before looking at the offset keep
          * that order: the device checks comp_size==0, then max_size, then the offset — same as :328-332 */
     } else {
+        /* a host image or one in device memory: the offset guard (:331) is evaluated against the image as it is */
         for (zpack_u64 i = 0; i < count; i++) fill_desc(&desc[i], entries[i], entries[i]->offset, max_sizes[i]);
     }
-    if (rc == ZPACK_OK && on_device) {
+    if (rc == ZPACK_OK && from == ZI_SRC_DEVICE && !span) {
+        /* the IMAGE in device memory: the compressed bytes stay there — one zpk_codec_decode_batch_dimage call on the codec of the
+         * image's device (no shard), the destinations host pointers or, on_device, device pointers on that device */
+        zpk_codec* codec = NULL;
+        for (int k = 0; k < ctx->n && !codec; k++) if (zpk_codec_device(ctx->dev[k]) == d_device) codec = ctx->dev[k];
+        if (!codec) rc = ZPACK_ERROR_NOT_AVAILABLE;
+        else {
+            const int crc = zpk_codec_decode_batch_dimage(codec, d_image, image_size, desc, count, buffers, on_device, res);
+            if (crc != ZPK_OK) rc = crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
+        }
+    } else if (rc == ZPACK_OK && on_device) {
         zpk_codec* codec = zi_ctx_codec_of(ctx, buffers, sizeof(*buffers), max_sizes, sizeof(*max_sizes), sizeof(size_t) == 8, count, &rc);
         if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: verdicts only) */
         if (codec) {
@@ -422,7 +517,7 @@ static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zp
                       zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int on_device)
 {
     if (count == 0) return ZPACK_OK;
-    if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
+    if (zi_reader_source(reader, NULL, NULL) == ZI_SRC_NONE) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
     /* the caller's context, else this reader's own, created on first use (lib/zpack_read.c:17-31) and freed by zpack_close_reader */
     zi_ctx* ctx = zi_pick_ctx(dctx, &reader->zstd_dctx);
     if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
@@ -448,7 +543,7 @@ int zpack_read_file(zpack_reader* reader, zpack_file_entry* entry, zpack_u8* buf
     }
     if ((zpack_u64)max_size < entry->uncomp_size) return ZPACK_ERROR_BUFFER_TOO_SMALL;
     if (entry->offset + entry->comp_size >= reader->file_size) return ZPACK_ERROR_FILE_OFFSET_INVALID;
-    if (!reader->file && !reader->buffer) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
+    if (zi_reader_source(reader, NULL, NULL) == ZI_SRC_NONE) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
     zi_ctx* ctx = zi_pick_ctx(dctx, &reader->zstd_dctx);
     if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
     /* an in-order caller is answered from the context's read-ahead window when that decode ended ZPACK_OK (readahead.c) */
@@ -525,12 +620,15 @@ static int zi_stream_replay(zpack_reader* reader, const zpack_file_entry* entry,
     zpack_u8* tmp = (zpack_u8*)malloc(piece);
     if (!tmp) return ZPACK_ERROR_MALLOC_FAILED;
     int rc = ZPACK_OK, first = 1;
+    const zpack_u8* d_image = NULL;
+    const zi_source from = zi_reader_source(reader, &d_image, NULL);
     for (zpack_u64 off = 0; (off < upto || first) && rc == ZPACK_OK; ) {
         const size_t n = (size_t)(upto - off < piece ? upto - off : piece);
         const zpack_u64 at = entry->offset + off;
         if (n) {
-            if (reader->file) rc = read_at(reader->file, at, tmp, n);
-            else if (reader->buffer) memcpy(tmp, reader->buffer + at, n);
+            if (from == ZI_SRC_FILE) rc = read_at(reader->file, at, tmp, n);
+            else if (from == ZI_SRC_MEMORY) memcpy(tmp, reader->buffer + at, n);
+            else if (from == ZI_SRC_DEVICE) rc = zi_dimage_fetch(d_image, at, tmp, n);
             else rc = ZPACK_ERROR_ARCHIVE_NOT_LOADED;
         }
         if (rc == ZPACK_OK) rc = zpk_dstream_replay(d, entry->comp_method, entry->comp_size, entry->uncomp_size, entry->hash, tmp, n, first);

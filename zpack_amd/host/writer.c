@@ -255,10 +255,13 @@ int zpack_write_files_from_archive(zpack_writer* writer, zpack_reader* reader, z
     if (!writer->file && !writer->buffer) return ZPACK_ERROR_WRITER_NOT_OPENED;
     zpack_u8* tmp = NULL; size_t tmp_cap = 0;
     int rc = ZPACK_OK;
+    const zi_source from = zi_reader_source(reader, NULL, NULL);
     for (zpack_u64 i = 0; i < file_count && rc == ZPACK_OK; i++) {
         const zpack_file_entry* src = entries + i;
         const zpack_u8* payload = NULL;
-        if (reader->file) {
+        if (from == ZI_SRC_FILE || from == ZI_SRC_DEVICE) {
+            /* (an image in device memory: the guard of the host image below, then the payload comes home through zpack_read_raw_file) */
+            if (from == ZI_SRC_DEVICE && (src->offset >= reader->file_size || src->comp_size > reader->file_size - src->offset)) { rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
             if (src->comp_size > SIZE_MAX) { rc = ZPACK_ERROR_MALLOC_FAILED; break; }
             if (tmp_cap < src->comp_size) {
                 zpack_u8* nb = (zpack_u8*)realloc(tmp, (size_t)src->comp_size);
