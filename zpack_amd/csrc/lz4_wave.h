@@ -76,6 +76,10 @@ static_assert(LZ4W_SEG <= 64u, "the visited-position mask of a segment is one 64
 #define LZ4W_RUNIN LZ4W_SEG                       // bytes of run-in before a segment's speculative walk
 #endif
 
+#ifndef LZ4W_FIX_CONT
+#define LZ4W_FIX_CONT 1                           // developer A/B: 0 = fix-up rounds without the one-successor continuation
+#endif
+
 #ifndef LZ4W_SPLIT_FIRST
 #define LZ4W_SPLIT_FIRST 0
 #endif
@@ -205,16 +209,14 @@ __device__ __forceinline__ Lz4Walk lz4_walk(const Lz4Bytes& B, bool on, u32 from
     const lds_cp8 base = B.S + (seg_start - B.cbase);
     const bool start_in = on && (i32)(from - seg_start) < seg_len;
     i32 rp = start_in ? (i32)(from - seg_start) : seg_len;
-    bool live = start_in, merged = false;
+    bool live = start_in;
     u32 flags = 0, exit_far = from, far = on && !start_in ? 1u : 0u;
     u64 m = 0;
     for (;;) {
         live = live && rp < seg_len;
         const bool inseg = FIRST ? rp >= 0 : true;
         if (!FIRST) {                                               // (a first walk has nothing to merge with)
-            const bool hit = live && ((u32)(old.m >> (rp & 63)) & 1u);
-            merged = merged || hit;
-            live = live && !hit;
+            live = live && !((u32)(old.m >> (rp & 63)) & 1u);         // a hit ends the walk where it stands: before seg_len
         }
         if (__builtin_amdgcn_ballot_w64(live) == 0) break;
         SEQ_STAT(if (FIRST) stt.hops_first++; else stt.hops_fix++);
@@ -239,7 +241,9 @@ __device__ __forceinline__ Lz4Walk lz4_walk(const Lz4Bytes& B, bool on, u32 from
         rp = live ? nx : rp;
     }
     Lz4Walk w; w.m = m; w.flags = flags; w.exit = far ? exit_far : seg_start + (u32)rp;
-    if (merged) {
+    // merged: a re-walk that stopped before seg_len stopped on a visited position (one that did not start has rp == seg_len).  Derived here,
+    // not carried through the loop: one scalar instruction less per iteration and a mask less in scalar registers across it
+    if (!FIRST && rp < seg_len) {
         const u64 tail = old.m & ~((1ull << (rp & 63)) - 1);
         w.m |= tail;
         w.flags |= old.flags;
@@ -301,6 +305,75 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
         // lane 0 starts on the true chain, the others speculate from inside the previous lane's segment
         w = lz4_walk<true>(B, active, lane == 0 ? my_start : (my_start - cpos > LZ4W_RUNIN ? my_start - LZ4W_RUNIN : cpos), my_start, my_end, C, w, my_entry, stt);
         SEQ_STAT({ u64 t2 = SEQ_T(); stt.t_walk1 += t2 - ts; ts = t2; });
+#if LZ4W_FIX_CONT
+        // Fix-up rounds with the ONE-SUCCESSOR CONTINUATION.  A round is one or two steps through the same walk: (1) every lane whose
+        // predecessor's exit changed re-walks its own segment from there; (2) a lane whose re-walk gave it a NEW exit inside the next
+        // lane's segment goes on through that segment, against the successor's record as of the round's start, and hands the result
+        // over: a merge gives visits + the successor's tail, exit and flags, no merge gives the visits and where the walk stands —
+        // what lz4_walk returns either way.  The hand-over replaces the successor's record and entry (it wins over the successor's own
+        // re-walk of this round, which started from the exit that has just changed), so the successor does not cost a further round.
+        // An exit behind the successor's segment does not continue, nor does the chunk's last active lane (no segment follows).  The
+        // lowest wrong lane has a right predecessor, nobody hands it anything, its own walk makes it right: every round fixes a lane,
+        // as before.  Step 2 is skipped when no lane continues (uniform).  ONE call site: one instance of the loop.
+        // The records travel between lanes through the token list's LDS (not in use before the walks are done), 16 bytes per lane:
+        // every lane's record as of the round's start, read by its predecessor in step 2; in step 2 every lane parks its own new
+        // record there, a continuing lane overwrites its successor's, and every lane takes back what its slot then holds.  (The LDS
+        // operations of one wave complete in order.)  So no record is held in registers across a walk but the one walked against.
+        {
+            static_assert(sizeof(sh.rec) >= 16 * (WAVE + 1), "65 records of 16 bytes (lane 63 reads a slot nobody uses)");
+            const lds_p8 slot = to_lds_rw((u8*)sh.rec) + 16u * (u32)lane;
+            const auto pack = [](const Lz4Walk& a) { u128 v; v.lo = a.m; v.hi = ((u64)a.flags << 32) | a.exit; return v; };
+            const auto unpack = [](const u128& v) { Lz4Walk a; a.m = v.lo; a.exit = (u32)v.hi; a.flags = (u32)(v.hi >> 32); return a; };
+            // lane 0 is on the true chain and never walks again, nobody hands it a record, and the shuffle below gives it its own exit:
+            // with that as its entry it is never `on`, without a select in the loop
+            if (lane == 0) my_entry = w.exit;
+            // iter counts steps: even = a round's own re-walks, odd = its continuations; `on` = the lanes that walk in this step
+            bool on = false;
+            for (int iter = 0; iter < 2 * 66;) {
+                const bool step2 = iter & 1;
+                // the segment walked: the lane's own, or the next one (a lane that continues has a whole segment).  Segments end at
+                // tok_end = min(C, cpos + LZ4W_CHUNK); cut at C alone they are the same for every lane but 63 in step 2, which never
+                // continues (its exit is not inside the chunk), and tok_end need not stay in a register
+                const u32 s0 = my_start + (step2 ? LZ4W_SEG : 0u);
+                const u32 s1 = s0 + LZ4W_SEG < C ? s0 + LZ4W_SEG : C;
+                const u32 next_end = s1 + LZ4W_SEG < C ? s1 + LZ4W_SEG : C;
+                u32 from; Lz4Walk old;
+                wave_mem_fence();
+                if (!step2) {
+                    SEQ_STAT(stt.fix_iters++);
+                    from = (u32)__shfl_up((int)w.exit, 1, 64);                        // >= my_start: a predecessor's exit (lane 0: its own)
+                    on = active && from != my_entry;
+                    if (__ballot(on) == 0) break;
+                    old = w;
+                    lds_st128(slot, pack(w));
+                } else {
+                    from = w.exit;
+                    old = unpack(lds_ld128(slot + 16));
+                    wave_mem_fence();
+                    lds_st128(slot, pack(w));
+                }
+                wave_mem_fence();
+                u32 unused;
+                const Lz4Walk r = lz4_walk<false>(B, on, from, s0, s1, C, old, unused, stt);
+                if (!step2) {
+                    my_entry = on ? from : my_entry;
+                    // continues: a NEW exit (the old one left the successor's entry right) inside the successor's segment
+                    on = on && r.exit != w.exit && r.exit < next_end && r.exit - cpos < LZ4W_CHUNK;
+                    w = r;
+                    iter += __ballot(on) != 0 ? 1 : 2;
+                } else {
+                    const u32 hn = (u32)__shfl_up((int)from, 1, 64);                  // the entry of a record handed over: the predecessor's exit
+                    const bool got = ((__ballot(on) << 1) >> lane) & 1;
+                    wave_mem_fence();
+                    if (on) lds_st128(slot + 16, pack(r));
+                    wave_mem_fence();
+                    w = unpack(lds_ld128(slot));
+                    my_entry = got ? hn : my_entry;
+                    iter++;
+                }
+            }
+        }
+#else
         for (int iter = 0; iter < 66; iter++) {
             SEQ_STAT(stt.fix_iters++);
             u32 e = (u32)__shfl_up((int)w.exit, 1, 64);
@@ -311,6 +384,7 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
             w = lz4_walk<false>(B, changed, e, my_start, my_end, C, w, unused, stt);       // e >= my_start: a predecessor's exit
             my_entry = changed ? e : my_entry;
         }
+#endif
         SEQ_STAT({ u64 t2 = SEQ_T(); stt.t_fix += t2 - ts; ts = t2; });
         // inactive lanes forward the chain position
         if (!active) { w.exit = (u32)__shfl((int)w.exit, 63, 64); }
@@ -330,6 +404,11 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
         // Every segment lists the token positions of its sequences (chunk-relative, 16 bit) at their sequence
         // numbers in LDS — a short loop over the set bits of its mask — so that a batch lane finds its token with
         // one ds_read.  The list holds LZ4W_NREC entries; a chunk with more sequences is listed in windows.
+        // (the batch loop's own copy of the block pointer: a short live range that stays in scalar registers through the loop, whatever
+        // becomes of `ip` across the walks above)
+        const u8* ipb = ip;
+        asm volatile("" : "+s"(ipb));
+        Lz4Bytes Bb = B; Bb.g = ipb;
         ZPK_LDS u16* const rec = (ZPK_LDS u16*)sh.rec;
         // (LZ4W_SPLIT_FIRST, developer A/B: a chunk's first 64 sequences go as two batches of 32, so that the second half finds the
         // room the whole batch does not — measured and left off, profiles/r12)
@@ -356,24 +435,24 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
             }
             const int cnt = (int)(nseq - b0 < bstep ? nseq - b0 : bstep);
             const u64 tq0 = SEQ_T(); (void)tq0;
-            SeqBatch q; q.lit = ip; q.lit_lds = SEQ_NO_LDS; q.ll = 0; q.ml = 0; q.off = 1; q.bad = 0;
+            SeqBatch q; q.lit = ipb; q.lit_lds = SEQ_NO_LDS; q.ll = 0; q.ml = 0; q.off = 1; q.bad = 0;
             u32 tok_pos = cpos;
             if (lane < cnt) {
                 const u32 p = cpos + (u32)rec[bw + (u32)lane];
                 tok_pos = p;
                 const Lz4Quick t = lz4_quick(B.S, B.cbase, p, lim);
                 if (!t.slow) {                                                               // straight-line common case
-                    q.lit = ip + t.lit_pos; q.ll = t.lit; q.ml = t.ml; q.off = t.off;
+                    q.lit = ipb + t.lit_pos; q.ll = t.lit; q.ml = t.ml; q.off = t.off;
                 } else {
-                    const Lz4Tok tt = lz4_token_at(B, p, C, true);
-                    q.lit = ip + tt.lit_pos; q.ll = tt.lit; q.ml = tt.ml; q.off = tt.off;
+                    const Lz4Tok tt = lz4_token_at(Bb, p, C, true);
+                    q.lit = ipb + tt.lit_pos; q.ll = tt.lit; q.ml = tt.ml; q.off = tt.off;
                     if (tt.flags & 1) q.bad = (tt.flags & 4) ? 2u : 1u;
                 }
                 // (a block holds at most 4 MiB of output: longer lengths only have to stay longer than that, and 64 of them
                 // must not wrap the 32-bit prefix sums)
                 if (q.ll > (1u << 23)) q.ll = 1u << 23;            // 64 x 2 x 2^23 = 2^30: the executor's 32-bit arithmetic holds
                 if (q.ml > (1u << 23)) q.ml = 1u << 23;
-                const u32 lp = (u32)(q.lit - ip);                                      // literals that sit in the staged chunk
+                const u32 lp = (u32)(q.lit - ipb);                                      // literals that sit in the staged chunk
                 if (q.ll <= SEQ_OWN_MAX && lp + q.ll <= B.cend) q.lit_lds = lp - B.cbase;
             }
             SEQ_STAT({ u64 t2 = SEQ_T(); stt.t_parse += t2 - tq0; stt.t_tok += t2 - tq0; });
@@ -404,7 +483,7 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
                 dead = (u32)__builtin_amdgcn_readfirstlane((int)(nxt > own ? nxt : own));
             }
             int rc;
-            if constexpr (EMIT) { (void)dead; rc = emit(q, cnt, (u32)(q.lit - ip)); }
+            if constexpr (EMIT) { (void)dead; rc = emit(q, cnt, (u32)(q.lit - ipb)); }
             else rc = seq_exec_batch<true, COOP, SEQ_ASM_LONG_LIT != 0>(q, cnt, op, oend, dst_lo, -1, lane, stt, B.S, to_lds_rw(sh.stage), dead);
             if (rc != D_OK) { op_io = op; return rc; }
         }
