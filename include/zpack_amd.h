@@ -25,7 +25,8 @@ ZPACK_EXPORT int zpack_amd_read_ahead_stats(const zpack_reader* reader, void* dc
  *
  * Call model.  Synchronous: a call returns when the buffers hold the plaintext / the archive holds the entries.  `entries`, `results`,
  *   `max_sizes`, `out_offsets` and the zpack_file array (its filenames and options) are host memory; the reader is memory-backed,
- *   file-backed or over an image in device memory (zpack_amd_init_reader_device, below) and the writer heap- or file-backed.
+ *   file-backed or over an image in device memory (zpack_amd_init_reader_device, below) and the writer heap- or file-backed or over an image in device memory
+ *   (zpack_amd_init_writer_device, further below).
  * results[i], the bytes, last_return.  results[i] and the bytes in d_buffers[i] are what zpack_read_files gives for the same arguments
  *   with host buffers; reader->last_return is set by the same rule (the last entry's, or the last failing one's).  One bad entry does
  *   not stop the others.
@@ -92,6 +93,47 @@ ZPACK_EXPORT int zpack_amd_write_files_device(zpack_writer* writer, zpack_file* 
 ZPACK_EXPORT int zpack_amd_init_reader_device(zpack_reader* reader, const void* d_image, size_t size);
 /* *d_image / *device of a reader opened by the call above (NULL / -1 for any other reader). */
 ZPACK_EXPORT int zpack_amd_reader_device_image(const zpack_reader* reader, const void** d_image, int* device);
+
+/* ---- a WRITER whose sink is an archive image in DEVICE memory ----------------------------------------------------------------------
+ * A third kind of writer beside the heap- and the file-backed one: the archive is written where it will be used — a checkpoint or data
+ * set kept compressed beside the model, an image about to leave by a device-to-device transfer — and its compressed bytes never cross
+ * the bus.  With zpack_amd_init_reader_device the loop closes: written on the device, read on the device; only descriptors, results and
+ * the small host-built blocks (header, data signature, CDR, EOCDR) touch the host.
+ *
+ * After a successful init.  buffer == NULL and file == NULL; buffer_capacity holds `capacity`.  Where the image lives is kept beside the
+ *   writer (zpack_writer has the reference's fixed layout), zpack_amd_writer_device_image tells.  The image is BORROWED: the caller keeps
+ *   it alive until zpack_close_writer, which frees the entry table and the writer's context, drops the record and leaves the image
+ *   alone.  The sink does NOT grow.  A writer that was never opened still answers ZPACK_ERROR_WRITER_NOT_OPENED.
+ * Return codes of the init.  A NULL writer or d_image is ZPACK_ERROR_STREAM_INVALID.  No HIP device: ZPACK_ERROR_NOT_AVAILABLE.  A
+ *   pointer that is not device memory, or a range [d_image, d_image + capacity) that leaves its allocation, is
+ *   ZPACK_ERROR_STREAM_INVALID, checked on the host; nothing is touched.
+ * Which write calls work, and their results.  zpack_write_header[_ex], zpack_write_data_header, zpack_write_files, zpack_write_file,
+ *   zpack_amd_write_files_device, zpack_write_files_from_archive, zpack_write_file_stream and _end, zpack_write_cdr[_ex],
+ *   zpack_write_eocdr[_ex], zpack_write_archive.  After any sequence of calls the bytes [0, write_offset) of the image are the bytes of
+ *   a heap writer's buffer after the same calls, and file_entries (names, offsets, sizes, hashes, methods), file_count, write_offset,
+ *   file_size, cdr_offset, eocdr_offset, every return value and last_return are equal too.  Bytes in [write_offset, capacity) are
+ *   unspecified; nothing outside [d_image, d_image + capacity) is ever written.
+ * A full sink.  The reference's loop appends the files in front of the first failing one and stops (lib/zpack_write.c:299-303); a file
+ *   that does not fit what is left of the image is treated the same way: the files in front of it are appended and entered, the call
+ *   returns ZPACK_ERROR_BUFFER_TOO_SMALL and last_return is that file's comp_size.  A fixed block — header, data signature, CDR, EOCDR,
+ *   an entry of a raw copy, a stream window — that does not fit writes nothing and returns ZPACK_ERROR_BUFFER_TOO_SMALL; the offsets do
+ *   not move.
+ * How a batch gets there.  zpack_write_files and zpack_amd_write_files_device make ONE codec call: the frames are compressed into the
+ *   codec's staging (large entries in pieces, assembled on the device) and committed to the image by two kernels under the rule above;
+ *   results and the cut come home, no compressed byte does.  zpack_write_files_from_archive from a reader over a device image on the
+ *   same device is one copy kernel; from any other reader the payloads are fetched or read, then stored.
+ * Which device.  The image's device must be one of the context's (the files' common cctx, else the writer's own: ZPACK_AMD_DEVICES),
+ *   else ZPACK_ERROR_NOT_AVAILABLE; device plaintext (zpack_amd_write_files_device) on another device than the image is
+ *   ZPACK_ERROR_STREAM_INVALID, and so is device memory handed to zpack_write_files as a host buffer: nothing is written.  The batch runs
+ *   on the image's device's codec alone, with no shard.
+ * Stream ordering.  Synchronous, like the other device calls: when a call returns, the image holds the bytes.  The caller's earlier work
+ *   on the image and on device plaintext must have completed. */
+
+/* A writer whose sink is [d_image, d_image + capacity) on one HIP device.  BORROWED: the caller keeps it alive until
+ * zpack_close_writer, which does not free it.  The sink does not grow. */
+ZPACK_EXPORT int zpack_amd_init_writer_device(zpack_writer* writer, void* d_image, size_t capacity);
+/* *d_image / *capacity / *device of such a writer (NULL / 0 / -1 for any other writer). */
+ZPACK_EXPORT int zpack_amd_writer_device_image(const zpack_writer* writer, void** d_image, size_t* capacity, int* device);
 
 #ifdef __cplusplus
 }

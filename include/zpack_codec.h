@@ -51,7 +51,9 @@ extern "C" {
                                         zpk_codec_packed_stride: the host-pointer paths with the PLAINTEXT in the caller's device memory, and the kernel that moves it;
                                         decode_stats2 out[14], out[15], which read 0: sub-batches through the host path's pipeline / k_span_copy launches.
                                         zpk_codec_fetch_device, zpk_codec_decode_batch_dimage, ZPK_OPT_DIMAGE_CHUNK, zpk_codec_dimage_stats: the host-pointer paths
-                                        with the ARCHIVE IMAGE in the caller's device memory.) */
+                                        with the ARCHIVE IMAGE in the caller's device memory.
+                                        zpk_codec_store_device, zpk_codec_encode_batch_dsink, zpk_codec_dsink_stats, zpk_codec_stream_sync: a batch compressed into a bounded SINK in the
+                                        caller's device memory.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -148,8 +150,9 @@ int         zpk_codec_device(const zpk_codec* c);
  *                                   whole chip — one wave per 64 KiB, then one short chain per entry — instead of by one wave; anything
  *                                   else, and any entry that fails a guard, goes through the one-wave kernels (verdicts other than OK /
  *                                   hash mismatch come from there only).  Default 256 KiB; the least size taken is 1025; 0 = never.
- *   ZPK_OPT_DIMAGE_CHUNK            zpk_codec_decode_batch_dimage: bytes of staging slots per sub-batch (an entry whose slot is larger goes
- *                                   alone).  0 = the default, ZPK_HOST_CHUNK_BYTES (4 GiB): what zpk_codec_decode_batch_host cuts by. */
+ *   ZPK_OPT_DIMAGE_CHUNK            zpk_codec_decode_batch_dimage, zpk_codec_encode_batch_dsink: bytes of staging slots per sub-batch (an entry
+ *                                   whose slot is larger goes alone).  0 = the default, ZPK_HOST_CHUNK_BYTES (4 GiB): what
+ *                                   zpk_codec_decode_batch_host cuts by. */
 /* (2..5 were the opt-in two-stage LZ4 path of round 4 and its measurement aids: measured slower than the one-kernel decoder, removed in round 5) */
 enum { ZPK_OPT_ENC_SPLIT_MIN = 6, ZPK_OPT_DEC_SPLIT_MIN = 7, ZPK_OPT_ORDER_MIN = 8, ZPK_OPT_ORDER_FAST_LAST = 9 /* a batch of ONE size class runs the entries that did not compress (a copy to decode) last: 1 (default) / 0 */ };
 #define ZPK_OPT_STORED_SPAN_MIN 10
@@ -278,6 +281,42 @@ int zpk_codec_encode_batch_host(zpk_codec* c, const uint8_t* const* src_ptrs,
 int zpk_codec_encode_batch_dsrc(zpk_codec* c, const uint8_t* const* d_src_ptrs,
                                 const zpk_encode_desc* desc, uint64_t n,
                                 uint8_t* const* dst_ptrs, zpk_encode_result* results);
+
+/* ---- a bounded SINK in the caller's device memory -------------------------------------------------------
+ * instance-free, the mirror of zpk_codec_fetch_device: copies [host_src, host_src + bytes) to d_dst, synchronously.  ZPK_E_INVALID when
+ * d_dst is not `bytes` bytes of one allocation in device memory (checked first, nothing copied); ZPK_E_NO_DEVICE without a runtime.
+ * host_src NULL: the check alone.  bytes 0: ZPK_OK wherever the pointers point. */
+int zpk_codec_store_device(void* d_dst, const void* host_src, uint64_t bytes);
+
+/* zpk_codec_encode_batch_host / _dsrc whose payloads go, back to back in the order given, to [d_sink, d_sink + sink_room) in DEVICE
+ * memory on the codec's device — under the append rule of the reference's loop (lib/zpack_write.c:299-303: the files in front of the
+ * first failing one are appended), with "does not fit" as one more way to stop.  src_ptrs is a HOST array of n host pointers
+ * (src_on_device == 0) or n device pointers on the codec's device (1); desc, results, placed and bytes are host memory; synchronous: when
+ * the call returns the sink holds the bytes.  desc[i].src_offset and .dst_offset are ignored; desc[i].dst_capacity bounds entry i's frame
+ * as in the host calls.
+ * The sources are staged as those calls stage them (the upload, or ONE k_span_copy), the batch is cut into sub-batches by the bytes of its
+ * staging slots (ZPK_OPT_DIMAGE_CHUNK), each sub-batch is encoded into slots of the codec's by the body of zpk_codec_encode_big_device
+ * (large entries in pieces, their frame assembled on the device), scanned (offsets = the prefix sums of the sizes of the entries with
+ * status 0) and committed by two kernels: k_sink_cut finds f, the first entry with status != 0 or offsets[f + 1] > room, and
+ * k_sink_place — a persistent grid over (entry, 16 KiB span) items whose count it reads from the device — copies the payloads of [0, f)
+ * to d_sink + offsets[i].  NOTHING is stored at or behind d_sink + offsets[f].  A later sub-batch lands behind the one before it; a cut
+ * short of a sub-batch's entries ends the call.
+ * *placed = the entries committed, in order from entry 0; *bytes = what they take; entry i of them lies at the sum of the comp_size of
+ * those before it.  results[i] for i <= *placed (i < n) is byte for byte zpk_codec_encode_batch_host's, and so are the frames; entry
+ * *placed, when there is one, is the one that stopped the call: by its status, else because its comp_size did not fit.  results behind
+ * it are unspecified.  The only bytes that come home are [results | the cut], one copy per sub-batch.
+ * POINTER CHECK, on the host before anything is enqueued: [d_sink, + sink_room) and, with device sources, every [src_ptrs[i], + size)
+ * pass the check of zpk_codec_decode_batch_host_dptr; a host source with bytes must not be NULL or device memory.  Else ZPK_E_INVALID and
+ * nothing has run. */
+int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device,
+                                 const zpk_encode_desc* desc, uint64_t n,
+                                 uint8_t* d_sink, uint64_t sink_room,
+                                 zpk_encode_result* results, uint64_t* placed, uint64_t* bytes);
+/* the most recent such call: out[0] sub-batches, out[1] workgroups of its last k_sink_place launch, out[2] = out[3] = 0.  With profiling
+ * on, zpk_codec_kernel_ms(ZPK_K_PACK) is the last k_sink_place's time. */
+int zpk_codec_dsink_stats(zpk_codec* c, uint32_t out[4]);
+/* returns when everything enqueued on the codec's own stream has run (zpk_codec_copy_spans_device with stream NULL enqueues there) */
+int zpk_codec_stream_sync(zpk_codec* c);
 
 /* zpk_codec_encode_batch_device for batches that hold LARGE entries: d_src, d_dst and d_results are DEVICE pointers, `desc` is HOST memory
  * (consumed before the call returns).  An entry with size >= ZPK_OPT_ENC_SPLIT_MIN, size > 512 KiB and a valid method is compressed as

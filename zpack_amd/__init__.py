@@ -298,6 +298,36 @@ class Codec:
         self._chk(self.L.zpk_codec_dimage_stats(self.h, a), "zpk_codec_dimage_stats")
         return dict(sub_batches=a[0], span_copy_launches=a[1], bytes_copied_home=a[2])
 
+    # ---- a bounded SINK in the caller's device memory (a uint8 CUDA tensor; sources host arrays or device addresses; the tables host memory) ----
+    def encode_batch_dsink(self, srcs, desc, sink, sink_offset=0, room=None, src_on_device=False):
+        """encode_batch_host / _dsrc whose payloads are committed back to back to sink[sink_offset, sink_offset + room) under the append
+        rule (zpack_codec.h): srcs[i] is a np.uint8 array (host) or a device address (src_on_device) of desc[i].size bytes.  Returns
+        (results, placed, bytes).  Raises on ZPK_E_INVALID (a pointer the check turned down: nothing has run)."""
+        self._settle(None)
+        desc = np.ascontiguousarray(desc, dtype=ENCODE_DESC)
+        n = len(desc)
+        if src_on_device:
+            ptrs = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in srcs])
+        else:
+            keep = [np.ascontiguousarray(a, dtype=np.uint8) for a in srcs]
+            ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in keep])
+        if room is None:
+            room = sink.numel() - sink_offset
+        res = np.zeros(n, dtype=ENCODE_RESULT)
+        placed, nbytes = C.c_uint64(0), C.c_uint64(0)
+        self.L.zpk_codec_encode_batch_dsink.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self._chk(self.L.zpk_codec_encode_batch_dsink(self.h, ptrs, 1 if src_on_device else 0, desc.ctypes.data, n, sink.data_ptr() + sink_offset, room,
+                                                      res.ctypes.data, C.byref(placed), C.byref(nbytes)), "zpk_codec_encode_batch_dsink")
+        return res, placed.value, nbytes.value
+
+    def dsink_stats(self):
+        """The last encode_batch_dsink call: its sub-batches (OPT_DIMAGE_CHUNK) and the workgroups of its last k_sink_place launch."""
+        a = (C.c_uint32 * 4)()
+        self.L.zpk_codec_dsink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        self._chk(self.L.zpk_codec_dsink_stats(self.h, a), "zpk_codec_dsink_stats")
+        return dict(sub_batches=a[0], place_groups=a[1])
+
     def copy_spans_device(self, rows, stream=None):
         """rows: (n, 3) uint64 array of (src address, dst address, len): one k_span_copy launch, asynchronous on `stream` (None: the
         codec's own; synchronise the device before reading the destinations)."""

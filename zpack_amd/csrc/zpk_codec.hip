@@ -47,6 +47,7 @@
 // kernel at the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
 namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
 #include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
+#include "dsink_plan.h"                          // a batch compressed into a bounded sink in DEVICE memory: the cut, the span table, room and chaining, the staging (plain C++, likewise); the kernels: sink_commit.hip
 #include "stream_plan.h"                        // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
 
 using namespace zpk;
@@ -707,9 +708,15 @@ struct zpk_codec {
     // zpk_codec_decode_batch_dimage call, its sub-batches, k_span_copy launches and the bytes it copied home (saturating)
     u64   dimage_chunk = 0;
     u32   dimage_last[3] = {0, 0, 0};
-    DevBufBase* const bufs[26] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_bigwalk, &d_sspan, &d_sc,
+    // a sink in the caller's device memory (dsink_plan.h / sink_commit.h): the slots a sub-batch is encoded into — c->d_dst holds the pieces
+    // of its large entries meanwhile —, the commit's tables (results | cut record | offsets | slot offsets), the resident workgroups of
+    // k_sink_place (0: not asked yet) and, of the most recent zpk_codec_encode_batch_dsink call, its sub-batches and the last grid
+    DevBuf<u8> d_sink_slots, d_sink_tab;
+    u32   sink_groups = 0;
+    u32   dsink_last[2] = {0, 0};
+    DevBufBase* const bufs[28] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_bigwalk, &d_sspan, &d_sc,
                                    &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
-                                   &d_xpart, &d_zarena, &d_zstate };
+                                   &d_xpart, &d_zarena, &d_zstate, &d_sink_slots, &d_sink_tab };
     PinBuf* const pins[6] = { &h_bigsrc, &h_bigwalk, &h_sspan, &h_bigenc[0], &h_bigenc[1], &h_sc };
 };
 
@@ -826,7 +833,7 @@ void zpk_codec_reset(zpk_codec* c)
     // a context keeps its grown staging between batches (the next batch of that size starts at once); a reset gives the large pieces
     // back — a process that holds many readers can bound what each one retains (zpack_reset_reader_dctx / zpack_reset_writer_cctx)
     const u64 keep = 64ull << 20;
-    for (DevBufBase* b : { (DevBufBase*)&c->d_src, (DevBufBase*)&c->d_dst, (DevBufBase*)&c->d_zarena, (DevBufBase*)&c->d_lit }) if (b->cap > keep) release(*b);
+    for (DevBufBase* b : { (DevBufBase*)&c->d_src, (DevBufBase*)&c->d_dst, (DevBufBase*)&c->d_zarena, (DevBufBase*)&c->d_lit, (DevBufBase*)&c->d_sink_slots }) if (b->cap > keep) release(*b);
 }
 const char* zpk_codec_last_error(const zpk_codec* c) { return c ? c->err : "no codec"; }
 int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
@@ -2436,4 +2443,5 @@ int zpk_codec_timer_stop(zpk_codec* c, void* stream, float* elapsed_ms)
 }  // extern "C"
 
 #include "zpk_encode.inc"
+#include "zpk_dsink.inc"
 #include "zpk_stream.inc"

@@ -1,13 +1,14 @@
 """Archives read into and written from CUDA tensors: the plaintext stays in device memory, only compressed bytes cross the bus.
 
 A thin ctypes view of the three device-memory calls of libzpack_amd.so (include/zpack_amd.h: zpack_amd_read_files_device,
-zpack_amd_read_files_device_packed, zpack_amd_write_files_device) and of the reader over an archive image in device memory
-(zpack_amd_init_reader_device), with torch for the memory.  There is no CPU fallback: without a HIP device the calls return
+zpack_amd_read_files_device_packed, zpack_amd_write_files_device), of the reader over an archive image in device memory
+(zpack_amd_init_reader_device) and of the writer whose sink is one (zpack_amd_init_writer_device), with torch for the memory.  There is no CPU fallback: without a HIP device the calls return
 ZPACK_ERROR_NOT_AVAILABLE and these functions raise.
 
     tensors, statuses = read_files_device("weights.zpk")                  # every entry, in archive order
     tensors, statuses = read_files_device(image)                          # ... of an archive that lies in a uint8 CUDA tensor
     write_files_device("weights.zpk", {"layer0": t0, "layer1": t1}, method=METHOD_LZ4, level=0)
+    image = write_archive_device({"layer0": t0, "layer1": t1})            # the archive as a uint8 CUDA tensor: no compressed byte crosses the bus
 
 The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
 are ZPACK_ERROR_NOT_AVAILABLE.
@@ -72,6 +73,7 @@ def lib():
         L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
         L.zpack_init_writer.argtypes = [W, C.c_char_p]
         L.zpack_init_writer_heap.argtypes = [W, C.c_size_t]
+        L.zpack_amd_init_writer_device.argtypes = [W, vp, C.c_size_t]
         L.zpack_write_header.argtypes = [W]
         L.zpack_write_data_header.argtypes = [W]
         L.zpack_amd_write_files_device.argtypes = [W, C.POINTER(File), u64]
@@ -174,6 +176,57 @@ def write_files_device(path, tensors, method=METHOD_LZ4, level=0):
         if path is None:
             return C.string_at(w.buffer, w.file_size)
         return None
+    finally:
+        L.zpack_close_writer(C.byref(w))
+
+
+def archive_capacity(sizes, names, method):
+    """Bytes that hold any archive of entries of `sizes` bytes named `names`, compressed with `method`: header (6) and data signature (4),
+    the compress bounds, the CDR (20 + 35 + the name's length per entry) and the EOCDR (12)."""
+    from . import lib as codec_lib
+    bound = codec_lib().zpk_codec_compress_bound
+    return 10 + sum(int(bound(int(method), int(s))) for s in sizes) + 20 + sum(35 + len(n.encode()) for n in names) + 12
+
+
+def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None):
+    """Writes an archive with one entry per item of `tensors` ({name: CUDA tensor}, all on one device) INTO DEVICE MEMORY
+    (zpack_amd_init_writer_device): header, files, CDR and EOCDR go into a fresh uint8 tensor of `capacity` bytes on the tensors' device
+    (None: archive_capacity, which holds whatever the entries compress to), the frames are committed there by the codec's kernels and no
+    compressed byte crosses the bus.  Returns the tensor trimmed to the archive's size; it is byte for byte what write_files_device
+    returns for path None.  A capacity that is too small raises (ZPACK_ERROR_BUFFER_TOO_SMALL, 12).
+
+        image = write_archive_device({"a": ta, "b": tb}, method=METHOD_ZSTD, level=1)
+        tensors, statuses = read_files_device(image)                      # zpack_amd_init_reader_device: read where it was written
+    """
+    import torch
+    L = lib()
+    items = list(tensors.items())
+    flat = [t.contiguous().reshape(-1).view(dtype=_u8()) for _, t in items]
+    for t in flat:
+        if not t.is_cuda:
+            raise ValueError("write_archive_device takes CUDA tensors")
+    dev = flat[0].device if flat else torch.device("cuda", 0)
+    if capacity is None:
+        capacity = archive_capacity([t.numel() for t in flat], [name for name, _ in items], method)
+    image = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=dev)
+    w = Writer()
+    _settle(dev)
+    _check(L.zpack_amd_init_writer_device(C.byref(w), image.data_ptr(), int(capacity)), "zpack_amd_init_writer_device")
+    try:
+        opts = CompressOptions(int(method), int(level))
+        arr = (File * max(len(items), 1))()
+        for i, ((name, _), t) in enumerate(zip(items, flat)):
+            arr[i].filename = name.encode()
+            arr[i].buffer = t.data_ptr() if t.numel() else None
+            arr[i].size = t.numel()
+            arr[i].options = C.pointer(opts)
+            arr[i].cctx = None
+        _check(L.zpack_write_header(C.byref(w)), "zpack_write_header")
+        _check(L.zpack_write_data_header(C.byref(w)), "zpack_write_data_header")
+        _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
+        _check(L.zpack_write_cdr(C.byref(w)), "zpack_write_cdr")
+        _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
+        return image[:int(w.file_size)]
     finally:
         L.zpack_close_writer(C.byref(w))
 

@@ -89,7 +89,19 @@ typedef struct zi_stream_state_s {
     zpack_u64    entry_offset;       /* streaming write: archive offset of the entry being written */
 } zi_stream_state;
 
-/* the writer's unified sink: file or growing heap buffer, at the writer's cursor */
+/* Is a writer opened, and on what: its FILE, its growing heap buffer, or a bounded image in device memory (zpack_amd_init_writer_device:
+ * *d_image, *capacity, *device; each may be NULL).  zpack_writer has a fixed layout and no field for the image: it is kept in a side table
+ * keyed by the writer's address (writer.c), which is only asked when the writer has neither a file nor a buffer.  A record that outlived
+ * its writer (a struct never closed whose address serves again) is replaced by the next zpack_amd_init_writer_device there, dropped by the
+ * other inits and by zpack_close_writer, and does not answer for a struct whose buffer_capacity is not the record's capacity — a zeroed
+ * struct is ZPACK_ERROR_WRITER_NOT_OPENED. */
+typedef enum { ZI_SINK_NONE = 0, ZI_SINK_FILE, ZI_SINK_HEAP, ZI_SINK_DEVICE } zi_sink;
+zi_sink zi_writer_sink(const zpack_writer* w, zpack_u8** d_image, size_t* capacity, int* device);
+int  zi_writer_dsink_set(const zpack_writer* w, void* d_image, size_t capacity, int device);   /* 1, or 0 when there is no memory for the record */
+void zi_writer_dsink_drop(const zpack_writer* w);
+
+/* the writer's unified sink: file, growing heap buffer or bounded device image, at the writer's cursor.  A block that does not fit a
+ * device image writes nothing: ZPACK_ERROR_BUFFER_TOO_SMALL, the offsets do not move. */
 int zi_writer_put(zpack_writer* w, const zpack_u8* data, size_t size);
 zpack_file_entry* zi_writer_push_entry(zpack_writer* w);
 

@@ -8,13 +8,68 @@
  */
 #include "internal.h"
 #include "zpack_amd.h"
+#include <pthread.h>
+#include <stdint.h>
 
 /* ------------------------------------------------------------------ sink + entry table */
 
 static zpack_u64 pow2_at_least(zpack_u64 n) { zpack_u64 b = 1; while (b < n) b <<= 1; return b; }
 
-/* append `size` bytes at the writer's cursor: file (seek + write) or heap (power-of-two growth,
- * like lib/zpack_common.c:83-104) */
+/* zpack_amd.h: a writer whose sink is an image in DEVICE memory.  zpack_writer has the reference's fixed layout, so where the image lives
+ * is kept beside the writer, in a table keyed by its address (as the readers' records are: readahead.c). */
+typedef struct zi_dsink_s { const zpack_writer* writer; zpack_u8* d_image; size_t capacity; int device; struct zi_dsink_s* next; } zi_dsink;
+#define ZI_DSINK_BUCKETS 64
+static pthread_rwlock_t g_dsink_mu = PTHREAD_RWLOCK_INITIALIZER;
+static zi_dsink* g_dsink[ZI_DSINK_BUCKETS];
+
+static zi_dsink** dsink_slot(const zpack_writer* w)
+{
+    zi_dsink** pp = &g_dsink[((uintptr_t)w >> 4) % ZI_DSINK_BUCKETS];
+    while (*pp && (*pp)->writer != w) pp = &(*pp)->next;
+    return pp;
+}
+
+int zi_writer_dsink_set(const zpack_writer* w, void* d_image, size_t capacity, int device)
+{
+    pthread_rwlock_wrlock(&g_dsink_mu);
+    zi_dsink** pp = dsink_slot(w);
+    if (!*pp && (*pp = (zi_dsink*)calloc(1, sizeof(zi_dsink))) != NULL) (*pp)->writer = w;
+    if (*pp) { (*pp)->d_image = (zpack_u8*)d_image; (*pp)->capacity = capacity; (*pp)->device = device; }      /* (a record left at this address: replaced) */
+    const int ok = *pp != NULL;
+    pthread_rwlock_unlock(&g_dsink_mu);
+    return ok;
+}
+
+void zi_writer_dsink_drop(const zpack_writer* w)
+{
+    pthread_rwlock_wrlock(&g_dsink_mu);
+    zi_dsink** pp = dsink_slot(w);
+    if (*pp) { zi_dsink* g = *pp; *pp = g->next; free(g); }
+    pthread_rwlock_unlock(&g_dsink_mu);
+}
+
+zi_sink zi_writer_sink(const zpack_writer* w, zpack_u8** d_image, size_t* capacity, int* device)
+{
+    if (d_image) *d_image = NULL;
+    if (capacity) *capacity = 0;
+    if (device) *device = -1;
+    if (w->file) return ZI_SINK_FILE;
+    if (w->buffer) return ZI_SINK_HEAP;
+    zi_sink kind = ZI_SINK_NONE;
+    pthread_rwlock_rdlock(&g_dsink_mu);
+    zi_dsink** pp = dsink_slot(w);
+    if (*pp && (*pp)->capacity == w->buffer_capacity) {       /* (a zeroed struct at the address of a writer that was never closed: not this record's) */
+        kind = ZI_SINK_DEVICE;
+        if (d_image) *d_image = (*pp)->d_image;
+        if (capacity) *capacity = (*pp)->capacity;
+        if (device) *device = (*pp)->device;
+    }
+    pthread_rwlock_unlock(&g_dsink_mu);
+    return kind;
+}
+
+/* append `size` bytes at the writer's cursor: file (seek + write), heap (power-of-two growth, like lib/zpack_common.c:83-104) or an
+ * image in device memory (a room check, then zpk_codec_store_device: the sink does not grow) */
 int zi_writer_put(zpack_writer* w, const zpack_u8* data, size_t size)
 {
     if (w->file) {
@@ -31,7 +86,10 @@ int zi_writer_put(zpack_writer* w, const zpack_u8* data, size_t size)
         }
         if (size) memcpy(w->buffer + w->write_offset, data, size);
     } else {
-        return ZPACK_ERROR_WRITER_NOT_OPENED;
+        zpack_u8* d_image; size_t capacity;
+        if (zi_writer_sink(w, &d_image, &capacity, NULL) != ZI_SINK_DEVICE) return ZPACK_ERROR_WRITER_NOT_OPENED;
+        if (w->write_offset > capacity || size > capacity - w->write_offset) return ZPACK_ERROR_BUFFER_TOO_SMALL;
+        if (zpk_codec_store_device(d_image + w->write_offset, data, size) != ZPK_OK) return ZPACK_ERROR_WRITE_FAILED;
     }
     w->write_offset += size;
     w->file_size += size;
@@ -64,6 +122,7 @@ static char* dup_name(const char* s)
 
 int zpack_init_writer(zpack_writer* writer, const char* path)
 {
+    zi_writer_dsink_drop(writer);                         /* (a device-sink record left at this address by a writer that was never closed) */
     writer->file = fopen(path, "wb");
     return writer->file ? ZPACK_OK : ZPACK_ERROR_OPEN_FAILED;
 }
@@ -71,6 +130,7 @@ int zpack_init_writer(zpack_writer* writer, const char* path)
 int zpack_init_writer_cfile(zpack_writer* writer, FILE* fp)
 {
     if (!fp) return ZPACK_ERROR_OPEN_FAILED;
+    zi_writer_dsink_drop(writer);
     writer->file = fp;
     return ZPACK_OK;
 }
@@ -78,9 +138,34 @@ int zpack_init_writer_cfile(zpack_writer* writer, FILE* fp)
 int zpack_init_writer_heap(zpack_writer* writer, size_t initial_size)
 {
     const size_t least = ZPACK_HEADER_SIZE + ZPACK_SIGNATURE_SIZE;
+    zi_writer_dsink_drop(writer);
     writer->buffer_capacity = initial_size > least ? initial_size : least;
     writer->buffer = (zpack_u8*)malloc(writer->buffer_capacity);
     return writer->buffer ? ZPACK_OK : ZPACK_ERROR_MALLOC_FAILED;
+}
+
+int zpack_amd_init_writer_device(zpack_writer* writer, void* d_image, size_t capacity)
+{
+    if (!writer || !d_image) return ZPACK_ERROR_STREAM_INVALID;
+    if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
+    /* the whole range is checked against its allocation before anything is touched */
+    const int device = zpk_codec_pointer_device(d_image);
+    if (device < 0 || zpk_codec_store_device(d_image, NULL, capacity) != ZPK_OK) return ZPACK_ERROR_STREAM_INVALID;
+    if (!zi_writer_dsink_set(writer, d_image, capacity, device)) return ZPACK_ERROR_MALLOC_FAILED;
+    writer->buffer = NULL; writer->file = NULL;
+    writer->buffer_capacity = capacity;                                            /* (what zi_writer_sink knows the record by) */
+    return ZPACK_OK;
+}
+
+int zpack_amd_writer_device_image(const zpack_writer* writer, void** d_image, size_t* capacity, int* device)
+{
+    if (!writer) return ZPACK_ERROR_STREAM_INVALID;
+    zpack_u8* p = NULL; size_t cap = 0; int dev = -1;
+    if (zi_writer_sink(writer, &p, &cap, &dev) != ZI_SINK_DEVICE) { p = NULL; cap = 0; dev = -1; }
+    if (d_image) *d_image = p;
+    if (capacity) *capacity = cap;
+    if (device) *device = dev;
+    return ZPACK_OK;
 }
 
 /* ------------------------------------------------------------------ fixed blocks */
@@ -104,7 +189,7 @@ int zpack_write_data_header(zpack_writer* writer)
 
 int zpack_write_cdr_ex(zpack_writer* writer, zpack_file_entry* entries, zpack_u64 file_count)
 {
-    if (!writer->file && !writer->buffer) return ZPACK_ERROR_WRITER_NOT_OPENED;
+    if (zi_writer_sink(writer, NULL, NULL, NULL) == ZI_SINK_NONE) return ZPACK_ERROR_WRITER_NOT_OPENED;
     zpack_u64 block = 0;
     for (zpack_u64 i = 0; i < file_count; i++) {
         const size_t n = strlen(entries[i].filename);
@@ -163,13 +248,61 @@ static void write_part(void* arg, int k)
     j->rc[k] = n ? zpk_codec_encode_batch_host(j->ctx->dev[k], j->srcs + lo, j->desc + lo, n, j->dsts + lo, j->res + lo) : ZPK_OK;
 }
 
+/* the codec of `ctx` on HIP device `device`, NULL when the context holds none */
+static zpk_codec* ctx_codec_on(zi_ctx* ctx, int device)
+{
+    for (int k = 0; k < ctx->n; k++) if (zpk_codec_device(ctx->dev[k]) == device) return ctx->dev[k];
+    return NULL;
+}
+
+/* The sink is an image in DEVICE memory: ONE zpk_codec_encode_batch_dsink call on the codec of the sink's device, no shard — the frames
+ * are committed to the image on the device under the append rule below (the files in front of the first failing one, where "does not
+ * fit" fails too), and only the results and the cut come home: no scratch of compress-bound size on the host. */
+static int write_files_dsink(zpack_writer* writer, zi_ctx* ctx, zpack_file* files, zpack_u64 file_count, int on_device,
+                             const zpack_u8* const* srcs, const zpk_encode_desc* desc, zpk_encode_result* res)
+{
+    zpack_u8* d_image; size_t capacity; int device;
+    if (zi_writer_sink(writer, &d_image, &capacity, &device) != ZI_SINK_DEVICE) return ZPACK_ERROR_WRITER_NOT_OPENED;
+    zpk_codec* codec = ctx_codec_on(ctx, device);
+    if (!codec) return ZPACK_ERROR_NOT_AVAILABLE;                                  /* the sink's device is not one of the context's */
+    if (on_device) {                                                               /* device plaintext lies on the sink's device */
+        int rc = ZPACK_OK;
+        zpk_codec* of = zi_ctx_codec_of(ctx, &files[0].buffer, sizeof(files[0]), &files[0].size, sizeof(files[0]), 1, file_count, &rc);
+        if (rc == ZPACK_ERROR_NOT_AVAILABLE || (of && zpk_codec_device(of) != device)) return ZPACK_ERROR_STREAM_INVALID;
+        if (rc != ZPACK_OK) return rc;
+    }
+    const zpack_u64 at0 = writer->write_offset;
+    const zpack_u64 room = at0 < capacity ? capacity - at0 : 0;
+    uint64_t placed = 0, bytes = 0;
+    const int crc = zpk_codec_encode_batch_dsink(codec, srcs, on_device, desc, file_count, d_image + (at0 < capacity ? at0 : capacity), room, res, &placed, &bytes);
+    if (crc != ZPK_OK) return crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
+    for (zpack_u64 i = 0; i < placed; i++) {                                       /* entered as the loop below enters them: at the running sum */
+        writer->last_return = (size_t)res[i].comp_size;
+        const zpack_u64 at = writer->write_offset;
+        writer->write_offset += (size_t)res[i].comp_size;
+        writer->file_size += (size_t)res[i].comp_size;
+        zpack_file_entry* e = zi_writer_push_entry(writer);
+        if (!e || !(e->filename = dup_name(files[i].filename))) return ZPACK_ERROR_MALLOC_FAILED;
+        e->offset = at;
+        e->comp_size = res[i].comp_size;
+        e->uncomp_size = files[i].size;
+        e->hash = res[i].hash;
+        e->comp_method = (zpack_u8)files[i].options->method;
+    }
+    if (placed == file_count) return ZPACK_OK;
+    /* the file that stopped the call: its own status, else it did not fit what is left of the image */
+    writer->last_return = res[placed].status ? (size_t)0 - res[placed].detail : (size_t)res[placed].comp_size;
+    return res[placed].status ? res[placed].status : ZPACK_ERROR_BUFFER_TOO_SMALL;
+}
+
 /* on_device: files[i].buffer are DEVICE pointers (zpack_amd_write_files_device) — the plaintext is compressed where it lies, only the
  * compressed bytes cross the bus: one zpk_codec_encode_batch_dsrc call on the codec of the pointers' device (no shard: one call's
  * pointers belong to one device).  Everything behind the codec call is the same code, so the archive is the same bytes. */
 static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, int on_device)
 {
     if (file_count == 0) return ZPACK_OK;
-    if (!writer->file && !writer->buffer) return ZPACK_ERROR_WRITER_NOT_OPENED;
+    const zi_sink sink = zi_writer_sink(writer, NULL, NULL, NULL);
+    if (sink == ZI_SINK_NONE) return ZPACK_ERROR_WRITER_NOT_OPENED;
     /* contexts: a per-file cctx is honoured when every file names the same one, else the writer's own */
     void* explicit_ctx = files[0].cctx;
     for (zpack_u64 i = 1; i < file_count; i++) if (files[i].cctx != explicit_ctx) explicit_ctx = NULL;
@@ -179,8 +312,8 @@ static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_c
     zpk_encode_desc* desc = (zpk_encode_desc*)calloc((size_t)file_count, sizeof(*desc));
     zpk_encode_result* res = (zpk_encode_result*)calloc((size_t)file_count, sizeof(*res));
     const zpack_u8** srcs = (const zpack_u8**)calloc((size_t)file_count, sizeof(*srcs));
-    zpack_u8** dsts = (zpack_u8**)calloc((size_t)file_count, sizeof(*dsts));
-    int rc = (desc && res && srcs && dsts) ? ZPACK_OK : ZPACK_ERROR_MALLOC_FAILED;
+    zpack_u8** dsts = sink == ZI_SINK_DEVICE ? NULL : (zpack_u8**)calloc((size_t)file_count, sizeof(*dsts));
+    int rc = (desc && res && srcs && (dsts || sink == ZI_SINK_DEVICE)) ? ZPACK_OK : ZPACK_ERROR_MALLOC_FAILED;
     zpack_u64 slots = 0;
     for (zpack_u64 i = 0; i < file_count && rc == ZPACK_OK; i++) {
         const zpack_compression_method m = files[i].options->method;
@@ -191,6 +324,11 @@ static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_c
         desc[i].dst_capacity = zpk_codec_compress_bound((uint32_t)m, (size_t)files[i].size);     /* lib/zpack_write.c:125-150 */
         slots += desc[i].dst_capacity + 16;
         srcs[i] = files[i].buffer;
+    }
+    if (sink == ZI_SINK_DEVICE) {
+        if (rc == ZPACK_OK) rc = write_files_dsink(writer, ctx, files, file_count, on_device, srcs, desc, res);
+        free(desc); free(res); free(srcs);
+        return rc;
     }
     zpack_u8* scratch = NULL;
     if (rc == ZPACK_OK) {
@@ -249,13 +387,54 @@ int zpack_amd_write_files_device(zpack_writer* writer, zpack_file* files, zpack_
     return write_files(writer, files, file_count, 1);
 }
 
+/* ... from an image in device memory to an image in device memory ON THE SAME DEVICE: the payloads never leave it.  The loop below, in
+ * two passes: the entries that pass its guards and fit the image, in order, are rows of ONE zpk_codec_copy_spans_device launch; then they
+ * are entered.  *rc = what the first entry that stops the loop returns.  0: no codec of the writer's context is on that device, the
+ * caller copies through the host. */
+static int from_archive_on_device(zpack_writer* writer, const zpack_reader* reader, const zpack_u8* d_src, zpack_u8* d_image, size_t capacity, int device,
+                                  const zpack_file_entry* entries, zpack_u64 file_count, int* rc)
+{
+    zi_ctx* ctx = zi_pick_ctx(NULL, &writer->zstd_cctx);
+    zpk_codec* codec = ctx ? ctx_codec_on(ctx, device) : NULL;
+    if (!codec) return 0;
+    zpk_span_copy* rows = (zpk_span_copy*)malloc(sizeof(*rows) * (size_t)(file_count ? file_count : 1));
+    if (!rows) { *rc = ZPACK_ERROR_MALLOC_FAILED; return 1; }
+    zpack_u64 k = 0, at = writer->write_offset;
+    *rc = ZPACK_OK;
+    for (; k < file_count; k++) {
+        const zpack_file_entry* src = entries + k;
+        if (src->offset >= reader->file_size || src->comp_size > reader->file_size - src->offset) { *rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
+        if (at > capacity || src->comp_size > capacity - at) { *rc = ZPACK_ERROR_BUFFER_TOO_SMALL; break; }
+        rows[k].src = (uint64_t)(uintptr_t)(d_src + src->offset); rows[k].dst = (uint64_t)(uintptr_t)(d_image + at); rows[k].len = src->comp_size;
+        at += src->comp_size;
+    }
+    if (k && (zpk_codec_copy_spans_device(codec, rows, k, NULL) != ZPK_OK || zpk_codec_stream_sync(codec) != ZPK_OK)) { free(rows); *rc = ZPACK_ERROR_WRITE_FAILED; return 1; }
+    free(rows);
+    for (zpack_u64 i = 0; i < k; i++) {
+        const zpack_file_entry* src = entries + i;
+        const zpack_u64 here = writer->write_offset;
+        writer->write_offset += (size_t)src->comp_size;
+        writer->file_size += (size_t)src->comp_size;
+        zpack_file_entry* e = zi_writer_push_entry(writer);
+        if (!e) { *rc = ZPACK_ERROR_MALLOC_FAILED; return 1; }
+        *e = *src;
+        e->offset = here;
+        if (!(e->filename = dup_name(src->filename))) { *rc = ZPACK_ERROR_MALLOC_FAILED; return 1; }
+    }
+    return 1;
+}
+
 /* raw entry copy between archives: no codec involved (lib/zpack_write.c:345-428) */
 int zpack_write_files_from_archive(zpack_writer* writer, zpack_reader* reader, zpack_file_entry* entries, zpack_u64 file_count)
 {
-    if (!writer->file && !writer->buffer) return ZPACK_ERROR_WRITER_NOT_OPENED;
+    zpack_u8* d_sink; size_t sink_capacity; int sink_device;
+    if (zi_writer_sink(writer, &d_sink, &sink_capacity, &sink_device) == ZI_SINK_NONE) return ZPACK_ERROR_WRITER_NOT_OPENED;
     zpack_u8* tmp = NULL; size_t tmp_cap = 0;
     int rc = ZPACK_OK;
-    const zi_source from = zi_reader_source(reader, NULL, NULL);
+    const zpack_u8* d_from; int from_device;
+    const zi_source from = zi_reader_source(reader, &d_from, &from_device);
+    if (d_sink && from == ZI_SRC_DEVICE && from_device == sink_device &&
+        from_archive_on_device(writer, reader, d_from, d_sink, sink_capacity, sink_device, entries, file_count, &rc)) return rc;
     for (zpack_u64 i = 0; i < file_count && rc == ZPACK_OK; i++) {
         const zpack_file_entry* src = entries + i;
         const zpack_u8* payload = NULL;
@@ -305,7 +484,7 @@ int zpack_write_file_stream(zpack_writer* writer, zpack_compress_options* option
     if (!stream->next_in || !stream->next_out || !stream->avail_out) return ZPACK_ERROR_STREAM_INVALID;
     const zpack_compression_method m = options->method;
     if (m != ZPACK_COMPRESSION_NONE && m != ZPACK_COMPRESSION_ZSTD && m != ZPACK_COMPRESSION_LZ4) return ZPACK_ERROR_COMP_METHOD_INVALID;
-    if (!writer->file && !writer->buffer) return ZPACK_ERROR_WRITER_NOT_OPENED;
+    if (zi_writer_sink(writer, NULL, NULL, NULL) == ZI_SINK_NONE) return ZPACK_ERROR_WRITER_NOT_OPENED;
     zi_stream_state* st = (zi_stream_state*)stream->xxh3_state;
     if (!st) return ZPACK_ERROR_STREAM_INVALID;
     zi_ctx* ctx = zi_pick_ctx(cctx, &writer->zstd_cctx);
@@ -331,7 +510,7 @@ int zpack_write_file_stream_end(zpack_writer* writer, char* filename, zpack_comp
     if (!stream->next_out || !stream->avail_out) return ZPACK_ERROR_STREAM_INVALID;
     const zpack_compression_method m = options->method;
     if (m != ZPACK_COMPRESSION_NONE && m != ZPACK_COMPRESSION_ZSTD && m != ZPACK_COMPRESSION_LZ4) return ZPACK_ERROR_COMP_METHOD_INVALID;
-    if (!writer->file && !writer->buffer) return ZPACK_ERROR_WRITER_NOT_OPENED;
+    if (zi_writer_sink(writer, NULL, NULL, NULL) == ZI_SINK_NONE) return ZPACK_ERROR_WRITER_NOT_OPENED;
     zi_stream_state* st = (zi_stream_state*)stream->xxh3_state;
     if (!st) return ZPACK_ERROR_STREAM_INVALID;
     zi_ctx* ctx = zi_pick_ctx(cctx, &writer->zstd_cctx);
@@ -367,6 +546,7 @@ int zpack_write_archive(zpack_writer* writer, zpack_file* files, zpack_u64 file_
 
 void zpack_close_writer(zpack_writer* writer)
 {
+    zi_writer_dsink_drop(writer);                         /* (the image is the caller's: left alone) */
     if (writer->file) fclose(writer->file);
     free(writer->buffer);
     if (writer->file_entries) {
