@@ -15,44 +15,13 @@ import pytest
 import zpack_amd
 from benchdata import datagen as dg
 from tests import zpk
-from tests._libs import ZPackAPI, Reader, Writer, FileEntry, Stream, u8p, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4
-from tests.test_gpu_device_io import _plain, _build, _layout, CANARY, GAP
+from tests._libs import Reader, Writer, FileEntry, Stream, u8p, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4
+from tests.device_mem import torch, Z, _plain, _build, _layout, CANARY, GAP            # noqa: F401  (torch, Z: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 PFE = C.POINTER(FileEntry)
 NOT_LOADED, FILE_TOO_SMALL, STREAM_INVALID, NOT_AVAILABLE = 1, 5, 21, 24
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available()
-    return t
-
-
-@pytest.fixture(scope="module")
-def Z():
-    z = ZPackAPI(zpack_amd.ZPACK_SO)
-    L = z.lib
-    R, vp, u64 = C.POINTER(Reader), C.c_void_p, C.c_uint64
-    L.zpack_amd_init_reader_device.argtypes = [R, vp, C.c_size_t]
-    L.zpack_amd_reader_device_image.argtypes = [R, C.POINTER(vp), C.POINTER(C.c_int)]
-    L.zpack_read_file.argtypes = [R, PFE, vp, C.c_size_t, vp]
-    L.zpack_read_files.argtypes = [R, C.POINTER(PFE), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]
-    L.zpack_amd_read_files_device.argtypes = L.zpack_read_files.argtypes
-    L.zpack_read_files_packed.argtypes = [R, C.POINTER(PFE), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
-    L.zpack_amd_read_files_device_packed.argtypes = L.zpack_read_files_packed.argtypes
-    L.zpack_read_raw_file.argtypes = [R, PFE, vp, C.c_size_t]
-    L.zpack_read_archive_memory.argtypes = [R]
-    L.zpack_read_archive.argtypes = [R]
-    L.zpack_write_files_from_archive.argtypes = [C.POINTER(Writer), R, PFE, u64]
-    L.zpack_amd_read_ahead_stats.argtypes = [R, vp, C.POINTER(u64)]
-    L.zpack_create_dctx.restype = vp
-    L.zpack_create_dctx.argtypes = [C.c_int]
-    L.zpack_free_dctx.restype = None
-    L.zpack_free_dctx.argtypes = [C.c_int, vp]
-    return z
 
 
 # ------------------------------------------------------------------------------------------------ helpers
@@ -510,6 +479,43 @@ def test_bad_images(Z, torch, golden_dir):
         assert Z.lib.zpack_amd_init_reader_device(C.byref(r), image_at, size) == STREAM_INVALID
         assert bytes(r) == bytes(C.sizeof(Reader))                                     # turned down before anything was copied or parsed
         assert _not_loaded(Z, r) == (NOT_LOADED,) * 2
+    r = Reader()
+    assert Z.lib.zpack_amd_init_reader_device(C.byref(r), None, len(arc)) == STREAM_INVALID                 # NULL with bytes
+    assert bytes(r) == bytes(C.sizeof(Reader)) and _not_loaded(Z, r) == (NOT_LOADED,) * 2
+    # ... and the device destinations of a batch read from a good image: NULL with bytes, a host address, a destination that leaves its
+    # allocation are turned down before anything runs; no bytes pass wherever they point; the next good call on the same reader reads
+    rd, keep = _open_dev(Z, torch, arc)
+    ents = [rd.file_entries[i] for i in range(rd.file_count) if rd.file_entries[i].uncomp_size > 0][:4]
+    n, k = len(ents), len(ents) - 1
+    caps = [int(e.uncomp_size) for e in ents]
+    offs, total = _layout(caps, (0,))
+    dst = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda:0")
+    small = torch.full((4096,), CANARY, dtype=torch.uint8, device="cuda:0")
+    hostbuf = np.full(max(caps) + 64, CANARY, dtype=np.uint8)
+    torch.cuda.synchronize()
+
+    def read(at, cap):
+        addr = [dst.data_ptr() + o for o in offs[:k]] + [at]
+        res = (C.c_int * n)(*([-1] * n))
+        rc = Z.lib.zpack_amd_read_files_device(C.byref(rd), (PFE * n)(*[C.pointer(e) for e in ents]), n, (C.c_void_p * n)(*addr),
+                                               (C.c_size_t * n)(*(caps[:k] + [cap])), res, None)
+        torch.cuda.synchronize()
+        return rc, list(res)
+
+    for at, cap in ((None, caps[k]), (hostbuf.ctypes.data, caps[k]), (small.data_ptr() + 100, 1 << 40)):
+        assert read(at, cap) == (STREAM_INVALID, [-1] * n)
+        assert bool((dst == CANARY).all()) and bool((small == CANARY).all()) and bool((hostbuf == CANARY).all())
+    if torch.cuda.device_count() > 1:                                                  # memory of another device than the image's
+        other = torch.full((caps[k] + 64,), CANARY, dtype=torch.uint8, device="cuda:1")
+        torch.cuda.synchronize(1)
+        assert read(other.data_ptr(), caps[k]) == (STREAM_INVALID, [-1] * n)
+        assert bool((dst == CANARY).all()) and bool((other == CANARY).all())
+    for at in (None, hostbuf.ctypes.data):
+        rc, res = read(at, 0)
+        assert rc == 0 and res[:k] == [0] * k and res[k] == 12                         # (max_size 0 < uncomp_size: BUFFER_TOO_SMALL, as on every path)
+        assert bool((hostbuf == CANARY).all())
+    assert read(dst.data_ptr() + offs[k], caps[k]) == (0, [0] * n)
+    Z.lib.zpack_close_reader(C.byref(rd))
     cdr = int.from_bytes(arc[-8:], "little")
     cases = {"41 bytes": arc[:41],
              "header signature": b"\0" + arc[1:],

@@ -15,46 +15,15 @@ import pytest
 import zpack_amd
 from benchdata import datagen as dg
 from tests import zpk
-from tests._libs import ZPackAPI, Reader, Writer, File, FileEntry, CompressOptions, u8p, oracle, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4
+from tests._libs import Reader, Writer, File, FileEntry, CompressOptions, u8p, oracle, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4
+from tests.device_mem import torch, Z, _plain, _build, _layout, CANARY, GAP            # noqa: F401  (torch, Z: fixtures)
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xA5
-GAP = 64
 PFE = C.POINTER(FileEntry)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available()
-    return t
-
-
-@pytest.fixture(scope="module")
-def Z():
-    z = ZPackAPI(zpack_amd.ZPACK_SO)
-    L = z.lib
-    L.zpack_read_files.argtypes = [C.POINTER(Reader), C.POINTER(PFE), C.c_uint64, C.POINTER(u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_void_p]
-    L.zpack_amd_read_files_device.argtypes = [C.POINTER(Reader), C.POINTER(PFE), C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                              C.POINTER(C.c_int), C.c_void_p]
-    L.zpack_amd_read_files_device_packed.argtypes = [C.POINTER(Reader), C.POINTER(PFE), C.c_uint64, C.c_void_p, C.c_size_t,
-                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_void_p]
-    L.zpack_amd_write_files_device.argtypes = [C.POINTER(Writer), C.POINTER(File), C.c_uint64]
-    return z
-
-
 # ------------------------------------------------------------------------------------------------ helpers
-
-def _layout(caps, mis):
-    """device destinations back to back in one buffer, at least GAP canary bytes around each; destination i at an address = mis[i % len] mod 16"""
-    pos, offs = GAP, []
-    for i, c in enumerate(caps):
-        pos = ((pos + 15) & ~15) + mis[i % len(mis)]
-        offs.append(pos)
-        pos += c + GAP
-    return offs, pos + GAP
-
 
 def _entry_ptrs(ents):
     return (PFE * max(len(ents), 1))(*[C.pointer(e) for e in ents])
@@ -69,10 +38,11 @@ def _read_host(Z, r, ents, caps):
     return rc, list(res)[:n], [b[:c] for b, c in zip(bufs, caps)], int(r.last_return)
 
 
-def _read_dev(Z, torch, r, ents, caps, mis=(0,), override=None):
-    """-> rc, results, the whole device buffer (host copy), the destinations' offsets in it, last_return.  override: {i: address}"""
+def _read_dev(Z, torch, r, ents, caps, mis=(0,), override=None, room=None):
+    """-> rc, results, the whole device buffer (host copy), the destinations' offsets in it, last_return.  override: {i: address};
+    room: the sizes the buffer is laid out for, where they are not the max_sizes handed to the call"""
     n = len(ents)
-    offs, total = _layout(caps, mis)
+    offs, total = _layout(room or caps, mis)
     buf = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
     addr = [buf.data_ptr() + o for o in offs]
@@ -107,36 +77,6 @@ def _same_as_host(Z, torch, r, ents, caps, mis=(0,), bytes_of=(0, 15)):
         raise AssertionError("byte %d of the device buffer differs (near destination %d at %d, %d bytes): %d, want %d"
                              % (bad, k, offs[k], caps[k], dbuf[bad], want[bad]))
     return hres
-
-
-def _plain(i, n):
-    """n bytes, three kinds: text with edits (matches at many distances), random bytes, long runs"""
-    rng = np.random.default_rng(1000 + i)
-    if n == 0:
-        return b""
-    if i % 3 == 0:
-        words = [b"alpha ", b"beta ", b"gamma delta ", b"epsilon\n", b"0123456789", b"the quick brown fox "]
-        out = bytearray()
-        while len(out) < n:
-            out += words[int(rng.integers(len(words)))]
-            if rng.integers(8) == 0:
-                out += bytes(rng.integers(0, 256, 3, dtype=np.uint8))
-        return bytes(out[:n])
-    if i % 3 == 1:
-        return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
-    unit = bytes([i & 255]) * 700 + b"ab" * 150 + rng.integers(0, 256, 40, dtype=np.uint8).tobytes()
-    return (unit * (n // len(unit) + 1))[:n]
-
-
-def _build(specs):
-    """specs: [(method, level, plaintext)] -> archive bytes, plaintexts"""
-    payloads, entries, pos = [], [], 10
-    for i, (m, lv, data) in enumerate(specs):
-        p = dg.compress(m, lv, data)
-        payloads.append(p)
-        entries.append(("e%04d" % i, pos, len(p), len(data), dg.xxh3(data), m))
-        pos += len(p)
-    return zpk.assemble(payloads, entries)
 
 
 def _open(Z, arc):
@@ -192,11 +132,29 @@ def test_span_copy_kernel_lengths_and_alignments(torch):
     dst.fill_(CANARY); torch.cuda.synchronize()
     small = torch.zeros(4096, dtype=torch.uint8, device="cuda:0")
     host = np.zeros(64, dtype=np.uint8)
-    for bad in ([small.data_ptr(), dst.data_ptr() + GAP, 1 << 40], [host.ctypes.data, dst.data_ptr() + GAP, 64], [src.data_ptr(), 0, 16]):
+    for bad in ([small.data_ptr(), dst.data_ptr() + GAP, 1 << 40], [host.ctypes.data, dst.data_ptr() + GAP, 64], [src.data_ptr(), 0, 16],
+                [0, dst.data_ptr() + GAP, 16], [src.data_ptr(), host.ctypes.data, 64], [src.data_ptr(), small.data_ptr() + 100, 1 << 40]):
         both = np.array([[src.data_ptr(), dst.data_ptr() + GAP, 100], bad], dtype=np.uint64)
         assert L.zpk_codec_copy_spans_device(codec.h, both.ctypes.data, 2, None) == -2
+    if torch.cuda.device_count() > 1:                                                  # memory of another device than the codec's, either end
+        other = torch.full((4096,), CANARY, dtype=torch.uint8, device="cuda:1")
+        torch.cuda.synchronize(1)
+        for bad in ([other.data_ptr(), dst.data_ptr() + GAP, 64], [src.data_ptr(), other.data_ptr(), 64]):
+            both = np.array([[src.data_ptr(), dst.data_ptr() + GAP, 100], bad], dtype=np.uint64)
+            assert L.zpk_codec_copy_spans_device(codec.h, both.ctypes.data, 2, None) == -2
+        torch.cuda.synchronize(1)
+        assert bool((other == CANARY).all())
     torch.cuda.synchronize()
-    assert bool((dst == CANARY).all())
+    assert bool((dst == CANARY).all()) and not host.any()
+    # a span of no bytes passes wherever it points, NULL and host addresses included: the good row beside it is copied, and only that
+    for nothing in ([0, 0, 0], [host.ctypes.data, host.ctypes.data + 8, 0]):
+        both = np.array([nothing, [src.data_ptr(), dst.data_ptr() + GAP, 100]], dtype=np.uint64)
+        assert L.zpk_codec_copy_spans_device(codec.h, both.ctypes.data, 2, None) == 0
+        torch.cuda.synchronize()
+        got = dst.cpu().numpy()
+        assert np.array_equal(got[GAP:GAP + 100], src_h[:100]) and bool((got[:GAP] == CANARY).all()) and bool((got[GAP + 100:] == CANARY).all())
+        dst.fill_(CANARY); torch.cuda.synchronize()
+    assert not host.any()
     codec.close()
 
 
@@ -374,6 +332,26 @@ def test_pointer_check_null_and_host_addresses(Z, torch, mixed):
             assert rc == 21, override
             assert res == [-1] * len(ents)                                             # rejected on the host: nothing ran, no result was written
             assert bool((dbuf == CANARY).all()) and bool((host == CANARY).all())
+        # a destination that leaves its allocation: 2^40 bytes from inside a 4 KiB tensor
+        small = torch.full((4096,), CANARY, dtype=torch.uint8, device="cuda:0")
+        huge = list(caps); huge[3] = 1 << 40
+        rc, res, dbuf, offs, _ = _read_dev(Z, torch, r, ents, huge, override={3: small.data_ptr() + 100}, room=caps)
+        assert rc == 21 and res == [-1] * len(ents)
+        assert bool((dbuf == CANARY).all()) and bool((small == CANARY).all())
+        if torch.cuda.device_count() > 1:                                              # memory of another device than the batch's
+            other = torch.full((max(caps) + 64,), CANARY, dtype=torch.uint8, device="cuda:1")
+            torch.cuda.synchronize(1)
+            rc, res, dbuf, offs, _ = _read_dev(Z, torch, r, ents, caps, override={4: other.data_ptr()})
+            assert rc == 21 and res == [-1] * len(ents)
+            assert bool((dbuf == CANARY).all()) and bool((other == CANARY).all())
+        # no bytes at NULL and at a host address pass the rule: the call runs, that entry gets the verdict the host path gives it
+        none = list(caps); none[2] = 0
+        hrc, hres, _, hlast = _read_host(Z, r, ents, none)
+        assert hrc == 0 and hres[2] != 0 and [v for k, v in enumerate(hres) if k != 2] == [0] * (len(ents) - 1)
+        for at in (None, host.ctypes.data):
+            rc, res, dbuf, offs, last = _read_dev(Z, torch, r, ents, none, override={2: at})
+            assert (rc, res, last) == (hrc, hres, hlast)
+            assert bool((host == CANARY).all())
         # the same batch with good pointers still reads
         assert _same_as_host(Z, torch, r, ents, caps) == [0] * len(ents)
     finally:
@@ -458,6 +436,18 @@ def test_write_pointer_check(Z, torch, tmp_path):
         arr[1].filename = b"bad"; arr[1].buffer = C.cast(ptr, u8p) if ptr else None; arr[1].size = 4096; arr[1].options = C.pointer(opts)
         assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == 21
         assert w.file_count == 0 and w.write_offset == 0
+        if ptr is None and torch.cuda.device_count() > 1:                              # memory of another device than the batch's
+            other = torch.zeros(4096, dtype=torch.uint8, device="cuda:1")
+            torch.cuda.synchronize(1)
+            arr[1].buffer = C.cast(other.data_ptr(), u8p)
+            assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == 21
+            assert w.file_count == 0 and w.write_offset == 0
+        # no bytes at that address pass the rule, and the next call on the same writer writes both files
+        # (a source that leaves its allocation is checked where no scratch of its compress bound is asked for first: on a device sink,
+        # test_gpu_device_sink.py::test_pointers_are_checked_on_the_host)
+        arr[1].buffer = C.cast(ptr, u8p) if ptr else None; arr[1].size = 0
+        assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == 0
+        assert w.file_count == 2 and w.file_entries[0].uncomp_size == 4096 and w.file_entries[1].uncomp_size == 0
         Z.lib.zpack_close_writer(C.byref(w))
 
 

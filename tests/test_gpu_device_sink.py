@@ -13,9 +13,9 @@ import pytest
 import zpack_amd
 from benchdata import datagen as dg
 from tests import zpk
-from tests._libs import (ZPackAPI, Reader, Writer, File, FileEntry, Stream, CompressOptions, u8p, oracle, have_ref, ref,
+from tests._libs import (Reader, Writer, File, FileEntry, Stream, CompressOptions, u8p, oracle, have_ref, ref,
                          METHOD_NONE, METHOD_ZSTD, METHOD_LZ4)
-from tests.test_gpu_device_io import _plain
+from tests.device_mem import torch, Z, _plain                                          # noqa: F401  (torch, Z: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,27 +25,6 @@ GUARD, FILL = 256, 0xA5
 BIG = (2 << 20) + 17                             # the smallest entry written in pieces (ZPK_OPT_ENC_SPLIT_MIN: 2 MiB)
 SIZES = [4095, 0, 1, 15, 16, 17, 65537, BIG]     # (the first file has bytes: "inside file 0" needs some)
 KINDS = [(METHOD_NONE, 0), (METHOD_LZ4, 0), (METHOD_ZSTD, 1), (METHOD_ZSTD, 3)]
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    assert t.cuda.is_available()
-    return t
-
-
-@pytest.fixture(scope="module")
-def Z():
-    z = ZPackAPI(zpack_amd.ZPACK_SO)
-    L = z.lib
-    R, W, vp, u64 = C.POINTER(Reader), C.POINTER(Writer), C.c_void_p, C.c_uint64
-    L.zpack_amd_init_writer_device.argtypes = [W, vp, C.c_size_t]
-    L.zpack_amd_writer_device_image.argtypes = [W, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
-    L.zpack_amd_write_files_device.argtypes = [W, C.POINTER(File), u64]
-    L.zpack_amd_init_reader_device.argtypes = [R, vp, C.c_size_t]
-    L.zpack_amd_read_files_device.argtypes = [R, C.POINTER(PFE), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]
-    L.zpack_write_files_from_archive.argtypes = [W, R, PFE, u64]
-    return z
 
 
 @pytest.fixture(scope="module")
@@ -549,10 +528,28 @@ def test_pointers_are_checked_on_the_host(Z, torch):
     assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == STREAM_INVALID
     arr[1].buffer = None
     assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == STREAM_INVALID
+    # ... a source that leaves its allocation, and, on a box with two cards, memory of another device than the sink's
+    arr[1].buffer = C.cast(t.data_ptr() + 100, u8p); arr[1].size = 1 << 40
+    assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == STREAM_INVALID
+    arr[1].size = 4096
+    if torch.cuda.device_count() > 1:
+        other = torch.zeros(4096, dtype=torch.uint8, device="cuda:1")
+        torch.cuda.synchronize(1)
+        arr[1].buffer = C.cast(other.data_ptr(), u8p)
+        assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == STREAM_INVALID
     assert w.file_count == 0 and w.write_offset == 10 and sink.bytes() == before and sink.guards_intact()
     # ... and the writer is still good
     arr[1].buffer = C.cast(t.data_ptr() + 1, u8p); arr[1].size = 4095
     assert Z.lib.zpack_amd_write_files_device(C.byref(w), arr, 2) == OK and w.file_count == 2
+    # no bytes pass wherever they point: NULL and a host address, from device and from host plaintext
+    arr[1].size = 0
+    for k, (at, write) in enumerate(((None, Z.lib.zpack_amd_write_files_device), (C.cast(hostbuf, u8p), Z.lib.zpack_amd_write_files_device),
+                                     (C.cast(t.data_ptr(), u8p), Z.lib.zpack_write_files))):
+        arr[1].buffer = at
+        if write is Z.lib.zpack_write_files:
+            arr[0].buffer = C.cast(hostbuf, u8p)
+        assert write(C.byref(w), arr, 2) == OK and w.file_count == 4 + 2 * k
+    assert sink.guards_intact()
     Z.lib.zpack_close_writer(C.byref(w))
     assert sink.guards_intact()
 

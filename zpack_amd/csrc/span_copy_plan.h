@@ -1,7 +1,9 @@
 // span_copy_plan.h — the plaintext of a batch moved between the codec's staging and the CALLER'S DEVICE BUFFERS by one kernel
 // (k_span_copy, span_copy.h), decided in one place for zpk_codec_decode_batch_host_dptr, zpk_codec_encode_batch_dsrc and
 // zpk_codec_copy_spans_device: the row table the kernel reads, its work items and launches, where a sub-batch's slots lie in the staging
-// (both directions), the offsets of the packed read, and the test a caller's pointer has to pass before anything is enqueued.
+// (both directions), the offsets of the packed read, and the range test a caller's pointer has to pass before anything is enqueued
+// (span_copy_in_range; who asks HIP for the allocation and under which policy: zpk_codec.hip, device_range_of and PtrRule — the one rule
+// of every batch call and of zpk_codec_fetch_device / _store_device.  span_copy_enqueue there fills the row table from a callable).
 // Plain C++17, pj_types.h and standard headers only: tools/hostfuzz builds this file with g++ under ASan + UBSan (g++ knows no HIP),
 // which keeps it so.
 #pragma once

@@ -700,9 +700,8 @@ struct zpk_codec {
     int totals_valid = 0;
     char err[256] = {0};
     // plaintext in the caller's device memory (span_copy_plan.h / span_copy.h): the row table of k_span_copy, pinned going up — the event
-    // says that the upload has run, the block is written again only behind it — and the allocation the pointer check saw last
+    // says that the upload has run, the block is written again only behind it
     DevBuf<u8> d_sc; PinBuf h_sc; hipEvent_t sc_ev = nullptr; bool sc_pending = false;
-    u64   sc_base = 0, sc_size = 0;
     u32   pipe_last = 0, sc_last = 0;                // most recent host decode call: sub-batches that took the three-stage pipeline; k_span_copy launches
     // the archive image in the caller's device memory (dimage_plan.h): ZPK_OPT_DIMAGE_CHUNK (0 = the default) and, of the most recent
     // zpk_codec_decode_batch_dimage call, its sub-batches, k_span_copy launches and the bytes it copied home (saturating)
@@ -848,30 +847,106 @@ int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
 #define ZPK_WD_ARG
 #endif
 
-// ---- plaintext in the caller's DEVICE memory (span_copy_plan.h, span_copy.h) -------------------------------------------------------------
-// The pointer check, on the host: [ptr, ptr + len) lies inside ONE allocation on the codec's device.  The last allocation seen is kept for
-// the duration of one call (span_check_begin forgets it: the caller may have freed the buffer since), so a batch into one buffer is one query.
-static void span_check_begin(zpk_codec* c) { c->sc_base = 0; c->sc_size = 0; }
-static bool span_ptr_ok(zpk_codec* c, const void* ptr, u64 len)
+// ---- memory of the caller's ON THE DEVICE: the pointer rule, the checked copy, k_span_copy's table (span_copy_plan.h, span_copy.h) -------------
+// THE QUERY, the one place that asks HIP about a caller's address: which device it lies on and which allocation [base, base + size) holds it.
+// ZPK_OK: *r says so; ZPK_E_INVALID: NULL, host memory (HIP may never have seen it: its last error is cleared), memory of another device
+// than `only` (that device is not entered; DEV_ANY: every device will do, DEV_NONE: none, the caller wants r->device alone), or no
+// allocation; ZPK_E_LAUNCH: the allocation's device could not be entered.
+// r->device is the memory's device whenever it is device memory, whatever else fails; -1 otherwise.  The current device is entered through
+// `on`, which puts it back when it goes: at the end of the call or, handed in by the caller, when the caller is done with that device.
+struct DevRange { int device; u64 base, size; };
+enum { DEV_ANY = -1, DEV_NONE = -2 };
+struct OnDevice {
+    int was = -1, now = -1;
+    bool enter(int device)
+    {
+        if (hipGetDevice(&was) != hipSuccess) { (void)hipGetLastError(); was = -1; }
+        if (was != device && hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return false; }
+        now = device;
+        return true;
+    }
+    OnDevice() {}
+    ~OnDevice() { if (now >= 0 && was >= 0 && was != now) (void)hipSetDevice(was); }
+    OnDevice(const OnDevice&) = delete;
+    OnDevice& operator=(const OnDevice&) = delete;
+};
+static int device_range_of(const void* ptr, DevRange* r, int only, OnDevice* stay = nullptr)
 {
-    if (len == 0) return true;
-    if (!ptr) return false;
-    if (c->sc_size && span_copy_in_range((u64)ptr, len, c->sc_base, c->sc_size)) return true;
+    *r = DevRange{ -1, 0, 0 };
     hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }      // (host memory HIP has not seen)
-    if (at.type != hipMemoryTypeDevice || at.device != c->device) return false;
+    if (!ptr || hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_INVALID; }
+    if (at.type != hipMemoryTypeDevice) return ZPK_E_INVALID;
+    r->device = at.device;
+    if (only != DEV_ANY && at.device != only) return ZPK_E_INVALID;
+    OnDevice here;
+    if (!(stay ? stay : &here)->enter(at.device)) return ZPK_E_LAUNCH;
     hipDeviceptr_t base = nullptr; size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
-    c->sc_base = (u64)base; c->sc_size = size;
-    return span_copy_in_range((u64)ptr, len, c->sc_base, c->sc_size);
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_INVALID; }
+    r->base = (u64)base; r->size = (u64)size;
+    return ZPK_OK;
 }
+// The rule — [ptr, ptr + len) lies inside ONE allocation (span_copy_in_range; no bytes pass wherever they point) — under its two policies:
+//   a BATCH call (PtrRule) demands the codec's own device, before anything is enqueued.  The last allocation seen is kept while the rule
+//     object lives, which is one call — the caller may free the buffer afterwards —, so a batch into one buffer is one query;
+//   the instance-free copy (checked_copy: zpk_codec_fetch_device / _store_device) accepts any device and enters it for the copy.
+extern "C++" {
+struct PtrRule {
+    zpk_codec* const c;
+    DevRange last = { -1, 0, 0 };
+    explicit PtrRule(zpk_codec* codec) : c(codec) {}
+    bool ok(const void* ptr, u64 len)
+    {
+        if (len == 0) return true;
+        if (!ptr) return false;
+        if (last.size && span_copy_in_range((u64)ptr, len, last.base, last.size)) return true;
+        DevRange r;
+        if (device_range_of(ptr, &r, c->device) != ZPK_OK) return false;
+        last = r;
+        return span_copy_in_range((u64)ptr, len, r.base, r.size);
+    }
+    // entries [0, n) of a batch, `noun` i at ptr(i) with len(i) bytes; ZPK_E_INVALID with the message written
+    template <class PtrFn, class LenFn>
+    int batch(const char* noun, u64 n, PtrFn ptr, LenFn len)
+    {
+        for (u64 i = 0; i < n; i++)
+            if (!ok(ptr(i), len(i))) {
+                snprintf(c->err, sizeof(c->err), "%s %llu is not %llu bytes of one allocation on device %d", noun, (unsigned long long)i, (unsigned long long)len(i), c->device);
+                return ZPK_E_INVALID;
+            }
+        return ZPK_OK;
+    }
+};
+}  // extern "C++"
 
-// in[0, n) in ONE k_span_copy on `st` (a table past one grid: several, over the same table); returns when the table's upload and the
-// kernel are enqueued.  The pointers have been checked by the caller, or are the codec's own.
-static int span_copy_enqueue(zpk_codec* c, const zpk_span_copy* in, u64 n, hipStream_t st)
+// instance-free: `bytes` bytes between [d_ptr, + bytes), when that lies inside one allocation in device memory, and `host` (none: the check
+// alone); the memory's device is entered once, for the query and the copy
+static int checked_copy(const void* d_ptr, void* host, u64 bytes, hipMemcpyKind dir)
+{
+    if (zpk_codec_device_count() <= 0) return ZPK_E_NO_DEVICE;
+    if (bytes == 0) return ZPK_OK;
+    OnDevice on;
+    DevRange r;
+    const int rc = device_range_of(d_ptr, &r, DEV_ANY, &on);
+    if (rc) return rc;
+    if (!span_copy_in_range((u64)d_ptr, bytes, r.base, r.size)) return ZPK_E_INVALID;
+    const bool up = dir == hipMemcpyHostToDevice;
+    if (host && hipMemcpy(up ? (void*)d_ptr : host, up ? host : d_ptr, bytes, dir) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_LAUNCH; }
+    return ZPK_OK;
+}
+int zpk_codec_fetch_device(const void* d_src, void* host_dst, uint64_t bytes) { return checked_copy(d_src, host_dst, bytes, hipMemcpyDeviceToHost); }
+int zpk_codec_store_device(void* d_dst, const void* host_src, uint64_t bytes) { return checked_copy(d_dst, (void*)host_src, bytes, hipMemcpyHostToDevice); }
+// the device whose memory `ptr` is, -1 for anything else: the memory's kind alone decides, as a host must not read through such a pointer
+int zpk_codec_pointer_device(const void* ptr) { DevRange r; (void)device_range_of(ptr, &r, DEV_NONE); return r.device; }
+
+// Entries [0, n), entry i the span row(i) (a zpk_span_copy; no bytes: no row), in ONE k_span_copy on `st` (a table past one grid: several,
+// over the same table); returns when the table's upload and the kernel are enqueued.  The rows are written straight into the pinned
+// table: row() is asked twice per entry, once for the count.  The pointers have been checked by the caller, or are the codec's own.
+extern "C++" {
+template <class RowFn>
+static int span_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
 {
     u64 nz = 0;
-    for (u64 i = 0; i < n; i++) nz += in[i].len != 0;
+    for (u64 i = 0; i < n; i++) nz += row(i).len != 0;
     if (nz == 0) return ZPK_OK;
     if (nz > ZPK_SC_MAX_ROWS) return ZPK_E_INVALID;
     if (c->sc_pending) { HIPCHK(c, hipEventSynchronize(c->sc_ev)); c->sc_pending = false; }             // the pinned block's last upload has run
@@ -881,7 +956,7 @@ static int span_copy_enqueue(zpk_codec* c, const zpk_span_copy* in, u64 n, hipSt
     if ((rc = grow(c, c->d_sc, nz * sizeof(SpanCopyRow)))) return rc;
     SpanCopyRow* const rows = (SpanCopyRow*)c->h_sc.p;
     SpanCopyPlan p = { 0, 0 };
-    for (u64 i = 0; i < n; i++) (void)span_copy_emit(in[i].src, in[i].dst, in[i].len, rows, p);
+    for (u64 i = 0; i < n; i++) { const zpk_span_copy s = row(i); (void)span_copy_emit(s.src, s.dst, s.len, rows, p); }
     HIPCHK(c, hipMemcpyAsync(c->d_sc, rows, p.nrows * sizeof(SpanCopyRow), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->sc_ev, st));
     c->sc_pending = true;
@@ -894,6 +969,7 @@ static int span_copy_enqueue(zpk_codec* c, const zpk_span_copy* in, u64 n, hipSt
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
 }
+}  // extern "C++"
 
 // XXH3-64 of `nspans` long spans of `base` (xxh3_span.h): enqueues the upload of the span list and the two kernels; the hashes stay on
 // the device, *d_hash_out says where (inside c->d_xpart, valid until the next call that hashes spans).  `h_spans` must stay as it is
@@ -1277,6 +1353,18 @@ static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t*
     for (int k = 0; k < 2 && e == hipSuccess; k++) if (used[k]) e = hipEventSynchronize(evs[k]);
     return ZPK_OK;
 }
+
+// The sources of a sub-batch into the staging c->d_src[0, in_total), entry i at off(i) with len(i) bytes (encode_batch_host_any, dsink_sub):
+// DEVICE sources by ONE launch of k_span_copy, a single host source as it is, several gathered through the pinned buffers (h2d_gather).
+// `e` as h2d_gather leaves it: the caller's table upload follows it and reports both.
+template <class OffFn, class LenFn>
+static int stage_sources(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, u64 n, OffFn off, LenFn len, u64 in_total, hipStream_t st, hipError_t& e)
+{
+    e = hipSuccess;
+    if (dsrc) return span_copy_enqueue(c, n, [&](u64 i) { return zpk_span_copy{ (u64)src_ptrs[i], (u64)(c->d_src + off(i)), len(i) }; }, st);
+    if (n == 1) { if (len(0)) e = hipMemcpyAsync(c->d_src, src_ptrs[0], len(0), hipMemcpyHostToDevice, st); return ZPK_OK; }
+    return h2d_gather(c, c->d_src, in_total, n, src_ptrs, off, len, e, st);
+}
 }  // extern "C++"
 
 // the staged image is followed by ZPK_SRC_SLACK bytes of the codec's own: the kernels may READ ZPK_SRC_READ_SLACK bytes past its
@@ -1324,10 +1412,7 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
     }
     if (ddst) {
         // DEVICE destinations: the same bytes — [slot, slot + produced) of every entry — by ONE launch of k_span_copy, no host in between
-        std::vector<zpk_span_copy> sp;
-        try { sp.reserve(n); } catch (...) { return ZPK_E_NOMEM; }
-        for (u64 i = 0; i < n; i++) if (results[i].produced) sp.push_back(zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], results[i].produced });
-        if ((rc = span_copy_enqueue(c, sp.data(), sp.size(), c->stream))) return rc;
+        if ((rc = span_copy_enqueue(c, n, [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], results[i].produced }; }, c->stream))) return rc;
         e = hipStreamSynchronize(c->stream);
     } else if (n > 1 && produced_total && produced_total * 2 >= out_total) {
         // dense: the slots come back in pieces of ZPK_PIN_CHUNK bytes through two PINNED staging buffers — piece j + 1 is on the bus
@@ -1461,7 +1546,6 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         // DEVICE destinations (zpk_codec_decode_batch_host_dptr): there is no download.  Piece by piece, as soon as its decode has run: the
         // verdicts come home and ONE k_span_copy on the download stream moves the piece's slots to their pointers — [slot, slot + produced),
         // the bytes the scatter below copies — while the upload and the decode of the pieces behind it go on.
-        std::vector<zpk_span_copy> sp;
         for (int k = 0; k < np && rc == ZPK_OK && e == hipSuccess; k++) {
             int l;
             while ((l = launched.load()) >= 0 && l <= k) std::this_thread::yield();
@@ -1471,14 +1555,10 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             if (e == hipSuccess) e = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->s_dn);
             if (e == hipSuccess) e = hipStreamSynchronize(c->s_dn);
             if (e != hipSuccess) break;
-            try {
-                sp.clear();
-                for (u64 i = P.e0; i < P.e1; i++) {
-                    const u64 p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
-                    if (p) sp.push_back(zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], p });
-                }
-            } catch (...) { rc = ZPK_E_NOMEM; break; }
-            rc = span_copy_enqueue(c, sp.data(), sp.size(), c->s_dn);
+            rc = span_copy_enqueue(c, P.e1 - P.e0, [&](u64 k2) {
+                const u64 i = P.e0 + k2, p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
+                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], p };
+            }, c->s_dn);
         }
     } else
     rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; },
@@ -1792,9 +1872,8 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         c->big_last[0]++; c->big_last[1] += (u32)E.nsub;
     }
     if (ddst) {                                                                        // DEVICE destinations: one launch of k_span_copy
-        std::vector<zpk_span_copy> sp;
-        for (u64 k = 0; k < ng; k++) if (!redo[g0 + k]) sp.push_back(zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], desc[be[g0 + k].idx].uncomp_size });
-        if ((rc = span_copy_enqueue(c, sp.data(), sp.size(), c->stream))) return rc;
+        auto row = [&](u64 k) { return zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size }; };
+        if ((rc = span_copy_enqueue(c, ng, row, c->stream))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ZPK_OK;
     }
@@ -1906,11 +1985,8 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    if (ddst) {                                                                       // the pointer check: before anything is enqueued
-        span_check_begin(c);
-        for (u64 i = 0; i < n; i++)
-            if (!span_ptr_ok(c, dst_ptrs[i], desc[i].dst_capacity)) { snprintf(c->err, sizeof(c->err), "destination %llu is not %llu bytes of one allocation on device %d", (unsigned long long)i, (unsigned long long)desc[i].dst_capacity, c->device); return ZPK_E_INVALID; }
-    }
+    // the pointer rule (PtrRule): before anything is enqueued
+    if (ddst && PtrRule(c).batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
     begin_decode_call(c);
     // ---- which entries are sequences of frames worth decoding frame-parallel ----
     std::vector<BigEntry> be;
@@ -1992,19 +2068,11 @@ int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    span_check_begin(c);
-    for (u64 i = 0; i < n; i++)
-        if (!span_ptr_ok(c, (const void*)rows[i].src, rows[i].len) || !span_ptr_ok(c, (const void*)rows[i].dst, rows[i].len)) {
-            snprintf(c->err, sizeof(c->err), "span %llu does not lie inside one allocation on device %d", (unsigned long long)i, c->device); return ZPK_E_INVALID;
-        }
-    return span_copy_enqueue(c, rows, n, stream ? (hipStream_t)stream : c->stream);
-}
-
-int zpk_codec_pointer_device(const void* ptr)
-{
-    hipPointerAttribute_t at;
-    if (!ptr || hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return -1; }
-    return at.type == hipMemoryTypeDevice ? at.device : -1;
+    PtrRule rule(c);                                                                  // the pointer rule, on both ends of every span
+    auto len = [&](u64 i) { return (u64)rows[i].len; };
+    if (rule.batch("span source", n, [&](u64 i) { return (const void*)rows[i].src; }, len) ||
+        rule.batch("span destination", n, [&](u64 i) { return (const void*)rows[i].dst; }, len)) return ZPK_E_INVALID;
+    return span_copy_enqueue(c, n, [&](u64 i) { return rows[i]; }, stream ? (hipStream_t)stream : c->stream);
 }
 
 uint64_t zpk_codec_packed_stride(uint64_t uncomp_size) { return span_copy_packed_stride(uncomp_size); }
@@ -2230,11 +2298,9 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
     c->dimage_last[0] = c->dimage_last[1] = c->dimage_last[2] = 0;
     if (n == 0) return ZPK_OK;
     const bool ddst = dst_on_device != 0;
-    span_check_begin(c);                                                              // the pointer checks: before anything is enqueued
-    if (!span_ptr_ok(c, d_archive, archive_size)) { snprintf(c->err, sizeof(c->err), "the archive is not %llu bytes of one allocation on device %d", (unsigned long long)archive_size, c->device); return ZPK_E_INVALID; }
-    if (ddst)
-        for (u64 i = 0; i < n; i++)
-            if (!span_ptr_ok(c, dst_ptrs[i], desc[i].dst_capacity)) { snprintf(c->err, sizeof(c->err), "destination %llu is not %llu bytes of one allocation on device %d", (unsigned long long)i, (unsigned long long)desc[i].dst_capacity, c->device); return ZPK_E_INVALID; }
+    PtrRule rule(c);                                                                  // the pointer rule: before anything is enqueued
+    if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
+    if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
     begin_decode_call(c);
     const u64 chunk = dimage_chunk(c->dimage_chunk);
     auto slot = [&](u64 i) { return dimage_slot(desc[i].method == ZPK_METHOD_NONE, desc[i].uncomp_size, desc[i].dst_capacity); };
@@ -2275,26 +2341,6 @@ int zpk_codec_dimage_stats(zpk_codec* c, uint32_t out[4])
     CodecLock lk(c);
     out[0] = c->dimage_last[0]; out[1] = c->dimage_last[1]; out[2] = c->dimage_last[2]; out[3] = 0;
     return ZPK_OK;
-}
-
-// instance-free: [d_src, d_src + bytes) home, when it is that many bytes of one allocation in device memory (span_copy_in_range)
-int zpk_codec_fetch_device(const void* d_src, void* host_dst, uint64_t bytes)
-{
-    if (zpk_codec_device_count() <= 0) return ZPK_E_NO_DEVICE;
-    if (bytes == 0) return ZPK_OK;
-    hipPointerAttribute_t at;
-    if (!d_src || hipPointerGetAttributes(&at, d_src) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_INVALID; }
-    if (at.type != hipMemoryTypeDevice) return ZPK_E_INVALID;
-    int was = -1;
-    if (hipGetDevice(&was) != hipSuccess) { (void)hipGetLastError(); was = -1; }
-    if (was != at.device && hipSetDevice(at.device) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_LAUNCH; }
-    hipDeviceptr_t base = nullptr; size_t size = 0;
-    int rc = ZPK_OK;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_src) != hipSuccess) { (void)hipGetLastError(); rc = ZPK_E_INVALID; }
-    else if (!span_copy_in_range((u64)d_src, bytes, (u64)base, size)) rc = ZPK_E_INVALID;
-    else if (host_dst && hipMemcpy(host_dst, d_src, bytes, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = ZPK_E_LAUNCH; }
-    if (was >= 0 && was != at.device) (void)hipSetDevice(was);
-    return rc;
 }
 
 int zpk_codec_hash_batch_device(zpk_codec* c, const uint8_t* src, const uint64_t* offsets, const uint64_t* sizes, uint64_t n,

@@ -1,7 +1,8 @@
-// zpk_dsink.inc — a batch compressed INTO A BOUNDED SINK IN THE CALLER'S DEVICE MEMORY (zpk_codec_encode_batch_dsink) and the small
-// host-built blocks that go there (zpk_codec_store_device): what libzpack_amd.so writes an archive image in device memory with
-// (zpack_amd.h: zpack_amd_init_writer_device).  The rules are dsink_plan.h's, the two kernels sink_commit.h's; they are compiled in a file
-// of their own (sink_commit.hip), as k_span_copy is.
+// zpk_dsink.inc — a batch compressed INTO A BOUNDED SINK IN THE CALLER'S DEVICE MEMORY (zpk_codec_encode_batch_dsink): what libzpack_amd.so
+// writes an archive image in device memory with (zpack_amd.h: zpack_amd_init_writer_device).  The rules are dsink_plan.h's, the two kernels
+// sink_commit.h's; they are compiled in a file of their own (sink_commit.hip), as k_span_copy is.  What it shares with the other
+// device-memory paths is in zpk_codec.hip: the pointer rule (PtrRule over device_range_of), the staging of a sub-batch's sources
+// (stage_sources) and the checked copy behind zpk_codec_store_device, with which the small host-built blocks go to the sink.
 namespace zpk {
 void sink_commit_launch(const u8* d_slots, const u64* d_slot_off, const zpk_encode_result* d_res, const u64* d_offsets, const u64* d_span_first,
                         u32 n, u64 room, u64* d_rec, u8* d_sink, u32 grid, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
@@ -45,17 +46,8 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
         (rc = grow(c, c->d_sink_tab, o_slot + m * sizeof(u64)))) return rc;
     hipStream_t st = c->stream;
     hipError_t e = hipSuccess;
-    if (dsrc) {                                                                       // DEVICE sources: ONE launch of k_span_copy, as zpk_codec_encode_batch_dsrc
-        std::vector<zpk_span_copy> sp;
-        try { sp.reserve(m); } catch (...) { return ZPK_E_NOMEM; }
-        for (u64 i = 0; i < m; i++) if (desc[i].size) sp.push_back(zpk_span_copy{ (u64)src_ptrs[i], (u64)(c->d_src + hd[i].src_offset), desc[i].size });
-        if ((rc = span_copy_enqueue(c, sp.data(), sp.size(), st))) return rc;
-    }
-    else if (m == 1) { if (desc[0].size) e = hipMemcpyAsync(c->d_src, src_ptrs[0], desc[0].size, hipMemcpyHostToDevice, st); }
-    else {
-        const int grc = h2d_gather(c, c->d_src, in_total, m, src_ptrs, [&](u64 i) { return (u64)hd[i].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, e, st);
-        if (grc) return grc;
-    }
+    // the sources, as zpk_codec_encode_batch_host / _dsrc stage them (zpk_codec.hip, stage_sources)
+    if ((rc = stage_sources(c, src_ptrs, dsrc, m, [&](u64 i) { return (u64)hd[i].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, in_total, st, e))) return rc;
     u8* const tab = c->d_sink_tab;
     zpk_encode_result* const d_res = (zpk_encode_result*)tab;
     u64* const d_rec = (u64*)(tab + o_rec); u64* const d_off = (u64*)(tab + o_off); u64* const d_slot = (u64*)(tab + o_slot);
@@ -89,26 +81,6 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
 
 extern "C" {
 
-// instance-free, the mirror of zpk_codec_fetch_device: [host_src, + bytes) to d_dst, when that is `bytes` bytes of one allocation in device memory
-int zpk_codec_store_device(void* d_dst, const void* host_src, uint64_t bytes)
-{
-    if (zpk_codec_device_count() <= 0) return ZPK_E_NO_DEVICE;
-    if (bytes == 0) return ZPK_OK;
-    hipPointerAttribute_t at;
-    if (!d_dst || hipPointerGetAttributes(&at, d_dst) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_INVALID; }
-    if (at.type != hipMemoryTypeDevice) return ZPK_E_INVALID;
-    int was = -1;
-    if (hipGetDevice(&was) != hipSuccess) { (void)hipGetLastError(); was = -1; }
-    if (was != at.device && hipSetDevice(at.device) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_LAUNCH; }
-    hipDeviceptr_t base = nullptr; size_t size = 0;
-    int rc = ZPK_OK;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_dst) != hipSuccess) { (void)hipGetLastError(); rc = ZPK_E_INVALID; }
-    else if (!span_copy_in_range((u64)d_dst, bytes, (u64)base, size)) rc = ZPK_E_INVALID;
-    else if (host_src && hipMemcpy(d_dst, host_src, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); rc = ZPK_E_LAUNCH; }
-    if (was >= 0 && was != at.device) (void)hipSetDevice(was);
-    return rc;
-}
-
 int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,
                                  uint8_t* d_sink, uint64_t sink_room_bytes, zpk_encode_result* results, uint64_t* placed, uint64_t* bytes)
 {
@@ -118,14 +90,16 @@ int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, i
     c->dsink_last[0] = c->dsink_last[1] = 0;
     if (n == 0) return ZPK_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    // the pointer check: before anything is enqueued.  The sink and device sources lie inside one allocation each on this device; a host
-    // source is not device memory (a device pointer in a host array would be read by the host)
-    span_check_begin(c);
-    if (!span_ptr_ok(c, d_sink, sink_room_bytes)) { snprintf(c->err, sizeof(c->err), "the sink is not %llu bytes of one allocation on device %d", (unsigned long long)sink_room_bytes, c->device); return ZPK_E_INVALID; }
-    for (u64 i = 0; i < n; i++) {
-        const bool ok = src_on_device ? span_ptr_ok(c, src_ptrs[i], desc[i].size) : (desc[i].size == 0 || (src_ptrs[i] && zpk_codec_pointer_device(src_ptrs[i]) < 0));
-        if (!ok) { snprintf(c->err, sizeof(c->err), "source %llu is not %llu bytes of %s memory", (unsigned long long)i, (unsigned long long)desc[i].size, src_on_device ? "this device's" : "host"); return ZPK_E_INVALID; }
-    }
+    // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued.  The sink and device sources lie inside one allocation each on
+    // this device; a host source with bytes is not device memory (the host would read through such a pointer)
+    PtrRule rule(c);
+    if (rule.batch("sink", 1, [&](u64) { return d_sink; }, [&](u64) { return (u64)sink_room_bytes; }) ||
+        (src_on_device && rule.batch("source", n, [&](u64 i) { return src_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].size; }))) return ZPK_E_INVALID;
+    for (u64 i = 0; i < n && !src_on_device; i++)
+        if (desc[i].size && (!src_ptrs[i] || zpk_codec_pointer_device(src_ptrs[i]) >= 0)) {
+            snprintf(c->err, sizeof(c->err), "source %llu is not %llu bytes of host memory (the codec of device %d reads it on the host)", (unsigned long long)i, (unsigned long long)desc[i].size, c->device);
+            return ZPK_E_INVALID;
+        }
     const u64 chunk = dimage_chunk(c->dimage_chunk);
     SinkChain ch = { 0, 0, true };
     for (u64 first = 0; first < n && ch.open; ) {

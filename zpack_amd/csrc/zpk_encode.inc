@@ -1597,11 +1597,8 @@ static int encode_batch_host_any(zpk_codec* c, const uint8_t* const* src_ptrs, c
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    if (dsrc) {                                                                       // the pointer check: before anything is enqueued
-        span_check_begin(c);
-        for (u64 i = 0; i < n; i++)
-            if (!span_ptr_ok(c, src_ptrs[i], desc[i].size)) { snprintf(c->err, sizeof(c->err), "source %llu is not %llu bytes of one allocation on device %d", (unsigned long long)i, (unsigned long long)desc[i].size, c->device); return ZPK_E_INVALID; }
-    }
+    // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued
+    if (dsrc && PtrRule(c).batch("source", n, [&](u64 i) { return src_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].size; })) return ZPK_E_INVALID;
     const u64 split_min = c->enc_split_min;
     u64 np = 0, nsplit = 0;
     for (u64 i = 0; i < n; i++) { np += enc_piece_count(split_min, desc[i]); nsplit += enc_is_split(split_min, desc[i]); }
@@ -1635,20 +1632,8 @@ static int encode_batch_host_any(zpk_codec* c, const uint8_t* const* src_ptrs, c
         (rc = grow(c, c->d_desc, np * sizeof(zpk_encode_desc))) ||
         (rc = grow(c, c->d_res, np * sizeof(zpk_encode_result)))) return rc;
     hipError_t e = hipSuccess;
-    // the sources go up through the pinned staging buffers, gathered piece by piece (zpk_codec.hip, h2d_gather); a single large entry
-    // goes as it is
-    if (dsrc) {
-        // DEVICE sources: entry i to its place in the staging, hd[first[i]].src_offset, all of them by ONE launch of k_span_copy
-        std::vector<zpk_span_copy> sp;
-        try { sp.reserve(n); } catch (...) { return ZPK_E_NOMEM; }
-        for (u64 i = 0; i < n; i++) if (desc[i].size) sp.push_back(zpk_span_copy{ (u64)src_ptrs[i], (u64)(c->d_src + hd[first[i]].src_offset), desc[i].size });
-        if ((rc = span_copy_enqueue(c, sp.data(), sp.size(), c->stream))) return rc;
-    }
-    else if (n == 1) { if (desc[0].size) e = hipMemcpyAsync(c->d_src, src_ptrs[0], desc[0].size, hipMemcpyHostToDevice, c->stream); }
-    else {
-        const int grc = h2d_gather(c, c->d_src, in_total, n, src_ptrs, [&](u64 i) { return (u64)hd[first[i]].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, e, c->stream);
-        if (grc) return grc;
-    }
+    // the sources go up, entry i to its place in the staging, hd[first[i]].src_offset (zpk_codec.hip, stage_sources)
+    if ((rc = stage_sources(c, src_ptrs, dsrc, n, [&](u64 i) { return (u64)hd[first[i]].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, in_total, c->stream, e))) return rc;
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_desc, hd, np * sizeof(zpk_encode_desc), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     rc = zpk_codec_encode_batch_device(c, c->d_src, in_total, (const zpk_encode_desc*)c->d_desc, np, c->d_dst, out_total,

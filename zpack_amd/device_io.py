@@ -146,36 +146,45 @@ def read_files_device(archive, names=None, device=0):
         L.zpack_close_reader(C.byref(r))
 
 
-def write_files_device(path, tensors, method=METHOD_LZ4, level=0):
-    """Writes the archive `path` with one entry per item of `tensors` ({name: CUDA tensor}, all on one device; any dtype: an entry is the
-    tensor's bytes in memory order).  path None: the archive is built on the heap and returned as bytes."""
-    L = lib()
+def _flatten(tensors, who):
+    """{name: CUDA tensor} as ([(name, tensor)], [its bytes in memory order as a flat uint8 tensor])"""
     items = list(tensors.items())
     flat = [t.contiguous().reshape(-1).view(dtype=_u8()) for _, t in items]
     for t in flat:
         if not t.is_cuda:
-            raise ValueError("write_files_device takes CUDA tensors (zpack_write_files is the call for host memory)")
+            raise ValueError("%s takes CUDA tensors (zpack_write_files is the call for host memory)" % who)
+    return items, flat
+
+
+def _write_archive(L, w, items, flat, method, level):
+    """The body both writers share: header, data signature, the entries out of device memory, CDR and EOCDR into the opened writer `w`"""
+    opts = CompressOptions(int(method), int(level))
+    arr = (File * max(len(items), 1))()
+    for i, ((name, _), t) in enumerate(zip(items, flat)):
+        arr[i].filename = name.encode()
+        arr[i].buffer = t.data_ptr() if t.numel() else None
+        arr[i].size = t.numel()
+        arr[i].options = C.pointer(opts)
+        arr[i].cctx = None
+    _check(L.zpack_write_header(C.byref(w)), "zpack_write_header")
+    _check(L.zpack_write_data_header(C.byref(w)), "zpack_write_data_header")
+    _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
+    _check(L.zpack_write_cdr(C.byref(w)), "zpack_write_cdr")
+    _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
+
+
+def write_files_device(path, tensors, method=METHOD_LZ4, level=0):
+    """Writes the archive `path` with one entry per item of `tensors` ({name: CUDA tensor}, all on one device; any dtype: an entry is the
+    tensor's bytes in memory order).  path None: the archive is built on the heap and returned as bytes."""
+    L = lib()
+    items, flat = _flatten(tensors, "write_files_device")
     w = Writer()
     _check(L.zpack_init_writer(C.byref(w), os.fsencode(path)) if path is not None else L.zpack_init_writer_heap(C.byref(w), 0), "zpack_init_writer")
     try:
-        opts = CompressOptions(int(method), int(level))
-        arr = (File * max(len(items), 1))()
-        for i, ((name, _), t) in enumerate(zip(items, flat)):
-            arr[i].filename = name.encode()
-            arr[i].buffer = t.data_ptr() if t.numel() else None
-            arr[i].size = t.numel()
-            arr[i].options = C.pointer(opts)
-            arr[i].cctx = None
         if flat:
             _settle(flat[0].device)
-        _check(L.zpack_write_header(C.byref(w)), "zpack_write_header")
-        _check(L.zpack_write_data_header(C.byref(w)), "zpack_write_data_header")
-        _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
-        _check(L.zpack_write_cdr(C.byref(w)), "zpack_write_cdr")
-        _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
-        if path is None:
-            return C.string_at(w.buffer, w.file_size)
-        return None
+        _write_archive(L, w, items, flat, method, level)
+        return C.string_at(w.buffer, w.file_size) if path is None else None
     finally:
         L.zpack_close_writer(C.byref(w))
 
@@ -200,11 +209,7 @@ def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None):
     """
     import torch
     L = lib()
-    items = list(tensors.items())
-    flat = [t.contiguous().reshape(-1).view(dtype=_u8()) for _, t in items]
-    for t in flat:
-        if not t.is_cuda:
-            raise ValueError("write_archive_device takes CUDA tensors")
+    items, flat = _flatten(tensors, "write_archive_device")
     dev = flat[0].device if flat else torch.device("cuda", 0)
     if capacity is None:
         capacity = archive_capacity([t.numel() for t in flat], [name for name, _ in items], method)
@@ -213,19 +218,7 @@ def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None):
     _settle(dev)
     _check(L.zpack_amd_init_writer_device(C.byref(w), image.data_ptr(), int(capacity)), "zpack_amd_init_writer_device")
     try:
-        opts = CompressOptions(int(method), int(level))
-        arr = (File * max(len(items), 1))()
-        for i, ((name, _), t) in enumerate(zip(items, flat)):
-            arr[i].filename = name.encode()
-            arr[i].buffer = t.data_ptr() if t.numel() else None
-            arr[i].size = t.numel()
-            arr[i].options = C.pointer(opts)
-            arr[i].cctx = None
-        _check(L.zpack_write_header(C.byref(w)), "zpack_write_header")
-        _check(L.zpack_write_data_header(C.byref(w)), "zpack_write_data_header")
-        _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
-        _check(L.zpack_write_cdr(C.byref(w)), "zpack_write_cdr")
-        _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
+        _write_archive(L, w, items, flat, method, level)
         return image[:int(w.file_size)]
     finally:
         L.zpack_close_writer(C.byref(w))

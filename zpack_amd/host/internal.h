@@ -1,5 +1,8 @@
-/* internal.h — shared by the host-side zpack.h implementation (reader.c, writer.c, stream.c, util.c).
- * Nothing here is part of the public API. */
+/* internal.h — shared by the host-side zpack.h implementation (reader.c, writer.c, readahead.c, stream.c, util.c).
+ * Nothing here is part of the public API.  util.c holds what more than one file needs: the contexts and their codec lookup
+ * (zi_ctx_codec_on, zi_ctx_codec_of), the mapping of a codec's return (zi_rc_of_codec), the static shard (zi_shard) and the one
+ * side-table implementation (zi_side_*) behind the readers' and the writers' records; writer.c holds the one way a file is entered
+ * (zi_writer_enter). */
 #ifndef ZPACK_AMD_INTERNAL_H
 #define ZPACK_AMD_INTERNAL_H
 
@@ -7,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <sys/types.h>
+#include <pthread.h>
 #include "zpack.h"
 #include "zpack_codec.h"
 
@@ -32,8 +36,9 @@ void    zi_ctx_destroy(zi_ctx* x);
 void    zi_ctx_reset(zi_ctx* x);
 /* resolve the context of a call: the explicit one, else the owner's (created on first use, freed by zpack_close_*) */
 zi_ctx* zi_pick_ctx(void* explicit_ctx, void** owner_slot);
-/* contiguous split of `count` weighted items into `parts` ranges: cut[0..parts] */
-void zi_split(const zpack_u64* w, zpack_u64 count, int parts, zpack_u64* cut);
+/* the static shard of a batch over the context's codecs: contiguous ranges of about equal weight(items, i), at most one
+ * per codec and per item, cut[k] .. cut[k + 1] for k in [0, parts); returns parts (1: one codec, one item, or no memory for the weights) */
+int zi_shard(zi_ctx* ctx, zpack_u64 count, zpack_u64 (*weight)(const void* items, zpack_u64 i), const void* items, zpack_u64* cut);
 void zi_parallel(int parts, void (*fn)(void*, int), void* arg);
 /* name index of reader-owned entry tables (zpack_get_file_entry) */
 void zi_index_register(const zpack_file_entry* table, zpack_u64 count);
@@ -54,6 +59,24 @@ int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry
  * pointer / size to the next, the arrays may be fields of structs).  *rc = ZPACK_OK with NULL: no entry has bytes, any codec serves;
  * ZPACK_ERROR_STREAM_INVALID: bytes, but no device pointer; ZPACK_ERROR_NOT_AVAILABLE: a device the context does not hold */
 zpk_codec* zi_ctx_codec_of(zi_ctx* ctx, const void* ptrs, size_t ptr_stride, const void* sizes, size_t size_stride, int size_is_u64, zpack_u64 n, int* rc);
+/* the codec of `ctx` on HIP device `device`, NULL when the context holds none */
+zpk_codec* zi_ctx_codec_on(zi_ctx* ctx, int device);
+/* what a batch call of the codec returned, as the library reports it: ZPK_E_INVALID (the pointer rule turned something down) is
+ * ZPACK_ERROR_STREAM_INVALID, any other failure ZPACK_ERROR_NOT_AVAILABLE */
+int zi_rc_of_codec(int crc);
+
+/* side tables (util.c): records kept beside structs of fixed layout, keyed by the struct's address.  One implementation, two instances —
+ * the readers' (readahead.c: word = the generation) and the writers' (writer.c: word = the image's capacity) — and never one table for
+ * both: a closed reader's address may become a writer's.  find -> 1 and *out, 0 when there is no record; set creates or replaces -> 1,
+ * 0 when there is no memory for the record; drop forgets (a missing key: nothing). */
+typedef struct { const void* image; zpack_u64 word; int device; } zi_side_rec;
+typedef struct zi_side_node_s { const void* key; zi_side_rec rec; struct zi_side_node_s* next; } zi_side_node;
+#define ZI_SIDE_BUCKETS 64
+typedef struct { pthread_rwlock_t mu; zi_side_node* bucket[ZI_SIDE_BUCKETS]; } zi_side_table;
+#define ZI_SIDE_TABLE_INIT { PTHREAD_RWLOCK_INITIALIZER, { NULL } }
+int  zi_side_find(zi_side_table* t, const void* key, zi_side_rec* out);
+int  zi_side_set(zi_side_table* t, const void* key, const zi_side_rec* rec);
+void zi_side_drop(zi_side_table* t, const void* key);
 
 /* read-ahead for in-order zpack_read_file callers (readahead.c) */
 struct zi_ra_s* zi_ra_create(void);          /* reads ZPACK_AMD_READ_AHEAD; NULL when out of memory (read-ahead is then off) */
@@ -68,7 +91,7 @@ void zi_ra_step(zi_ctx* ctx, zpack_reader* reader, const zpack_file_entry* entry
 void      zi_reader_gen_new(const zpack_reader* reader);
 void      zi_reader_gen_drop(const zpack_reader* reader);
 zpack_u64 zi_reader_gen(const zpack_reader* reader);
-/* ... and, in the same record, the image of a reader opened by zpack_amd_init_reader_device (zpack_reader has a fixed layout and no field
+/* ... and, in the same record of the readers' side table, the image of a reader opened by zpack_amd_init_reader_device (zpack_reader has a fixed layout and no field
  * for it): set -> 1, 0 when there is no memory for the record; get -> the image (*device: its HIP ordinal), NULL for any other reader.
  * zi_reader_gen_drop forgets it with the record. */
 int         zi_reader_dimage_set(const zpack_reader* reader, const void* d_image, int device);
@@ -90,8 +113,8 @@ typedef struct zi_stream_state_s {
 } zi_stream_state;
 
 /* Is a writer opened, and on what: its FILE, its growing heap buffer, or a bounded image in device memory (zpack_amd_init_writer_device:
- * *d_image, *capacity, *device; each may be NULL).  zpack_writer has a fixed layout and no field for the image: it is kept in a side table
- * keyed by the writer's address (writer.c), which is only asked when the writer has neither a file nor a buffer.  A record that outlived
+ * *d_image, *capacity, *device; each may be NULL).  zpack_writer has a fixed layout and no field for the image: it is kept in the writers' side
+ * table (zi_side_table, above), which is only asked when the writer has neither a file nor a buffer.  A record that outlived
  * its writer (a struct never closed whose address serves again) is replaced by the next zpack_amd_init_writer_device there, dropped by the
  * other inits and by zpack_close_writer, and does not answer for a struct whose buffer_capacity is not the record's capacity — a zeroed
  * struct is ZPACK_ERROR_WRITER_NOT_OPENED. */
@@ -104,5 +127,9 @@ void zi_writer_dsink_drop(const zpack_writer* w);
  * device image writes nothing: ZPACK_ERROR_BUFFER_TOO_SMALL, the offsets do not move. */
 int zi_writer_put(zpack_writer* w, const zpack_u8* data, size_t size);
 zpack_file_entry* zi_writer_push_entry(zpack_writer* w);
+/* a file entered into the writer's table under a copy of `name`: ZPACK_OK, or ZPACK_ERROR_MALLOC_FAILED */
+int zi_writer_enter(zpack_writer* w, const char* name, zpack_u64 offset, zpack_u64 comp_size, zpack_u64 uncomp_size, zpack_u64 hash, zpack_u8 method);
+/* the offset guard of a raw entry against its image (lib/zpack_write.c:345-428): the payload lies inside file_size bytes */
+static inline int zi_entry_in_image(const zpack_file_entry* e, zpack_u64 file_size) { return e->offset < file_size && e->comp_size <= file_size - e->offset; }
 
 #endif

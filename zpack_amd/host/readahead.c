@@ -54,64 +54,41 @@ typedef struct zi_ra_s {
 /* ------------------------------------------------------------------ reader generations
  * zpack_reader has the reference's fixed layout: the generation of a reader lives in a side table keyed by its address. */
 
-typedef struct zi_gen_s { const zpack_reader* reader; zpack_u64 gen; const void* d_image; int device; struct zi_gen_s* next; } zi_gen;   /* d_image: zpack_amd_init_reader_device */
-#define ZI_GEN_BUCKETS 64
-static pthread_rwlock_t g_gen_mu = PTHREAD_RWLOCK_INITIALIZER;     /* every zpack_read_file reads it: shared */
-static zi_gen* g_gen[ZI_GEN_BUCKETS];
+static zi_side_table g_readers = ZI_SIDE_TABLE_INIT;     /* image: zpack_amd_init_reader_device's; word: the generation */
 static zpack_u64 g_gen_next = 1;
-
-static zi_gen** gen_slot(const zpack_reader* reader)
-{
-    zi_gen** pp = &g_gen[((uintptr_t)reader >> 4) % ZI_GEN_BUCKETS];
-    while (*pp && (*pp)->reader != reader) pp = &(*pp)->next;
-    return pp;
-}
+/* zi_reader_gen_new and zi_reader_dimage_set read a record and write it back in two steps of the table, so they are not atomic per record:
+ * both run while a reader is opened or parsed, which one thread does; the finds of other threads see the old record or the new one whole. */
 
 void zi_reader_gen_new(const zpack_reader* reader)
 {
-    pthread_rwlock_wrlock(&g_gen_mu);
-    zi_gen** pp = gen_slot(reader);
-    if (!*pp && (*pp = (zi_gen*)calloc(1, sizeof(zi_gen))) != NULL) (*pp)->reader = reader;
-    if (*pp) (*pp)->gen = g_gen_next++;             /* (out of memory: no generation, so this reader never reads ahead) */
-    pthread_rwlock_unlock(&g_gen_mu);
+    zi_side_rec r = { NULL, 0, -1 };
+    (void)zi_side_find(&g_readers, reader, &r);             /* (a record at this address keeps its image) */
+    r.word = __atomic_fetch_add(&g_gen_next, 1, __ATOMIC_RELAXED);
+    (void)zi_side_set(&g_readers, reader, &r);              /* (out of memory: no generation, so this reader never reads ahead) */
 }
 
-void zi_reader_gen_drop(const zpack_reader* reader)
-{
-    pthread_rwlock_wrlock(&g_gen_mu);
-    zi_gen** pp = gen_slot(reader);
-    if (*pp) { zi_gen* g = *pp; *pp = g->next; free(g); }
-    pthread_rwlock_unlock(&g_gen_mu);
-}
+void zi_reader_gen_drop(const zpack_reader* reader) { zi_side_drop(&g_readers, reader); }
 
 zpack_u64 zi_reader_gen(const zpack_reader* reader)
 {
-    pthread_rwlock_rdlock(&g_gen_mu);
-    zi_gen** pp = gen_slot(reader);
-    const zpack_u64 g = *pp ? (*pp)->gen : 0;
-    pthread_rwlock_unlock(&g_gen_mu);
-    return g;
+    zi_side_rec r;
+    return zi_side_find(&g_readers, reader, &r) ? r.word : 0;
 }
 
 int zi_reader_dimage_set(const zpack_reader* reader, const void* d_image, int device)
 {
-    pthread_rwlock_wrlock(&g_gen_mu);
-    zi_gen** pp = gen_slot(reader);
-    if (!*pp && (*pp = (zi_gen*)calloc(1, sizeof(zi_gen))) != NULL) (*pp)->reader = reader;
-    if (*pp) { (*pp)->d_image = d_image; (*pp)->device = device; }
-    const int ok = *pp != NULL;
-    pthread_rwlock_unlock(&g_gen_mu);
-    return ok;
+    zi_side_rec r = { NULL, 0, -1 };
+    (void)zi_side_find(&g_readers, reader, &r);             /* (... and its generation) */
+    r.image = d_image; r.device = device;
+    return zi_side_set(&g_readers, reader, &r);
 }
 
 const void* zi_reader_dimage(const zpack_reader* reader, int* device)
 {
-    pthread_rwlock_rdlock(&g_gen_mu);
-    zi_gen** pp = gen_slot(reader);
-    const void* p = *pp ? (*pp)->d_image : NULL;
-    if (device) *device = p ? (*pp)->device : -1;
-    pthread_rwlock_unlock(&g_gen_mu);
-    return p;
+    zi_side_rec r = { NULL, 0, -1 };
+    (void)zi_side_find(&g_readers, reader, &r);
+    if (device) *device = r.image ? r.device : -1;
+    return r.image;
 }
 
 /* ------------------------------------------------------------------ the window */

@@ -403,6 +403,12 @@ static void read_part(void* arg, int k)
     j->rc[k] = n ? zpk_codec_decode_batch_host(j->ctx->dev[k], j->image, j->image_size, j->desc + lo, n, j->buffers + lo, j->res + lo) : ZPK_OK;
 }
 
+static zpack_u64 entry_weight(const void* entries, zpack_u64 i)
+{
+    const zpack_file_entry* e = ((zpack_file_entry* const*)entries)[i];
+    return e->comp_size + e->uncomp_size;
+}
+
 /* n entries in ONE device batch.  Memory-backed readers hand the codec the archive image itself
  * (zero-copy on the host side, as the reference does at lib/zpack_read.c:345-346); file-backed readers
  * gather the payloads first (the reference mallocs + freads per entry, :336-344). */
@@ -476,36 +482,17 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
     if (rc == ZPACK_OK && from == ZI_SRC_DEVICE && !span) {
         /* the IMAGE in device memory: the compressed bytes stay there — one zpk_codec_decode_batch_dimage call on the codec of the
          * image's device (no shard), the destinations host pointers or, on_device, device pointers on that device */
-        zpk_codec* codec = NULL;
-        for (int k = 0; k < ctx->n && !codec; k++) if (zpk_codec_device(ctx->dev[k]) == d_device) codec = ctx->dev[k];
-        if (!codec) rc = ZPACK_ERROR_NOT_AVAILABLE;
-        else {
-            const int crc = zpk_codec_decode_batch_dimage(codec, d_image, image_size, desc, count, buffers, on_device, res);
-            if (crc != ZPK_OK) rc = crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
-        }
+        zpk_codec* codec = zi_ctx_codec_on(ctx, d_device);
+        rc = codec ? zi_rc_of_codec(zpk_codec_decode_batch_dimage(codec, d_image, image_size, desc, count, buffers, on_device, res)) : ZPACK_ERROR_NOT_AVAILABLE;
     } else if (rc == ZPACK_OK && on_device) {
         zpk_codec* codec = zi_ctx_codec_of(ctx, buffers, sizeof(*buffers), max_sizes, sizeof(*max_sizes), sizeof(size_t) == 8, count, &rc);
         if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: verdicts only) */
-        if (codec) {
-            const int crc = zpk_codec_decode_batch_host_dptr(codec, image, image_size, desc, count, buffers, res);
-            if (crc != ZPK_OK) rc = crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
-        }
+        if (codec) rc = zi_rc_of_codec(zpk_codec_decode_batch_host_dptr(codec, image, image_size, desc, count, buffers, res));
     } else if (rc == ZPACK_OK) {
         read_job job = { ctx, image, image_size, desc, buffers, res, {0}, {0} };
-        int parts = ctx->n;
-        if ((zpack_u64)parts > count) parts = (int)count;
-        if (parts > 1) {
-            /* static shard: contiguous ranges of the batch balanced by comp + uncomp bytes, one host thread
-             * and one codec per device, nothing exchanged; results land in their own slices of res[] */
-            zpack_u64* w = (zpack_u64*)malloc(sizeof(zpack_u64) * (size_t)count);
-            if (!w) parts = 1;
-            else {
-                for (zpack_u64 i = 0; i < count; i++) w[i] = entries[i]->comp_size + entries[i]->uncomp_size;
-                zi_split(w, count, parts, job.cut);
-                free(w);
-            }
-        }
-        if (parts <= 1) { job.cut[0] = 0; job.cut[1] = count; parts = 1; }
+        /* static shard: contiguous ranges of the batch balanced by comp + uncomp bytes, one host thread
+         * and one codec per device, nothing exchanged; results land in their own slices of res[] */
+        const int parts = zi_shard(ctx, count, entry_weight, entries, job.cut);
         zi_parallel(parts, read_part, &job);
         for (int k = 0; k < parts; k++) if (job.rc[k] != ZPK_OK) rc = ZPACK_ERROR_NOT_AVAILABLE;
     }
@@ -562,24 +549,33 @@ int zpack_read_files(zpack_reader* reader, zpack_file_entry* const* entries, zpa
     return read_batch(reader, entries, count, buffers, max_sizes, results, dctx, 0);
 }
 
-int zpack_read_files_packed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
-                            zpack_u8* buffer, size_t buffer_size, zpack_u64* out_offsets, int* results, void* dctx)
+/* the packed reads: entry i lands at the running sum of the strides of the entries before it — its uncomp_size or, on_device, that
+ * rounded up to 256 (zpk_codec_packed_stride), where the sum saturates: a position past every buffer leaves no room. */
+static int read_packed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count, zpack_u8* buffer, size_t buffer_size,
+                       zpack_u64* out_offsets, int* results, void* dctx, int on_device)
 {
-    if (!reader || (count && (!entries || !buffer || !out_offsets || !results))) return ZPACK_ERROR_STREAM_INVALID;
     zpack_u8** bufs = (zpack_u8**)malloc(sizeof(zpack_u8*) * (size_t)(count ? count : 1));
     size_t* caps = (size_t*)malloc(sizeof(size_t) * (size_t)(count ? count : 1));
     if (!bufs || !caps) { free(bufs); free(caps); return ZPACK_ERROR_MALLOC_FAILED; }
     zpack_u64 pos = 0;
     for (zpack_u64 i = 0; i < count; i++) {
         out_offsets[i] = pos;
-        zpack_u64 room = pos <= buffer_size ? buffer_size - pos : 0;
+        const zpack_u64 room = pos <= buffer_size ? buffer_size - pos : 0;
         caps[i] = (size_t)(entries[i]->uncomp_size <= room ? entries[i]->uncomp_size : room);   /* too little room => BUFFER_TOO_SMALL */
         bufs[i] = buffer + (pos <= buffer_size ? pos : buffer_size);
-        pos += entries[i]->uncomp_size;
+        const zpack_u64 stride = on_device ? zpk_codec_packed_stride(entries[i]->uncomp_size) : entries[i]->uncomp_size;
+        pos = on_device && stride > ~(zpack_u64)0 - pos ? ~(zpack_u64)0 : pos + stride;
     }
-    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx, 0);
+    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx, on_device);
     free(bufs); free(caps);
     return rc;
+}
+
+int zpack_read_files_packed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                            zpack_u8* buffer, size_t buffer_size, zpack_u64* out_offsets, int* results, void* dctx)
+{
+    if (!reader || (count && (!entries || !buffer || !out_offsets || !results))) return ZPACK_ERROR_STREAM_INVALID;
+    return read_packed(reader, entries, count, buffer, buffer_size, out_offsets, results, dctx, 0);
 }
 
 /* ---- zpack_amd.h: the same reads with the plaintext in DEVICE memory — thin fronts for read_batch's on_device mode.  They neither use
@@ -597,21 +593,7 @@ int zpack_amd_read_files_device_packed(zpack_reader* reader, zpack_file_entry* c
 {
     if (!reader || (count && (!entries || !d_buffer || !out_offsets || !results))) return ZPACK_ERROR_STREAM_INVALID;
     if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;
-    zpack_u8** bufs = (zpack_u8**)malloc(sizeof(zpack_u8*) * (size_t)(count ? count : 1));
-    size_t* caps = (size_t*)malloc(sizeof(size_t) * (size_t)(count ? count : 1));
-    if (!bufs || !caps) { free(bufs); free(caps); return ZPACK_ERROR_MALLOC_FAILED; }
-    zpack_u64 pos = 0;
-    for (zpack_u64 i = 0; i < count; i++) {
-        out_offsets[i] = pos;
-        const zpack_u64 room = pos <= buffer_size ? buffer_size - pos : 0;
-        caps[i] = (size_t)(entries[i]->uncomp_size <= room ? entries[i]->uncomp_size : room);   /* too little room => BUFFER_TOO_SMALL */
-        bufs[i] = (zpack_u8*)d_buffer + (pos <= buffer_size ? pos : buffer_size);
-        const zpack_u64 stride = zpk_codec_packed_stride(entries[i]->uncomp_size);  /* every entry starts at a multiple of 256 */
-        pos = stride > ~(zpack_u64)0 - pos ? ~(zpack_u64)0 : pos + stride;
-    }
-    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx, 1);
-    free(bufs); free(caps);
-    return rc;
+    return read_packed(reader, entries, count, (zpack_u8*)d_buffer, buffer_size, out_offsets, results, dctx, 1);
 }
 
 static int zi_stream_replay(zpack_reader* reader, const zpack_file_entry* entry, zpk_dstream* d, zpack_u64 upto)

@@ -1,6 +1,6 @@
 /* util.c — codec context plumbing and small helpers for the host library. */
 #include "internal.h"
-#include <pthread.h>
+#include <stdint.h>
 
 /* ------------------------------------------------------------------ contexts
  *
@@ -100,16 +100,66 @@ zpk_codec* zi_ctx_codec_of(zi_ctx* ctx, const void* ptrs, size_t ptr_stride, con
         any_bytes = 1;
         const int ordinal = zpk_codec_pointer_device(*(void* const*)((const char*)ptrs + i * ptr_stride));
         if (ordinal < 0) continue;
-        for (int k = 0; k < ctx->n; k++) if (zpk_codec_device(ctx->dev[k]) == ordinal) return ctx->dev[k];
-        *rc = ZPACK_ERROR_NOT_AVAILABLE;
-        return NULL;
+        zpk_codec* const codec = zi_ctx_codec_on(ctx, ordinal);
+        if (!codec) *rc = ZPACK_ERROR_NOT_AVAILABLE;
+        return codec;
     }
     if (any_bytes) *rc = ZPACK_ERROR_STREAM_INVALID;
     return NULL;
 }
 
-/* split `count` items with weights w[] into x->n contiguous ranges of about equal weight: cut[k] .. cut[k+1] */
-void zi_split(const zpack_u64* w, zpack_u64 count, int parts, zpack_u64* cut)
+zpk_codec* zi_ctx_codec_on(zi_ctx* ctx, int device)
+{
+    for (int k = 0; k < ctx->n; k++) if (zpk_codec_device(ctx->dev[k]) == device) return ctx->dev[k];
+    return NULL;
+}
+
+int zi_rc_of_codec(int crc)
+{
+    return crc == ZPK_OK ? ZPACK_OK : crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
+}
+
+/* ------------------------------------------------------------------ side tables
+ * zpack_reader and zpack_writer have the reference's fixed layouts: what this library keeps beside one of them is a record in a table
+ * keyed by the struct's address.  64 chains under one rwlock per table (every zpack_read_file asks the readers': shared). */
+
+static zi_side_node** side_slot(zi_side_table* t, const void* key)
+{
+    zi_side_node** pp = &t->bucket[((uintptr_t)key >> 4) % ZI_SIDE_BUCKETS];
+    while (*pp && (*pp)->key != key) pp = &(*pp)->next;
+    return pp;
+}
+
+int zi_side_find(zi_side_table* t, const void* key, zi_side_rec* out)
+{
+    pthread_rwlock_rdlock(&t->mu);
+    zi_side_node* const n = *side_slot(t, key);
+    if (n) *out = n->rec;
+    pthread_rwlock_unlock(&t->mu);
+    return n != NULL;
+}
+
+int zi_side_set(zi_side_table* t, const void* key, const zi_side_rec* rec)
+{
+    pthread_rwlock_wrlock(&t->mu);
+    zi_side_node** pp = side_slot(t, key);
+    if (!*pp && (*pp = (zi_side_node*)calloc(1, sizeof(zi_side_node))) != NULL) (*pp)->key = key;
+    if (*pp) (*pp)->rec = *rec;
+    const int ok = *pp != NULL;
+    pthread_rwlock_unlock(&t->mu);
+    return ok;
+}
+
+void zi_side_drop(zi_side_table* t, const void* key)
+{
+    pthread_rwlock_wrlock(&t->mu);
+    zi_side_node** pp = side_slot(t, key);
+    if (*pp) { zi_side_node* n = *pp; *pp = n->next; free(n); }
+    pthread_rwlock_unlock(&t->mu);
+}
+
+/* split `count` items with weights w[] into `parts` contiguous ranges of about equal weight: cut[k] .. cut[k+1] */
+static void zi_split(const zpack_u64* w, zpack_u64 count, int parts, zpack_u64* cut)
 {
     zpack_u64 total = 0;
     for (zpack_u64 i = 0; i < count; i++) total += w[i] + 1;
@@ -121,6 +171,19 @@ void zi_split(const zpack_u64* w, zpack_u64 count, int parts, zpack_u64* cut)
         cut[k] = i;
     }
     cut[parts] = count;
+}
+
+int zi_shard(zi_ctx* ctx, zpack_u64 count, zpack_u64 (*weight)(const void* items, zpack_u64 i), const void* items, zpack_u64* cut)
+{
+    int parts = ctx->n;
+    if ((zpack_u64)parts > count) parts = (int)count;
+    if (parts > 1) {
+        zpack_u64* w = (zpack_u64*)malloc(sizeof(zpack_u64) * (size_t)count);
+        if (!w) parts = 1;
+        else { for (zpack_u64 i = 0; i < count; i++) w[i] = weight(items, i); zi_split(w, count, parts, cut); free(w); }
+    }
+    if (parts <= 1) { cut[0] = 0; cut[1] = count; parts = 1; }
+    return parts;
 }
 
 typedef struct { void (*fn)(void*, int); void* arg; int part; } zi_job;

@@ -16,37 +16,16 @@
 static zpack_u64 pow2_at_least(zpack_u64 n) { zpack_u64 b = 1; while (b < n) b <<= 1; return b; }
 
 /* zpack_amd.h: a writer whose sink is an image in DEVICE memory.  zpack_writer has the reference's fixed layout, so where the image lives
- * is kept beside the writer, in a table keyed by its address (as the readers' records are: readahead.c). */
-typedef struct zi_dsink_s { const zpack_writer* writer; zpack_u8* d_image; size_t capacity; int device; struct zi_dsink_s* next; } zi_dsink;
-#define ZI_DSINK_BUCKETS 64
-static pthread_rwlock_t g_dsink_mu = PTHREAD_RWLOCK_INITIALIZER;
-static zi_dsink* g_dsink[ZI_DSINK_BUCKETS];
-
-static zi_dsink** dsink_slot(const zpack_writer* w)
-{
-    zi_dsink** pp = &g_dsink[((uintptr_t)w >> 4) % ZI_DSINK_BUCKETS];
-    while (*pp && (*pp)->writer != w) pp = &(*pp)->next;
-    return pp;
-}
+ * is kept beside the writer, in the writers' side table (internal.h; as the readers' records are: readahead.c). */
+static zi_side_table g_writers = ZI_SIDE_TABLE_INIT;      /* image: the sink; word: its capacity */
 
 int zi_writer_dsink_set(const zpack_writer* w, void* d_image, size_t capacity, int device)
 {
-    pthread_rwlock_wrlock(&g_dsink_mu);
-    zi_dsink** pp = dsink_slot(w);
-    if (!*pp && (*pp = (zi_dsink*)calloc(1, sizeof(zi_dsink))) != NULL) (*pp)->writer = w;
-    if (*pp) { (*pp)->d_image = (zpack_u8*)d_image; (*pp)->capacity = capacity; (*pp)->device = device; }      /* (a record left at this address: replaced) */
-    const int ok = *pp != NULL;
-    pthread_rwlock_unlock(&g_dsink_mu);
-    return ok;
+    const zi_side_rec r = { d_image, capacity, device };
+    return zi_side_set(&g_writers, w, &r);                /* (a record left at this address: replaced) */
 }
 
-void zi_writer_dsink_drop(const zpack_writer* w)
-{
-    pthread_rwlock_wrlock(&g_dsink_mu);
-    zi_dsink** pp = dsink_slot(w);
-    if (*pp) { zi_dsink* g = *pp; *pp = g->next; free(g); }
-    pthread_rwlock_unlock(&g_dsink_mu);
-}
+void zi_writer_dsink_drop(const zpack_writer* w) { zi_side_drop(&g_writers, w); }
 
 zi_sink zi_writer_sink(const zpack_writer* w, zpack_u8** d_image, size_t* capacity, int* device)
 {
@@ -55,17 +34,13 @@ zi_sink zi_writer_sink(const zpack_writer* w, zpack_u8** d_image, size_t* capaci
     if (device) *device = -1;
     if (w->file) return ZI_SINK_FILE;
     if (w->buffer) return ZI_SINK_HEAP;
-    zi_sink kind = ZI_SINK_NONE;
-    pthread_rwlock_rdlock(&g_dsink_mu);
-    zi_dsink** pp = dsink_slot(w);
-    if (*pp && (*pp)->capacity == w->buffer_capacity) {       /* (a zeroed struct at the address of a writer that was never closed: not this record's) */
-        kind = ZI_SINK_DEVICE;
-        if (d_image) *d_image = (*pp)->d_image;
-        if (capacity) *capacity = (*pp)->capacity;
-        if (device) *device = (*pp)->device;
-    }
-    pthread_rwlock_unlock(&g_dsink_mu);
-    return kind;
+    zi_side_rec r;
+    /* (a zeroed struct at the address of a writer that was never closed: not this record's) */
+    if (!zi_side_find(&g_writers, w, &r) || r.word != (zpack_u64)w->buffer_capacity) return ZI_SINK_NONE;
+    if (d_image) *d_image = (zpack_u8*)r.image;
+    if (capacity) *capacity = (size_t)r.word;
+    if (device) *device = r.device;
+    return ZI_SINK_DEVICE;
 }
 
 /* append `size` bytes at the writer's cursor: file (seek + write), heap (power-of-two growth, like lib/zpack_common.c:83-104) or an
@@ -110,12 +85,32 @@ zpack_file_entry* zi_writer_push_entry(zpack_writer* w)
     return e;
 }
 
-static char* dup_name(const char* s)
+int zi_writer_enter(zpack_writer* w, const char* name, zpack_u64 offset, zpack_u64 comp_size, zpack_u64 uncomp_size, zpack_u64 hash, zpack_u8 method)
 {
-    const size_t n = strlen(s) + 1;
-    char* d = (char*)malloc(n);
-    if (d) memcpy(d, s, n);
-    return d;
+    zpack_file_entry* e = zi_writer_push_entry(w);
+    if (!e) return ZPACK_ERROR_MALLOC_FAILED;
+    const size_t n = strlen(name) + 1;
+    if (!(e->filename = (char*)malloc(n))) return ZPACK_ERROR_MALLOC_FAILED;
+    memcpy(e->filename, name, n);
+    e->offset = offset;
+    e->comp_size = comp_size;
+    e->uncomp_size = uncomp_size;
+    e->hash = hash;                                           /* XXH3-64 of the plaintext, lib/zpack_write.c:256 */
+    e->comp_method = method;
+    return ZPACK_OK;
+}
+/* ... a raw copy of `src` whose payload went to `offset` */
+static int writer_enter_copy(zpack_writer* w, const zpack_file_entry* src, zpack_u64 offset)
+{
+    return zi_writer_enter(w, src->filename, offset, src->comp_size, src->uncomp_size, src->hash, src->comp_method);
+}
+/* `bytes` that reached a device image without zi_writer_put (a codec call placed them): the cursor moves on; returns where they begin */
+static zpack_u64 writer_placed(zpack_writer* w, zpack_u64 bytes)
+{
+    const zpack_u64 at = w->write_offset;
+    w->write_offset += (size_t)bytes;
+    w->file_size += (size_t)bytes;
+    return at;
 }
 
 /* ------------------------------------------------------------------ open */
@@ -248,12 +243,7 @@ static void write_part(void* arg, int k)
     j->rc[k] = n ? zpk_codec_encode_batch_host(j->ctx->dev[k], j->srcs + lo, j->desc + lo, n, j->dsts + lo, j->res + lo) : ZPK_OK;
 }
 
-/* the codec of `ctx` on HIP device `device`, NULL when the context holds none */
-static zpk_codec* ctx_codec_on(zi_ctx* ctx, int device)
-{
-    for (int k = 0; k < ctx->n; k++) if (zpk_codec_device(ctx->dev[k]) == device) return ctx->dev[k];
-    return NULL;
-}
+static zpack_u64 file_weight(const void* files, zpack_u64 i) { return ((const zpack_file*)files)[i].size; }
 
 /* The sink is an image in DEVICE memory: ONE zpk_codec_encode_batch_dsink call on the codec of the sink's device, no shard — the frames
  * are committed to the image on the device under the append rule below (the files in front of the first failing one, where "does not
@@ -263,7 +253,7 @@ static int write_files_dsink(zpack_writer* writer, zi_ctx* ctx, zpack_file* file
 {
     zpack_u8* d_image; size_t capacity; int device;
     if (zi_writer_sink(writer, &d_image, &capacity, &device) != ZI_SINK_DEVICE) return ZPACK_ERROR_WRITER_NOT_OPENED;
-    zpk_codec* codec = ctx_codec_on(ctx, device);
+    zpk_codec* codec = zi_ctx_codec_on(ctx, device);
     if (!codec) return ZPACK_ERROR_NOT_AVAILABLE;                                  /* the sink's device is not one of the context's */
     if (on_device) {                                                               /* device plaintext lies on the sink's device */
         int rc = ZPACK_OK;
@@ -275,19 +265,11 @@ static int write_files_dsink(zpack_writer* writer, zi_ctx* ctx, zpack_file* file
     const zpack_u64 room = at0 < capacity ? capacity - at0 : 0;
     uint64_t placed = 0, bytes = 0;
     const int crc = zpk_codec_encode_batch_dsink(codec, srcs, on_device, desc, file_count, d_image + (at0 < capacity ? at0 : capacity), room, res, &placed, &bytes);
-    if (crc != ZPK_OK) return crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
+    if (crc != ZPK_OK) return zi_rc_of_codec(crc);
     for (zpack_u64 i = 0; i < placed; i++) {                                       /* entered as the loop below enters them: at the running sum */
         writer->last_return = (size_t)res[i].comp_size;
-        const zpack_u64 at = writer->write_offset;
-        writer->write_offset += (size_t)res[i].comp_size;
-        writer->file_size += (size_t)res[i].comp_size;
-        zpack_file_entry* e = zi_writer_push_entry(writer);
-        if (!e || !(e->filename = dup_name(files[i].filename))) return ZPACK_ERROR_MALLOC_FAILED;
-        e->offset = at;
-        e->comp_size = res[i].comp_size;
-        e->uncomp_size = files[i].size;
-        e->hash = res[i].hash;
-        e->comp_method = (zpack_u8)files[i].options->method;
+        const zpack_u64 at = writer_placed(writer, res[i].comp_size);
+        if (zi_writer_enter(writer, files[i].filename, at, res[i].comp_size, files[i].size, res[i].hash, (zpack_u8)files[i].options->method)) return ZPACK_ERROR_MALLOC_FAILED;
     }
     if (placed == file_count) return ZPACK_OK;
     /* the file that stopped the call: its own status, else it did not fit what is left of the image */
@@ -342,20 +324,11 @@ static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_c
     if (rc == ZPACK_OK && on_device) {
         zpk_codec* codec = zi_ctx_codec_of(ctx, &files[0].buffer, sizeof(files[0]), &files[0].size, sizeof(files[0]), 1, file_count, &rc);
         if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: empty entries only) */
-        if (codec) {
-            const int crc = zpk_codec_encode_batch_dsrc(codec, srcs, desc, file_count, dsts, res);
-            if (crc != ZPK_OK) rc = crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
-        }
+        if (codec) rc = zi_rc_of_codec(zpk_codec_encode_batch_dsrc(codec, srcs, desc, file_count, dsts, res));
     } else if (rc == ZPACK_OK) {
         write_job job = { ctx, srcs, desc, dsts, res, {0}, {0} };
-        int parts = ctx->n;
-        if ((zpack_u64)parts > file_count) parts = (int)file_count;
-        if (parts > 1) {           /* static shard by source bytes: one host thread + one codec per device */
-            zpack_u64* w = (zpack_u64*)malloc(sizeof(zpack_u64) * (size_t)file_count);
-            if (!w) parts = 1;
-            else { for (zpack_u64 i = 0; i < file_count; i++) w[i] = files[i].size; zi_split(w, file_count, parts, job.cut); free(w); }
-        }
-        if (parts <= 1) { job.cut[0] = 0; job.cut[1] = file_count; parts = 1; }
+        /* static shard by source bytes: one host thread + one codec per device */
+        const int parts = zi_shard(ctx, file_count, file_weight, files, job.cut);
         zi_parallel(parts, write_part, &job);
         for (int k = 0; k < parts; k++) if (job.rc[k] != ZPK_OK) rc = ZPACK_ERROR_NOT_AVAILABLE;
     }
@@ -365,13 +338,7 @@ static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_c
         if (res[i].status != ZPACK_OK) { rc = res[i].status; break; }
         const zpack_u64 at = writer->write_offset;
         if ((rc = zi_writer_put(writer, dsts[i], (size_t)res[i].comp_size))) break;
-        zpack_file_entry* e = zi_writer_push_entry(writer);
-        if (!e || !(e->filename = dup_name(files[i].filename))) { rc = ZPACK_ERROR_MALLOC_FAILED; break; }
-        e->offset = at;
-        e->comp_size = res[i].comp_size;
-        e->uncomp_size = files[i].size;
-        e->hash = res[i].hash;                                                  /* XXH3-64 of the source, :256 */
-        e->comp_method = (zpack_u8)files[i].options->method;
+        if ((rc = zi_writer_enter(writer, files[i].filename, at, res[i].comp_size, files[i].size, res[i].hash, (zpack_u8)files[i].options->method))) break;
     }
     free(scratch); free(desc); free(res); free(srcs); free(dsts);
     return rc;
@@ -395,7 +362,7 @@ static int from_archive_on_device(zpack_writer* writer, const zpack_reader* read
                                   const zpack_file_entry* entries, zpack_u64 file_count, int* rc)
 {
     zi_ctx* ctx = zi_pick_ctx(NULL, &writer->zstd_cctx);
-    zpk_codec* codec = ctx ? ctx_codec_on(ctx, device) : NULL;
+    zpk_codec* codec = ctx ? zi_ctx_codec_on(ctx, device) : NULL;
     if (!codec) return 0;
     zpk_span_copy* rows = (zpk_span_copy*)malloc(sizeof(*rows) * (size_t)(file_count ? file_count : 1));
     if (!rows) { *rc = ZPACK_ERROR_MALLOC_FAILED; return 1; }
@@ -403,24 +370,15 @@ static int from_archive_on_device(zpack_writer* writer, const zpack_reader* read
     *rc = ZPACK_OK;
     for (; k < file_count; k++) {
         const zpack_file_entry* src = entries + k;
-        if (src->offset >= reader->file_size || src->comp_size > reader->file_size - src->offset) { *rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
+        if (!zi_entry_in_image(src, reader->file_size)) { *rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
         if (at > capacity || src->comp_size > capacity - at) { *rc = ZPACK_ERROR_BUFFER_TOO_SMALL; break; }
         rows[k].src = (uint64_t)(uintptr_t)(d_src + src->offset); rows[k].dst = (uint64_t)(uintptr_t)(d_image + at); rows[k].len = src->comp_size;
         at += src->comp_size;
     }
     if (k && (zpk_codec_copy_spans_device(codec, rows, k, NULL) != ZPK_OK || zpk_codec_stream_sync(codec) != ZPK_OK)) { free(rows); *rc = ZPACK_ERROR_WRITE_FAILED; return 1; }
     free(rows);
-    for (zpack_u64 i = 0; i < k; i++) {
-        const zpack_file_entry* src = entries + i;
-        const zpack_u64 here = writer->write_offset;
-        writer->write_offset += (size_t)src->comp_size;
-        writer->file_size += (size_t)src->comp_size;
-        zpack_file_entry* e = zi_writer_push_entry(writer);
-        if (!e) { *rc = ZPACK_ERROR_MALLOC_FAILED; return 1; }
-        *e = *src;
-        e->offset = here;
-        if (!(e->filename = dup_name(src->filename))) { *rc = ZPACK_ERROR_MALLOC_FAILED; return 1; }
-    }
+    for (zpack_u64 i = 0; i < k; i++)
+        if (writer_enter_copy(writer, entries + i, writer_placed(writer, entries[i].comp_size))) { *rc = ZPACK_ERROR_MALLOC_FAILED; return 1; }
     return 1;
 }
 
@@ -440,7 +398,7 @@ int zpack_write_files_from_archive(zpack_writer* writer, zpack_reader* reader, z
         const zpack_u8* payload = NULL;
         if (from == ZI_SRC_FILE || from == ZI_SRC_DEVICE) {
             /* (an image in device memory: the guard of the host image below, then the payload comes home through zpack_read_raw_file) */
-            if (from == ZI_SRC_DEVICE && (src->offset >= reader->file_size || src->comp_size > reader->file_size - src->offset)) { rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
+            if (from == ZI_SRC_DEVICE && !zi_entry_in_image(src, reader->file_size)) { rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
             if (src->comp_size > SIZE_MAX) { rc = ZPACK_ERROR_MALLOC_FAILED; break; }
             if (tmp_cap < src->comp_size) {
                 zpack_u8* nb = (zpack_u8*)realloc(tmp, (size_t)src->comp_size);
@@ -450,16 +408,12 @@ int zpack_write_files_from_archive(zpack_writer* writer, zpack_reader* reader, z
             if ((rc = zpack_read_raw_file(reader, (zpack_file_entry*)src, tmp, tmp_cap))) break;
             payload = tmp;
         } else if (reader->buffer) {
-            if (src->offset >= reader->file_size || src->comp_size > reader->file_size - src->offset) { rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
+            if (!zi_entry_in_image(src, reader->file_size)) { rc = ZPACK_ERROR_FILE_OFFSET_INVALID; break; }
             payload = reader->buffer + src->offset;
         } else { rc = ZPACK_ERROR_ARCHIVE_NOT_LOADED; break; }
         const zpack_u64 at = writer->write_offset;
         if ((rc = zi_writer_put(writer, payload, (size_t)src->comp_size))) break;
-        zpack_file_entry* e = zi_writer_push_entry(writer);
-        if (!e) { rc = ZPACK_ERROR_MALLOC_FAILED; break; }
-        *e = *src;
-        e->offset = at;
-        if (!(e->filename = dup_name(src->filename))) { rc = ZPACK_ERROR_MALLOC_FAILED; break; }
+        if ((rc = writer_enter_copy(writer, src, at))) break;
     }
     free(tmp);
     return rc;
@@ -522,13 +476,7 @@ int zpack_write_file_stream_end(zpack_writer* writer, char* filename, zpack_comp
     int rc = zpk_cstream_finish(st->c, (uint32_t)m, options->level, &csize, &usize, &hash);
     if (rc) return rc;
     if ((rc = stream_drain(writer, stream, st))) return rc;
-    zpack_file_entry* e = zi_writer_push_entry(writer);
-    if (!e || !(e->filename = dup_name(filename))) return ZPACK_ERROR_MALLOC_FAILED;
-    e->offset = st->entry_offset;
-    e->comp_size = csize;
-    e->uncomp_size = usize;
-    e->hash = hash;
-    e->comp_method = (zpack_u8)m;
+    if ((rc = zi_writer_enter(writer, filename, st->entry_offset, csize, usize, hash, (zpack_u8)m))) return rc;
     zpk_cstream_reset(st->c);
     st->c_active = 0;
     return ZPACK_OK;
