@@ -378,7 +378,12 @@ int zpk_codec_set_profiling(zpk_codec* c, int enabled);
  * out[12], out[13] = stored entries the most recent zpk_codec_decode_big_batch_device / zpk_codec_decode_big_device call copied chip-wide
  * (ZPK_OPT_STORED_SPAN_MIN) / their groups of 64 KiB;
  * out[14] = sub-batches of the most recent zpk_codec_decode_batch_host / _dptr call that took the three-stage pipeline; out[15] = k_span_copy
- * launches of the most recent zpk_codec_decode_batch_host_dptr call */
+ * launches of the most recent zpk_codec_decode_batch_host_dptr call.
+ * The indices by name (added within ABI 3; the numbers are the ones above and do not move): */
+enum { ZPK_DS2_RETRY_LZ4 = 0, ZPK_DS2_RETRY_ZSTD = 1, ZPK_DS2_RESERVED2 = 2 /* reads 0 */, ZPK_DS2_LZ4_RUNS = 3, ZPK_DS2_RESERVED4 = 4 /* reads 0 */,
+       ZPK_DS2_BIG_ENTRIES = 5, ZPK_DS2_BIG_FRAMES = 6, ZPK_DS2_ZPJ_ERR = 7 /* developer: why the most recent large Zstandard frame was not finished block-parallel (0: it was, or none came) */,
+       ZPK_DS2_LZ4_HANDED = 8, ZPK_DS2_LZ4_GEN = 9, ZPK_DS2_WALKED = 10, ZPK_DS2_WALK_ACCEPTED = 11, ZPK_DS2_SPAN_ENTRIES = 12, ZPK_DS2_SPAN_GROUPS = 13,
+       ZPK_DS2_PIPE_SUBS = 14, ZPK_DS2_SPAN_COPIES = 15, ZPK_DS2_COUNT = 16 };
 int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16]);
 /* counters of the most recent decode batch (synchronises): out[0..2] = entries on the stored / zstd / lz4 work
  * lists, out[3] = Zstandard entries finished on pre-decoded sequences (two-stage path), out[4] = by the fused decoder,

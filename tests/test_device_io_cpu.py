@@ -137,6 +137,7 @@ def test_span_copy_plan_under_asan_ubsan():
                  "item_base: ascending and disjoint without a gap, 15 items searched for land in their own rows",
                  "launches: one grid holds 8589934588 items, one more is a second launch of 1; 262150 items at 1000 a grid are 263 launches that tile them",
                  "slots: read slots hold what the entry may produce, write slots the source and 16 bytes, both at multiples of 256",
+                 "staged: the caller's descriptor at its slot's offset; a stored entry that fits is cut to uncomp_size, every other capacity stays",
                  "packed: uncomp_size 0, 1, 255, 256, 257 land at 0, 0, 256, 512, 768 and end at 1280",
                  "range: the first and the last byte of an allocation pass, one before and one behind do not, ptr + len that wraps does not"):
         assert line in p.stdout, p.stdout[-1500:]

@@ -90,6 +90,27 @@ int main()
     for (u64 n : { 0ull, 1ull, 239ull, 240ull, 241ull, 65535ull, 65536ull, (2ull << 20) + 17 }) CHECK(span_copy_write_slot(n) >= n + 16 && span_copy_write_slot(n) % 256 == 0 && span_copy_write_slot(n) < n + 16 + 256);
     printf("slots: read slots hold what the entry may produce, write slots the source and 16 bytes, both at multiples of 256\n");
 
+    // ---- the descriptor of a staged entry ----
+    {
+        struct Desc { u64 src_offset, comp_size, uncomp_size, expect_hash, dst_offset, dst_capacity; uint32_t method, flags; };   // (the fields of zpk_decode_desc)
+        const Desc d = { 11, 22, 100, 0x1234, 999, 300, 2, 1 };
+        auto same_but = [&](const Desc& s, u64 off, u64 cap) {
+            return s.src_offset == d.src_offset && s.comp_size == d.comp_size && s.uncomp_size == d.uncomp_size && s.expect_hash == d.expect_hash &&
+                   s.method == d.method && s.flags == d.flags && s.dst_offset == off && s.dst_capacity == cap;
+        };
+        CHECK(same_but(span_copy_staged_desc(d, false, 512), 512, 300));                           // a compressed entry: the caller's capacity
+        CHECK(same_but(span_copy_staged_desc(d, true, 0), 0, 100));                                // a stored entry that fits: cut to uncomp_size, its slot
+        Desc e = d; e.dst_capacity = 100;
+        CHECK(span_copy_staged_desc(e, true, 256).dst_capacity == 100 && span_copy_staged_desc(e, true, 256).dst_offset == 256);      // exactly as large
+        e.dst_capacity = 99;
+        CHECK(span_copy_staged_desc(e, true, 256).dst_capacity == 99 && span_copy_staged_desc(e, false, 256).dst_capacity == 99);     // too small: as given, the device's guard judges it
+        e.uncomp_size = 0; e.dst_capacity = 0;
+        CHECK(span_copy_staged_desc(e, true, 768).dst_capacity == 0 && span_copy_staged_desc(e, true, 768).dst_offset == 768);
+        for (u64 cap : { 0ull, 99ull, 100ull, 101ull, ~0ull })                                     // what is kept never exceeds the slot's bytes
+            { Desc f = d; f.dst_capacity = cap; if (cap >= f.uncomp_size) CHECK(span_copy_staged_desc(f, true, 0).dst_capacity == span_copy_read_slot_bytes(true, f.uncomp_size, cap)); }
+        printf("staged: the caller's descriptor at its slot's offset; a stored entry that fits is cut to uncomp_size, every other capacity stays\n");
+    }
+
     // ---- the packed read ----
     {
         const u64 sizes[] = { 0, 1, 255, 256, 257 };

@@ -59,6 +59,16 @@ static inline SpanCopyLaunch span_copy_launch(u64 items, u64 j, u64 max_items = 
 // slots follow each other at multiples of 256.  What goes to the caller is [slot, slot + produced).
 static inline u64 span_copy_read_slot_bytes(bool stored, u64 uncomp_size, u64 dst_capacity) { return stored && uncomp_size < dst_capacity ? uncomp_size : dst_capacity; }
 static inline u64 span_copy_read_slot(bool stored, u64 uncomp_size, u64 dst_capacity) { return (span_copy_read_slot_bytes(stored, uncomp_size, dst_capacity) + 255) & ~255ull; }
+// The descriptor the device sees of an entry staged at `slot_offset` (Desc: zpk_decode_desc; `stored`: its method is NONE): the caller's,
+// with dst_offset = the slot.  The device still judges `max_size < uncomp_size` on the caller's capacity, so dst_capacity stays as given —
+// except for a stored entry that passes that guard: it writes uncomp_size bytes and its slot is that long.
+template <class Desc> static inline Desc span_copy_staged_desc(const Desc& d, bool stored, u64 slot_offset)
+{
+    Desc s = d;
+    s.dst_offset = slot_offset;
+    if (stored && d.dst_capacity >= d.uncomp_size) s.dst_capacity = span_copy_read_slot_bytes(true, d.uncomp_size, d.dst_capacity);
+    return s;
+}
 // Writing (c->d_src): the sources follow each other at multiples of 256 with at least 16 bytes behind each — the slack the encode
 // kernels' 16-byte loads ask for, which a caller's own allocation cannot promise.
 static inline u64 span_copy_write_slot(u64 size) { return (size + 255 + 16) & ~255ull; }

@@ -49,6 +49,7 @@ namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 
 #include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
 #include "dsink_plan.h"                          // a batch compressed into a bounded sink in DEVICE memory: the cut, the span table, room and chaining, the staging (plain C++, likewise); the kernels: sink_commit.hip
 #include "stream_plan.h"                        // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
+#include "codec_res.h"                           // what a codec or a stream context holds, each owned by its member: DevBuf, PinBuf / PinBlock, Event, Stream (plain C++ over the HIP runtime, likewise)
 
 using namespace zpk;
 
@@ -602,121 +603,130 @@ __global__ __launch_bounds__(256) void k_hash(const u8* __restrict__ src, const 
 #define ZPK_PJ_CHUNK_BLOCKS 512u                   // lz4_pj.h: blocks per chunk = 32 MiB of output, 128 MiB of byte references (the Infinity Cache holds 256)
 #endif
 #define ZPK_PJ_MAX_CHUNKS 64u
-// One device buffer the codec owns (pointer + capacity in bytes).  grow() enlarges it; every one is a member of zpk_codec and is
-// listed in zpk_codec::bufs, which is what zpk_codec_destroy frees.
-struct DevBufBase { void* p = nullptr; u64 cap = 0; };
-template <class T> struct DevBuf : DevBufBase {
-    operator T*() const { return (T*)p; }
-    template <class U> explicit operator U*() const { return (U*)p; }
-};
-// One block of pinned host memory the codec owns, for tables and bytes that travel in one copy; every one is listed in zpk_codec::pins,
-// which is what zpk_codec_destroy frees.  grow_pinned -> the block holds `need` bytes; false: no pinned memory (the HIP error is cleared,
-// the block is empty) — what then is the caller's policy.  A block is regrown only while nothing on a stream still reads or writes it: a
-// call that uses one drains the stream it put the copies on before it returns (h_bigsrc, h_bigwalk: hipStreamSynchronize behind the copy
-// home; h_sspan: the run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the
-// block's next turn (h_bigenc).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
-struct PinBuf { u8* p = nullptr; u64 cap = 0; };
-static bool grow_pinned(PinBuf& b, u64 need)
-{
-    if (need <= b.cap) return true;
-    if (b.p) (void)hipHostFree(b.p);
-    b.p = nullptr; b.cap = 0;
-    const u64 want = need + need / 4 + 4096;
-    if (hipHostMalloc((void**)&b.p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
-    b.cap = want;
-    return true;
-}
-// A second stream beside the batch's own (created on first use) with the event pair that forks work onto it and joins it back
-struct SideStream { hipStream_t s = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
 
+// What a batch holds, handed to decode_launch by the caller that knows: 1 / 0 = it does / does not hold an entry of the method (the host
+// paths count while they cut the batch), -1 = a device batch, which may hold any
+struct BatchMethods { int zstd, lz4; };
+
+// The words the stats calls report of the most recent call.  begin_decode_call zeroes the decode words; dimage, dsink and enc_big are
+// zeroed by the one call that counts them; totals_valid by every launch, fell_back_fused by the launch that decides it.
+struct LastCall {
+    u32  big[2] = {0, 0};                        // host decode path: entries decoded frame-parallel or block-parallel, their frames / blocks
+    u32  walk[2] = {0, 0};                       // zpk_codec_decode_big_batch_device: entries walked on the device, those the walk accepted
+    u32  span[2] = {0, 0};                       // large stored entries copied chip-wide, their groups
+    u32  pipe = 0, sc = 0;                       // host decode call: sub-batches that took the three-stage pipeline; k_span_copy launches
+    u32  zpj_err = 0;                            // developer: the flag word of the most recent large Zstandard frame (why it went to the one-wave decoder)
+    u32  dimage[3] = {0, 0, 0};                  // zpk_codec_decode_batch_dimage: its sub-batches, k_span_copy launches and the bytes it copied home (saturating)
+    u32  dsink[2] = {0, 0};                      // zpk_codec_encode_batch_dsink: its sub-batches and the last grid of k_sink_place
+    u32  enc_big[2] = {0, 0};                    // zpk_codec_encode_big_device: entries written in pieces, their pieces
+    int  fell_back_fused = 0;                    // the last decode batch could not get its sequence arena and ran the fused decoder only
+    // the host-path pipeline decodes one call in several launches: their counters are brought back piece by piece and summed, so that
+    // decode_stats / decode_stats2 describe the whole call (a retry or watchdog event in an early piece is not lost)
+    u32  host_totals[N_COUNTERS] = {};
+    int  totals_valid = 0;
+};
+
+// Every HIP resource below is owned by the member that names it (codec_res.h): deleting the codec releases all of them.
+// A growable pinned block (PinBuf) is regrown only while nothing on a stream still reads or writes it: a call that uses one drains the
+// stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk: hipStreamSynchronize behind the copy home; sspan.h: the
+// run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the block's next turn
+// (bigenc.h, sc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
 struct zpk_codec {
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     // One codec = one in-flight batch: the work lists, counters and staging buffers below are shared by every call.
     // The host-pointer entry points (decode/encode_batch_host, hash_host, the streaming triple) take `mu` for their
     // whole duration, so threads that share a codec are serialised, never corrupted.  The device-pointer entry points
     // take it only while they enqueue: batches on ONE stream are ordered by the stream; a codec must not be driven
     // from two streams at once (create one codec per stream — contexts are cheap).
     pthread_mutex_t mu;
+    char err[256] = {0};
+    LastCall last;
+
+    // zpk_codec_set_option
+    struct {
+        int  order_fast_last = 1;                          // ZPK_OPT_ORDER_FAST_LAST: a batch of one size class runs its incompressible entries last
+        u64  order_min = 8192;                             // ZPK_OPT_ORDER_MIN: decode batches of at least this many entries run their work lists largest entries first
+        u64  enc_order_min = 4608;                         // ... and encode batches their ticket queue (the encoder's resident waves: 18 per CU)
+        u64  dec_split_min = ZPK_DEC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_DEC_SPLIT_MIN: entries of at least this many bytes that ARE sequences of frames are decoded frame-parallel
+        u64  enc_split_min = ZPK_ENC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_ENC_SPLIT_MIN: entries of at least this many bytes are written as a sequence of frames
+        u64  stored_span_min = ZPK_STORED_SPAN_MIN_DEFAULT; // ZPK_OPT_STORED_SPAN_MIN: stored entries of at least this many bytes go chip-wide
+        u64  dimage_chunk = 0;                             // ZPK_OPT_DIMAGE_CHUNK (0 = the default): the staging of one sub-batch of an archive image in device memory (dimage_plan.h)
+    } opt;
+
+    // staging every path shares
     DevBuf<u32> d_counters;                      // N_COUNTERS words (zpk_layout.h)
-    DevBuf<u32> d_lists;                         // N_LIST_SLOTS work lists (zpk_layout.h)
-    DevBuf<u8>  d_lit;
-    // host-API staging
-    DevBuf<u8>  d_src;
-    u8*  h_pin[2] = {nullptr, nullptr};          // pinned staging of the host-pointer paths (ZPK_PIN_CHUNK bytes each), created on first use
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    hipStream_t s_up = nullptr, s_dn = nullptr;  // host-pointer decode pipeline: upload / download streams beside `stream` (created on first use)
-    SideStream side;                             // decode batches: the LZ4 kernels beside the Zstandard stages (low priority)
-    DevBuf<void> d_pj_blocks, d_pj_recs, d_pj_masks, d_pj_S;   // large single LZ4 frames (lz4_pj.h): block table, sequence records, start masks, byte references
-    DevBuf<u32>  d_pj_flags;                     // ... and flags (256 bytes)
-    PinBuf h_bigsrc;                                 // pinned: the compressed bytes of one large device-resident entry, for the host's block walk (zpk_codec_decode_big_device)
-    DevBuf<u8> d_bigwalk;                            // zpk_codec_decode_big_batch_device: candidates | records | block tables (k_big_walk)
-    PinBuf h_bigwalk;                                // ... pinned: the candidates going up, the records and tables coming home
-    u32   walk_last[2] = {0, 0};                     // ... most recent call: entries walked on the device, those the walk accepted
-    // large stored entries of a device-resident call (stored_plan.h / stored_span.h): span table | destination offsets | 64 bytes of XXH3
-    // partial sums per 1 KiB block | hashes — a buffer of its own, d_xpart belongs to the block-parallel readers of the same call
-    DevBuf<u8> d_sspan;
-    PinBuf h_sspan;                                      // ... pinned: the table going up, the hashes coming home
-    SideStream span;                                     // ... the second stream of the forked form (created on first use)
-    u64   stored_span_min = ZPK_STORED_SPAN_MIN_DEFAULT; // ZPK_OPT_STORED_SPAN_MIN: stored entries of at least this many bytes go chip-wide
-    u32   span_last[2] = {0, 0};                         // ... most recent call: entries copied chip-wide, their groups
-    u32   zpj_last_err = 0;                          // developer: the flag word of the most recent large Zstandard frame (why it went to the one-wave decoder)
-    DevBuf<void> d_zpj_blocks, d_zpj_aux, d_zpj_pos; // large single Zstandard frames (zstd_pj.h): block table; work items, states, final histories; sequence positions
-    SideStream left;                             // decode batches: k_lz4_left (the LZ4 entries that are mostly runs) beside k_lz4_wave
-    volatile SeenCounts* h_seen = nullptr;       // pinned: the work-list counts of an earlier device batch (what the next one probably holds)
-    hipEvent_t pipe_ev[2 * 64] = {};             // per piece: uploaded, decoded
+    DevBuf<u8>  d_src;                           // host-API staging
     DevBuf<u8>  d_dst;
     DevBuf<void> d_desc, d_res;
     DevBuf<u64> d_dbg;
-    DevBuf<u64> d_seq;                                 // encoder: sequence lists, one per workgroup
-    DevBuf<u8>  d_pack;                                // K7: block sums + span index of the compaction
-    DevBuf<u8>  d_packed;                              // host encode path: packed payload stream
-    DevBuf<u8>  d_packoff;                             // host encode path: payload offsets
-    DevBuf<u8>  d_xpart;                               // host encode path, split entries: span list | 64 bytes of XXH3 partial sums per 1 KiB block | hashes
-    u64  enc_order_min = 4608;                         // ... and encode batches their ticket queue (the encoder's resident waves: 18 per CU)
-    int  order_fast_last = 1;                          // ZPK_OPT_ORDER_FAST_LAST: a batch of one size class runs its incompressible entries last
-    u64  order_min = 8192;                             // ZPK_OPT_ORDER_MIN: decode batches of at least this many entries run their work lists largest entries first
-    u64  dec_split_min = ZPK_DEC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_DEC_SPLIT_MIN: entries of at least this many bytes that ARE sequences of frames are decoded frame-parallel
-    hipEvent_t pj_ev[ZPK_PJ_MAX_CHUNKS] = {};           // lz4_pj.h: one event behind every chunk of a large LZ4 frame (its bytes may go home)
-    u32  big_last[2] = {0, 0};                         // host decode path, most recent call: entries decoded frame-parallel, their frames
-    u64  enc_split_min = ZPK_ENC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_ENC_SPLIT_MIN: entries of at least this many bytes are written as a sequence of frames
-    // zpk_codec_encode_big_device: the tables of one call (descriptors, pieces, entry table, spans) go up from pinned memory behind
-    // whatever the stream still holds; two blocks take turns, the event says that a block's upload has run
-    PinBuf h_bigenc[2]; hipEvent_t bigenc_ev[2] = {nullptr, nullptr}; u32 bigenc_turn = 0;
-    u32  enc_big_last[2] = {0, 0};                     // ... most recent call: entries written in pieces, their pieces
-    DevBuf<u64> d_zarena;                              // decoder: pre-decoded Zstandard sequences, laid out like dst (zstd_fse4.h)
-    DevBuf<u32> d_zstate;                              // decoder: per entry, 1 = its sequences are in the arena
-    int lz4_hint = -1;           // host path: does the batch hold an LZ4 entry?  -1 = unknown (device path)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t kev[ZPK_K_COUNT][2] = {};
+    DevBuf<u8>  d_xpart;                         // span list | 64 bytes of XXH3 partial sums per 1 KiB block | hashes (xxh3_span.h): split entries of the host encode path, the block-parallel readers
+    // timing (zpk_codec_timer_*, zpk_codec_set_profiling)
+    Event ev0, ev1;
+    Event kev[ZPK_K_COUNT][2];
     int profiling = 0;
-    int zstd_hint = -1;          // host path: does the batch hold a Zstandard entry (1 / 0)?  -1 = unknown (device path)
-    int fell_back_fused = 0;     // the last decode batch could not get its sequence arena and ran the fused decoder only
-    // the host-path pipeline decodes one call in several launches: their counters are brought back piece by piece and summed, so that
-    // decode_stats / decode_stats2 describe the whole call (a retry or watchdog event in an early piece is not lost)
-    u64* h_pj = nullptr;                               // 8 pinned words (pin_ready): hash and flags of a large LZ4 frame come home without blocking the launcher
-    u32 (*piece_counters)[N_COUNTERS] = nullptr;     // [64], pinned (pin_ready): a D2H copy into pageable memory would block the launcher thread per piece
-    u32 host_totals[N_COUNTERS] = {};
-    int totals_valid = 0;
-    char err[256] = {0};
+
+    // the classify / one-wave launch (decode_launch)
+    struct {
+        DevBuf<u32> d_lists;                     // N_LIST_SLOTS work lists (zpk_layout.h); an ordered encode batch keeps its ticket queue here
+        DevBuf<u8>  d_lit;
+        DevBuf<u64> d_zarena;                    // pre-decoded Zstandard sequences, laid out like dst (zstd_fse4.h)
+        DevBuf<u32> d_zstate;                    // per entry, 1 = its sequences are in the arena
+        SideStream side;                         // the LZ4 kernels beside the Zstandard stages (low priority)
+        SideStream left;                         // k_lz4_left (the LZ4 entries that are mostly runs) beside k_lz4_wave
+        PinBlock<volatile SeenCounts> h_seen;    // pinned: the work-list counts of an earlier device batch (what the next one probably holds)
+    } wave;
+
+    // the host-pointer decode pipeline (pin_ready, d2h_scatter / h2d_gather, decode_host_pipelined)
+    struct {
+        PinBlock<u8> h_pin[2];                   // pinned staging of the host-pointer paths (ZPK_PIN_CHUNK bytes each), created on first use
+        Event pin_ev[2];
+        Stream s_up, s_dn;                       // upload / download streams beside `stream` (created on first use)
+        Event ev[2 * 64];                        // per piece: uploaded, decoded
+        PinBlock<u32[N_COUNTERS]> piece_counters; // [64], pinned (pin_ready): a D2H copy into pageable memory would block the launcher thread per piece
+    } pipe;
+
+    // the block-parallel readers of large single frames (lz4_pj.h, zstd_pj.h)
+    struct {
+        DevBuf<void> d_blocks, d_recs, d_masks, d_S;   // LZ4: block table, sequence records, start masks, byte references
+        DevBuf<u32>  d_flags;                    // ... and flags (256 bytes)
+        DevBuf<void> d_zblocks, d_zaux, d_zpos;  // Zstandard: block table; work items, states, final histories; sequence positions
+        Event ev[ZPK_PJ_MAX_CHUNKS];             // one event behind every chunk of a large frame (its bytes may go home)
+        PinBlock<u64> h_words;                   // 8 pinned words (pin_ready): hash and flags of a large frame come home without blocking the launcher
+    } pj;
+
+    // the walk over the block headers of large device-resident entries
+    struct {
+        PinBuf h_bigsrc;                         // pinned: the compressed bytes of one large device-resident entry, for the host's block walk (zpk_codec_decode_big_device)
+        DevBuf<u8> d_bigwalk;                    // zpk_codec_decode_big_batch_device: candidates | records | block tables (k_big_walk)
+        PinBuf h_bigwalk;                        // ... pinned: the candidates going up, the records and tables coming home
+    } walk;
+
+    // large stored entries of a device-resident call (stored_plan.h / stored_span.h): span table | destination offsets | 64 bytes of XXH3
+    // partial sums per 1 KiB block | hashes — a buffer of its own, d_xpart belongs to the block-parallel readers of the same call
+    struct {
+        DevBuf<u8> d;
+        PinBuf h;                                // pinned: the table going up, the hashes coming home
+        SideStream side;                         // the second stream of the forked form (created on first use)
+    } sspan;
+
     // plaintext in the caller's device memory (span_copy_plan.h / span_copy.h): the row table of k_span_copy, pinned going up — the event
     // says that the upload has run, the block is written again only behind it
-    DevBuf<u8> d_sc; PinBuf h_sc; hipEvent_t sc_ev = nullptr; bool sc_pending = false;
-    u32   pipe_last = 0, sc_last = 0;                // most recent host decode call: sub-batches that took the three-stage pipeline; k_span_copy launches
-    // the archive image in the caller's device memory (dimage_plan.h): ZPK_OPT_DIMAGE_CHUNK (0 = the default) and, of the most recent
-    // zpk_codec_decode_batch_dimage call, its sub-batches, k_span_copy launches and the bytes it copied home (saturating)
-    u64   dimage_chunk = 0;
-    u32   dimage_last[3] = {0, 0, 0};
-    // a sink in the caller's device memory (dsink_plan.h / sink_commit.h): the slots a sub-batch is encoded into — c->d_dst holds the pieces
-    // of its large entries meanwhile —, the commit's tables (results | cut record | offsets | slot offsets), the resident workgroups of
-    // k_sink_place (0: not asked yet) and, of the most recent zpk_codec_encode_batch_dsink call, its sub-batches and the last grid
-    DevBuf<u8> d_sink_slots, d_sink_tab;
-    u32   sink_groups = 0;
-    u32   dsink_last[2] = {0, 0};
-    DevBufBase* const bufs[28] = { &d_counters, &d_lists, &d_lit, &d_src, &d_pj_blocks, &d_pj_recs, &d_pj_masks, &d_pj_S, &d_pj_flags, &d_bigwalk, &d_sspan, &d_sc,
-                                   &d_zpj_blocks, &d_zpj_aux, &d_zpj_pos, &d_dst, &d_desc, &d_res, &d_dbg, &d_seq, &d_pack, &d_packed, &d_packoff,
-                                   &d_xpart, &d_zarena, &d_zstate, &d_sink_slots, &d_sink_tab };
-    PinBuf* const pins[6] = { &h_bigsrc, &h_bigwalk, &h_sspan, &h_bigenc[0], &h_bigenc[1], &h_sc };
+    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } sc;
+
+    // the encoder
+    DevBuf<u64> d_seq;                           // sequence lists, one per workgroup
+    DevBuf<u8>  d_pack;                          // K7: block sums + span index of the compaction
+    DevBuf<u8>  d_packed;                        // host encode path: packed payload stream
+    DevBuf<u8>  d_packoff;                       // host encode path: payload offsets
+    // zpk_codec_encode_big_device: the tables of one call (descriptors, pieces, entry table, spans) go up from pinned memory behind
+    // whatever the stream still holds; two blocks take turns, the event says that a block's upload has run
+    struct { PinBuf h[2]; Event ev[2]; u32 turn = 0; } bigenc;
+
+    // a sink in the caller's device memory (dsink_plan.h / sink_commit.h): the slots a sub-batch is encoded into — d_dst holds the pieces
+    // of its large entries meanwhile —, the commit's tables (results | cut record | offsets | slot offsets) and the resident workgroups of
+    // k_sink_place (0: not asked yet)
+    struct { DevBuf<u8> d_slots, d_tab; u32 groups = 0; } sink;
 };
 
 struct CodecLock {
@@ -730,22 +740,16 @@ struct CodecLock {
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     snprintf((c)->err, sizeof((c)->err), "%s: %s", #call, hipGetErrorString(e_)); return ZPK_E_LAUNCH; } } while (0)
 
-static void release(DevBufBase& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
 static int grow(zpk_codec* c, DevBufBase& b, u64 need)
 {
     if (need <= b.cap) return ZPK_OK;
     // the buffer may still be in use by work enqueued earlier on the codec's stream or the caller's
-    if (b.p) { (void)hipDeviceSynchronize(); release(b); }
+    if (b.p) { (void)hipDeviceSynchronize(); b.release(); }
     u64 want = need + need / 4 + 4096;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!b.alloc(want)) {
         want = need + 256;                                                          // the slack was a convenience, not a need
-        if (hipMalloc(&b.p, want) != hipSuccess) {
-            (void)hipGetLastError();
-            snprintf(c->err, sizeof(c->err), "hipMalloc(%llu) failed", (unsigned long long)want); return ZPK_E_NOMEM;
-        }
+        if (!b.alloc(want)) { snprintf(c->err, sizeof(c->err), "hipMalloc(%llu) failed", (unsigned long long)want); return ZPK_E_NOMEM; }
     }
-    b.cap = want;
     return ZPK_OK;
 }
 
@@ -780,41 +784,22 @@ int zpk_codec_create(zpk_codec** out, int device)
         pthread_mutexattr_t at; pthread_mutexattr_init(&at); pthread_mutexattr_settype(&at, PTHREAD_MUTEX_RECURSIVE);
         pthread_mutex_init(&c->mu, &at); pthread_mutexattr_destroy(&at);
     }
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->d_counters.p, N_COUNTERS * sizeof(u32)) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
-        zpk_codec_destroy(c);
+    if (hipSetDevice(device) != hipSuccess || c->stream.ready(hipStreamNonBlocking) != hipSuccess ||
+        !c->d_counters.ensure(N_COUNTERS * sizeof(u32)) ||
+        c->ev0.ready(hipEventDefault) != hipSuccess || c->ev1.ready(hipEventDefault) != hipSuccess) {
+        zpk_codec_destroy(c);                                                       // (whatever exists by now goes with it)
         return ZPK_E_NO_DEVICE;
     }
     *out = c;
     return ZPK_OK;
 }
 
+// the members own what they hold (codec_res.h): on the codec's device, behind whatever its stream still carries
 void zpk_codec_destroy(zpk_codec* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    for (DevBufBase* b : c->bufs) release(*b);
-    for (int k = 0; k < 2; k++) { if (c->h_pin[k]) (void)hipHostFree(c->h_pin[k]); if (c->pin_ev[k]) (void)hipEventDestroy(c->pin_ev[k]); }
-    if (c->piece_counters) (void)hipHostFree(c->piece_counters);
-    if (c->h_pj) (void)hipHostFree(c->h_pj);
-    if (c->h_seen) (void)hipHostFree((void*)c->h_seen);
-    for (PinBuf* b : c->pins) if (b->p) (void)hipHostFree(b->p);
-    for (int k = 0; k < 2; k++) if (c->bigenc_ev[k]) (void)hipEventDestroy(c->bigenc_ev[k]);
-    if (c->sc_ev) (void)hipEventDestroy(c->sc_ev);
-    for (SideStream* x : { &c->side, &c->left, &c->span }) {
-        if (x->s) (void)hipStreamDestroy(x->s);
-        if (x->fork) (void)hipEventDestroy(x->fork);
-        if (x->join) (void)hipEventDestroy(x->join);
-    }
-    for (u32 k = 0; k < ZPK_PJ_MAX_CHUNKS; k++) if (c->pj_ev[k]) (void)hipEventDestroy(c->pj_ev[k]);
-    if (c->s_up) (void)hipStreamDestroy(c->s_up);
-    if (c->s_dn) (void)hipStreamDestroy(c->s_dn);
-    for (int k = 0; k < 2 * 64; k++) if (c->pipe_ev[k]) (void)hipEventDestroy(c->pipe_ev[k]);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (int i = 0; i < ZPK_K_COUNT; i++) for (int j = 0; j < 2; j++) if (c->kev[i][j]) (void)hipEventDestroy(c->kev[i][j]);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
     pthread_mutex_destroy(&c->mu);
     delete c;
 }
@@ -832,7 +817,7 @@ void zpk_codec_reset(zpk_codec* c)
     // a context keeps its grown staging between batches (the next batch of that size starts at once); a reset gives the large pieces
     // back — a process that holds many readers can bound what each one retains (zpack_reset_reader_dctx / zpack_reset_writer_cctx)
     const u64 keep = 64ull << 20;
-    for (DevBufBase* b : { (DevBufBase*)&c->d_src, (DevBufBase*)&c->d_dst, (DevBufBase*)&c->d_zarena, (DevBufBase*)&c->d_lit, (DevBufBase*)&c->d_sink_slots }) if (b->cap > keep) release(*b);
+    for (DevBufBase* b : { (DevBufBase*)&c->d_src, (DevBufBase*)&c->d_dst, (DevBufBase*)&c->wave.d_zarena, (DevBufBase*)&c->wave.d_lit, (DevBufBase*)&c->sink.d_slots }) if (b->cap > keep) b->release();
 }
 const char* zpk_codec_last_error(const zpk_codec* c) { return c ? c->err : "no codec"; }
 int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
@@ -949,22 +934,22 @@ static int span_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
     for (u64 i = 0; i < n; i++) nz += row(i).len != 0;
     if (nz == 0) return ZPK_OK;
     if (nz > ZPK_SC_MAX_ROWS) return ZPK_E_INVALID;
-    if (c->sc_pending) { HIPCHK(c, hipEventSynchronize(c->sc_ev)); c->sc_pending = false; }             // the pinned block's last upload has run
-    if (!c->sc_ev && hipEventCreateWithFlags(&c->sc_ev, hipEventDisableTiming) != hipSuccess) { c->sc_ev = nullptr; (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "span copy: no event"); return ZPK_E_LAUNCH; }
-    if (!grow_pinned(c->h_sc, nz * sizeof(SpanCopyRow))) { snprintf(c->err, sizeof(c->err), "span copy: out of pinned memory"); return ZPK_E_NOMEM; }
+    if (c->sc.pending) { HIPCHK(c, hipEventSynchronize(c->sc.ev)); c->sc.pending = false; }             // the pinned block's last upload has run
+    if (c->sc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "span copy: no event"); return ZPK_E_LAUNCH; }
+    if (!c->sc.h.grow(nz * sizeof(SpanCopyRow))) { snprintf(c->err, sizeof(c->err), "span copy: out of pinned memory"); return ZPK_E_NOMEM; }
     int rc;
-    if ((rc = grow(c, c->d_sc, nz * sizeof(SpanCopyRow)))) return rc;
-    SpanCopyRow* const rows = (SpanCopyRow*)c->h_sc.p;
+    if ((rc = grow(c, c->sc.d, nz * sizeof(SpanCopyRow)))) return rc;
+    SpanCopyRow* const rows = (SpanCopyRow*)c->sc.h.p;
     SpanCopyPlan p = { 0, 0 };
     for (u64 i = 0; i < n; i++) { const zpk_span_copy s = row(i); (void)span_copy_emit(s.src, s.dst, s.len, rows, p); }
-    HIPCHK(c, hipMemcpyAsync(c->d_sc, rows, p.nrows * sizeof(SpanCopyRow), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->sc_ev, st));
-    c->sc_pending = true;
+    HIPCHK(c, hipMemcpyAsync(c->sc.d, rows, p.nrows * sizeof(SpanCopyRow), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->sc.ev, st));
+    c->sc.pending = true;
     const u64 nl = span_copy_launches(p.items);
     for (u64 j = 0; j < nl; j++) {
         const SpanCopyLaunch L = span_copy_launch(p.items, j);
-        span_copy_launch((const SpanCopyRow*)(const u8*)c->d_sc, (u32)p.nrows, L.item0, L.items, L.grid, st);
-        c->sc_last++;
+        span_copy_launch((const SpanCopyRow*)(const u8*)c->sc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
+        c->last.sc++;
     }
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
@@ -1011,10 +996,10 @@ static bool fork_stream(SideStream& x, hipStream_t from, bool low_priority)
     if (!x.s) {
         int lo_prio = 0, hi_prio = 0;
         if (low_priority) (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
-        if ((low_priority ? hipStreamCreateWithPriority(&x.s, hipStreamNonBlocking, lo_prio) : hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking)) != hipSuccess) x.s = nullptr;
+        (void)(low_priority ? x.s.ready_priority(hipStreamNonBlocking, lo_prio) : x.s.ready(hipStreamNonBlocking));
     }
-    if (!x.fork && hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess) x.fork = nullptr;
-    if (!x.join && hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess) x.join = nullptr;
+    (void)x.fork.ready(hipEventDisableTiming);
+    (void)x.join.ready(hipEventDisableTiming);
     return x.s && x.fork && x.join && hipEventRecord(x.fork, from) == hipSuccess && hipStreamWaitEvent(x.s, x.fork, 0) == hipSuccess;
 }
 // Join: `into` goes on behind what x.s holds; when that cannot be enqueued the host waits for x.s instead.
@@ -1023,16 +1008,16 @@ static void join_stream(SideStream& x, hipStream_t into)
     if (hipEventRecord(x.join, x.s) != hipSuccess || hipStreamWaitEvent(into, x.join, 0) != hipSuccess) (void)hipStreamSynchronize(x.s);
 }
 
-static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* read_lo, const u8* read_hi,
+static int decode_launch(zpk_codec* c, BatchMethods holds, const u8* src, u64 src_size, const u8* read_lo, const u8* read_hi,
                          const zpk_decode_desc* desc, u64 n, u8* dst, u64 dst_size, zpk_decode_result* res, hipStream_t st)
 {
     if (n == 0) return ZPK_OK;
     if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;               // one workgroup per LZ4 entry: the grid's x limit
-    c->totals_valid = 0;                                        // (the pipeline sets it again once it has summed its pieces)
+    c->last.totals_valid = 0;                                        // (the pipeline sets it again once it has summed its pieces)
     int rc;
-    if ((rc = grow(c, c->d_lists, N_LIST_SLOTS * n * sizeof(u32)))) return rc;
-    const u64 stride = c->d_lists.cap / (N_LIST_SLOTS * sizeof(u32));
-    auto list_at = [&](int slot) { return c->d_lists + (u64)slot * stride; };
+    if ((rc = grow(c, c->wave.d_lists, N_LIST_SLOTS * n * sizeof(u32)))) return rc;
+    const u64 stride = c->wave.d_lists.cap / (N_LIST_SLOTS * sizeof(u32));
+    auto list_at = [&](int slot) { return c->wave.d_lists + (u64)slot * stride; };
     u32* const retry_lz4 = list_at(S_RETRY_LZ4);
     u32* const retry_zstd = list_at(S_RETRY_ZSTD);
     u32* const left_lz4 = list_at(S_LZ4_RUNS);
@@ -1053,22 +1038,22 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
 #endif
     const u32 zstd_grid = (u32)(n < ZSTD_GRID_MAX ? n : ZSTD_GRID_MAX);
     const u32 exec_grid = (u32)(n < ZSTD_EXEC_GRID_MAX ? n : ZSTD_EXEC_GRID_MAX);
-    const bool maybe_zstd = c->zstd_hint != 0;                  // the host path knows its methods; device batches may hold any
-    if (maybe_zstd && (rc = grow(c, c->d_lit, (u64)(exec_grid > zstd_grid ? exec_grid : zstd_grid) * ZSTD_LIT_SCRATCH))) return rc;
+    const bool maybe_zstd = holds.zstd != 0;                  // the host path knows its methods; device batches may hold any
+    if (maybe_zstd && (rc = grow(c, c->wave.d_lit, (u64)(exec_grid > zstd_grid ? exec_grid : zstd_grid) * ZSTD_LIT_SCRATCH))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), st));
     ZPK_TRACE_STEP("memset");
 #define ZPK_KEV(k, j) do { if (c->profiling) (void)hipEventRecord(c->kev[k][j], st); } while (0)
     ZPK_KEV(ZPK_K_CLASSIFY, 0);
     hipLaunchKernelGGL(k_classify, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, src, desc, n, src_size, dst_size, res,
-                       c->d_lists, stride, c->d_counters);
+                       c->wave.d_lists, stride, c->d_counters);
     // largest entries first (see k_order_count); batches that fit the resident waves in one round have nothing to order
     const u32* zstd_list = list_at(S_ZSTD);
     const u32* lz4_list = list_at(S_LZ4);
     int gen_slot = S_LZ4_GEN;                                   // the LZ4 entries that are not plain frames
-    if (n >= c->order_min) {
+    if (n >= c->opt.order_min) {
         const dim3 og((u32)((n + 255) / 256), N_ORDERED);
-        hipLaunchKernelGGL(k_order_count, og, dim3(256), 0, st, desc, (const u32*)c->d_lists, stride, c->d_counters, c->order_fast_last);
-        hipLaunchKernelGGL(k_order_fill, og, dim3(256), 0, st, desc, (const u32*)c->d_lists, stride, c->d_lists, c->d_counters, c->order_fast_last);
+        hipLaunchKernelGGL(k_order_count, og, dim3(256), 0, st, desc, (const u32*)c->wave.d_lists, stride, c->d_counters, c->opt.order_fast_last);
+        hipLaunchKernelGGL(k_order_fill, og, dim3(256), 0, st, desc, (const u32*)c->wave.d_lists, stride, c->wave.d_lists, c->d_counters, c->opt.order_fast_last);
         zstd_list = list_at(S_ZSTD_ORDERED); lz4_list = list_at(S_LZ4_ORDERED);
         gen_slot = S_LZ4_GEN_ORDERED;
     }
@@ -1083,7 +1068,7 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     // LZ4: one wave per work-list slot (lz4_wave.h).  A batch that may hold both methods runs the LZ4 kernels on a SIDE stream of
     // low priority, beside the Zstandard stages: those are bound by the latency of their serial chains and by LDS capacity (12 or
     // 16 workgroups per CU leave 3-8 KiB of LDS and most of the vector issue slots idle), so LZ4 waves fill what they leave.
-    const bool maybe_lz4 = c->lz4_hint != 0;
+    const bool maybe_lz4 = holds.lz4 != 0;
     hipStream_t sl = st;
     // (measured, 125 000 mixed entries: 112.0 -> 90.9 ms per batch, the LZ4 kernel's 25 ms disappear inside the Zstandard stages, which
     // get 1-3 ms longer; a pure LZ4 batch — the Zstandard kernels find empty lists — is unchanged within noise: 618.4 vs 618.2 GiB/s.)
@@ -1091,11 +1076,11 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     // workgroup per entry, and 100 000 EMPTY workgroups trickling through at low priority beside the pre-decode stage cost it 15 ms
     // (71.9 -> 87.6 ms).  So the codec looks at the work-list counts of the batch BEFORE (copied to pinned memory behind every batch,
     // no synchronisation): both methods there, or nothing known yet -> side stream; a codec fed batches of one method stays on one stream.
-    if (!c->h_seen && hipHostMalloc((void**)&c->h_seen, 64, hipHostMallocDefault) == hipSuccess) {
-        c->h_seen->none = 0; c->h_seen->zstd = 1; c->h_seen->lz4 = 1; c->h_seen->lz4_gen = 1; c->h_seen->lz4_runs = 1;      // nothing known yet
+    if (!c->wave.h_seen && c->wave.h_seen.ready(64, hipHostMallocDefault)) {
+        c->wave.h_seen->none = 0; c->wave.h_seen->zstd = 1; c->wave.h_seen->lz4 = 1; c->wave.h_seen->lz4_gen = 1; c->wave.h_seen->lz4_runs = 1;      // nothing known yet
     }
-    const bool both_seen = c->zstd_hint >= 0 /* the host path knows */ || (c->h_seen && c->h_seen->zstd != 0 && (c->h_seen->lz4 != 0 || c->h_seen->lz4_gen != 0));
-    if (maybe_lz4 && maybe_zstd && both_seen && !(skip & 6) && fork_stream(c->side, st, true)) sl = c->side.s;
+    const bool both_seen = holds.zstd >= 0 /* the host path knows */ || (c->wave.h_seen && c->wave.h_seen->zstd != 0 && (c->wave.h_seen->lz4 != 0 || c->wave.h_seen->lz4_gen != 0));
+    if (maybe_lz4 && maybe_zstd && both_seen && !(skip & 6) && fork_stream(c->wave.side, st, true)) sl = c->wave.side.s;
     auto launch_lz4 = [&]() {
         if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_LZ4][0], sl);
         if (!(skip & 2) && maybe_lz4) {
@@ -1105,7 +1090,7 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
             hipStream_t sx = sl;
             // (a small batch is latency, not throughput: no second stream; neither when the batch BEFORE had no such entry — then the launch
             // is an empty grid in front of k_lz4_wave, and a batch that does have some pays the serial stretch once)
-            if (n >= 4096 && c->h_seen && c->h_seen->lz4_runs != 0 && fork_stream(c->left, sl, false)) sx = c->left.s;
+            if (n >= 4096 && c->wave.h_seen && c->wave.h_seen->lz4_runs != 0 && fork_stream(c->wave.left, sl, false)) sx = c->wave.left.s;
             hipLaunchKernelGGL(k_lz4_left, dim3((u32)(n < LZ4_LEFT_GRID_MAX ? n : LZ4_LEFT_GRID_MAX)), dim3(64), 0, sx, src, read_lo, read_hi, desc, dst, res,
                                (const u32*)left_lz4, c->d_counters, c->d_dbg, retry_lz4, wd_scale);
             // the hot kernel: plain frames only; whatever it does not finish cleanly is on its hand-over list
@@ -1121,15 +1106,15 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
             // above — when the batch BEFORE had such entries, or nothing is known yet.  Otherwise the list is expected to be empty and
             // is left to k_lz4_retry below, so that archives of plain frames pay for no launch they do not need (a batch that does have
             // some then runs them on the small grid, once).
-            if (!c->h_seen || c->h_seen->lz4_gen != 0)               // (the host-pointer paths do not bring the counts home: always launched there)
+            if (!c->wave.h_seen || c->wave.h_seen->lz4_gen != 0)               // (the host-pointer paths do not bring the counts home: always launched there)
                 hipLaunchKernelGGL(k_lz4_general, dim3((u32)(n < LZ4_GENERAL_GRID_MAX ? n : LZ4_GENERAL_GRID_MAX)), dim3(64), 0, sl, src, read_lo, read_hi,
                                    desc, dst, res, gen_list, c->d_counters, c->d_dbg, retry_lz4, wd_scale);
-            if (sx != sl) join_stream(c->left, sl);
+            if (sx != sl) join_stream(c->wave.left, sl);
             // whatever is left: k_lz4_general's list if that was not launched, what k_lz4_wave handed over, and the entries whose decoder
             // ran out of its time budget (ZPK_WATCHDOG_RETRY_SCALE times the budget; a small grid that leaves at once when the lists
             // are empty — the normal case)
             hipLaunchKernelGGL(k_lz4_retry, dim3((u32)(n < 256 ? n : 256)), dim3(64), 0, sl, src, read_lo, read_hi, desc, dst, res,
-                               (const u32*)c->d_lists, stride, c->d_counters, c->d_dbg, gen_slot);
+                               (const u32*)c->wave.d_lists, stride, c->d_counters, c->d_dbg, gen_slot);
         }
         if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_LZ4][1], sl);
     };
@@ -1141,30 +1126,30 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     // (zpk_codec_decode_stats out[7] bit 31, zpk_codec_last_error).
     bool two_stage = maybe_zstd && dst_size >= 64;
     ZPK_DEV(static const int fused_only = getenv("ZPK_ZSTD_FUSED") ? atoi(getenv("ZPK_ZSTD_FUSED")) : 0; if (fused_only) two_stage = false;)
-    c->fell_back_fused = 0;
-    if (two_stage && (grow(c, c->d_zarena, dst_size + 64) != ZPK_OK ||
-                      grow(c, c->d_zstate, 2 * n * sizeof(u32)) != ZPK_OK)) {
-        two_stage = false; c->fell_back_fused = 1;
+    c->last.fell_back_fused = 0;
+    if (two_stage && (grow(c, c->wave.d_zarena, dst_size + 64) != ZPK_OK ||
+                      grow(c, c->wave.d_zstate, 2 * n * sizeof(u32)) != ZPK_OK)) {
+        two_stage = false; c->last.fell_back_fused = 1;
         snprintf(c->err, sizeof(c->err), "note: no memory for the %llu-byte Zstandard sequence arena; this batch ran the fused decoder",
                  (unsigned long long)dst_size + 64);
     }
-    u32* const leftover = two_stage ? c->d_zstate + n : nullptr;          // entries k_zstd_exec hands to the full decoder
+    u32* const leftover = two_stage ? c->wave.d_zstate + n : nullptr;          // entries k_zstd_exec hands to the full decoder
     ZPK_KEV(ZPK_K_ZSTD_FSE, 0);
     if (!(skip & 4) && two_stage) {
-        HIPCHK(c, hipMemsetAsync(c->d_zstate, 0, n * sizeof(u32), st));          // entries k_zstd_fse never reaches stay unmarked
+        HIPCHK(c, hipMemsetAsync(c->wave.d_zstate, 0, n * sizeof(u32), st));          // entries k_zstd_fse never reaches stay unmarked
         const u64 zwaves = (n + ZF_ROWS - 1) / ZF_ROWS;
         hipLaunchKernelGGL(k_zstd_fse, dim3((u32)(zwaves < ZF_GRID_MAX ? zwaves : ZF_GRID_MAX)), dim3(64), 0, st, src, desc,
-                           zstd_list, c->d_counters, c->d_zarena, c->d_zstate);
+                           zstd_list, c->d_counters, c->wave.d_zarena, c->wave.d_zstate);
     }
     ZPK_KEV(ZPK_K_ZSTD_FSE, 1);
     ZPK_TRACE_STEP("k_zstd_fse");
     ZPK_KEV(ZPK_K_ZSTD, 0);
     if (!(skip & 4) && two_stage)
         hipLaunchKernelGGL(k_zstd_exec, dim3(exec_grid), dim3(ZSTD_WG_THREADS), 0, st, src, desc, dst, res,
-                           zstd_list, c->d_counters, c->d_lit, c->d_zarena, c->d_zstate, leftover, c->d_dbg);
+                           zstd_list, c->d_counters, c->wave.d_lit, c->wave.d_zarena, c->wave.d_zstate, leftover, c->d_dbg);
     if (!(skip & 4) && maybe_zstd)
         hipLaunchKernelGGL(k_zstd, dim3(zstd_grid), dim3(ZSTD_WG_THREADS), 0, st, src, desc, dst, res,
-                       two_stage ? (const u32*)leftover : zstd_list, c->d_counters, c->d_lit, c->d_dbg,
+                       two_stage ? (const u32*)leftover : zstd_list, c->d_counters, c->wave.d_lit, c->d_dbg,
                        two_stage ? (int)C_ZSTD_LEFT : (int)C_ZSTD, (int)C_ZSTD_HEAD, retry_zstd, (int)C_RETRY_ZSTD, wd_scale);
     ZPK_KEV(ZPK_K_ZSTD, 1);
     ZPK_TRACE_STEP("k_zstd");
@@ -1173,16 +1158,16 @@ static int decode_launch(zpk_codec* c, const u8* src, u64 src_size, const u8* re
     // when their list is empty (the normal case).
     if (!(skip & 4) && maybe_zstd)
         hipLaunchKernelGGL(k_zstd, dim3(zstd_grid < 128 ? zstd_grid : 128), dim3(ZSTD_WG_THREADS), 0, st, src, desc, dst, res,
-                           (const u32*)retry_zstd, c->d_counters, c->d_lit, c->d_dbg, (int)C_RETRY_ZSTD, (int)C_ZSTD_RETRY_HEAD,
+                           (const u32*)retry_zstd, c->d_counters, c->wave.d_lit, c->d_dbg, (int)C_RETRY_ZSTD, (int)C_ZSTD_RETRY_HEAD,
                            (u32*)nullptr, 0, (u32)ZPK_WATCHDOG_RETRY_SCALE);
     if (sl != st) {                                 // the LZ4 kernels, beside the above; the batch is done when both streams are
         launch_lz4();
-        join_stream(c->side, st);
+        join_stream(c->wave.side, st);
     }
     ZPK_TRACE_STEP("retry");
     // what this batch held, for the next one: none / zstd / lz4 / lz4_gen (adjacent counter words: zpk_layout.h) in one copy; did it have LZ4 entries of runs?
-    if (c->h_seen && c->zstd_hint < 0) (void)hipMemcpyAsync((void*)&c->h_seen->none, c->d_counters + C_NONE, 4 * sizeof(u32), hipMemcpyDeviceToHost, st);
-    if (c->h_seen) (void)hipMemcpyAsync((void*)&c->h_seen->lz4_runs, c->d_counters + C_LZ4_RUNS, sizeof(u32), hipMemcpyDeviceToHost, st);
+    if (c->wave.h_seen && holds.zstd < 0) (void)hipMemcpyAsync((void*)&c->wave.h_seen->none, c->d_counters + C_NONE, 4 * sizeof(u32), hipMemcpyDeviceToHost, st);
+    if (c->wave.h_seen) (void)hipMemcpyAsync((void*)&c->wave.h_seen->lz4_runs, c->d_counters + C_LZ4_RUNS, sizeof(u32), hipMemcpyDeviceToHost, st);
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
 }
@@ -1194,8 +1179,7 @@ int zpk_codec_decode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    c->zstd_hint = -1; c->lz4_hint = -1;
-    return decode_launch(c, src, src_size, src, src + src_size, desc, n, dst, dst_size, results, st);
+    return decode_launch(c, BatchMethods{ -1, -1 }, src, src_size, src, src + src_size, desc, n, dst, dst_size, results, st);
 }
 
 // An entry whose frames end before uncomp_size bytes exist (a short decode is not an error of the libraries): lib/zpack_read.c:466
@@ -1243,11 +1227,11 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
 #endif
 static int pin_ready(zpk_codec* c)
 {
-    if (!c->h_pj && hipHostMalloc((void**)&c->h_pj, 64, hipHostMallocDefault) != hipSuccess) { c->h_pj = nullptr; return ZPK_E_NOMEM; }
-    if (!c->piece_counters && hipHostMalloc((void**)&c->piece_counters, 64 * N_COUNTERS * sizeof(u32), hipHostMallocDefault) != hipSuccess) { c->piece_counters = nullptr; return ZPK_E_NOMEM; }
+    if (!c->pj.h_words.ready(64, hipHostMallocDefault)) return ZPK_E_NOMEM;
+    if (!c->pipe.piece_counters.ready(64 * N_COUNTERS * sizeof(u32), hipHostMallocDefault)) return ZPK_E_NOMEM;
     for (int k = 0; k < 2; k++) {
-        if (!c->h_pin[k] && hipHostMalloc((void**)&c->h_pin[k], ZPK_PIN_CHUNK, ZPK_PIN_FLAGS) != hipSuccess) { c->h_pin[k] = nullptr; snprintf(c->err, sizeof(c->err), "pinned staging: out of memory"); return ZPK_E_NOMEM; }
-        if (!c->pin_ev[k] && hipEventCreateWithFlags(&c->pin_ev[k], hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) { c->pin_ev[k] = nullptr; return ZPK_E_LAUNCH; }
+        if (!c->pipe.h_pin[k].ready(ZPK_PIN_CHUNK, ZPK_PIN_FLAGS)) { snprintf(c->err, sizeof(c->err), "pinned staging: out of memory"); return ZPK_E_NOMEM; }
+        if (c->pipe.pin_ev[k].ready(hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) return ZPK_E_LAUNCH;
     }
     return ZPK_OK;
 }
@@ -1305,21 +1289,21 @@ static int d2h_scatter(zpk_codec* c, const u8* d_base, u64 total, u64 n, uint8_t
     const u64 npieces = (total + ZPK_PIN_CHUNK - 1) / ZPK_PIN_CHUNK;
     u64 ei = 0;                                                                       // first entry that may still reach into the current piece
     e = pre(total < ZPK_PIN_CHUNK ? total : ZPK_PIN_CHUNK);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->h_pin[0], d_base, total < ZPK_PIN_CHUNK ? total : ZPK_PIN_CHUNK, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipEventRecord(c->pin_ev[0], st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pipe.h_pin[0], d_base, total < ZPK_PIN_CHUNK ? total : ZPK_PIN_CHUNK, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipEventRecord(c->pipe.pin_ev[0], st);
     for (u64 j = 0; j < npieces && e == hipSuccess; j++) {
         const int k = (int)(j & 1);
         const u64 p0 = j * ZPK_PIN_CHUNK, p1 = p0 + ZPK_PIN_CHUNK < total ? p0 + ZPK_PIN_CHUNK : total;
         if (j + 1 < npieces) {
             const u64 q0 = p1, q1 = q0 + ZPK_PIN_CHUNK < total ? q0 + ZPK_PIN_CHUNK : total;
             e = pre(q1);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->h_pin[k ^ 1], d_base + q0, q1 - q0, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipEventRecord(c->pin_ev[k ^ 1], st);
+            if (e == hipSuccess) e = hipMemcpyAsync(c->pipe.h_pin[k ^ 1], d_base + q0, q1 - q0, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipEventRecord(c->pipe.pin_ev[k ^ 1], st);
             if (e != hipSuccess) break;
         }
-        e = hipEventSynchronize(c->pin_ev[k]);
+        e = hipEventSynchronize(c->pipe.pin_ev[k]);
         if (e != hipSuccess) break;
-        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(dst_ptrs[i] + in_entry, c->h_pin[k] + in_piece, bytes); });
+        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(dst_ptrs[i] + in_entry, c->pipe.h_pin[k] + in_piece, bytes); });
     }
     return ZPK_OK;
 }
@@ -1329,12 +1313,12 @@ static int d2h_scatter(zpk_codec* c, const u8* d_base, u64 total, u64 n, uint8_t
 // while piece j is on the bus.  Entry i owns bytes [off(i), off(i) + len(i)) of the range (ascending in i); the gaps between entries
 // carry whatever the staging buffer held.  (One hipMemcpyAsync per entry out of pageable memory: 40 000 x 64 KiB took 0.5 s.)
 template <class OffFn, class LenFn>
-static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t* const* src_ptrs, OffFn off, LenFn len, hipError_t& e, hipStream_t st,
-                      u8* const* pins = nullptr, hipEvent_t* evs = nullptr)
+static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t* const* src_ptrs, OffFn off, LenFn len, hipError_t& e, hipStream_t st)
 {
-    int rc = pins ? ZPK_OK : pin_ready(c);
+    int rc = pin_ready(c);
     if (rc) return rc;
-    if (!pins) { pins = c->h_pin; evs = c->pin_ev; }
+    PinBlock<u8>* const pin = c->pipe.h_pin;
+    Event* const evs = c->pipe.pin_ev;
     e = hipSuccess;
     if (total == 0) return ZPK_OK;
     const u64 npieces = (total + ZPK_PIN_CHUNK - 1) / ZPK_PIN_CHUNK;
@@ -1344,8 +1328,8 @@ static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t*
         const int k = (int)(j & 1);
         const u64 p0 = j * ZPK_PIN_CHUNK, p1 = p0 + ZPK_PIN_CHUNK < total ? p0 + ZPK_PIN_CHUNK : total;
         if (used[k]) { e = hipEventSynchronize(evs[k]); if (e != hipSuccess) break; }      // the buffer's previous piece has left
-        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(pins[k] + in_piece, src_ptrs[i] + in_entry, bytes); });
-        e = hipMemcpyAsync(d_base + p0, pins[k], p1 - p0, hipMemcpyHostToDevice, st);
+        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(pin[k] + in_piece, src_ptrs[i] + in_entry, bytes); });
+        e = hipMemcpyAsync(d_base + p0, pin[k], p1 - p0, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipEventRecord(evs[k], st);
         used[k] = true;
     }
@@ -1374,7 +1358,7 @@ static int stage_sources(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc
 static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
                          zpk_decode_result* results, bool ddst, u64* home = nullptr);
 static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
-                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst = false)
+                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, BatchMethods holds, bool ddst = false)
 {
     int rc;
     if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
@@ -1386,7 +1370,7 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     // base pointer such that base + src_offset lands in the staged range; reads are clamped to it
     const u8* base = c->d_src - lo;
-    rc = decode_launch(c, base, image_size, c->d_src, c->d_src + (hi - lo) + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, n,
+    rc = decode_launch(c, holds, base, image_size, c->d_src, c->d_src + (hi - lo) + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, n,
                        c->d_dst, out_total, (zpk_decode_result*)c->d_res, c->stream);
     if (rc) return rc;
     e = hipMemcpyAsync(results, c->d_res, n * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
@@ -1447,10 +1431,10 @@ struct HostPiece { u64 e0, e1, clo, chi, olo, ohi; };
 
 static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
                                  const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results,
-                                 bool& taken, bool ddst = false)
+                                 bool& taken, BatchMethods holds, bool ddst = false)
 {
     taken = false;
-    const u64 min_entries = c->zstd_hint ? 12288 : 4096;
+    const u64 min_entries = holds.zstd ? 12288 : 4096;
     if (out_total < 3 * ZPK_PIPE_PIECE || n < 3 * min_entries) return ZPK_OK;
     // ---- pieces ----
     HostPiece pc[64];
@@ -1480,12 +1464,11 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
         (rc = grow(c, c->d_desc, n * sizeof(zpk_decode_desc))) ||
         (rc = grow(c, c->d_res, n * sizeof(zpk_decode_result))) || (rc = pin_ready(c))) return rc;
-    if (!c->s_up && hipStreamCreateWithFlags(&c->s_up, hipStreamNonBlocking) != hipSuccess) { c->s_up = nullptr; return ZPK_OK; }
-    if (!c->s_dn && hipStreamCreateWithFlags(&c->s_dn, hipStreamNonBlocking) != hipSuccess) { c->s_dn = nullptr; return ZPK_OK; }
+    if (c->pipe.s_up.ready(hipStreamNonBlocking) != hipSuccess || c->pipe.s_dn.ready(hipStreamNonBlocking) != hipSuccess) return ZPK_OK;
     for (int k = 0; k < 2 * np; k++)
-        if (!c->pipe_ev[k] && hipEventCreateWithFlags(&c->pipe_ev[k], hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) { c->pipe_ev[k] = nullptr; return ZPK_OK; }
+        if (c->pipe.ev[k].ready(hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) return ZPK_OK;
     taken = true;
-    c->pipe_last++;
+    c->last.pipe++;
     hipError_t e = hipMemcpyAsync(c->d_desc, hd, n * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     std::atomic<int> uploaded(0), launched(0);   // pieces whose upload / decode has been ENQUEUED with its event recorded (-1: failed)
@@ -1496,8 +1479,8 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         if (hipSetDevice(device) != hipSuccess) { uploaded.store(-1); return; }
         for (int k = 0; k < np; k++) {
             hipError_t ue = hipSuccess;
-            if (pc[k].chi > pc[k].clo) ue = hipMemcpyAsync(c->d_src + (pc[k].clo - lo), image + pc[k].clo, pc[k].chi - pc[k].clo, hipMemcpyHostToDevice, c->s_up);
-            if (ue == hipSuccess) ue = hipEventRecord(c->pipe_ev[2 * k], c->s_up);
+            if (pc[k].chi > pc[k].clo) ue = hipMemcpyAsync(c->d_src + (pc[k].clo - lo), image + pc[k].clo, pc[k].chi - pc[k].clo, hipMemcpyHostToDevice, c->pipe.s_up);
+            if (ue == hipSuccess) ue = hipEventRecord(c->pipe.ev[2 * k], c->pipe.s_up);
             if (ue != hipSuccess) { uploaded.store(-1); return; }
             uploaded.store(k + 1);
         }
@@ -1508,13 +1491,13 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             int u;
             while ((u = uploaded.load()) >= 0 && u <= k) std::this_thread::yield();
             int lrc = u < 0 ? (int)ZPK_E_LAUNCH : (int)ZPK_OK;
-            if (lrc == ZPK_OK && hipStreamWaitEvent(c->stream, c->pipe_ev[2 * k], 0) != hipSuccess) lrc = ZPK_E_LAUNCH;
+            if (lrc == ZPK_OK && hipStreamWaitEvent(c->stream, c->pipe.ev[2 * k], 0) != hipSuccess) lrc = ZPK_E_LAUNCH;
             const HostPiece& P = pc[k];
             if (lrc == ZPK_OK)
-                lrc = decode_launch(c, base, image_size, c->d_src + (P.clo - lo), c->d_src + (P.chi - lo) + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc + P.e0,
+                lrc = decode_launch(c, holds, base, image_size, c->d_src + (P.clo - lo), c->d_src + (P.chi - lo) + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc + P.e0,
                                     P.e1 - P.e0, c->d_dst, out_total, (zpk_decode_result*)c->d_res + P.e0, c->stream);
-            if (lrc == ZPK_OK && hipMemcpyAsync(c->piece_counters[k], c->d_counters, N_COUNTERS * sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess) lrc = ZPK_E_LAUNCH;
-            if (lrc == ZPK_OK && hipEventRecord(c->pipe_ev[2 * k + 1], c->stream) != hipSuccess) lrc = ZPK_E_LAUNCH;
+            if (lrc == ZPK_OK && hipMemcpyAsync(c->pipe.piece_counters[k], c->d_counters, N_COUNTERS * sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess) lrc = ZPK_E_LAUNCH;
+            if (lrc == ZPK_OK && hipEventRecord(c->pipe.ev[2 * k + 1], c->stream) != hipSuccess) lrc = ZPK_E_LAUNCH;
             if (lrc != ZPK_OK) { launch_rc.store(lrc); launched.store(-1); return; }
             launched.store(k + 1);
         }
@@ -1533,10 +1516,10 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             int l;
             while ((l = launched.load()) >= 0 && l <= next) std::this_thread::yield();
             if (l < 0) return hipErrorUnknown;
-            hipError_t pe = hipStreamWaitEvent(c->s_dn, c->pipe_ev[2 * next + 1], 0);
+            hipError_t pe = hipStreamWaitEvent(c->pipe.s_dn, c->pipe.ev[2 * next + 1], 0);
             const HostPiece& P = pc[next];
             if (pe == hipSuccess) pe = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result),
-                                                      hipMemcpyDeviceToHost, c->s_dn);      // in stream order before the bytes: there when they are scattered
+                                                      hipMemcpyDeviceToHost, c->pipe.s_dn);      // in stream order before the bytes: there when they are scattered
             if (pe != hipSuccess) return pe;
             next++;
         }
@@ -1551,30 +1534,30 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             while ((l = launched.load()) >= 0 && l <= k) std::this_thread::yield();
             if (l < 0) { e = hipErrorUnknown; break; }
             const HostPiece& P = pc[k];
-            e = hipStreamWaitEvent(c->s_dn, c->pipe_ev[2 * k + 1], 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->s_dn);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->s_dn);
+            e = hipStreamWaitEvent(c->pipe.s_dn, c->pipe.ev[2 * k + 1], 0);
+            if (e == hipSuccess) e = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->pipe.s_dn);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->pipe.s_dn);
             if (e != hipSuccess) break;
             rc = span_copy_enqueue(c, P.e1 - P.e0, [&](u64 k2) {
                 const u64 i = P.e0 + k2, p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
                 return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], p };
-            }, c->s_dn);
+            }, c->pipe.s_dn);
         }
     } else
     rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; },
-                     [&](u64 i) { const u64 p = results[i].produced; return p > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : p; }, e, c->s_dn, pre);
+                     [&](u64 i) { const u64 p = results[i].produced; return p > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : p; }, e, c->pipe.s_dn, pre);
     if (up_threaded) t_up.join();
     if (launch_threaded) t_launch.join();
     if (!ddst && rc == ZPK_OK && e == hipSuccess) e = pre(out_total + 1);       // (pieces with no output bytes: their results still come back)
-    if (rc == ZPK_OK && e == hipSuccess) e = hipStreamSynchronize(c->s_dn);
+    if (rc == ZPK_OK && e == hipSuccess) e = hipStreamSynchronize(c->pipe.s_dn);
     if (launch_rc.load() != ZPK_OK) rc = launch_rc.load();
     else if (rc == ZPK_OK && e != hipSuccess) { snprintf(c->err, sizeof(c->err), "host decode pipeline: %s", hipGetErrorString(e)); rc = ZPK_E_LAUNCH; }
-    if (rc != ZPK_OK) { (void)hipStreamSynchronize(c->s_up); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->s_dn); }
+    if (rc != ZPK_OK) { (void)hipStreamSynchronize(c->pipe.s_up); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->pipe.s_dn); }
     for (u64 i = 0; i < n && rc == ZPK_OK; i++) if (results[i].produced > desc[i].dst_capacity) results[i].produced = desc[i].dst_capacity;     // (cannot happen)
     if (rc == ZPK_OK && hipStreamSynchronize(c->stream) == hipSuccess) {
-        memset(c->host_totals, 0, sizeof(c->host_totals));
-        for (int k = 0; k < np; k++) for (int w = 0; w < N_COUNTERS; w++) c->host_totals[w] += c->piece_counters[k][w];
-        c->totals_valid = 1;
+        memset(c->last.host_totals, 0, sizeof(c->last.host_totals));
+        for (int k = 0; k < np; k++) for (int w = 0; w < N_COUNTERS; w++) c->last.host_totals[w] += c->pipe.piece_counters[k][w];
+        c->last.totals_valid = 1;
     }
     if (rc == ZPK_OK) rc = rehash_short_entries(c, hd, desc, n, dst_ptrs, results, ddst);
     return rc;
@@ -1594,21 +1577,21 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
 {
     const u64 nb = hb.size(), n = d.uncomp_size;
     hipStream_t st = c->stream;
-    PjBlock* const B = (PjBlock*)c->d_pj_blocks;
-    u32* const S = (u32*)c->d_pj_S;
+    PjBlock* const B = (PjBlock*)c->pj.d_blocks;
+    u32* const S = (u32*)c->pj.d_S;
     hipError_t e;
     int rc;
     if (chunk_blocks * ZPK_PJ_MAX_CHUNKS < nb) chunk_blocks = (nb + ZPK_PJ_MAX_CHUNKS - 1) / ZPK_PJ_MAX_CHUNKS;      // (small blocks, a very large entry: larger chunks)
     const u64 nchunks = (nb + chunk_blocks - 1) / chunk_blocks;
     if (nchunks > ZPK_PJ_MAX_CHUNKS) return ZPK_OK;
-    for (u64 k = 0; k < nchunks; k++) if (!c->pj_ev[k] && hipEventCreateWithFlags(&c->pj_ev[k], hipEventDisableTiming) != hipSuccess) { c->pj_ev[k] = nullptr; return ZPK_OK; }
-    if (!c->s_dn && hipStreamCreateWithFlags(&c->s_dn, hipStreamNonBlocking) != hipSuccess) { c->s_dn = nullptr; return ZPK_OK; }
+    for (u64 k = 0; k < nchunks; k++) if (c->pj.ev[k].ready(hipEventDisableTiming) != hipSuccess) return ZPK_OK;
+    if (c->pipe.s_dn.ready(hipStreamNonBlocking) != hipSuccess) return ZPK_OK;
     if ((rc = pin_ready(c))) return rc;
     // the XXH3 of the output runs BESIDE all this on its own stream, section by section as the chunks become final (xxh3_span.h: the
     // partial sums of a section's blocks side by side, then the one-wave chain over them — 14 ms for 256 MiB, as long as everything else
     // together, which is why it must not come behind)
-    if (!c->left.s && hipStreamCreateWithFlags(&c->left.s, hipStreamNonBlocking) != hipSuccess) { c->left.s = nullptr; return ZPK_OK; }
-    hipStream_t sh = c->left.s;
+    if (c->wave.left.s.ready(hipStreamNonBlocking) != hipSuccess) return ZPK_OK;
+    hipStream_t sh = c->wave.left.s;
     const u64 part_blocks = xxh3_span_blocks(n), ngroups = part_blocks / XS_GROUP;
     if ((rc = grow(c, c->d_xpart, 256 + part_blocks * 64 + 256))) return rc;
     zpk_span* const d_span = (zpk_span*)c->d_xpart;
@@ -1633,14 +1616,14 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
         auto pre = [&](u64 q1) -> hipError_t {
             while (waited < nchunks && (waited == 0 || chunk_hi[waited - 1] < q1)) {
                 while (enqueued.load(std::memory_order_acquire) <= waited) { if (give_up.load(std::memory_order_acquire)) return hipErrorUnknown; std::this_thread::yield(); }
-                const hipError_t we = hipStreamWaitEvent(c->s_dn, c->pj_ev[waited], 0);
+                const hipError_t we = hipStreamWaitEvent(c->pipe.s_dn, c->pj.ev[waited], 0);
                 if (we != hipSuccess) return we;
                 waited++;
             }
             return hipSuccess;
         };
         uint8_t* optr[1] = { dst_ptr };
-        dn_rc = d2h_scatter(c, d_out, n, 1, optr, [&](u64) { return (u64)0; }, [&](u64) { return n; }, dn_e, c->s_dn, pre);
+        dn_rc = d2h_scatter(c, d_out, n, 1, optr, [&](u64) { return (u64)0; }, [&](u64) { return n; }, dn_e, c->pipe.s_dn, pre);
     };
     std::thread dn_thread;
     bool dn_started = false;
@@ -1653,14 +1636,14 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
         const u32 b0 = (u32)(k * chunk_blocks), b1 = (u32)(b0 + chunk_blocks < nb ? b0 + chunk_blocks : nb);
         const u64 lo = hb[b0].out_off, hi = chunk_hi[k];
         const u32 grid = (u32)((hi - (lo & ~3ull) + 1023) / 1024), jgrid = (u32)((hi - lo + 1023) / 1024);
-        (void)hipMemsetAsync(c->d_pj_flags + PJ_ROUND0, 0, PJ_MAX_ROUNDS * 4, st);
+        (void)hipMemsetAsync(c->pj.d_flags + PJ_ROUND0, 0, PJ_MAX_ROUNDS * 4, st);
         init(b0, b1, st);
         if (grid) {
             for (u32 r = 0; r < PJ_MAX_ROUNDS; r++)
-                hipLaunchKernelGGL(k_pj_jump, dim3(jgrid), dim3(256), 0, st, S, (const PjBlock*)B, b0, b1, (u32)nb, c->d_pj_flags, r);
-            hipLaunchKernelGGL(k_pj_gather, dim3(grid), dim3(256), 0, st, (const u32*)S, (const PjBlock*)B, b0, b1, (u32)nb, (const u8*)c->d_src, gather_src_size, d_out, c->d_pj_flags);
+                hipLaunchKernelGGL(k_pj_jump, dim3(jgrid), dim3(256), 0, st, S, (const PjBlock*)B, b0, b1, (u32)nb, c->pj.d_flags, r);
+            hipLaunchKernelGGL(k_pj_gather, dim3(grid), dim3(256), 0, st, (const u32*)S, (const PjBlock*)B, b0, b1, (u32)nb, (const u8*)c->d_src, gather_src_size, d_out, c->pj.d_flags);
         }
-        if (hipEventRecord(c->pj_ev[k], st) != hipSuccess || hipStreamWaitEvent(sh, c->pj_ev[k], 0) != hipSuccess) { launch_failed = true; break; }
+        if (hipEventRecord(c->pj.ev[k], st) != hipSuccess || hipStreamWaitEvent(sh, c->pj.ev[k], 0) != hipSuccess) { launch_failed = true; break; }
         enqueued.store(k + 1, std::memory_order_release);
         const bool last = k + 1 == nchunks;
         const u64 g_hi = last ? ngroups : (hi >> 10) / XS_GROUP;                       // groups of 64 blocks that are final now
@@ -1670,8 +1653,8 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
         if (g_hi > g_lo) g_lo = g_hi;
     }
     if (launch_failed) give_up.store(1, std::memory_order_release);
-    e = launch_failed ? hipErrorUnknown : hipMemcpyAsync(&c->h_pj[0], d_hash, 8, hipMemcpyDeviceToHost, sh);
-    if (e == hipSuccess) e = hipMemcpyAsync(&c->h_pj[1], c->d_pj_flags, 4, hipMemcpyDeviceToHost, sh);
+    e = launch_failed ? hipErrorUnknown : hipMemcpyAsync(&c->pj.h_words[0], d_hash, 8, hipMemcpyDeviceToHost, sh);
+    if (e == hipSuccess) e = hipMemcpyAsync(&c->pj.h_words[1], c->pj.d_flags, 4, hipMemcpyDeviceToHost, sh);
     if (dn_started) dn_thread.join(); else if (!launch_failed && dst_ptr) download();
     if (e != hipSuccess || dn_rc != ZPK_OK || dn_e != hipSuccess) {
         (void)hipDeviceSynchronize();
@@ -1679,15 +1662,15 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
         snprintf(c->err, sizeof(c->err), "large frame: %s", hipGetErrorString(e != hipSuccess ? e : dn_e));
         return ZPK_E_LAUNCH;
     }
-    e = dst_ptr ? hipStreamSynchronize(c->s_dn) : hipSuccess;
+    e = dst_ptr ? hipStreamSynchronize(c->pipe.s_dn) : hipSuccess;
     const hipError_t e2 = hipStreamSynchronize(sh), e3 = hipStreamSynchronize(st);
     if (e == hipSuccess) e = e2 != hipSuccess ? e2 : e3;
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large frame: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    if ((u32)c->h_pj[1] != 0) return ZPK_OK;                                                       // PJ_ERR: something was irregular after all
-    const zpk_decode_result v = dec_hash_verdict(d, c->h_pj[0]);
+    if ((u32)c->pj.h_words[1] != 0) return ZPK_OK;                                                       // PJ_ERR: something was irregular after all
+    const zpk_decode_result v = dec_hash_verdict(d, c->pj.h_words[0]);
     if (v.status != DEC_R_OK && !accept_mismatch) return ZPK_OK;                                   // (the one-wave decoder gives this entry's verdict)
     result = v;
-    c->big_last[0]++; c->big_last[1] += (u32)nb;
+    c->last.big[0]++; c->last.big[1] += (u32)nb;
     redo = 0;
     return ZPK_OK;
 }
@@ -1708,29 +1691,29 @@ static int decode_big_lz4_single(zpk_codec* c, const BigSrc& src, const zpk_deco
     const u64 total_recs = (u64)blocks.back().rec_base + ((blocks.back().comp_size >> 31) ? 0 : (blocks.back().comp_size / 3 + 2));
     int rc;
     if ((rc = grow(c, c->d_src, d.comp_size + ZPK_SRC_SLACK)) || (!dst.on_device && (rc = grow(c, c->d_dst, n + 16))) ||
-        (rc = grow(c, c->d_pj_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->d_pj_recs, (total_recs + 64) * 8)) ||
-        (rc = grow(c, c->d_pj_masks, nb * (PJ_BLOCK / 8))) || (rc = grow(c, c->d_pj_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }     // no memory for the scratch: the one-wave decoder
-    if (!c->d_pj_flags && hipMalloc(&c->d_pj_flags.p, 256) != hipSuccess) { c->d_pj_flags.p = nullptr; (void)hipGetLastError(); return ZPK_OK; }
+        (rc = grow(c, c->pj.d_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->pj.d_recs, (total_recs + 64) * 8)) ||
+        (rc = grow(c, c->pj.d_masks, nb * (PJ_BLOCK / 8))) || (rc = grow(c, c->pj.d_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }     // no memory for the scratch: the one-wave decoder
+    if (!c->pj.d_flags.ensure(256)) return ZPK_OK;
     hipStream_t st = c->stream;
     hipError_t e = hipMemcpyAsync(c->d_src, src.archive + d.src_offset, d.comp_size, src.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_pj_blocks, blocks.data(), nb * sizeof(PjBlock), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_pj_flags, 0, 256, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pj.d_blocks, blocks.data(), nb * sizeof(PjBlock), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->pj.d_flags, 0, 256, st);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    PjBlock* const B = (PjBlock*)c->d_pj_blocks;
-    u32* const S = (u32*)c->d_pj_S;
-    hipLaunchKernelGGL(k_pj_parse, dim3((u32)nb), dim3(64), 0, st, (const u8*)c->d_src, d.comp_size, B, (u32)nb, (u64*)c->d_pj_recs, (u32*)c->d_pj_masks, c->d_pj_flags);
-    hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, (u32)nb, c->d_pj_flags);
+    PjBlock* const B = (PjBlock*)c->pj.d_blocks;
+    u32* const S = (u32*)c->pj.d_S;
+    hipLaunchKernelGGL(k_pj_parse, dim3((u32)nb), dim3(64), 0, st, (const u8*)c->d_src, d.comp_size, B, (u32)nb, (u64*)c->pj.d_recs, (u32*)c->pj.d_masks, c->pj.d_flags);
+    hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, (u32)nb, c->pj.d_flags);
     u32 hf[4] = {0, 0, 0, 0};
     // the verdict of the parse and the block table with its output offsets, back on the host (the one round trip of this path):
     // chunk k = blocks [k * ZPK_PJ_CHUNK_BLOCKS, ...) = output bytes [lo_k, hi_k)
     std::vector<PjBlock> hb(nb);
-    e = hipMemcpyAsync(hf, c->d_pj_flags, sizeof(hf), hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(hf, c->pj.d_flags, sizeof(hf), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), B, nb * sizeof(PjBlock), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large LZ4 frame: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     if (hf[PJ_ERR] || (((u64)hf[PJ_TOTAL + 1] << 32) | hf[PJ_TOTAL]) != n) return ZPK_OK;          // irregular, or the sizes do not add up
     auto init = [&](u32 b0, u32 b1, hipStream_t s2) {
-        hipLaunchKernelGGL(k_pj_init, dim3(b1 - b0), dim3(256), 0, s2, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->d_pj_recs, (const u32*)c->d_pj_masks, S, n, c->d_pj_flags, independent);
+        hipLaunchKernelGGL(k_pj_init, dim3(b1 - b0), dim3(256), 0, s2, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->pj.d_recs, (const u32*)c->pj.d_masks, S, n, c->pj.d_flags, independent);
     };
     return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS, d.comp_size, init, true, dst.on_device ? dst.p : (u8*)c->d_dst, dst.on_device ? nullptr : dst.p, result, redo);
 }
@@ -1759,50 +1742,50 @@ static int decode_big_zstd_single(zpk_codec* c, const BigSrc& src, const zpk_dec
               aux_rep = aux_state + ((nb * 4 + 255) & ~255ull), aux_size = aux_rep + nb * 12 + 256;
     int rc;
     if ((rc = grow(c, c->d_src, arena_off + lit_total + ZPK_SRC_SLACK)) || (!dst.on_device && (rc = grow(c, c->d_dst, n + 16))) ||
-        (rc = grow(c, c->d_pj_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->d_zpj_blocks, nb * sizeof(ZpjBlock))) ||
-        (rc = grow(c, c->d_zpj_aux, aux_size)) || (rc = grow(c, c->d_pj_recs, (slots + 64) * 8)) ||
-        (rc = grow(c, c->d_zpj_pos, (slots + 64) * 8)) || (rc = grow(c, c->d_pj_masks, nb * (ZPJ_BLOCK / 8))) ||
-        (rc = grow(c, c->d_pj_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }        // no memory for the scratch: the one-wave decoder
-    if (!c->d_pj_flags && hipMalloc(&c->d_pj_flags.p, 256) != hipSuccess) { c->d_pj_flags.p = nullptr; (void)hipGetLastError(); return ZPK_OK; }
+        (rc = grow(c, c->pj.d_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->pj.d_zblocks, nb * sizeof(ZpjBlock))) ||
+        (rc = grow(c, c->pj.d_zaux, aux_size)) || (rc = grow(c, c->pj.d_recs, (slots + 64) * 8)) ||
+        (rc = grow(c, c->pj.d_zpos, (slots + 64) * 8)) || (rc = grow(c, c->pj.d_masks, nb * (ZPJ_BLOCK / 8))) ||
+        (rc = grow(c, c->pj.d_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }        // no memory for the scratch: the one-wave decoder
+    if (!c->pj.d_flags.ensure(256)) return ZPK_OK;
     hipStream_t st = c->stream;
-    u8* const aux = (u8*)c->d_zpj_aux;
+    u8* const aux = (u8*)c->pj.d_zaux;
     u32 hflags[ZPJ_FLAG_WORDS]; memset(hflags, 0, sizeof(hflags));
     hflags[ZPJ_CNT + C_ZSTD] = (u32)list.size();
     std::vector<PjBlock> hb(nb);
     memset(hb.data(), 0, nb * sizeof(PjBlock));
     hipError_t e = hipMemcpyAsync(c->d_src, src.archive + d.src_offset, d.comp_size, src.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_zpj_blocks, blocks.data(), nb * sizeof(ZpjBlock), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_pj_blocks, hb.data(), nb * sizeof(PjBlock), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pj.d_zblocks, blocks.data(), nb * sizeof(ZpjBlock), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pj.d_blocks, hb.data(), nb * sizeof(PjBlock), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(aux + aux_desc, items.data(), nb * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && !list.empty()) e = hipMemcpyAsync(aux + aux_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(aux + aux_state, 0, aux_size - aux_state, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_pj_flags, hflags, sizeof(hflags), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pj.d_flags, hflags, sizeof(hflags), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    PjBlock* const B = (PjBlock*)c->d_pj_blocks;
-    ZpjBlock* const ZB = (ZpjBlock*)c->d_zpj_blocks;
-    u32* const S = (u32*)c->d_pj_S;
+    PjBlock* const B = (PjBlock*)c->pj.d_blocks;
+    ZpjBlock* const ZB = (ZpjBlock*)c->pj.d_zblocks;
+    u32* const S = (u32*)c->pj.d_S;
     u32* const state = (u32*)(aux + aux_state);
     u32* const rep_out = (u32*)(aux + aux_rep);
     if (!list.empty()) {
         const u32 rows = (u32)list.size();
         const u32 grid = (rows + ZF_ROWS - 1) / ZF_ROWS < ZF_GRID_MAX ? (rows + ZF_ROWS - 1) / ZF_ROWS : ZF_GRID_MAX;
         hipLaunchKernelGGL(k_zstd_fse_blocks, dim3(grid), dim3(64), 0, st, (const u8*)c->d_src, (const zpk_decode_desc*)(aux + aux_desc), (const u32*)(aux + aux_list),
-                           c->d_pj_flags + ZPJ_CNT, (u64*)c->d_pj_recs, state, rep_out, d.comp_size);
+                           c->pj.d_flags + ZPJ_CNT, (u64*)c->pj.d_recs, state, rep_out, d.comp_size);
     }
-    hipLaunchKernelGGL(k_zpj_lit, dim3((u32)nb), dim3(64), 0, st, c->d_src, arena_off + lit_total, arena_off, (const ZpjBlock*)ZB, (u32)nb, c->d_pj_flags);
-    hipLaunchKernelGGL(k_zpj_reps, dim3(1), dim3(64), 0, st, ZB, (u32)nb, (const u32*)state, (const u32*)rep_out, c->d_pj_flags);
-    hipLaunchKernelGGL(k_zpj_pos, dim3((u32)nb), dim3(256), 0, st, (const ZpjBlock*)ZB, B, (u32)nb, (const u64*)c->d_pj_recs, (u64*)c->d_zpj_pos, (u32*)c->d_pj_masks, c->d_pj_flags);
-    hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, (u32)nb, c->d_pj_flags);
+    hipLaunchKernelGGL(k_zpj_lit, dim3((u32)nb), dim3(64), 0, st, c->d_src, arena_off + lit_total, arena_off, (const ZpjBlock*)ZB, (u32)nb, c->pj.d_flags);
+    hipLaunchKernelGGL(k_zpj_reps, dim3(1), dim3(64), 0, st, ZB, (u32)nb, (const u32*)state, (const u32*)rep_out, c->pj.d_flags);
+    hipLaunchKernelGGL(k_zpj_pos, dim3((u32)nb), dim3(256), 0, st, (const ZpjBlock*)ZB, B, (u32)nb, (const u64*)c->pj.d_recs, (u64*)c->pj.d_zpos, (u32*)c->pj.d_masks, c->pj.d_flags);
+    hipLaunchKernelGGL(k_pj_scan, dim3(1), dim3(64), 0, st, B, (u32)nb, c->pj.d_flags);
     u32 hf[4] = {0, 0, 0, 0};
-    e = hipMemcpyAsync(hf, c->d_pj_flags, sizeof(hf), hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(hf, c->pj.d_flags, sizeof(hf), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), B, nb * sizeof(PjBlock), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large Zstandard frame: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    c->zpj_last_err = hf[PJ_ERR] | ((((u64)hf[PJ_TOTAL + 1] << 32) | hf[PJ_TOTAL]) != n ? 0x40000000u : 0u);
+    c->last.zpj_err = hf[PJ_ERR] | ((((u64)hf[PJ_TOTAL + 1] << 32) | hf[PJ_TOTAL]) != n ? 0x40000000u : 0u);
     if (hf[PJ_ERR] || (((u64)hf[PJ_TOTAL + 1] << 32) | hf[PJ_TOTAL]) != n) return ZPK_OK;          // irregular, or the sizes do not add up
     auto init = [&](u32 b0, u32 b1, hipStream_t s2) {
-        hipLaunchKernelGGL(k_zpj_init, dim3(b1 - b0), dim3(256), 0, s2, (const ZpjBlock*)ZB, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->d_pj_recs, (const u64*)c->d_zpj_pos,
-                           (const u32*)c->d_pj_masks, S, n, c->d_pj_flags);
+        hipLaunchKernelGGL(k_zpj_init, dim3(b1 - b0), dim3(256), 0, s2, (const ZpjBlock*)ZB, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->pj.d_recs, (const u64*)c->pj.d_zpos,
+                           (const u32*)c->pj.d_masks, S, n, c->pj.d_flags);
     };
     return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS * PJ_BLOCK / ZPJ_BLOCK, arena_off + lit_total, init, false, dst.on_device ? dst.p : (u8*)c->d_dst, dst.on_device ? nullptr : dst.p, result, redo);
 }
@@ -1851,9 +1834,8 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     }
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_desc, hd.data(), nsub * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    c->zstd_hint = has_zstd; c->lz4_hint = has_lz4;
     // (image size = the staged bytes + 1: the last frame still passes the `offset + comp_size < file_size` guard of :331)
-    rc = decode_launch(c, c->d_src, ct + 1, c->d_src, c->d_src + ct + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, nsub,
+    rc = decode_launch(c, BatchMethods{ has_zstd, has_lz4 }, c->d_src, ct + 1, c->d_src, c->d_src + ct + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, nsub,
                        c->d_dst, ot, (zpk_decode_result*)c->d_res, c->stream);
     if (rc) return rc;
     if ((rc = xxh3_spans_launch(c, c->d_dst, spans.data(), ng, part_blocks, h_hash.data(), c->stream))) return rc;
@@ -1869,7 +1851,7 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         redo[g0 + k] = ok ? 0 : 1;
         if (!ok) continue;
         results[E.idx] = dec_hash_verdict(d, h_hash[k]);
-        c->big_last[0]++; c->big_last[1] += (u32)E.nsub;
+        c->last.big[0]++; c->last.big[1] += (u32)E.nsub;
     }
     if (ddst) {                                                                        // DEVICE destinations: one launch of k_span_copy
         auto row = [&](u64 k) { return zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size }; };
@@ -1915,7 +1897,7 @@ static int decode_big_single(zpk_codec* c, PjEntry& P, const zpk_decode_desc& d,
 }
 
 // the counts decode_stats2 reports of the most recent decode call: none yet
-static void begin_decode_call(zpk_codec* c) { c->big_last[0] = c->big_last[1] = 0; c->walk_last[0] = c->walk_last[1] = 0; c->span_last[0] = c->span_last[1] = 0; c->pipe_last = c->sc_last = 0; }
+static void begin_decode_call(zpk_codec* c) { LastCall& l = c->last; l.big[0] = l.big[1] = 0; l.walk[0] = l.walk[1] = 0; l.span[0] = l.span[1] = 0; l.pipe = l.sc = 0; }
 
 static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                    uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst = false)
@@ -1932,14 +1914,9 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
         while (first + cnt < n) {
             const zpk_decode_desc& d = desc[first + cnt];
             // stored entries copy exactly uncomp_size bytes (lib/zpack_read.c:366); the decoders may fill all of max_size
-            const u64 slot_bytes = span_copy_read_slot_bytes(d.method == ZPK_METHOD_NONE, d.uncomp_size, d.dst_capacity);
             const u64 slot = span_copy_read_slot(d.method == ZPK_METHOD_NONE, d.uncomp_size, d.dst_capacity);      // (span_copy_plan.h states the layout for both kinds of destination)
             if (cnt && (out_total + slot > ZPK_HOST_CHUNK_BYTES || cnt >= 0x7FFFFFF0ull)) break;
-            hd[first + cnt] = d;
-            hd[first + cnt].dst_offset = out_total;
-            // (the device still judges `max_size < uncomp_size` on the caller's capacity: dst_capacity stays as given
-            // except for stored entries, whose slot is the smaller of the two and whose guard passed or failed on the host values)
-            if (d.method == ZPK_METHOD_NONE && d.dst_capacity >= d.uncomp_size) hd[first + cnt].dst_capacity = slot_bytes;
+            hd[first + cnt] = span_copy_staged_desc(d, d.method == ZPK_METHOD_NONE, out_total);
             out_total += slot;
             if (dec_has_payload(d) && dec_src_in_image(d, archive_size)) { if (d.src_offset < lo) lo = d.src_offset; if (d.src_offset + d.comp_size > hi) hi = d.src_offset + d.comp_size; comp_sum += d.comp_size; }
             if (d.method == ZPK_METHOD_ZSTD) has_zstd = 1;
@@ -1947,7 +1924,7 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
             cnt++;
         }
         if (lo > hi) { lo = 0; hi = 0; }
-        c->zstd_hint = has_zstd; c->lz4_hint = has_lz4;
+        const BatchMethods holds = { has_zstd, has_lz4 };
         const u8* image = archive; u64 image_size = archive_size;
         if (hi - lo > 2 * comp_sum + (1u << 20)) {
             // sparse picks out of a large archive: stage only the payloads.  Entries that pass the reference's offset guard
@@ -1966,12 +1943,11 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
             image = gathered; image_size = total; lo = 0; hi = pos;
         }
         bool piped = false;
-        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, piped, ddst);
+        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, piped, holds, ddst);
         if (rc == ZPK_OK && !piped)
-            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, ddst);
+            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, holds, ddst);
         first += cnt;
     }
-    c->zstd_hint = -1; c->lz4_hint = -1;
     free(gathered);
     free(hd);
     return rc;
@@ -1992,11 +1968,11 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
     std::vector<BigEntry> be;
     std::vector<BigSub> subs;
     std::vector<PjEntry> pj;                                                          // large single frames (lz4_pj.h, zstd_pj.h)
-    if (archive && c->dec_split_min != ~0ull) {
+    if (archive && c->opt.dec_split_min != ~0ull) {
         try {
             for (u64 i = 0; i < n; i++) {
                 const zpk_decode_desc& d = desc[i];
-                if (!dec_big_candidate(d, archive_size, c->dec_split_min)) continue;      // (an entry that earns a verdict from a guard gets it from the usual path)
+                if (!dec_big_candidate(d, archive_size, c->opt.dec_split_min)) continue;      // (an entry that earns a verdict from a guard gets it from the usual path)
                 const size_t s0 = subs.size();
                 bool ok = false;
                 if (d.method == ZPK_METHOD_NONE) {
@@ -2046,7 +2022,6 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
-    c->zstd_hint = -1; c->lz4_hint = -1;
     return rc;
 }
 
@@ -2092,38 +2067,38 @@ struct StoredSpanRun {
 static int stored_span_enqueue(zpk_codec* c, const u8* d_archive, u64 archive_size, const zpk_decode_desc* desc, u64 n, u8* d_dst, u64 dst_size,
                                bool fork, StoredSpanRun& run)
 {
-    if (c->stored_span_min == ~0ull) return ZPK_OK;
+    if (c->opt.stored_span_min == ~0ull) return ZPK_OK;
     u64 k = 0;
-    for (u64 i = 0; i < n; i++) k += stored_span_takes(desc[i], archive_size, dst_size, c->stored_span_min) ? 1 : 0;
+    for (u64 i = 0; i < n; i++) k += stored_span_takes(desc[i], archive_size, dst_size, c->opt.stored_span_min) ? 1 : 0;
     if (k == 0) return ZPK_OK;
-    const hipStream_t st = fork && fork_stream(c->span, c->stream, false) ? c->span.s : c->stream;
+    const hipStream_t st = fork && fork_stream(c->sspan.side, c->stream, false) ? c->sspan.side.s : c->stream;
     const u64 dst_at = (k * sizeof(StoredSpanRow) + 255) & ~255ull, up_bytes = dst_at + ((k * 8 + 255) & ~255ull), h_total = up_bytes + k * 8;
-    if (!grow_pinned(c->h_sspan, h_total)) return ZPK_OK;                            // no pinned memory for the table: one wave per entry
-    u8* const h_sspan = c->h_sspan.p;
+    if (!c->sspan.h.grow(h_total)) return ZPK_OK;                            // no pinned memory for the table: one wave per entry
+    u8* const h_sspan = c->sspan.h.p;
     StoredSpanRow* const rows = (StoredSpanRow*)h_sspan;
     u64* const dst_off = (u64*)(h_sspan + dst_at);
     StoredPlan plan = { 0, 0, 0 };
     run.idx.reserve(k);
     for (u64 i = 0; i < n; i++)
-        if (stored_span_takes(desc[i], archive_size, dst_size, c->stored_span_min)) {
+        if (stored_span_takes(desc[i], archive_size, dst_size, c->opt.stored_span_min)) {
             if (!stored_span_emit(desc[i], rows, dst_off, plan)) break;              // the launch is full: the rest stays one wave per entry
             run.idx.push_back(i);
         }
     if (plan.nspans == 0) return ZPK_OK;
     const u64 part_at = up_bytes, hash_at = part_at + plan.part_blocks * 64;
-    if (grow(c, c->d_sspan, hash_at + plan.nspans * 8 + 64)) { c->err[0] = 0; run.idx.clear(); return ZPK_OK; }
-    const zpk_span* const d_spans = (const zpk_span*)(u8*)c->d_sspan;
-    u64* const d_part = (u64*)(c->d_sspan + part_at);
-    u64* const d_hash = (u64*)(c->d_sspan + hash_at);
+    if (grow(c, c->sspan.d, hash_at + plan.nspans * 8 + 64)) { c->err[0] = 0; run.idx.clear(); return ZPK_OK; }
+    const zpk_span* const d_spans = (const zpk_span*)(u8*)c->sspan.d;
+    u64* const d_part = (u64*)(c->sspan.d + part_at);
+    u64* const d_hash = (u64*)(c->sspan.d + hash_at);
     run.h_hash = (const u64*)(h_sspan + up_bytes);
     run.st = st;
-    HIPCHK(c, hipMemcpyAsync(c->d_sspan, h_sspan, up_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->sspan.d, h_sspan, up_bytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_stored_span, dim3((u32)((plan.groups + 3) / 4)), dim3(256), 0, st, d_archive, d_dst, d_spans,
-                       (const u64*)(c->d_sspan + dst_at), (u32)plan.nspans, plan.groups, d_part);
+                       (const u64*)(c->sspan.d + dst_at), (u32)plan.nspans, plan.groups, d_part);
     hipLaunchKernelGGL(k_xxh3_chain, dim3((u32)plan.nspans), dim3(64), 0, st, d_archive, d_spans, (const u64*)d_part, d_hash, (u64*)nullptr, (u64)0, ~(u64)0, 1);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_sspan + up_bytes, d_hash, plan.nspans * 8, hipMemcpyDeviceToHost, st));
-    c->span_last[0] += (u32)plan.nspans; c->span_last[1] += (u32)(plan.groups > 0xFFFFFFFFull ? 0xFFFFFFFFull : plan.groups);      // (+=: as walk_last)
+    c->last.span[0] += (u32)plan.nspans; c->last.span[1] += (u32)(plan.groups > 0xFFFFFFFFull ? 0xFFFFFFFFull : plan.groups);      // (+=: as last.walk)
     return ZPK_OK;
 }
 // ... the join: their stream has drained -> their hashes are in the pinned block, their results are composed
@@ -2145,7 +2120,7 @@ static int decode_rest_device(zpk_codec* c, const u8* d_archive, u64 archive_siz
                               u8* d_dst, u64 dst_size, zpk_decode_result* results)
 {
     if (nr == 0) {
-        if (c->span_last[0]) { (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->totals_valid = 0; }
+        if (c->last.span[0]) { (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->last.totals_valid = 0; }
         return ZPK_OK;
     }
     std::vector<zpk_decode_desc> rd(nr);
@@ -2154,8 +2129,7 @@ static int decode_rest_device(zpk_codec* c, const u8* d_archive, u64 archive_siz
     int rc;
     if ((rc = grow(c, c->d_desc, nr * sizeof(zpk_decode_desc))) || (rc = grow(c, c->d_res, nr * sizeof(zpk_decode_result)))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_desc, rd.data(), nr * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream));
-    c->zstd_hint = -1; c->lz4_hint = -1;
-    if ((rc = decode_launch(c, d_archive, archive_size, d_archive, d_archive + archive_size, (const zpk_decode_desc*)c->d_desc, nr,
+    if ((rc = decode_launch(c, BatchMethods{ -1, -1 }, d_archive, archive_size, d_archive, d_archive + archive_size, (const zpk_decode_desc*)c->d_desc, nr,
                             d_dst, dst_size, (zpk_decode_result*)c->d_res, c->stream))) return rc;
     HIPCHK(c, hipMemcpyAsync(rr.data(), c->d_res, nr * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2181,12 +2155,12 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
     int rc = ZPK_OK;
     bool done = false;                                                                // a chip-wide path has finished the entry
     try {
-        if (d_dst && stored_span_takes(d, archive_size, dst_size, c->stored_span_min)) {   // a large stored entry: copied and hashed chip-wide (serial form)
+        if (d_dst && stored_span_takes(d, archive_size, dst_size, c->opt.stored_span_min)) {   // a large stored entry: copied and hashed chip-wide (serial form)
             StoredSpanRun run;
             if ((rc = stored_span_enqueue(c, d_archive, archive_size, &d, 1, d_dst, dst_size, false, run)) || (rc = stored_span_finish(c, run, &d, result))) return rc;
             done = !run.idx.empty();
-        } else if (d_dst && dec_big_candidate_device(d, archive_size, dst_size, c->dec_split_min) && grow_pinned(c->h_bigsrc, d.comp_size)) {
-            u8* const h_src = c->h_bigsrc.p;                                          // (no pinned memory for the entry's bytes: one wave)
+        } else if (d_dst && dec_big_candidate_device(d, archive_size, dst_size, c->opt.dec_split_min) && c->walk.h_bigsrc.grow(d.comp_size)) {
+            u8* const h_src = c->walk.h_bigsrc.p;                                          // (no pinned memory for the entry's bytes: one wave)
             hipError_t e = hipMemcpyAsync(h_src, d_archive + d.src_offset, d.comp_size, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large entry: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
@@ -2198,7 +2172,7 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
                 if (!redo) { *result = r; done = true; }
             }
         }
-    } catch (...) { c->span_last[0] = c->span_last[1] = 0; }                          // out of host memory for a table: one wave
+    } catch (...) { c->last.span[0] = c->last.span[1] = 0; }                          // out of host memory for a table: one wave
     const u64 self = 0;
     try { rc = decode_rest_device(c, d_archive, archive_size, &d, &self, done ? 0 : 1, d_dst, dst_size, result); } catch (...) { rc = ZPK_E_NOMEM; }
     return rc;
@@ -2224,28 +2198,28 @@ static int decode_big_batch_body(zpk_codec* c, const uint8_t* d_archive, uint64_
         if ((rc = stored_span_enqueue(c, d_archive, archive_size, desc, n, d_dst, dst_size, ZPK_STORED_SPAN_FORK != 0, span))) return rc;
         // ---- the candidates, walked where they lie: one launch over all of them, one copy home (records + tables), one synchronisation ----
         std::vector<u64> cand;
-        for (u64 i = 0; i < n; i++) if (dec_big_candidate_device(desc[i], archive_size, dst_size, c->dec_split_min)) cand.push_back(i);
+        for (u64 i = 0; i < n; i++) if (dec_big_candidate_device(desc[i], archive_size, dst_size, c->opt.dec_split_min)) cand.push_back(i);
         const u64 nc = cand.size();
         std::vector<BigWalkItem> items;
         const BigWalkLayout L = dec_walk_layout(desc, cand.data(), nc, items);
         std::vector<PjEntry> pj;
-        bool walk = nc > 0 && grow_pinned(c->h_bigwalk, L.total);
-        if (walk && grow(c, c->d_bigwalk, L.total)) { c->err[0] = 0; walk = false; }  // no memory for the tables, pinned or on the device: one wave per entry
+        bool walk = nc > 0 && c->walk.h_bigwalk.grow(L.total);
+        if (walk && grow(c, c->walk.d_bigwalk, L.total)) { c->err[0] = 0; walk = false; }  // no memory for the tables, pinned or on the device: one wave per entry
         if (walk) {
-            u8* const h_walk = c->h_bigwalk.p;
+            u8* const h_walk = c->walk.h_bigwalk.p;
             memcpy(h_walk, items.data(), nc * sizeof(BigWalkItem));
-            HIPCHK(c, hipMemcpyAsync(c->d_bigwalk, h_walk, nc * sizeof(BigWalkItem), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_big_walk, dim3((u32)nc), dim3(64), 0, c->stream, d_archive, (const BigWalkItem*)(u8*)c->d_bigwalk, (u32)nc,
-                               (u8*)c->d_bigwalk, (BigWalkRec*)(c->d_bigwalk + L.rec_off));
+            HIPCHK(c, hipMemcpyAsync(c->walk.d_bigwalk, h_walk, nc * sizeof(BigWalkItem), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_big_walk, dim3((u32)nc), dim3(64), 0, c->stream, d_archive, (const BigWalkItem*)(u8*)c->walk.d_bigwalk, (u32)nc,
+                               (u8*)c->walk.d_bigwalk, (BigWalkRec*)(c->walk.d_bigwalk + L.rec_off));
             HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(h_walk + L.rec_off, c->d_bigwalk + L.rec_off, L.total - L.rec_off, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h_walk + L.rec_off, c->walk.d_bigwalk + L.rec_off, L.total - L.rec_off, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             const BigWalkRec* const recs = (const BigWalkRec*)(h_walk + L.rec_off);
-            c->walk_last[0] += (u32)nc;                                                // (+=: begin_decode_call zeroed it; the sub-batches of zpk_codec_decode_batch_dimage add up)
+            c->last.walk[0] += (u32)nc;                                                // (+=: begin_decode_call zeroed it; the sub-batches of zpk_codec_decode_batch_dimage add up)
             for (u64 k = 0; k < nc; k++) {
                 const BigWalkRec& r = recs[k];
                 if (r.accepted != 1 || r.nblocks == 0 || r.nblocks > items[k].cap) continue;
-                c->walk_last[1]++;
+                c->last.walk[1]++;
                 PjEntry P; P.idx = cand[k]; P.independent = (int)(r.independent & 1); P.slots = r.slots; P.lit_total = r.lit_total;
                 if (items[k].method == ZPK_METHOD_LZ4) { const PjBlock* t = (const PjBlock*)(h_walk + items[k].tab_off); P.blocks.assign(t, t + r.nblocks); }
                 else { const ZpjBlock* t = (const ZpjBlock*)(h_walk + items[k].tab_off); P.zblocks.assign(t, t + r.nblocks); }
@@ -2295,14 +2269,14 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
     if (!c || (n && (!desc || !results || !dst_ptrs || !d_archive))) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->dimage_last[0] = c->dimage_last[1] = c->dimage_last[2] = 0;
+    c->last.dimage[0] = c->last.dimage[1] = c->last.dimage[2] = 0;
     if (n == 0) return ZPK_OK;
     const bool ddst = dst_on_device != 0;
     PtrRule rule(c);                                                                  // the pointer rule: before anything is enqueued
     if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
     if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
     begin_decode_call(c);
-    const u64 chunk = dimage_chunk(c->dimage_chunk);
+    const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
     auto slot = [&](u64 i) { return dimage_slot(desc[i].method == ZPK_METHOD_NONE, desc[i].uncomp_size, desc[i].dst_capacity); };
     int rc = ZPK_OK;
     u64 home_total = 0;
@@ -2312,26 +2286,19 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
         for (u64 first = 0; first < n && rc == ZPK_OK; ) {
             const DimageCut cut = dimage_cut(first, n, chunk, slot, at.data() + first);
             hd.resize(cut.count);
-            for (u64 k = 0; k < cut.count; k++) {
-                const zpk_decode_desc& d = desc[first + k];
-                hd[k] = d;
-                hd[k].dst_offset = at[first + k];
-                // (as in the host path: the device judges `max_size < uncomp_size` on the caller's capacity, a stored entry that passes
-                // it writes uncomp_size bytes and its slot is that long)
-                if (d.method == ZPK_METHOD_NONE && d.dst_capacity >= d.uncomp_size) hd[k].dst_capacity = span_copy_read_slot_bytes(true, d.uncomp_size, d.dst_capacity);
-            }
+            for (u64 k = 0; k < cut.count; k++) hd[k] = span_copy_staged_desc(desc[first + k], desc[first + k].method == ZPK_METHOD_NONE, at[first + k]);      // (as in the host path)
             if (cut.out_total > ~0ull - 16) { snprintf(c->err, sizeof(c->err), "a staging slot of %llu bytes", (unsigned long long)cut.out_total); rc = ZPK_E_NOMEM; break; }
             if ((rc = grow(c, c->d_dst, cut.out_total + 16))) break;
             if ((rc = decode_big_batch_body(c, d_archive, archive_size, hd.data(), cut.count, c->d_dst, cut.out_total, results + first))) break;
             u64 home = 0;
             if ((rc = deliver_slots(c, hd.data(), desc + first, cut.count, cut.out_total, dst_ptrs + first, results + first, ddst, &home))) break;
             home_total = home > ~0ull - home_total ? ~0ull : home_total + home;
-            c->dimage_last[0]++;
+            c->last.dimage[0]++;
             first += cut.count;
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
-    c->dimage_last[1] = c->sc_last;
-    c->dimage_last[2] = home_total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)home_total;
+    c->last.dimage[1] = c->last.sc;
+    c->last.dimage[2] = home_total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)home_total;
     return rc;
 }
 
@@ -2339,7 +2306,7 @@ int zpk_codec_dimage_stats(zpk_codec* c, uint32_t out[4])
 {
     if (!c || !out) return ZPK_E_INVALID;
     CodecLock lk(c);
-    out[0] = c->dimage_last[0]; out[1] = c->dimage_last[1]; out[2] = c->dimage_last[2]; out[3] = 0;
+    out[0] = c->last.dimage[0]; out[1] = c->last.dimage[1]; out[2] = c->last.dimage[2]; out[3] = 0;
     return ZPK_OK;
 }
 
@@ -2391,10 +2358,10 @@ int zpk_codec_decode_stats(zpk_codec* c, uint32_t out[8])
     HIPCHK(c, hipDeviceSynchronize());
     u32 h[N_COUNTERS];
     HIPCHK(c, hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
-    if (c->totals_valid) memcpy(h, c->host_totals, sizeof(h));          // a pipelined host batch: the sum over its launches
+    if (c->last.totals_valid) memcpy(h, c->last.host_totals, sizeof(h));          // a pipelined host batch: the sum over its launches
     out[0] = h[C_NONE]; out[1] = h[C_ZSTD]; out[2] = h[C_LZ4] + h[C_LZ4_RUNS] + h[C_LZ4_GEN] /* the three LZ4 lists */; out[3] = h[C_ZSTD_TWO_STAGE]; out[4] = h[C_ZSTD_FUSED];
     out[5] = h[C_FSE_WATCHDOG]; out[6] = h[C_FSE_BUDGET]; out[7] = h[C_FSE_MARKED];
-    if (c->fell_back_fused) out[7] |= 0x80000000u;          // the batch could not get its sequence arena: fused decoder only
+    if (c->last.fell_back_fused) out[7] |= 0x80000000u;          // the batch could not get its sequence arena: fused decoder only
     ZPK_DEV(if (getenv("ZPK_TRACE")) fprintf(stderr, "[zpk] fse marked %u, pass-0 failures %u, last failure status/rc %08x\n", h[C_FSE_MARKED], h[C_EXEC_FAILED], h[C_EXEC_LAST_RC]);)
     return ZPK_OK;
 }
@@ -2409,17 +2376,17 @@ int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16])
     HIPCHK(c, hipDeviceSynchronize());
     u32 h[N_COUNTERS];
     HIPCHK(c, hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
-    if (c->totals_valid) memcpy(h, c->host_totals, sizeof(h));
-    memset(out, 0, 16 * sizeof(uint32_t));
-    out[0] = h[C_RETRY_LZ4]; out[1] = h[C_RETRY_ZSTD];
-    out[2] = 0; out[3] = h[C_LZ4_RUNS]; out[4] = 0;      // [3]: LZ4 entries that are mostly runs, decoded by k_lz4_left (the two-stage path of round 4 is gone: [2], [4] read 0)
-    out[5] = c->big_last[0]; out[6] = c->big_last[1];
-    out[7] = c->zpj_last_err;                              // why the most recent large Zstandard frame was NOT finished block-parallel (0: it was, or none came)
-    out[8] = h[C_LZ4_HANDED];                              // LZ4 entries k_lz4_wave handed to the general decoder without judging them
-    out[9] = h[C_LZ4_GEN];                                 // LZ4 entries whose header is not that of a plain frame: k_lz4_general's
-    out[10] = c->walk_last[0]; out[11] = c->walk_last[1];  // zpk_codec_decode_big_batch_device: entries walked on the device (k_big_walk), those the walk accepted
-    out[12] = c->span_last[0]; out[13] = c->span_last[1];  // ... and zpk_codec_decode_big_device: stored entries copied chip-wide (k_stored_span), their groups
-    out[14] = c->pipe_last; out[15] = c->sc_last;          // zpk_codec_decode_batch_host / _dptr: sub-batches through the three-stage pipeline; k_span_copy launches (_dptr)
+    if (c->last.totals_valid) memcpy(h, c->last.host_totals, sizeof(h));
+    memset(out, 0, ZPK_DS2_COUNT * sizeof(uint32_t));                                  // (ZPK_DS2_RESERVED2, _RESERVED4: the two-stage path of round 4 is gone, they read 0)
+    out[ZPK_DS2_RETRY_LZ4] = h[C_RETRY_LZ4]; out[ZPK_DS2_RETRY_ZSTD] = h[C_RETRY_ZSTD];
+    out[ZPK_DS2_LZ4_RUNS] = h[C_LZ4_RUNS];                                             // LZ4 entries that are mostly runs, decoded by k_lz4_left
+    out[ZPK_DS2_BIG_ENTRIES] = c->last.big[0]; out[ZPK_DS2_BIG_FRAMES] = c->last.big[1];
+    out[ZPK_DS2_ZPJ_ERR] = c->last.zpj_err;                                            // why the most recent large Zstandard frame was NOT finished block-parallel (0: it was, or none came)
+    out[ZPK_DS2_LZ4_HANDED] = h[C_LZ4_HANDED];                                         // LZ4 entries k_lz4_wave handed to the general decoder without judging them
+    out[ZPK_DS2_LZ4_GEN] = h[C_LZ4_GEN];                                               // LZ4 entries whose header is not that of a plain frame: k_lz4_general's
+    out[ZPK_DS2_WALKED] = c->last.walk[0]; out[ZPK_DS2_WALK_ACCEPTED] = c->last.walk[1];     // zpk_codec_decode_big_batch_device: entries walked on the device (k_big_walk), those the walk accepted
+    out[ZPK_DS2_SPAN_ENTRIES] = c->last.span[0]; out[ZPK_DS2_SPAN_GROUPS] = c->last.span[1]; // ... and zpk_codec_decode_big_device: stored entries copied chip-wide (k_stored_span), their groups
+    out[ZPK_DS2_PIPE_SUBS] = c->last.pipe; out[ZPK_DS2_SPAN_COPIES] = c->last.sc;      // zpk_codec_decode_batch_host / _dptr: sub-batches through the three-stage pipeline; k_span_copy launches (_dptr)
     return ZPK_OK;
 }
 
@@ -2428,8 +2395,8 @@ int zpk_codec_decode_stats2(zpk_codec* c, uint32_t out[16])
 int zpk_codec_debug_fetch(zpk_codec* c, int what, uint64_t offset, void* host, uint64_t bytes)
 {
     if (!c || !host) return ZPK_E_INVALID;
-    const u8* base = what == 0 ? (const u8*)c->d_zarena : (const u8*)c->d_zstate;
-    const u64 cap = what == 0 ? c->d_zarena.cap : c->d_zstate.cap;
+    const u8* base = what == 0 ? (const u8*)c->wave.d_zarena : (const u8*)c->wave.d_zstate;
+    const u64 cap = what == 0 ? c->wave.d_zarena.cap : c->wave.d_zstate.cap;
     if (!base || offset > cap || bytes > cap - offset) return ZPK_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
@@ -2441,12 +2408,12 @@ int zpk_codec_set_option(zpk_codec* c, int option, int value)
 {
     if (!c) return ZPK_E_INVALID;
     CodecLock lk(c);
-    if (option == ZPK_OPT_ORDER_FAST_LAST) { c->order_fast_last = value ? 1 : 0; return ZPK_OK; }
-    if (option == ZPK_OPT_ORDER_MIN) { if (value < 0) return ZPK_E_INVALID; c->order_min = c->enc_order_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
-    if (option == ZPK_OPT_DEC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->dec_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
-    if (option == ZPK_OPT_ENC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->enc_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
-    if (option == ZPK_OPT_STORED_SPAN_MIN) { if (value < 0) return ZPK_E_INVALID; c->stored_span_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
-    if (option == ZPK_OPT_DIMAGE_CHUNK) { if (value < 0) return ZPK_E_INVALID; c->dimage_chunk = (u64)value; return ZPK_OK; }       // (0 = the default: dimage_chunk())
+    if (option == ZPK_OPT_ORDER_FAST_LAST) { c->opt.order_fast_last = value ? 1 : 0; return ZPK_OK; }
+    if (option == ZPK_OPT_ORDER_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.order_min = c->opt.enc_order_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
+    if (option == ZPK_OPT_DEC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.dec_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
+    if (option == ZPK_OPT_ENC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.enc_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
+    if (option == ZPK_OPT_STORED_SPAN_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.stored_span_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
+    if (option == ZPK_OPT_DIMAGE_CHUNK) { if (value < 0) return ZPK_E_INVALID; c->opt.dimage_chunk = (u64)value; return ZPK_OK; }       // (0 = the default: dimage_chunk())
     return ZPK_E_INVALID;
 }
 
@@ -2456,7 +2423,7 @@ int zpk_codec_set_profiling(zpk_codec* c, int enabled)
     HIPCHK(c, hipSetDevice(c->device));
     if (enabled)
         for (int i = 0; i < ZPK_K_COUNT; i++) for (int j = 0; j < 2; j++)
-            if (!c->kev[i][j]) HIPCHK(c, hipEventCreate(&c->kev[i][j]));
+            if (const hipError_t e = c->kev[i][j].ready(hipEventDefault)) { snprintf(c->err, sizeof(c->err), "profiling: no event: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     c->profiling = enabled ? 1 : 0;
     return ZPK_OK;
 }

@@ -11,12 +11,12 @@ void sink_commit_launch(const u8* d_slots, const u64* d_slot_off, const zpk_enco
 // workgroups of four waves the chip holds at once at k_sink_place's occupancy of 8 waves per SIMD
 static u32 sink_resident_groups(zpk_codec* c)
 {
-    if (!c->sink_groups) {
+    if (!c->sink.groups) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-        c->sink_groups = (u32)cus * 8u;
+        c->sink.groups = (u32)cus * 8u;
     }
-    return c->sink_groups;
+    return c->sink.groups;
 }
 
 // One sub-batch: desc[0, m) staged, encoded into slots of the codec's, scanned, cut against `room` and committed to d_sink; results[0, m)
@@ -42,19 +42,19 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
     const u64 o_rec = res_bytes, o_off = o_rec + SINK_REC_WORDS * sizeof(u64), o_slot = o_off + (m + 1) * sizeof(u64);
     const u64 nblocks = (m + PK_BLOCK - 1) / PK_BLOCK;
     int rc;
-    if ((rc = grow(c, c->d_src, in_total + 64)) || (rc = grow(c, c->d_sink_slots, out_total + 64)) ||
-        (rc = grow(c, c->d_sink_tab, o_slot + m * sizeof(u64)))) return rc;
+    if ((rc = grow(c, c->d_src, in_total + 64)) || (rc = grow(c, c->sink.d_slots, out_total + 64)) ||
+        (rc = grow(c, c->sink.d_tab, o_slot + m * sizeof(u64)))) return rc;
     hipStream_t st = c->stream;
     hipError_t e = hipSuccess;
     // the sources, as zpk_codec_encode_batch_host / _dsrc stage them (zpk_codec.hip, stage_sources)
     if ((rc = stage_sources(c, src_ptrs, dsrc, m, [&](u64 i) { return (u64)hd[i].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, in_total, st, e))) return rc;
-    u8* const tab = c->d_sink_tab;
+    u8* const tab = c->sink.d_tab;
     zpk_encode_result* const d_res = (zpk_encode_result*)tab;
     u64* const d_rec = (u64*)(tab + o_rec); u64* const d_off = (u64*)(tab + o_off); u64* const d_slot = (u64*)(tab + o_slot);
     if (e == hipSuccess) e = hipMemcpyAsync(d_slot, slot_off.data(), m * sizeof(u64), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     // the frames, into the slots: large entries in pieces with their frame assembled on the device, every other entry by the one-wave launch
-    if ((rc = zpk_codec_encode_big_device(c, c->d_src, in_total, hd.data(), m, c->d_sink_slots, out_total, d_res, st))) return rc;
+    if ((rc = zpk_codec_encode_big_device(c, c->d_src, in_total, hd.data(), m, c->sink.d_slots, out_total, d_res, st))) return rc;
     // where they go: the sizes-only scan, and the same scan over the entries' spans (pack_launch's layout of c->d_pack, which it has grown)
     if ((rc = pack_launch(c, nullptr, nullptr, d_res, m, nullptr, 0, d_off, 0, st))) return rc;
     u64* const span_blocks = (u64*)c->d_pack + nblocks;
@@ -65,7 +65,7 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
     HIPCHK(c, hipGetLastError());
     // the commit
     const u32 grid = sink_grid(items_bound, sink_resident_groups(c));
-    sink_commit_launch(c->d_sink_slots, d_slot, d_res, d_off, span_first, (u32)m, room, d_rec, d_sink, grid,
+    sink_commit_launch(c->sink.d_slots, d_slot, d_res, d_off, span_first, (u32)m, room, d_rec, d_sink, grid,
                        c->profiling ? c->kev[ZPK_K_PACK][0] : nullptr, c->profiling ? c->kev[ZPK_K_PACK][1] : nullptr, st);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(home.data(), tab, home_bytes, hipMemcpyDeviceToHost, st));          // [results | cut record], one copy
@@ -75,7 +75,7 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
     memcpy(rec, home.data() + res_bytes, sizeof(rec));
     cut->placed = rec[0]; cut->bytes = rec[1];
     if (cut->placed > m || cut->bytes > room) { snprintf(c->err, sizeof(c->err), "sink commit: a cut of %llu entries, %llu bytes", (unsigned long long)rec[0], (unsigned long long)rec[1]); return ZPK_E_LAUNCH; }
-    c->dsink_last[0]++; c->dsink_last[1] = grid;
+    c->last.dsink[0]++; c->last.dsink[1] = grid;
     return ZPK_OK;
 }
 
@@ -87,7 +87,7 @@ int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, i
     if (!c || !placed || !bytes || (n && (!desc || !results || !src_ptrs))) return ZPK_E_INVALID;
     *placed = 0; *bytes = 0;
     CodecLock lk(c);
-    c->dsink_last[0] = c->dsink_last[1] = 0;
+    c->last.dsink[0] = c->last.dsink[1] = 0;
     if (n == 0) return ZPK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued.  The sink and device sources lie inside one allocation each on
@@ -100,7 +100,7 @@ int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, i
             snprintf(c->err, sizeof(c->err), "source %llu is not %llu bytes of host memory (the codec of device %d reads it on the host)", (unsigned long long)i, (unsigned long long)desc[i].size, c->device);
             return ZPK_E_INVALID;
         }
-    const u64 chunk = dimage_chunk(c->dimage_chunk);
+    const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
     SinkChain ch = { 0, 0, true };
     for (u64 first = 0; first < n && ch.open; ) {
         const DimageCut sub = dimage_cut(first, n, chunk, [&](u64 i) { return sink_slot(desc[i].dst_capacity); });
@@ -128,7 +128,7 @@ int zpk_codec_dsink_stats(zpk_codec* c, uint32_t out[4])
 {
     if (!c || !out) return ZPK_E_INVALID;
     CodecLock lk(c);
-    out[0] = c->dsink_last[0]; out[1] = c->dsink_last[1]; out[2] = out[3] = 0;
+    out[0] = c->last.dsink[0]; out[1] = c->last.dsink[1]; out[2] = out[3] = 0;
     return ZPK_OK;
 }
 

@@ -1554,11 +1554,11 @@ static int encode_launch(zpk_codec* c, const uint8_t* src, const zpk_encode_desc
     if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_ENCODE][0], st);
     HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), st));   // the two kernels' dequeue heads, the order histogram
     const u32* order = nullptr;
-    if (n >= c->enc_order_min) {
-        if ((rc = grow(c, c->d_lists, (u64)N_LIST_SLOTS * n * sizeof(u32)))) return rc;     // (sized like the decode lists)
+    if (n >= c->opt.enc_order_min) {
+        if ((rc = grow(c, c->wave.d_lists, (u64)N_LIST_SLOTS * n * sizeof(u32)))) return rc;     // (sized like the decode lists)
         hipLaunchKernelGGL(k_enc_order_count, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, desc, n, c->d_counters);
-        hipLaunchKernelGGL(k_enc_order_fill, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, desc, n, c->d_lists, c->d_counters);
-        order = c->d_lists;
+        hipLaunchKernelGGL(k_enc_order_fill, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, desc, n, c->wave.d_lists, c->d_counters);
+        order = c->wave.d_lists;
     }
     hipLaunchKernelGGL(k_encode<LZ4E_HASH_LOG>, dim3(grid), dim3(64), 0, st, src, desc, n, dst, results, c->d_seq, c->d_counters, order);
     hipLaunchKernelGGL(k_encode<LZ4E_HASH_LOG_MID>, dim3(grid), dim3(64), 0, st, src, desc, n, dst, results, c->d_seq, c->d_counters, order);
@@ -1586,7 +1586,7 @@ int zpk_codec_encode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
 // each other they slow each other down by more than the overlap gains.  Removed; the stages run one after the other.)
 
 extern "C" {
-// Entries of at least c->enc_split_min bytes go to the device as 512 KiB pieces, one wave each, and come back as ONE frame (enc_plan.h: which
+// Entries of at least c->opt.enc_split_min bytes go to the device as 512 KiB pieces, one wave each, and come back as ONE frame (enc_plan.h: which
 // entries, their pieces, the frame's header and end, the entry's verdict); the packed stream keeps the pieces in order.  The entry's hash
 // is that of the whole plaintext (the two kernels of xxh3_span.h).
 // (dsrc: zpk_codec_encode_batch_dsrc — src_ptrs are DEVICE pointers, gathered into the same staging by one launch of k_span_copy)
@@ -1599,7 +1599,7 @@ static int encode_batch_host_any(zpk_codec* c, const uint8_t* const* src_ptrs, c
     HIPCHK(c, hipSetDevice(c->device));
     // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued
     if (dsrc && PtrRule(c).batch("source", n, [&](u64 i) { return src_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].size; })) return ZPK_E_INVALID;
-    const u64 split_min = c->enc_split_min;
+    const u64 split_min = c->opt.enc_split_min;
     u64 np = 0, nsplit = 0;
     for (u64 i = 0; i < n; i++) { np += enc_piece_count(split_min, desc[i]); nsplit += enc_is_split(split_min, desc[i]); }
     if (np > 0x7FFFFFFFull) return ZPK_E_INVALID;
@@ -1764,14 +1764,15 @@ __global__ __launch_bounds__(64) void k_big_close(const zpk_encode_result* __res
 }
 
 // a pinned block of `need` bytes for one call's tables: the two blocks take turns, and a block is handed out again only when the upload
-// that read it last has run (the caller records c->bigenc_ev[*slot] behind its uploads)
+// that read it last has run (the caller records c->bigenc.ev[*slot] behind its uploads)
 static int big_tables_block(zpk_codec* c, u64 need, u8** out, int* slot)
 {
-    const int k = (int)(c->bigenc_turn++ & 1u);
-    if (!c->bigenc_ev[k]) HIPCHK(c, hipEventCreateWithFlags(&c->bigenc_ev[k], hipEventDisableTiming));
-    else HIPCHK(c, hipEventSynchronize(c->bigenc_ev[k]));
-    if (!grow_pinned(c->h_bigenc[k], need)) { snprintf(c->err, sizeof(c->err), "pinned tables: out of memory"); return ZPK_E_NOMEM; }
-    *out = c->h_bigenc[k].p; *slot = k;
+    const int k = (int)(c->bigenc.turn++ & 1u);
+    if (!c->bigenc.ev[k]) {
+        if (const hipError_t e = c->bigenc.ev[k].ready(hipEventDisableTiming)) { snprintf(c->err, sizeof(c->err), "big encode: no event: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
+    } else HIPCHK(c, hipEventSynchronize(c->bigenc.ev[k]));
+    if (!c->bigenc.h[k].grow(need)) { snprintf(c->err, sizeof(c->err), "pinned tables: out of memory"); return ZPK_E_NOMEM; }
+    *out = c->bigenc.h[k].p; *slot = k;
     return ZPK_OK;
 }
 
@@ -1782,12 +1783,12 @@ int zpk_codec_encode_big_device(zpk_codec* c, const uint8_t* d_src, uint64_t src
 {
     if (!c || (n && (!desc || !d_results))) return ZPK_E_INVALID;
     CodecLock lk(c);
-    c->enc_big_last[0] = c->enc_big_last[1] = 0;
+    c->last.enc_big[0] = c->last.enc_big[1] = 0;
     if (n == 0) return ZPK_OK;
     if (n > 0x7FFFFFFFull) return ZPK_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const u64 split_min = c->enc_split_min;
+    const u64 split_min = c->opt.enc_split_min;
     u64 np = 0, ns = 0;
     for (u64 i = 0; i < n; i++) {
         if (desc[i].src_offset > src_size || desc[i].size > src_size - desc[i].src_offset ||
@@ -1827,7 +1828,7 @@ int zpk_codec_encode_big_device(zpk_codec* c, const uint8_t* d_src, uint64_t src
     HIPCHK(c, hipMemcpyAsync(dt, h, up_bytes, hipMemcpyHostToDevice, st));
     u64* d_hash = nullptr;
     rc = xxh3_spans_enqueue(c, d_src, spans, ns, part_blocks, &d_hash, st);           // the hashes of the entries in pieces: by the whole chip, over the plaintext where it lies
-    HIPCHK(c, hipEventRecord(c->bigenc_ev[slot], st));                                 // (behind the last upload out of the block, whatever rc says)
+    HIPCHK(c, hipEventRecord(c->bigenc.ev[slot], st));                                 // (behind the last upload out of the block, whatever rc says)
     if (rc) return rc;
     if (ns < n && (rc = encode_launch(c, d_src, (const zpk_encode_desc*)dt, n, d_dst, d_results, st))) return rc;      // the others: as zpk_codec_encode_batch_device does them
     if (ns == 0) return ZPK_OK;
@@ -1842,7 +1843,7 @@ int zpk_codec_encode_big_device(zpk_codec* c, const uint8_t* d_src, uint64_t src
     if (c->profiling) (void)hipEventRecord(c->kev[ZPK_K_PACK][1], st);
     hipLaunchKernelGGL(k_big_close, dim3((u32)ns), dim3(64), 0, st, dr, (const u64*)doff, (const BigEncEntry*)(dt + o_big), (const u64*)d_hash, d_dst, d_results);
     HIPCHK(c, hipGetLastError());
-    c->enc_big_last[0] = (u32)ns; c->enc_big_last[1] = (u32)np;
+    c->last.enc_big[0] = (u32)ns; c->last.enc_big[1] = (u32)np;
     return ZPK_OK;
 }
 
@@ -1851,7 +1852,7 @@ int zpk_codec_encode_stats(zpk_codec* c, uint32_t out[8])
     if (!c || !out) return ZPK_E_INVALID;
     CodecLock lk(c);
     memset(out, 0, 8 * sizeof(uint32_t));
-    out[0] = c->enc_big_last[0]; out[1] = c->enc_big_last[1];
+    out[0] = c->last.enc_big[0]; out[1] = c->last.enc_big[1];
     return ZPK_OK;
 }
 

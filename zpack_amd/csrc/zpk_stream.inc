@@ -78,17 +78,17 @@ struct DsFastEntry {
 };
 struct DsFast : DsFastEntry {
     u8* pend; u64 pend_cap;                      // host: compressed bytes that are not decoded yet (from a block boundary on)
-    u8* d_f; u64 f_cap;                          // device: everything an LZ4 step needs (a fixed ~40 MiB, dstream_fast_layout); the scratch of a Zstandard step
-    u8* d_fo; u64 fo_cap;                        // device, Zstandard: [history | a step's output] + what persists between steps (XXH3 state)
-    u8* h_out;                                   // host, pinned: the output of the last step
+    DevBuf<u8> d_f;                              // device: everything an LZ4 step needs (a fixed ~40 MiB, dstream_fast_layout); the scratch of a Zstandard step
+    DevBuf<u8> d_fo;                             // device, Zstandard: [history | a step's output] + what persists between steps (XXH3 state)
+    PinBlock<u8> h_out;                          // host, pinned: the output of the last step
     u8* tree;                                    // host: the most recent block whose literals section carries a tree (Treeless blocks of later steps read it)
 };
 struct zpk_dstream {
     zpk_codec* c;                                // the codec of the CURRENT call (a stream outlives codecs: never touched by reset / destroy)
     int device;                                  // where the buffers below live
-    u8* d_in;  u64 in_len, in_cap;               // device: the compressed bytes so far
-    u8* d_out; u64 out_cap;                      // device: the output slot (uncomp_size)
-    u8* d_aux; u64 aux_cap;                      // device: zpk_stream_rec | ZstdResume | literal scratch
+    DevBuf<u8> d_in; u64 in_len;                 // device: the compressed bytes so far
+    DevBuf<u8> d_out;                            // device: the output slot (uncomp_size)
+    DevBuf<u8> d_aux;                            // device: zpk_stream_rec | ZstdResume | literal scratch
     u64 avail, out_pos;                          // output bytes that exist on the device / that the caller has
     int complete, status;                        // the frame is decoded and hashed; the verdict to give with the last byte
     // Small chunks are gathered on the host first (round 4): the reference's own test feeds 16-byte windows (tests/read_archive.c:38-82),
@@ -141,30 +141,27 @@ __global__ __launch_bounds__(64) void k_xxh3s_finish(zpk_cs_state* __restrict__ 
 struct zpk_cstream {
     zpk_codec* c;
     int device;
-    u8* d_in;  u64 in_len, in_cap;               // device: [carry][plaintext not yet compressed]
-    u8* d_out; u64 out_cap;                      // device: the frames not yet handed out, back to back
-    u8* d_slots; u64 slots_cap;                  // device: bound-sized output slots of one step
-    u8* d_aux; u64 aux_cap;                      // device: zpk_cs_state | descriptors | results | offsets
+    DevBuf<u8> d_in; u64 in_len;                 // device: [carry][plaintext not yet compressed]
+    DevBuf<u8> d_out;                            // device: the frames not yet handed out, back to back
+    DevBuf<u8> d_slots;                          // device: bound-sized output slots of one step
+    DevBuf<u8> d_aux;                            // device: zpk_cs_state | descriptors | results | offsets
     u64 out_len, out_pos;
     u64 total_in, total_out;                     // of the entry so far (total_out: compressed bytes produced)
     u32 method; i32 level; int configured, steps;
     int framed;                                  // the frame header of an entry that goes out in pieces has been written
 };
 
-static void dfree(u8** p, u64* cap) { if (*p) { (void)hipFree(*p); *p = nullptr; } *cap = 0; }
-
 // device buffer of at least `need` bytes that keeps its first `keep` bytes.  Sizes here derive from what the caller says about the
 // entry: nothing may wrap (a wrapped size would allocate a few bytes and hand the kernels a huge capacity).
-static int dgrow_keep(zpk_codec* c, u8** p, u64* cap, u64 need, u64 keep)
+static int dgrow_keep(zpk_codec* c, DevBuf<u8>& b, u64 need, u64 keep)
 {
-    if (need <= *cap) return ZPK_OK;
-    if (need > ZPK_STREAM_MAX_BYTES || keep > *cap) return ZPK_E_NOMEM;
-    u64 want = need + need / 2 + 4096;
-    u8* nb = nullptr;
-    if (hipMalloc((void**)&nb, want) != hipSuccess) { (void)hipGetLastError(); want = need + 256; if (hipMalloc((void**)&nb, want) != hipSuccess) { (void)hipGetLastError(); return ZPK_E_NOMEM; } }
-    if (*p && keep && hipMemcpyAsync(nb, *p, keep, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) { (void)hipFree(nb); return ZPK_E_LAUNCH; }
-    if (*p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(*p); }
-    *p = nb; *cap = want;
+    if (need <= b.cap) return ZPK_OK;
+    if (need > ZPK_STREAM_MAX_BYTES || keep > b.cap) return ZPK_E_NOMEM;
+    DevBuf<u8> nb;                                                                   // (the old block leaves with it, behind the copy)
+    if (!nb.alloc(need + need / 2 + 4096) && !nb.alloc(need + 256)) return ZPK_E_NOMEM;
+    if (b && keep && hipMemcpyAsync(nb, b, keep, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZPK_E_LAUNCH;
+    if (b) (void)hipStreamSynchronize(c->stream);
+    b.swap(nb);
     return ZPK_OK;
 }
 
@@ -173,7 +170,7 @@ extern "C" {
 int zpk_dstream_create(zpk_codec* c, zpk_dstream** out)
 {
     if (!c || !out) return ZPK_E_INVALID;
-    zpk_dstream* s = (zpk_dstream*)calloc(1, sizeof(zpk_dstream));
+    zpk_dstream* s = new (std::nothrow) zpk_dstream();                                // (no member has an initialiser: all zero, the buffers empty)
     if (!s) return ZPK_E_NOMEM;
     s->c = c; s->device = c->device; *out = s;
     return ZPK_OK;
@@ -187,11 +184,11 @@ static void dstream_release(zpk_dstream* s)
     if (s && s->f.tree) { free(s->f.tree); s->f.tree = nullptr; s->f.tree_len = 0; }
     if (!s || !(s->d_in || s->d_out || s->d_aux || s->f.d_f || s->f.h_out || s->f.d_fo)) return;
     if (hipSetDevice(s->device) != hipSuccess) return;
-    if (s->f.h_out) { (void)hipHostFree(s->f.h_out); s->f.h_out = nullptr; }
-    dfree(&s->f.d_f, &s->f.f_cap); dfree(&s->f.d_fo, &s->f.fo_cap);
+    s->f.h_out.release();
+    s->f.d_f.release(); s->f.d_fo.release();
     // (every step ends with a synchronisation of the stream it ran on, so nothing is in flight on these buffers: no device-wide wait —
     // hipFree itself orders the release behind outstanding work)
-    dfree(&s->d_in, &s->in_cap); dfree(&s->d_out, &s->out_cap); dfree(&s->d_aux, &s->aux_cap);
+    s->d_in.release(); s->d_out.release(); s->d_aux.release();
 }
 
 // The state of the entry being read, cleared in one place.  A replay (the entry's bytes once more through the windowless step, after
@@ -220,13 +217,13 @@ void zpk_dstream_reset(zpk_dstream* s)
     if (!s) return;
     dstream_clear(s, false);
     // a stream that has carried a large entry gives the device memory back between entries
-    if (s->in_cap + s->out_cap + s->f.f_cap + s->f.fo_cap > (64ull << 20)) dstream_release(s);
+    if (s->d_in.cap + s->d_out.cap + s->f.d_f.cap + s->f.d_fo.cap > (64ull << 20)) dstream_release(s);
 }
 
-void zpk_dstream_destroy(zpk_dstream* s) { if (s) { dstream_release(s); free(s); } }
+void zpk_dstream_destroy(zpk_dstream* s) { if (s) { dstream_release(s); delete s; } }
 
 // diagnostics: bytes of device memory the stream holds right now
-uint64_t zpk_dstream_device_bytes(const zpk_dstream* s) { return s ? s->in_cap + s->out_cap + s->aux_cap + s->f.f_cap + s->f.fo_cap : 0; }
+uint64_t zpk_dstream_device_bytes(const zpk_dstream* s) { return s ? s->d_in.cap + s->d_out.cap + s->d_aux.cap + s->f.d_f.cap + s->f.d_fo.cap : 0; }
 
 // diagnostics: decode steps launched / calls served since the last reset
 void zpk_dstream_counters(const zpk_dstream* s, uint64_t* launches, uint64_t* calls)
@@ -297,15 +294,13 @@ static void dstream_fast_header_done(zpk_dstream* s, int hdr)
 }
 
 // the device block `need` bytes large and the pinned output buffer: nothing of this entry lives there before its first step, which allocates
-static int dstream_fast_buffers(zpk_dstream* s, u8** dev, u64* cap, u64 need)
+static int dstream_fast_buffers(zpk_dstream* s, DevBuf<u8>& dev, u64 need)
 {
-    if (*cap < need) {
+    if (dev.cap < need) {
         if (s->f.T != 0) return ZPK_DS_RESTART;
-        dfree(dev, cap);
-        if (hipMalloc((void**)dev, need) != hipSuccess) { (void)hipGetLastError(); *dev = nullptr; return ZPK_DS_RESTART; }
-        *cap = need;
+        if (!dev.alloc(need)) return ZPK_DS_RESTART;
     }
-    if (!s->f.h_out && hipHostMalloc((void**)&s->f.h_out, F_HOST_OUT, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s->f.h_out = nullptr; return ZPK_DS_RESTART; }
+    if (!s->f.h_out.ready(F_HOST_OUT, hipHostMallocDefault)) { (void)hipGetLastError(); return ZPK_DS_RESTART; }
     return 0;
 }
 
@@ -422,7 +417,7 @@ static int dstream_fast_lz4(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, ui
     // ---- one step ----
     if (hipSetDevice(c->device) != hipSuccess) return 24;
     const FastLayout L = dstream_fast_layout();
-    if ((rc = dstream_fast_buffers(s, &s->f.d_f, &s->f.f_cap, L.size)) != 0) return rc;
+    if ((rc = dstream_fast_buffers(s, s->f.d_f, L.size)) != 0) return rc;
     u8* const d_f = s->f.d_f;
     u8* const d_in = d_f + L.in; u32* const S = (u32*)(d_f + L.S); PjBlock* const B = (PjBlock*)(d_f + L.blocks);
     FastStep F(c->stream);
@@ -522,12 +517,9 @@ static int dstream_fast_zstd(zpk_dstream* s, zpk_codec* c, uint64_t comp_size, u
     const u32 nt = tb + nb;                                     // table entries
     const u64 in_len = in_base + q, arena_off = (in_len + 64 + 255) & ~255ull, src_total = arena_off + lit_total;
     const FzLayout L = dstream_fz_layout(nt, slots, src_total, s->f.hist_cap);
-    if ((rc = dstream_fast_buffers(s, &s->f.d_fo, &s->f.fo_cap, L.fo_need)) != 0) return rc;
-    if (s->f.f_cap < L.size) {                                  // the scratch holds nothing between steps: any step may grow it
-        dfree(&s->f.d_f, &s->f.f_cap);
-        const u64 want_cap = fz_scratch_alloc(L.size);
-        if (hipMalloc((void**)&s->f.d_f, want_cap) != hipSuccess) { (void)hipGetLastError(); s->f.d_f = nullptr; return ZPK_DS_RESTART; }
-        s->f.f_cap = want_cap;
+    if ((rc = dstream_fast_buffers(s, s->f.d_fo, L.fo_need)) != 0) return rc;
+    if (s->f.d_f.cap < L.size) {                                  // the scratch holds nothing between steps: any step may grow it
+        if (!s->f.d_f.alloc(fz_scratch_alloc(L.size))) return ZPK_DS_RESTART;
     }
     u8* const d_f = s->f.d_f; u8* const d_fo = s->f.d_fo;
     u8* const d_in = d_f + L.in;
@@ -666,7 +658,7 @@ static int dstream_windowless_step(zpk_dstream* s, zpk_codec* c, uint32_t method
         const bool last_byte_here = s->in_len + s->h_len + take_all == comp_size;
         const u8* up = in; u64 up_len = take_all;                             // what goes to the device in this call
         if (s->h_len && take_all >= ZPK_DS_GATHER) {                          // a large chunk behind gathered bytes: those go up first
-            if (dgrow_keep(c, &s->d_in, &s->in_cap, s->in_len + s->h_len + take_all + 64, s->in_len) != ZPK_OK) return 10;
+            if (dgrow_keep(c, s->d_in, s->in_len + s->h_len + take_all + 64, s->in_len) != ZPK_OK) return 10;
             if (hipMemcpyAsync(s->d_in + s->in_len, s->h_in, s->h_len, hipMemcpyHostToDevice, c->stream) != hipSuccess) return 24;
             if (hipStreamSynchronize(c->stream) != hipSuccess) return 24;
             s->in_len += s->h_len; s->h_len = 0;
@@ -678,8 +670,8 @@ static int dstream_windowless_step(zpk_dstream* s, zpk_codec* c, uint32_t method
             up = s->h_in; up_len = s->h_len;
         }
         const u64 take = up_len;
-        if (dgrow_keep(c, &s->d_in, &s->in_cap, s->in_len + take + 64, s->in_len) != ZPK_OK) return 10;
-        if (dgrow_keep(c, &s->d_aux, &s->aux_cap, aux_need, 0) != ZPK_OK) return 10;
+        if (dgrow_keep(c, s->d_in, s->in_len + take + 64, s->in_len) != ZPK_OK) return 10;
+        if (dgrow_keep(c, s->d_aux, aux_need, 0) != ZPK_OK) return 10;
         zpk_stream_rec* rec = (zpk_stream_rec*)s->d_aux;
         ZstdResume* zr = (ZstdResume*)(s->d_aux + 256);
         u8* lit = s->d_aux + 256 + sizeof(ZstdResume);
@@ -702,14 +694,14 @@ static int dstream_windowless_step(zpk_dstream* s, zpk_codec* c, uint32_t method
             // The output slot grows with what the frame PRODUCES (first 8 MiB, then doubling, never beyond uncomp_size): a step that
             // runs out of room is run again from its resume record in the larger slot (both decoders resume in front of a block).
             for (;;) {
-                u64 cap_now = s->out_cap >= 64 ? s->out_cap - 64 : 0;
+                u64 cap_now = s->d_out.cap >= 64 ? s->d_out.cap - 64 : 0;
                 if (cap_now > uncomp_size) cap_now = uncomp_size;
                 if (cap_now == 0 && uncomp_size) {
                     const u64 first = uncomp_size < (8ull << 20) ? uncomp_size : (8ull << 20);
-                    if (dgrow_keep(c, &s->d_out, &s->out_cap, first + 64, 0) != ZPK_OK) return 10;
+                    if (dgrow_keep(c, s->d_out, first + 64, 0) != ZPK_OK) return 10;
                     continue;
                 }
-                if (!s->d_out && dgrow_keep(c, &s->d_out, &s->out_cap, 64, 0) != ZPK_OK) return 10;      // (an empty entry: still a buffer to point at)
+                if (!s->d_out && dgrow_keep(c, s->d_out, 64, 0) != ZPK_OK) return 10;      // (an empty entry: still a buffer to point at)
                 if (method == ZPK_METHOD_LZ4) hipLaunchKernelGGL(k_lz4_stream, dim3(1), dim3(64), 0, c->stream, (const u8*)s->d_in, s->in_len, s->d_out, cap_now, rec);
                 else hipLaunchKernelGGL(k_zstd_stream, dim3(1), dim3(ZSTD_WG_THREADS), 0, c->stream, (const u8*)s->d_in, s->in_len, s->d_out, cap_now, rec, zr, lit, all_in ? 1 : 0);
                 e = hipMemcpyAsync(&h, rec, sizeof(h), hipMemcpyDeviceToHost, c->stream);
@@ -722,7 +714,7 @@ static int dstream_windowless_step(zpk_dstream* s, zpk_codec* c, uint32_t method
                 u64 bigger = cap_now < (1ull << 45) ? 2 * cap_now : cap_now;
                 if (bigger > uncomp_size) bigger = uncomp_size;
                 const u64 keep = h.produced < cap_now ? h.produced : cap_now;            // history for the blocks to come
-                if (bigger <= cap_now || dgrow_keep(c, &s->d_out, &s->out_cap, bigger + 64, keep) != ZPK_OK) return 10;
+                if (bigger <= cap_now || dgrow_keep(c, s->d_out, bigger + 64, keep) != ZPK_OK) return 10;
             }
         }
         const u8* const body = method == ZPK_METHOD_NONE ? s->d_in : s->d_out;
@@ -780,7 +772,7 @@ int zpk_dstream_step(zpk_dstream* s, uint32_t method, uint64_t comp_size, uint64
     if (method != ZPK_METHOD_NONE && method != ZPK_METHOD_ZSTD && method != ZPK_METHOD_LZ4) return 19; /* ZPACK_ERROR_COMP_METHOD_INVALID */
     CodecLock lk(c);
     if (hipSetDevice(c->device) != hipSuccess) return 24; /* ZPACK_ERROR_NOT_AVAILABLE: never a CPU fallback */
-    if (s->fast == 0) s->fast = ((method == ZPK_METHOD_LZ4 || method == ZPK_METHOD_ZSTD) && comp_size >= ZPK_DS_FAST_MIN && c->dec_split_min != ~0ull) ? 1 : -1;
+    if (s->fast == 0) s->fast = ((method == ZPK_METHOD_LZ4 || method == ZPK_METHOD_ZSTD) && comp_size >= ZPK_DS_FAST_MIN && c->opt.dec_split_min != ~0ull) ? 1 : -1;
     if (s->fast == 1) {
         const int frc = method == ZPK_METHOD_LZ4 ? dstream_fast_lz4(s, c, comp_size, uncomp_size, hash, in, in_size, consumed, out, out_cap, produced, done)
                                                  : dstream_fast_zstd(s, c, comp_size, uncomp_size, hash, in, in_size, consumed, out, out_cap, produced, done);
@@ -795,7 +787,7 @@ int zpk_dstream_step(zpk_dstream* s, uint32_t method, uint64_t comp_size, uint64
 int zpk_cstream_create(zpk_codec* c, zpk_cstream** out)
 {
     if (!c || !out) return ZPK_E_INVALID;
-    zpk_cstream* s = (zpk_cstream*)calloc(1, sizeof(zpk_cstream));
+    zpk_cstream* s = new (std::nothrow) zpk_cstream();                                // (no member has an initialiser: all zero, the buffers empty)
     if (!s) return ZPK_E_NOMEM;
     s->c = c; s->device = c->device; *out = s;
     return ZPK_OK;
@@ -805,7 +797,7 @@ static void cstream_release(zpk_cstream* s)
 {
     if (!s || !(s->d_in || s->d_out || s->d_slots || s->d_aux)) return;
     if (hipSetDevice(s->device) != hipSuccess) return;
-    dfree(&s->d_in, &s->in_cap); dfree(&s->d_out, &s->out_cap); dfree(&s->d_slots, &s->slots_cap); dfree(&s->d_aux, &s->aux_cap);
+    s->d_in.release(); s->d_out.release(); s->d_slots.release(); s->d_aux.release();
 }
 
 void zpk_cstream_bind(zpk_cstream* s, zpk_codec* c)
@@ -818,9 +810,9 @@ void zpk_cstream_reset(zpk_cstream* s)
 {
     if (!s) return;
     s->in_len = 0; s->out_len = 0; s->out_pos = 0; s->total_in = 0; s->total_out = 0; s->configured = 0; s->steps = 0; s->framed = 0;
-    if (s->in_cap + s->out_cap + s->slots_cap > (64ull << 20)) cstream_release(s);
+    if (s->d_in.cap + s->d_out.cap + s->d_slots.cap > (64ull << 20)) cstream_release(s);
 }
-void zpk_cstream_destroy(zpk_cstream* s) { if (s) { cstream_release(s); free(s); } }
+void zpk_cstream_destroy(zpk_cstream* s) { if (s) { cstream_release(s); delete s; } }
 
 // method and level of the entry being written: from here on zpk_cstream_update compresses as the plaintext arrives
 int zpk_cstream_configure(zpk_cstream* s, uint32_t method, int32_t level)
@@ -842,7 +834,7 @@ int zpk_cstream_configure(zpk_cstream* s, uint32_t method, int32_t level)
 static int cstream_append(zpk_cstream* s, const u8* bytes, u32 n)
 {
     zpk_codec* c = s->c;
-    if (dgrow_keep(c, &s->d_out, &s->out_cap, s->out_len + n + 64, s->out_len) != ZPK_OK) return 10;
+    if (dgrow_keep(c, s->d_out, s->out_len + n + 64, s->out_len) != ZPK_OK) return 10;
     if (hipMemcpyAsync(s->d_out + s->out_len, bytes, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return 24;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return 24;              // (the bytes are the caller's stack)
     s->out_len += n; s->total_out += n;
@@ -859,13 +851,13 @@ static int cstream_step(zpk_cstream* s, u32 npieces, u64 last_len, u64 hash_bloc
     if (hash_blocks) hipLaunchKernelGGL(k_xxh3s_blocks, dim3(1), dim3(64), 0, c->stream, st, (const u8*)plain, hash_blocks);
     const u64 bytes = (u64)(npieces - 1) * ZPK_ENC_PIECE + last_len;
     if (s->method == ZPK_METHOD_NONE) {
-        if (dgrow_keep(c, &s->d_out, &s->out_cap, s->out_len + bytes + 64, s->out_len) != ZPK_OK) return 10;
+        if (dgrow_keep(c, s->d_out, s->out_len + bytes + 64, s->out_len) != ZPK_OK) return 10;
         if (bytes && hipMemcpyAsync(s->d_out + s->out_len, plain, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return 24;
         s->out_len += bytes; s->total_out += bytes; s->steps++;
         return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : 24;
     }
     const u64 bound = zpk_codec_compress_bound(s->method, ZPK_ENC_PIECE), slot = (bound + 255) & ~255ull;
-    if (dgrow_keep(c, &s->d_slots, &s->slots_cap, slot * ZPK_CS_PIECES + 64, 0) != ZPK_OK) return 10;
+    if (dgrow_keep(c, s->d_slots, slot * ZPK_CS_PIECES + 64, 0) != ZPK_OK) return 10;
     if (sequence && !s->framed) {
         // an entry that goes out in pieces is ONE frame (round 5; what the reference's streaming writer keeps open across calls,
         // lib/zpack_write.c:477-574): its header now — no content size, it is not known yet —, the pieces as runs of blocks, the end of
@@ -887,7 +879,7 @@ static int cstream_step(zpk_cstream* s, u32 npieces, u64 last_len, u64 hash_bloc
     if (hipMemcpyAsync(dd, hd, npieces * sizeof(zpk_encode_desc), hipMemcpyHostToDevice, c->stream) != hipSuccess) return 24;
     if (zpk_codec_encode_batch_device(c, plain, bytes + 16, dd, npieces, s->d_slots, slot * ZPK_CS_PIECES, dr, c->stream) != ZPK_OK) return 24;
     // the frames back to back behind what is still waiting to be handed out
-    if (dgrow_keep(c, &s->d_out, &s->out_cap, s->out_len + bound * npieces + 64, s->out_len) != ZPK_OK) return 10;
+    if (dgrow_keep(c, s->d_out, s->out_len + bound * npieces + 64, s->out_len) != ZPK_OK) return 10;
     if (zpk_codec_pack_batch_device(c, s->d_slots, dd, dr, npieces, s->d_out + s->out_len, bound * npieces, doff, bound, c->stream) != ZPK_OK) return 24;
     zpk_encode_result hr[ZPK_CS_PIECES]; u64 hoff[ZPK_CS_PIECES + 1];
     hipError_t e = hipMemcpyAsync(hr, dr, npieces * sizeof(zpk_encode_result), hipMemcpyDeviceToHost, c->stream);
@@ -908,10 +900,10 @@ int zpk_cstream_update(zpk_cstream* s, const uint8_t* in, size_t in_size)
     CodecLock lk(c);
     if (hipSetDevice(c->device) != hipSuccess) return 24;
     if (!s->configured) { s->method = ZPK_METHOD_NONE; s->level = 0; }        // (a caller that never configures: everything is compressed by zpk_cstream_finish)
-    if (dgrow_keep(c, &s->d_aux, &s->aux_cap, ZPK_CS_AUX_BYTES, 0) != ZPK_OK) return 10;
+    if (dgrow_keep(c, s->d_aux, ZPK_CS_AUX_BYTES, 0) != ZPK_OK) return 10;
     if (s->total_in == 0) {
         hipLaunchKernelGGL(k_xxh3s_init, dim3(1), dim3(64), 0, c->stream, (zpk_cs_state*)(s->d_aux + ZPK_CS_AUX_STATE));
-        if (dgrow_keep(c, &s->d_in, &s->in_cap, ZPK_CS_CARRY + 64, 0) != ZPK_OK) return 10;
+        if (dgrow_keep(c, s->d_in, ZPK_CS_CARRY + 64, 0) != ZPK_OK) return 10;
         if (hipMemsetAsync(s->d_in, 0, ZPK_CS_CARRY, c->stream) != hipSuccess) return 24;
     }
     while (in_size) {
@@ -921,7 +913,7 @@ int zpk_cstream_update(zpk_cstream* s, const uint8_t* in, size_t in_size)
         const u64 thr = !s->configured ? ~0ull >> 2 : (s->steps == 0 ? (u64)ZPK_ENC_PIECE : (u64)ZPK_ENC_PIECE * ZPK_CS_PIECES);
         const u64 room = thr + 1 - s->in_len;                               // (in_len <= thr here: a step leaves at most one piece behind)
         const u64 take = in_size < room ? in_size : room;
-        if (dgrow_keep(c, &s->d_in, &s->in_cap, ZPK_CS_CARRY + s->in_len + take + 64, ZPK_CS_CARRY + s->in_len) != ZPK_OK) return 10;
+        if (dgrow_keep(c, s->d_in, ZPK_CS_CARRY + s->in_len + take + 64, ZPK_CS_CARRY + s->in_len) != ZPK_OK) return 10;
         if (hipMemcpyAsync(s->d_in + ZPK_CS_CARRY + s->in_len, in, take, hipMemcpyHostToDevice, c->stream) != hipSuccess) return 24;
         s->in_len += take; s->total_in += take; in += take; in_size -= take;
         if (s->in_len > thr) {
@@ -948,8 +940,8 @@ int zpk_cstream_finish(zpk_cstream* s, uint32_t method, int32_t level, uint64_t*
     CodecLock lk(c);
     if (hipSetDevice(c->device) != hipSuccess) return 24;
     if (!s->configured || s->total_in == 0) { s->method = method; s->level = level; }
-    if (dgrow_keep(c, &s->d_aux, &s->aux_cap, ZPK_CS_AUX_BYTES, 0) != ZPK_OK) return 10;
-    if (dgrow_keep(c, &s->d_in, &s->in_cap, ZPK_CS_CARRY + s->in_len + 64, s->total_in ? ZPK_CS_CARRY + s->in_len : 0) != ZPK_OK) return 10;   // (an empty entry that never saw an update: still a buffer to point at, nothing to keep)
+    if (dgrow_keep(c, s->d_aux, ZPK_CS_AUX_BYTES, 0) != ZPK_OK) return 10;
+    if (dgrow_keep(c, s->d_in, ZPK_CS_CARRY + s->in_len + 64, s->total_in ? ZPK_CS_CARRY + s->in_len : 0) != ZPK_OK) return 10;   // (an empty entry that never saw an update: still a buffer to point at, nothing to keep)
     zpk_cs_state* const st = (zpk_cs_state*)(s->d_aux + ZPK_CS_AUX_STATE);
     if (s->total_in == 0) hipLaunchKernelGGL(k_xxh3s_init, dim3(1), dim3(64), 0, c->stream, st);
     hipLaunchKernelGGL(k_xxh3s_finish, dim3(1), dim3(64), 0, c->stream, st, (const u8*)(s->d_in + ZPK_CS_CARRY), s->in_len, s->total_in);
