@@ -45,23 +45,27 @@ class Batch:
     """Plaintexts laid out in one source blob (offsets NOT 16-aligned, 64 bytes of allocation behind the last byte) and one slot per
     entry in one larger tensor, a canary region in front of, between and behind the slots."""
 
-    def __init__(self, plains, methods, caps=None):
+    def __init__(self, plains, methods, caps=None, dst_offsets=None, tail=256):
+        """dst_offsets: where the slots start (default: one behind the other's bound, 77 to 89 bytes between them); tail: bytes of
+        allocation behind the last slot"""
         self.plains, self.methods, self.n = plains, methods, len(plains)
         self.desc = d = np.zeros(self.n, dtype=zpack_amd.ENCODE_DESC)
         bound = zpack_amd.lib().zpk_codec_compress_bound
-        pos, out = 5, 131
+        pos, out, end = 5, 131, 0
         for i, (p, (m, lv)) in enumerate(zip(plains, methods)):
             pos += (3, 7, 11, 1)[i % 4]
             if pos % 16 == 0:
                 pos += 3
             full = int(bound(m, len(p)))
-            d[i] = (pos, len(p), out, full if caps is None or caps[i] is None else caps[i], m, lv)
+            cap = full if caps is None or caps[i] is None else caps[i]
+            d[i] = (pos, len(p), out if dst_offsets is None else dst_offsets[i], cap, m, lv)
             pos += len(p) + 16
             out += full + 77 + 2 * (i % 7)                                   # (the slots stay where they are whatever `caps` says)
+            end = max(end, int(d[i]["dst_offset"]) + cap)
         self.blob = np.zeros(pos + 64, dtype=np.uint8)
         for p, e in zip(plains, d):
             self.blob[int(e["src_offset"]):int(e["src_offset"]) + len(p)] = p
-        self.dst_bytes = out + 256
+        self.dst_bytes = out + tail if dst_offsets is None else end + tail
 
     def run(self, codec, desc=None, stream=None, call="big"):
         """-> (slots tensor, results tensor): enqueued, not waited for"""

@@ -492,6 +492,9 @@ struct ZeBits {
     u8* ptr; u64 c; u32 n;
     __device__ __forceinline__ void add(u32 v, u32 nb) { c |= (u64)(v & ((1u << nb) - 1u)) << n; n += nb; }      // nb <= 31
     __device__ __forceinline__ void flush() { st64(ptr, c); ptr += n >> 3; c = (n & ~7u) ? c >> (n & ~7u) : c; n &= 7u; }
+    // flush() stores eight bytes whatever it holds: fine where more of the block follows, but behind the END of a block's bitstream the
+    // spare bytes of the frame's last block landed behind comp_size (inside the slot, yet not the entry's).  This one stores the bytes it holds.
+    __device__ __forceinline__ void flush_exact() { for (u32 i = 0; i < ((n + 7u) >> 3); i++) st8(ptr + i, (u8)(c >> (8u * i))); ptr += n >> 3; c = (n & ~7u) ? c >> (n & ~7u) : c; n &= 7u; }
 };
 struct ZeState { u32 v; };
 // the encoder table of one of the three code kinds for the current block: the predefined one (mode 0), none (mode 1, RLE: the
@@ -1170,10 +1173,10 @@ __device__ inline u32 zstde_block_inner(Lz4EncSharedT<HLOG>& she, ZstdEncShared&
         so.v = (u32)__builtin_amdgcn_readlane((int)r_state, 0); sm.v = (u32)__builtin_amdgcn_readlane((int)r_state, 1); sl.v = (u32)__builtin_amdgcn_readlane((int)r_state, 2);
         lane0_guard();
         if (lane == 0 && ok) {
-            if (tm.mode != 1) { b.add(sm.v, tm.log); b.flush(); }
-            if (to.mode != 1) { b.add(so.v, to.log); b.flush(); }
-            if (tl.mode != 1) { b.add(sl.v, tl.log); b.flush(); }
-            b.add(1, 1); b.flush();                                         // end mark
+            if (tm.mode != 1) { b.add(sm.v, tm.log); b.flush_exact(); }
+            if (to.mode != 1) { b.add(so.v, to.log); b.flush_exact(); }
+            if (tl.mode != 1) { b.add(sl.v, tl.log); b.flush_exact(); }
+            b.add(1, 1); b.flush_exact();                                   // end mark
             seq_bytes = (u32)(b.ptr - sq) + (b.n ? 1u : 0u);
         }
     }
