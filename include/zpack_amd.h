@@ -94,6 +94,27 @@ ZPACK_EXPORT int zpack_amd_init_reader_device(zpack_reader* reader, const void* 
 /* *d_image / *device of a reader opened by the call above (NULL / -1 for any other reader). */
 ZPACK_EXPORT int zpack_amd_reader_device_image(const zpack_reader* reader, const void** d_image, int* device);
 
+/* ---- entries TESTED on the device: verdicts without plaintext --------------------------------------------------------------------------
+ * What `t` of the reference's command line does (programs/commands.c:706-773) and what a user does to a checkpoint before trusting it:
+ * every entry is decoded and hashed, the verdict is kept, the bytes are not.  The verdict is complete on the device, so no plaintext
+ * byte crosses the bus and the caller provides no buffer — for a reader over an image in device memory nothing crosses but descriptors
+ * and results, and the image can stay compressed.
+ *
+ * Results.  results[i], the return value and reader->last_return are exactly what zpack_read_files gives for the same entries when
+ *   buffer i is uncomp_size bytes, zero-filled; last_return by the same rule (the last entry's, or the last failing one's).  One bad
+ *   entry does not stop the others.  ZPACK_ERROR_BUFFER_TOO_SMALL cannot occur.
+ * Readers.  Memory-backed, file-backed and over an image in device memory.  Host and file readers shard over the context's devices
+ *   (ZPACK_AMD_DEVICES) as zpack_read_files does; a file reader gathers the payloads as that call does; a device image runs on the
+ *   image's device alone, which must be one of the context's (else ZPACK_ERROR_NOT_AVAILABLE).
+ * Read-ahead.  The call neither uses nor feeds the read-ahead windows: zpack_amd_read_ahead_stats is unchanged by it.
+ * Errors.  A NULL reader, or a NULL array with count > 0, is ZPACK_ERROR_STREAM_INVALID, checked before any context is created.
+ *   count == 0 is ZPACK_OK.  No device: ZPACK_ERROR_NOT_AVAILABLE.  A reader that is not loaded: ZPACK_ERROR_ARCHIVE_NOT_LOADED.  Staging
+ *   that cannot be allocated, on the host or on the device: ZPACK_ERROR_MALLOC_FAILED, and no result is set.
+ * Short decodes.  An entry whose frames end before uncomp_size bytes exist is hashed by the reference over its decoded bytes and
+ *   whatever the caller's buffer held behind them (lib/zpack_read.c:466).  Here there is no buffer: the tail counts as ZEROS — which is
+ *   why the contract above says "zero-filled". */
+ZPACK_EXPORT int zpack_amd_test_files(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count, int* results, void* dctx);
+
 /* ---- a WRITER whose sink is an archive image in DEVICE memory ----------------------------------------------------------------------
  * A third kind of writer beside the heap- and the file-backed one: the archive is written where it will be used — a checkpoint or data
  * set kept compressed beside the model, an image about to leave by a device-to-device transfer — and its compressed bytes never cross

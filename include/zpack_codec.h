@@ -53,7 +53,8 @@ extern "C" {
                                         zpk_codec_fetch_device, zpk_codec_decode_batch_dimage, ZPK_OPT_DIMAGE_CHUNK, zpk_codec_dimage_stats: the host-pointer paths
                                         with the ARCHIVE IMAGE in the caller's device memory.
                                         zpk_codec_store_device, zpk_codec_encode_batch_dsink, zpk_codec_dsink_stats, zpk_codec_stream_sync: a batch compressed into a bounded SINK in the
-                                        caller's device memory.) */
+                                        caller's device memory.
+                                        zpk_codec_verify_batch_host, zpk_codec_verify_batch_dimage, zpk_codec_verify_stats: a batch that is only TESTED, verdicts without plaintext.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -263,6 +264,28 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
                                   uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results);
 /* the most recent such call: out[0] sub-batches, out[1] k_span_copy launches, out[2] bytes copied home (saturating), out[3] 0 */
 int zpk_codec_dimage_stats(zpk_codec* c, uint32_t out[4]);
+
+/* ---- a batch that is only TESTED: verdicts without plaintext --------------------------------------------------------
+ * zpk_codec_decode_batch_host and zpk_codec_decode_batch_dimage with NO destination (lib/zpack_read.c:326-471 as `command_test` of the
+ * reference uses it, programs/commands.c:706-773: the bytes are thrown away, the verdict is kept).  desc and results are host memory;
+ * `archive` is host memory, `d_archive` device memory on the codec's device (the pointer check of zpk_codec_decode_batch_dimage);
+ * synchronous.  desc[i].dst_offset and .dst_capacity are ignored: the capacity counts as uncomp_size, so BUFFER_TOO_SMALL cannot occur,
+ * and results[i] is field for field what the read call gives for buffers of exactly uncomp_size bytes filled with ZEROS — an entry whose
+ * frames end before uncomp_size bytes exist is hashed with zeros behind its decoded bytes (the slot's tail is zeroed on the device).
+ * The routing is that of the read calls, through their own code, with a third kind of destination: the frame-parallel and block-parallel
+ * routes of large entries, the chip-wide route of large stored ones (k_xxh3_partials over the source instead of the fused copy), one
+ * one-wave launch for the rest, the pipelined upload of a large host sub-batch (no download stream; decode_stats2 out[14] counts it).
+ * A STORED entry has no staging slot at all: k_stored_hash, k_stored without the copy, hashes the payload where it lies.  Compressed
+ * entries decode into the codec's staging, which is never copied anywhere: only the results come home, and no k_span_copy is launched.
+ * Both calls cut their sub-batches by ZPK_OPT_DIMAGE_CHUNK.  decode_stats / decode_stats2 describe the call as they describe the read.
+ * n == 0: ZPK_OK; a NULL desc, results or image with n > 0: ZPK_E_INVALID. */
+int zpk_codec_verify_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
+                                const zpk_decode_desc* desc, uint64_t n, zpk_decode_result* results);
+int zpk_codec_verify_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size,
+                                  const zpk_decode_desc* desc, uint64_t n, zpk_decode_result* results);
+/* the most recent of these two calls (any later decode call counts its own): out[0] sub-batches, out[1] stored entries hashed in place —
+ * those with a payload that passed every guard —, out[2] plaintext bytes that came home (saturating), which reads 0, out[3] 0 */
+int zpk_codec_verify_stats(zpk_codec* c, uint32_t out[4]);
 
 /* ---- batch encode + hash ------------------------------------------------------------------ */
 size_t zpk_codec_compress_bound(uint32_t method, size_t src_size);

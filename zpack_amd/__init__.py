@@ -298,6 +298,35 @@ class Codec:
         self._chk(self.L.zpk_codec_dimage_stats(self.h, a), "zpk_codec_dimage_stats")
         return dict(sub_batches=a[0], span_copy_launches=a[1], bytes_copied_home=a[2])
 
+    # ---- a batch that is only TESTED: the verdicts of decode_batch_host / decode_batch_dimage, no plaintext anywhere ----
+    def verify_batch_host(self, archive, desc):
+        """archive: bytes/np.uint8 (host); desc: np array of DECODE_DESC, dst_offset / dst_capacity ignored.  Returns the results."""
+        arc = np.ascontiguousarray(np.frombuffer(archive, dtype=np.uint8) if not isinstance(archive, np.ndarray) else archive)
+        desc = np.ascontiguousarray(desc, dtype=DECODE_DESC)
+        res = np.zeros(len(desc), dtype=DECODE_RESULT)
+        self.L.zpk_codec_verify_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        self._chk(self.L.zpk_codec_verify_batch_host(self.h, arc.ctypes.data, arc.size, desc.ctypes.data, len(desc), res.ctypes.data),
+                  "zpk_codec_verify_batch_host")
+        return res
+
+    def verify_batch_dimage(self, image, desc):
+        """... with the archive image in device memory (a uint8 CUDA tensor on this codec's device)."""
+        self._settle(None)
+        desc = np.ascontiguousarray(desc, dtype=DECODE_DESC)
+        res = np.zeros(len(desc), dtype=DECODE_RESULT)
+        self.L.zpk_codec_verify_batch_dimage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        self._chk(self.L.zpk_codec_verify_batch_dimage(self.h, image.data_ptr(), image.numel(), desc.ctypes.data, len(desc), res.ctypes.data),
+                  "zpk_codec_verify_batch_dimage")
+        return res
+
+    def verify_stats(self):
+        """The last verify_batch_* call: its sub-batches (OPT_DIMAGE_CHUNK), the stored entries hashed in place and the plaintext bytes
+        that came home (0)."""
+        a = (C.c_uint32 * 4)()
+        self.L.zpk_codec_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        self._chk(self.L.zpk_codec_verify_stats(self.h, a), "zpk_codec_verify_stats")
+        return dict(sub_batches=a[0], stored_hashed_in_place=a[1], bytes_copied_home=a[2])
+
     # ---- a bounded SINK in the caller's device memory (a uint8 CUDA tensor; sources host arrays or device addresses; the tables host memory) ----
     def encode_batch_dsink(self, srcs, desc, sink, sink_offset=0, room=None, src_on_device=False):
         """encode_batch_host / _dsrc whose payloads are committed back to back to sink[sink_offset, sink_offset + room) under the append

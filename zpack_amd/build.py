@@ -62,7 +62,7 @@ def build_codec(force=False, verbose=False):
         return CODEC_SO
     dig = dig or _digest(srcs, flags)
     cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
-           "-Wno-unused-function", "-o", CODEC_SO, os.path.join(CSRC, "zpk_codec.hip"), os.path.join(CSRC, "span_copy.hip"), os.path.join(CSRC, "sink_commit.hip")]
+           "-Wno-unused-function", "-o", CODEC_SO, os.path.join(CSRC, "zpk_codec.hip"), os.path.join(CSRC, "span_copy.hip"), os.path.join(CSRC, "sink_commit.hip"), os.path.join(CSRC, "stored_hash.hip")]
     if os.environ.get("ZPK_STATS"):          # developer build: per-phase cycle counters in the decode kernels
         cmd.insert(1, "-DZPK_STATS=1")
     for d in os.environ.get("ZPK_DEFINES", "").split():      # developer build: A/B variants (-D names)
@@ -85,7 +85,7 @@ def build_codec_dev(force=False, verbose=False):
     dig = dig or _digest(srcs, "dev")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-DZPK_DEVELOPER",
-           "-o", out, os.path.join(CSRC, "zpk_codec.hip"), os.path.join(CSRC, "span_copy.hip"), os.path.join(CSRC, "sink_commit.hip")]
+           "-o", out, os.path.join(CSRC, "zpk_codec.hip"), os.path.join(CSRC, "span_copy.hip"), os.path.join(CSRC, "sink_commit.hip"), os.path.join(CSRC, "stored_hash.hip")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -116,7 +116,7 @@ def build_programs(force=False, verbose=False):
     """zpack_amd/zpk-batch: the batch-aware `t` / `x` commands over libzpack_amd.so (programs/zpk_batch.c)"""
     src = os.path.join(HERE, "programs", "zpk_batch.c")
     exe = os.path.join(HERE, "zpk-batch")
-    deps = [src, ZPACK_SO, os.path.join(ROOT, "include", "zpack.h")]
+    deps = [src, ZPACK_SO, os.path.join(ROOT, "include", "zpack.h"), os.path.join(ROOT, "include", "zpack_amd.h")]
     dig = _stale(exe, deps)
     if not force and dig is None:
         return exe

@@ -46,6 +46,8 @@
 // k_span_copy (span_copy.h) is compiled in a file of its own, span_copy.hip: this file's code object stays the one it was, kernel for
 // kernel at the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
 namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
+// ... and so is k_stored_hash (stored_hash.h, stored_hash.hip): k_stored without the copy, for a batch that has no destination
+namespace zpk { void stored_hash_launch(const u8* src, const zpk_decode_desc* desc, zpk_decode_result* res, const u32* list, const u32* counters, u32 grid, hipStream_t st); }
 #include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
 #include "dsink_plan.h"                          // a batch compressed into a bounded sink in DEVICE memory: the cut, the span table, room and chaining, the staging (plain C++, likewise); the kernels: sink_commit.hip
 #include "stream_plan.h"                        // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
@@ -608,6 +610,19 @@ __global__ __launch_bounds__(256) void k_hash(const u8* __restrict__ src, const 
 // paths count while they cut the batch), -1 = a device batch, which may hold any
 struct BatchMethods { int zstd, lz4; };
 
+// Where the plaintext of a host-path or device-image batch goes: the caller's HOST buffers (the copy home and the scatter), the caller's
+// DEVICE buffers (k_span_copy), or NOWHERE — the batch is only tested (zpk_codec_verify_batch_host / _dimage): the verdicts come home,
+// no plaintext byte does.  One routing serves the three.  Without a destination dst_ptrs is not looked at (it may be NULL), the
+// descriptors' capacity is uncomp_size (verify_descs), a stored entry has no staging slot and is hashed where it lies (k_stored_hash;
+// a large one: k_xxh3_partials over the source), and the tail of a short decode counts as zeros (rehash_short_entries).
+enum class Dst : int { Host = 0, Device = 1, None = 2 };
+// the staging slot of an entry under destination `to` (span_copy_plan.h states the layout for the two kinds that have one)
+static inline u64 staging_slot(Dst to, const zpk_decode_desc& d)
+{
+    const bool stored = d.method == ZPK_METHOD_NONE;
+    return to == Dst::None ? (stored ? 0ull : span_copy_read_slot(false, d.uncomp_size, d.uncomp_size)) : span_copy_read_slot(stored, d.uncomp_size, d.dst_capacity);
+}
+
 // The words the stats calls report of the most recent call.  begin_decode_call zeroes the decode words; dimage, dsink and enc_big are
 // zeroed by the one call that counts them; totals_valid by every launch, fell_back_fused by the launch that decides it.
 struct LastCall {
@@ -617,6 +632,9 @@ struct LastCall {
     u32  pipe = 0, sc = 0;                       // host decode call: sub-batches that took the three-stage pipeline; k_span_copy launches
     u32  zpj_err = 0;                            // developer: the flag word of the most recent large Zstandard frame (why it went to the one-wave decoder)
     u32  dimage[3] = {0, 0, 0};                  // zpk_codec_decode_batch_dimage: its sub-batches, k_span_copy launches and the bytes it copied home (saturating)
+    u32  subs = 0;                               // host decode call, device-image call: their sub-batches (zpk_codec_verify_stats reports them for the calls without a destination)
+    u64  home = 0;                               // ... the PLAINTEXT bytes they copied home (saturating) — 0 for a call without a destination
+    u32  vstored = 0;                            // zpk_codec_verify_batch_host / _dimage: stored entries hashed where they lay
     u32  dsink[2] = {0, 0};                      // zpk_codec_encode_batch_dsink: its sub-batches and the last grid of k_sink_place
     u32  enc_big[2] = {0, 0};                    // zpk_codec_encode_big_device: entries written in pieces, their pieces
     int  fell_back_fused = 0;                    // the last decode batch could not get its sequence arena and ran the fused decoder only
@@ -1008,8 +1026,10 @@ static void join_stream(SideStream& x, hipStream_t into)
     if (hipEventRecord(x.join, x.s) != hipSuccess || hipStreamWaitEvent(into, x.join, 0) != hipSuccess) (void)hipStreamSynchronize(x.s);
 }
 
+// hash_only: the batch has no destination (Dst::None) — its stored entries have no slot in dst and are hashed where they lie
+// (k_stored_hash in place of k_stored); everything else decodes into its slot as ever.
 static int decode_launch(zpk_codec* c, BatchMethods holds, const u8* src, u64 src_size, const u8* read_lo, const u8* read_hi,
-                         const zpk_decode_desc* desc, u64 n, u8* dst, u64 dst_size, zpk_decode_result* res, hipStream_t st)
+                         const zpk_decode_desc* desc, u64 n, u8* dst, u64 dst_size, zpk_decode_result* res, hipStream_t st, bool hash_only = false)
 {
     if (n == 0) return ZPK_OK;
     if (n > 0x7FFFFFF0ull) return ZPK_E_INVALID;               // one workgroup per LZ4 entry: the grid's x limit
@@ -1044,7 +1064,9 @@ static int decode_launch(zpk_codec* c, BatchMethods holds, const u8* src, u64 sr
     ZPK_TRACE_STEP("memset");
 #define ZPK_KEV(k, j) do { if (c->profiling) (void)hipEventRecord(c->kev[k][j], st); } while (0)
     ZPK_KEV(ZPK_K_CLASSIFY, 0);
-    hipLaunchKernelGGL(k_classify, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, src, desc, n, src_size, dst_size, res,
+    // (hash_only: k_classify's last guard — the slot lies inside dst, the bound of a CALLER'S layout in the device-resident call — is
+    // switched off by its size: the slots are the codec's own layout of these very descriptors, and a stored entry has none)
+    hipLaunchKernelGGL(k_classify, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, src, desc, n, src_size, hash_only ? ~0ull : dst_size, res,
                        c->wave.d_lists, stride, c->d_counters);
     // largest entries first (see k_order_count); batches that fit the resident waves in one round have nothing to order
     const u32* zstd_list = list_at(S_ZSTD);
@@ -1062,7 +1084,8 @@ static int decode_launch(zpk_codec* c, BatchMethods holds, const u8* src, u64 sr
     ZPK_TRACE_STEP("k_classify");
     const u32 wgrid = (u32)((n + 3) / 4);          // one wave per list slot
     ZPK_KEV(ZPK_K_STORED, 0);
-    if (!(skip & 1)) hipLaunchKernelGGL(k_stored, dim3(wgrid), dim3(256), 0, st, src, desc, dst, res, list_at(S_NONE), c->d_counters);
+    if (hash_only) { if (!(skip & 1)) stored_hash_launch(src, desc, res, list_at(S_NONE), c->d_counters, wgrid, st); }
+    else if (!(skip & 1)) hipLaunchKernelGGL(k_stored, dim3(wgrid), dim3(256), 0, st, src, desc, dst, res, list_at(S_NONE), c->d_counters);
     ZPK_KEV(ZPK_K_STORED, 1);
     ZPK_TRACE_STEP("k_stored");
     // LZ4: one wave per work-list slot (lz4_wave.h).  A batch that may hold both methods runs the LZ4 kernels on a SIDE stream of
@@ -1186,9 +1209,11 @@ int zpk_codec_decode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
 // hashes buffer[0, uncomp_size) all the same — the decoded bytes followed by whatever the CALLER'S buffer held.  The device slot holds
 // something else there (an earlier batch's output), so for these rare entries the caller's bytes are brought up behind the decoded
 // ones and the slot is hashed again: the verdict is the one the reference reaches on this caller's buffer.
-// (ddst: dst_ptrs are DEVICE pointers — zpk_codec_decode_batch_host_dptr — and the caller's bytes come over from there)
+// (Dst::Device: dst_ptrs are DEVICE pointers — zpk_codec_decode_batch_host_dptr — and the caller's bytes come over from there.
+// Dst::None: there is no caller's buffer; the tail counts as ZEROS — the slot's tail is zeroed on the device, and the verdict is the one
+// a read into a zero-filled buffer of uncomp_size bytes reaches.)
 static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, uint8_t* const* dst_ptrs,
-                                zpk_decode_result* results, bool ddst = false)
+                                zpk_decode_result* results, Dst to = Dst::Host)
 {
     for (u64 i = 0; i < n; i++) {
         zpk_decode_result& r = results[i];
@@ -1198,7 +1223,8 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
         if ((rc = grow(c, c->d_xpart, 64))) return rc;
         const u64 tail = desc[i].uncomp_size - r.produced;
         u64 meta[3] = { hd[i].dst_offset, desc[i].uncomp_size, 0 };
-        HIPCHK(c, hipMemcpyAsync(c->d_dst + hd[i].dst_offset + r.produced, dst_ptrs[i] + r.produced, tail, ddst ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        if (to == Dst::None) HIPCHK(c, hipMemsetAsync(c->d_dst + hd[i].dst_offset + r.produced, 0, tail, c->stream));
+        else HIPCHK(c, hipMemcpyAsync(c->d_dst + hd[i].dst_offset + r.produced, dst_ptrs[i] + r.produced, tail, to == Dst::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_xpart, meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
         u64* m = (u64*)c->d_xpart;
         hipLaunchKernelGGL(k_hash, dim3(1), dim3(64), 0, c->stream, (const u8*)c->d_dst, (const u64*)m, (const u64*)(m + 1), (u64)1, m + 2);
@@ -1356,9 +1382,9 @@ static int stage_sources(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc
 #define ZPK_SRC_SLACK 192u
 #define ZPK_SRC_READ_SLACK 128u
 static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
-                         zpk_decode_result* results, bool ddst, u64* home = nullptr);
+                         zpk_decode_result* results, Dst to, u64* home = nullptr);
 static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
-                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, BatchMethods holds, bool ddst = false)
+                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, BatchMethods holds, Dst to = Dst::Host)
 {
     int rc;
     if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
@@ -1371,20 +1397,20 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
     // base pointer such that base + src_offset lands in the staged range; reads are clamped to it
     const u8* base = c->d_src - lo;
     rc = decode_launch(c, holds, base, image_size, c->d_src, c->d_src + (hi - lo) + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, n,
-                       c->d_dst, out_total, (zpk_decode_result*)c->d_res, c->stream);
+                       c->d_dst, out_total, (zpk_decode_result*)c->d_res, c->stream, to == Dst::None);
     if (rc) return rc;
     e = hipMemcpyAsync(results, c->d_res, n * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "decode: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    return deliver_slots(c, hd, desc, n, out_total, dst_ptrs, results, ddst);
+    return deliver_slots(c, hd, desc, n, out_total, dst_ptrs, results, to);
 }
 
 // The slots of a decoded sub-batch, c->d_dst + hd[i].dst_offset, handed to the caller (decode_host_chunk; zpk_codec_decode_batch_dimage):
 // everything the codec produced (a hash mismatch leaves the data in the buffer, like the reference), and only that — a generous
 // max_size costs device address space, not PCIe time.  results[0, n) are home and the decode has completed.  *home: the bytes that
-// crossed the bus for it.
+// crossed the bus for it.  Dst::None: nothing is handed over — no copy, no k_span_copy; only the short decodes are looked at.
 static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
-                         zpk_decode_result* results, bool ddst, u64* home)
+                         zpk_decode_result* results, Dst to, u64* home)
 {
     int rc;
     hipError_t e = hipSuccess;
@@ -1394,7 +1420,8 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
         if (results[i].produced > desc[i].dst_capacity) results[i].produced = desc[i].dst_capacity;     // (cannot happen)
         produced_total += results[i].produced;
     }
-    if (ddst) {
+    if (to == Dst::None) return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to);
+    if (to == Dst::Device) {
         // DEVICE destinations: the same bytes — [slot, slot + produced) of every entry — by ONE launch of k_span_copy, no host in between
         if ((rc = span_copy_enqueue(c, n, [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], results[i].produced }; }, c->stream))) return rc;
         e = hipStreamSynchronize(c->stream);
@@ -1405,13 +1432,15 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
         rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; }, [&](u64 i) { return (u64)results[i].produced; }, e);
         if (rc) return rc;
         if (home) *home = out_total;
+        c->last.home = out_total > ~0ull - c->last.home ? ~0ull : c->last.home + out_total;
     } else {
         for (u64 i = 0; i < n && e == hipSuccess; i++)
             if (results[i].produced) e = hipMemcpy(dst_ptrs[i], c->d_dst + hd[i].dst_offset, results[i].produced, hipMemcpyDeviceToHost);
         if (home) *home = produced_total;
+        c->last.home = produced_total > ~0ull - c->last.home ? ~0ull : c->last.home + produced_total;
     }
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "D2H: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, ddst);
+    return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to);
 }
 
 // ---- the same chunk as a three-stage pipeline (round 3) ------------------------------------------------------------------------
@@ -1431,8 +1460,11 @@ struct HostPiece { u64 e0, e1, clo, chi, olo, ohi; };
 
 static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
                                  const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results,
-                                 bool& taken, BatchMethods holds, bool ddst = false)
+                                 bool& taken, BatchMethods holds, Dst to = Dst::Host)
 {
+    // Dst::None: stage 1 (the upload) still runs beside stage 2 (the decode); there is no stage 3 — no download stream, no `decoded`
+    // events — and the verdicts come home in one copy behind the last piece
+    const bool ddst = to == Dst::Device, none = to == Dst::None;
     taken = false;
     const u64 min_entries = holds.zstd ? 12288 : 4096;
     if (out_total < 3 * ZPK_PIPE_PIECE || n < 3 * min_entries) return ZPK_OK;
@@ -1464,9 +1496,9 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
         (rc = grow(c, c->d_desc, n * sizeof(zpk_decode_desc))) ||
         (rc = grow(c, c->d_res, n * sizeof(zpk_decode_result))) || (rc = pin_ready(c))) return rc;
-    if (c->pipe.s_up.ready(hipStreamNonBlocking) != hipSuccess || c->pipe.s_dn.ready(hipStreamNonBlocking) != hipSuccess) return ZPK_OK;
+    if (c->pipe.s_up.ready(hipStreamNonBlocking) != hipSuccess || (!none && c->pipe.s_dn.ready(hipStreamNonBlocking) != hipSuccess)) return ZPK_OK;
     for (int k = 0; k < 2 * np; k++)
-        if (c->pipe.ev[k].ready(hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) return ZPK_OK;
+        if (!(none && (k & 1)) && c->pipe.ev[k].ready(hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) return ZPK_OK;
     taken = true;
     c->last.pipe++;
     hipError_t e = hipMemcpyAsync(c->d_desc, hd, n * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
@@ -1495,9 +1527,9 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             const HostPiece& P = pc[k];
             if (lrc == ZPK_OK)
                 lrc = decode_launch(c, holds, base, image_size, c->d_src + (P.clo - lo), c->d_src + (P.chi - lo) + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc + P.e0,
-                                    P.e1 - P.e0, c->d_dst, out_total, (zpk_decode_result*)c->d_res + P.e0, c->stream);
+                                    P.e1 - P.e0, c->d_dst, out_total, (zpk_decode_result*)c->d_res + P.e0, c->stream, none);
             if (lrc == ZPK_OK && hipMemcpyAsync(c->pipe.piece_counters[k], c->d_counters, N_COUNTERS * sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess) lrc = ZPK_E_LAUNCH;
-            if (lrc == ZPK_OK && hipEventRecord(c->pipe.ev[2 * k + 1], c->stream) != hipSuccess) lrc = ZPK_E_LAUNCH;
+            if (lrc == ZPK_OK && !none && hipEventRecord(c->pipe.ev[2 * k + 1], c->stream) != hipSuccess) lrc = ZPK_E_LAUNCH;
             if (lrc != ZPK_OK) { launch_rc.store(lrc); launched.store(-1); return; }
             launched.store(k + 1);
         }
@@ -1525,7 +1557,9 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         }
         return hipSuccess;
     };
-    if (ddst) {
+    if (none) {
+        // no destination: nothing comes home while the pieces run; the verdicts follow the last piece, below
+    } else if (ddst) {
         // DEVICE destinations (zpk_codec_decode_batch_host_dptr): there is no download.  Piece by piece, as soon as its decode has run: the
         // verdicts come home and ONE k_span_copy on the download stream moves the piece's slots to their pointers — [slot, slot + produced),
         // the bytes the scatter below copies — while the upload and the decode of the pieces behind it go on.
@@ -1546,10 +1580,15 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     } else
     rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; },
                      [&](u64 i) { const u64 p = results[i].produced; return p > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : p; }, e, c->pipe.s_dn, pre);
+    if (!ddst && !none && rc == ZPK_OK) c->last.home = out_total > ~0ull - c->last.home ? ~0ull : c->last.home + out_total;
     if (up_threaded) t_up.join();
     if (launch_threaded) t_launch.join();
-    if (!ddst && rc == ZPK_OK && e == hipSuccess) e = pre(out_total + 1);       // (pieces with no output bytes: their results still come back)
-    if (rc == ZPK_OK && e == hipSuccess) e = hipStreamSynchronize(c->pipe.s_dn);
+    if (none && launch_rc.load() == ZPK_OK) {                                   // every piece is enqueued: the verdicts, behind the last one
+        e = hipMemcpyAsync(results, c->d_res, n * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    if (!ddst && !none && rc == ZPK_OK && e == hipSuccess) e = pre(out_total + 1);       // (pieces with no output bytes: their results still come back)
+    if (!none && rc == ZPK_OK && e == hipSuccess) e = hipStreamSynchronize(c->pipe.s_dn);
     if (launch_rc.load() != ZPK_OK) rc = launch_rc.load();
     else if (rc == ZPK_OK && e != hipSuccess) { snprintf(c->err, sizeof(c->err), "host decode pipeline: %s", hipGetErrorString(e)); rc = ZPK_E_LAUNCH; }
     if (rc != ZPK_OK) { (void)hipStreamSynchronize(c->pipe.s_up); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->pipe.s_dn); }
@@ -1559,7 +1598,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         for (int k = 0; k < np; k++) for (int w = 0; w < N_COUNTERS; w++) c->last.host_totals[w] += c->pipe.piece_counters[k][w];
         c->last.totals_valid = 1;
     }
-    if (rc == ZPK_OK) rc = rehash_short_entries(c, hd, desc, n, dst_ptrs, results, ddst);
+    if (rc == ZPK_OK) rc = rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to);
     return rc;
 }
 
@@ -1585,7 +1624,7 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
     const u64 nchunks = (nb + chunk_blocks - 1) / chunk_blocks;
     if (nchunks > ZPK_PJ_MAX_CHUNKS) return ZPK_OK;
     for (u64 k = 0; k < nchunks; k++) if (c->pj.ev[k].ready(hipEventDisableTiming) != hipSuccess) return ZPK_OK;
-    if (c->pipe.s_dn.ready(hipStreamNonBlocking) != hipSuccess) return ZPK_OK;
+    if (dst_ptr && c->pipe.s_dn.ready(hipStreamNonBlocking) != hipSuccess) return ZPK_OK;    // (no host destination: no download, no stream for one)
     if ((rc = pin_ready(c))) return rc;
     // the XXH3 of the output runs BESIDE all this on its own stream, section by section as the chunks become final (xxh3_span.h: the
     // partial sums of a section's blocks side by side, then the one-wave chain over them — 14 ms for 256 MiB, as long as everything else
@@ -1666,7 +1705,8 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
     const hipError_t e2 = hipStreamSynchronize(sh), e3 = hipStreamSynchronize(st);
     if (e == hipSuccess) e = e2 != hipSuccess ? e2 : e3;
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large frame: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    if ((u32)c->pj.h_words[1] != 0) return ZPK_OK;                                                       // PJ_ERR: something was irregular after all
+    if (dst_ptr) c->last.home = n > ~0ull - c->last.home ? ~0ull : c->last.home + n;
+    if ((u32)c->pj.h_words[1] != 0) return ZPK_OK;                                                      // PJ_ERR: something was irregular after all
     const zpk_decode_result v = dec_hash_verdict(d, c->pj.h_words[0]);
     if (v.status != DEC_R_OK && !accept_mismatch) return ZPK_OK;                                   // (the one-wave decoder gives this entry's verdict)
     result = v;
@@ -1680,7 +1720,11 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
 // The two ends of a block-parallel entry: the archive its bytes are read from (archive + src_offset) and where ITS output goes, each
 // either host or device memory.  Output on the device stays where it is written; a host destination gets it through c->d_dst.
 struct BigSrc { const u8* archive; bool on_device; };
-struct BigDst { u8* p; bool on_device; };
+struct BigDst {                                                                      // to = Dst::None: p is not looked at, the output stays in c->d_dst and only its XXH3 is asked for
+    u8* p; Dst to;
+    bool staged() const { return to != Dst::Device; }                                // decoded into c->d_dst (from where a host destination gets it)
+    u8* host() const { return to == Dst::Host ? p : nullptr; }
+};
 
 // -> ZPK_OK with redo = 0: the entry is decoded, hashed and delivered; redo = 1: not this path's (the one-wave decoder decides)
 static int decode_big_lz4_single(zpk_codec* c, const BigSrc& src, const zpk_decode_desc& d, const std::vector<PjBlock>& blocks, int independent,
@@ -1690,7 +1734,7 @@ static int decode_big_lz4_single(zpk_codec* c, const BigSrc& src, const zpk_deco
     const u64 nb = blocks.size(), n = d.uncomp_size;
     const u64 total_recs = (u64)blocks.back().rec_base + ((blocks.back().comp_size >> 31) ? 0 : (blocks.back().comp_size / 3 + 2));
     int rc;
-    if ((rc = grow(c, c->d_src, d.comp_size + ZPK_SRC_SLACK)) || (!dst.on_device && (rc = grow(c, c->d_dst, n + 16))) ||
+    if ((rc = grow(c, c->d_src, d.comp_size + ZPK_SRC_SLACK)) || (dst.staged() && (rc = grow(c, c->d_dst, n + 16))) ||
         (rc = grow(c, c->pj.d_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->pj.d_recs, (total_recs + 64) * 8)) ||
         (rc = grow(c, c->pj.d_masks, nb * (PJ_BLOCK / 8))) || (rc = grow(c, c->pj.d_S, n * 4 + 64))) { c->err[0] = 0; return ZPK_OK; }     // no memory for the scratch: the one-wave decoder
     if (!c->pj.d_flags.ensure(256)) return ZPK_OK;
@@ -1715,7 +1759,7 @@ static int decode_big_lz4_single(zpk_codec* c, const BigSrc& src, const zpk_deco
     auto init = [&](u32 b0, u32 b1, hipStream_t s2) {
         hipLaunchKernelGGL(k_pj_init, dim3(b1 - b0), dim3(256), 0, s2, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->pj.d_recs, (const u32*)c->pj.d_masks, S, n, c->pj.d_flags, independent);
     };
-    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS, d.comp_size, init, true, dst.on_device ? dst.p : (u8*)c->d_dst, dst.on_device ? nullptr : dst.p, result, redo);
+    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS, d.comp_size, init, true, dst.staged() ? (u8*)c->d_dst : dst.p, dst.host(), result, redo);
 }
 
 // -> ZPK_OK with redo = 0: the entry is decoded, its XXH3 is the expected one, the bytes are delivered; redo = 1: not this path's
@@ -1741,7 +1785,7 @@ static int decode_big_zstd_single(zpk_codec* c, const BigSrc& src, const zpk_dec
     const u64 aux_desc = 0, aux_list = (nb * sizeof(zpk_decode_desc) + 255) & ~255ull, aux_state = aux_list + ((nb * 4 + 255) & ~255ull),
               aux_rep = aux_state + ((nb * 4 + 255) & ~255ull), aux_size = aux_rep + nb * 12 + 256;
     int rc;
-    if ((rc = grow(c, c->d_src, arena_off + lit_total + ZPK_SRC_SLACK)) || (!dst.on_device && (rc = grow(c, c->d_dst, n + 16))) ||
+    if ((rc = grow(c, c->d_src, arena_off + lit_total + ZPK_SRC_SLACK)) || (dst.staged() && (rc = grow(c, c->d_dst, n + 16))) ||
         (rc = grow(c, c->pj.d_blocks, nb * sizeof(PjBlock))) || (rc = grow(c, c->pj.d_zblocks, nb * sizeof(ZpjBlock))) ||
         (rc = grow(c, c->pj.d_zaux, aux_size)) || (rc = grow(c, c->pj.d_recs, (slots + 64) * 8)) ||
         (rc = grow(c, c->pj.d_zpos, (slots + 64) * 8)) || (rc = grow(c, c->pj.d_masks, nb * (ZPJ_BLOCK / 8))) ||
@@ -1787,16 +1831,19 @@ static int decode_big_zstd_single(zpk_codec* c, const BigSrc& src, const zpk_dec
         hipLaunchKernelGGL(k_zpj_init, dim3(b1 - b0), dim3(256), 0, s2, (const ZpjBlock*)ZB, (const PjBlock*)B, b0, (u32)nb, (const u64*)c->pj.d_recs, (const u64*)c->pj.d_zpos,
                            (const u32*)c->pj.d_masks, S, n, c->pj.d_flags);
     };
-    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS * PJ_BLOCK / ZPJ_BLOCK, arena_off + lit_total, init, false, dst.on_device ? dst.p : (u8*)c->d_dst, dst.on_device ? nullptr : dst.p, result, redo);
+    return pj_finish(c, d, hb, ZPK_PJ_CHUNK_BLOCKS * PJ_BLOCK / ZPJ_BLOCK, arena_off + lit_total, init, false, dst.staged() ? (u8*)c->d_dst : dst.p, dst.host(), result, redo);
 }
 
-// the frames of entries [g0, g1) of `be` as one device batch; redo[k] = 1: entry k takes the serial path after all
+// the frames of entries [g0, g1) of `be` as one device batch; redo[k] = 1: entry k takes the serial path after all.
+// Dst::None: nothing is handed over.  A group of STORED entries (the caller keeps the kinds apart then) is not cut into pieces and gets
+// no slots at all: its staged payloads are hashed where they lie, the partial sums and the chain over c->d_src.
 static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_desc* desc, const BigEntry* be, u64 g0, u64 g1,
-                            const std::vector<BigSub>& subs, uint8_t* const* dst_ptrs, zpk_decode_result* results, u8* redo, bool ddst = false)
+                            const std::vector<BigSub>& subs, uint8_t* const* dst_ptrs, zpk_decode_result* results, u8* redo, Dst to = Dst::Host)
 {
     const u64 ng = g1 - g0;
+    const bool src_only = to == Dst::None && desc[be[g0].idx].method == ZPK_METHOD_NONE;
     u64 nsub = 0;
-    for (u64 k = g0; k < g1; k++) nsub += be[k].nsub;
+    for (u64 k = g0; k < g1 && !src_only; k++) nsub += be[k].nsub;
     std::vector<u64> coff(ng + 1), ooff(ng + 1);
     std::vector<zpk_span> spans(ng);
     std::vector<u64> h_hash(ng);
@@ -1809,15 +1856,15 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         const BigEntry& E = be[g0 + k];
         const zpk_decode_desc& d = desc[E.idx];
         coff[k] = ct; ooff[k] = ot; cptr[k] = archive + d.src_offset;
-        for (u64 f = 0; f < E.nsub; f++, j++) {
+        for (u64 f = 0; f < E.nsub && !src_only; f++, j++) {
             const BigSub& S = subs[E.first_sub + f];
             zpk_decode_desc& x = hd[j];
             x.src_offset = ct + S.src_off; x.comp_size = S.comp; x.uncomp_size = S.size; x.expect_hash = 0;
             x.dst_offset = ot + S.out_off; x.dst_capacity = S.size; x.method = d.method; x.flags = ZPK_DF_SKIP_HASH;
         }
-        spans[k].off = ot; spans[k].len = d.uncomp_size; spans[k].part_base = part_blocks;
+        spans[k].off = src_only ? ct : ot; spans[k].len = d.uncomp_size; spans[k].part_base = part_blocks;
         part_blocks += xxh3_span_blocks(d.uncomp_size);
-        ct += (d.comp_size + 255) & ~255ull; ot += (d.uncomp_size + 255) & ~255ull;
+        ct += (d.comp_size + 255) & ~255ull; if (!src_only) ot += (d.uncomp_size + 255) & ~255ull;
         if (d.method == ZPK_METHOD_ZSTD) has_zstd = 1;
         if (d.method == ZPK_METHOD_LZ4) has_lz4 = 1;
     }
@@ -1832,14 +1879,14 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         const int grc = h2d_gather(c, c->d_src, ct, ng, cptr.data(), [&](u64 k) { return coff[k]; }, [&](u64 k) { return (u64)desc[be[g0 + k].idx].comp_size; }, e, c->stream);
         if (grc) return grc;
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_desc, hd.data(), nsub * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nsub) e = hipMemcpyAsync(c->d_desc, hd.data(), nsub * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     // (image size = the staged bytes + 1: the last frame still passes the `offset + comp_size < file_size` guard of :331)
     rc = decode_launch(c, BatchMethods{ has_zstd, has_lz4 }, c->d_src, ct + 1, c->d_src, c->d_src + ct + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, nsub,
                        c->d_dst, ot, (zpk_decode_result*)c->d_res, c->stream);
     if (rc) return rc;
-    if ((rc = xxh3_spans_launch(c, c->d_dst, spans.data(), ng, part_blocks, h_hash.data(), c->stream))) return rc;
-    e = hipMemcpyAsync(hr.data(), c->d_res, nsub * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
+    if ((rc = xxh3_spans_launch(c, src_only ? c->d_src : c->d_dst, spans.data(), ng, part_blocks, h_hash.data(), c->stream))) return rc;
+    if (nsub) e = hipMemcpyAsync(hr.data(), c->d_res, nsub * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "decode: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     j = 0;
@@ -1847,13 +1894,14 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         const BigEntry& E = be[g0 + k];
         const zpk_decode_desc& d = desc[E.idx];
         bool ok = true;
-        for (u64 f = 0; f < E.nsub; f++, j++) if (hr[j].status != 0 || hr[j].produced != subs[E.first_sub + f].size) ok = false;
+        for (u64 f = 0; f < E.nsub && !src_only; f++, j++) if (hr[j].status != 0 || hr[j].produced != subs[E.first_sub + f].size) ok = false;
         redo[g0 + k] = ok ? 0 : 1;
         if (!ok) continue;
         results[E.idx] = dec_hash_verdict(d, h_hash[k]);
         c->last.big[0]++; c->last.big[1] += (u32)E.nsub;
     }
-    if (ddst) {                                                                        // DEVICE destinations: one launch of k_span_copy
+    if (to == Dst::None) return ZPK_OK;                                                // no destination: the verdicts were all
+    if (to == Dst::Device) {                                                           // DEVICE destinations: one launch of k_span_copy
         auto row = [&](u64 k) { return zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size }; };
         if ((rc = span_copy_enqueue(c, ng, row, c->stream))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1864,6 +1912,7 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     rc = d2h_scatter(c, c->d_dst, ot, ng, optr.data(), [&](u64 k) { return ooff[k]; }, [&](u64 k) { return redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size; }, e);
     if (rc) return rc;
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "D2H: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
+    c->last.home = ot > ~0ull - c->last.home ? ~0ull : c->last.home + ot;
     return ZPK_OK;
 }
 
@@ -1897,12 +1946,14 @@ static int decode_big_single(zpk_codec* c, PjEntry& P, const zpk_decode_desc& d,
 }
 
 // the counts decode_stats2 reports of the most recent decode call: none yet
-static void begin_decode_call(zpk_codec* c) { LastCall& l = c->last; l.big[0] = l.big[1] = 0; l.walk[0] = l.walk[1] = 0; l.span[0] = l.span[1] = 0; l.pipe = l.sc = 0; }
+static void begin_decode_call(zpk_codec* c) { LastCall& l = c->last; l.big[0] = l.big[1] = 0; l.walk[0] = l.walk[1] = 0; l.span[0] = l.span[1] = 0; l.pipe = l.sc = 0; l.subs = 0; l.home = 0; l.vstored = 0; }
 
 static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                   uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst = false)
+                                   uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to = Dst::Host)
 {
     if (n == 0) return ZPK_OK;
+    // (no destination: the sub-batches are cut by ZPK_OPT_DIMAGE_CHUNK, as those of a device image are — a caller can force several cheaply)
+    const u64 chunk_bytes = to == Dst::None ? dimage_chunk(c->opt.dimage_chunk) : ZPK_HOST_CHUNK_BYTES;
     zpk_decode_desc* hd = (zpk_decode_desc*)malloc(n * sizeof(zpk_decode_desc));
     if (!hd) return ZPK_E_NOMEM;
     int rc = ZPK_OK;
@@ -1914,8 +1965,8 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
         while (first + cnt < n) {
             const zpk_decode_desc& d = desc[first + cnt];
             // stored entries copy exactly uncomp_size bytes (lib/zpack_read.c:366); the decoders may fill all of max_size
-            const u64 slot = span_copy_read_slot(d.method == ZPK_METHOD_NONE, d.uncomp_size, d.dst_capacity);      // (span_copy_plan.h states the layout for both kinds of destination)
-            if (cnt && (out_total + slot > ZPK_HOST_CHUNK_BYTES || cnt >= 0x7FFFFFF0ull)) break;
+            const u64 slot = staging_slot(to, d);                                             // (span_copy_plan.h states the layout for both kinds of destination; none: a stored entry has no slot)
+            if (cnt && (out_total + slot > chunk_bytes || cnt >= 0x7FFFFFF0ull)) break;
             hd[first + cnt] = span_copy_staged_desc(d, d.method == ZPK_METHOD_NONE, out_total);
             out_total += slot;
             if (dec_has_payload(d) && dec_src_in_image(d, archive_size)) { if (d.src_offset < lo) lo = d.src_offset; if (d.src_offset + d.comp_size > hi) hi = d.src_offset + d.comp_size; comp_sum += d.comp_size; }
@@ -1943,9 +1994,11 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
             image = gathered; image_size = total; lo = 0; hi = pos;
         }
         bool piped = false;
-        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, piped, holds, ddst);
+        uint8_t* const* const sub_ptrs = dst_ptrs ? dst_ptrs + first : nullptr;
+        c->last.subs++;
+        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, piped, holds, to);
         if (rc == ZPK_OK && !piped)
-            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, dst_ptrs + first, results + first, holds, ddst);
+            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, holds, to);
         first += cnt;
     }
     free(gathered);
@@ -1953,11 +2006,13 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
     return rc;
 }
 
-// zpk_codec_decode_batch_host and, ddst, zpk_codec_decode_batch_host_dptr: one routing, the destinations host or device memory
+// zpk_codec_decode_batch_host, zpk_codec_decode_batch_host_dptr and zpk_codec_verify_batch_host: one routing, the destinations host
+// memory, device memory or none (Dst)
 static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                 uint8_t* const* dst_ptrs, zpk_decode_result* results, bool ddst)
+                                 uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to)
 {
-    if (!c || (n && (!desc || !results || !dst_ptrs))) return ZPK_E_INVALID;
+    const bool ddst = to == Dst::Device;
+    if (!c || (n && (!desc || !results || (!dst_ptrs && to != Dst::None)))) return ZPK_E_INVALID;
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1993,14 +2048,16 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             }
         } catch (...) { be.clear(); subs.clear(); pj.clear(); }                       // out of host memory for the plan: the usual path
     }
-    if (be.empty() && pj.empty()) return decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results, ddst);
+    if (be.empty() && pj.empty()) return decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results, to);
     int rc = ZPK_OK;
     try {
         std::vector<u8> redo(be.size(), 0), is_big(n, 0);
         for (u64 g0 = 0; g0 < be.size() && rc == ZPK_OK; ) {                          // groups by the size of their output
             u64 g1 = g0, out = 0;
-            while (g1 < be.size() && (g1 == g0 || out + desc[be[g1].idx].uncomp_size <= ZPK_HOST_CHUNK_BYTES)) { out += (desc[be[g1].idx].uncomp_size + 255) & ~255ull; g1++; }
-            rc = decode_big_group(c, archive, desc, be.data(), g0, g1, subs, dst_ptrs, results, redo.data(), ddst);
+            // (no destination: stored entries and compressed ones in groups of their own — the stored ones are hashed in the staged source)
+            auto same_kind = [&](u64 g) { return to != Dst::None || (desc[be[g].idx].method == ZPK_METHOD_NONE) == (desc[be[g0].idx].method == ZPK_METHOD_NONE); };
+            while (g1 < be.size() && (g1 == g0 || (same_kind(g1) && out + desc[be[g1].idx].uncomp_size <= ZPK_HOST_CHUNK_BYTES))) { out += (desc[be[g1].idx].uncomp_size + 255) & ~255ull; g1++; }
+            rc = decode_big_group(c, archive, desc, be.data(), g0, g1, subs, dst_ptrs, results, redo.data(), to);
             g0 = g1;
         }
         // ---- everything else, and the entries a frame of which did not decode, through the usual path ----
@@ -2008,7 +2065,7 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
         pj_choose(desc, n, pj);
         for (u64 k = 0; k < pj.size() && rc == ZPK_OK; k++) {                         // one large frame at a time: each fills the chip
             u8 again = 1;
-            rc = decode_big_single(c, pj[k], desc[pj[k].idx], BigSrc{ archive, false }, BigDst{ dst_ptrs[pj[k].idx], ddst }, results[pj[k].idx], again);
+            rc = decode_big_single(c, pj[k], desc[pj[k].idx], BigSrc{ archive, false }, BigDst{ to == Dst::None ? nullptr : dst_ptrs[pj[k].idx], to }, results[pj[k].idx], again);
             if (rc == ZPK_OK && !again) is_big[pj[k].idx] = 1;
         }
         std::vector<u64> rest;
@@ -2017,8 +2074,8 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             std::vector<zpk_decode_desc> rd(rest.size());
             std::vector<uint8_t*> rp(rest.size());
             std::vector<zpk_decode_result> rr(rest.size());
-            for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = dst_ptrs[rest[k]]; }
-            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), ddst);
+            for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]]; }
+            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to);
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
@@ -2028,13 +2085,13 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
 int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                 uint8_t* const* dst_ptrs, zpk_decode_result* results)
 {
-    return decode_batch_host_any(c, archive, archive_size, desc, n, dst_ptrs, results, false);
+    return decode_batch_host_any(c, archive, archive_size, desc, n, dst_ptrs, results, Dst::Host);
 }
 
 int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                      uint8_t* const* d_dst_ptrs, zpk_decode_result* results)
 {
-    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, true);
+    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device);
 }
 
 int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_t n, void* stream)
@@ -2064,10 +2121,13 @@ struct StoredSpanRun {
     std::vector<u64> idx; const u64* h_hash = nullptr; hipStream_t st = nullptr;
     ~StoredSpanRun() { if (st) (void)hipStreamSynchronize(st); }
 };
+// hash_only (the batch has no destination): the entries have no slots — dst_size does not bound them, and k_xxh3_partials over the source
+// stands in for k_stored_span: the same sums in the same places without the copy; the chain behind them hashes from the source either way.
 static int stored_span_enqueue(zpk_codec* c, const u8* d_archive, u64 archive_size, const zpk_decode_desc* desc, u64 n, u8* d_dst, u64 dst_size,
-                               bool fork, StoredSpanRun& run)
+                               bool fork, StoredSpanRun& run, bool hash_only = false)
 {
     if (c->opt.stored_span_min == ~0ull) return ZPK_OK;
+    if (hash_only) dst_size = ~0ull;
     u64 k = 0;
     for (u64 i = 0; i < n; i++) k += stored_span_takes(desc[i], archive_size, dst_size, c->opt.stored_span_min) ? 1 : 0;
     if (k == 0) return ZPK_OK;
@@ -2093,7 +2153,8 @@ static int stored_span_enqueue(zpk_codec* c, const u8* d_archive, u64 archive_si
     run.h_hash = (const u64*)(h_sspan + up_bytes);
     run.st = st;
     HIPCHK(c, hipMemcpyAsync(c->sspan.d, h_sspan, up_bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_stored_span, dim3((u32)((plan.groups + 3) / 4)), dim3(256), 0, st, d_archive, d_dst, d_spans,
+    if (hash_only) hipLaunchKernelGGL(k_xxh3_partials, dim3((u32)((plan.groups + 3) / 4)), dim3(256), 0, st, d_archive, d_spans, (u32)plan.nspans, (u64)0, plan.groups, d_part);
+    else hipLaunchKernelGGL(k_stored_span, dim3((u32)((plan.groups + 3) / 4)), dim3(256), 0, st, d_archive, d_dst, d_spans,
                        (const u64*)(c->sspan.d + dst_at), (u32)plan.nspans, plan.groups, d_part);
     hipLaunchKernelGGL(k_xxh3_chain, dim3((u32)plan.nspans), dim3(64), 0, st, d_archive, d_spans, (const u64*)d_part, d_hash, (u64*)nullptr, (u64)0, ~(u64)0, 1);
     HIPCHK(c, hipGetLastError());
@@ -2117,7 +2178,7 @@ static int stored_span_finish(zpk_codec* c, StoredSpanRun& run, const zpk_decode
 // scattered to results[rest[k]]; returns when they are home.  No entry left while the stored spans took some: no work list held an entry
 // in this call, the counters say so.
 static int decode_rest_device(zpk_codec* c, const u8* d_archive, u64 archive_size, const zpk_decode_desc* desc, const u64* rest, u64 nr,
-                              u8* d_dst, u64 dst_size, zpk_decode_result* results)
+                              u8* d_dst, u64 dst_size, zpk_decode_result* results, bool hash_only = false)
 {
     if (nr == 0) {
         if (c->last.span[0]) { (void)hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(u32), c->stream); c->last.totals_valid = 0; }
@@ -2130,7 +2191,7 @@ static int decode_rest_device(zpk_codec* c, const u8* d_archive, u64 archive_siz
     if ((rc = grow(c, c->d_desc, nr * sizeof(zpk_decode_desc))) || (rc = grow(c, c->d_res, nr * sizeof(zpk_decode_result)))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_desc, rd.data(), nr * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream));
     if ((rc = decode_launch(c, BatchMethods{ -1, -1 }, d_archive, archive_size, d_archive, d_archive + archive_size, (const zpk_decode_desc*)c->d_desc, nr,
-                            d_dst, dst_size, (zpk_decode_result*)c->d_res, c->stream))) return rc;
+                            d_dst, dst_size, (zpk_decode_result*)c->d_res, c->stream, hash_only))) return rc;
     HIPCHK(c, hipMemcpyAsync(rr.data(), c->d_res, nr * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (u64 k = 0; k < nr; k++) results[rest[k]] = rr[k];
@@ -2168,7 +2229,7 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
             if (walk_single(h_src, d, 0, P)) {
                 zpk_decode_result r; memset(&r, 0, sizeof(r));
                 u8 redo = 1;
-                if ((rc = decode_big_single(c, P, d, BigSrc{ d_archive, true }, BigDst{ d_dst + d.dst_offset, true }, r, redo))) return rc;
+                if ((rc = decode_big_single(c, P, d, BigSrc{ d_archive, true }, BigDst{ d_dst + d.dst_offset, Dst::Device }, r, redo))) return rc;
                 if (!redo) { *result = r; done = true; }
             }
         }
@@ -2186,16 +2247,18 @@ int zpk_codec_decode_big_device(zpk_codec* c, const uint8_t* d_archive, uint64_t
 // every other entry — and every entry the block-parallel path does not finish — is decoded by the one-wave kernels in ONE launch over
 // their descriptors, exactly as zpk_codec_decode_batch_device would: every verdict other than OK / hash mismatch is theirs.
 // (the body: the caller holds the lock, has set the device and called begin_decode_call — zpk_codec_decode_batch_dimage runs it once per
-// sub-batch, with d_dst = the codec's own staging)
+// sub-batch, with d_dst = the codec's own staging; to = Dst::None there when the batch is only tested: the stored entries have no slot in
+// d_dst and are hashed where they lie, large ones chip-wide, everything else decodes into its slot as ever)
 static int decode_big_batch_body(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                 uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results)
+                                 uint8_t* d_dst, uint64_t dst_size, zpk_decode_result* results, Dst to = Dst::Device)
 {
+    const bool hash_only = to == Dst::None;
     int rc = ZPK_OK;
     StoredSpanRun span;                                                               // (declared in front of the try: it waits on every way out)
     try {
         // ---- the large stored entries: copy + XXH3 across the chip.  Serial form: on c->stream, in front of the walk.  Forked form: on a
         // second stream beside the walk, the block-parallel entries and the one-wave launch.
-        if ((rc = stored_span_enqueue(c, d_archive, archive_size, desc, n, d_dst, dst_size, ZPK_STORED_SPAN_FORK != 0, span))) return rc;
+        if ((rc = stored_span_enqueue(c, d_archive, archive_size, desc, n, d_dst, dst_size, ZPK_STORED_SPAN_FORK != 0, span, hash_only))) return rc;
         // ---- the candidates, walked where they lie: one launch over all of them, one copy home (records + tables), one synchronisation ----
         std::vector<u64> cand;
         for (u64 i = 0; i < n; i++) if (dec_big_candidate_device(desc[i], archive_size, dst_size, c->opt.dec_split_min)) cand.push_back(i);
@@ -2233,13 +2296,13 @@ static int decode_big_batch_body(zpk_codec* c, const uint8_t* d_archive, uint64_
             const zpk_decode_desc& d = desc[pj[k].idx];
             zpk_decode_result r; memset(&r, 0, sizeof(r));
             u8 again = 1;
-            if ((rc = decode_big_single(c, pj[k], d, BigSrc{ d_archive, true }, BigDst{ d_dst + d.dst_offset, true }, r, again))) return rc;
+            if ((rc = decode_big_single(c, pj[k], d, BigSrc{ d_archive, true }, BigDst{ d_dst + d.dst_offset, Dst::Device }, r, again))) return rc;
             if (!again) { results[pj[k].idx] = r; is_big[pj[k].idx] = 1; }
         }
         // ---- everything else through the one-wave kernels, one launch (every verdict is theirs) ----
         std::vector<u64> rest;
         for (u64 i = 0; i < n; i++) if (!is_big[i]) rest.push_back(i);
-        if ((rc = decode_rest_device(c, d_archive, archive_size, desc, rest.data(), rest.size(), d_dst, dst_size, results))) return rc;
+        if ((rc = decode_rest_device(c, d_archive, archive_size, desc, rest.data(), rest.size(), d_dst, dst_size, results, hash_only))) return rc;
         rc = stored_span_finish(c, span, desc, results);
     } catch (...) { rc = ZPK_E_NOMEM; }
     return rc;
@@ -2262,22 +2325,26 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
 // of their staging slots (dimage_cut), each runs the body of zpk_codec_decode_big_batch_device with d_dst = c->d_dst — the walk on the
 // device, dec_choose, the stored spans, one one-wave launch for the rest: the verdicts come from where they always came from — and
 // deliver_slots hands the slots over as the host path does: one k_span_copy to device pointers; the copy home and the scatter to host
-// pointers.  The compressed bytes never cross the bus.
-int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                  uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results)
+// pointers.  The compressed bytes never cross the bus.  (Dst::None — zpk_codec_verify_batch_dimage: the same sub-batches and the same body;
+// nothing is handed over, only descriptors go up and verdicts come home.)
+static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                   uint8_t* const* dst_ptrs, Dst to, zpk_decode_result* results)
 {
-    if (!c || (n && (!desc || !results || !dst_ptrs || !d_archive))) return ZPK_E_INVALID;
+    if (!c || (n && (!desc || !results || (!dst_ptrs && to != Dst::None) || !d_archive))) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
     c->last.dimage[0] = c->last.dimage[1] = c->last.dimage[2] = 0;
     if (n == 0) return ZPK_OK;
-    const bool ddst = dst_on_device != 0;
+    const bool ddst = to == Dst::Device, none = to == Dst::None;
     PtrRule rule(c);                                                                  // the pointer rule: before anything is enqueued
     if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
     if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
     begin_decode_call(c);
     const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
-    auto slot = [&](u64 i) { return dimage_slot(desc[i].method == ZPK_METHOD_NONE, desc[i].uncomp_size, desc[i].dst_capacity); };
+    auto slot = [&](u64 i) {                                                          // (no destination: a stored entry has no slot)
+        const bool stored = desc[i].method == ZPK_METHOD_NONE;
+        return none && stored ? 0ull : dimage_slot(stored, desc[i].uncomp_size, desc[i].dst_capacity);
+    };
     int rc = ZPK_OK;
     u64 home_total = 0;
     try {
@@ -2289,17 +2356,82 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
             for (u64 k = 0; k < cut.count; k++) hd[k] = span_copy_staged_desc(desc[first + k], desc[first + k].method == ZPK_METHOD_NONE, at[first + k]);      // (as in the host path)
             if (cut.out_total > ~0ull - 16) { snprintf(c->err, sizeof(c->err), "a staging slot of %llu bytes", (unsigned long long)cut.out_total); rc = ZPK_E_NOMEM; break; }
             if ((rc = grow(c, c->d_dst, cut.out_total + 16))) break;
-            if ((rc = decode_big_batch_body(c, d_archive, archive_size, hd.data(), cut.count, c->d_dst, cut.out_total, results + first))) break;
+            if ((rc = decode_big_batch_body(c, d_archive, archive_size, hd.data(), cut.count, c->d_dst, cut.out_total, results + first, none ? Dst::None : Dst::Device))) break;
             u64 home = 0;
-            if ((rc = deliver_slots(c, hd.data(), desc + first, cut.count, cut.out_total, dst_ptrs + first, results + first, ddst, &home))) break;
+            if ((rc = deliver_slots(c, hd.data(), desc + first, cut.count, cut.out_total, dst_ptrs ? dst_ptrs + first : nullptr, results + first, to, &home))) break;
             home_total = home > ~0ull - home_total ? ~0ull : home_total + home;
-            c->last.dimage[0]++;
+            c->last.dimage[0]++; c->last.subs++;
             first += cut.count;
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
     c->last.dimage[1] = c->last.sc;
     c->last.dimage[2] = home_total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)home_total;
     return rc;
+}
+
+int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                  uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results)
+{
+    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results);
+}
+
+// ---- a batch that is only TESTED: the verdicts of the two calls above without a destination (Dst::None) --------------------------------------
+// The descriptors as the routing sees them: dst_offset and dst_capacity of the caller's are ignored, the capacity counts as uncomp_size —
+// what an exact-size buffer gives, so BUFFER_TOO_SMALL cannot occur.
+static std::vector<zpk_decode_desc> verify_descs(const zpk_decode_desc* desc, u64 n)
+{
+    std::vector<zpk_decode_desc> vd(desc, desc + n);
+    for (zpk_decode_desc& d : vd) { d.dst_offset = 0; d.dst_capacity = d.uncomp_size; }
+    return vd;
+}
+// the stored entries that were hashed where they lay: those with a payload that passed every guard (OK or a hash mismatch is all that is left)
+static void verify_count_stored(zpk_codec* c, const zpk_decode_desc* desc, const zpk_decode_result* results, u64 n)
+{
+    u64 k = 0;
+    for (u64 i = 0; i < n; i++) k += desc[i].method == ZPK_METHOD_NONE && desc[i].comp_size != 0 && (results[i].status == DEC_R_OK || results[i].status == DEC_R_FILE_HASH_MISMATCH);
+    c->last.vstored = k > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)k;
+}
+
+int zpk_codec_verify_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                zpk_decode_result* results)
+{
+    if (!c || (n && (!desc || !results))) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    begin_decode_call(c);
+    if (n == 0) return ZPK_OK;
+    int rc;
+    try {
+        const std::vector<zpk_decode_desc> vd = verify_descs(desc, n);
+        rc = decode_batch_host_any(c, archive, archive_size, vd.data(), n, nullptr, results, Dst::None);
+        if (rc == ZPK_OK) verify_count_stored(c, vd.data(), results, n);
+    } catch (...) { rc = ZPK_E_NOMEM; }
+    return rc;
+}
+
+int zpk_codec_verify_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                  zpk_decode_result* results)
+{
+    if (!c || (n && (!desc || !results || !d_archive))) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    begin_decode_call(c);
+    if (n == 0) return ZPK_OK;
+    int rc;
+    try {
+        const std::vector<zpk_decode_desc> vd = verify_descs(desc, n);
+        rc = decode_batch_dimage_any(c, d_archive, archive_size, vd.data(), n, nullptr, Dst::None, results);
+        if (rc == ZPK_OK) verify_count_stored(c, vd.data(), results, n);
+    } catch (...) { rc = ZPK_E_NOMEM; }
+    return rc;
+}
+
+// the most recent of the two: out[0] sub-batches, out[1] stored entries hashed where they lay, out[2] plaintext bytes that came home
+// (saturating; 0: such a call brings none), out[3] 0
+int zpk_codec_verify_stats(zpk_codec* c, uint32_t out[4])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    out[0] = c->last.subs; out[1] = c->last.vstored; out[2] = c->last.home > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)c->last.home; out[3] = 0;
+    return ZPK_OK;
 }
 
 int zpk_codec_dimage_stats(zpk_codec* c, uint32_t out[4])

@@ -1,7 +1,7 @@
 """Archives read into and written from CUDA tensors: the plaintext stays in device memory, only compressed bytes cross the bus.
 
 A thin ctypes view of the three device-memory calls of libzpack_amd.so (include/zpack_amd.h: zpack_amd_read_files_device,
-zpack_amd_read_files_device_packed, zpack_amd_write_files_device), of the reader over an archive image in device memory
+zpack_amd_read_files_device_packed, zpack_amd_write_files_device), of the verdict-only read (zpack_amd_test_files), of the reader over an archive image in device memory
 (zpack_amd_init_reader_device) and of the writer whose sink is one (zpack_amd_init_writer_device), with torch for the memory.  There is no CPU fallback: without a HIP device the calls return
 ZPACK_ERROR_NOT_AVAILABLE and these functions raise.
 
@@ -9,6 +9,7 @@ ZPACK_ERROR_NOT_AVAILABLE and these functions raise.
     tensors, statuses = read_files_device(image)                          # ... of an archive that lies in a uint8 CUDA tensor
     write_files_device("weights.zpk", {"layer0": t0, "layer1": t1}, method=METHOD_LZ4, level=0)
     image = write_archive_device({"layer0": t0, "layer1": t1})            # the archive as a uint8 CUDA tensor: no compressed byte crosses the bus
+    statuses = test_files(image)                                          # every entry decoded and hashed on the device: verdicts, no tensor
 
 The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
 are ZPACK_ERROR_NOT_AVAILABLE.
@@ -71,6 +72,7 @@ def lib():
         L.zpack_close_reader.restype = None
         L.zpack_amd_read_files_device.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]
         L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
+        L.zpack_amd_test_files.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(C.c_int), vp]
         L.zpack_init_writer.argtypes = [W, C.c_char_p]
         L.zpack_init_writer_heap.argtypes = [W, C.c_size_t]
         L.zpack_amd_init_writer_device.argtypes = [W, vp, C.c_size_t]
@@ -98,15 +100,10 @@ def _check(rc, what):
                                                  if rc == NOT_AVAILABLE else ""))
 
 
-def read_files_device(archive, names=None, device=0):
-    """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
-    compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
-    in that order (None: all, in archive order).
-    Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
-    a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
+def _open_reader(L, r, archive, device):
+    """Opens `r` over `archive` — a path, the archive's bytes, or the image as a contiguous uint8 CUDA tensor — and returns the device the
+    call works with (the tensor's for an image); the caller closes the reader"""
     import torch
-    L = lib()
-    r = Reader()
     if isinstance(archive, torch.Tensor):
         if not (archive.is_cuda and archive.dtype == torch.uint8 and archive.dim() == 1 and archive.is_contiguous()):
             raise ValueError("an archive image in device memory is a contiguous one-dimensional uint8 CUDA tensor")
@@ -118,14 +115,52 @@ def read_files_device(archive, names=None, device=0):
     else:
         raw = bytes(archive)
         _check(L.zpack_init_reader_memory(C.byref(r), raw, len(raw)), "zpack_init_reader_memory")
+    return device
+
+
+def _picks(r, names):
+    """the entries `names` of an opened reader, in that order (None: all, in archive order), as indices into its table"""
+    if names is None:
+        return list(range(r.file_count))
+    first = {}
+    for i in range(r.file_count):
+        first.setdefault(r.file_entries[i].filename.decode(), i)
+    return [first[n] for n in names]                                                # KeyError: no such entry
+
+
+def test_files(archive, names=None, device=0):
+    """The verdicts of read_files_device without the tensors (zpack_amd_test_files): every entry is decoded and hashed on the device and
+    nothing but descriptors and results crosses the bus — for an image in device memory not even the compressed bytes.  `archive` and
+    `names` as in read_files_device; no tensor is allocated.  Returns the zpack_result of each entry (0 = decoded and its XXH3 verified)."""
+    L = lib()
+    r = Reader()
+    _open_reader(L, r, archive, device)
     try:
-        if names is None:
-            picks = list(range(r.file_count))
-        else:
-            first = {}
-            for i in range(r.file_count):
-                first.setdefault(r.file_entries[i].filename.decode(), i)
-            picks = [first[n] for n in names]                                       # KeyError: no such entry
+        picks = _picks(r, names)
+        n = len(picks)
+        ents = (C.POINTER(FileEntry) * max(n, 1))(*[C.pointer(r.file_entries[i]) for i in picks])
+        res = (C.c_int * max(n, 1))()
+        _check(L.zpack_amd_test_files(C.byref(r), ents, n, res, None), "zpack_amd_test_files")
+        return [int(res[i]) for i in range(n)]
+    finally:
+        L.zpack_close_reader(C.byref(r))
+
+
+test_files.__test__ = False                     # (a library function, not a test: pytest collects nothing here)
+
+
+def read_files_device(archive, names=None, device=0):
+    """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
+    compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
+    in that order (None: all, in archive order).
+    Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
+    a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
+    import torch
+    L = lib()
+    r = Reader()
+    device = _open_reader(L, r, archive, device)
+    try:
+        picks = _picks(r, names)
         n = len(picks)
         sizes = [int(r.file_entries[i].uncomp_size) for i in picks]
         starts, total = [], 0

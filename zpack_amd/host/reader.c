@@ -391,6 +391,10 @@ static void fill_desc(zpk_decode_desc* d, const zpack_file_entry* e, zpack_u64 s
     d->method = e->comp_method;
 }
 
+/* where the plaintext of a batch goes: the caller's host buffers, the caller's device buffers, or nowhere — the batch is only tested
+ * (zpack_amd_test_files: buffers and max_sizes are NULL, an entry's capacity counts as its uncomp_size) */
+enum { ZI_DST_HOST = 0, ZI_DST_DEVICE = 1, ZI_DST_NONE = 2 };
+
 typedef struct {
     zi_ctx* ctx; const zpack_u8* image; zpack_u64 image_size; const zpk_decode_desc* desc; zpack_u8* const* buffers;
     zpk_decode_result* res; zpack_u64 cut[ZI_MAX_DEVICES + 1]; int rc[ZI_MAX_DEVICES];
@@ -400,8 +404,13 @@ static void read_part(void* arg, int k)
 {
     read_job* j = (read_job*)arg;
     const zpack_u64 lo = j->cut[k], n = j->cut[k + 1] - lo;
-    j->rc[k] = n ? zpk_codec_decode_batch_host(j->ctx->dev[k], j->image, j->image_size, j->desc + lo, n, j->buffers + lo, j->res + lo) : ZPK_OK;
+    if (!n) j->rc[k] = ZPK_OK;
+    else if (!j->buffers) j->rc[k] = zpk_codec_verify_batch_host(j->ctx->dev[k], j->image, j->image_size, j->desc + lo, n, j->res + lo);
+    else j->rc[k] = zpk_codec_decode_batch_host(j->ctx->dev[k], j->image, j->image_size, j->desc + lo, n, j->buffers + lo, j->res + lo);
 }
+
+/* a test call says when the codec ran out of memory for its staging; a read reports every codec failure alike */
+static int test_rc_of_codec(int crc) { return crc == ZPK_E_NOMEM ? ZPACK_ERROR_MALLOC_FAILED : zi_rc_of_codec(crc); }
 
 static zpack_u64 entry_weight(const void* entries, zpack_u64 i)
 {
@@ -414,27 +423,31 @@ static zpack_u64 entry_weight(const void* entries, zpack_u64 i)
  * gather the payloads first (the reference mallocs + freads per entry, :336-344). */
 static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                           zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
-                          const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int on_device);
+                          const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int dest);
 
 int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                       zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                       const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size)
 {
-    return decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, span, span_lo, span_size, 0);
+    return decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, span, span_lo, span_size, ZI_DST_HOST);
 }
 
 int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                              zpack_u8* const* d_buffers, const size_t* max_sizes, zpk_decode_result* res)
 {
-    return decode_entries(reader, ctx, entries, count, d_buffers, max_sizes, res, NULL, 0, 0, 1);
+    return decode_entries(reader, ctx, entries, count, d_buffers, max_sizes, res, NULL, 0, 0, ZI_DST_DEVICE);
 }
 
-/* on_device: buffers[i] are DEVICE pointers — the plaintext stays there, only the compressed bytes cross the bus: the batch is one
- * zpk_codec_decode_batch_host_dptr call on the codec of the pointers' device (no shard: one call's pointers belong to one device) */
+/* ZI_DST_DEVICE: buffers[i] are DEVICE pointers — the plaintext stays there, only the compressed bytes cross the bus: the batch is one
+ * zpk_codec_decode_batch_host_dptr call on the codec of the pointers' device (no shard: one call's pointers belong to one device).
+ * ZI_DST_NONE: there are no buffers — the same descriptors, the same gather of a file reader's payloads and the same shard go to the
+ * codec's verify calls, and only verdicts come back */
 static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                           zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
-                          const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int on_device)
+                          const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int dest)
 {
+    const int on_device = dest == ZI_DST_DEVICE, none = dest == ZI_DST_NONE;
+#define ZI_CAP(i) (none ? (size_t)entries[i]->uncomp_size : max_sizes[i])
     if (count == 0) return ZPACK_OK;
     const zpack_u8* d_image = NULL;
     int d_device = -1;
@@ -450,7 +463,7 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
     if (span) {
         /* the caller staged archive bytes [span_lo, span_lo + span_size - 1) of entries that all pass the host guards, plus a
          * 1-byte pad: the same image as the gathered one below, payloads at their distances from each other */
-        for (zpack_u64 i = 0; i < count; i++) fill_desc(&desc[i], entries[i], entries[i]->offset - span_lo, max_sizes[i]);
+        for (zpack_u64 i = 0; i < count; i++) fill_desc(&desc[i], entries[i], entries[i]->offset - span_lo, ZI_CAP(i));
         image = span; image_size = span_size;
     } else if (reader->file) {
         /* pack the payloads of the entries that pass the reference's guards behind a 1-byte pad, so that
@@ -465,10 +478,10 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
             const zpack_file_entry* e = entries[i];
             if (e->comp_size && e->offset + e->comp_size < reader->file_size) {
                 rc = read_at(reader->file, e->offset, gathered + pos, (size_t)e->comp_size);
-                fill_desc(&desc[i], e, pos, max_sizes[i]);
+                fill_desc(&desc[i], e, pos, ZI_CAP(i));
                 pos += e->comp_size;
             } else {
-                fill_desc(&desc[i], e, total + 1, max_sizes[i]);                 /* fails the offset guard on the device */
+                fill_desc(&desc[i], e, total + 1, ZI_CAP(i));                 /* fails the offset guard on the device */
             }
         }
         gathered[pos] = 0;
@@ -477,13 +490,15 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
          * that order: the device checks comp_size==0, then max_size, then the offset — same as :328-332 */
     } else {
         /* a host image or one in device memory: the offset guard (:331) is evaluated against the image as it is */
-        for (zpack_u64 i = 0; i < count; i++) fill_desc(&desc[i], entries[i], entries[i]->offset, max_sizes[i]);
+        for (zpack_u64 i = 0; i < count; i++) fill_desc(&desc[i], entries[i], entries[i]->offset, ZI_CAP(i));
     }
     if (rc == ZPACK_OK && from == ZI_SRC_DEVICE && !span) {
         /* the IMAGE in device memory: the compressed bytes stay there — one zpk_codec_decode_batch_dimage call on the codec of the
          * image's device (no shard), the destinations host pointers or, on_device, device pointers on that device */
         zpk_codec* codec = zi_ctx_codec_on(ctx, d_device);
-        rc = codec ? zi_rc_of_codec(zpk_codec_decode_batch_dimage(codec, d_image, image_size, desc, count, buffers, on_device, res)) : ZPACK_ERROR_NOT_AVAILABLE;
+        if (!codec) rc = ZPACK_ERROR_NOT_AVAILABLE;
+        else if (none) rc = test_rc_of_codec(zpk_codec_verify_batch_dimage(codec, d_image, image_size, desc, count, res));
+        else rc = zi_rc_of_codec(zpk_codec_decode_batch_dimage(codec, d_image, image_size, desc, count, buffers, on_device, res));
     } else if (rc == ZPACK_OK && on_device) {
         zpk_codec* codec = zi_ctx_codec_of(ctx, buffers, sizeof(*buffers), max_sizes, sizeof(*max_sizes), sizeof(size_t) == 8, count, &rc);
         if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: verdicts only) */
@@ -494,14 +509,15 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
          * and one codec per device, nothing exchanged; results land in their own slices of res[] */
         const int parts = zi_shard(ctx, count, entry_weight, entries, job.cut);
         zi_parallel(parts, read_part, &job);
-        for (int k = 0; k < parts; k++) if (job.rc[k] != ZPK_OK) rc = ZPACK_ERROR_NOT_AVAILABLE;
+        for (int k = 0; k < parts; k++) if (job.rc[k] != ZPK_OK) rc = none && job.rc[k] == ZPK_E_NOMEM ? ZPACK_ERROR_MALLOC_FAILED : ZPACK_ERROR_NOT_AVAILABLE;
     }
+#undef ZI_CAP
     free(gathered); free(desc);
     return rc;
 }
 
 static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
-                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int on_device)
+                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int dest)
 {
     if (count == 0) return ZPACK_OK;
     if (zi_reader_source(reader, NULL, NULL) == ZI_SRC_NONE) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
@@ -510,7 +526,7 @@ static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zp
     if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
     zpk_decode_result* res = (zpk_decode_result*)calloc((size_t)count, sizeof(*res));
     if (!res) return ZPACK_ERROR_MALLOC_FAILED;
-    const int rc = decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0, on_device);
+    const int rc = decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0, dest);
     if (rc == ZPACK_OK)
         for (zpack_u64 i = 0; i < count; i++) {
             results[i] = res[i].status;
@@ -538,7 +554,7 @@ int zpack_read_file(zpack_reader* reader, zpack_file_entry* entry, zpack_u8* buf
     int result = ZPACK_OK;
     zpack_file_entry* one = entry;
     zpack_u8* out = buffer;
-    int rc = read_batch(reader, &one, 1, &out, &max_size, &result, ctx, 0);
+    int rc = read_batch(reader, &one, 1, &out, &max_size, &result, ctx, ZI_DST_HOST);
     return rc ? rc : result;
 }
 
@@ -546,7 +562,7 @@ int zpack_read_files(zpack_reader* reader, zpack_file_entry* const* entries, zpa
                      zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx)
 {
     if (!reader || (count && (!entries || !buffers || !max_sizes || !results))) return ZPACK_ERROR_STREAM_INVALID;
-    return read_batch(reader, entries, count, buffers, max_sizes, results, dctx, 0);
+    return read_batch(reader, entries, count, buffers, max_sizes, results, dctx, ZI_DST_HOST);
 }
 
 /* the packed reads: entry i lands at the running sum of the strides of the entries before it — its uncomp_size or, on_device, that
@@ -566,7 +582,7 @@ static int read_packed(zpack_reader* reader, zpack_file_entry* const* entries, z
         const zpack_u64 stride = on_device ? zpk_codec_packed_stride(entries[i]->uncomp_size) : entries[i]->uncomp_size;
         pos = on_device && stride > ~(zpack_u64)0 - pos ? ~(zpack_u64)0 : pos + stride;
     }
-    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx, on_device);
+    int rc = read_batch(reader, entries, count, bufs, caps, results, dctx, on_device ? ZI_DST_DEVICE : ZI_DST_HOST);
     free(bufs); free(caps);
     return rc;
 }
@@ -585,7 +601,7 @@ int zpack_amd_read_files_device(zpack_reader* reader, zpack_file_entry* const* e
 {
     if (!reader || (count && (!entries || !d_buffers || !max_sizes || !results))) return ZPACK_ERROR_STREAM_INVALID;
     if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
-    return read_batch(reader, entries, count, (zpack_u8* const*)d_buffers, max_sizes, results, dctx, 1);
+    return read_batch(reader, entries, count, (zpack_u8* const*)d_buffers, max_sizes, results, dctx, ZI_DST_DEVICE);
 }
 
 int zpack_amd_read_files_device_packed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
@@ -594,6 +610,16 @@ int zpack_amd_read_files_device_packed(zpack_reader* reader, zpack_file_entry* c
     if (!reader || (count && (!entries || !d_buffer || !out_offsets || !results))) return ZPACK_ERROR_STREAM_INVALID;
     if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;
     return read_packed(reader, entries, count, (zpack_u8*)d_buffer, buffer_size, out_offsets, results, dctx, 1);
+}
+
+/* ---- zpack_amd.h: the entries TESTED, no plaintext anywhere — read_batch without a destination: the same descriptors, the same shard,
+ * the same last_return rule; the codec's verify calls give the verdicts a read into zero-filled buffers of uncomp_size bytes gives */
+int zpack_amd_test_files(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count, int* results, void* dctx)
+{
+    if (!reader || (count && (!entries || !results))) return ZPACK_ERROR_STREAM_INVALID;
+    if (count == 0) return ZPACK_OK;
+    if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
+    return read_batch(reader, entries, count, NULL, NULL, results, dctx, ZI_DST_NONE);
 }
 
 static int zi_stream_replay(zpack_reader* reader, const zpack_file_entry* entry, zpk_dstream* d, zpack_u64 upto)

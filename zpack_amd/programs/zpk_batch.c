@@ -2,7 +2,8 @@
  *
  * The reference's CLI tests and extracts one entry at a time through the streaming reader
  * (programs/commands.c:706-773 command_test, :413-487 extract_files_i / :330-409 extract_file).  Here the same
- * two commands hand the codec whole batches — zpack_read_files_packed, up to ZPK_BATCH_BYTES of output per call —
+ * two commands hand the codec whole batches — up to ZPK_BATCH_BYTES of output per call: `x` through zpack_read_files_packed,
+ * `t` through zpack_amd_test_files, which brings the verdicts home and no plaintext (the cut still bounds the device staging) —
  * and print what the reference prints: the same lines, in the same entry order, with the same verdict per entry
  * (a hash mismatch is "corrupted" and the run goes on; for `t` any other error ends the run with status 1 at that
  * entry, for `x` it counts as an error and the run goes on).
@@ -18,6 +19,7 @@
 #include <string.h>
 #include <sys/stat.h>
 #include "zpack.h"
+#include "zpack_amd.h"
 
 #ifndef ZPK_BATCH_BYTES
 #define ZPK_BATCH_BYTES ((zpack_u64)1 << 30)
@@ -104,13 +106,14 @@ int main(int argc, char** argv)
             bytes += u; cnt++;
         }
         if (rc) break;
-        if (bytes > buf_cap) {
+        if (extract && bytes > buf_cap) {
             free(buf);
             buf = (zpack_u8*)malloc((size_t)bytes);
             buf_cap = buf ? (size_t)bytes : 0;
             if (!buf) { printf("Error: out of memory for a %" PRIu64 "-byte batch\n", bytes); rc = 1; break; }
         }
-        ret = zpack_read_files_packed(&reader, ptrs, cnt, buf, (size_t)bytes, offs, results, NULL);
+        ret = extract ? zpack_read_files_packed(&reader, ptrs, cnt, buf, (size_t)bytes, offs, results, NULL)
+                      : zpack_amd_test_files(&reader, ptrs, cnt, results, NULL);
         if (ret) { printf("Error: Failed to decompress the batch at \"%s\" (error %d)\n", ptrs[0]->filename, ret); rc = 1; break; }
         for (zpack_u64 k = 0; k < cnt; k++) {
             const zpack_file_entry* e = ptrs[k];
