@@ -55,6 +55,31 @@ ZPACK_EXPORT int zpack_amd_read_files_device_packed(zpack_reader* reader, zpack_
 /* zpack_write_files where files[i].buffer is a DEVICE pointer (files[i].size bytes) */
 ZPACK_EXPORT int zpack_amd_write_files_device(zpack_writer* writer, zpack_file* files, zpack_u64 file_count);
 
+/* ---- BYTE-PLANE entries: float tensors that compress ----------------------------------------------------------------------------------
+ * A float tensor alternates bytes that compress (sign and exponent) with bytes that are noise (mantissa); stored with byte 0 of every
+ * element first, then byte 1 of every element, and so on, the codecs gain on it (DESIGN.md section 10.5 has the figures).  For an entry of
+ * n bytes with element size k in {2, 4, 8} and m = n / k whole elements:
+ *     stored[p * m + j] = plain[j * k + p]   (0 <= p < k, 0 <= j < m),   stored[k * m + t] = plain[k * m + t] for the n - k * m tail bytes;
+ * k = 1 is the identity.  The two calls below are zpack_amd_write_files_device and zpack_amd_read_files_device with one element size per
+ * entry (host memory, file_count / count values): the grouping happens inside the copy that moves the plaintext between the caller's
+ * buffers and the codec's staging anyway, so it costs no further pass over the plaintext and no second copy of it.  The .zpk format does
+ * not change: a grouped entry is an ordinary entry whose plaintext is the grouped bytes, its hash is over those, any reader reads and
+ * verifies it (and gets the grouped bytes), zpack_amd_test_files works on it unchanged.  The element size is NOT in the archive: the
+ * caller hands the same value to both sides.  Every kind of writer (heap, file, device image) and reader (memory, file, device image).
+ *
+ * elem_sizes == NULL is zpack_amd_write_files_device / zpack_amd_read_files_device, the same code.
+ * A value outside {1, 2, 4, 8} is ZPACK_ERROR_STREAM_INVALID, checked before any context is created: nothing is written, no result is set.
+ * The written archive is byte for byte the one zpack_amd_write_files_device writes from device buffers that already hold the grouped
+ *   bytes; entries, hashes, offsets, write_offset and the return value when a file fails are equal too.
+ * results[i], the return value and reader->last_return are those of zpack_amd_read_files_device for the same entries.  The bytes in
+ *   d_buffers[i] are the JOIN of the bytes that call delivers when entry i decodes to all of its uncomp_size bytes (ZPACK_OK or
+ *   ZPACK_ERROR_FILE_HASH_MISMATCH); otherwise the buffer is untouched.
+ * Which device, stream ordering, read-ahead, bad pointers, no device: as for the calls beside them (above). */
+ZPACK_EXPORT int zpack_amd_write_files_device_planes(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, const zpack_u8* elem_sizes);
+ZPACK_EXPORT int zpack_amd_read_files_device_planes(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                                    void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
+                                                    int* results, void* dctx);
+
 /* ---- the archive IMAGE in DEVICE memory -------------------------------------------------------------------------------------------
  * A third kind of reader beside the memory-backed and the file-backed one: the archive lies in device memory — a data set or checkpoint
  * kept compressed in HBM, an archive that arrived by a device-to-device transfer — and its compressed bytes never cross the bus.

@@ -54,7 +54,9 @@ extern "C" {
                                         with the ARCHIVE IMAGE in the caller's device memory.
                                         zpk_codec_store_device, zpk_codec_encode_batch_dsink, zpk_codec_dsink_stats, zpk_codec_stream_sync: a batch compressed into a bounded SINK in the
                                         caller's device memory.
-                                        zpk_codec_verify_batch_host, zpk_codec_verify_batch_dimage, zpk_codec_verify_stats: a batch that is only TESTED, verdicts without plaintext.) */
+                                        zpk_codec_verify_batch_host, zpk_codec_verify_batch_dimage, zpk_codec_verify_stats: a batch that is only TESTED, verdicts without plaintext.
+                                        zpk_codec_plane_copy_device, the _planes forms of _encode_batch_dsrc, _encode_batch_dsink, _decode_batch_host_dptr and _decode_batch_dimage,
+                                        zpk_codec_planes_stats: byte-plane entries, split and joined in the copies.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -340,6 +342,46 @@ int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, i
 int zpk_codec_dsink_stats(zpk_codec* c, uint32_t out[4]);
 /* returns when everything enqueued on the codec's own stream has run (zpk_codec_copy_spans_device with stream NULL enqueues there) */
 int zpk_codec_stream_sync(zpk_codec* c);
+
+/* ---- BYTE-PLANE entries: float tensors that compress, split and joined in the copies (k_plane_copy) -------------------------------
+ * An entry of n bytes whose elements are k bytes wide (k in {2, 4, 8}; m = n / k whole elements) is STORED grouped by byte position:
+ *     stored[p * m + j] = plain[j * k + p]   (0 <= p < k, 0 <= j < m),   stored[k * m + t] = plain[k * m + t] for the n - k * m tail bytes;
+ * k = 1 is the identity.  The archive knows nothing of it: the grouped bytes are the entry's plaintext and its XXH3 is over them.  The
+ * transposition rides on the copies that move plaintext between the caller's DEVICE buffers and the codec's staging anyway: sources are
+ * SPLIT on the way in, decoded slots are JOINED on the way out — no further pass over the plaintext, no second copy of it.
+ *
+ * zpk_codec_plane_copy_device: the kernel on its own, as zpk_codec_copy_spans_device is k_span_copy's.  rows[0, n) is HOST memory, consumed
+ * before the call returns; src and dst are DEVICE addresses on the codec's device, any alignment, not overlapping; join 0 takes plain
+ * bytes at src to grouped bytes at dst, join 1 the reverse; elem 1 copies.  An element size outside {1, 2, 4, 8}, or a row that fails the
+ * pointer check of zpk_codec_decode_batch_host_dptr on either end (len 0 passes): ZPK_E_INVALID and nothing has run.  Asynchronous on
+ * `stream` (NULL = the codec's own). */
+typedef struct zpk_plane_copy { uint64_t src, dst, len; uint32_t elem, join; } zpk_plane_copy;
+int zpk_codec_plane_copy_device(zpk_codec* c, const zpk_plane_copy* rows, uint64_t n, void* stream);
+/* The calls whose plaintext lies in the caller's device memory, with one more argument: elem[i] is the element size of entry i (HOST
+ * memory, n values; NULL = every entry has element size 1, which IS the call without the suffix: the same body).  A value outside
+ * {1, 2, 4, 8}: ZPK_E_INVALID and nothing has run.  A batch in which every elem is 1 launches exactly what the plain call launches.
+ * Writing: the sources with elem > 1 reach the staging through k_plane_copy (split), the others through k_span_copy; everything behind
+ * the staging sees grouped bytes.  Host sources (_dsink with src_on_device 0) take no element size but 1.
+ * Reading: wherever a slot is handed to a device pointer, entries with elem > 1 go through k_plane_copy (join) — and only when the entry
+ * decoded to all of its uncomp_size bytes (status OK or a hash mismatch); for every other status nothing is written to its buffer.  A
+ * large frame that would decode straight into the caller's buffer decodes into the staging instead and is joined from there.  The
+ * results are the plain call's.  Host destinations (_dimage with dst_on_device 0) take no element size but 1. */
+int zpk_codec_encode_batch_dsrc_planes(zpk_codec* c, const uint8_t* const* d_src_ptrs,
+                                       const zpk_encode_desc* desc, uint64_t n,
+                                       uint8_t* const* dst_ptrs, zpk_encode_result* results, const uint8_t* elem);
+int zpk_codec_encode_batch_dsink_planes(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device,
+                                        const zpk_encode_desc* desc, uint64_t n,
+                                        uint8_t* d_sink, uint64_t sink_room,
+                                        zpk_encode_result* results, uint64_t* placed, uint64_t* bytes, const uint8_t* elem);
+int zpk_codec_decode_batch_host_dptr_planes(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
+                                            const zpk_decode_desc* desc, uint64_t n,
+                                            uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem);
+int zpk_codec_decode_batch_dimage_planes(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size,
+                                         const zpk_decode_desc* desc, uint64_t n,
+                                         uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem);
+/* the most recent of the calls above, or of the plain calls they extend: out[0] rows split, out[1] rows joined, out[2] k_plane_copy
+ * launches, out[3] entries that decoded into the staging only because they were grouped */
+int zpk_codec_planes_stats(zpk_codec* c, uint32_t out[4]);
 
 /* zpk_codec_encode_batch_device for batches that hold LARGE entries: d_src, d_dst and d_results are DEVICE pointers, `desc` is HOST memory
  * (consumed before the call returns).  An entry with size >= ZPK_OPT_ENC_SPLIT_MIN, size > 512 KiB and a valid method is compressed as

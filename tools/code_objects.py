@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The gfx950 code objects of two builds of libzpk_codec.so, compared: the bytes of .text and every defined FUNC / OBJECT symbol with
 its address, size, type and binding (the kernels, their .kd descriptors, the device variables).  A refactor of host code must leave
-both as they are.  Prints a markdown report; exit status 1 when anything differs.
+both as they are; a build that adds a .hip file behind the parent's must leave the parent's as they are (the added code objects are
+listed, not compared).  Prints a markdown report; exit status 1 when anything differs.
 
   python tools/code_objects.py PARENT/zpack_amd/libzpk_codec.so zpack_amd/libzpk_codec.so [--names zpk_codec.hip span_copy.hip ...]
 
@@ -65,7 +66,7 @@ def main():
         raise SystemExit(__doc__)
     with tempfile.TemporaryDirectory() as wa, tempfile.TemporaryDirectory() as wb:
         a, b = code_objects(args[0], wa), code_objects(args[1], wb)
-    same = len(a) == len(b)
+    same = len(a) <= len(b)                      # (a build may ADD code objects behind the parent's: those are listed, not compared)
     sha = lambda x: hashlib.sha256(x).hexdigest()[:16]
     print("| code object | .text bytes | .text sha256 (parent) | .text sha256 (this build) | symbols | symbol listing sha256 (parent) | (this build) |")
     print("|---|---|---|---|---|---|---|")
@@ -75,6 +76,9 @@ def main():
         same = same and ta == tb and sa == sb
         print("| %s | %d%s | `%s` | `%s` | %d%s | `%s` | `%s` |" % (names[k] if k < len(names) else "bundle %d" % k, len(ta), "" if len(ta) == len(tb) else " / %d" % len(tb),
                                                                  sha(ta), sha(tb), len(sa), "" if len(sa) == len(sb) else " / %d" % len(sb), sha(la), sha(lb)))
+    for k in range(len(a), len(b)):
+        tb, sb = b[k]
+        print("| %s (added) | %d | | `%s` | %d | | `%s` |" % (names[k] if k < len(names) else "bundle %d" % k, len(tb), sha(tb), len(sb), sha("\n".join(sb).encode())))
     print("\n(sha256 shortened to its first 16 hex digits.)\n")
     for k in range(min(len(a), len(b))):
         sa, sb = a[k][1], b[k][1]

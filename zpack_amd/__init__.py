@@ -31,6 +31,8 @@ ENCODE_DESC = np.dtype([("src_offset", "<u8"), ("size", "<u8"), ("dst_offset", "
 ENCODE_RESULT = np.dtype([("status", "<i4"), ("detail", "<u4"), ("comp_size", "<u8"), ("hash", "<u8")])
 assert DECODE_DESC.itemsize == 56 and DECODE_RESULT.itemsize == 24
 assert ENCODE_DESC.itemsize == 40 and ENCODE_RESULT.itemsize == 24
+PLANE_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u8"), ("elem", "<u4"), ("join", "<u4")])       # zpk_plane_copy
+assert PLANE_COPY.itemsize == 32
 
 _lib = None
 
@@ -71,6 +73,9 @@ def lib():
             L.zpk_codec_pointer_device.argtypes = [vp]
             L.zpk_codec_packed_stride.argtypes = [u64]
             L.zpk_codec_packed_stride.restype = u64
+        if hasattr(L, "zpk_codec_plane_copy_device"):         # (likewise: byte-plane entries)
+            L.zpk_codec_plane_copy_device.argtypes = [vp, vp, u64, vp]
+            L.zpk_codec_planes_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.zpk_codec_pack_batch_device.argtypes = [vp, u8p, vp, vp, u64, u8p, u64, vp, u64, vp]
         L.zpk_codec_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
         L.zpk_codec_compress_bound.restype = C.c_size_t
@@ -257,8 +262,14 @@ class Codec:
         return res, [o[:int(d["dst_capacity"])] for o, d in zip(outs, desc)]
 
     # ---- the plaintext in the caller's DEVICE memory (torch tensors; archive and tables host memory) ----
-    def decode_batch_host_dptr(self, archive, desc, dst_ptrs):
+    @staticmethod
+    def _elem(elem, n):
+        """the element sizes of a byte-plane call as the C array its last argument takes (None: NULL, the plain call)"""
+        return None if elem is None else (C.c_uint8 * max(n, 1))(*[int(k) for k in elem])
+
+    def decode_batch_host_dptr(self, archive, desc, dst_ptrs, elem=None):
         """decode_batch_host with device destinations: dst_ptrs[i] = device address of desc[i].dst_capacity bytes on this codec's device.
+        elem: one element size per entry — those above 1 are byte-plane entries, joined on the way (None: the plain call).
         Returns the results; raises on ZPK_E_INVALID (a pointer the check turned down: nothing has run)."""
         self._settle(None)
         arc = np.ascontiguousarray(np.frombuffer(archive, dtype=np.uint8) if not isinstance(archive, np.ndarray) else archive)
@@ -266,15 +277,21 @@ class Codec:
         n = len(desc)
         ptrs = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in dst_ptrs])
         res = np.zeros(n, dtype=DECODE_RESULT)
-        self._chk(self.L.zpk_codec_decode_batch_host_dptr(self.h, arc.ctypes.data, arc.size, desc.ctypes.data, n, ptrs, res.ctypes.data),
-                  "zpk_codec_decode_batch_host_dptr")
+        if elem is None:
+            self._chk(self.L.zpk_codec_decode_batch_host_dptr(self.h, arc.ctypes.data, arc.size, desc.ctypes.data, n, ptrs, res.ctypes.data),
+                      "zpk_codec_decode_batch_host_dptr")
+            return res
+        self.L.zpk_codec_decode_batch_host_dptr_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.L.zpk_codec_decode_batch_host_dptr_planes(self.h, arc.ctypes.data, arc.size, desc.ctypes.data, n, ptrs, res.ctypes.data, self._elem(elem, n)),
+                  "zpk_codec_decode_batch_host_dptr_planes")
         return res
 
     # ---- the ARCHIVE IMAGE in the caller's device memory (a uint8 CUDA tensor; the tables host memory) ----
-    def decode_batch_dimage(self, image, desc, dst_ptrs=None):
+    def decode_batch_dimage(self, image, desc, dst_ptrs=None, elem=None):
         """decode_batch_host / decode_batch_host_dptr with the archive in device memory.  dst_ptrs None: host destinations — returns
         (results, [output bytes]) like decode_batch_host; else dst_ptrs[i] = device address of desc[i].dst_capacity bytes on this codec's
-        device — returns the results.  Raises on ZPK_E_INVALID (a pointer the check turned down: nothing has run)."""
+        device — returns the results; elem: as in decode_batch_host_dptr.  Raises on ZPK_E_INVALID (a pointer the check turned down:
+        nothing has run)."""
         self._settle(None)
         desc = np.ascontiguousarray(desc, dtype=DECODE_DESC)
         n = len(desc)
@@ -285,8 +302,14 @@ class Codec:
             ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
         else:
             ptrs = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in dst_ptrs])
-        self._chk(self.L.zpk_codec_decode_batch_dimage(self.h, image.data_ptr(), image.numel(), desc.ctypes.data, n, ptrs,
-                                                       0 if dst_ptrs is None else 1, res.ctypes.data), "zpk_codec_decode_batch_dimage")
+        if elem is None:
+            self._chk(self.L.zpk_codec_decode_batch_dimage(self.h, image.data_ptr(), image.numel(), desc.ctypes.data, n, ptrs,
+                                                           0 if dst_ptrs is None else 1, res.ctypes.data), "zpk_codec_decode_batch_dimage")
+        else:
+            self.L.zpk_codec_decode_batch_dimage_planes.argtypes = self.L.zpk_codec_decode_batch_dimage.argtypes + [C.c_void_p]
+            self._chk(self.L.zpk_codec_decode_batch_dimage_planes(self.h, image.data_ptr(), image.numel(), desc.ctypes.data, n, ptrs,
+                                                                  0 if dst_ptrs is None else 1, res.ctypes.data, self._elem(elem, n)),
+                      "zpk_codec_decode_batch_dimage_planes")
         if dst_ptrs is None:
             return res, [o[:int(d["dst_capacity"])] for o, d in zip(outs, desc)]
         return res
@@ -328,10 +351,11 @@ class Codec:
         return dict(sub_batches=a[0], stored_hashed_in_place=a[1], bytes_copied_home=a[2])
 
     # ---- a bounded SINK in the caller's device memory (a uint8 CUDA tensor; sources host arrays or device addresses; the tables host memory) ----
-    def encode_batch_dsink(self, srcs, desc, sink, sink_offset=0, room=None, src_on_device=False):
+    def encode_batch_dsink(self, srcs, desc, sink, sink_offset=0, room=None, src_on_device=False, elem=None):
         """encode_batch_host / _dsrc whose payloads are committed back to back to sink[sink_offset, sink_offset + room) under the append
         rule (zpack_codec.h): srcs[i] is a np.uint8 array (host) or a device address (src_on_device) of desc[i].size bytes.  Returns
-        (results, placed, bytes).  Raises on ZPK_E_INVALID (a pointer the check turned down: nothing has run)."""
+        (results, placed, bytes).  elem (device sources): one element size per entry — those above 1 are split into byte planes on the
+        way into the staging (None: the plain call).  Raises on ZPK_E_INVALID (a pointer the check turned down: nothing has run)."""
         self._settle(None)
         desc = np.ascontiguousarray(desc, dtype=ENCODE_DESC)
         n = len(desc)
@@ -346,8 +370,14 @@ class Codec:
         placed, nbytes = C.c_uint64(0), C.c_uint64(0)
         self.L.zpk_codec_encode_batch_dsink.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        self._chk(self.L.zpk_codec_encode_batch_dsink(self.h, ptrs, 1 if src_on_device else 0, desc.ctypes.data, n, sink.data_ptr() + sink_offset, room,
-                                                      res.ctypes.data, C.byref(placed), C.byref(nbytes)), "zpk_codec_encode_batch_dsink")
+        if elem is None:
+            self._chk(self.L.zpk_codec_encode_batch_dsink(self.h, ptrs, 1 if src_on_device else 0, desc.ctypes.data, n, sink.data_ptr() + sink_offset, room,
+                                                          res.ctypes.data, C.byref(placed), C.byref(nbytes)), "zpk_codec_encode_batch_dsink")
+        else:
+            self.L.zpk_codec_encode_batch_dsink_planes.argtypes = self.L.zpk_codec_encode_batch_dsink.argtypes + [C.c_void_p]
+            self._chk(self.L.zpk_codec_encode_batch_dsink_planes(self.h, ptrs, 1 if src_on_device else 0, desc.ctypes.data, n, sink.data_ptr() + sink_offset, room,
+                                                                 res.ctypes.data, C.byref(placed), C.byref(nbytes), self._elem(elem, n)),
+                      "zpk_codec_encode_batch_dsink_planes")
         return res, placed.value, nbytes.value
 
     def dsink_stats(self):
@@ -364,6 +394,22 @@ class Codec:
         rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 3)
         self._chk(self.L.zpk_codec_copy_spans_device(self.h, rows.ctypes.data, len(rows), C.c_void_p(stream) if stream else None),
                   "zpk_codec_copy_spans_device")
+
+    def plane_copy_device(self, rows, stream=None):
+        """rows: PLANE_COPY array of (src address, dst address, len, elem, join): one k_plane_copy launch — join 0 groups the bytes of
+        elements of `elem` bytes into planes (include/zpack_codec.h states the layout), join 1 puts them back —, asynchronous on `stream`
+        (None: the codec's own; synchronise the device before reading the destinations)."""
+        self._settle(stream)
+        rows = np.ascontiguousarray(rows, dtype=PLANE_COPY)
+        self._chk(self.L.zpk_codec_plane_copy_device(self.h, rows.ctypes.data, len(rows), C.c_void_p(stream) if stream else None),
+                  "zpk_codec_plane_copy_device")
+
+    def planes_stats(self):
+        """The most recent call that could split or join byte planes: rows split, rows joined, k_plane_copy launches, entries that decoded
+        into the staging only because they were grouped."""
+        a = (C.c_uint32 * 4)()
+        self._chk(self.L.zpk_codec_planes_stats(self.h, a), "zpk_codec_planes_stats")
+        return dict(split=a[0], joined=a[1], launches=a[2], staged=a[3])
 
     def hash_host(self, data):
         a = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))

@@ -46,6 +46,9 @@
 // k_span_copy (span_copy.h) is compiled in a file of its own, span_copy.hip: this file's code object stays the one it was, kernel for
 // kernel at the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
 namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
+#include "plane_copy_plan.h"                     // byte-plane entries: the layout, the row table, items and launches of k_plane_copy (plain C++, likewise)
+// k_plane_copy (plane_copy.h) is compiled in plane_copy.hip, for the same reason
+namespace zpk { void plane_copy_launch(const PlaneCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
 // ... and so is k_stored_hash (stored_hash.h, stored_hash.hip): k_stored without the copy, for a batch that has no destination
 namespace zpk { void stored_hash_launch(const u8* src, const zpk_decode_desc* desc, zpk_decode_result* res, const u32* list, const u32* counters, u32 grid, hipStream_t st); }
 #include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
@@ -616,6 +619,21 @@ struct BatchMethods { int zstd, lz4; };
 // descriptors' capacity is uncomp_size (verify_descs), a stored entry has no staging slot and is hashed where it lies (k_stored_hash;
 // a large one: k_xxh3_partials over the source), and the tail of a short decode counts as zeros (rehash_short_entries).
 enum class Dst : int { Host = 0, Device = 1, None = 2 };
+// The element sizes of a batch whose plaintext lies in the caller's device memory (plane_copy_plan.h): elem[i] of entry i, none = every
+// entry is plain bytes (element size 1).  Handed down as an argument to whatever stages sources or delivers slots.
+struct Planes {
+    const u8* elem = nullptr;
+    u32 of(u64 i) const { return elem ? elem[i] : 1u; }
+    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr }; }
+    bool any() const { return elem != nullptr; }
+};
+// ZPK_E_INVALID: an element size that is none (plane_elem_valid), before anything is enqueued
+static int planes_check(zpk_codec* c, const u8* elem, u64 n);
+// what of a decoded entry is joined: all of it when all of it is there — status OK or a hash mismatch —, else nothing
+static inline u64 planes_join_len(const zpk_decode_desc& d, const zpk_decode_result& r)
+{
+    return (r.status == DEC_R_OK || r.status == DEC_R_FILE_HASH_MISMATCH) && r.produced == d.uncomp_size ? (u64)d.uncomp_size : 0ull;
+}
 // the staging slot of an entry under destination `to` (span_copy_plan.h states the layout for the two kinds that have one)
 static inline u64 staging_slot(Dst to, const zpk_decode_desc& d)
 {
@@ -637,6 +655,7 @@ struct LastCall {
     u32  vstored = 0;                            // zpk_codec_verify_batch_host / _dimage: stored entries hashed where they lay
     u32  dsink[2] = {0, 0};                      // zpk_codec_encode_batch_dsink: its sub-batches and the last grid of k_sink_place
     u32  enc_big[2] = {0, 0};                    // zpk_codec_encode_big_device: entries written in pieces, their pieces
+    u32  planes[4] = {0, 0, 0, 0};               // zpk_codec_planes_stats: rows split, rows joined, k_plane_copy launches, entries staged only because they were grouped
     int  fell_back_fused = 0;                    // the last decode batch could not get its sequence arena and ran the fused decoder only
     // the host-path pipeline decodes one call in several launches: their counters are brought back piece by piece and summed, so that
     // decode_stats / decode_stats2 describe the whole call (a retry or watchdog event in an early piece is not lost)
@@ -648,7 +667,7 @@ struct LastCall {
 // A growable pinned block (PinBuf) is regrown only while nothing on a stream still reads or writes it: a call that uses one drains the
 // stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk: hipStreamSynchronize behind the copy home; sspan.h: the
 // run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the block's next turn
-// (bigenc.h, sc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
+// (bigenc.h, sc.h, pc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
 struct zpk_codec {
     int device = 0;
     Stream stream;
@@ -731,6 +750,9 @@ struct zpk_codec {
     // plaintext in the caller's device memory (span_copy_plan.h / span_copy.h): the row table of k_span_copy, pinned going up — the event
     // says that the upload has run, the block is written again only behind it
     struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } sc;
+    // ... and the row table of k_plane_copy (plane_copy_plan.h / plane_copy.h), a block of its own under the same rule: a call with
+    // byte-plane entries fills both tables before either kernel has run
+    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } pc;
 
     // the encoder
     DevBuf<u64> d_seq;                           // sequence lists, one per workgroup
@@ -972,7 +994,56 @@ static int span_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
 }
+// The same for k_plane_copy: entry i the row row(i) (a zpk_plane_copy; no bytes: no row), through the codec's second pinned table.  The
+// element sizes have been checked by the caller (planes_check).
+template <class RowFn>
+static int plane_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
+{
+    u64 nz = 0;
+    for (u64 i = 0; i < n; i++) nz += row(i).len != 0;
+    if (nz == 0) return ZPK_OK;
+    if (nz > ZPK_PC_MAX_ROWS) return ZPK_E_INVALID;
+    if (c->pc.pending) { HIPCHK(c, hipEventSynchronize(c->pc.ev)); c->pc.pending = false; }             // the pinned block's last upload has run
+    if (c->pc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "plane copy: no event"); return ZPK_E_LAUNCH; }
+    if (!c->pc.h.grow(nz * sizeof(PlaneCopyRow))) { snprintf(c->err, sizeof(c->err), "plane copy: out of pinned memory"); return ZPK_E_NOMEM; }
+    int rc;
+    if ((rc = grow(c, c->pc.d, nz * sizeof(PlaneCopyRow)))) return rc;
+    PlaneCopyRow* const rows = (PlaneCopyRow*)c->pc.h.p;
+    PlaneCopyPlan p = { 0, 0 };
+    for (u64 i = 0; i < n; i++) {
+        const zpk_plane_copy s = row(i);
+        if (!plane_copy_emit(s.src, s.dst, s.len, s.elem, s.join, rows, p)) return ZPK_E_INVALID;
+        if (s.len) c->last.planes[s.join ? 1 : 0]++;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->pc.d, rows, p.nrows * sizeof(PlaneCopyRow), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->pc.ev, st));
+    c->pc.pending = true;
+    const u64 nl = plane_copy_launches(p.items);
+    for (u64 j = 0; j < nl; j++) {
+        const PlaneCopyLaunch L = plane_copy_launch(p.items, j);
+        plane_copy_launch((const PlaneCopyRow*)(const u8*)c->pc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
+        c->last.planes[2]++;
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZPK_OK;
+}
+// The spans row(i) of a batch with element sizes `pl`, all of one direction: those of element size 1 in ONE k_span_copy as ever, the
+// others in ONE k_plane_copy (join: PLANE_SPLIT / PLANE_JOIN).  No element sizes: span_copy_enqueue and nothing else.
+template <class RowFn>
+static int rows_enqueue(zpk_codec* c, u64 n, RowFn row, const Planes& pl, u32 join, hipStream_t st)
+{
+    if (!pl.any()) return span_copy_enqueue(c, n, row, st);
+    int rc = span_copy_enqueue(c, n, [&](u64 i) { zpk_span_copy s = row(i); if (pl.of(i) > 1) s.len = 0; return s; }, st);
+    if (rc) return rc;
+    return plane_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u32 k = pl.of(i); return zpk_plane_copy{ s.src, s.dst, k > 1 ? s.len : 0ull, k, join }; }, st);
+}
 }  // extern "C++"
+static int planes_check(zpk_codec* c, const u8* elem, u64 n)
+{
+    for (u64 i = 0; elem && i < n; i++)
+        if (!plane_elem_valid(elem[i])) { snprintf(c->err, sizeof(c->err), "entry %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)elem[i]); return ZPK_E_INVALID; }
+    return ZPK_OK;
+}
 
 // XXH3-64 of `nspans` long spans of `base` (xxh3_span.h): enqueues the upload of the span list and the two kernels; the hashes stay on
 // the device, *d_hash_out says where (inside c->d_xpart, valid until the next call that hashes spans).  `h_spans` must stay as it is
@@ -1365,13 +1436,15 @@ static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t*
 }
 
 // The sources of a sub-batch into the staging c->d_src[0, in_total), entry i at off(i) with len(i) bytes (encode_batch_host_any, dsink_sub):
-// DEVICE sources by ONE launch of k_span_copy, a single host source as it is, several gathered through the pinned buffers (h2d_gather).
+// DEVICE sources by ONE launch of k_span_copy (byte-plane entries: rows_enqueue), a single host source as it is, several gathered through the pinned buffers (h2d_gather).
 // `e` as h2d_gather leaves it: the caller's table upload follows it and reports both.
 template <class OffFn, class LenFn>
-static int stage_sources(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, u64 n, OffFn off, LenFn len, u64 in_total, hipStream_t st, hipError_t& e)
+static int stage_sources(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, u64 n, OffFn off, LenFn len, u64 in_total, hipStream_t st, hipError_t& e,
+                         const Planes& pl = Planes())
 {
     e = hipSuccess;
-    if (dsrc) return span_copy_enqueue(c, n, [&](u64 i) { return zpk_span_copy{ (u64)src_ptrs[i], (u64)(c->d_src + off(i)), len(i) }; }, st);
+    // (device sources with element sizes: those above 1 are SPLIT on the way, by ONE k_plane_copy — the staging holds the grouped bytes)
+    if (dsrc) return rows_enqueue(c, n, [&](u64 i) { return zpk_span_copy{ (u64)src_ptrs[i], (u64)(c->d_src + off(i)), len(i) }; }, pl, PLANE_SPLIT, st);
     if (n == 1) { if (len(0)) e = hipMemcpyAsync(c->d_src, src_ptrs[0], len(0), hipMemcpyHostToDevice, st); return ZPK_OK; }
     return h2d_gather(c, c->d_src, in_total, n, src_ptrs, off, len, e, st);
 }
@@ -1382,9 +1455,10 @@ static int stage_sources(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc
 #define ZPK_SRC_SLACK 192u
 #define ZPK_SRC_READ_SLACK 128u
 static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
-                         zpk_decode_result* results, Dst to, u64* home = nullptr);
+                         zpk_decode_result* results, Dst to, u64* home = nullptr, const Planes& pl = Planes());
 static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
-                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, BatchMethods holds, Dst to = Dst::Host)
+                             const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results, BatchMethods holds, Dst to = Dst::Host,
+                             const Planes& pl = Planes())
 {
     int rc;
     if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
@@ -1402,7 +1476,7 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
     e = hipMemcpyAsync(results, c->d_res, n * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "decode: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    return deliver_slots(c, hd, desc, n, out_total, dst_ptrs, results, to);
+    return deliver_slots(c, hd, desc, n, out_total, dst_ptrs, results, to, nullptr, pl);
 }
 
 // The slots of a decoded sub-batch, c->d_dst + hd[i].dst_offset, handed to the caller (decode_host_chunk; zpk_codec_decode_batch_dimage):
@@ -1410,7 +1484,7 @@ static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 
 // max_size costs device address space, not PCIe time.  results[0, n) are home and the decode has completed.  *home: the bytes that
 // crossed the bus for it.  Dst::None: nothing is handed over — no copy, no k_span_copy; only the short decodes are looked at.
 static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
-                         zpk_decode_result* results, Dst to, u64* home)
+                         zpk_decode_result* results, Dst to, u64* home, const Planes& pl)
 {
     int rc;
     hipError_t e = hipSuccess;
@@ -1423,7 +1497,9 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
     if (to == Dst::None) return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to);
     if (to == Dst::Device) {
         // DEVICE destinations: the same bytes — [slot, slot + produced) of every entry — by ONE launch of k_span_copy, no host in between
-        if ((rc = span_copy_enqueue(c, n, [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], results[i].produced }; }, c->stream))) return rc;
+        // (an entry with an element size above 1 is JOINED on the way, all of it or none: planes_join_len)
+        auto row = [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.of(i) > 1 ? planes_join_len(desc[i], results[i]) : (u64)results[i].produced }; };
+        if ((rc = rows_enqueue(c, n, row, pl, PLANE_JOIN, c->stream))) return rc;
         e = hipStreamSynchronize(c->stream);
     } else if (n > 1 && produced_total && produced_total * 2 >= out_total) {
         // dense: the slots come back in pieces of ZPK_PIN_CHUNK bytes through two PINNED staging buffers — piece j + 1 is on the bus
@@ -1460,7 +1536,7 @@ struct HostPiece { u64 e0, e1, clo, chi, olo, ohi; };
 
 static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
                                  const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results,
-                                 bool& taken, BatchMethods holds, Dst to = Dst::Host)
+                                 bool& taken, BatchMethods holds, Dst to = Dst::Host, const Planes& pl = Planes())
 {
     // Dst::None: stage 1 (the upload) still runs beside stage 2 (the decode); there is no stage 3 — no download stream, no `decoded`
     // events — and the verdicts come home in one copy behind the last piece
@@ -1572,10 +1648,10 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             if (e == hipSuccess) e = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->pipe.s_dn);
             if (e == hipSuccess) e = hipStreamSynchronize(c->pipe.s_dn);
             if (e != hipSuccess) break;
-            rc = span_copy_enqueue(c, P.e1 - P.e0, [&](u64 k2) {
+            rc = rows_enqueue(c, P.e1 - P.e0, [&](u64 k2) {
                 const u64 i = P.e0 + k2, p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
-                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], p };
-            }, c->pipe.s_dn);
+                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.of(i) > 1 ? planes_join_len(desc[i], results[i]) : p };
+            }, pl.from(P.e0), PLANE_JOIN, c->pipe.s_dn);
         }
     } else
     rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; },
@@ -1838,7 +1914,8 @@ static int decode_big_zstd_single(zpk_codec* c, const BigSrc& src, const zpk_dec
 // Dst::None: nothing is handed over.  A group of STORED entries (the caller keeps the kinds apart then) is not cut into pieces and gets
 // no slots at all: its staged payloads are hashed where they lie, the partial sums and the chain over c->d_src.
 static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_desc* desc, const BigEntry* be, u64 g0, u64 g1,
-                            const std::vector<BigSub>& subs, uint8_t* const* dst_ptrs, zpk_decode_result* results, u8* redo, Dst to = Dst::Host)
+                            const std::vector<BigSub>& subs, uint8_t* const* dst_ptrs, zpk_decode_result* results, u8* redo, Dst to = Dst::Host,
+                            const Planes& pl = Planes())
 {
     const u64 ng = g1 - g0;
     const bool src_only = to == Dst::None && desc[be[g0].idx].method == ZPK_METHOD_NONE;
@@ -1903,7 +1980,9 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     if (to == Dst::None) return ZPK_OK;                                                // no destination: the verdicts were all
     if (to == Dst::Device) {                                                           // DEVICE destinations: one launch of k_span_copy
         auto row = [&](u64 k) { return zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size }; };
-        if ((rc = span_copy_enqueue(c, ng, row, c->stream))) return rc;
+        std::vector<u8> gelem;                                                         // (the group's element sizes, in its own order)
+        if (pl.any()) { gelem.resize(ng); for (u64 k = 0; k < ng; k++) gelem[k] = (u8)pl.of(be[g0 + k].idx); }
+        if ((rc = rows_enqueue(c, ng, row, Planes{ pl.any() ? gelem.data() : nullptr }, PLANE_JOIN, c->stream))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ZPK_OK;
     }
@@ -1946,10 +2025,10 @@ static int decode_big_single(zpk_codec* c, PjEntry& P, const zpk_decode_desc& d,
 }
 
 // the counts decode_stats2 reports of the most recent decode call: none yet
-static void begin_decode_call(zpk_codec* c) { LastCall& l = c->last; l.big[0] = l.big[1] = 0; l.walk[0] = l.walk[1] = 0; l.span[0] = l.span[1] = 0; l.pipe = l.sc = 0; l.subs = 0; l.home = 0; l.vstored = 0; }
+static void begin_decode_call(zpk_codec* c) { LastCall& l = c->last; l.planes[0] = l.planes[1] = l.planes[2] = l.planes[3] = 0; l.big[0] = l.big[1] = 0; l.walk[0] = l.walk[1] = 0; l.span[0] = l.span[1] = 0; l.pipe = l.sc = 0; l.subs = 0; l.home = 0; l.vstored = 0; }
 
 static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                   uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to = Dst::Host)
+                                   uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to = Dst::Host, const Planes& pl = Planes())
 {
     if (n == 0) return ZPK_OK;
     // (no destination: the sub-batches are cut by ZPK_OPT_DIMAGE_CHUNK, as those of a device image are — a caller can force several cheaply)
@@ -1996,9 +2075,9 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
         bool piped = false;
         uint8_t* const* const sub_ptrs = dst_ptrs ? dst_ptrs + first : nullptr;
         c->last.subs++;
-        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, piped, holds, to);
+        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, piped, holds, to, pl.from(first));
         if (rc == ZPK_OK && !piped)
-            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, holds, to);
+            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, holds, to, pl.from(first));
         first += cnt;
     }
     free(gathered);
@@ -2009,13 +2088,14 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
 // zpk_codec_decode_batch_host, zpk_codec_decode_batch_host_dptr and zpk_codec_verify_batch_host: one routing, the destinations host
 // memory, device memory or none (Dst)
 static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                 uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to)
+                                 uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to, const Planes& pl = Planes())
 {
     const bool ddst = to == Dst::Device;
     if (!c || (n && (!desc || !results || (!dst_ptrs && to != Dst::None)))) return ZPK_E_INVALID;
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
+    if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
     // the pointer rule (PtrRule): before anything is enqueued
     if (ddst && PtrRule(c).batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
     begin_decode_call(c);
@@ -2048,7 +2128,7 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             }
         } catch (...) { be.clear(); subs.clear(); pj.clear(); }                       // out of host memory for the plan: the usual path
     }
-    if (be.empty() && pj.empty()) return decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results, to);
+    if (be.empty() && pj.empty()) return decode_batch_host_plain(c, archive, archive_size, desc, n, dst_ptrs, results, to, pl);
     int rc = ZPK_OK;
     try {
         std::vector<u8> redo(be.size(), 0), is_big(n, 0);
@@ -2057,7 +2137,7 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             // (no destination: stored entries and compressed ones in groups of their own — the stored ones are hashed in the staged source)
             auto same_kind = [&](u64 g) { return to != Dst::None || (desc[be[g].idx].method == ZPK_METHOD_NONE) == (desc[be[g0].idx].method == ZPK_METHOD_NONE); };
             while (g1 < be.size() && (g1 == g0 || (same_kind(g1) && out + desc[be[g1].idx].uncomp_size <= ZPK_HOST_CHUNK_BYTES))) { out += (desc[be[g1].idx].uncomp_size + 255) & ~255ull; g1++; }
-            rc = decode_big_group(c, archive, desc, be.data(), g0, g1, subs, dst_ptrs, results, redo.data(), to);
+            rc = decode_big_group(c, archive, desc, be.data(), g0, g1, subs, dst_ptrs, results, redo.data(), to, pl);
             g0 = g1;
         }
         // ---- everything else, and the entries a frame of which did not decode, through the usual path ----
@@ -2065,8 +2145,17 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
         pj_choose(desc, n, pj);
         for (u64 k = 0; k < pj.size() && rc == ZPK_OK; k++) {                         // one large frame at a time: each fills the chip
             u8 again = 1;
-            rc = decode_big_single(c, pj[k], desc[pj[k].idx], BigSrc{ archive, false }, BigDst{ to == Dst::None ? nullptr : dst_ptrs[pj[k].idx], to }, results[pj[k].idx], again);
-            if (rc == ZPK_OK && !again) is_big[pj[k].idx] = 1;
+            const u64 idx = pj[k].idx;
+            // a device destination is decoded into straight away — unless the entry has an element size above 1: that one decodes into the
+            // staging, as an entry without a destination does, and is JOINED from there
+            const bool grouped = ddst && pl.of(idx) > 1;
+            rc = decode_big_single(c, pj[k], desc[idx], BigSrc{ archive, false }, grouped ? BigDst{ nullptr, Dst::None } : BigDst{ to == Dst::None ? nullptr : dst_ptrs[idx], to }, results[idx], again);
+            if (rc == ZPK_OK && !again && grouped) {
+                c->last.planes[3]++;
+                const zpk_plane_copy row = { (u64)(u8*)c->d_dst, (u64)dst_ptrs[idx], planes_join_len(desc[idx], results[idx]), pl.of(idx), PLANE_JOIN };
+                if ((rc = plane_copy_enqueue(c, 1, [&](u64) { return row; }, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
+            }
+            if (rc == ZPK_OK && !again) is_big[idx] = 1;
         }
         std::vector<u64> rest;
         for (u64 i = 0; i < n; i++) if (!is_big[i]) rest.push_back(i);
@@ -2074,8 +2163,9 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             std::vector<zpk_decode_desc> rd(rest.size());
             std::vector<uint8_t*> rp(rest.size());
             std::vector<zpk_decode_result> rr(rest.size());
-            for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]]; }
-            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to);
+            std::vector<u8> re(pl.any() ? rest.size() : 0);
+            for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]]; if (pl.any()) re[k] = (u8)pl.of(rest[k]); }
+            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to, Planes{ pl.any() ? re.data() : nullptr });
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
@@ -2094,6 +2184,12 @@ int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint6
     return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device);
 }
 
+int zpk_codec_decode_batch_host_dptr_planes(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                            uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem)
+{
+    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem });
+}
+
 int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_t n, void* stream)
 {
     if (!c || (n && !rows)) return ZPK_E_INVALID;
@@ -2105,6 +2201,33 @@ int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_
     if (rule.batch("span source", n, [&](u64 i) { return (const void*)rows[i].src; }, len) ||
         rule.batch("span destination", n, [&](u64 i) { return (const void*)rows[i].dst; }, len)) return ZPK_E_INVALID;
     return span_copy_enqueue(c, n, [&](u64 i) { return rows[i]; }, stream ? (hipStream_t)stream : c->stream);
+}
+
+// rows of k_plane_copy on their own: element size, direction and both ends per row; the pointer rule on both ends of every row
+int zpk_codec_plane_copy_device(zpk_codec* c, const zpk_plane_copy* rows, uint64_t n, void* stream)
+{
+    if (!c || (n && !rows)) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    c->last.planes[0] = c->last.planes[1] = c->last.planes[2] = c->last.planes[3] = 0;
+    if (n == 0) return ZPK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (u64 i = 0; i < n; i++)
+        if (!plane_elem_valid(rows[i].elem)) { snprintf(c->err, sizeof(c->err), "row %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
+    PtrRule rule(c);
+    auto len = [&](u64 i) { return (u64)rows[i].len; };
+    if (rule.batch("plane source", n, [&](u64 i) { return (const void*)rows[i].src; }, len) ||
+        rule.batch("plane destination", n, [&](u64 i) { return (const void*)rows[i].dst; }, len)) return ZPK_E_INVALID;
+    return plane_copy_enqueue(c, n, [&](u64 i) { return rows[i]; }, stream ? (hipStream_t)stream : c->stream);
+}
+
+// the most recent call that could split or join: out[0] rows split, out[1] rows joined, out[2] k_plane_copy launches, out[3] entries that
+// decoded into the staging only because they were grouped
+int zpk_codec_planes_stats(zpk_codec* c, uint32_t out[4])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    for (int k = 0; k < 4; k++) out[k] = c->last.planes[k];
+    return ZPK_OK;
 }
 
 uint64_t zpk_codec_packed_stride(uint64_t uncomp_size) { return span_copy_packed_stride(uncomp_size); }
@@ -2328,13 +2451,14 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
 // pointers.  The compressed bytes never cross the bus.  (Dst::None — zpk_codec_verify_batch_dimage: the same sub-batches and the same body;
 // nothing is handed over, only descriptors go up and verdicts come home.)
 static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                   uint8_t* const* dst_ptrs, Dst to, zpk_decode_result* results)
+                                   uint8_t* const* dst_ptrs, Dst to, zpk_decode_result* results, const Planes& pl = Planes())
 {
     if (!c || (n && (!desc || !results || (!dst_ptrs && to != Dst::None) || !d_archive))) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
     c->last.dimage[0] = c->last.dimage[1] = c->last.dimage[2] = 0;
     if (n == 0) return ZPK_OK;
+    if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
     const bool ddst = to == Dst::Device, none = to == Dst::None;
     PtrRule rule(c);                                                                  // the pointer rule: before anything is enqueued
     if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
@@ -2358,7 +2482,7 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
             if ((rc = grow(c, c->d_dst, cut.out_total + 16))) break;
             if ((rc = decode_big_batch_body(c, d_archive, archive_size, hd.data(), cut.count, c->d_dst, cut.out_total, results + first, none ? Dst::None : Dst::Device))) break;
             u64 home = 0;
-            if ((rc = deliver_slots(c, hd.data(), desc + first, cut.count, cut.out_total, dst_ptrs ? dst_ptrs + first : nullptr, results + first, to, &home))) break;
+            if ((rc = deliver_slots(c, hd.data(), desc + first, cut.count, cut.out_total, dst_ptrs ? dst_ptrs + first : nullptr, results + first, to, &home, pl.from(first)))) break;
             home_total = home > ~0ull - home_total ? ~0ull : home_total + home;
             c->last.dimage[0]++; c->last.subs++;
             first += cut.count;
@@ -2373,6 +2497,14 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
                                   uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results)
 {
     return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results);
+}
+
+// (element sizes belong to DEVICE destinations: with host destinations every one of them has to be 1)
+int zpk_codec_decode_batch_dimage_planes(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                         uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem)
+{
+    if (!dst_on_device) for (u64 i = 0; elem && i < n; i++) if (elem[i] != 1) return ZPK_E_INVALID;
+    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results, Planes{ dst_on_device ? elem : nullptr });
 }
 
 // ---- a batch that is only TESTED: the verdicts of the two calls above without a destination (Dst::None) --------------------------------------

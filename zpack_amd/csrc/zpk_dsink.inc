@@ -22,7 +22,7 @@ static u32 sink_resident_groups(zpk_codec* c)
 // One sub-batch: desc[0, m) staged, encoded into slots of the codec's, scanned, cut against `room` and committed to d_sink; results[0, m)
 // and the cut come home in one copy.  Returns when the sink holds the bytes.
 static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, const zpk_encode_desc* desc, u64 m, u8* d_sink, u64 room,
-                     zpk_encode_result* results, SinkCut* cut)
+                     zpk_encode_result* results, SinkCut* cut, const Planes& pl)
 {
     std::vector<zpk_encode_desc> hd;
     std::vector<u64> slot_off;
@@ -47,7 +47,7 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
     hipStream_t st = c->stream;
     hipError_t e = hipSuccess;
     // the sources, as zpk_codec_encode_batch_host / _dsrc stage them (zpk_codec.hip, stage_sources)
-    if ((rc = stage_sources(c, src_ptrs, dsrc, m, [&](u64 i) { return (u64)hd[i].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, in_total, st, e))) return rc;
+    if ((rc = stage_sources(c, src_ptrs, dsrc, m, [&](u64 i) { return (u64)hd[i].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, in_total, st, e, pl))) return rc;
     u8* const tab = c->sink.d_tab;
     zpk_encode_result* const d_res = (zpk_encode_result*)tab;
     u64* const d_rec = (u64*)(tab + o_rec); u64* const d_off = (u64*)(tab + o_off); u64* const d_slot = (u64*)(tab + o_slot);
@@ -81,15 +81,21 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
 
 extern "C" {
 
-int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,
-                                 uint8_t* d_sink, uint64_t sink_room_bytes, zpk_encode_result* results, uint64_t* placed, uint64_t* bytes)
+// (elem: the element sizes of DEVICE sources, plane_copy_plan.h — NULL: every entry is plain bytes; host sources take no other)
+int zpk_codec_encode_batch_dsink_planes(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,
+                                        uint8_t* d_sink, uint64_t sink_room_bytes, zpk_encode_result* results, uint64_t* placed, uint64_t* bytes,
+                                        const uint8_t* elem)
 {
     if (!c || !placed || !bytes || (n && (!desc || !results || !src_ptrs))) return ZPK_E_INVALID;
     *placed = 0; *bytes = 0;
     CodecLock lk(c);
     c->last.dsink[0] = c->last.dsink[1] = 0;
+    c->last.planes[0] = c->last.planes[1] = c->last.planes[2] = c->last.planes[3] = 0;
     if (n == 0) return ZPK_OK;
     HIPCHK(c, hipSetDevice(c->device));
+    if (planes_check(c, elem, n)) return ZPK_E_INVALID;
+    for (u64 i = 0; elem && !src_on_device && i < n; i++) if (elem[i] != 1) { snprintf(c->err, sizeof(c->err), "source %llu: an element size of %u for host memory", (unsigned long long)i, (unsigned)elem[i]); return ZPK_E_INVALID; }
+    const Planes pl = { src_on_device ? elem : nullptr };
     // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued.  The sink and device sources lie inside one allocation each on
     // this device; a host source with bytes is not device memory (the host would read through such a pointer)
     PtrRule rule(c);
@@ -105,13 +111,19 @@ int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, i
     for (u64 first = 0; first < n && ch.open; ) {
         const DimageCut sub = dimage_cut(first, n, chunk, [&](u64 i) { return sink_slot(desc[i].dst_capacity); });
         SinkCut cut = { 0, 0 };
-        const int rc = dsink_sub(c, src_ptrs + first, src_on_device != 0, desc + first, sub.count, d_sink + ch.bytes, sink_room(sink_room_bytes, ch.bytes), results + first, &cut);
+        const int rc = dsink_sub(c, src_ptrs + first, src_on_device != 0, desc + first, sub.count, d_sink + ch.bytes, sink_room(sink_room_bytes, ch.bytes), results + first, &cut, pl.from(first));
         if (rc) { *placed = ch.placed; *bytes = ch.bytes; return rc; }
         sink_chain(ch, sub.count, cut);
         first += sub.count;
     }
     *placed = ch.placed; *bytes = ch.bytes;
     return ZPK_OK;
+}
+
+int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,
+                                 uint8_t* d_sink, uint64_t sink_room_bytes, zpk_encode_result* results, uint64_t* placed, uint64_t* bytes)
+{
+    return zpk_codec_encode_batch_dsink_planes(c, src_ptrs, src_on_device, desc, n, d_sink, sink_room_bytes, results, placed, bytes, nullptr);
 }
 
 // waits for what the codec's own stream holds (zpk_codec_copy_spans_device enqueues there and returns)

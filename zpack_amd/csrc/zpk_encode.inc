@@ -1594,12 +1594,14 @@ extern "C" {
 // is that of the whole plaintext (the two kernels of xxh3_span.h).
 // (dsrc: zpk_codec_encode_batch_dsrc — src_ptrs are DEVICE pointers, gathered into the same staging by one launch of k_span_copy)
 static int encode_batch_host_any(zpk_codec* c, const uint8_t* const* src_ptrs, const zpk_encode_desc* desc, uint64_t n,
-                                 uint8_t* const* dst_ptrs, zpk_encode_result* results, bool dsrc)
+                                 uint8_t* const* dst_ptrs, zpk_encode_result* results, bool dsrc, const Planes& pl = Planes())
 {
     if (!c || (n && (!desc || !results || !src_ptrs || !dst_ptrs))) return ZPK_E_INVALID;
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
+    c->last.planes[0] = c->last.planes[1] = c->last.planes[2] = c->last.planes[3] = 0;
     HIPCHK(c, hipSetDevice(c->device));
+    if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
     // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued
     if (dsrc && PtrRule(c).batch("source", n, [&](u64 i) { return src_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].size; })) return ZPK_E_INVALID;
     const u64 split_min = c->opt.enc_split_min;
@@ -1636,7 +1638,7 @@ static int encode_batch_host_any(zpk_codec* c, const uint8_t* const* src_ptrs, c
         (rc = grow(c, c->d_res, np * sizeof(zpk_encode_result)))) return rc;
     hipError_t e = hipSuccess;
     // the sources go up, entry i to its place in the staging, hd[first[i]].src_offset (zpk_codec.hip, stage_sources)
-    if ((rc = stage_sources(c, src_ptrs, dsrc, n, [&](u64 i) { return (u64)hd[first[i]].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, in_total, c->stream, e))) return rc;
+    if ((rc = stage_sources(c, src_ptrs, dsrc, n, [&](u64 i) { return (u64)hd[first[i]].src_offset; }, [&](u64 i) { return (u64)desc[i].size; }, in_total, c->stream, e, pl))) return rc;
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_desc, hd, np * sizeof(zpk_encode_desc), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     rc = zpk_codec_encode_batch_device(c, c->d_src, in_total, (const zpk_encode_desc*)c->d_desc, np, c->d_dst, out_total,
@@ -1691,6 +1693,13 @@ int zpk_codec_encode_batch_dsrc(zpk_codec* c, const uint8_t* const* d_src_ptrs, 
                                 uint8_t* const* dst_ptrs, zpk_encode_result* results)
 {
     return encode_batch_host_any(c, d_src_ptrs, desc, n, dst_ptrs, results, true);
+}
+
+// ... whose entry i has elements of elem[i] bytes (plane_copy_plan.h): the staging, and with it everything behind it, holds the grouped bytes
+int zpk_codec_encode_batch_dsrc_planes(zpk_codec* c, const uint8_t* const* d_src_ptrs, const zpk_encode_desc* desc, uint64_t n,
+                                       uint8_t* const* dst_ptrs, zpk_encode_result* results, const uint8_t* elem)
+{
+    return encode_batch_host_any(c, d_src_ptrs, desc, n, dst_ptrs, results, true, Planes{ elem });
 }
 
 }  // extern "C"

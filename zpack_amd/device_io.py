@@ -10,6 +10,15 @@ ZPACK_ERROR_NOT_AVAILABLE and these functions raise.
     write_files_device("weights.zpk", {"layer0": t0, "layer1": t1}, method=METHOD_LZ4, level=0)
     image = write_archive_device({"layer0": t0, "layer1": t1})            # the archive as a uint8 CUDA tensor: no compressed byte crosses the bus
     statuses = test_files(image)                                          # every entry decoded and hashed on the device: verdicts, no tensor
+    image = write_archive_device({"layer0": t0, ...}, planes="dtype")      # float tensors stored as byte planes: they compress (below)
+    tensors, statuses = read_files_device(image, planes="manifest")       # ... and come back as they were
+
+Byte planes (include/zpack_amd.h: zpack_amd_write_files_device_planes, zpack_amd_read_files_device_planes).  A float tensor alternates
+bytes that compress with bytes that are noise; an entry with element size k in {2, 4, 8} is stored with byte 0 of every element first,
+then byte 1 of every element, and so on.  The grouping happens inside the copy the codec makes of the plaintext anyway.  `planes` is
+{name: element size} (names left out: 1) or, writing, "dtype": tensor.element_size() for floating dtypes of 2, 4 or 8 bytes, 1 for
+everything else — the writer then appends one stored entry, PLANES_MANIFEST, that holds the map as JSON, and read_files_device(...,
+planes="manifest") applies it.  To any other reader a grouped entry is an ordinary entry whose bytes are the grouped bytes.
 
 The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
 are ZPACK_ERROR_NOT_AVAILABLE.
@@ -20,6 +29,7 @@ import os
 from . import ZPACK_SO, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4            # noqa: F401  (the methods are part of this module's interface)
 
 OK, BUFFER_TOO_SMALL, STREAM_INVALID, NOT_AVAILABLE = 0, 12, 21, 24     # enum zpack_result (include/zpack.h)
+PLANES_MANIFEST = ".zpack_amd/planes.json"                              # the entry write_*(planes="dtype") appends: {name: element size}
 
 
 class FileEntry(C.Structure):                # zpack_file_entry (include/zpack.h)
@@ -71,6 +81,8 @@ def lib():
         L.zpack_close_reader.argtypes = [R]
         L.zpack_close_reader.restype = None
         L.zpack_amd_read_files_device.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]
+        L.zpack_amd_read_files_device_planes.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(C.c_int), vp]
+        L.zpack_read_file.argtypes = [R, C.POINTER(FileEntry), vp, C.c_size_t, vp]
         L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
         L.zpack_amd_test_files.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(C.c_int), vp]
         L.zpack_init_writer.argtypes = [W, C.c_char_p]
@@ -79,6 +91,8 @@ def lib():
         L.zpack_write_header.argtypes = [W]
         L.zpack_write_data_header.argtypes = [W]
         L.zpack_amd_write_files_device.argtypes = [W, C.POINTER(File), u64]
+        L.zpack_amd_write_files_device_planes.argtypes = [W, C.POINTER(File), u64, C.POINTER(C.c_uint8)]
+        L.zpack_write_files.argtypes = [W, C.POINTER(File), u64]
         L.zpack_write_cdr.argtypes = [W]
         L.zpack_write_eocdr.argtypes = [W]
         L.zpack_close_writer.argtypes = [W]
@@ -149,10 +163,32 @@ def test_files(archive, names=None, device=0):
 test_files.__test__ = False                     # (a library function, not a test: pytest collects nothing here)
 
 
-def read_files_device(archive, names=None, device=0):
+def _read_manifest(L, r):
+    """the {name: element size} map of the opened reader's PLANES_MANIFEST entry, read through the host call; raises when there is none
+    or it does not parse"""
+    import json
+    for i in range(r.file_count):
+        e = r.file_entries[i]
+        if e.filename.decode() != PLANES_MANIFEST:
+            continue
+        raw = C.create_string_buffer(max(int(e.uncomp_size), 1))
+        _check(L.zpack_read_file(C.byref(r), C.pointer(e), raw, int(e.uncomp_size), None), "zpack_read_file(%s)" % PLANES_MANIFEST)
+        try:
+            m = json.loads(raw.raw[:int(e.uncomp_size)].decode())
+            if not isinstance(m, dict) or not all(isinstance(k, str) and v in (1, 2, 4, 8) and not isinstance(v, bool) for k, v in m.items()):
+                raise ValueError("not a {name: 1 | 2 | 4 | 8} map")
+        except ValueError as err:                                                   # (json's and unicode's errors are ValueErrors)
+            raise ValueError("%s does not parse: %s" % (PLANES_MANIFEST, err)) from None
+        return m
+    raise KeyError("the archive has no %s entry: it was not written with planes=\"dtype\"" % PLANES_MANIFEST)
+
+
+def read_files_device(archive, names=None, device=0, planes=None):
     """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
     compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
-    in that order (None: all, in archive order).
+    in that order (None: all, in archive order).  `planes`: None — the entries' bytes as they are stored; {name: element size} — those
+    entries are byte-plane entries and come back joined (names left out: 1); "manifest" — the map is the archive's PLANES_MANIFEST entry
+    (raises when that is missing or does not parse), and with names None that entry is left out of what is returned.
     Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
     a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
     import torch
@@ -161,6 +197,12 @@ def read_files_device(archive, names=None, device=0):
     device = _open_reader(L, r, archive, device)
     try:
         picks = _picks(r, names)
+        if planes == "manifest":
+            planes = _read_manifest(L, r)
+            if names is None:
+                picks = [i for i in picks if r.file_entries[i].filename.decode() != PLANES_MANIFEST]
+        elif planes is not None and not isinstance(planes, dict):
+            raise ValueError("planes is None, a {name: element size} dict or \"manifest\"")
         n = len(picks)
         sizes = [int(r.file_entries[i].uncomp_size) for i in picks]
         starts, total = [], 0
@@ -175,7 +217,11 @@ def read_files_device(archive, names=None, device=0):
         caps = (C.c_size_t * max(n, 1))(*sizes)
         res = (C.c_int * max(n, 1))()
         _settle(dev)
-        _check(L.zpack_amd_read_files_device(C.byref(r), ents, n, bufs, caps, res, None), "zpack_amd_read_files_device")
+        if planes is None:
+            _check(L.zpack_amd_read_files_device(C.byref(r), ents, n, bufs, caps, res, None), "zpack_amd_read_files_device")
+        else:
+            elem = (C.c_uint8 * max(n, 1))(*[int(planes.get(r.file_entries[i].filename.decode(), 1)) for i in picks])
+            _check(L.zpack_amd_read_files_device_planes(C.byref(r), ents, n, bufs, caps, elem, res, None), "zpack_amd_read_files_device_planes")
         return tensors, [int(res[i]) for i in range(n)]
     finally:
         L.zpack_close_reader(C.byref(r))
@@ -191,8 +237,24 @@ def _flatten(tensors, who):
     return items, flat
 
 
-def _write_archive(L, w, items, flat, method, level):
-    """The body both writers share: header, data signature, the entries out of device memory, CDR and EOCDR into the opened writer `w`"""
+def _elem_sizes(items, planes):
+    """(element size per item or None, the manifest's bytes or None) for the `planes` argument of the writers"""
+    import json
+    if planes is None:
+        return None, None
+    if isinstance(planes, dict):
+        return [int(planes.get(name, 1)) for name, _ in items], None
+    if planes != "dtype":
+        raise ValueError("planes is None, a {name: element size} dict or \"dtype\"")
+    if any(name == PLANES_MANIFEST for name, _ in items):
+        raise ValueError("%s is the name of the manifest planes=\"dtype\" writes" % PLANES_MANIFEST)
+    elem = [t.element_size() if t.dtype.is_floating_point and t.element_size() in (2, 4, 8) else 1 for _, t in items]
+    return elem, json.dumps({name: k for (name, _), k in zip(items, elem)}, separators=(",", ":")).encode()
+
+
+def _write_archive(L, w, items, flat, method, level, elem=None, manifest=None):
+    """The body both writers share: header, data signature, the entries out of device memory (elem: their element sizes, byte planes),
+    the manifest as one stored entry out of host memory, CDR and EOCDR into the opened writer `w`"""
     opts = CompressOptions(int(method), int(level))
     arr = (File * max(len(items), 1))()
     for i, ((name, _), t) in enumerate(zip(items, flat)):
@@ -203,22 +265,38 @@ def _write_archive(L, w, items, flat, method, level):
         arr[i].cctx = None
     _check(L.zpack_write_header(C.byref(w)), "zpack_write_header")
     _check(L.zpack_write_data_header(C.byref(w)), "zpack_write_data_header")
-    _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
+    if elem is None:
+        _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
+    else:
+        _check(L.zpack_amd_write_files_device_planes(C.byref(w), arr, len(items), (C.c_uint8 * max(len(items), 1))(*elem)), "zpack_amd_write_files_device_planes")
+    if manifest is not None:
+        stored = CompressOptions(int(METHOD_NONE), 0)
+        raw = C.create_string_buffer(manifest, len(manifest))
+        one = (File * 1)()
+        one[0].filename = PLANES_MANIFEST.encode()
+        one[0].buffer = C.cast(raw, C.c_void_p)
+        one[0].size = len(manifest)
+        one[0].options = C.pointer(stored)
+        one[0].cctx = None
+        _check(L.zpack_write_files(C.byref(w), one, 1), "zpack_write_files(%s)" % PLANES_MANIFEST)
     _check(L.zpack_write_cdr(C.byref(w)), "zpack_write_cdr")
     _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
 
 
-def write_files_device(path, tensors, method=METHOD_LZ4, level=0):
+def write_files_device(path, tensors, method=METHOD_LZ4, level=0, planes=None):
     """Writes the archive `path` with one entry per item of `tensors` ({name: CUDA tensor}, all on one device; any dtype: an entry is the
-    tensor's bytes in memory order).  path None: the archive is built on the heap and returned as bytes."""
+    tensor's bytes in memory order).  path None: the archive is built on the heap and returned as bytes.  `planes`: None — the bytes as
+    they are; {name: element size} — those entries are stored as byte planes; "dtype" — the element size of every floating tensor of 2,
+    4 or 8 bytes an element, and the PLANES_MANIFEST entry behind the tensors' (the module's docstring)."""
     L = lib()
     items, flat = _flatten(tensors, "write_files_device")
+    elem, manifest = _elem_sizes(items, planes)
     w = Writer()
     _check(L.zpack_init_writer(C.byref(w), os.fsencode(path)) if path is not None else L.zpack_init_writer_heap(C.byref(w), 0), "zpack_init_writer")
     try:
         if flat:
             _settle(flat[0].device)
-        _write_archive(L, w, items, flat, method, level)
+        _write_archive(L, w, items, flat, method, level, elem, manifest)
         return C.string_at(w.buffer, w.file_size) if path is None else None
     finally:
         L.zpack_close_writer(C.byref(w))
@@ -232,12 +310,12 @@ def archive_capacity(sizes, names, method):
     return 10 + sum(int(bound(int(method), int(s))) for s in sizes) + 20 + sum(35 + len(n.encode()) for n in names) + 12
 
 
-def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None):
+def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None, planes=None):
     """Writes an archive with one entry per item of `tensors` ({name: CUDA tensor}, all on one device) INTO DEVICE MEMORY
     (zpack_amd_init_writer_device): header, files, CDR and EOCDR go into a fresh uint8 tensor of `capacity` bytes on the tensors' device
     (None: archive_capacity, which holds whatever the entries compress to), the frames are committed there by the codec's kernels and no
     compressed byte crosses the bus.  Returns the tensor trimmed to the archive's size; it is byte for byte what write_files_device
-    returns for path None.  A capacity that is too small raises (ZPACK_ERROR_BUFFER_TOO_SMALL, 12).
+    returns for path None.  A capacity that is too small raises (ZPACK_ERROR_BUFFER_TOO_SMALL, 12).  `planes`: as in write_files_device.
 
         image = write_archive_device({"a": ta, "b": tb}, method=METHOD_ZSTD, level=1)
         tensors, statuses = read_files_device(image)                      # zpack_amd_init_reader_device: read where it was written
@@ -245,15 +323,18 @@ def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None):
     import torch
     L = lib()
     items, flat = _flatten(tensors, "write_archive_device")
+    elem, manifest = _elem_sizes(items, planes)
     dev = flat[0].device if flat else torch.device("cuda", 0)
     if capacity is None:
         capacity = archive_capacity([t.numel() for t in flat], [name for name, _ in items], method)
+        if manifest is not None:                                                    # (a stored entry: its bound is its size)
+            capacity += archive_capacity([len(manifest)], [PLANES_MANIFEST], METHOD_NONE) - 42
     image = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=dev)
     w = Writer()
     _settle(dev)
     _check(L.zpack_amd_init_writer_device(C.byref(w), image.data_ptr(), int(capacity)), "zpack_amd_init_writer_device")
     try:
-        _write_archive(L, w, items, flat, method, level)
+        _write_archive(L, w, items, flat, method, level, elem, manifest)
         return image[:int(w.file_size)]
     finally:
         L.zpack_close_writer(C.byref(w))

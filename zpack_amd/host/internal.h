@@ -64,6 +64,8 @@ zpk_codec* zi_ctx_codec_on(zi_ctx* ctx, int device);
 /* what a batch call of the codec returned, as the library reports it: ZPK_E_INVALID (the pointer rule turned something down) is
  * ZPACK_ERROR_STREAM_INVALID, any other failure ZPACK_ERROR_NOT_AVAILABLE */
 int zi_rc_of_codec(int crc);
+/* the element sizes of a byte-plane call (zpack_amd.h): 1 when there are none (NULL) or every one of the n is 1, 2, 4 or 8 */
+int zi_elem_sizes_valid(const zpack_u8* elem_sizes, zpack_u64 n);
 
 /* side tables (util.c): records kept beside structs of fixed layout, keyed by the struct's address.  One implementation, two instances —
  * the readers' (readahead.c: word = the generation) and the writers' (writer.c: word = the image's capacity) — and never one table for

@@ -119,6 +119,13 @@ int zi_rc_of_codec(int crc)
     return crc == ZPK_OK ? ZPACK_OK : crc == ZPK_E_INVALID ? ZPACK_ERROR_STREAM_INVALID : ZPACK_ERROR_NOT_AVAILABLE;
 }
 
+int zi_elem_sizes_valid(const zpack_u8* elem_sizes, zpack_u64 n)
+{
+    for (zpack_u64 i = 0; elem_sizes && i < n; i++)
+        if (elem_sizes[i] != 1 && elem_sizes[i] != 2 && elem_sizes[i] != 4 && elem_sizes[i] != 8) return 0;
+    return 1;
+}
+
 /* ------------------------------------------------------------------ side tables
  * zpack_reader and zpack_writer have the reference's fixed layouts: what this library keeps beside one of them is a record in a table
  * keyed by the struct's address.  64 chains under one rwlock per table (every zpack_read_file asks the readers': shared). */
