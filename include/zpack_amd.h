@@ -80,6 +80,38 @@ ZPACK_EXPORT int zpack_amd_read_files_device_planes(zpack_reader* reader, zpack_
                                                     void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
                                                     int* results, void* dctx);
 
+/* ---- DELTA entries: a tensor stored as its XOR against a base in device memory --------------------------------------------------------
+ * What compresses in a checkpoint is its difference to the previous one, which the caller holds in device memory anyway: most weights do
+ * not change in a step, those that do change in their low mantissa bits, so `new XOR old` is mostly zero bytes and its high byte planes
+ * are almost all zero (DESIGN.md section 10.6 has the figures).  For an entry of n bytes with element size k in {1, 2, 4, 8} and a base
+ * of n bytes:
+ *     stored = split_k(plain XOR base)          plain = join_k(stored) XOR base
+ * where split_k / join_k are the byte-plane layout above and k = 1 is the bare XOR; the base is indexed by plain byte index and the tail
+ * bytes are XORed like the rest.  The two calls below are the _planes calls with one base per entry (host array of file_count / count
+ * DEVICE pointers, on the same device as the other pointers; d_bases[i] covers files[i].size bytes writing and entries[i]->uncomp_size
+ * bytes reading; NULL: entry i has no base and is a byte-plane entry).  The XOR rides on the copy that carries the plaintext anyway: one
+ * more read stream, no further pass over the plaintext, no second copy of it.  The .zpk format does not change: a delta entry is an
+ * ordinary entry whose plaintext is the stored bytes, its hash is over those, any reader reads and verifies it (and gets the stored
+ * bytes), zpack_amd_test_files works on it unchanged.  NEITHER the element size NOR the base is in the archive: the caller hands the
+ * same values to both sides; a base that is itself a delta entry is the caller's business.  Every kind of writer and reader.
+ *
+ * d_bases == NULL is the _planes call, the same code; elem_sizes == NULL: every entry has element size 1.
+ * Reading, d_bases[i] == d_buffers[i] exactly is legal: the buffer that holds the previous checkpoint becomes the new one, no second copy
+ *   of the tensor.  A base that is not that many bytes of one allocation on that device, or that overlaps its destination in any other
+ *   way, is ZPACK_ERROR_STREAM_INVALID, checked before anything is enqueued: nothing is read or written, no result is set.
+ * The written archive is byte for byte the one zpack_amd_write_files_device_planes writes from device buffers that already hold
+ *   plain XOR base; entries, hashes, offsets, write_offset and the return value when a file fails are equal too.
+ * results[i], the return value and reader->last_return are those of zpack_amd_read_files_device_planes for the same entries.  The bytes
+ *   in d_buffers[i] are that call's bytes XOR the base when entry i decodes to all of its uncomp_size bytes (ZPACK_OK or
+ *   ZPACK_ERROR_FILE_HASH_MISMATCH); otherwise the buffer is untouched — with d_bases[i] == d_buffers[i] the previous checkpoint
+ *   survives a damaged entry.
+ * Which device, stream ordering, read-ahead, no device (ZPACK_ERROR_NOT_AVAILABLE): as for the calls beside them (above). */
+ZPACK_EXPORT int zpack_amd_write_files_device_delta(zpack_writer* writer, zpack_file* files, zpack_u64 file_count,
+                                                    const zpack_u8* elem_sizes, const void* const* d_bases);
+ZPACK_EXPORT int zpack_amd_read_files_device_delta(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                                   void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
+                                                   const void* const* d_bases, int* results, void* dctx);
+
 /* ---- the archive IMAGE in DEVICE memory -------------------------------------------------------------------------------------------
  * A third kind of reader beside the memory-backed and the file-backed one: the archive lies in device memory — a data set or checkpoint
  * kept compressed in HBM, an archive that arrived by a device-to-device transfer — and its compressed bytes never cross the bus.

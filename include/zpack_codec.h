@@ -56,7 +56,9 @@ extern "C" {
                                         caller's device memory.
                                         zpk_codec_verify_batch_host, zpk_codec_verify_batch_dimage, zpk_codec_verify_stats: a batch that is only TESTED, verdicts without plaintext.
                                         zpk_codec_plane_copy_device, the _planes forms of _encode_batch_dsrc, _encode_batch_dsink, _decode_batch_host_dptr and _decode_batch_dimage,
-                                        zpk_codec_planes_stats: byte-plane entries, split and joined in the copies.) */
+                                        zpk_codec_planes_stats: byte-plane entries, split and joined in the copies.
+                                        zpk_codec_delta_copy_device, the _delta forms of the same four calls, zpk_codec_delta_stats: delta entries, a tensor stored as its XOR
+                                        against a base in device memory.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -382,6 +384,53 @@ int zpk_codec_decode_batch_dimage_planes(zpk_codec* c, const uint8_t* d_archive,
 /* the most recent of the calls above, or of the plain calls they extend: out[0] rows split, out[1] rows joined, out[2] k_plane_copy
  * launches, out[3] entries that decoded into the staging only because they were grouped */
 int zpk_codec_planes_stats(zpk_codec* c, uint32_t out[4]);
+
+/* ---- DELTA entries: a tensor stored as its XOR against a BASE in device memory (k_delta_copy) ---------------------------------------
+ * What compresses in a checkpoint is its difference to the previous one, which the caller holds in device memory anyway: most weights do
+ * not change in a step, those that do change in their low mantissa bits.  For an entry of n bytes with element size k in {1, 2, 4, 8}
+ * and a base of n bytes:
+ *     stored = split_k(plain XOR base)          plain = join_k(stored) XOR base
+ * split_k / join_k are the byte-plane layout above; k = 1 is the bare XOR.  The base is indexed by PLAIN byte index, the tail bytes are
+ * XORed like the rest.  An entry without a base is a byte-plane entry.  The archive knows nothing of it: the stored bytes are the entry's
+ * plaintext and its XXH3 is over them; neither the element size nor the base is recorded, the caller hands both to both sides.  The XOR
+ * rides on the copy that carries the plaintext anyway: one more read stream, no further pass, no second copy of the tensor.
+ *
+ * zpk_codec_delta_copy_device: the kernel on its own, as zpk_codec_plane_copy_device is k_plane_copy's.  rows[0, n) is HOST memory,
+ * consumed before the call returns; src, dst and base are DEVICE addresses on the codec's device, any alignment; join 0 takes plain bytes
+ * at src to stored bytes at dst, join 1 the reverse; the base has len bytes and lies beside the plain side.  On a JOIN base == dst
+ * exactly is legal — the buffer that holds the previous checkpoint becomes the new one —; any other overlap of [base, base + len) with
+ * [dst, dst + len), base == dst on a split, base == 0 with len > 0 (such a row belongs to zpk_codec_plane_copy_device), an element size
+ * outside {1, 2, 4, 8}, or an end that fails the pointer check of zpk_codec_decode_batch_host_dptr (len 0 passes): ZPK_E_INVALID and
+ * nothing has run.  The base may overlap the source freely (both are only read).  Asynchronous on `stream` (NULL = the codec's own). */
+typedef struct zpk_delta_copy { uint64_t src, dst, base, len; uint32_t elem, join; } zpk_delta_copy;
+int zpk_codec_delta_copy_device(zpk_codec* c, const zpk_delta_copy* rows, uint64_t n, void* stream);
+/* The _planes calls with one more argument: d_base[i] is the base of entry i, DEVICE memory on the codec's device of the entry's plain
+ * size (desc[i].size writing, desc[i].uncomp_size reading); HOST array of n pointers.  d_base == NULL IS the _planes call, the same body;
+ * d_base[i] == NULL: entry i has no base.  elem == NULL: every element size is 1.  A base that fails the pointer check, or — reading —
+ * overlaps its entry's destination other than by being it: ZPK_E_INVALID and nothing has run.  A batch without bases launches exactly
+ * what the _planes call launches.
+ * Writing: the sources with a base reach the staging through k_delta_copy (split); everything behind the staging sees the stored bytes.
+ * Reading: an entry with a base is treated wherever an entry with elem > 1 is — it is delivered through k_delta_copy (join) only when it
+ * decoded to all of its uncomp_size bytes (status OK or a hash mismatch), a large frame decodes into the staging and is joined from
+ * there; for every other status nothing is written to its buffer, so with base == destination the previous checkpoint survives a damaged
+ * entry.  The results are the plain call's.  Host sources and host destinations take no base. */
+int zpk_codec_encode_batch_dsrc_delta(zpk_codec* c, const uint8_t* const* d_src_ptrs,
+                                      const zpk_encode_desc* desc, uint64_t n,
+                                      uint8_t* const* dst_ptrs, zpk_encode_result* results, const uint8_t* elem, const uint8_t* const* d_base);
+int zpk_codec_encode_batch_dsink_delta(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device,
+                                       const zpk_encode_desc* desc, uint64_t n,
+                                       uint8_t* d_sink, uint64_t sink_room,
+                                       zpk_encode_result* results, uint64_t* placed, uint64_t* bytes, const uint8_t* elem, const uint8_t* const* d_base);
+int zpk_codec_decode_batch_host_dptr_delta(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
+                                           const zpk_decode_desc* desc, uint64_t n,
+                                           uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base);
+int zpk_codec_decode_batch_dimage_delta(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size,
+                                        const zpk_decode_desc* desc, uint64_t n,
+                                        uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base);
+/* the most recent of the calls above, or of the calls they extend: out[0] rows split with a base, out[1] rows joined with a base, out[2]
+ * k_delta_copy launches, out[3] entries that decoded into the staging only because they had a base (element size 1).
+ * zpk_codec_planes_stats keeps its meaning: it counts the rows of k_plane_copy, which are those without a base. */
+int zpk_codec_delta_stats(zpk_codec* c, uint32_t out[4]);
 
 /* zpk_codec_encode_batch_device for batches that hold LARGE entries: d_src, d_dst and d_results are DEVICE pointers, `desc` is HOST memory
  * (consumed before the call returns).  An entry with size >= ZPK_OPT_ENC_SPLIT_MIN, size > 512 KiB and a valid method is compressed as

@@ -1,0 +1,9 @@
+#!/bin/bash
+# CPU, AddressSanitizer + UBSan: the layout of a delta entry and the row table of k_delta_copy, every item walked as the kernel walks it,
+# in place too (zpack_amd/csrc/delta_copy_plan.h: the very header the codec compiles).  tools/hostfuzz/run_delta_copy_plan.sh
+set -e
+cd "$(dirname "$0")/../.."
+work=$(mktemp -d -t zpk_deltacopyplan.XXXXXX)    # private to this run: a directory left by another user cannot block it
+trap 'rm -rf "$work"' EXIT
+g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -std=c++17 -Wall -Wno-unused-function -I zpack_amd/csrc -o "$work/delta_copy_plan" tools/hostfuzz/delta_copy_plan_main.cpp
+"$work/delta_copy_plan" "$@"

@@ -33,6 +33,8 @@ assert DECODE_DESC.itemsize == 56 and DECODE_RESULT.itemsize == 24
 assert ENCODE_DESC.itemsize == 40 and ENCODE_RESULT.itemsize == 24
 PLANE_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u8"), ("elem", "<u4"), ("join", "<u4")])       # zpk_plane_copy
 assert PLANE_COPY.itemsize == 32
+DELTA_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("base", "<u8"), ("len", "<u8"), ("elem", "<u4"), ("join", "<u4")])   # zpk_delta_copy
+assert DELTA_COPY.itemsize == 40
 
 _lib = None
 
@@ -76,6 +78,9 @@ def lib():
         if hasattr(L, "zpk_codec_plane_copy_device"):         # (likewise: byte-plane entries)
             L.zpk_codec_plane_copy_device.argtypes = [vp, vp, u64, vp]
             L.zpk_codec_planes_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
+        if hasattr(L, "zpk_codec_delta_copy_device"):         # (likewise: delta entries)
+            L.zpk_codec_delta_copy_device.argtypes = [vp, vp, u64, vp]
+            L.zpk_codec_delta_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.zpk_codec_pack_batch_device.argtypes = [vp, u8p, vp, vp, u64, u8p, u64, vp, u64, vp]
         L.zpk_codec_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
         L.zpk_codec_compress_bound.restype = C.c_size_t
@@ -403,6 +408,23 @@ class Codec:
         rows = np.ascontiguousarray(rows, dtype=PLANE_COPY)
         self._chk(self.L.zpk_codec_plane_copy_device(self.h, rows.ctypes.data, len(rows), C.c_void_p(stream) if stream else None),
                   "zpk_codec_plane_copy_device")
+
+    def delta_copy_device(self, rows, stream=None):
+        """rows: DELTA_COPY array of (src address, dst address, base address, len, elem, join): one k_delta_copy launch — join 0 takes plain
+        bytes to split(plain ^ base), join 1 stored bytes to join(stored) ^ base (include/zpack_codec.h states the layout); on a join
+        base == dst is legal.  Asynchronous on `stream` (None: the codec's own; synchronise the device before reading the destinations).
+        Raises on ZPK_E_INVALID (a pointer, a missing base or an overlap the check turned down: nothing has run)."""
+        self._settle(stream)
+        rows = np.ascontiguousarray(rows, dtype=DELTA_COPY)
+        self._chk(self.L.zpk_codec_delta_copy_device(self.h, rows.ctypes.data, len(rows), C.c_void_p(stream) if stream else None),
+                  "zpk_codec_delta_copy_device")
+
+    def delta_stats(self):
+        """The most recent call that could split or join: rows split with a base, rows joined with a base, k_delta_copy launches, entries
+        that decoded into the staging only because they had a base."""
+        a = (C.c_uint32 * 4)()
+        self._chk(self.L.zpk_codec_delta_stats(self.h, a), "zpk_codec_delta_stats")
+        return dict(split=a[0], joined=a[1], launches=a[2], staged=a[3])
 
     def planes_stats(self):
         """The most recent call that could split or join byte planes: rows split, rows joined, k_plane_copy launches, entries that decoded

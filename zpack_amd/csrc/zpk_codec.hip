@@ -49,6 +49,9 @@ namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 
 #include "plane_copy_plan.h"                     // byte-plane entries: the layout, the row table, items and launches of k_plane_copy (plain C++, likewise)
 // k_plane_copy (plane_copy.h) is compiled in plane_copy.hip, for the same reason
 namespace zpk { void plane_copy_launch(const PlaneCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
+#include "delta_copy_plan.h"                     // delta entries: a tensor stored as its XOR against a base in device memory, and the row table of k_delta_copy (plain C++, likewise)
+// k_delta_copy (delta_copy.h) is compiled in delta_copy.hip, for the same reason
+namespace zpk { void delta_copy_launch(const DeltaCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
 // ... and so is k_stored_hash (stored_hash.h, stored_hash.hip): k_stored without the copy, for a batch that has no destination
 namespace zpk { void stored_hash_launch(const u8* src, const zpk_decode_desc* desc, zpk_decode_result* res, const u32* list, const u32* counters, u32 grid, hipStream_t st); }
 #include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
@@ -621,11 +624,16 @@ struct BatchMethods { int zstd, lz4; };
 enum class Dst : int { Host = 0, Device = 1, None = 2 };
 // The element sizes of a batch whose plaintext lies in the caller's device memory (plane_copy_plan.h): elem[i] of entry i, none = every
 // entry is plain bytes (element size 1).  Handed down as an argument to whatever stages sources or delivers slots.
+// ... and their BASES (delta_copy_plan.h): base[i] of entry i is device memory of the entry's plain size, none (or NULL for an entry) =
+// the entry has no base.  An entry with a base is stored as split(plain XOR base) and is treated wherever an element size above 1 is.
 struct Planes {
     const u8* elem = nullptr;
+    const u8* const* base = nullptr;
     u32 of(u64 i) const { return elem ? elem[i] : 1u; }
-    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr }; }
-    bool any() const { return elem != nullptr; }
+    const u8* base_of(u64 i) const { return base ? base[i] : nullptr; }
+    bool grouped(u64 i) const { return of(i) > 1 || base_of(i) != nullptr; }         // not a plain copy: k_plane_copy's or k_delta_copy's
+    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr, base ? base + first : nullptr }; }
+    bool any() const { return elem != nullptr || base != nullptr; }
 };
 // ZPK_E_INVALID: an element size that is none (plane_elem_valid), before anything is enqueued
 static int planes_check(zpk_codec* c, const u8* elem, u64 n);
@@ -655,6 +663,8 @@ struct LastCall {
     u32  vstored = 0;                            // zpk_codec_verify_batch_host / _dimage: stored entries hashed where they lay
     u32  dsink[2] = {0, 0};                      // zpk_codec_encode_batch_dsink: its sub-batches and the last grid of k_sink_place
     u32  enc_big[2] = {0, 0};                    // zpk_codec_encode_big_device: entries written in pieces, their pieces
+    u32  delta[4] = {0, 0, 0, 0};                // zpk_codec_delta_stats: rows split with a base, rows joined with a base, k_delta_copy launches, entries staged only because they had a base
+    void no_planes() { for (int k = 0; k < 4; k++) planes[k] = delta[k] = 0; }      // (a call that could split or join begins with this)
     u32  planes[4] = {0, 0, 0, 0};               // zpk_codec_planes_stats: rows split, rows joined, k_plane_copy launches, entries staged only because they were grouped
     int  fell_back_fused = 0;                    // the last decode batch could not get its sequence arena and ran the fused decoder only
     // the host-path pipeline decodes one call in several launches: their counters are brought back piece by piece and summed, so that
@@ -667,7 +677,7 @@ struct LastCall {
 // A growable pinned block (PinBuf) is regrown only while nothing on a stream still reads or writes it: a call that uses one drains the
 // stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk: hipStreamSynchronize behind the copy home; sspan.h: the
 // run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the block's next turn
-// (bigenc.h, sc.h, pc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
+// (bigenc.h, sc.h, pc.h, dc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
 struct zpk_codec {
     int device = 0;
     Stream stream;
@@ -753,6 +763,8 @@ struct zpk_codec {
     // ... and the row table of k_plane_copy (plane_copy_plan.h / plane_copy.h), a block of its own under the same rule: a call with
     // byte-plane entries fills both tables before either kernel has run
     struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } pc;
+    // ... and that of k_delta_copy (delta_copy_plan.h / delta_copy.h), a third block under the same rule
+    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } dc;
 
     // the encoder
     DevBuf<u64> d_seq;                           // sequence lists, one per workgroup
@@ -1027,15 +1039,51 @@ static int plane_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
 }
-// The spans row(i) of a batch with element sizes `pl`, all of one direction: those of element size 1 in ONE k_span_copy as ever, the
-// others in ONE k_plane_copy (join: PLANE_SPLIT / PLANE_JOIN).  No element sizes: span_copy_enqueue and nothing else.
+// The same for k_delta_copy: entry i the row row(i) (a zpk_delta_copy; no bytes: no row), through the codec's third pinned table.  Element
+// sizes, bases and their overlap with the destinations have been checked by the caller.
+template <class RowFn>
+static int delta_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
+{
+    u64 nz = 0;
+    for (u64 i = 0; i < n; i++) nz += row(i).len != 0;
+    if (nz == 0) return ZPK_OK;
+    if (nz > ZPK_PC_MAX_ROWS) return ZPK_E_INVALID;
+    if (c->dc.pending) { HIPCHK(c, hipEventSynchronize(c->dc.ev)); c->dc.pending = false; }             // the pinned block's last upload has run
+    if (c->dc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "delta copy: no event"); return ZPK_E_LAUNCH; }
+    if (!c->dc.h.grow(nz * sizeof(DeltaCopyRow))) { snprintf(c->err, sizeof(c->err), "delta copy: out of pinned memory"); return ZPK_E_NOMEM; }
+    int rc;
+    if ((rc = grow(c, c->dc.d, nz * sizeof(DeltaCopyRow)))) return rc;
+    DeltaCopyRow* const rows = (DeltaCopyRow*)c->dc.h.p;
+    PlaneCopyPlan p = { 0, 0 };
+    for (u64 i = 0; i < n; i++) {
+        const zpk_delta_copy s = row(i);
+        if (!delta_copy_emit(s.src, s.dst, s.base, s.len, s.elem, s.join, rows, p)) return ZPK_E_INVALID;
+        if (s.len) c->last.delta[s.join ? 1 : 0]++;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->dc.d, rows, p.nrows * sizeof(DeltaCopyRow), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->dc.ev, st));
+    c->dc.pending = true;
+    const u64 nl = plane_copy_launches(p.items);
+    for (u64 j = 0; j < nl; j++) {
+        const PlaneCopyLaunch L = plane_copy_launch(p.items, j);
+        delta_copy_launch((const DeltaCopyRow*)(const u8*)c->dc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
+        c->last.delta[2]++;
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZPK_OK;
+}
+// The spans row(i) of a batch with element sizes and bases `pl`, all of one direction (join: PLANE_SPLIT / PLANE_JOIN), split THREE ways:
+// those with a base in ONE k_delta_copy, those without a base and with an element size above 1 in ONE k_plane_copy, the rest in ONE
+// k_span_copy as ever.  No element sizes and no bases: span_copy_enqueue and nothing else; no bases: what it was before there were any.
 template <class RowFn>
 static int rows_enqueue(zpk_codec* c, u64 n, RowFn row, const Planes& pl, u32 join, hipStream_t st)
 {
     if (!pl.any()) return span_copy_enqueue(c, n, row, st);
-    int rc = span_copy_enqueue(c, n, [&](u64 i) { zpk_span_copy s = row(i); if (pl.of(i) > 1) s.len = 0; return s; }, st);
+    int rc = span_copy_enqueue(c, n, [&](u64 i) { zpk_span_copy s = row(i); if (pl.grouped(i)) s.len = 0; return s; }, st);
     if (rc) return rc;
-    return plane_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u32 k = pl.of(i); return zpk_plane_copy{ s.src, s.dst, k > 1 ? s.len : 0ull, k, join }; }, st);
+    rc = plane_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u32 k = pl.of(i); return zpk_plane_copy{ s.src, s.dst, k > 1 && !pl.base_of(i) ? s.len : 0ull, k, join }; }, st);
+    if (rc || !pl.base) return rc;
+    return delta_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u8* const b = pl.base_of(i); return zpk_delta_copy{ s.src, s.dst, (u64)b, b ? s.len : 0ull, pl.of(i), join }; }, st);
 }
 }  // extern "C++"
 static int planes_check(zpk_codec* c, const u8* elem, u64 n)
@@ -1044,6 +1092,22 @@ static int planes_check(zpk_codec* c, const u8* elem, u64 n)
         if (!plane_elem_valid(elem[i])) { snprintf(c->err, sizeof(c->err), "entry %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)elem[i]); return ZPK_E_INVALID; }
     return ZPK_OK;
 }
+// ZPK_E_INVALID, before anything is enqueued: a base (those that are not NULL) that fails the pointer rule over len(i) bytes, or — where
+// there are destinations, reading — one that overlaps its entry's destination other than exactly (delta_overlap_ok)
+extern "C++" {
+template <class LenFn>
+static int bases_check(zpk_codec* c, PtrRule& rule, const Planes& pl, u64 n, LenFn len, uint8_t* const* dst_ptrs)
+{
+    if (!pl.base) return ZPK_OK;
+    if (rule.batch("base", n, [&](u64 i) { return (const void*)pl.base[i]; }, [&](u64 i) { return pl.base[i] ? len(i) : 0ull; })) return ZPK_E_INVALID;
+    for (u64 i = 0; dst_ptrs && i < n; i++)
+        if (pl.base[i] && !delta_overlap_ok((u64)pl.base[i], (u64)dst_ptrs[i], len(i))) {
+            snprintf(c->err, sizeof(c->err), "base %llu overlaps its destination without being it", (unsigned long long)i);
+            return ZPK_E_INVALID;
+        }
+    return ZPK_OK;
+}
+}  // extern "C++"
 
 // XXH3-64 of `nspans` long spans of `base` (xxh3_span.h): enqueues the upload of the span list and the two kernels; the hashes stay on
 // the device, *d_hash_out says where (inside c->d_xpart, valid until the next call that hashes spans).  `h_spans` must stay as it is
@@ -1498,7 +1562,7 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
     if (to == Dst::Device) {
         // DEVICE destinations: the same bytes — [slot, slot + produced) of every entry — by ONE launch of k_span_copy, no host in between
         // (an entry with an element size above 1 is JOINED on the way, all of it or none: planes_join_len)
-        auto row = [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.of(i) > 1 ? planes_join_len(desc[i], results[i]) : (u64)results[i].produced }; };
+        auto row = [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? planes_join_len(desc[i], results[i]) : (u64)results[i].produced }; };
         if ((rc = rows_enqueue(c, n, row, pl, PLANE_JOIN, c->stream))) return rc;
         e = hipStreamSynchronize(c->stream);
     } else if (n > 1 && produced_total && produced_total * 2 >= out_total) {
@@ -1650,7 +1714,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             if (e != hipSuccess) break;
             rc = rows_enqueue(c, P.e1 - P.e0, [&](u64 k2) {
                 const u64 i = P.e0 + k2, p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
-                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.of(i) > 1 ? planes_join_len(desc[i], results[i]) : p };
+                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? planes_join_len(desc[i], results[i]) : p };
             }, pl.from(P.e0), PLANE_JOIN, c->pipe.s_dn);
         }
     } else
@@ -1980,9 +2044,11 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     if (to == Dst::None) return ZPK_OK;                                                // no destination: the verdicts were all
     if (to == Dst::Device) {                                                           // DEVICE destinations: one launch of k_span_copy
         auto row = [&](u64 k) { return zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size }; };
-        std::vector<u8> gelem;                                                         // (the group's element sizes, in its own order)
+        std::vector<u8> gelem;                                                         // (the group's element sizes and bases, in its own order)
+        std::vector<const u8*> gbase;
         if (pl.any()) { gelem.resize(ng); for (u64 k = 0; k < ng; k++) gelem[k] = (u8)pl.of(be[g0 + k].idx); }
-        if ((rc = rows_enqueue(c, ng, row, Planes{ pl.any() ? gelem.data() : nullptr }, PLANE_JOIN, c->stream))) return rc;
+        if (pl.base) { gbase.resize(ng); for (u64 k = 0; k < ng; k++) gbase[k] = pl.base_of(be[g0 + k].idx); }
+        if ((rc = rows_enqueue(c, ng, row, Planes{ pl.any() ? gelem.data() : nullptr, pl.base ? gbase.data() : nullptr }, PLANE_JOIN, c->stream))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ZPK_OK;
     }
@@ -2025,7 +2091,7 @@ static int decode_big_single(zpk_codec* c, PjEntry& P, const zpk_decode_desc& d,
 }
 
 // the counts decode_stats2 reports of the most recent decode call: none yet
-static void begin_decode_call(zpk_codec* c) { LastCall& l = c->last; l.planes[0] = l.planes[1] = l.planes[2] = l.planes[3] = 0; l.big[0] = l.big[1] = 0; l.walk[0] = l.walk[1] = 0; l.span[0] = l.span[1] = 0; l.pipe = l.sc = 0; l.subs = 0; l.home = 0; l.vstored = 0; }
+static void begin_decode_call(zpk_codec* c) { LastCall& l = c->last; l.no_planes(); l.big[0] = l.big[1] = 0; l.walk[0] = l.walk[1] = 0; l.span[0] = l.span[1] = 0; l.pipe = l.sc = 0; l.subs = 0; l.home = 0; l.vstored = 0; }
 
 static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                    uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to = Dst::Host, const Planes& pl = Planes())
@@ -2097,7 +2163,9 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
     HIPCHK(c, hipSetDevice(c->device));
     if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
     // the pointer rule (PtrRule): before anything is enqueued
-    if (ddst && PtrRule(c).batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
+    PtrRule rule(c);
+    if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
+    if (bases_check(c, rule, pl, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, dst_ptrs)) return ZPK_E_INVALID;
     begin_decode_call(c);
     // ---- which entries are sequences of frames worth decoding frame-parallel ----
     std::vector<BigEntry> be;
@@ -2146,14 +2214,16 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
         for (u64 k = 0; k < pj.size() && rc == ZPK_OK; k++) {                         // one large frame at a time: each fills the chip
             u8 again = 1;
             const u64 idx = pj[k].idx;
-            // a device destination is decoded into straight away — unless the entry has an element size above 1: that one decodes into the
-            // staging, as an entry without a destination does, and is JOINED from there
-            const bool grouped = ddst && pl.of(idx) > 1;
+            // a device destination is decoded into straight away — unless the entry has an element size above 1 or a base: that one decodes
+            // into the staging, as an entry without a destination does, and is JOINED from there
+            const bool grouped = ddst && pl.grouped(idx);
             rc = decode_big_single(c, pj[k], desc[idx], BigSrc{ archive, false }, grouped ? BigDst{ nullptr, Dst::None } : BigDst{ to == Dst::None ? nullptr : dst_ptrs[idx], to }, results[idx], again);
             if (rc == ZPK_OK && !again && grouped) {
-                c->last.planes[3]++;
-                const zpk_plane_copy row = { (u64)(u8*)c->d_dst, (u64)dst_ptrs[idx], planes_join_len(desc[idx], results[idx]), pl.of(idx), PLANE_JOIN };
-                if ((rc = plane_copy_enqueue(c, 1, [&](u64) { return row; }, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
+                const u8 k1 = (u8)pl.of(idx);
+                const u8* const b1 = pl.base_of(idx);
+                if (k1 > 1) c->last.planes[3]++; else c->last.delta[3]++;              // (staged because it was grouped; staged only because it had a base)
+                const zpk_span_copy row = { (u64)(u8*)c->d_dst, (u64)dst_ptrs[idx], planes_join_len(desc[idx], results[idx]) };
+                if ((rc = rows_enqueue(c, 1, [&](u64) { return row; }, Planes{ &k1, pl.base ? &b1 : nullptr }, PLANE_JOIN, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
             }
             if (rc == ZPK_OK && !again) is_big[idx] = 1;
         }
@@ -2164,8 +2234,9 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             std::vector<uint8_t*> rp(rest.size());
             std::vector<zpk_decode_result> rr(rest.size());
             std::vector<u8> re(pl.any() ? rest.size() : 0);
-            for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]]; if (pl.any()) re[k] = (u8)pl.of(rest[k]); }
-            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to, Planes{ pl.any() ? re.data() : nullptr });
+            std::vector<const u8*> rb(pl.base ? rest.size() : 0);
+            for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]]; if (pl.any()) re[k] = (u8)pl.of(rest[k]); if (pl.base) rb[k] = pl.base_of(rest[k]); }
+            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to, Planes{ pl.any() ? re.data() : nullptr, pl.base ? rb.data() : nullptr });
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
@@ -2184,10 +2255,16 @@ int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint6
     return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device);
 }
 
+int zpk_codec_decode_batch_host_dptr_delta(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                           uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base)
+{
+    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem, d_base });
+}
+
 int zpk_codec_decode_batch_host_dptr_planes(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                             uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem)
 {
-    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem });
+    return zpk_codec_decode_batch_host_dptr_delta(c, archive, archive_size, desc, n, d_dst_ptrs, results, elem, nullptr);
 }
 
 int zpk_codec_copy_spans_device(zpk_codec* c, const zpk_span_copy* rows, uint64_t n, void* stream)
@@ -2208,7 +2285,7 @@ int zpk_codec_plane_copy_device(zpk_codec* c, const zpk_plane_copy* rows, uint64
 {
     if (!c || (n && !rows)) return ZPK_E_INVALID;
     CodecLock lk(c);
-    c->last.planes[0] = c->last.planes[1] = c->last.planes[2] = c->last.planes[3] = 0;
+    c->last.no_planes();
     if (n == 0) return ZPK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     for (u64 i = 0; i < n; i++)
@@ -2218,6 +2295,42 @@ int zpk_codec_plane_copy_device(zpk_codec* c, const zpk_plane_copy* rows, uint64
     if (rule.batch("plane source", n, [&](u64 i) { return (const void*)rows[i].src; }, len) ||
         rule.batch("plane destination", n, [&](u64 i) { return (const void*)rows[i].dst; }, len)) return ZPK_E_INVALID;
     return plane_copy_enqueue(c, n, [&](u64 i) { return rows[i]; }, stream ? (hipStream_t)stream : c->stream);
+}
+
+// rows of k_delta_copy on their own: element size, direction, both ends and the base per row; the pointer rule on all three ends of every
+// row, and the overlap rule between base and destination (delta_overlap_ok) — on refusal nothing has run
+int zpk_codec_delta_copy_device(zpk_codec* c, const zpk_delta_copy* rows, uint64_t n, void* stream)
+{
+    if (!c || (n && !rows)) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    c->last.no_planes();
+    if (n == 0) return ZPK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (u64 i = 0; i < n; i++) {
+        if (!plane_elem_valid(rows[i].elem)) { snprintf(c->err, sizeof(c->err), "row %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
+        if (rows[i].len && !rows[i].base) { snprintf(c->err, sizeof(c->err), "row %llu has no base: a row of zpk_codec_plane_copy_device", (unsigned long long)i); return ZPK_E_INVALID; }
+    }
+    PtrRule rule(c);
+    auto len = [&](u64 i) { return (u64)rows[i].len; };
+    if (rule.batch("delta source", n, [&](u64 i) { return (const void*)rows[i].src; }, len) ||
+        rule.batch("delta destination", n, [&](u64 i) { return (const void*)rows[i].dst; }, len) ||
+        rule.batch("delta base", n, [&](u64 i) { return (const void*)rows[i].base; }, len)) return ZPK_E_INVALID;
+    for (u64 i = 0; i < n; i++)
+        if (!delta_overlap_ok(rows[i].base, rows[i].dst, rows[i].len) || (!rows[i].join && rows[i].len && rows[i].base == rows[i].dst)) {
+            snprintf(c->err, sizeof(c->err), "row %llu: the base overlaps the destination (only a join may have base == dst, exactly)", (unsigned long long)i);
+            return ZPK_E_INVALID;
+        }
+    return delta_copy_enqueue(c, n, [&](u64 i) { return rows[i]; }, stream ? (hipStream_t)stream : c->stream);
+}
+
+// the most recent call that could split or join: out[0] rows split with a base, out[1] rows joined with a base, out[2] k_delta_copy
+// launches, out[3] entries that decoded into the staging only because they had a base
+int zpk_codec_delta_stats(zpk_codec* c, uint32_t out[4])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    for (int k = 0; k < 4; k++) out[k] = c->last.delta[k];
+    return ZPK_OK;
 }
 
 // the most recent call that could split or join: out[0] rows split, out[1] rows joined, out[2] k_plane_copy launches, out[3] entries that
@@ -2463,6 +2576,7 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
     PtrRule rule(c);                                                                  // the pointer rule: before anything is enqueued
     if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
     if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
+    if (bases_check(c, rule, pl, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, dst_ptrs)) return ZPK_E_INVALID;
     begin_decode_call(c);
     const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
     auto slot = [&](u64 i) {                                                          // (no destination: a stored entry has no slot)
@@ -2499,12 +2613,19 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
     return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results);
 }
 
-// (element sizes belong to DEVICE destinations: with host destinations every one of them has to be 1)
+// (element sizes and bases belong to DEVICE destinations: with host destinations every element size has to be 1 and no entry has a base)
+int zpk_codec_decode_batch_dimage_delta(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                        uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base)
+{
+    if (!dst_on_device) for (u64 i = 0; i < n; i++) if ((elem && elem[i] != 1) || (d_base && d_base[i])) return ZPK_E_INVALID;
+    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results,
+                                   Planes{ dst_on_device ? elem : nullptr, dst_on_device ? d_base : nullptr });
+}
+
 int zpk_codec_decode_batch_dimage_planes(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                          uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem)
 {
-    if (!dst_on_device) for (u64 i = 0; elem && i < n; i++) if (elem[i] != 1) return ZPK_E_INVALID;
-    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results, Planes{ dst_on_device ? elem : nullptr });
+    return zpk_codec_decode_batch_dimage_delta(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device, results, elem, nullptr);
 }
 
 // ---- a batch that is only TESTED: the verdicts of the two calls above without a destination (Dst::None) --------------------------------------

@@ -81,26 +81,29 @@ static int dsink_sub(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc, co
 
 extern "C" {
 
-// (elem: the element sizes of DEVICE sources, plane_copy_plan.h — NULL: every entry is plain bytes; host sources take no other)
-int zpk_codec_encode_batch_dsink_planes(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,
-                                        uint8_t* d_sink, uint64_t sink_room_bytes, zpk_encode_result* results, uint64_t* placed, uint64_t* bytes,
-                                        const uint8_t* elem)
+// (elem: the element sizes of DEVICE sources, plane_copy_plan.h — NULL: every entry is plain bytes; host sources take no other.
+// d_base: their bases, delta_copy_plan.h — NULL, or NULL for an entry: no base; host sources take none)
+int zpk_codec_encode_batch_dsink_delta(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,
+                                       uint8_t* d_sink, uint64_t sink_room_bytes, zpk_encode_result* results, uint64_t* placed, uint64_t* bytes,
+                                       const uint8_t* elem, const uint8_t* const* d_base)
 {
     if (!c || !placed || !bytes || (n && (!desc || !results || !src_ptrs))) return ZPK_E_INVALID;
     *placed = 0; *bytes = 0;
     CodecLock lk(c);
     c->last.dsink[0] = c->last.dsink[1] = 0;
-    c->last.planes[0] = c->last.planes[1] = c->last.planes[2] = c->last.planes[3] = 0;
+    c->last.no_planes();
     if (n == 0) return ZPK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (planes_check(c, elem, n)) return ZPK_E_INVALID;
     for (u64 i = 0; elem && !src_on_device && i < n; i++) if (elem[i] != 1) { snprintf(c->err, sizeof(c->err), "source %llu: an element size of %u for host memory", (unsigned long long)i, (unsigned)elem[i]); return ZPK_E_INVALID; }
-    const Planes pl = { src_on_device ? elem : nullptr };
+    for (u64 i = 0; d_base && !src_on_device && i < n; i++) if (d_base[i]) { snprintf(c->err, sizeof(c->err), "source %llu: a base for host memory", (unsigned long long)i); return ZPK_E_INVALID; }
+    const Planes pl = { src_on_device ? elem : nullptr, src_on_device ? d_base : nullptr };
     // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued.  The sink and device sources lie inside one allocation each on
     // this device; a host source with bytes is not device memory (the host would read through such a pointer)
     PtrRule rule(c);
     if (rule.batch("sink", 1, [&](u64) { return d_sink; }, [&](u64) { return (u64)sink_room_bytes; }) ||
         (src_on_device && rule.batch("source", n, [&](u64 i) { return src_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].size; }))) return ZPK_E_INVALID;
+    if (bases_check(c, rule, pl, n, [&](u64 i) { return (u64)desc[i].size; }, nullptr)) return ZPK_E_INVALID;
     for (u64 i = 0; i < n && !src_on_device; i++)
         if (desc[i].size && (!src_ptrs[i] || zpk_codec_pointer_device(src_ptrs[i]) >= 0)) {
             snprintf(c->err, sizeof(c->err), "source %llu is not %llu bytes of host memory (the codec of device %d reads it on the host)", (unsigned long long)i, (unsigned long long)desc[i].size, c->device);
@@ -118,6 +121,13 @@ int zpk_codec_encode_batch_dsink_planes(zpk_codec* c, const uint8_t* const* src_
     }
     *placed = ch.placed; *bytes = ch.bytes;
     return ZPK_OK;
+}
+
+int zpk_codec_encode_batch_dsink_planes(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,
+                                        uint8_t* d_sink, uint64_t sink_room_bytes, zpk_encode_result* results, uint64_t* placed, uint64_t* bytes,
+                                        const uint8_t* elem)
+{
+    return zpk_codec_encode_batch_dsink_delta(c, src_ptrs, src_on_device, desc, n, d_sink, sink_room_bytes, results, placed, bytes, elem, nullptr);
 }
 
 int zpk_codec_encode_batch_dsink(zpk_codec* c, const uint8_t* const* src_ptrs, int src_on_device, const zpk_encode_desc* desc, uint64_t n,

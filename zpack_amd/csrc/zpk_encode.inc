@@ -1599,11 +1599,13 @@ static int encode_batch_host_any(zpk_codec* c, const uint8_t* const* src_ptrs, c
     if (!c || (n && (!desc || !results || !src_ptrs || !dst_ptrs))) return ZPK_E_INVALID;
     if (n == 0) return ZPK_OK;
     CodecLock lk(c);
-    c->last.planes[0] = c->last.planes[1] = c->last.planes[2] = c->last.planes[3] = 0;
+    c->last.no_planes();
     HIPCHK(c, hipSetDevice(c->device));
     if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
     // the pointer rule (zpk_codec.hip, PtrRule): before anything is enqueued
-    if (dsrc && PtrRule(c).batch("source", n, [&](u64 i) { return src_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].size; })) return ZPK_E_INVALID;
+    PtrRule rule(c);
+    if (dsrc && rule.batch("source", n, [&](u64 i) { return src_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].size; })) return ZPK_E_INVALID;
+    if (bases_check(c, rule, pl, n, [&](u64 i) { return (u64)desc[i].size; }, nullptr)) return ZPK_E_INVALID;
     const u64 split_min = c->opt.enc_split_min;
     u64 np = 0, nsplit = 0;
     for (u64 i = 0; i < n; i++) { np += enc_piece_count(split_min, desc[i]); nsplit += enc_is_split(split_min, desc[i]); }
@@ -1695,11 +1697,18 @@ int zpk_codec_encode_batch_dsrc(zpk_codec* c, const uint8_t* const* d_src_ptrs, 
     return encode_batch_host_any(c, d_src_ptrs, desc, n, dst_ptrs, results, true);
 }
 
-// ... whose entry i has elements of elem[i] bytes (plane_copy_plan.h): the staging, and with it everything behind it, holds the grouped bytes
+// ... whose entry i has elements of elem[i] bytes (plane_copy_plan.h) and the base d_base[i] (delta_copy_plan.h): the staging, and with it
+// everything behind it, holds the stored bytes — split(plain XOR base)
+int zpk_codec_encode_batch_dsrc_delta(zpk_codec* c, const uint8_t* const* d_src_ptrs, const zpk_encode_desc* desc, uint64_t n,
+                                      uint8_t* const* dst_ptrs, zpk_encode_result* results, const uint8_t* elem, const uint8_t* const* d_base)
+{
+    return encode_batch_host_any(c, d_src_ptrs, desc, n, dst_ptrs, results, true, Planes{ elem, d_base });
+}
+
 int zpk_codec_encode_batch_dsrc_planes(zpk_codec* c, const uint8_t* const* d_src_ptrs, const zpk_encode_desc* desc, uint64_t n,
                                        uint8_t* const* dst_ptrs, zpk_encode_result* results, const uint8_t* elem)
 {
-    return encode_batch_host_any(c, d_src_ptrs, desc, n, dst_ptrs, results, true, Planes{ elem });
+    return zpk_codec_encode_batch_dsrc_delta(c, d_src_ptrs, desc, n, dst_ptrs, results, elem, nullptr);
 }
 
 }  // extern "C"

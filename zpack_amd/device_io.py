@@ -20,6 +20,16 @@ then byte 1 of every element, and so on.  The grouping happens inside the copy t
 everything else — the writer then appends one stored entry, PLANES_MANIFEST, that holds the map as JSON, and read_files_device(...,
 planes="manifest") applies it.  To any other reader a grouped entry is an ordinary entry whose bytes are the grouped bytes.
 
+Delta entries (include/zpack_amd.h: zpack_amd_write_files_device_delta, zpack_amd_read_files_device_delta).  What compresses in a
+checkpoint is its difference to the previous one: with base={name: tensor} — the previous checkpoint's tensors, which lie in device
+memory anyway — an entry is stored as the byte planes of `tensor XOR base`, and read_files_device(..., base=...) hands back the tensor.
+inplace=True reads into the base tensors themselves: the previous checkpoint becomes the new one, without a second copy.  The base is
+not in the archive; with planes="dtype" the writer appends DELTA_MANIFEST, the names of the delta entries and the caller's `base_id`,
+and planes="manifest" refuses to hand out a delta entry for which no base was given.
+
+    image = write_archive_device(new, planes="dtype", base=old, base_id="step 1000")
+    tensors, statuses = read_files_device(image, planes="manifest", base=old, base_id="step 1000", inplace=True)     # `old` now holds `new`
+
 The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
 are ZPACK_ERROR_NOT_AVAILABLE.
 """
@@ -30,6 +40,7 @@ from . import ZPACK_SO, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4            # noqa: 
 
 OK, BUFFER_TOO_SMALL, STREAM_INVALID, NOT_AVAILABLE = 0, 12, 21, 24     # enum zpack_result (include/zpack.h)
 PLANES_MANIFEST = ".zpack_amd/planes.json"                              # the entry write_*(planes="dtype") appends: {name: element size}
+DELTA_MANIFEST = ".zpack_amd/delta.json"                                # ... and with base=: {"entries": [names], "base_id": string or null}
 
 
 class FileEntry(C.Structure):                # zpack_file_entry (include/zpack.h)
@@ -82,6 +93,8 @@ def lib():
         L.zpack_close_reader.restype = None
         L.zpack_amd_read_files_device.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]
         L.zpack_amd_read_files_device_planes.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(C.c_int), vp]
+        L.zpack_amd_read_files_device_delta.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(vp),
+                                                        C.POINTER(C.c_int), vp]
         L.zpack_read_file.argtypes = [R, C.POINTER(FileEntry), vp, C.c_size_t, vp]
         L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
         L.zpack_amd_test_files.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(C.c_int), vp]
@@ -92,6 +105,7 @@ def lib():
         L.zpack_write_data_header.argtypes = [W]
         L.zpack_amd_write_files_device.argtypes = [W, C.POINTER(File), u64]
         L.zpack_amd_write_files_device_planes.argtypes = [W, C.POINTER(File), u64, C.POINTER(C.c_uint8)]
+        L.zpack_amd_write_files_device_delta.argtypes = [W, C.POINTER(File), u64, C.POINTER(C.c_uint8), C.POINTER(vp)]
         L.zpack_write_files.argtypes = [W, C.POINTER(File), u64]
         L.zpack_write_cdr.argtypes = [W]
         L.zpack_write_eocdr.argtypes = [W]
@@ -163,32 +177,63 @@ def test_files(archive, names=None, device=0):
 test_files.__test__ = False                     # (a library function, not a test: pytest collects nothing here)
 
 
-def _read_manifest(L, r):
-    """the {name: element size} map of the opened reader's PLANES_MANIFEST entry, read through the host call; raises when there is none
-    or it does not parse"""
+def _read_json_entry(L, r, name, valid, what):
+    """the JSON value of the opened reader's entry `name`, read through the host call; None when there is no such entry; raises when it
+    does not parse or valid(value) is false (`what` says what it should have been)"""
     import json
     for i in range(r.file_count):
         e = r.file_entries[i]
-        if e.filename.decode() != PLANES_MANIFEST:
+        if e.filename.decode() != name:
             continue
         raw = C.create_string_buffer(max(int(e.uncomp_size), 1))
-        _check(L.zpack_read_file(C.byref(r), C.pointer(e), raw, int(e.uncomp_size), None), "zpack_read_file(%s)" % PLANES_MANIFEST)
+        _check(L.zpack_read_file(C.byref(r), C.pointer(e), raw, int(e.uncomp_size), None), "zpack_read_file(%s)" % name)
         try:
             m = json.loads(raw.raw[:int(e.uncomp_size)].decode())
-            if not isinstance(m, dict) or not all(isinstance(k, str) and v in (1, 2, 4, 8) and not isinstance(v, bool) for k, v in m.items()):
-                raise ValueError("not a {name: 1 | 2 | 4 | 8} map")
+            if not valid(m):
+                raise ValueError("not %s" % what)
         except ValueError as err:                                                   # (json's and unicode's errors are ValueErrors)
-            raise ValueError("%s does not parse: %s" % (PLANES_MANIFEST, err)) from None
+            raise ValueError("%s does not parse: %s" % (name, err)) from None
         return m
-    raise KeyError("the archive has no %s entry: it was not written with planes=\"dtype\"" % PLANES_MANIFEST)
+    return None
 
 
-def read_files_device(archive, names=None, device=0, planes=None):
+def _read_manifest(L, r):
+    """the {name: element size} map of the opened reader's PLANES_MANIFEST entry; raises when there is none or it does not parse"""
+    m = _read_json_entry(L, r, PLANES_MANIFEST, lambda m: isinstance(m, dict) and all(isinstance(k, str) and v in (1, 2, 4, 8) and not isinstance(v, bool)
+                                                                                    for k, v in m.items()), "a {name: 1 | 2 | 4 | 8} map")
+    if m is None:
+        raise KeyError("the archive has no %s entry: it was not written with planes=\"dtype\"" % PLANES_MANIFEST)
+    return m
+
+
+def _read_delta_manifest(L, r):
+    """(names of the delta entries, recorded base_id or None) of the opened reader's DELTA_MANIFEST entry; ([], None) when there is none"""
+    m = _read_json_entry(L, r, DELTA_MANIFEST, lambda m: isinstance(m, dict) and isinstance(m.get("entries"), list) and all(isinstance(k, str) for k in m["entries"])
+                         and (m.get("base_id") is None or isinstance(m["base_id"], str)), "{\"entries\": [names], \"base_id\": string or null}")
+    return ([], None) if m is None else (m["entries"], m.get("base_id"))
+
+
+def _base_bytes(name, t, size):
+    """the base tensor of entry `name` as its bytes in memory order — a view, never a copy: it may be the destination"""
+    if not (t.is_cuda and t.is_contiguous()):
+        raise ValueError("the base of %s is a contiguous CUDA tensor" % name)
+    flat = t.reshape(-1).view(dtype=_u8())
+    if flat.numel() != size:
+        raise ValueError("the base of %s has %d bytes, the entry %d" % (name, flat.numel(), size))
+    return flat
+
+
+def read_files_device(archive, names=None, device=0, planes=None, base=None, inplace=False, base_id=None):
     """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
     compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
     in that order (None: all, in archive order).  `planes`: None — the entries' bytes as they are stored; {name: element size} — those
     entries are byte-plane entries and come back joined (names left out: 1); "manifest" — the map is the archive's PLANES_MANIFEST entry
     (raises when that is missing or does not parse), and with names None that entry is left out of what is returned.
+    `base`: {name: CUDA tensor of the entry's size} — those entries are delta entries and come back XORed with their base (the module's
+    docstring); inplace=True: the base tensors are the destinations and are what is returned for their entries — an entry that does not
+    decode leaves its base as it was.  With planes="manifest" the archive's DELTA_MANIFEST says which entries are delta entries: one
+    of those among the entries read without a base raises KeyError naming it (its bytes alone are not the tensor), and a `base_id`
+    that differs from the recorded one raises ValueError; with names None that entry is left out too.
     Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
     a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
     import torch
@@ -197,10 +242,18 @@ def read_files_device(archive, names=None, device=0, planes=None):
     device = _open_reader(L, r, archive, device)
     try:
         picks = _picks(r, names)
+        base = dict(base or {})
         if planes == "manifest":
             planes = _read_manifest(L, r)
+            delta_names, recorded_id = _read_delta_manifest(L, r)
             if names is None:
-                picks = [i for i in picks if r.file_entries[i].filename.decode() != PLANES_MANIFEST]
+                picks = [i for i in picks if r.file_entries[i].filename.decode() not in (PLANES_MANIFEST, DELTA_MANIFEST)]
+            if base_id is not None and base_id != recorded_id:
+                raise ValueError("the archive's entries are deltas against base %r, not %r" % (recorded_id, base_id))
+            picked = set(r.file_entries[i].filename.decode() for i in picks)
+            for name in delta_names:
+                if name in picked and name not in base:
+                    raise KeyError("%s is a delta entry: read_files_device needs base[%r]" % (name, name))
         elif planes is not None and not isinstance(planes, dict):
             raise ValueError("planes is None, a {name: element size} dict or \"manifest\"")
         n = len(picks)
@@ -212,17 +265,30 @@ def read_files_device(archive, names=None, device=0, planes=None):
         dev = torch.device("cuda", device)
         backing = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         tensors = [backing[a:a + s] for a, s in zip(starts, sizes)]
+        pnames = [r.file_entries[i].filename.decode() for i in picks]
+        bases = [_base_bytes(nm, base[nm], s) if nm in base else None for nm, s in zip(pnames, sizes)]
+        out = list(tensors)
+        if inplace:
+            for k, b in enumerate(bases):
+                if b is not None:
+                    tensors[k], out[k] = b, base[pnames[k]]
         ents = (C.POINTER(FileEntry) * max(n, 1))(*[C.pointer(r.file_entries[i]) for i in picks])
         bufs = (C.c_void_p * max(n, 1))(*[t.data_ptr() if s else None for t, s in zip(tensors, sizes)])
         caps = (C.c_size_t * max(n, 1))(*sizes)
         res = (C.c_int * max(n, 1))()
         _settle(dev)
-        if planes is None:
+        elem = None if planes is None else (C.c_uint8 * max(n, 1))(*[int(planes.get(nm, 1)) for nm in pnames])
+        if any(b is not None for b in bases):
+            for b in bases:
+                if b is not None:
+                    _settle(b.device)
+            d_bases = (C.c_void_p * max(n, 1))(*[b.data_ptr() if b is not None and b.numel() else None for b in bases])
+            _check(L.zpack_amd_read_files_device_delta(C.byref(r), ents, n, bufs, caps, elem, d_bases, res, None), "zpack_amd_read_files_device_delta")
+        elif planes is None:
             _check(L.zpack_amd_read_files_device(C.byref(r), ents, n, bufs, caps, res, None), "zpack_amd_read_files_device")
         else:
-            elem = (C.c_uint8 * max(n, 1))(*[int(planes.get(r.file_entries[i].filename.decode(), 1)) for i in picks])
             _check(L.zpack_amd_read_files_device_planes(C.byref(r), ents, n, bufs, caps, elem, res, None), "zpack_amd_read_files_device_planes")
-        return tensors, [int(res[i]) for i in range(n)]
+        return out, [int(res[i]) for i in range(n)]
     finally:
         L.zpack_close_reader(C.byref(r))
 
@@ -252,9 +318,28 @@ def _elem_sizes(items, planes):
     return elem, json.dumps({name: k for (name, _), k in zip(items, elem)}, separators=(",", ":")).encode()
 
 
-def _write_archive(L, w, items, flat, method, level, elem=None, manifest=None):
-    """The body both writers share: header, data signature, the entries out of device memory (elem: their element sizes, byte planes),
-    the manifest as one stored entry out of host memory, CDR and EOCDR into the opened writer `w`"""
+def _bases_of(items, flat, base, base_id, with_manifest):
+    """(the base's bytes per item or None — None when no item has one —, DELTA_MANIFEST's bytes or None) for the `base` argument of the writers"""
+    import json
+    if not base:
+        return None, None
+    unknown = [name for name in base if name not in dict(items)]
+    if unknown:
+        raise KeyError("base names no tensor of this call: %s" % ", ".join(unknown))
+    if base_id is not None and not isinstance(base_id, str):
+        raise ValueError("base_id is a string")
+    bases = [_base_bytes(name, base[name], t.numel()) if name in base else None for (name, _), t in zip(items, flat)]
+    if not with_manifest:
+        return bases, None
+    if any(name == DELTA_MANIFEST for name, _ in items):
+        raise ValueError("%s is the name of the manifest base= writes" % DELTA_MANIFEST)
+    return bases, json.dumps({"entries": [name for name, _ in items if name in base], "base_id": base_id}, separators=(",", ":")).encode()
+
+
+def _write_archive(L, w, items, flat, method, level, elem=None, manifest=None, bases=None, delta_manifest=None):
+    """The body both writers share: header, data signature, the entries out of device memory (elem: their element sizes, byte planes;
+    bases: what they are XORed with, delta entries), the manifests as stored entries out of host memory, CDR and EOCDR into the opened
+    writer `w`"""
     opts = CompressOptions(int(method), int(level))
     arr = (File * max(len(items), 1))()
     for i, ((name, _), t) in enumerate(zip(items, flat)):
@@ -265,38 +350,50 @@ def _write_archive(L, w, items, flat, method, level, elem=None, manifest=None):
         arr[i].cctx = None
     _check(L.zpack_write_header(C.byref(w)), "zpack_write_header")
     _check(L.zpack_write_data_header(C.byref(w)), "zpack_write_data_header")
-    if elem is None:
+    c_elem = None if elem is None else (C.c_uint8 * max(len(items), 1))(*elem)
+    if bases is not None:
+        for b in bases:
+            if b is not None:
+                _settle(b.device)
+        d_bases = (C.c_void_p * max(len(items), 1))(*[b.data_ptr() if b is not None and b.numel() else None for b in bases])
+        _check(L.zpack_amd_write_files_device_delta(C.byref(w), arr, len(items), c_elem, d_bases), "zpack_amd_write_files_device_delta")
+    elif elem is None:
         _check(L.zpack_amd_write_files_device(C.byref(w), arr, len(items)), "zpack_amd_write_files_device")
     else:
-        _check(L.zpack_amd_write_files_device_planes(C.byref(w), arr, len(items), (C.c_uint8 * max(len(items), 1))(*elem)), "zpack_amd_write_files_device_planes")
-    if manifest is not None:
+        _check(L.zpack_amd_write_files_device_planes(C.byref(w), arr, len(items), c_elem), "zpack_amd_write_files_device_planes")
+    for mname, mbytes in ((PLANES_MANIFEST, manifest), (DELTA_MANIFEST, delta_manifest)):
+        if mbytes is None:
+            continue
         stored = CompressOptions(int(METHOD_NONE), 0)
-        raw = C.create_string_buffer(manifest, len(manifest))
+        raw = C.create_string_buffer(mbytes, len(mbytes))
         one = (File * 1)()
-        one[0].filename = PLANES_MANIFEST.encode()
+        one[0].filename = mname.encode()
         one[0].buffer = C.cast(raw, C.c_void_p)
-        one[0].size = len(manifest)
+        one[0].size = len(mbytes)
         one[0].options = C.pointer(stored)
         one[0].cctx = None
-        _check(L.zpack_write_files(C.byref(w), one, 1), "zpack_write_files(%s)" % PLANES_MANIFEST)
+        _check(L.zpack_write_files(C.byref(w), one, 1), "zpack_write_files(%s)" % mname)
     _check(L.zpack_write_cdr(C.byref(w)), "zpack_write_cdr")
     _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
 
 
-def write_files_device(path, tensors, method=METHOD_LZ4, level=0, planes=None):
+def write_files_device(path, tensors, method=METHOD_LZ4, level=0, planes=None, base=None, base_id=None):
     """Writes the archive `path` with one entry per item of `tensors` ({name: CUDA tensor}, all on one device; any dtype: an entry is the
     tensor's bytes in memory order).  path None: the archive is built on the heap and returned as bytes.  `planes`: None — the bytes as
     they are; {name: element size} — those entries are stored as byte planes; "dtype" — the element size of every floating tensor of 2,
-    4 or 8 bytes an element, and the PLANES_MANIFEST entry behind the tensors' (the module's docstring)."""
+    4 or 8 bytes an element, and the PLANES_MANIFEST entry behind the tensors' (the module's docstring).  `base`: {name: CUDA tensor
+    with the nbytes of tensors[name]} — those entries are stored as deltas against it; with planes="dtype" the DELTA_MANIFEST entry
+    records their names and `base_id`, a string of the caller's that names the base (None: none)."""
     L = lib()
     items, flat = _flatten(tensors, "write_files_device")
     elem, manifest = _elem_sizes(items, planes)
+    bases, delta_manifest = _bases_of(items, flat, base, base_id, manifest is not None)
     w = Writer()
     _check(L.zpack_init_writer(C.byref(w), os.fsencode(path)) if path is not None else L.zpack_init_writer_heap(C.byref(w), 0), "zpack_init_writer")
     try:
         if flat:
             _settle(flat[0].device)
-        _write_archive(L, w, items, flat, method, level, elem, manifest)
+        _write_archive(L, w, items, flat, method, level, elem, manifest, bases, delta_manifest)
         return C.string_at(w.buffer, w.file_size) if path is None else None
     finally:
         L.zpack_close_writer(C.byref(w))
@@ -310,12 +407,13 @@ def archive_capacity(sizes, names, method):
     return 10 + sum(int(bound(int(method), int(s))) for s in sizes) + 20 + sum(35 + len(n.encode()) for n in names) + 12
 
 
-def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None, planes=None):
+def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None, planes=None, base=None, base_id=None):
     """Writes an archive with one entry per item of `tensors` ({name: CUDA tensor}, all on one device) INTO DEVICE MEMORY
     (zpack_amd_init_writer_device): header, files, CDR and EOCDR go into a fresh uint8 tensor of `capacity` bytes on the tensors' device
     (None: archive_capacity, which holds whatever the entries compress to), the frames are committed there by the codec's kernels and no
     compressed byte crosses the bus.  Returns the tensor trimmed to the archive's size; it is byte for byte what write_files_device
-    returns for path None.  A capacity that is too small raises (ZPACK_ERROR_BUFFER_TOO_SMALL, 12).  `planes`: as in write_files_device.
+    returns for path None.  A capacity that is too small raises (ZPACK_ERROR_BUFFER_TOO_SMALL, 12).  `planes`, `base`, `base_id`:
+    as in write_files_device.
 
         image = write_archive_device({"a": ta, "b": tb}, method=METHOD_ZSTD, level=1)
         tensors, statuses = read_files_device(image)                      # zpack_amd_init_reader_device: read where it was written
@@ -324,17 +422,20 @@ def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None, pla
     L = lib()
     items, flat = _flatten(tensors, "write_archive_device")
     elem, manifest = _elem_sizes(items, planes)
+    bases, delta_manifest = _bases_of(items, flat, base, base_id, manifest is not None)
     dev = flat[0].device if flat else torch.device("cuda", 0)
     if capacity is None:
         capacity = archive_capacity([t.numel() for t in flat], [name for name, _ in items], method)
         if manifest is not None:                                                    # (a stored entry: its bound is its size)
             capacity += archive_capacity([len(manifest)], [PLANES_MANIFEST], METHOD_NONE) - 42
+        if delta_manifest is not None:
+            capacity += archive_capacity([len(delta_manifest)], [DELTA_MANIFEST], METHOD_NONE) - 42
     image = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=dev)
     w = Writer()
     _settle(dev)
     _check(L.zpack_amd_init_writer_device(C.byref(w), image.data_ptr(), int(capacity)), "zpack_amd_init_writer_device")
     try:
-        _write_archive(L, w, items, flat, method, level, elem, manifest)
+        _write_archive(L, w, items, flat, method, level, elem, manifest, bases, delta_manifest)
         return image[:int(w.file_size)]
     finally:
         L.zpack_close_writer(C.byref(w))

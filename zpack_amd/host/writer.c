@@ -249,7 +249,8 @@ static zpack_u64 file_weight(const void* files, zpack_u64 i) { return ((const zp
  * are committed to the image on the device under the append rule below (the files in front of the first failing one, where "does not
  * fit" fails too), and only the results and the cut come home: no scratch of compress-bound size on the host. */
 static int write_files_dsink(zpack_writer* writer, zi_ctx* ctx, zpack_file* files, zpack_u64 file_count, int on_device,
-                             const zpack_u8* const* srcs, const zpk_encode_desc* desc, zpk_encode_result* res, const zpack_u8* elem)
+                             const zpack_u8* const* srcs, const zpk_encode_desc* desc, zpk_encode_result* res, const zpack_u8* elem,
+                             const zpack_u8* const* bases)
 {
     zpack_u8* d_image; size_t capacity; int device;
     if (zi_writer_sink(writer, &d_image, &capacity, &device) != ZI_SINK_DEVICE) return ZPACK_ERROR_WRITER_NOT_OPENED;
@@ -264,7 +265,7 @@ static int write_files_dsink(zpack_writer* writer, zi_ctx* ctx, zpack_file* file
     const zpack_u64 at0 = writer->write_offset;
     const zpack_u64 room = at0 < capacity ? capacity - at0 : 0;
     uint64_t placed = 0, bytes = 0;
-    const int crc = zpk_codec_encode_batch_dsink_planes(codec, srcs, on_device, desc, file_count, d_image + (at0 < capacity ? at0 : capacity), room, res, &placed, &bytes, elem);
+    const int crc = zpk_codec_encode_batch_dsink_delta(codec, srcs, on_device, desc, file_count, d_image + (at0 < capacity ? at0 : capacity), room, res, &placed, &bytes, elem, bases);
     if (crc != ZPK_OK) return zi_rc_of_codec(crc);
     for (zpack_u64 i = 0; i < placed; i++) {                                       /* entered as the loop below enters them: at the running sum */
         writer->last_return = (size_t)res[i].comp_size;
@@ -280,8 +281,10 @@ static int write_files_dsink(zpack_writer* writer, zi_ctx* ctx, zpack_file* file
 /* on_device: files[i].buffer are DEVICE pointers (zpack_amd_write_files_device) — the plaintext is compressed where it lies, only the
  * compressed bytes cross the bus: one zpk_codec_encode_batch_dsrc call on the codec of the pointers' device (no shard: one call's
  * pointers belong to one device).  Everything behind the codec call is the same code, so the archive is the same bytes.
- * elem (on_device only, else NULL): the files' element sizes — the codec splits the byte planes on the way into its staging */
-static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, int on_device, const zpack_u8* elem)
+ * elem (on_device only, else NULL): the files' element sizes — the codec splits the byte planes on the way into its staging.
+ * bases (likewise): the files' bases in device memory, NULL for a file that has none — the codec XORs them in on the same way */
+static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, int on_device, const zpack_u8* elem,
+                       const zpack_u8* const* bases)
 {
     if (file_count == 0) return ZPACK_OK;
     const zi_sink sink = zi_writer_sink(writer, NULL, NULL, NULL);
@@ -309,7 +312,7 @@ static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_c
         srcs[i] = files[i].buffer;
     }
     if (sink == ZI_SINK_DEVICE) {
-        if (rc == ZPACK_OK) rc = write_files_dsink(writer, ctx, files, file_count, on_device, srcs, desc, res, elem);
+        if (rc == ZPACK_OK) rc = write_files_dsink(writer, ctx, files, file_count, on_device, srcs, desc, res, elem, bases);
         free(desc); free(res); free(srcs);
         return rc;
     }
@@ -325,7 +328,7 @@ static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_c
     if (rc == ZPACK_OK && on_device) {
         zpk_codec* codec = zi_ctx_codec_of(ctx, &files[0].buffer, sizeof(files[0]), &files[0].size, sizeof(files[0]), 1, file_count, &rc);
         if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: empty entries only) */
-        if (codec) rc = zi_rc_of_codec(zpk_codec_encode_batch_dsrc_planes(codec, srcs, desc, file_count, dsts, res, elem));
+        if (codec) rc = zi_rc_of_codec(zpk_codec_encode_batch_dsrc_delta(codec, srcs, desc, file_count, dsts, res, elem, bases));
     } else if (rc == ZPACK_OK) {
         write_job job = { ctx, srcs, desc, dsts, res, {0}, {0} };
         /* static shard by source bytes: one host thread + one codec per device */
@@ -345,15 +348,22 @@ static int write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_c
     return rc;
 }
 
-int zpack_write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count) { return write_files(writer, files, file_count, 0, NULL); }
+int zpack_write_files(zpack_writer* writer, zpack_file* files, zpack_u64 file_count) { return write_files(writer, files, file_count, 0, NULL, NULL); }
 
-int zpack_amd_write_files_device_planes(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, const zpack_u8* elem_sizes)
+/* DELTA entries: file i is stored as split(plain XOR d_bases[i]); d_bases NULL is the byte-plane call, the same code */
+int zpack_amd_write_files_device_delta(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, const zpack_u8* elem_sizes,
+                                       const void* const* d_bases)
 {
     if (!writer || (file_count && !files)) return ZPACK_ERROR_STREAM_INVALID;
     for (zpack_u64 i = 0; i < file_count; i++) if (!files[i].options || !files[i].filename) return ZPACK_ERROR_STREAM_INVALID;
     if (!zi_elem_sizes_valid(elem_sizes, file_count)) return ZPACK_ERROR_STREAM_INVALID;    /* before any context is created */
     if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
-    return write_files(writer, files, file_count, 1, elem_sizes);
+    return write_files(writer, files, file_count, 1, elem_sizes, (const zpack_u8* const*)d_bases);
+}
+
+int zpack_amd_write_files_device_planes(zpack_writer* writer, zpack_file* files, zpack_u64 file_count, const zpack_u8* elem_sizes)
+{
+    return zpack_amd_write_files_device_delta(writer, files, file_count, elem_sizes, NULL);
 }
 
 int zpack_amd_write_files_device(zpack_writer* writer, zpack_file* files, zpack_u64 file_count)
