@@ -25,12 +25,16 @@ codec._chk(codec.L.zpk_codec_debug_read(codec.h, a.ctypes.data, a.nbytes), "debu
 if os.environ.get("LW_ASM"):        # a -DZPK_STATS_ASM build: the eight words are the assembly counters (zpk_codec.hip, lz4_stats_out)
     hi, lo = (a >> 32).sum(0).astype(np.float64), (a & 0xFFFFFFFF).sum(0).astype(np.float64)
     nb, t_asm, t_dir = hi[0], float(a[:, 5].sum()), float(a[:, 6].sum())
+    # word 4 holds four 16-bit counters per entry (zpk_codec.hip, lz4_stats_out)
+    so16, so1, a_self, x_rounds = (float(((a[:, 4] >> np.uint64(sh)) & np.uint64(0xFFFF)).sum()) for sh in (48, 32, 16, 0))
     print("assembly of batches (mix %d, %d entries): %.0f batches, %.1f per entry" % (mix, n, nb, nb / n))
     for k, v in (("assembled", lo[0]), ("direct: no room only", hi[1]), ("direct: a long piece only", lo[1]), ("direct: both", hi[2]),
                  ("direct: straddle only", lo[2])):
         print("  %-28s %6.2f %%" % (k, 100 * v / nb))
     print("  of the batches with room, share of ALL batches that hold: literal run > 32 %.2f %%, plain match > 32 %.2f %%, "
-          "self-overlap offset >= 16 %.2f %%, self-overlap offset < 16 %.2f %%" % tuple(100 * v / nb for v in (hi[3], lo[3], hi[4], lo[4])))
+          "self-overlap offset >= 16 %.2f %%, self-overlap offset < 16 %.2f %%" % tuple(100 * v / nb for v in (hi[3], lo[3], so16, so1)))
+    print("  the piece rule (SEQ_ASM_SELF): %.2f %% of all batches are assembled AND hold a self-overlapping match; "
+          "rounds of assembled batches in which no lane finished: %.2f per such batch" % (100 * a_self / nb, x_rounds / max(a_self, 1)))
     n_dir = nb - lo[0]
     print("  ticks per batch: assembled %.0f, direct %.0f; per output byte: assembled %.3f (mean %.0f B), direct %.3f (mean %.0f B)" % (
         t_asm / max(lo[0], 1), t_dir / max(n_dir, 1), t_asm / max(hi[7], 1), hi[7] / max(lo[0], 1), t_dir / max(lo[7], 1), lo[7] / max(n_dir, 1)))

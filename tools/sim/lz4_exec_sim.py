@@ -32,6 +32,97 @@ def sequences(d):
     return out
 
 
+DEP_ROUNDS = 4                  # SEQ_DEP_ROUNDS of seq_exec.h
+OWN_MAX = 32                    # SEQ_OWN_MAX
+ROUND_GUARD = 64 * 6 + 16       # the round guard of an assembled batch under the piece rule (a match of 32 bytes at offset 1: 6 pieces)
+
+
+def dependencies(recs):
+    """seq_dependencies of seq_exec.h, lane by lane: recs = [(ms, ml, off)] in batch positions (ml = 0: no match) ->
+    (src, need) per lane: the possibly re-pointed source of the first min(ml, off) bytes and the set of earlier lanes whose match output
+    must be final before it is read.  One search for the earlier matches the source touches; a source wholly inside the externally
+    sourced part of exactly ONE of them is re-pointed at that match's source, DEP_ROUNDS rounds of pointer jumping, every lane
+    reading its candidate's (delta, need, inside) as they stood before the round."""
+    n = len(recs)
+    src = [ms - off for ms, ml, off in recs]
+    nl = [min(ml, off) for ms, ml, off in recs]
+    need = [frozenset()] * n
+    inside = [-1] * n
+    for k, (ms, ml, off) in enumerate(recs):
+        e = src[k] + nl[k]
+        if ml == 0 or e <= 0:
+            continue
+        need[k] = frozenset(j for j in range(k) if recs[j][1] and recs[j][0] < e and recs[j][0] + recs[j][1] > src[k])
+        if len(need[k]) == 1:
+            j = next(iter(need[k]))
+            if recs[j][0] <= src[k] and e <= recs[j][0] + nl[j]:
+                inside[k] = j
+    for _ in range(DEP_ROUNDS):
+        if all(i < 0 for i in inside):
+            break
+        delta = [recs[k][0] - src[k] for k in range(n)]
+        need0, inside0 = list(need), list(inside)
+        for k in range(n):
+            j = inside0[k]
+            if j >= 0:
+                src[k] -= delta[j]; need[k] = need0[j]; inside[k] = inside0[j]
+    return src, need
+
+
+def exec_assembled(history, bs, guard=ROUND_GUARD, refine=False):
+    """One assembled batch under the piece rule, as section 3a of seq_exec.h executes it.  history: the output in front of the batch;
+    bs = [(literal bytes, ml, off)] (ml = 0: no match; every ml <= OWN_MAX).  -> (the batch's bytes, rounds), or (None, rounds) when the
+    guard trips or no lane is ready.  Per lane d = where its match output continues, rem = bytes still to write, s = source position,
+    av = bytes valid at s; a ready lane copies L = min(rem, av) bytes and goes on from its own start: s = ms, d += L, rem -= L,
+    av = d - ms.  All loads of a round come before its stores, as in one wave instruction.
+    refine: the variant that was compiled and not shipped (profiles/r30): a match whose source was not re-pointed and lies in the batch
+    keeps reading at ms - off, av = d - (ms - off), so its pieces are off, 2 off, 4 off ...: one step fewer."""
+    recs, pos = [], 0
+    for lit, ml, off in bs:
+        assert ml <= OWN_MAX
+        recs.append((pos + len(lit), ml, off))
+        pos += len(lit) + ml
+    total, H = pos, len(history)
+    buf = bytearray(history) + bytearray(total)             # batch position x is buf[H + x]
+    src, need = dependencies(recs)
+    n = len(bs)
+    d = [r[0] for r in recs]; rem = [r[1] for r in recs]; av = [min(r[1], r[2]) for r in recs]; s = list(src)
+    early = [recs[k][1] != 0 and src[k] + av[k] <= 0 for k in range(n)]
+    home = [recs[k][0] - recs[k][2] if refine and not early[k] and src[k] == recs[k][0] - recs[k][2] else recs[k][0] for k in range(n)]
+    first = {}
+    for k in range(n):                                      # literals and the first pieces of the early matches: loads, then stores
+        if early[k]:
+            assert H + s[k] >= 0
+            first[k] = bytes(buf[H + s[k]:H + s[k] + av[k]])
+    for k, (lit, ml, off) in enumerate(bs):
+        buf[H + recs[k][0] - len(lit):H + recs[k][0]] = lit
+        if early[k]:
+            L = av[k]
+            buf[H + d[k]:H + d[k] + L] = first[k]
+            s[k] = recs[k][0]; d[k] += L; rem[k] -= L; av[k] = d[k] - recs[k][0]
+            need[k] = frozenset()                           # it goes on from its own output
+    done = set(k for k in range(n) if rem[k] == 0)          # lanes without a match, and early matches that are complete
+    pending = set(range(n)) - done
+    rounds = 0
+    while pending:
+        ready = [k for k in sorted(pending) if need[k] <= done]
+        rounds += 1
+        if not ready or rounds > guard:
+            return None, rounds
+        loads = {}
+        for k in ready:
+            L = min(rem[k], av[k])
+            assert H + s[k] >= 0 and s[k] + L <= d[k]
+            loads[k] = (L, bytes(buf[H + s[k]:H + s[k] + L]))
+        for k in ready:
+            L, v = loads[k]
+            buf[H + d[k]:H + d[k] + L] = v
+            s[k] = home[k]; d[k] += L; rem[k] -= L; av[k] = d[k] - home[k]
+            if rem[k] == 0:
+                done.add(k); pending.discard(k)
+    return bytes(buf[H:]), rounds
+
+
 def batch_stats(seqs, B, st):
     n = len(seqs)
     for b0 in range(0, n, B):
@@ -43,6 +134,15 @@ def batch_stats(seqs, B, st):
             recs.append((pos, ms, me, ms - off, min(ml, off), off, ml))
             pos = me
         st["batches"] += 1; st["seqs"] += len(bs); st["bytes"] += pos
+        if "piece_batches" in st and all(ml <= OWN_MAX for ll, ml, off in bs):
+            # the piece rule: rounds of the batch were it assembled (the bytes do not matter here), against the same without its
+            # self-overlapping matches' further pieces
+            hist = bytes(max([off for ll, ml, off in bs if ml], default=0))
+            r = exec_assembled(hist, [(bytes(ll), ml, off) for ll, ml, off in bs])[1]
+            so = any(ml > off for ll, ml, off in bs)
+            st["piece_batches"] += 1; st["piece_rounds"] += r
+            st["piece_self_batches"] += so; st["piece_self_rounds"] += r * so
+            st["piece_rounds_hist"][min(r, 15)] += 1
         # classify
         pend = []
         for k, (ls, ms, me, s, nl, off, ml) in enumerate(recs):
@@ -124,7 +224,7 @@ def main():
     B = int(sys.argv[3]) if len(sys.argv) > 3 else 64
     b = dg.Batch(n, 65536, method=dg.LZ4, level=0, seed=1, mix=mix, threads=4)
     st = dict(batches=0, seqs=0, bytes=0, matches=0, early=0, pending=0, coop=0, pend_nodep=0, rounds_exact=0, rounds_jump=0, rounds_water=0,
-              jump_early=0, pend_hist=np.zeros(65, int), rounds_exact_hist=np.zeros(16, int), rounds_jump_hist=np.zeros(16, int))
+              jump_early=0, piece_batches=0, piece_rounds=0, piece_self_batches=0, piece_self_rounds=0, piece_rounds_hist=np.zeros(16, int), pend_hist=np.zeros(65, int), rounds_exact_hist=np.zeros(16, int), rounds_jump_hist=np.zeros(16, int))
     lls = []; mls = []; offs = []
     for i in range(b.n):
         fr = b.archive[int(b.offsets[i]):int(b.offsets[i] + b.comp_sizes[i])]
@@ -143,6 +243,10 @@ def main():
         st["matches"] / nb, st["early"] / nb, st["pending"] / nb, st["pend_nodep"] / nb, st["coop"] / nb))
     print("  rounds per batch: exact deps %.2f | exact + full re-pointing %.2f (re-pointed to early: %.1f/batch) | watermark %.2f" % (
         st["rounds_exact"] / nb, st["rounds_jump"] / nb, st["jump_early"] / nb, st["rounds_water"] / nb))
+    print("  piece rule, batches without a piece longer than %d (%.1f %%): %.2f rounds per batch; those holding a self-overlapping match (%.1f %%): %.2f" % (
+        OWN_MAX, 100.0 * st["piece_batches"] / nb, st["piece_rounds"] / max(st["piece_batches"], 1),
+        100.0 * st["piece_self_batches"] / nb, st["piece_self_rounds"] / max(st["piece_self_batches"], 1)))
+    print("  piece rule rounds hist:", st["piece_rounds_hist"].tolist())
     print("  pending histogram (0..64, by 8):", [int(st["pend_hist"][i:i + 8].sum()) for i in range(0, 65, 8)])
     print("  rounds exact hist:", st["rounds_exact_hist"].tolist())
     print("  rounds jump  hist:", st["rounds_jump_hist"].tolist())

@@ -484,7 +484,7 @@ __device__ inline int lz4_block_wave(Lz4WaveShared& sh, Watchdog& wd, SeqStats& 
             }
             int rc;
             if constexpr (EMIT) { (void)dead; rc = emit(q, cnt, (u32)(q.lit - ipb)); }
-            else rc = seq_exec_batch<true, COOP, SEQ_ASM_LONG_LIT != 0>(q, cnt, op, oend, dst_lo, -1, lane, stt, B.S, to_lds_rw(sh.stage), dead);
+            else rc = seq_exec_batch<true, COOP, SEQ_ASM_LONG_LIT != 0, SEQ_ASM_SELF != 0>(q, cnt, op, oend, dst_lo, -1, lane, stt, B.S, to_lds_rw(sh.stage), dead);
             if (rc != D_OK) { op_io = op; return rc; }
         }
         if (fl) return D_MALFORMED;                                            // (not reached: the executor saw the malformed token)

@@ -17,6 +17,9 @@
 //   4. rounds: all lanes whose dependencies are done copy at once (short, non-overlapping matches by
 //      their own lane; long or self-overlapping ones by the whole wave, period handled with a modulo);
 //      the done mask is a ballot.  The lowest unfinished sequence is always ready, so the loop ends.
+//      In a batch assembled in LDS (section 3a) a self-overlapping match of at most 32 bytes is copied by its own lane as well, in
+//      pieces through the same round body (the LZ4 decoder, SELF_ASM: off, off, 2 off, 4 off ... bytes, each piece read from the
+//      match's own start; the lane counts as done when the last piece is written).
 //
 // One round costs about one HBM/L2 round trip for up to 64 sequences, where the serial decoder paid one
 // or two round trips per sequence.
@@ -240,7 +243,9 @@ struct SeqStats { u64 t_parse, t_lit, t_dep, t_rounds; u32 rounds, batches, coop
     // why a batch was not assembled (ZPK_STATS_ASM, tools/lw_stats.py): no room only / a long piece only / both / straddle only; of the batches
     // that had the room, those with a literal run > SEQ_OWN_MAX, a plain match > SEQ_OWN_MAX, a self-overlapping match of offset >= 16, < 16
     // (a batch counts once per kind); ticks and output bytes of assembled against direct batches
-    u32 r_room, r_piece, r_both, r_straddle, k_lit, k_match, k_so16, k_so1; u64 t_asm, t_dir; u32 b_asm, b_dir; };
+    u32 r_room, r_piece, r_both, r_straddle, k_lit, k_match, k_so16, k_so1; u64 t_asm, t_dir; u32 b_asm, b_dir;
+    // SELF_ASM: batches assembled that hold a self-overlapping match, and rounds of assembled batches in which no lane finished
+    u32 a_self, x_rounds; };
 #define SEQ_T() __builtin_amdgcn_s_memtime()
 #define SEQ_STAT(x) do { x; } while (0)
 #else
@@ -263,6 +268,15 @@ struct SeqStats { };
 #ifndef SEQ_ASM_LONG_LIT
 #define SEQ_ASM_LONG_LIT 1
 #endif
+// SELF_ASM of seq_exec_batch as the LZ4 decoder sets it: an assembled batch may hold self-overlapping matches of at most SEQ_OWN_MAX bytes,
+// which their lanes copy in pieces through the round body (0 = such a batch takes the direct path, as it did before: developer A/B).
+// The Zstandard callers leave SELF_ASM off.
+#ifndef SEQ_ASM_SELF
+#define SEQ_ASM_SELF 1
+#endif
+// rounds an assembled batch may take: a match of SEQ_OWN_MAX bytes at offset 1 is 6 pieces (1, 1, 2, 4, 8, 16), and in a chain of 64 such
+// matches, each reading the end of the one before, only one lane moves per round: 64 x 6, plus slack.  Without SELF_ASM a lane moves once.
+#define SEQ_ASM_ROUNDS_SELF (64u * 6u + 16u)
 // Batch assembly buffer (optional, LDS, per wave): SEQ_ASM_PRE bytes of history, the batch output, 16 bytes of
 // read slack.
 #define SEQ_ASM_PRE 32u
@@ -348,7 +362,7 @@ __device__ __forceinline__ u64 seq_dependencies(bool has_match, u32 r_ms, u32 r_
 // batch's literals in lit_stage (the LZ4 caller hands over everything before the next batch's first token): the
 // literals are read before the first store there.  Its first SEQ_ASM_PRE bytes must not (lz4_wave.h says why they
 // never do).  A batch whose output fits (SEQ_ASM_PRE + total + SEQ_ASM_SLACK <= asm_cap) and that has no long or
-// self-overlapping piece (LONG_LIT: match) is ASSEMBLED IN LDS: literals and matches are written there, in-batch sources are
+// self-overlapping piece (LONG_LIT: match; SELF_ASM: no match longer than SEQ_OWN_MAX) is ASSEMBLED IN LDS: literals and matches are written there, in-batch sources are
 // read back from there at LDS latency instead of a store->load round trip through L2, and the finished batch
 // goes to memory as one contiguous 16-bytes-per-lane stream — one or two full store instructions instead of
 // ~17 partially filled ones.
@@ -362,7 +376,20 @@ __device__ __forceinline__ u64 seq_dependencies(bool has_match, u32 r_ms, u32 r_
 // path changes: +3.7 % vector instructions, +18 % wait cycles; instruction-cache misses are nil), as a real call (__noinline__) 31 %:
 // profiles/r05/r05_coop_variants_ab.txt.  So k_classify sends the LZ4 entries that are mostly runs (compressed to less than an eighth)
 // to k_lz4_left, built with COOP = 2, and k_lz4_wave is the code it was.
-template <bool NARROW_ONLY = false, int COOP = 2, bool LONG_LIT = false>
+// SELF_ASM (the piece rule): a self-overlapping match of at most SEQ_OWN_MAX bytes, any offset, no longer keeps a batch direct.  In an
+// assembled batch a lane may take several passes through the SAME round body.  Per lane: d = where its match output continues (starts at
+// r_ms), rem = bytes still to write (ml), s = source position (the possibly re-pointed src), av = bytes valid at s (need_len = min(ml,
+// off)).  A ready lane copies L = min(rem, av) bytes with the two lds_ld128 and the lds_store_wide32 of a plain match, then
+//     s = r_ms; d += L; rem -= L; av = d - r_ms;
+// from its second piece on the match reads its own start, so the pieces are off, off, 2 off, 4 off ...: every piece begins at a multiple
+// of the period, which makes the copy exact.  For a plain match L == ml and nothing changes.  A lane joins `done` only in the round in
+// which rem reaches 0, so a lane that reads the match's output waits for all of it.  The dependency analysis is unchanged: its
+// containment test uses need_len, the externally sourced part, so a reader inside a self-overlapping match's first period is re-pointed
+// (window[x] == window[x - offset] holds there) and any other reader of its output waits.  A match whose first period lies wholly in
+// older output is early: need_len bytes go out with the early loads and stores, and the lane stays pending, with an empty need, while
+// rem > 0.  Self-overlapping matches longer than SEQ_OWN_MAX and long plain matches still send the batch down the direct path, which
+// does not change.
+template <bool NARROW_ONLY = false, int COOP = 2, bool LONG_LIT = false, bool SELF_ASM = false>
 __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& op, u8* oend, const u8* dst_lo, int lit_rle, int lane,
                                               SeqStats& stt, lds_cp8 lit_stage = nullptr, lds_p8 asm_buf = nullptr, u32 asm_cap = 0)
 {
@@ -410,27 +437,39 @@ __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& o
     const bool coop = has_match && (ml > SEQ_OWN_MAX || self_overlap);
     // matches whose whole source is older than this batch go out together with the literals
     const bool early = has_match && !coop && src + (i64)need_len <= 0;
+    // SELF_ASM: what keeps a batch out of the assembly (a match longer than SEQ_OWN_MAX), and what is early inside one (no `!coop`:
+    // no assembled batch holds such a match)
+    // (long_a is written through `coop` on purpose: the mask is then formed ahead of the section.  Formed on the direct path only, the
+    // compiler takes the block pointer out of its scalar registers for the whole batch loop of k_lz4_wave: 54 lane accesses of scalar
+    // spills instead of 42, profiles/r30/r30_isa_static_counts.txt.  This steers register allocation and nothing else; it is fragile, and
+    // tests/test_lz4_lean_isa_cpu.py, which counts those accesses, is what guards it.)
+    const bool long_a = SELF_ASM && coop && ml > SEQ_OWN_MAX;
+    const bool early_s = SELF_ASM && has_match && src + (i64)need_len <= 0;
+#define SEQ_COOP_A (SELF_ASM ? long_a : coop)
+#define SEQ_EARLY_A (SELF_ASM ? early_s : early)
     SEQ_STAT({ u64 t1 = SEQ_T(); stt.t_dep += t1 - t0; t0 = t1; });
 
 #ifdef ZPK_STATS
         if (lit_rle < 0 && NARROW_ONLY) {            // (the LZ4 decoder: its assembly buffer is the stage, LDS address 0)
             const bool fits = total + (SEQ_ASM_PRE + SEQ_ASM_SLACK) <= (u64)asm_cap;
             const u64 kl = __ballot(ll > SEQ_OWN_MAX), km = __ballot(has_match && !self_overlap && ml > SEQ_OWN_MAX);
-            const u64 k16 = __ballot(has_match && self_overlap && q.off >= 16u), k1 = __ballot(has_match && self_overlap && q.off < 16u);
+            // (SELF_ASM: a self-overlapping match keeps a batch direct, and counts as a piece, only when it is longer than SEQ_OWN_MAX)
+            const bool so_piece = has_match && self_overlap && (!SELF_ASM || ml > SEQ_OWN_MAX);
+            const u64 k16 = __ballot(so_piece && q.off >= 16u), k1 = __ballot(so_piece && q.off < 16u);
             const bool piece = ((LONG_LIT ? 0ull : kl) | km | k16 | k1) != 0;
             if (!fits) { if (piece) stt.r_both++; else stt.r_room++; }
             else {
                 if (piece) stt.r_piece++;
-                else if (__ballot(has_match && !early && src < 0) != 0 && (u64)(op - dst_lo) < SEQ_ASM_PRE) stt.r_straddle++;
+                else if (__ballot(has_match && !SEQ_EARLY_A && src < 0) != 0 && (u64)(op - dst_lo) < SEQ_ASM_PRE) stt.r_straddle++;
                 stt.k_lit += kl != 0; stt.k_match += km != 0; stt.k_so16 += k16 != 0; stt.k_so1 += k1 != 0;
             }
         }
 #endif
     // ---- 3a. assembly in LDS ----
     if (lit_rle < 0 && total + (SEQ_ASM_PRE + SEQ_ASM_SLACK) <= (u64)asm_cap) {
-        const bool straddle = has_match && !early && src < 0;                       // source begins before the batch, ends inside
+        const bool straddle = has_match && !SEQ_EARLY_A && src < 0;                       // source begins before the batch, ends inside
         const u64 sm = __ballot(straddle);
-        if (__ballot(coop || (!LONG_LIT && ll > SEQ_OWN_MAX)) == 0 && (sm == 0 || (u64)(op - dst_lo) >= SEQ_ASM_PRE)) {
+        if (__ballot(SEQ_COOP_A || (!LONG_LIT && ll > SEQ_OWN_MAX)) == 0 && (sm == 0 || (u64)(op - dst_lo) >= SEQ_ASM_PRE)) {
             SEQ_STAT(stt.asm_batches++);
             const lds_p8 ob = asm_buf + SEQ_ASM_PRE;                                // batch position 0
             // (asm_buf may cover this batch's own literals in lit_stage from byte SEQ_ASM_PRE on — the history bytes in front of
@@ -451,11 +490,45 @@ __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& o
                     lds_st128(p + at, ld128(q.lit + at));
                 }
             }
-            const u32 mn = early ? ml : 0u;
+            const u32 mn = SEQ_EARLY_A ? (SELF_ASM ? need_len : ml) : 0u;
             const Copy32 cb = gload_wide32(srcp, mn, srcp + 16 <= oend);
             lds_store_wide32(ob + (r_ms - ll), ca, ln);
             lds_store_wide32(ob + r_ms, cb, mn);
             wave_mem_fence();
+            if constexpr (SELF_ASM) {
+                // the piece rule (above): s, av and rem take the places of src, need_len and ml, which are dead behind this point
+                i32 s = (i32)src;                                                   // s >= -SEQ_ASM_PRE for every lane that loads from LDS
+                if (early_s) { s = (i32)r_ms; need = 0; }                           // an early match goes on from its own output: nothing else feeds it
+                u32 d = r_ms + mn, rem = ml - mn, av = need_len;                    // (an early match has written need_len bytes: they are valid at s)
+                // a lane is pending while it has bytes to write, and every other lane is done: `pending` alone carries both
+                pending = __ballot(rem != 0);
+#ifdef ZPK_STATS
+                if (__ballot(self_overlap) != 0) stt.a_self++;
+#endif
+                // one exit: `guard` runs out after SEQ_ASM_ROUNDS_SELF rounds, and at once in a round in which no lane copies (no progress)
+                u32 guard = SEQ_ASM_ROUNDS_SELF;
+                while (pending != 0 && guard != 0) {
+                    const bool ready = rem != 0 && (need & pending) == 0;
+                    const u64 rmask = __ballot(ready);                              // the lanes that copy in this round
+                    guard = rmask != 0 ? guard - 1u : 0u;
+                    SEQ_STAT(stt.rounds++);
+                    if (ready) {
+                        const u32 L = rem < av ? rem : av;
+                        const lds_cp8 sp = (lds_cp8)(ob + s);
+                        Copy32 c; c.hi.lo = c.hi.hi = 0;
+                        c.lo = lds_ld128(sp);
+                        if (L > 16) c.hi = lds_ld128(sp + (L - 16));
+                        lds_store_wide32(ob + d, c, L);
+                        s = (i32)r_ms; d += L; rem -= L; av = d - r_ms;
+                    }
+                    wave_mem_fence();
+                    SEQ_STAT(stt.x_rounds += __ballot(rem != 0) == pending);
+                    pending = __ballot(rem != 0);
+                }
+                if (pending != 0) return D_MALFORMED;
+            }
+            // (SELF_ASM: nothing is pending here and the compiler drops the loop below.  It stays un-nested, and the two conditions above
+            // are folded in place, so that with SELF_ASM off every kernel compiles to the code it was: profiles/r30/r30_code_objects.md)
             u64 done = ~pending | __ballot(early);
             pending &= ~done;
             u32 guard = 0;
@@ -488,6 +561,9 @@ __device__ __forceinline__ int seq_exec_batch(const SeqBatch& q, int cnt, u8*& o
             return D_OK;
         }
     }
+
+#undef SEQ_COOP_A
+#undef SEQ_EARLY_A
 
     // ---- 3. literals + early matches: every load is issued before the first store ----
     if (lit_rle >= 0) {

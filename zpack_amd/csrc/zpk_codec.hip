@@ -311,7 +311,9 @@ __device__ __forceinline__ void lz4_stats_out(u64* __restrict__ dbg, u32 e, cons
 #endif
 #ifdef ZPK_STATS_ASM
         g[0] = ((u64)stt.batches << 32) | stt.asm_batches; g[1] = ((u64)stt.r_room << 32) | stt.r_piece; g[2] = ((u64)stt.r_both << 32) | stt.r_straddle;
-        g[3] = ((u64)stt.k_lit << 32) | stt.k_match; g[4] = ((u64)stt.k_so16 << 32) | stt.k_so1; g[5] = stt.t_asm; g[6] = stt.t_dir;
+        g[3] = ((u64)stt.k_lit << 32) | stt.k_match; g[5] = stt.t_asm; g[6] = stt.t_dir;
+        // word 4: four counters of 16 bits (each fits them per entry): self-overlapping offset >= 16, < 16, assembled with a self-overlapping match, its extra rounds
+        g[4] = ((u64)(stt.k_so16 & 0xFFFFu) << 48) | ((u64)(stt.k_so1 & 0xFFFFu) << 32) | ((u64)(stt.a_self & 0xFFFFu) << 16) | (stt.x_rounds & 0xFFFFu);
         g[7] = ((u64)stt.b_asm << 32) | stt.b_dir;
 #endif
     }
