@@ -112,6 +112,34 @@ ZPACK_EXPORT int zpack_amd_read_files_device_delta(zpack_reader* reader, zpack_f
                                                    void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
                                                    const void* const* d_bases, int* results, void* dctx);
 
+/* ---- the BASE of a delta entry, checked on the device before it is applied --------------------------------------------------------------
+ * A delta entry's hash is over its STORED bytes, so a read against the wrong base — the checkpoint of another step, the same step after
+ * an optimizer update, a buffer of the right size from another tensor — decodes, verifies, returns ZPACK_OK and hands out garbage; with
+ * d_bases[i] == d_buffers[i] it overwrites the only copy of the previous checkpoint with it.  The two calls below close that: the writing
+ * side hashes its bases where they lie and keeps the values (there is no new write call; the .zpk format does not record them), the
+ * reading side hands them back in and the library hashes the bases it is given before it applies them.
+ *
+ * zpack_amd_hash_device.  hashes[i] = XXH3-64 (seed 0) of the sizes[i] bytes of device memory at d_ptrs[i], any alignment, hashed on
+ *   the device — one wave per span, a large span by the whole chip; nothing but the hashes crosses the bus.  The value is the `hash` field
+ *   the reference writes for an entry with those plain bytes, so a tensor in device memory can also be compared with a plain archive's
+ *   entry without reading it.  sizes[i] == 0 gives the hash of the empty input and d_ptrs[i] is not looked at.  Synchronous.  dctx: a
+ *   context of zpack_create_dctx whose devices include the pointers' (else ZPACK_ERROR_NOT_AVAILABLE), or NULL: a context of the call's
+ *   own, created and freed inside it.  Pointers, device and errors as for the calls above: all on ONE device, ZPACK_ERROR_STREAM_INVALID
+ *   for a NULL array with count > 0 or a span that is not that many bytes of one allocation (nothing has run), ZPACK_ERROR_NOT_AVAILABLE
+ *   without a device.
+ * zpack_amd_read_files_device_delta_checked.  zpack_amd_read_files_device_delta with base_hashes[i], the XXH3-64 the base of entry i has
+ *   to have (host memory, count values; the value of an entry with d_bases[i] == NULL is ignored).  base_hashes == NULL IS the _delta
+ *   call, the same code.  An entry with a base is delivered only when its base hashes to its value.  When it does not, NO byte of
+ *   d_buffers[i] is written — in place, the previous checkpoint survives — and, exactly where the entry would otherwise have been
+ *   delivered (ZPACK_OK or ZPACK_ERROR_FILE_HASH_MISMATCH), results[i] is ZPACK_AMD_ERROR_BASE_MISMATCH; every other result stays the
+ *   entry's own.  The call still returns ZPACK_OK: one bad entry does not stop the others.  reader->last_return follows the rule of the
+ *   _delta call with that result.  Every kind of reader. */
+#define ZPACK_AMD_ERROR_BASE_MISMATCH 64     /* a value of results[i] beside enum zpack_result (zpack.h), which ends at ZPACK_ERROR_NOT_AVAILABLE = 24 */
+ZPACK_EXPORT int zpack_amd_hash_device(const void* const* d_ptrs, const size_t* sizes, zpack_u64 count, zpack_u64* hashes, void* dctx);
+ZPACK_EXPORT int zpack_amd_read_files_device_delta_checked(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                                           void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
+                                                           const void* const* d_bases, const zpack_u64* base_hashes, int* results, void* dctx);
+
 /* ---- the archive IMAGE in DEVICE memory -------------------------------------------------------------------------------------------
  * A third kind of reader beside the memory-backed and the file-backed one: the archive lies in device memory — a data set or checkpoint
  * kept compressed in HBM, an archive that arrived by a device-to-device transfer — and its compressed bytes never cross the bus.

@@ -58,7 +58,9 @@ extern "C" {
                                         zpk_codec_plane_copy_device, the _planes forms of _encode_batch_dsrc, _encode_batch_dsink, _decode_batch_host_dptr and _decode_batch_dimage,
                                         zpk_codec_planes_stats: byte-plane entries, split and joined in the copies.
                                         zpk_codec_delta_copy_device, the _delta forms of the same four calls, zpk_codec_delta_stats: delta entries, a tensor stored as its XOR
-                                        against a base in device memory.) */
+                                        against a base in device memory.
+                                        zpk_codec_hash_spans_device, ZPK_OPT_SPAN_HASH_MIN, the _delta_checked forms of the two reads that take bases, ZPK_R_BASE_MISMATCH,
+                                        zpk_codec_base_check_stats: the base of a delta entry is hashed on the device before it is applied.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -157,11 +159,15 @@ int         zpk_codec_device(const zpk_codec* c);
  *                                   hash mismatch come from there only).  Default 256 KiB; the least size taken is 1025; 0 = never.
  *   ZPK_OPT_DIMAGE_CHUNK            zpk_codec_decode_batch_dimage, zpk_codec_encode_batch_dsink: bytes of staging slots per sub-batch (an entry
  *                                   whose slot is larger goes alone).  0 = the default, ZPK_HOST_CHUNK_BYTES (4 GiB): what
- *                                   zpk_codec_decode_batch_host cuts by. */
+ *                                   zpk_codec_decode_batch_host cuts by.
+ *   ZPK_OPT_SPAN_HASH_MIN           zpk_codec_hash_spans_device and the base check of the _delta_checked reads: a span of at least `value`
+ *                                   bytes is hashed by the whole chip — one wave per 64 KiB, then one short chain — instead of by one
+ *                                   wave.  Default 256 KiB; the least size taken is 1025; 0 = never. */
 /* (2..5 were the opt-in two-stage LZ4 path of round 4 and its measurement aids: measured slower than the one-kernel decoder, removed in round 5) */
 enum { ZPK_OPT_ENC_SPLIT_MIN = 6, ZPK_OPT_DEC_SPLIT_MIN = 7, ZPK_OPT_ORDER_MIN = 8, ZPK_OPT_ORDER_FAST_LAST = 9 /* a batch of ONE size class runs the entries that did not compress (a copy to decode) last: 1 (default) / 0 */ };
 #define ZPK_OPT_STORED_SPAN_MIN 10
 #define ZPK_OPT_DIMAGE_CHUNK 11
+#define ZPK_OPT_SPAN_HASH_MIN 12
 int         zpk_codec_set_option(zpk_codec* c, int option, int value);
 
 /* ---- batch decode + verify ----------------------------------------------------------------
@@ -431,6 +437,40 @@ int zpk_codec_decode_batch_dimage_delta(zpk_codec* c, const uint8_t* d_archive, 
  * k_delta_copy launches, out[3] entries that decoded into the staging only because they had a base (element size 1).
  * zpk_codec_planes_stats keeps its meaning: it counts the rows of k_plane_copy, which are those without a base. */
 int zpk_codec_delta_stats(zpk_codec* c, uint32_t out[4]);
+
+/* ---- the BASE of a delta entry, checked on the device before it is applied (k_span_hash) ------------------------------------------------
+ * The XXH3 of a delta entry is over its STORED bytes: a read against the wrong base — another step's checkpoint, the same step after an
+ * optimizer update, a buffer of the right size from another tensor — decodes, verifies and hands out garbage, and with base ==
+ * destination it overwrites the only copy of the previous checkpoint with it.  The writer's side hashes its bases, the reader's side
+ * hands the values back in, and the codec hashes the bases it is given before it joins anything.
+ *
+ * zpk_codec_hash_spans_device: XXH3-64 (seed 0: XXH3_64bits, the `hash` of an entry with those plain bytes) of n spans of DEVICE memory on
+ * the codec's device, any alignment, out_hashes[i] that of [rows[i].addr, + rows[i].len).  rows and out_hashes are HOST memory; rows is
+ * consumed and out_hashes is written before the call returns (the call waits for `stream`, NULL = the codec's own).  len 0 gives the
+ * hash of the empty input and its address is not looked at.  Rows below ZPK_OPT_SPAN_HASH_MIN take one wave each, all in one launch; the
+ * others go chip-wide.  Nothing outside the spans is read.  A row that fails the pointer check of zpk_codec_decode_batch_host_dptr:
+ * ZPK_E_INVALID and nothing has run. */
+typedef struct zpk_hash_span { uint64_t addr, len; } zpk_hash_span;
+int zpk_codec_hash_spans_device(zpk_codec* c, const zpk_hash_span* rows, uint64_t n, uint64_t* out_hashes, void* stream);
+/* The two _delta reads with one more argument: base_hash[i] is the XXH3-64 the base of entry i has to have (HOST memory, n values).
+ * base_hash == NULL IS the _delta call, the same body; the value of an entry with d_base[i] == NULL is ignored.
+ * THE RULE: an entry with a base is delivered only when its base hashes to base_hash[i].  When it does not, no byte of its destination is
+ * written — with base == destination the previous checkpoint survives — and, exactly where the entry would otherwise have been
+ * delivered (status OK or FILE_HASH_MISMATCH), results[i].status is ZPK_R_BASE_MISMATCH; every other status stays the entry's own.
+ * hash, produced and detail are the _delta call's.  All bases are hashed in one pass in front of the decode; every verdict is known
+ * before the first entry is delivered. */
+#define ZPK_R_BASE_MISMATCH 64       /* a per-entry status beside enum zpack_result, whose values end at 24 */
+int zpk_codec_decode_batch_host_dptr_delta_checked(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
+                                                   const zpk_decode_desc* desc, uint64_t n,
+                                                   uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                                   const uint64_t* base_hash);
+int zpk_codec_decode_batch_dimage_delta_checked(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size,
+                                                const zpk_decode_desc* desc, uint64_t n,
+                                                uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                                const uint64_t* base_hash);
+/* the most recent of the three calls above (or of a read they extend): out[0] spans hashed by one wave, out[1] spans hashed chip-wide,
+ * out[2] bases that did not hash to their value, out[3] kernel launches of the hash pass */
+int zpk_codec_base_check_stats(zpk_codec* c, uint32_t out[4]);
 
 /* zpk_codec_encode_batch_device for batches that hold LARGE entries: d_src, d_dst and d_results are DEVICE pointers, `desc` is HOST memory
  * (consumed before the call returns).  An entry with size >= ZPK_OPT_ENC_SPLIT_MIN, size > 512 KiB and a valid method is compressed as

@@ -21,6 +21,8 @@ K_CLASSIFY, K_STORED, K_LZ4, K_ZSTD, K_ZSTD_FSE, K_PACK, K_ENCODE = 0, 1, 2, 3, 
 OPT_ENC_SPLIT_MIN, OPT_DEC_SPLIT_MIN, OPT_ORDER_MIN, OPT_ORDER_FAST_LAST = 6, 7, 8, 9      # zpk_codec_set_option (include/zpack_codec.h)
 OPT_STORED_SPAN_MIN = 10
 OPT_DIMAGE_CHUNK = 11
+OPT_SPAN_HASH_MIN = 12
+R_BASE_MISMATCH = 64                         # ZPK_R_BASE_MISMATCH: the per-entry status of a delta entry whose base did not hash to its value
 
 # zpk_decode_desc / zpk_decode_result / zpk_encode_desc / zpk_encode_result (include/zpack_codec.h)
 DECODE_DESC = np.dtype([("src_offset", "<u8"), ("comp_size", "<u8"), ("uncomp_size", "<u8"), ("expect_hash", "<u8"),
@@ -35,6 +37,8 @@ PLANE_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u8"), ("elem", 
 assert PLANE_COPY.itemsize == 32
 DELTA_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("base", "<u8"), ("len", "<u8"), ("elem", "<u4"), ("join", "<u4")])   # zpk_delta_copy
 assert DELTA_COPY.itemsize == 40
+HASH_SPAN = np.dtype([("addr", "<u8"), ("len", "<u8")])                                                         # zpk_hash_span
+assert HASH_SPAN.itemsize == 16
 
 _lib = None
 
@@ -81,6 +85,9 @@ def lib():
         if hasattr(L, "zpk_codec_delta_copy_device"):         # (likewise: delta entries)
             L.zpk_codec_delta_copy_device.argtypes = [vp, vp, u64, vp]
             L.zpk_codec_delta_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
+        if hasattr(L, "zpk_codec_hash_spans_device"):         # (likewise: spans hashed on the device, the base check)
+            L.zpk_codec_hash_spans_device.argtypes = [vp, vp, u64, vp, vp]
+            L.zpk_codec_base_check_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.zpk_codec_pack_batch_device.argtypes = [vp, u8p, vp, vp, u64, u8p, u64, vp, u64, vp]
         L.zpk_codec_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
         L.zpk_codec_compress_bound.restype = C.c_size_t
@@ -425,6 +432,24 @@ class Codec:
         a = (C.c_uint32 * 4)()
         self._chk(self.L.zpk_codec_delta_stats(self.h, a), "zpk_codec_delta_stats")
         return dict(split=a[0], joined=a[1], launches=a[2], staged=a[3])
+
+    def hash_spans_device(self, rows, stream=None):
+        """rows: HASH_SPAN array of (device address, len), any alignment: the XXH3-64 (seed 0) of each span as a uint64 array — rows below
+        OPT_SPAN_HASH_MIN one wave each in one k_span_hash launch, the others chip-wide.  Synchronous: the hashes are home on return.
+        Raises on ZPK_E_INVALID (a span the pointer check turned down: nothing has run)."""
+        self._settle(stream)
+        rows = np.ascontiguousarray(rows, dtype=HASH_SPAN)
+        out = np.zeros(len(rows), dtype=np.uint64)
+        self._chk(self.L.zpk_codec_hash_spans_device(self.h, rows.ctypes.data, len(rows), out.ctypes.data, C.c_void_p(stream) if stream else None),
+                  "zpk_codec_hash_spans_device")
+        return out
+
+    def base_check_stats(self):
+        """The most recent call that hashed spans (hash_spans_device, a _delta_checked read): spans hashed by one wave, spans hashed
+        chip-wide, bases that did not hash to their value, kernel launches of the pass."""
+        a = (C.c_uint32 * 4)()
+        self._chk(self.L.zpk_codec_base_check_stats(self.h, a), "zpk_codec_base_check_stats")
+        return dict(wave=a[0], wide=a[1], refused=a[2], launches=a[3])
 
     def planes_stats(self):
         """The most recent call that could split or join byte planes: rows split, rows joined, k_plane_copy launches, entries that decoded

@@ -52,6 +52,9 @@ namespace zpk { void plane_copy_launch(const PlaneCopyRow* d_rows, u32 nrows, u6
 #include "delta_copy_plan.h"                     // delta entries: a tensor stored as its XOR against a base in device memory, and the row table of k_delta_copy (plain C++, likewise)
 // k_delta_copy (delta_copy.h) is compiled in delta_copy.hip, for the same reason
 namespace zpk { void delta_copy_launch(const DeltaCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
+#include "span_hash_plan.h"                      // XXH3 of arbitrary device spans (the bases of delta entries): one-wave and chip-wide rows, their tables, launches and loads (plain C++, likewise)
+// k_span_hash (span_hash.h) and its copies of the chip-wide pair are compiled in span_hash.hip, for the same reason
+namespace zpk { u32 span_hash_launch(u8* d_block, const SpanHashPlan& p, const SpanHashLayout& L, u64 max_wave_rows, u64 max_groups, u64 max_chains, hipStream_t st); }
 // ... and so is k_stored_hash (stored_hash.h, stored_hash.hip): k_stored without the copy, for a batch that has no destination
 namespace zpk { void stored_hash_launch(const u8* src, const zpk_decode_desc* desc, zpk_decode_result* res, const u32* list, const u32* counters, u32 grid, hipStream_t st); }
 #include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
@@ -605,6 +608,7 @@ __global__ __launch_bounds__(256) void k_hash(const u8* __restrict__ src, const 
 
 #define ZPK_ENC_SPLIT_MIN_DEFAULT (2ull << 20)
 #define ZPK_STORED_SPAN_MIN_DEFAULT (256ull << 10) // (round 17: tools/big_batch_device_rate.py --stored, profiles/r17)
+#define ZPK_SPAN_HASH_MIN_DEFAULT ZPK_STORED_SPAN_MIN_DEFAULT // (the same decision for spans that are no entries: tools/base_check_rate.py kernels, profiles/r31)
 #ifndef ZPK_STORED_SPAN_FORK
 #define ZPK_STORED_SPAN_FORK 1                     // zpk_codec_decode_big_batch_device runs the stored spans on a second stream beside the rest of the call; 0: on its own stream, in front of the walk
                                                    // (256 MiB stored + 256 MiB LZ4 text in one call: 14.9-15.2 ms forked against 23.6-23.9 ms serial, every forked run ahead: profiles/r17/r17_fork_ab.txt)
@@ -628,14 +632,19 @@ enum class Dst : int { Host = 0, Device = 1, None = 2 };
 // entry is plain bytes (element size 1).  Handed down as an argument to whatever stages sources or delivers slots.
 // ... and their BASES (delta_copy_plan.h): base[i] of entry i is device memory of the entry's plain size, none (or NULL for an entry) =
 // the entry has no base.  An entry with a base is stored as split(plain XOR base) and is treated wherever an element size above 1 is.
+// ... and the VERDICTS on those bases (the _delta_checked calls): refused[i] != 0 = the base of entry i did not hash to the value the
+// caller recorded for it; none = no base was checked.  The column travels with the other two.
 struct Planes {
     const u8* elem = nullptr;
     const u8* const* base = nullptr;
+    const u8* refused = nullptr;
     u32 of(u64 i) const { return elem ? elem[i] : 1u; }
     const u8* base_of(u64 i) const { return base ? base[i] : nullptr; }
+    bool refused_at(u64 i) const { return refused && refused[i] && base_of(i) != nullptr; }
     bool grouped(u64 i) const { return of(i) > 1 || base_of(i) != nullptr; }         // not a plain copy: k_plane_copy's or k_delta_copy's
-    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr, base ? base + first : nullptr }; }
+    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr, base ? base + first : nullptr, refused ? refused + first : nullptr }; }
     bool any() const { return elem != nullptr || base != nullptr; }
+    inline u64 join_len(u64 i, const zpk_decode_desc& d, const zpk_decode_result& r) const;
 };
 // ZPK_E_INVALID: an element size that is none (plane_elem_valid), before anything is enqueued
 static int planes_check(zpk_codec* c, const u8* elem, u64 n);
@@ -644,6 +653,12 @@ static inline u64 planes_join_len(const zpk_decode_desc& d, const zpk_decode_res
 {
     return (r.status == DEC_R_OK || r.status == DEC_R_FILE_HASH_MISMATCH) && r.produced == d.uncomp_size ? (u64)d.uncomp_size : 0ull;
 }
+// THE BASE RULE, beside it: an entry with a base is delivered only when its base hashes to the value the caller recorded.  A refused
+// entry (Planes::refused_at) is joined with no byte, so its destination — with base == dst the previous checkpoint — stays as it was,
+// and exactly where it would otherwise have been delivered, status OK or FILE_HASH_MISMATCH, its status becomes ZPK_R_BASE_MISMATCH
+// (base_verdicts_mark, once the call's results are final); every other status stays the entry's own.  The verdicts are complete before
+// the call's first row reaches rows_enqueue (base_verdicts runs in front of the routing), so all four delivery sites see them.
+inline u64 Planes::join_len(u64 i, const zpk_decode_desc& d, const zpk_decode_result& r) const { return refused_at(i) ? 0ull : planes_join_len(d, r); }
 // the staging slot of an entry under destination `to` (span_copy_plan.h states the layout for the two kinds that have one)
 static inline u64 staging_slot(Dst to, const zpk_decode_desc& d)
 {
@@ -666,7 +681,8 @@ struct LastCall {
     u32  dsink[2] = {0, 0};                      // zpk_codec_encode_batch_dsink: its sub-batches and the last grid of k_sink_place
     u32  enc_big[2] = {0, 0};                    // zpk_codec_encode_big_device: entries written in pieces, their pieces
     u32  delta[4] = {0, 0, 0, 0};                // zpk_codec_delta_stats: rows split with a base, rows joined with a base, k_delta_copy launches, entries staged only because they had a base
-    void no_planes() { for (int k = 0; k < 4; k++) planes[k] = delta[k] = 0; }      // (a call that could split or join begins with this)
+    u32  base_check[4] = {0, 0, 0, 0};           // zpk_codec_base_check_stats: rows hashed by one wave, rows hashed chip-wide, entries refused for their base, launches of the hash pass
+    void no_planes() { for (int k = 0; k < 4; k++) planes[k] = delta[k] = base_check[k] = 0; }      // (a call that could split or join begins with this)
     u32  planes[4] = {0, 0, 0, 0};               // zpk_codec_planes_stats: rows split, rows joined, k_plane_copy launches, entries staged only because they were grouped
     int  fell_back_fused = 0;                    // the last decode batch could not get its sequence arena and ran the fused decoder only
     // the host-path pipeline decodes one call in several launches: their counters are brought back piece by piece and summed, so that
@@ -677,7 +693,7 @@ struct LastCall {
 
 // Every HIP resource below is owned by the member that names it (codec_res.h): deleting the codec releases all of them.
 // A growable pinned block (PinBuf) is regrown only while nothing on a stream still reads or writes it: a call that uses one drains the
-// stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk: hipStreamSynchronize behind the copy home; sspan.h: the
+// stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk, sh.h: hipStreamSynchronize behind the copy home; sspan.h: the
 // run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the block's next turn
 // (bigenc.h, sc.h, pc.h, dc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
 struct zpk_codec {
@@ -701,6 +717,7 @@ struct zpk_codec {
         u64  enc_split_min = ZPK_ENC_SPLIT_MIN_DEFAULT;    // ZPK_OPT_ENC_SPLIT_MIN: entries of at least this many bytes are written as a sequence of frames
         u64  stored_span_min = ZPK_STORED_SPAN_MIN_DEFAULT; // ZPK_OPT_STORED_SPAN_MIN: stored entries of at least this many bytes go chip-wide
         u64  dimage_chunk = 0;                             // ZPK_OPT_DIMAGE_CHUNK (0 = the default): the staging of one sub-batch of an archive image in device memory (dimage_plan.h)
+        u64  span_hash_min = ZPK_SPAN_HASH_MIN_DEFAULT;    // ZPK_OPT_SPAN_HASH_MIN: spans of at least this many bytes are hashed chip-wide (span_hash_plan.h)
     } opt;
 
     // staging every path shares
@@ -767,6 +784,10 @@ struct zpk_codec {
     struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } pc;
     // ... and that of k_delta_copy (delta_copy_plan.h / delta_copy.h), a third block under the same rule
     struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } dc;
+    // the spans k_span_hash and the chip-wide pair hash (span_hash_plan.h / span_hash.h): tables | hashes | partial sums on the device,
+    // the tables going up and the hashes coming home through a pinned block of its own — a call that hashes spans waits for its stream
+    // behind the copy home, so the block is idle whenever the next call writes it
+    struct { DevBuf<u8> d; PinBuf h; } sh;
 
     // the encoder
     DevBuf<u64> d_seq;                           // sequence lists, one per workgroup
@@ -1109,7 +1130,73 @@ static int bases_check(zpk_codec* c, PtrRule& rule, const Planes& pl, u64 n, Len
         }
     return ZPK_OK;
 }
+
+// XXH3-64 of the spans row(i) = SpanHashRow{ address, len }, i in [0, n), into out[0, n) (HOST memory): the two tables of span_hash_plan.h
+// go up from the codec's pinned block, one pass of launches follows (span_hash_launch: k_span_hash for the short rows, the partial sums
+// and the chains for the long ones), the hashes come home and the stream is waited for.  The addresses have passed the pointer rule.
+// Adds to last.base_check[0], [1] and [3].
+template <class RowFn>
+static int span_hash_run(zpk_codec* c, u64 n, RowFn row, u64* out, hipStream_t st)
+{
+    if (n == 0) return ZPK_OK;
+    if (n > ZPK_SPAN_HASH_MAX_ROWS) { snprintf(c->err, sizeof(c->err), "span hash: %llu rows", (unsigned long long)n); return ZPK_E_INVALID; }
+    const u64 thr = c->opt.span_hash_min;
+    SpanHashPlan sized = { 0, 0, 0, 0 };
+    for (u64 i = 0; i < n; i++) {
+        const u64 len = row(i).len;
+        if (span_hash_wide(len, thr)) { sized.nwide++; sized.part_blocks += xxh3_span_blocks(len); } else sized.nwave++;
+    }
+    const SpanHashLayout L = span_hash_layout(sized);
+    if (!c->sh.h.grow(L.partial)) { snprintf(c->err, sizeof(c->err), "span hash: out of pinned memory"); return ZPK_E_NOMEM; }
+    int rc;
+    if ((rc = grow(c, c->sh.d, L.bytes))) return rc;
+    SpanHashRow* const wave = (SpanHashRow*)(c->sh.h.p + L.wave_rows);
+    SpanHashWide* const wide = (SpanHashWide*)(c->sh.h.p + L.wide_rows);
+    const u64* const home = (const u64*)(c->sh.h.p + L.out);
+    std::vector<u64> kept;
+    try { kept.resize(n); } catch (...) { return ZPK_E_NOMEM; }
+    SpanHashPlan p = { 0, 0, 0, 0 };
+    for (u64 i = 0; i < n; i++) { const SpanHashRow r = row(i); kept[i] = span_hash_emit(r.addr, r.len, thr, wave, wide, p); }
+    HIPCHK(c, hipMemcpyAsync(c->sh.d, c->sh.h.p, L.up_bytes, hipMemcpyHostToDevice, st));
+    const u32 launches = span_hash_launch(c->sh.d, p, L, ZPK_SPAN_HASH_MAX_WAVE_ROWS, ZPK_SPAN_HASH_MAX_GROUPS, ZPK_SPAN_HASH_MAX_CHAINS, st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->sh.h.p + L.out, c->sh.d + L.out, n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (u64 i = 0; i < n; i++) out[i] = home[span_hash_out_slot(kept[i], p.nwave)];
+    c->last.base_check[0] += (u32)p.nwave; c->last.base_check[1] += (u32)p.nwide; c->last.base_check[3] += launches;
+    return ZPK_OK;
+}
+
+// The verdicts of the base rule (beside planes_join_len) for a batch: the bases that are there are hashed in ONE pass on the codec's
+// stream, in front of everything the call enqueues, and compared with base_hash[i]; refused[i] = 1 where they differ.  No bases or no
+// hashes: `refused` stays empty and nothing runs — the call is the _delta call.  (The pass could run on a second stream beside the first
+// sub-batch's decode; it is waited for here instead, which keeps every delivery site behind the verdicts without an event per site —
+// profiles/r31 has what that costs.)
+template <class LenFn>
+static int base_verdicts(zpk_codec* c, const Planes& pl, const u64* base_hash, u64 n, LenFn len, std::vector<u8>& refused)
+{
+    refused.clear();
+    if (!pl.base || !base_hash) return ZPK_OK;
+    try {
+        std::vector<u64> idx;
+        for (u64 i = 0; i < n; i++) if (pl.base[i]) idx.push_back(i);
+        if (idx.empty()) return ZPK_OK;
+        std::vector<u64> h(idx.size());
+        const int rc = span_hash_run(c, idx.size(), [&](u64 k) { return SpanHashRow{ (u64)pl.base[idx[k]], len(idx[k]) }; }, h.data(), c->stream);
+        if (rc) return rc;
+        refused.assign(n, 0);
+        for (u64 k = 0; k < idx.size(); k++) if (h[k] != base_hash[idx[k]]) { refused[idx[k]] = 1; c->last.base_check[2]++; }
+    } catch (...) { return ZPK_E_NOMEM; }
+    return ZPK_OK;
+}
 }  // extern "C++"
+// ... and the status of the refused entries, once the call's results are final
+static void base_verdicts_mark(const std::vector<u8>& refused, const zpk_decode_desc* desc, zpk_decode_result* results, u64 n)
+{
+    for (u64 i = 0; i < n && !refused.empty(); i++)
+        if (refused[i] && (results[i].status == DEC_R_OK || results[i].status == DEC_R_FILE_HASH_MISMATCH) && results[i].produced == desc[i].uncomp_size)
+            results[i].status = ZPK_R_BASE_MISMATCH;                                  // (the condition of planes_join_len, with nothing to join counting as delivered)
+}
 
 // XXH3-64 of `nspans` long spans of `base` (xxh3_span.h): enqueues the upload of the span list and the two kernels; the hashes stay on
 // the device, *d_hash_out says where (inside c->d_xpart, valid until the next call that hashes spans).  `h_spans` must stay as it is
@@ -1564,7 +1651,7 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
     if (to == Dst::Device) {
         // DEVICE destinations: the same bytes — [slot, slot + produced) of every entry — by ONE launch of k_span_copy, no host in between
         // (an entry with an element size above 1 is JOINED on the way, all of it or none: planes_join_len)
-        auto row = [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? planes_join_len(desc[i], results[i]) : (u64)results[i].produced }; };
+        auto row = [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? pl.join_len(i, desc[i], results[i]) : (u64)results[i].produced }; };
         if ((rc = rows_enqueue(c, n, row, pl, PLANE_JOIN, c->stream))) return rc;
         e = hipStreamSynchronize(c->stream);
     } else if (n > 1 && produced_total && produced_total * 2 >= out_total) {
@@ -1716,7 +1803,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
             if (e != hipSuccess) break;
             rc = rows_enqueue(c, P.e1 - P.e0, [&](u64 k2) {
                 const u64 i = P.e0 + k2, p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
-                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? planes_join_len(desc[i], results[i]) : p };
+                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? pl.join_len(i, desc[i], results[i]) : p };
             }, pl.from(P.e0), PLANE_JOIN, c->pipe.s_dn);
         }
     } else
@@ -2045,7 +2132,7 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     }
     if (to == Dst::None) return ZPK_OK;                                                // no destination: the verdicts were all
     if (to == Dst::Device) {                                                           // DEVICE destinations: one launch of k_span_copy
-        auto row = [&](u64 k) { return zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size }; };
+        auto row = [&](u64 k) { return zpk_span_copy{ (u64)(c->d_dst + ooff[k]), (u64)dst_ptrs[be[g0 + k].idx], redo[g0 + k] || pl.refused_at(be[g0 + k].idx) ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size }; };   // (a refused base: no byte, the base rule)
         std::vector<u8> gelem;                                                         // (the group's element sizes and bases, in its own order)
         std::vector<const u8*> gbase;
         if (pl.any()) { gelem.resize(ng); for (u64 k = 0; k < ng; k++) gelem[k] = (u8)pl.of(be[g0 + k].idx); }
@@ -2155,8 +2242,11 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
 
 // zpk_codec_decode_batch_host, zpk_codec_decode_batch_host_dptr and zpk_codec_verify_batch_host: one routing, the destinations host
 // memory, device memory or none (Dst)
+static int decode_batch_host_routed(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                    uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to, const Planes& pl);
+// base_hash (the _delta_checked call; else NULL): the value the base of entry i has to hash to — the base rule, beside planes_join_len
 static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                 uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to, const Planes& pl = Planes())
+                                 uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to, const Planes& pl = Planes(), const u64* base_hash = nullptr)
 {
     const bool ddst = to == Dst::Device;
     if (!c || (n && (!desc || !results || (!dst_ptrs && to != Dst::None)))) return ZPK_E_INVALID;
@@ -2169,6 +2259,19 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
     if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
     if (bases_check(c, rule, pl, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, dst_ptrs)) return ZPK_E_INVALID;
     begin_decode_call(c);
+    // the base rule: every verdict is known before anything of the batch is routed, so before any row reaches rows_enqueue
+    std::vector<u8> refused;
+    int rc = base_verdicts(c, pl, base_hash, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, refused);
+    if (rc) return rc;
+    rc = decode_batch_host_routed(c, archive, archive_size, desc, n, dst_ptrs, results, to, Planes{ pl.elem, pl.base, refused.empty() ? nullptr : refused.data() });
+    if (rc == ZPK_OK) base_verdicts_mark(refused, desc, results, n);
+    return rc;
+}
+// ... what the call does once its arguments have passed: the lock is held, the device is the codec's
+static int decode_batch_host_routed(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                    uint8_t* const* dst_ptrs, zpk_decode_result* results, Dst to, const Planes& pl)
+{
+    const bool ddst = to == Dst::Device;
     // ---- which entries are sequences of frames worth decoding frame-parallel ----
     std::vector<BigEntry> be;
     std::vector<BigSub> subs;
@@ -2224,7 +2327,7 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
                 const u8 k1 = (u8)pl.of(idx);
                 const u8* const b1 = pl.base_of(idx);
                 if (k1 > 1) c->last.planes[3]++; else c->last.delta[3]++;              // (staged because it was grouped; staged only because it had a base)
-                const zpk_span_copy row = { (u64)(u8*)c->d_dst, (u64)dst_ptrs[idx], planes_join_len(desc[idx], results[idx]) };
+                const zpk_span_copy row = { (u64)(u8*)c->d_dst, (u64)dst_ptrs[idx], pl.join_len(idx, desc[idx], results[idx]) };
                 if ((rc = rows_enqueue(c, 1, [&](u64) { return row; }, Planes{ &k1, pl.base ? &b1 : nullptr }, PLANE_JOIN, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
             }
             if (rc == ZPK_OK && !again) is_big[idx] = 1;
@@ -2237,8 +2340,15 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
             std::vector<zpk_decode_result> rr(rest.size());
             std::vector<u8> re(pl.any() ? rest.size() : 0);
             std::vector<const u8*> rb(pl.base ? rest.size() : 0);
-            for (u64 k = 0; k < rest.size(); k++) { rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]]; if (pl.any()) re[k] = (u8)pl.of(rest[k]); if (pl.base) rb[k] = pl.base_of(rest[k]); }
-            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to, Planes{ pl.any() ? re.data() : nullptr, pl.base ? rb.data() : nullptr });
+            std::vector<u8> rf(pl.refused ? rest.size() : 0);
+            for (u64 k = 0; k < rest.size(); k++) {
+                rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]];
+                if (pl.any()) re[k] = (u8)pl.of(rest[k]);
+                if (pl.base) rb[k] = pl.base_of(rest[k]);
+                if (pl.refused) rf[k] = pl.refused[rest[k]];
+            }
+            rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to,
+                                         Planes{ pl.any() ? re.data() : nullptr, pl.base ? rb.data() : nullptr, pl.refused ? rf.data() : nullptr });
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
@@ -2257,10 +2367,17 @@ int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint6
     return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device);
 }
 
+int zpk_codec_decode_batch_host_dptr_delta_checked(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                                   uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                                   const uint64_t* base_hash)
+{
+    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem, d_base }, base_hash);
+}
+
 int zpk_codec_decode_batch_host_dptr_delta(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                            uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base)
 {
-    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem, d_base });
+    return zpk_codec_decode_batch_host_dptr_delta_checked(c, archive, archive_size, desc, n, d_dst_ptrs, results, elem, d_base, nullptr);
 }
 
 int zpk_codec_decode_batch_host_dptr_planes(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
@@ -2332,6 +2449,30 @@ int zpk_codec_delta_stats(zpk_codec* c, uint32_t out[4])
     if (!c || !out) return ZPK_E_INVALID;
     CodecLock lk(c);
     for (int k = 0; k < 4; k++) out[k] = c->last.delta[k];
+    return ZPK_OK;
+}
+
+// XXH3-64 of rows of device memory on their own (k_span_hash and the chip-wide pair): the pointer rule on every row — on refusal nothing
+// has run —, then one pass; the hashes are home when the call returns
+int zpk_codec_hash_spans_device(zpk_codec* c, const zpk_hash_span* rows, uint64_t n, uint64_t* out_hashes, void* stream)
+{
+    if (!c || (n && (!rows || !out_hashes))) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    for (int k = 0; k < 4; k++) c->last.base_check[k] = 0;
+    if (n == 0) return ZPK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    PtrRule rule(c);
+    if (rule.batch("span", n, [&](u64 i) { return (const void*)rows[i].addr; }, [&](u64 i) { return (u64)rows[i].len; })) return ZPK_E_INVALID;
+    return span_hash_run(c, n, [&](u64 i) { return SpanHashRow{ rows[i].addr, rows[i].len }; }, out_hashes, stream ? (hipStream_t)stream : c->stream);
+}
+
+// the most recent call that hashed spans or could have (the _delta_checked reads, the reads they extend): out[0] rows hashed by one wave,
+// out[1] rows hashed chip-wide, out[2] bases that did not hash to their value, out[3] launches of the hash pass
+int zpk_codec_base_check_stats(zpk_codec* c, uint32_t out[4])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    for (int k = 0; k < 4; k++) out[k] = c->last.base_check[k];
     return ZPK_OK;
 }
 
@@ -2566,20 +2707,25 @@ int zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, ui
 // pointers.  The compressed bytes never cross the bus.  (Dst::None — zpk_codec_verify_batch_dimage: the same sub-batches and the same body;
 // nothing is handed over, only descriptors go up and verdicts come home.)
 static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                   uint8_t* const* dst_ptrs, Dst to, zpk_decode_result* results, const Planes& pl = Planes())
+                                   uint8_t* const* dst_ptrs, Dst to, zpk_decode_result* results, const Planes& pl_given = Planes(), const u64* base_hash = nullptr)
 {
     if (!c || (n && (!desc || !results || (!dst_ptrs && to != Dst::None) || !d_archive))) return ZPK_E_INVALID;
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
     c->last.dimage[0] = c->last.dimage[1] = c->last.dimage[2] = 0;
     if (n == 0) return ZPK_OK;
-    if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
+    if (planes_check(c, pl_given.elem, n)) return ZPK_E_INVALID;
     const bool ddst = to == Dst::Device, none = to == Dst::None;
     PtrRule rule(c);                                                                  // the pointer rule: before anything is enqueued
     if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
     if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
-    if (bases_check(c, rule, pl, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, dst_ptrs)) return ZPK_E_INVALID;
+    if (bases_check(c, rule, pl_given, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, dst_ptrs)) return ZPK_E_INVALID;
     begin_decode_call(c);
+    // the base rule (beside planes_join_len): every verdict is known before the first sub-batch is decoded, so before any row reaches
+    // rows_enqueue; the column is cut with the others (Planes::from)
+    std::vector<u8> refused;
+    if (const int vrc = base_verdicts(c, pl_given, base_hash, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, refused)) return vrc;
+    const Planes pl = { pl_given.elem, pl_given.base, refused.empty() ? nullptr : refused.data() };
     const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
     auto slot = [&](u64 i) {                                                          // (no destination: a stored entry has no slot)
         const bool stored = desc[i].method == ZPK_METHOD_NONE;
@@ -2606,6 +2752,7 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
     } catch (...) { rc = ZPK_E_NOMEM; }
     c->last.dimage[1] = c->last.sc;
     c->last.dimage[2] = home_total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)home_total;
+    if (rc == ZPK_OK) base_verdicts_mark(refused, desc, results, n);
     return rc;
 }
 
@@ -2616,12 +2763,19 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
 }
 
 // (element sizes and bases belong to DEVICE destinations: with host destinations every element size has to be 1 and no entry has a base)
-int zpk_codec_decode_batch_dimage_delta(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
-                                        uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base)
+int zpk_codec_decode_batch_dimage_delta_checked(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                                uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                                const uint64_t* base_hash)
 {
     if (!dst_on_device) for (u64 i = 0; i < n; i++) if ((elem && elem[i] != 1) || (d_base && d_base[i])) return ZPK_E_INVALID;
     return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results,
-                                   Planes{ dst_on_device ? elem : nullptr, dst_on_device ? d_base : nullptr });
+                                   Planes{ dst_on_device ? elem : nullptr, dst_on_device ? d_base : nullptr }, base_hash);
+}
+
+int zpk_codec_decode_batch_dimage_delta(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                        uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base)
+{
+    return zpk_codec_decode_batch_dimage_delta_checked(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device, results, elem, d_base, nullptr);
 }
 
 int zpk_codec_decode_batch_dimage_planes(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
@@ -2800,6 +2954,7 @@ int zpk_codec_set_option(zpk_codec* c, int option, int value)
     if (option == ZPK_OPT_DEC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.dec_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     if (option == ZPK_OPT_ENC_SPLIT_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.enc_split_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     if (option == ZPK_OPT_STORED_SPAN_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.stored_span_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
+    if (option == ZPK_OPT_SPAN_HASH_MIN) { if (value < 0) return ZPK_E_INVALID; c->opt.span_hash_min = value == 0 ? ~0ull : (u64)value; return ZPK_OK; }
     if (option == ZPK_OPT_DIMAGE_CHUNK) { if (value < 0) return ZPK_E_INVALID; c->opt.dimage_chunk = (u64)value; return ZPK_OK; }       // (0 = the default: dimage_chunk())
     return ZPK_E_INVALID;
 }

@@ -27,6 +27,17 @@ inplace=True reads into the base tensors themselves: the previous checkpoint bec
 not in the archive; with planes="dtype" the writer appends DELTA_MANIFEST, the names of the delta entries and the caller's `base_id`,
 and planes="manifest" refuses to hand out a delta entry for which no base was given.
 
+The base is checked before it is applied (zpack_amd_hash_device, zpack_amd_read_files_device_delta_checked).  An entry's hash is over its
+stored bytes, so a read against the wrong base would decode, verify and return garbage — in place, over the only copy of the previous
+checkpoint.  With check_base=True the writers hash the bases on the device and record "base_xxh3": {name: 16 hex digits} in
+DELTA_MANIFEST beside the two fields it has (without it the manifest is written as it always was), and read_files_device(...,
+planes="manifest", base=...) of such an archive hashes the bases it is given on the device first: an entry whose base differs comes
+back with status BASE_MISMATCH and its tensor — with inplace=True the base itself — untouched.  `base_id` stays what it was, a string
+of the caller's; check_base=False on the read is the read without the check.
+
+    image = write_archive_device(new, planes="dtype", base=old, base_id="step 1000", check_base=True)  hash_tensors(tensors) gives the same values on their own:
+the `hash` field an archive records for an entry with those bytes.
+
     image = write_archive_device(new, planes="dtype", base=old, base_id="step 1000")
     tensors, statuses = read_files_device(image, planes="manifest", base=old, base_id="step 1000", inplace=True)     # `old` now holds `new`
 
@@ -39,8 +50,9 @@ import os
 from . import ZPACK_SO, METHOD_NONE, METHOD_ZSTD, METHOD_LZ4            # noqa: F401  (the methods are part of this module's interface)
 
 OK, BUFFER_TOO_SMALL, STREAM_INVALID, NOT_AVAILABLE = 0, 12, 21, 24     # enum zpack_result (include/zpack.h)
+BASE_MISMATCH = 64                                                      # ZPACK_AMD_ERROR_BASE_MISMATCH (include/zpack_amd.h): the entry's base is not the one it was written against
 PLANES_MANIFEST = ".zpack_amd/planes.json"                              # the entry write_*(planes="dtype") appends: {name: element size}
-DELTA_MANIFEST = ".zpack_amd/delta.json"                                # ... and with base=: {"entries": [names], "base_id": string or null}
+DELTA_MANIFEST = ".zpack_amd/delta.json"                                # ... and with base=: {"entries": [names], "base_id": string or null, "base_xxh3": {name: 16 hex digits}}
 
 
 class FileEntry(C.Structure):                # zpack_file_entry (include/zpack.h)
@@ -95,6 +107,9 @@ def lib():
         L.zpack_amd_read_files_device_planes.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(C.c_int), vp]
         L.zpack_amd_read_files_device_delta.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(vp),
                                                         C.POINTER(C.c_int), vp]
+        L.zpack_amd_read_files_device_delta_checked.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(vp),
+                                                                C.POINTER(u64), C.POINTER(C.c_int), vp]
+        L.zpack_amd_hash_device.argtypes = [C.POINTER(vp), C.POINTER(C.c_size_t), u64, C.POINTER(u64), vp]
         L.zpack_read_file.argtypes = [R, C.POINTER(FileEntry), vp, C.c_size_t, vp]
         L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
         L.zpack_amd_test_files.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(C.c_int), vp]
@@ -206,11 +221,56 @@ def _read_manifest(L, r):
     return m
 
 
+def _delta_manifest_valid(m):
+    """DELTA_MANIFEST as the writers write it; "base_xxh3" may be missing (archives from before the bases were hashed), but when it is
+    there it is {name: 16 lower-case hex digits} for exactly the names listed under "entries".  A plain function of the parsed JSON."""
+    if not (isinstance(m, dict) and isinstance(m.get("entries"), list) and all(isinstance(k, str) for k in m["entries"])
+            and (m.get("base_id") is None or isinstance(m["base_id"], str))):
+        return False
+    if "base_xxh3" not in m:
+        return True
+    h = m["base_xxh3"]
+    return (isinstance(h, dict) and set(h) == set(m["entries"])
+            and all(isinstance(v, str) and len(v) == 16 and all(ch in "0123456789abcdef" for ch in v) for v in h.values()))
+
+
+def _parse_delta_manifest(m):
+    """(names of the delta entries, recorded base_id or None, {name: the base's XXH3-64} or None) of DELTA_MANIFEST's value; None: no manifest"""
+    if m is None:
+        return [], None, None
+    hashes = m.get("base_xxh3")
+    return m["entries"], m.get("base_id"), None if hashes is None else {k: int(v, 16) for k, v in hashes.items()}
+
+
 def _read_delta_manifest(L, r):
-    """(names of the delta entries, recorded base_id or None) of the opened reader's DELTA_MANIFEST entry; ([], None) when there is none"""
-    m = _read_json_entry(L, r, DELTA_MANIFEST, lambda m: isinstance(m, dict) and isinstance(m.get("entries"), list) and all(isinstance(k, str) for k in m["entries"])
-                         and (m.get("base_id") is None or isinstance(m["base_id"], str)), "{\"entries\": [names], \"base_id\": string or null}")
-    return ([], None) if m is None else (m["entries"], m.get("base_id"))
+    """_parse_delta_manifest of the opened reader's DELTA_MANIFEST entry; raises when it does not parse"""
+    return _parse_delta_manifest(_read_json_entry(L, r, DELTA_MANIFEST, _delta_manifest_valid,
+                                                  "{\"entries\": [names], \"base_id\": string or null, \"base_xxh3\": {name: 16 hex digits}}"))
+
+
+def _hash_flat(L, flats):
+    """XXH3-64 of flat uint8 CUDA tensors, hashed where they lie (zpack_amd_hash_device), as ints"""
+    n = len(flats)
+    if n == 0:
+        return []
+    for d in set(t.device for t in flats):
+        _settle(d)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in flats])
+    sizes = (C.c_size_t * n)(*[t.numel() for t in flats])
+    out = (C.c_uint64 * n)()
+    _check(L.zpack_amd_hash_device(ptrs, sizes, n, out, None), "zpack_amd_hash_device")
+    return [int(out[i]) for i in range(n)]
+
+
+def hash_tensors(tensors):
+    """The XXH3-64 (seed 0) of each tensor's bytes in memory order, computed on the device (zpack_amd_hash_device): the value an archive
+    records as `hash` for an entry with those plain bytes, and the value DELTA_MANIFEST records for a base.  `tensors`: {name: CUDA
+    tensor} -> {name: int}, or a sequence of CUDA tensors -> [int].  All on one device; nothing but the hashes crosses the bus."""
+    if isinstance(tensors, dict):
+        _, flat = _flatten(tensors, "hash_tensors")
+        return dict(zip(tensors.keys(), _hash_flat(lib(), flat)))
+    _, flat = _flatten({str(i): t for i, t in enumerate(tensors)}, "hash_tensors")
+    return _hash_flat(lib(), flat)
 
 
 def _base_bytes(name, t, size):
@@ -223,7 +283,7 @@ def _base_bytes(name, t, size):
     return flat
 
 
-def read_files_device(archive, names=None, device=0, planes=None, base=None, inplace=False, base_id=None):
+def read_files_device(archive, names=None, device=0, planes=None, base=None, inplace=False, base_id=None, check_base=True):
     """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
     compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
     in that order (None: all, in archive order).  `planes`: None — the entries' bytes as they are stored; {name: element size} — those
@@ -233,7 +293,10 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
     docstring); inplace=True: the base tensors are the destinations and are what is returned for their entries — an entry that does not
     decode leaves its base as it was.  With planes="manifest" the archive's DELTA_MANIFEST says which entries are delta entries: one
     of those among the entries read without a base raises KeyError naming it (its bytes alone are not the tensor), and a `base_id`
-    that differs from the recorded one raises ValueError; with names None that entry is left out too.
+    that differs from the recorded one raises ValueError; with names None that entry is left out too.  When the manifest records the
+    bases' hashes ("base_xxh3") the bases given are hashed on the device before they are applied: an entry whose base is another comes back
+    with status BASE_MISMATCH, its tensor — with inplace=True its base — untouched; check_base=False reads without that check, as an
+    archive without the field is read.
     Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
     a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
     import torch
@@ -243,9 +306,10 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
     try:
         picks = _picks(r, names)
         base = dict(base or {})
+        recorded_hash = None
         if planes == "manifest":
             planes = _read_manifest(L, r)
-            delta_names, recorded_id = _read_delta_manifest(L, r)
+            delta_names, recorded_id, recorded_hash = _read_delta_manifest(L, r)
             if names is None:
                 picks = [i for i in picks if r.file_entries[i].filename.decode() not in (PLANES_MANIFEST, DELTA_MANIFEST)]
             if base_id is not None and base_id != recorded_id:
@@ -283,7 +347,15 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
                 if b is not None:
                     _settle(b.device)
             d_bases = (C.c_void_p * max(n, 1))(*[b.data_ptr() if b is not None and b.numel() else None for b in bases])
-            _check(L.zpack_amd_read_files_device_delta(C.byref(r), ents, n, bufs, caps, elem, d_bases, res, None), "zpack_amd_read_files_device_delta")
+            if check_base and recorded_hash is not None:
+                # (a base given for an entry the manifest does not list has no recorded value: its own hash, which passes)
+                unlisted = [k for k, (nm, b) in enumerate(zip(pnames, bases)) if b is not None and nm not in recorded_hash]
+                own = dict(zip(unlisted, _hash_flat(L, [bases[k] for k in unlisted])))
+                want = (C.c_uint64 * max(n, 1))(*[own[k] if k in own else recorded_hash.get(nm, 0) for k, nm in enumerate(pnames)])
+                _check(L.zpack_amd_read_files_device_delta_checked(C.byref(r), ents, n, bufs, caps, elem, d_bases, want, res, None),
+                       "zpack_amd_read_files_device_delta_checked")
+            else:
+                _check(L.zpack_amd_read_files_device_delta(C.byref(r), ents, n, bufs, caps, elem, d_bases, res, None), "zpack_amd_read_files_device_delta")
         elif planes is None:
             _check(L.zpack_amd_read_files_device(C.byref(r), ents, n, bufs, caps, res, None), "zpack_amd_read_files_device")
         else:
@@ -318,8 +390,9 @@ def _elem_sizes(items, planes):
     return elem, json.dumps({name: k for (name, _), k in zip(items, elem)}, separators=(",", ":")).encode()
 
 
-def _bases_of(items, flat, base, base_id, with_manifest):
-    """(the base's bytes per item or None — None when no item has one —, DELTA_MANIFEST's bytes or None) for the `base` argument of the writers"""
+def _bases_of(items, flat, base, base_id, with_manifest, check_base=False):
+    """(the base's bytes per item or None — None when no item has one —, DELTA_MANIFEST's bytes or None) for the `base` argument of the writers;
+    check_base: the manifest also records the bases' XXH3-64, hashed on the device ("base_xxh3")"""
     import json
     if not base:
         return None, None
@@ -333,7 +406,12 @@ def _bases_of(items, flat, base, base_id, with_manifest):
         return bases, None
     if any(name == DELTA_MANIFEST for name, _ in items):
         raise ValueError("%s is the name of the manifest base= writes" % DELTA_MANIFEST)
-    return bases, json.dumps({"entries": [name for name, _ in items if name in base], "base_id": base_id}, separators=(",", ":")).encode()
+    listed = [(name, b) for (name, _), b in zip(items, bases) if b is not None]
+    m = {"entries": [name for name, _ in listed], "base_id": base_id}
+    if check_base:
+        hashes = _hash_flat(lib(), [b for _, b in listed])                            # on the device, where the bases lie
+        m["base_xxh3"] = {name: "%016x" % h for (name, _), h in zip(listed, hashes)}
+    return bases, json.dumps(m, separators=(",", ":")).encode()
 
 
 def _write_archive(L, w, items, flat, method, level, elem=None, manifest=None, bases=None, delta_manifest=None):
@@ -377,17 +455,19 @@ def _write_archive(L, w, items, flat, method, level, elem=None, manifest=None, b
     _check(L.zpack_write_eocdr(C.byref(w)), "zpack_write_eocdr")
 
 
-def write_files_device(path, tensors, method=METHOD_LZ4, level=0, planes=None, base=None, base_id=None):
+def write_files_device(path, tensors, method=METHOD_LZ4, level=0, planes=None, base=None, base_id=None, check_base=False):
     """Writes the archive `path` with one entry per item of `tensors` ({name: CUDA tensor}, all on one device; any dtype: an entry is the
     tensor's bytes in memory order).  path None: the archive is built on the heap and returned as bytes.  `planes`: None — the bytes as
     they are; {name: element size} — those entries are stored as byte planes; "dtype" — the element size of every floating tensor of 2,
     4 or 8 bytes an element, and the PLANES_MANIFEST entry behind the tensors' (the module's docstring).  `base`: {name: CUDA tensor
     with the nbytes of tensors[name]} — those entries are stored as deltas against it; with planes="dtype" the DELTA_MANIFEST entry
-    records their names and `base_id`, a string of the caller's that names the base (None: none)."""
+    records their names and `base_id`, a string of the caller's that names the base (None: none).  check_base=True: the bases are
+    hashed on the device and DELTA_MANIFEST also records "base_xxh3", which makes read_files_device refuse any other base (the
+    module's docstring); the default writes the manifest as it always was."""
     L = lib()
     items, flat = _flatten(tensors, "write_files_device")
     elem, manifest = _elem_sizes(items, planes)
-    bases, delta_manifest = _bases_of(items, flat, base, base_id, manifest is not None)
+    bases, delta_manifest = _bases_of(items, flat, base, base_id, manifest is not None, check_base)
     w = Writer()
     _check(L.zpack_init_writer(C.byref(w), os.fsencode(path)) if path is not None else L.zpack_init_writer_heap(C.byref(w), 0), "zpack_init_writer")
     try:
@@ -407,13 +487,13 @@ def archive_capacity(sizes, names, method):
     return 10 + sum(int(bound(int(method), int(s))) for s in sizes) + 20 + sum(35 + len(n.encode()) for n in names) + 12
 
 
-def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None, planes=None, base=None, base_id=None):
+def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None, planes=None, base=None, base_id=None, check_base=False):
     """Writes an archive with one entry per item of `tensors` ({name: CUDA tensor}, all on one device) INTO DEVICE MEMORY
     (zpack_amd_init_writer_device): header, files, CDR and EOCDR go into a fresh uint8 tensor of `capacity` bytes on the tensors' device
     (None: archive_capacity, which holds whatever the entries compress to), the frames are committed there by the codec's kernels and no
     compressed byte crosses the bus.  Returns the tensor trimmed to the archive's size; it is byte for byte what write_files_device
-    returns for path None.  A capacity that is too small raises (ZPACK_ERROR_BUFFER_TOO_SMALL, 12).  `planes`, `base`, `base_id`:
-    as in write_files_device.
+    returns for path None.  A capacity that is too small raises (ZPACK_ERROR_BUFFER_TOO_SMALL, 12).  `planes`, `base`, `base_id`,
+    `check_base`: as in write_files_device.
 
         image = write_archive_device({"a": ta, "b": tb}, method=METHOD_ZSTD, level=1)
         tensors, statuses = read_files_device(image)                      # zpack_amd_init_reader_device: read where it was written
@@ -422,7 +502,7 @@ def write_archive_device(tensors, method=METHOD_LZ4, level=0, capacity=None, pla
     L = lib()
     items, flat = _flatten(tensors, "write_archive_device")
     elem, manifest = _elem_sizes(items, planes)
-    bases, delta_manifest = _bases_of(items, flat, base, base_id, manifest is not None)
+    bases, delta_manifest = _bases_of(items, flat, base, base_id, manifest is not None, check_base)
     dev = flat[0].device if flat else torch.device("cuda", 0)
     if capacity is None:
         capacity = archive_capacity([t.numel() for t in flat], [name for name, _ in items], method)

@@ -424,19 +424,19 @@ static zpack_u64 entry_weight(const void* entries, zpack_u64 i)
 static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                           zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                           const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int dest, const zpack_u8* elem,
-                          const zpack_u8* const* bases);
+                          const zpack_u8* const* bases, const zpack_u64* base_hashes);
 
 int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                       zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                       const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size)
 {
-    return decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, span, span_lo, span_size, ZI_DST_HOST, NULL, NULL);
+    return decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, span, span_lo, span_size, ZI_DST_HOST, NULL, NULL, NULL);
 }
 
 int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                              zpack_u8* const* d_buffers, const size_t* max_sizes, zpk_decode_result* res)
 {
-    return decode_entries(reader, ctx, entries, count, d_buffers, max_sizes, res, NULL, 0, 0, ZI_DST_DEVICE, NULL, NULL);
+    return decode_entries(reader, ctx, entries, count, d_buffers, max_sizes, res, NULL, 0, 0, ZI_DST_DEVICE, NULL, NULL, NULL);
 }
 
 /* ZI_DST_DEVICE: buffers[i] are DEVICE pointers — the plaintext stays there, only the compressed bytes cross the bus: the batch is one
@@ -444,11 +444,12 @@ int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry
  * ZI_DST_NONE: there are no buffers — the same descriptors, the same gather of a file reader's payloads and the same shard go to the
  * codec's verify calls, and only verdicts come back.
  * elem (ZI_DST_DEVICE only, else NULL): the entries' element sizes — the codec joins the byte planes on the way to the buffers.
- * bases (likewise): the entries' bases in device memory, NULL for an entry that has none — XORed in on the same way */
+ * bases (likewise): the entries' bases in device memory, NULL for an entry that has none — XORed in on the same way
+ * base_hashes (likewise): what each base has to hash to before it is applied (the codec's _delta_checked calls); NULL: no check */
 static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                           zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                           const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int dest, const zpack_u8* elem,
-                          const zpack_u8* const* bases)
+                          const zpack_u8* const* bases, const zpack_u64* base_hashes)
 {
     const int on_device = dest == ZI_DST_DEVICE, none = dest == ZI_DST_NONE;
 #define ZI_CAP(i) (none ? (size_t)entries[i]->uncomp_size : max_sizes[i])
@@ -502,11 +503,11 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
         zpk_codec* codec = zi_ctx_codec_on(ctx, d_device);
         if (!codec) rc = ZPACK_ERROR_NOT_AVAILABLE;
         else if (none) rc = test_rc_of_codec(zpk_codec_verify_batch_dimage(codec, d_image, image_size, desc, count, res));
-        else rc = zi_rc_of_codec(zpk_codec_decode_batch_dimage_delta(codec, d_image, image_size, desc, count, buffers, on_device, res, elem, bases));
+        else rc = zi_rc_of_codec(zpk_codec_decode_batch_dimage_delta_checked(codec, d_image, image_size, desc, count, buffers, on_device, res, elem, bases, base_hashes));
     } else if (rc == ZPACK_OK && on_device) {
         zpk_codec* codec = zi_ctx_codec_of(ctx, buffers, sizeof(*buffers), max_sizes, sizeof(*max_sizes), sizeof(size_t) == 8, count, &rc);
         if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: verdicts only) */
-        if (codec) rc = zi_rc_of_codec(zpk_codec_decode_batch_host_dptr_delta(codec, image, image_size, desc, count, buffers, res, elem, bases));
+        if (codec) rc = zi_rc_of_codec(zpk_codec_decode_batch_host_dptr_delta_checked(codec, image, image_size, desc, count, buffers, res, elem, bases, base_hashes));
     } else if (rc == ZPACK_OK) {
         read_job job = { ctx, image, image_size, desc, buffers, res, {0}, {0} };
         /* static shard: contiguous ranges of the batch balanced by comp + uncomp bytes, one host thread
@@ -522,7 +523,7 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
 
 static int read_batch_planes(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
                              zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int dest, const zpack_u8* elem,
-                             const zpack_u8* const* bases)
+                             const zpack_u8* const* bases, const zpack_u64* base_hashes)
 {
     if (count == 0) return ZPACK_OK;
     if (zi_reader_source(reader, NULL, NULL) == ZI_SRC_NONE) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
@@ -531,7 +532,7 @@ static int read_batch_planes(zpack_reader* reader, zpack_file_entry* const* entr
     if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
     zpk_decode_result* res = (zpk_decode_result*)calloc((size_t)count, sizeof(*res));
     if (!res) return ZPACK_ERROR_MALLOC_FAILED;
-    const int rc = decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0, dest, elem, bases);
+    const int rc = decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0, dest, elem, bases, base_hashes);
     if (rc == ZPACK_OK)
         for (zpack_u64 i = 0; i < count; i++) {
             results[i] = res[i].status;
@@ -544,7 +545,7 @@ static int read_batch_planes(zpack_reader* reader, zpack_file_entry* const* entr
 static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
                       zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int dest)
 {
-    return read_batch_planes(reader, entries, count, buffers, max_sizes, results, dctx, dest, NULL, NULL);
+    return read_batch_planes(reader, entries, count, buffers, max_sizes, results, dctx, dest, NULL, NULL, NULL);
 }
 
 int zpack_read_file(zpack_reader* reader, zpack_file_entry* entry, zpack_u8* buffer, size_t max_size, void* dctx)
@@ -616,16 +617,51 @@ int zpack_amd_read_files_device(zpack_reader* reader, zpack_file_entry* const* e
 }
 
 /* ... whose entries are DELTA entries: entry i has elements of elem_sizes[i] bytes and the base d_bases[i], joined and XORed on the way
- * into d_buffers[i]; d_bases NULL: BYTE-PLANE entries, the same code */
-int zpack_amd_read_files_device_delta(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
-                                      void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes, const void* const* d_bases,
-                                      int* results, void* dctx)
+ * into d_buffers[i]; d_bases NULL: BYTE-PLANE entries, the same code.  base_hashes: what each base has to hash to on the device before
+ * it is applied — an entry whose base does not is ZPACK_AMD_ERROR_BASE_MISMATCH and its buffer is untouched; NULL: the _delta call */
+_Static_assert(ZPACK_AMD_ERROR_BASE_MISMATCH == ZPK_R_BASE_MISMATCH, "results[i] is the codec's status as it is");
+_Static_assert(ZPACK_AMD_ERROR_BASE_MISMATCH > ZPACK_ERROR_NOT_AVAILABLE, "distinct from every value of zpack.h's enum, whose last this is");
+int zpack_amd_read_files_device_delta_checked(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                              void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes, const void* const* d_bases,
+                                              const zpack_u64* base_hashes, int* results, void* dctx)
 {
     if (!reader || (count && (!entries || !d_buffers || !max_sizes || !results))) return ZPACK_ERROR_STREAM_INVALID;
     if (!zi_elem_sizes_valid(elem_sizes, count)) return ZPACK_ERROR_STREAM_INVALID;  /* before any context is created */
     if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
     return read_batch_planes(reader, entries, count, (zpack_u8* const*)d_buffers, max_sizes, results, dctx, ZI_DST_DEVICE, elem_sizes,
-                             (const zpack_u8* const*)d_bases);
+                             (const zpack_u8* const*)d_bases, base_hashes);
+}
+
+int zpack_amd_read_files_device_delta(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                      void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes, const void* const* d_bases,
+                                      int* results, void* dctx)
+{
+    return zpack_amd_read_files_device_delta_checked(reader, entries, count, d_buffers, max_sizes, elem_sizes, d_bases, NULL, results, dctx);
+}
+
+/* XXH3-64 of `count` spans of device memory, hashed where they lie (zpk_codec_hash_spans_device on the codec of the pointers' device):
+ * the value the reference records as `hash` for an entry with those plain bytes.  dctx NULL: a context of the call's own. */
+int zpack_amd_hash_device(const void* const* d_ptrs, const size_t* sizes, zpack_u64 count, zpack_u64* hashes, void* dctx)
+{
+    if (count && (!d_ptrs || !sizes || !hashes)) return ZPACK_ERROR_STREAM_INVALID;
+    if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
+    if (count == 0) return ZPACK_OK;
+    zi_ctx* own = NULL;
+    zi_ctx* ctx = (zi_ctx*)dctx;
+    if (!ctx) ctx = own = zi_ctx_create();
+    if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;
+    int rc = ZPACK_OK;
+    zpk_codec* codec = zi_ctx_codec_of(ctx, d_ptrs, sizeof(*d_ptrs), sizes, sizeof(*sizes), sizeof(size_t) == 8, count, &rc);
+    if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                              /* (nothing has bytes: the hash of the empty input) */
+    zpk_hash_span* rows = codec ? (zpk_hash_span*)malloc(sizeof(zpk_hash_span) * (size_t)count) : NULL;
+    if (codec && !rows) rc = ZPACK_ERROR_MALLOC_FAILED;
+    if (rows) {
+        for (zpack_u64 i = 0; i < count; i++) { rows[i].addr = (uint64_t)(uintptr_t)d_ptrs[i]; rows[i].len = sizes[i]; }
+        rc = zi_rc_of_codec(zpk_codec_hash_spans_device(codec, rows, count, hashes, NULL));
+        free(rows);
+    }
+    if (own) zi_ctx_destroy(own);
+    return rc;
 }
 
 int zpack_amd_read_files_device_planes(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
