@@ -173,7 +173,11 @@ int         zpk_codec_set_option(zpk_codec* c, int option, int value);
 /* ---- batch decode + verify ----------------------------------------------------------------
  * Device-resident form: every pointer is a DEVICE pointer on the codec's device; work is enqueued on
  * `stream` (a hipStream_t passed as void*, NULL = the codec's own stream) and the call returns without
- * synchronising.  `src` is the archive image (or any packed frame stream), `n` descriptors. */
+ * synchronising.  `src` is the archive image (or any packed frame stream), `n` descriptors.
+ * `dst`, dst_offset and dst_capacity need no alignment, and slots may touch and lie in any order: nothing outside
+ * [dst_offset, dst_offset + dst_capacity) of an entry is written, whatever its verdict, and nothing at all for an entry that is refused
+ * before it is decoded (dst_capacity < uncomp_size, a slot that leaves dst).  The first `produced` bytes of a slot are the plaintext;
+ * what lies behind them inside the slot is not specified. */
 int zpk_codec_decode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src_size,
                                   const zpk_decode_desc* desc, uint64_t n,
                                   uint8_t* dst, uint64_t dst_size,
