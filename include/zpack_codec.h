@@ -504,7 +504,22 @@ int zpk_codec_encode_stats(zpk_codec* c, uint32_t out[8]);
  * is not NULL the payloads are gathered there back-to-back from their slots (`slots` + desc[i].dst_offset), i.e. the
  * archive's data section in CDR order.  Device pointers, asynchronous on `stream`.  `max_entry_size` = an upper bound
  * of any comp_size (e.g. the largest dst_capacity); it only sizes the launch.  If packed_cap < offsets[n] the bytes
- * that do not fit are not written (check offsets[n]). */
+ * that do not fit are not written (check offsets[n]).
+ * Pinned by tests/test_gpu_pack_alone.py (the call alone against numpy, `results` and `desc` written by the test):
+ * SHORT BUFFER: `offsets` is the whole scan whatever packed_cap is — offsets[n] > packed_cap tells the caller.  No byte at or
+ *   behind packed + packed_cap is written; every entry that ends at or in front of packed_cap is whole; of an entry that
+ *   crosses it, each byte in front of packed_cap is either its payload's or untouched (whole 16 KiB spans of it are dropped,
+ *   which ones is not promised).  Nothing behind packed + offsets[n] and nothing in front of `packed` is written; `slots`,
+ *   `desc` and `results` are only read, and a failed entry's comp_size is never looked at.
+ * ZPK_E_INVALID, twice: n > 2^31 - 1, judged before anything is allocated or enqueued; and, with `packed`,
+ *   n * max(1, ceil(max_entry_size / 16384)) > 2^30 - 1 (the gather's launch would not fit): this one is found BEHIND the
+ *   scans, which are already enqueued — `offsets` may be written, `packed` is not.
+ * max_entry_size below a real comp_size: the launch has n * ceil(max_entry_size / 16384) waves for the batch's 16 KiB
+ *   spans, counted through the batch in order; spans beyond that number — the tail of such an entry where it is the only
+ *   one, otherwise the end of the batch — stay ungathered, without a diagnostic (offsets are right all the same).  A bound
+ *   that is too large costs idle waves only.
+ * NOT safe from two streams at once on one codec: the block sums and the span table are scratch of the codec's (d_pack),
+ *   shared by every call; calls on ONE stream follow each other correctly. */
 int zpk_codec_pack_batch_device(zpk_codec* c, const uint8_t* slots, const zpk_encode_desc* desc,
                                 const zpk_encode_result* results, uint64_t n,
                                 uint8_t* packed, uint64_t packed_cap, uint64_t* offsets,
