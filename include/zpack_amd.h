@@ -140,6 +140,39 @@ ZPACK_EXPORT int zpack_amd_read_files_device_delta_checked(zpack_reader* reader,
                                                            void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
                                                            const void* const* d_bases, const zpack_u64* base_hashes, int* results, void* dctx);
 
+/* ---- WINDOW reads: a slice of an entry delivered to device memory -------------------------------------------------------------------------
+ * A checkpoint is often loaded under another layout than it was written under: tensor-parallel ranks that each own rows or columns of
+ * every weight, a pipeline stage that needs part of an embedding.  Such a reader needs a SLICE of every tensor, and the calls above make
+ * it allocate every tensor whole and cut its part out with a second pass.  A WINDOW is a 2-D sub-block of an entry's plain bytes seen
+ * as a matrix of rows x row_bytes; the copy that delivers the entry writes it densely into a buffer of window size, joining the byte
+ * planes and XORing the base on the way.  All fields in bytes; row_bytes == 0: no window, the entry whole.
+ * For an entry of n = uncomp_size plain bytes with element size k = elem_sizes[i] (1 without) a window is VALID when row_bytes > 0,
+ *   n % row_bytes == 0, row_bytes, col0 and cols are multiples of k, col0 + cols <= row_bytes and row0 + rows <= n / row_bytes, no sum
+ *   wrapping.  window_bytes = rows * cols, which may be 0.  Byte d of the buffer, d in [0, window_bytes), is plain byte
+ *   (row0 + d / cols) * row_bytes + col0 + d % cols of the entry, XOR byte d of the base when there is one.
+ * A slice [start, stop) along dimension `dim` of a contiguous tensor of `shape` and `itemsize` is the window
+ *   row_bytes = shape[dim] * inner, row0 = 0, rows = prod(shape[:dim]), col0 = start * inner, cols = (stop - start) * inner,
+ *   with inner = prod(shape[dim + 1:]) * itemsize.
+ *
+ * zpack_amd_read_files_device_windows.  zpack_amd_read_files_device_delta_checked with windows[i], the window of entry i (host memory,
+ *   count values).  windows == NULL IS that call, the same code.  Every kind of reader.  For an entry with a window:
+ *   d_buffers[i], d_bases[i] and base_hashes[i] are about window_bytes bytes — the base is the caller's shard of the previous checkpoint,
+ *     indexed like the buffer; d_bases[i] == d_buffers[i] exactly is legal.
+ *   max_sizes[i] < window_bytes: results[i] is ZPACK_ERROR_BUFFER_TOO_SMALL where zpack_read_file's guards, in their order, would say so
+ *     of too small a buffer, nothing of the entry is decoded and nothing is written.
+ *   Otherwise results[i] is what zpack_amd_test_files gives the entry (the tail of a short decode counts as zeros: a window buffer is
+ *     no buffer of uncomp_size bytes), and ZPACK_AMD_ERROR_BASE_MISMATCH by the rule above.
+ *   The bytes are the map above when the entry decoded to all of its uncomp_size bytes (ZPACK_OK or ZPACK_ERROR_FILE_HASH_MISMATCH) and
+ *     its base was accepted; otherwise the buffer is untouched.
+ * A window that is not valid, or a base of a windowed entry that overlaps its buffer other than by being it, is
+ *   ZPACK_ERROR_STREAM_INVALID, judged before any context is created or anything is enqueued: no result is set.
+ * Entries without a window in the same call, the return value and reader->last_return: as in the _delta_checked call. */
+typedef struct zpack_amd_window { zpack_u64 row_bytes, row0, rows, col0, cols; } zpack_amd_window;
+ZPACK_EXPORT int zpack_amd_read_files_device_windows(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                                     void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
+                                                     const void* const* d_bases, const zpack_u64* base_hashes,
+                                                     const zpack_amd_window* windows, int* results, void* dctx);
+
 /* ---- the archive IMAGE in DEVICE memory -------------------------------------------------------------------------------------------
  * A third kind of reader beside the memory-backed and the file-backed one: the archive lies in device memory — a data set or checkpoint
  * kept compressed in HBM, an archive that arrived by a device-to-device transfer — and its compressed bytes never cross the bus.

@@ -60,7 +60,9 @@ extern "C" {
                                         zpk_codec_delta_copy_device, the _delta forms of the same four calls, zpk_codec_delta_stats: delta entries, a tensor stored as its XOR
                                         against a base in device memory.
                                         zpk_codec_hash_spans_device, ZPK_OPT_SPAN_HASH_MIN, the _delta_checked forms of the two reads that take bases, ZPK_R_BASE_MISMATCH,
-                                        zpk_codec_base_check_stats: the base of a delta entry is hashed on the device before it is applied.) */
+                                        zpk_codec_base_check_stats: the base of a delta entry is hashed on the device before it is applied.
+                                        zpk_codec_window_copy_device, the _windows forms of the same two reads, zpk_codec_window_stats: a 2-D sub-block of an entry
+                                        delivered densely to device memory.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -475,6 +477,56 @@ int zpk_codec_decode_batch_dimage_delta_checked(zpk_codec* c, const uint8_t* d_a
 /* the most recent of the three calls above (or of a read they extend): out[0] spans hashed by one wave, out[1] spans hashed chip-wide,
  * out[2] bases that did not hash to their value, out[3] kernel launches of the hash pass */
 int zpk_codec_base_check_stats(zpk_codec* c, uint32_t out[4]);
+
+/* ---- WINDOW reads: a 2-D sub-block of an entry delivered to device memory (k_window_copy) ----------------------------------------------
+ * A reader that owns part of every tensor — a tensor-parallel rank, a pipeline stage — otherwise reads each entry whole into a full-size
+ * scratch buffer and cuts its part out with a second pass.  A WINDOW is a sub-block of the entry's plain bytes seen as a matrix of
+ * rows x row_bytes; the copy that delivers the entry writes it densely into a destination of window size, joining the byte planes and
+ * XORing the base on the way.  All fields in bytes; row_bytes == 0: no window, the entry whole.  For an entry of n plain bytes with
+ * element size k the window is valid when row_bytes > 0, n % row_bytes == 0, row_bytes, col0 and cols are multiples of k,
+ * col0 + cols <= row_bytes and row0 + rows <= n / row_bytes (no sum may wrap).  window_bytes = rows * cols, which may be 0.  For
+ * destination byte d in [0, window_bytes):
+ *     i(d)   = (row0 + d / cols) * row_bytes + col0 + d % cols
+ *     dst[d] = stored[index_k(i(d))] ^ (base ? base[d] : 0)          index_k: where the byte-plane layout above keeps plain byte i
+ * The base is indexed by DESTINATION byte: it is the caller's shard of the previous checkpoint, of window size.  A slice [start, stop)
+ * along dimension `dim` of a contiguous tensor of `shape` and `itemsize` is the window row_bytes = shape[dim] * inner, row0 = 0,
+ * rows = prod(shape[:dim]), col0 = start * inner, cols = (stop - start) * inner, with inner = prod(shape[dim + 1:]) * itemsize.
+ *
+ * zpk_codec_window_copy_device: the kernel on its own.  rows[0, n) is HOST memory, consumed before the call returns; src is the entry's
+ * n stored bytes, dst and base (0: none) have window_bytes bytes; DEVICE addresses on the codec's device, any alignment.  base == dst
+ * exactly is legal.  A window that is not valid, an element size outside {1, 2, 4, 8}, any other overlap of base and destination, or
+ * an end that fails the pointer check of zpk_codec_decode_batch_host_dptr (no bytes pass): ZPK_E_INVALID and nothing has run.
+ * Asynchronous on `stream` (NULL = the codec's own). */
+typedef struct zpk_window { uint64_t row_bytes, row0, rows, col0, cols; } zpk_window;
+typedef struct zpk_window_copy { uint64_t src, dst, base, n; zpk_window win; uint32_t elem, pad; } zpk_window_copy;
+int zpk_codec_window_copy_device(zpk_codec* c, const zpk_window_copy* rows, uint64_t n, void* stream);
+/* the rule on its own, instance-free, no device needed: 1 = `win` is a valid window of an entry of n plain bytes with element size elem
+ * (*bytes, when not NULL, becomes window_bytes), 0 = it is not (row_bytes == 0 included) */
+int zpk_codec_window_valid(uint64_t n, uint32_t elem, const zpk_window* win, uint64_t* bytes);
+/* ... and the overlap rule of a valid window: 1 = base == dst or the two ranges of window_bytes bytes are disjoint */
+int zpk_codec_window_overlap_ok(uint64_t base, uint64_t dst, const zpk_window* win);
+/* The two _delta_checked reads with one more argument: win[i] is the window of entry i (HOST memory, n values).  win == NULL IS the
+ * _delta_checked call, the same body; win[i].row_bytes == 0: entry i is read whole.  For an entry with a window the destination, the
+ * base and base_hash[i] are about window_bytes bytes, and desc[i].dst_capacity is the room at the destination: with less than
+ * window_bytes the entry is BUFFER_TOO_SMALL where the guards, in their order, say so, and nothing is written.  Otherwise the entry
+ * decodes into the codec's staging with a slot of uncomp_size, a large frame too — its verdict is that of a buffer of exactly that
+ * size — and is delivered through k_window_copy, whatever its element size or base, only when
+ * it decoded to all of its uncomp_size bytes (status OK or a hash mismatch) and its base was not refused; for every other status no
+ * byte of its buffer is written.  The tail of a short decode counts as zeros, as in zpk_codec_verify_batch_host.  A window that is not
+ * valid against desc[i].uncomp_size and elem[i], a window with host destinations, or a base that overlaps its destination other than by
+ * being it: ZPK_E_INVALID and nothing has run.  A batch without windows launches exactly what the _delta_checked call launches. */
+int zpk_codec_decode_batch_host_dptr_windows(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
+                                             const zpk_decode_desc* desc, uint64_t n,
+                                             uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                             const uint64_t* base_hash, const zpk_window* win);
+int zpk_codec_decode_batch_dimage_windows(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size,
+                                          const zpk_decode_desc* desc, uint64_t n,
+                                          uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                          const uint64_t* base_hash, const zpk_window* win);
+/* the most recent of the three calls above (or of a call that could split or join): out[0] rows windowed, out[1] k_window_copy launches,
+ * out[2] entries that decoded into the staging only because they had a window (element size 1, no base).  zpk_codec_planes_stats and
+ * zpk_codec_delta_stats keep their meaning: they count the rows of k_plane_copy and k_delta_copy, which are those without a window. */
+int zpk_codec_window_stats(zpk_codec* c, uint32_t out[3]);
 
 /* zpk_codec_encode_batch_device for batches that hold LARGE entries: d_src, d_dst and d_results are DEVICE pointers, `desc` is HOST memory
  * (consumed before the call returns).  An entry with size >= ZPK_OPT_ENC_SPLIT_MIN, size > 512 KiB and a valid method is compressed as

@@ -39,6 +39,29 @@ DELTA_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("base", "<u8"), ("len", 
 assert DELTA_COPY.itemsize == 40
 HASH_SPAN = np.dtype([("addr", "<u8"), ("len", "<u8")])                                                         # zpk_hash_span
 assert HASH_SPAN.itemsize == 16
+WINDOW = np.dtype([("row_bytes", "<u8"), ("row0", "<u8"), ("rows", "<u8"), ("col0", "<u8"), ("cols", "<u8")])           # zpk_window (and zpack_amd_window)
+WINDOW_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("base", "<u8"), ("n", "<u8"), ("win", WINDOW), ("elem", "<u4"), ("pad", "<u4")])   # zpk_window_copy
+assert WINDOW.itemsize == 40 and WINDOW_COPY.itemsize == 80
+
+
+def slice_window(shape, dim, start, stop, itemsize=1):
+    """The window (a WINDOW record's five values, in bytes) of the slice [start, stop) along dimension `dim` of a contiguous tensor of
+    `shape` whose elements have `itemsize` bytes (include/zpack_codec.h states the formula).  ValueError: dim, start or stop out of range."""
+    shape = [int(s) for s in shape]
+    if not shape or any(s < 0 for s in shape):
+        raise ValueError("shape %r" % (shape,))
+    if not -len(shape) <= dim < len(shape):
+        raise ValueError("dim %d of a %d-d shape" % (dim, len(shape)))
+    dim %= len(shape)
+    if not 0 <= start <= stop <= shape[dim]:
+        raise ValueError("[%d, %d) of %d along dim %d" % (start, stop, shape[dim], dim))
+    outer = inner = 1
+    for s in shape[:dim]:
+        outer *= s
+    for s in shape[dim + 1:]:
+        inner *= s
+    inner *= int(itemsize)
+    return (shape[dim] * inner, 0, outer, start * inner, (stop - start) * inner)
 
 _lib = None
 
@@ -88,6 +111,11 @@ def lib():
         if hasattr(L, "zpk_codec_hash_spans_device"):         # (likewise: spans hashed on the device, the base check)
             L.zpk_codec_hash_spans_device.argtypes = [vp, vp, u64, vp, vp]
             L.zpk_codec_base_check_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
+        if hasattr(L, "zpk_codec_window_copy_device"):        # (likewise: window reads)
+            L.zpk_codec_window_copy_device.argtypes = [vp, vp, u64, vp]
+            L.zpk_codec_window_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
+            L.zpk_codec_window_valid.argtypes = [u64, C.c_uint32, vp, C.POINTER(u64)]
+            L.zpk_codec_window_overlap_ok.argtypes = [u64, u64, vp]
         L.zpk_codec_pack_batch_device.argtypes = [vp, u8p, vp, vp, u64, u8p, u64, vp, u64, vp]
         L.zpk_codec_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
         L.zpk_codec_compress_bound.restype = C.c_size_t
@@ -432,6 +460,23 @@ class Codec:
         a = (C.c_uint32 * 4)()
         self._chk(self.L.zpk_codec_delta_stats(self.h, a), "zpk_codec_delta_stats")
         return dict(split=a[0], joined=a[1], launches=a[2], staged=a[3])
+
+    def window_copy_device(self, rows, stream=None):
+        """rows: WINDOW_COPY array of (src address, dst address, base address or 0, n, window, elem): one k_window_copy launch — the window
+        of the n stored bytes at src, joined and XORed with the base, densely to dst (include/zpack_codec.h states the map); base == dst
+        is legal.  Asynchronous on `stream` (None: the codec's own; synchronise the device before reading the destinations).  Raises on
+        ZPK_E_INVALID (a window, a pointer or an overlap the check turned down: nothing has run)."""
+        self._settle(stream)
+        rows = np.ascontiguousarray(rows, dtype=WINDOW_COPY)
+        self._chk(self.L.zpk_codec_window_copy_device(self.h, rows.ctypes.data, len(rows), C.c_void_p(stream) if stream else None),
+                  "zpk_codec_window_copy_device")
+
+    def window_stats(self):
+        """The most recent call that could split, join or cut a window: rows windowed, k_window_copy launches, entries that decoded into
+        the staging only because they had a window."""
+        a = (C.c_uint32 * 3)()
+        self._chk(self.L.zpk_codec_window_stats(self.h, a), "zpk_codec_window_stats")
+        return dict(rows=a[0], launches=a[1], staged=a[2])
 
     def hash_spans_device(self, rows, stream=None):
         """rows: HASH_SPAN array of (device address, len), any alignment: the XXH3-64 (seed 0) of each span as a uint64 array — rows below

@@ -52,6 +52,9 @@ namespace zpk { void plane_copy_launch(const PlaneCopyRow* d_rows, u32 nrows, u6
 #include "delta_copy_plan.h"                     // delta entries: a tensor stored as its XOR against a base in device memory, and the row table of k_delta_copy (plain C++, likewise)
 // k_delta_copy (delta_copy.h) is compiled in delta_copy.hip, for the same reason
 namespace zpk { void delta_copy_launch(const DeltaCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
+#include "window_copy_plan.h"                    // window reads: a 2-D sub-block of an entry delivered densely, the rule, the map and the row table of k_window_copy (plain C++, likewise)
+// k_window_copy (window_copy.h) is compiled in window_copy.hip, for the same reason
+namespace zpk { void window_copy_launch(const WindowCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
 #include "span_hash_plan.h"                      // XXH3 of arbitrary device spans (the bases of delta entries): one-wave and chip-wide rows, their tables, launches and loads (plain C++, likewise)
 // k_span_hash (span_hash.h) and its copies of the chip-wide pair are compiled in span_hash.hip, for the same reason
 namespace zpk { u32 span_hash_launch(u8* d_block, const SpanHashPlan& p, const SpanHashLayout& L, u64 max_wave_rows, u64 max_groups, u64 max_chains, hipStream_t st); }
@@ -634,16 +637,27 @@ enum class Dst : int { Host = 0, Device = 1, None = 2 };
 // the entry has no base.  An entry with a base is stored as split(plain XOR base) and is treated wherever an element size above 1 is.
 // ... and the VERDICTS on those bases (the _delta_checked calls): refused[i] != 0 = the base of entry i did not hash to the value the
 // caller recorded for it; none = no base was checked.  The column travels with the other two.
+// ... and their WINDOWS (window_copy_plan.h; the _windows reads): win[i].row_bytes != 0 = of entry i only that sub-block is delivered,
+// densely, to a destination — and against a base — of window_bytes bytes; none (or row_bytes == 0 for an entry) = the entry whole.  An
+// entry with a window is treated wherever a grouped entry is, whatever its element size or base.  The fourth column, cut and gathered
+// with the other three.
 struct Planes {
     const u8* elem = nullptr;
     const u8* const* base = nullptr;
     const u8* refused = nullptr;
+    const zpk_window* win = nullptr;
     u32 of(u64 i) const { return elem ? elem[i] : 1u; }
     const u8* base_of(u64 i) const { return base ? base[i] : nullptr; }
     bool refused_at(u64 i) const { return refused && refused[i] && base_of(i) != nullptr; }
-    bool grouped(u64 i) const { return of(i) > 1 || base_of(i) != nullptr; }         // not a plain copy: k_plane_copy's or k_delta_copy's
-    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr, base ? base + first : nullptr, refused ? refused + first : nullptr }; }
-    bool any() const { return elem != nullptr || base != nullptr; }
+    bool windowed(u64 i) const { return win && win[i].row_bytes != 0; }
+    Window window_of(u64 i) const { return windowed(i) ? Window{ win[i].row_bytes, win[i].row0, win[i].rows, win[i].col0, win[i].cols } : Window{ 0, 0, 0, 0, 0 }; }
+    bool grouped(u64 i) const { return of(i) > 1 || base_of(i) != nullptr || windowed(i); }        // not a plain copy: k_plane_copy's, k_delta_copy's or k_window_copy's
+    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr, base ? base + first : nullptr, refused ? refused + first : nullptr, win ? win + first : nullptr }; }
+    bool any() const { return elem != nullptr || base != nullptr || win != nullptr; }
+    // what the caller's buffer and the base of entry i hold: the window's bytes, or those given
+    u64 dst_len(u64 i, u64 whole) const { return windowed(i) ? window_bytes(window_of(i)) : whole; }
+    // what of the caller's buffer of `cap` bytes the call may write: all of it, of a window's no more than the window (too small a one: cap)
+    u64 room(u64 i, u64 cap) const { const u64 w = dst_len(i, cap); return w < cap ? w : cap; }
     inline u64 join_len(u64 i, const zpk_decode_desc& d, const zpk_decode_result& r) const;
 };
 // ZPK_E_INVALID: an element size that is none (plane_elem_valid), before anything is enqueued
@@ -682,7 +696,8 @@ struct LastCall {
     u32  enc_big[2] = {0, 0};                    // zpk_codec_encode_big_device: entries written in pieces, their pieces
     u32  delta[4] = {0, 0, 0, 0};                // zpk_codec_delta_stats: rows split with a base, rows joined with a base, k_delta_copy launches, entries staged only because they had a base
     u32  base_check[4] = {0, 0, 0, 0};           // zpk_codec_base_check_stats: rows hashed by one wave, rows hashed chip-wide, entries refused for their base, launches of the hash pass
-    void no_planes() { for (int k = 0; k < 4; k++) planes[k] = delta[k] = base_check[k] = 0; }      // (a call that could split or join begins with this)
+    u32  window[3] = {0, 0, 0};                  // zpk_codec_window_stats: rows windowed, k_window_copy launches, entries staged only because they had a window
+    void no_planes() { for (int k = 0; k < 4; k++) planes[k] = delta[k] = base_check[k] = 0; window[0] = window[1] = window[2] = 0; }      // (a call that could split or join begins with this)
     u32  planes[4] = {0, 0, 0, 0};               // zpk_codec_planes_stats: rows split, rows joined, k_plane_copy launches, entries staged only because they were grouped
     int  fell_back_fused = 0;                    // the last decode batch could not get its sequence arena and ran the fused decoder only
     // the host-path pipeline decodes one call in several launches: their counters are brought back piece by piece and summed, so that
@@ -695,7 +710,7 @@ struct LastCall {
 // A growable pinned block (PinBuf) is regrown only while nothing on a stream still reads or writes it: a call that uses one drains the
 // stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk, sh.h: hipStreamSynchronize behind the copy home; sspan.h: the
 // run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the block's next turn
-// (bigenc.h, sc.h, pc.h, dc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
+// (bigenc.h, sc.h, pc.h, dc.h, wc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
 struct zpk_codec {
     int device = 0;
     Stream stream;
@@ -784,6 +799,8 @@ struct zpk_codec {
     struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } pc;
     // ... and that of k_delta_copy (delta_copy_plan.h / delta_copy.h), a third block under the same rule
     struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } dc;
+    // ... and that of k_window_copy (window_copy_plan.h / window_copy.h), a fourth block under the same rule
+    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } wc;
     // the spans k_span_hash and the chip-wide pair hash (span_hash_plan.h / span_hash.h): tables | hashes | partial sums on the device,
     // the tables going up and the hashes coming home through a pinned block of its own — a call that hashes spans waits for its stream
     // behind the copy home, so the block is idle whenever the next call writes it
@@ -1095,18 +1112,61 @@ static int delta_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
     HIPCHK(c, hipGetLastError());
     return ZPK_OK;
 }
-// The spans row(i) of a batch with element sizes and bases `pl`, all of one direction (join: PLANE_SPLIT / PLANE_JOIN), split THREE ways:
-// those with a base in ONE k_delta_copy, those without a base and with an element size above 1 in ONE k_plane_copy, the rest in ONE
-// k_span_copy as ever.  No element sizes and no bases: span_copy_enqueue and nothing else; no bases: what it was before there were any.
+// The same for k_window_copy: entry i the row row(i) (a zpk_window_copy; an entry or a window of no bytes: no row), through the codec's
+// fourth pinned table.  Element sizes, windows (window_valid), bases and their overlap with the destinations have been checked by the
+// caller; a window that fails the rule all the same: ZPK_E_INVALID and nothing is launched.
+template <class RowFn>
+static int window_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
+{
+    auto bytes = [](const zpk_window_copy& s) { return s.n ? s.win.rows * s.win.cols : 0ull; };
+    u64 nz = 0;
+    for (u64 i = 0; i < n; i++) nz += bytes(row(i)) != 0;
+    if (nz == 0) return ZPK_OK;
+    if (nz > ZPK_PC_MAX_ROWS) return ZPK_E_INVALID;
+    if (c->wc.pending) { HIPCHK(c, hipEventSynchronize(c->wc.ev)); c->wc.pending = false; }             // the pinned block's last upload has run
+    if (c->wc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "window copy: no event"); return ZPK_E_LAUNCH; }
+    if (!c->wc.h.grow(nz * sizeof(WindowCopyRow))) { snprintf(c->err, sizeof(c->err), "window copy: out of pinned memory"); return ZPK_E_NOMEM; }
+    int rc;
+    if ((rc = grow(c, c->wc.d, nz * sizeof(WindowCopyRow)))) return rc;
+    WindowCopyRow* const rows = (WindowCopyRow*)c->wc.h.p;
+    PlaneCopyPlan p = { 0, 0 };
+    for (u64 i = 0; i < n; i++) {
+        const zpk_window_copy s = row(i);
+        if (!bytes(s)) continue;
+        if (!window_copy_emit(s.src, s.dst, s.base, s.n, Window{ s.win.row_bytes, s.win.row0, s.win.rows, s.win.col0, s.win.cols }, s.elem, rows, p)) return ZPK_E_INVALID;
+        c->last.window[0]++;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->wc.d, rows, p.nrows * sizeof(WindowCopyRow), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->wc.ev, st));
+    c->wc.pending = true;
+    const u64 nl = plane_copy_launches(p.items);
+    for (u64 j = 0; j < nl; j++) {
+        const PlaneCopyLaunch L = plane_copy_launch(p.items, j);
+        window_copy_launch((const WindowCopyRow*)(const u8*)c->wc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
+        c->last.window[1]++;
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZPK_OK;
+}
+// The spans row(i) of a batch with element sizes, bases and windows `pl`, all of one direction (join: PLANE_SPLIT / PLANE_JOIN), split
+// FOUR ways: those with a window in ONE k_window_copy, whatever their element size or base (row(i).len is the entry's plain size there,
+// or 0: nothing is delivered); of the others those with a base in ONE k_delta_copy, those without a base and with an element size above 1
+// in ONE k_plane_copy, the rest in ONE k_span_copy as ever.  No element sizes, bases or windows: span_copy_enqueue and nothing else; no
+// windows: what it was before there were any.
 template <class RowFn>
 static int rows_enqueue(zpk_codec* c, u64 n, RowFn row, const Planes& pl, u32 join, hipStream_t st)
 {
     if (!pl.any()) return span_copy_enqueue(c, n, row, st);
     int rc = span_copy_enqueue(c, n, [&](u64 i) { zpk_span_copy s = row(i); if (pl.grouped(i)) s.len = 0; return s; }, st);
     if (rc) return rc;
-    rc = plane_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u32 k = pl.of(i); return zpk_plane_copy{ s.src, s.dst, k > 1 && !pl.base_of(i) ? s.len : 0ull, k, join }; }, st);
-    if (rc || !pl.base) return rc;
-    return delta_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u8* const b = pl.base_of(i); return zpk_delta_copy{ s.src, s.dst, (u64)b, b ? s.len : 0ull, pl.of(i), join }; }, st);
+    rc = plane_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u32 k = pl.of(i); return zpk_plane_copy{ s.src, s.dst, k > 1 && !pl.base_of(i) && !pl.windowed(i) ? s.len : 0ull, k, join }; }, st);
+    if (rc) return rc;
+    if (pl.base) rc = delta_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u8* const b = pl.base_of(i); return zpk_delta_copy{ s.src, s.dst, (u64)b, b && !pl.windowed(i) ? s.len : 0ull, pl.of(i), join }; }, st);
+    if (rc || !pl.win) return rc;
+    return window_copy_enqueue(c, n, [&](u64 i) {
+        const zpk_span_copy s = row(i);
+        return zpk_window_copy{ s.src, s.dst, (u64)pl.base_of(i), pl.windowed(i) ? s.len : 0ull, pl.win[i], pl.of(i), 0u };
+    }, st);
 }
 }  // extern "C++"
 static int planes_check(zpk_codec* c, const u8* elem, u64 n)
@@ -1130,6 +1190,32 @@ static int bases_check(zpk_codec* c, PtrRule& rule, const Planes& pl, u64 n, Len
         }
     return ZPK_OK;
 }
+
+}  // extern "C++"
+// The windows of a batch, before anything is enqueued.  ZPK_E_INVALID: a window that fails window_valid against its entry's uncomp_size
+// and element size, or one on a batch whose destinations are not device memory.  `staged` becomes the descriptors as the routing is to
+// see them when an entry has a window (else it stays empty): such an entry decodes into the codec's staging with a slot of uncomp_size
+// — its dst_capacity counts as that; the caller's says what room its buffer has, window_bytes is all the delivery needs of it, and with
+// less the capacity counts as 0: the entry earns BUFFER_TOO_SMALL from the kernels' guards, in their order, and nothing is delivered.
+static int windows_check(zpk_codec* c, const Planes& pl, const zpk_decode_desc* desc, u64 n, bool ddst, std::vector<zpk_decode_desc>& staged)
+{
+    staged.clear();
+    bool any = false;
+    for (u64 i = 0; pl.win && i < n; i++) {
+        if (!pl.windowed(i)) continue;
+        if (!ddst || !window_valid(desc[i].uncomp_size, pl.of(i), pl.window_of(i))) {
+            snprintf(c->err, sizeof(c->err), "entry %llu: its window does not lie in %llu bytes of %u-byte elements%s", (unsigned long long)i, (unsigned long long)desc[i].uncomp_size,
+                     (unsigned)pl.of(i), ddst ? "" : " (windows belong to device destinations)");
+            return ZPK_E_INVALID;
+        }
+        any = true;
+    }
+    if (!any) return ZPK_OK;
+    try { staged.assign(desc, desc + n); } catch (...) { return ZPK_E_NOMEM; }
+    for (u64 i = 0; i < n; i++) if (pl.windowed(i)) staged[i].dst_capacity = desc[i].dst_capacity < window_bytes(pl.window_of(i)) ? 0 : desc[i].uncomp_size;
+    return ZPK_OK;
+}
+extern "C++" {
 
 // XXH3-64 of the spans row(i) = SpanHashRow{ address, len }, i in [0, n), into out[0, n) (HOST memory): the two tables of span_hash_plan.h
 // go up from the codec's pinned block, one pass of launches follows (span_hash_launch: k_span_hash for the short rows, the partial sums
@@ -1435,9 +1521,10 @@ int zpk_codec_decode_batch_device(zpk_codec* c, const uint8_t* src, uint64_t src
 // ones and the slot is hashed again: the verdict is the one the reference reaches on this caller's buffer.
 // (Dst::Device: dst_ptrs are DEVICE pointers — zpk_codec_decode_batch_host_dptr — and the caller's bytes come over from there.
 // Dst::None: there is no caller's buffer; the tail counts as ZEROS — the slot's tail is zeroed on the device, and the verdict is the one
-// a read into a zero-filled buffer of uncomp_size bytes reaches.)
+// a read into a zero-filled buffer of uncomp_size bytes reaches.  An entry with a WINDOW, pl.windowed: likewise — the caller's buffer
+// has window_bytes bytes and is no buffer of uncomp_size bytes, so the tail counts as zeros and the verdict is zpack_amd_test_files'.)
 static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, uint8_t* const* dst_ptrs,
-                                zpk_decode_result* results, Dst to = Dst::Host)
+                                zpk_decode_result* results, Dst to = Dst::Host, const Planes& pl = Planes())
 {
     for (u64 i = 0; i < n; i++) {
         zpk_decode_result& r = results[i];
@@ -1447,7 +1534,7 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
         if ((rc = grow(c, c->d_xpart, 64))) return rc;
         const u64 tail = desc[i].uncomp_size - r.produced;
         u64 meta[3] = { hd[i].dst_offset, desc[i].uncomp_size, 0 };
-        if (to == Dst::None) HIPCHK(c, hipMemsetAsync(c->d_dst + hd[i].dst_offset + r.produced, 0, tail, c->stream));
+        if (to == Dst::None || pl.windowed(i)) HIPCHK(c, hipMemsetAsync(c->d_dst + hd[i].dst_offset + r.produced, 0, tail, c->stream));
         else HIPCHK(c, hipMemcpyAsync(c->d_dst + hd[i].dst_offset + r.produced, dst_ptrs[i] + r.produced, tail, to == Dst::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_xpart, meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
         u64* m = (u64*)c->d_xpart;
@@ -1669,7 +1756,7 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
         c->last.home = produced_total > ~0ull - c->last.home ? ~0ull : c->last.home + produced_total;
     }
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "D2H: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to);
+    return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to, pl);
 }
 
 // ---- the same chunk as a three-stage pipeline (round 3) ------------------------------------------------------------------------
@@ -1827,7 +1914,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         for (int k = 0; k < np; k++) for (int w = 0; w < N_COUNTERS; w++) c->last.host_totals[w] += c->pipe.piece_counters[k][w];
         c->last.totals_valid = 1;
     }
-    if (rc == ZPK_OK) rc = rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to);
+    if (rc == ZPK_OK) rc = rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to, pl);
     return rc;
 }
 
@@ -2137,7 +2224,9 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         std::vector<const u8*> gbase;
         if (pl.any()) { gelem.resize(ng); for (u64 k = 0; k < ng; k++) gelem[k] = (u8)pl.of(be[g0 + k].idx); }
         if (pl.base) { gbase.resize(ng); for (u64 k = 0; k < ng; k++) gbase[k] = pl.base_of(be[g0 + k].idx); }
-        if ((rc = rows_enqueue(c, ng, row, Planes{ pl.any() ? gelem.data() : nullptr, pl.base ? gbase.data() : nullptr }, PLANE_JOIN, c->stream))) return rc;
+        std::vector<zpk_window> gwin;                                                  // (... and its windows)
+        if (pl.win) { gwin.resize(ng); for (u64 k = 0; k < ng; k++) gwin[k] = pl.win[be[g0 + k].idx]; }
+        if ((rc = rows_enqueue(c, ng, row, Planes{ pl.any() ? gelem.data() : nullptr, pl.base ? gbase.data() : nullptr, nullptr, pl.win ? gwin.data() : nullptr }, PLANE_JOIN, c->stream))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ZPK_OK;
     }
@@ -2254,16 +2343,19 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
     CodecLock lk(c);
     HIPCHK(c, hipSetDevice(c->device));
     if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
-    // the pointer rule (PtrRule): before anything is enqueued
+    std::vector<zpk_decode_desc> staged;                                              // (the windows: their rule, and the slots of the entries that have one)
+    if (const int wrc = windows_check(c, pl, desc, n, ddst, staged)) return wrc;
+    // the pointer rule (PtrRule): before anything is enqueued.  (A window's destination and base hold window_bytes bytes: Planes::dst_len.)
     PtrRule rule(c);
-    if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
-    if (bases_check(c, rule, pl, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, dst_ptrs)) return ZPK_E_INVALID;
+    if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return pl.room(i, desc[i].dst_capacity); })) return ZPK_E_INVALID;
+    if (bases_check(c, rule, pl, n, [&](u64 i) { return pl.dst_len(i, desc[i].uncomp_size); }, dst_ptrs)) return ZPK_E_INVALID;
     begin_decode_call(c);
     // the base rule: every verdict is known before anything of the batch is routed, so before any row reaches rows_enqueue
     std::vector<u8> refused;
-    int rc = base_verdicts(c, pl, base_hash, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, refused);
+    int rc = base_verdicts(c, pl, base_hash, n, [&](u64 i) { return pl.dst_len(i, desc[i].uncomp_size); }, refused);
     if (rc) return rc;
-    rc = decode_batch_host_routed(c, archive, archive_size, desc, n, dst_ptrs, results, to, Planes{ pl.elem, pl.base, refused.empty() ? nullptr : refused.data() });
+    if (!staged.empty()) desc = staged.data();
+    rc = decode_batch_host_routed(c, archive, archive_size, desc, n, dst_ptrs, results, to, Planes{ pl.elem, pl.base, refused.empty() ? nullptr : refused.data(), pl.win });
     if (rc == ZPK_OK) base_verdicts_mark(refused, desc, results, n);
     return rc;
 }
@@ -2319,16 +2411,17 @@ static int decode_batch_host_routed(zpk_codec* c, const uint8_t* archive, uint64
         for (u64 k = 0; k < pj.size() && rc == ZPK_OK; k++) {                         // one large frame at a time: each fills the chip
             u8 again = 1;
             const u64 idx = pj[k].idx;
-            // a device destination is decoded into straight away — unless the entry has an element size above 1 or a base: that one decodes
-            // into the staging, as an entry without a destination does, and is JOINED from there
+            // a device destination is decoded into straight away — unless the entry has an element size above 1, a base or a window: that one
+            // decodes into the staging, as an entry without a destination does, and is JOINED (or cut) from there
             const bool grouped = ddst && pl.grouped(idx);
             rc = decode_big_single(c, pj[k], desc[idx], BigSrc{ archive, false }, grouped ? BigDst{ nullptr, Dst::None } : BigDst{ to == Dst::None ? nullptr : dst_ptrs[idx], to }, results[idx], again);
             if (rc == ZPK_OK && !again && grouped) {
                 const u8 k1 = (u8)pl.of(idx);
                 const u8* const b1 = pl.base_of(idx);
-                if (k1 > 1) c->last.planes[3]++; else c->last.delta[3]++;              // (staged because it was grouped; staged only because it had a base)
+                if (k1 > 1) c->last.planes[3]++; else if (b1) c->last.delta[3]++; else c->last.window[2]++;     // (staged because it was grouped; staged only because it had a base; ... a window)
                 const zpk_span_copy row = { (u64)(u8*)c->d_dst, (u64)dst_ptrs[idx], pl.join_len(idx, desc[idx], results[idx]) };
-                if ((rc = rows_enqueue(c, 1, [&](u64) { return row; }, Planes{ &k1, pl.base ? &b1 : nullptr }, PLANE_JOIN, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
+                const zpk_window w1 = pl.win ? pl.win[idx] : zpk_window{ 0, 0, 0, 0, 0 };
+                if ((rc = rows_enqueue(c, 1, [&](u64) { return row; }, Planes{ &k1, pl.base ? &b1 : nullptr, nullptr, pl.win ? &w1 : nullptr }, PLANE_JOIN, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
             }
             if (rc == ZPK_OK && !again) is_big[idx] = 1;
         }
@@ -2341,14 +2434,16 @@ static int decode_batch_host_routed(zpk_codec* c, const uint8_t* archive, uint64
             std::vector<u8> re(pl.any() ? rest.size() : 0);
             std::vector<const u8*> rb(pl.base ? rest.size() : 0);
             std::vector<u8> rf(pl.refused ? rest.size() : 0);
+            std::vector<zpk_window> rw(pl.win ? rest.size() : 0);
             for (u64 k = 0; k < rest.size(); k++) {
                 rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]];
                 if (pl.any()) re[k] = (u8)pl.of(rest[k]);
                 if (pl.base) rb[k] = pl.base_of(rest[k]);
                 if (pl.refused) rf[k] = pl.refused[rest[k]];
+                if (pl.win) rw[k] = pl.win[rest[k]];
             }
             rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to,
-                                         Planes{ pl.any() ? re.data() : nullptr, pl.base ? rb.data() : nullptr, pl.refused ? rf.data() : nullptr });
+                                         Planes{ pl.any() ? re.data() : nullptr, pl.base ? rb.data() : nullptr, pl.refused ? rf.data() : nullptr, pl.win ? rw.data() : nullptr });
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
@@ -2367,11 +2462,18 @@ int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint6
     return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device);
 }
 
+int zpk_codec_decode_batch_host_dptr_windows(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                             uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                             const uint64_t* base_hash, const zpk_window* win)
+{
+    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem, d_base, nullptr, win }, base_hash);
+}
+
 int zpk_codec_decode_batch_host_dptr_delta_checked(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                                    uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
                                                    const uint64_t* base_hash)
 {
-    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem, d_base }, base_hash);
+    return zpk_codec_decode_batch_host_dptr_windows(c, archive, archive_size, desc, n, d_dst_ptrs, results, elem, d_base, base_hash, nullptr);
 }
 
 int zpk_codec_decode_batch_host_dptr_delta(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
@@ -2449,6 +2551,58 @@ int zpk_codec_delta_stats(zpk_codec* c, uint32_t out[4])
     if (!c || !out) return ZPK_E_INVALID;
     CodecLock lk(c);
     for (int k = 0; k < 4; k++) out[k] = c->last.delta[k];
+    return ZPK_OK;
+}
+
+// rows of k_window_copy on their own: element size, window, both ends and the base (0: none) per row; window_valid, the pointer rule on
+// all three ends of every row — the source over n bytes, destination and base over window_bytes — and the overlap rule between base and
+// destination (window_overlap_ok) — on refusal nothing has run
+int zpk_codec_window_copy_device(zpk_codec* c, const zpk_window_copy* rows, uint64_t n, void* stream)
+{
+    if (!c || (n && !rows)) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    c->last.no_planes();
+    if (n == 0) return ZPK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto win = [&](u64 i) { const zpk_window& w = rows[i].win; return Window{ w.row_bytes, w.row0, w.rows, w.col0, w.cols }; };
+    for (u64 i = 0; i < n; i++) {
+        if (!plane_elem_valid(rows[i].elem)) { snprintf(c->err, sizeof(c->err), "row %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
+        if (!window_valid(rows[i].n, rows[i].elem, win(i))) { snprintf(c->err, sizeof(c->err), "row %llu: its window does not lie in %llu bytes of %u-byte elements", (unsigned long long)i, (unsigned long long)rows[i].n, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
+    }
+    PtrRule rule(c);
+    auto len = [&](u64 i) { return window_bytes(win(i)); };
+    if (rule.batch("window source", n, [&](u64 i) { return (const void*)rows[i].src; }, [&](u64 i) { return len(i) ? (u64)rows[i].n : 0ull; }) ||
+        rule.batch("window destination", n, [&](u64 i) { return (const void*)rows[i].dst; }, len) ||
+        rule.batch("window base", n, [&](u64 i) { return (const void*)rows[i].base; }, [&](u64 i) { return rows[i].base ? len(i) : 0ull; })) return ZPK_E_INVALID;
+    for (u64 i = 0; i < n; i++)
+        if (rows[i].base && !window_overlap_ok(rows[i].base, rows[i].dst, win(i))) {
+            snprintf(c->err, sizeof(c->err), "row %llu: the base overlaps the destination without being it", (unsigned long long)i);
+            return ZPK_E_INVALID;
+        }
+    return window_copy_enqueue(c, n, [&](u64 i) { return rows[i]; }, stream ? (hipStream_t)stream : c->stream);
+}
+
+// window_valid and window_overlap_ok (window_copy_plan.h) for the callers that judge a window before they have a codec
+int zpk_codec_window_valid(uint64_t n, uint32_t elem, const zpk_window* win, uint64_t* bytes)
+{
+    if (!win) return 0;
+    const Window w = { win->row_bytes, win->row0, win->rows, win->col0, win->cols };
+    if (!window_valid(n, elem, w)) return 0;
+    if (bytes) *bytes = window_bytes(w);
+    return 1;
+}
+int zpk_codec_window_overlap_ok(uint64_t base, uint64_t dst, const zpk_window* win)
+{
+    return win && window_overlap_ok(base, dst, Window{ win->row_bytes, win->row0, win->rows, win->col0, win->cols }) ? 1 : 0;
+}
+
+// the most recent call that could split, join or cut: out[0] rows windowed, out[1] k_window_copy launches, out[2] entries that decoded
+// into the staging only because they had a window
+int zpk_codec_window_stats(zpk_codec* c, uint32_t out[3])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    for (int k = 0; k < 3; k++) out[k] = c->last.window[k];
     return ZPK_OK;
 }
 
@@ -2718,14 +2872,17 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
     const bool ddst = to == Dst::Device, none = to == Dst::None;
     PtrRule rule(c);                                                                  // the pointer rule: before anything is enqueued
     if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
-    if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return (u64)desc[i].dst_capacity; })) return ZPK_E_INVALID;
-    if (bases_check(c, rule, pl_given, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, dst_ptrs)) return ZPK_E_INVALID;
+    std::vector<zpk_decode_desc> staged;                                              // (the windows: their rule, and the slots of the entries that have one)
+    if (const int wrc = windows_check(c, pl_given, desc, n, ddst, staged)) return wrc;
+    if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return pl_given.room(i, desc[i].dst_capacity); })) return ZPK_E_INVALID;
+    if (bases_check(c, rule, pl_given, n, [&](u64 i) { return pl_given.dst_len(i, desc[i].uncomp_size); }, dst_ptrs)) return ZPK_E_INVALID;
     begin_decode_call(c);
     // the base rule (beside planes_join_len): every verdict is known before the first sub-batch is decoded, so before any row reaches
     // rows_enqueue; the column is cut with the others (Planes::from)
     std::vector<u8> refused;
-    if (const int vrc = base_verdicts(c, pl_given, base_hash, n, [&](u64 i) { return (u64)desc[i].uncomp_size; }, refused)) return vrc;
-    const Planes pl = { pl_given.elem, pl_given.base, refused.empty() ? nullptr : refused.data() };
+    if (const int vrc = base_verdicts(c, pl_given, base_hash, n, [&](u64 i) { return pl_given.dst_len(i, desc[i].uncomp_size); }, refused)) return vrc;
+    if (!staged.empty()) desc = staged.data();
+    const Planes pl = { pl_given.elem, pl_given.base, refused.empty() ? nullptr : refused.data(), pl_given.win };
     const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
     auto slot = [&](u64 i) {                                                          // (no destination: a stored entry has no slot)
         const bool stored = desc[i].method == ZPK_METHOD_NONE;
@@ -2763,13 +2920,21 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
 }
 
 // (element sizes and bases belong to DEVICE destinations: with host destinations every element size has to be 1 and no entry has a base)
+// (... and so do windows: with host destinations no entry has one)
+int zpk_codec_decode_batch_dimage_windows(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                          uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                          const uint64_t* base_hash, const zpk_window* win)
+{
+    if (!dst_on_device) for (u64 i = 0; i < n; i++) if ((elem && elem[i] != 1) || (d_base && d_base[i]) || (win && win[i].row_bytes)) return ZPK_E_INVALID;
+    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results,
+                                   Planes{ dst_on_device ? elem : nullptr, dst_on_device ? d_base : nullptr, nullptr, dst_on_device ? win : nullptr }, base_hash);
+}
+
 int zpk_codec_decode_batch_dimage_delta_checked(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                                 uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
                                                 const uint64_t* base_hash)
 {
-    if (!dst_on_device) for (u64 i = 0; i < n; i++) if ((elem && elem[i] != 1) || (d_base && d_base[i])) return ZPK_E_INVALID;
-    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results,
-                                   Planes{ dst_on_device ? elem : nullptr, dst_on_device ? d_base : nullptr }, base_hash);
+    return zpk_codec_decode_batch_dimage_windows(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device, results, elem, d_base, base_hash, nullptr);
 }
 
 int zpk_codec_decode_batch_dimage_delta(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,

@@ -41,6 +41,14 @@ the `hash` field an archive records for an entry with those bytes.
     image = write_archive_device(new, planes="dtype", base=old, base_id="step 1000")
     tensors, statuses = read_files_device(image, planes="manifest", base=old, base_id="step 1000", inplace=True)     # `old` now holds `new`
 
+Window reads (include/zpack_amd.h: zpack_amd_read_files_device_windows).  A checkpoint loaded under another layout than it was written
+under — tensor-parallel ranks, a pipeline stage — needs a slice of every tensor.  With window={name: (shape, dim, start, stop)} the
+tensor returned for an entry holds the slice [start, stop) along `dim` of the entry seen as a contiguous tensor of `shape`, cut inside
+the copy that delivers the entry: no full-size tensor is allocated and no second pass runs.  With base= the base is the caller's shard
+of the previous checkpoint, of the slice's size, and inplace=True reads into it.
+
+    mine, statuses = read_files_device(image, planes="manifest", window={"w": ((4096, 4096), 1, 0, 512)})    # columns [0, 512) of w
+
 The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
 are ZPACK_ERROR_NOT_AVAILABLE.
 """
@@ -109,6 +117,8 @@ def lib():
                                                         C.POINTER(C.c_int), vp]
         L.zpack_amd_read_files_device_delta_checked.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(vp),
                                                                 C.POINTER(u64), C.POINTER(C.c_int), vp]
+        L.zpack_amd_read_files_device_windows.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(vp),
+                                                          C.POINTER(u64), C.POINTER(Window), C.POINTER(C.c_int), vp]
         L.zpack_amd_hash_device.argtypes = [C.POINTER(vp), C.POINTER(C.c_size_t), u64, C.POINTER(u64), vp]
         L.zpack_read_file.argtypes = [R, C.POINTER(FileEntry), vp, C.c_size_t, vp]
         L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
@@ -283,7 +293,40 @@ def _base_bytes(name, t, size):
     return flat
 
 
-def read_files_device(archive, names=None, device=0, planes=None, base=None, inplace=False, base_id=None, check_base=True):
+class Window(C.Structure):                   # zpack_amd_window (include/zpack_amd.h)
+    _fields_ = [("row_bytes", C.c_uint64), ("row0", C.c_uint64), ("rows", C.c_uint64), ("col0", C.c_uint64), ("cols", C.c_uint64)]
+
+
+def _windows_of(pnames, sizes, planes, window):
+    """the `window` argument of read_files_device as one Window per entry read (row_bytes 0: the entry whole), or None when no entry has
+    one; ValueError naming the entry for a shape that does not multiply out to its size or a dim, start or stop out of range"""
+    from . import slice_window
+    if not window:
+        return None
+    unknown = [nm for nm in window if nm not in pnames]
+    if unknown:
+        raise KeyError("window names no entry of this read: %s" % ", ".join(unknown))
+    out = []
+    for nm, size in zip(pnames, sizes):
+        if nm not in window:
+            out.append(Window(0, 0, 0, 0, 0))
+            continue
+        try:
+            shape, dim, start, stop = window[nm]
+            shape, dim, start, stop = [int(x) for x in shape], int(dim), int(start), int(stop)
+            k = int(planes.get(nm, 1)) if planes else 1
+            count = 1
+            for x in shape:
+                count *= x
+            if not shape or any(x < 0 for x in shape) or count * k != size:
+                raise ValueError("shape %r of %d-byte elements is not its %d bytes" % (tuple(shape), k, size))
+            out.append(Window(*slice_window(shape, dim, start, stop, k)))
+        except (TypeError, ValueError) as err:
+            raise ValueError("window of %s: %s" % (nm, err)) from None
+    return out
+
+
+def read_files_device(archive, names=None, device=0, planes=None, base=None, inplace=False, base_id=None, check_base=True, window=None):
     """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
     compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
     in that order (None: all, in archive order).  `planes`: None — the entries' bytes as they are stored; {name: element size} — those
@@ -297,6 +340,13 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
     bases' hashes ("base_xxh3") the bases given are hashed on the device before they are applied: an entry whose base is another comes back
     with status BASE_MISMATCH, its tensor — with inplace=True its base — untouched; check_base=False reads without that check, as an
     archive without the field is read.
+    `window`: {name: (shape, dim, start, stop)} — of those entries only the slice [start, stop) along dimension `dim` of the entry seen
+    as a contiguous tensor of `shape` is delivered (zpack_amd_read_files_device_windows: the cut rides on the copy that delivers the
+    entry, no full-size tensor is allocated); `shape` counts elements of the entry's element size, its `planes` value or 1.  The tensor
+    returned for such an entry has the slice's bytes, and its base — with inplace=True the destination, as ever — is the caller's shard of
+    that size.  A shape that does not multiply out to the entry's size, or a dim, start or stop out of range, raises ValueError naming
+    the entry before anything is decoded.  A recorded "base_xxh3" is the hash of the WHOLE base, which the reader of a window does not
+    hold: a windowed entry with a base in such an archive raises ValueError unless check_base=False.  None: no entry has a window.
     Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
     a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
     import torch
@@ -322,6 +372,13 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
             raise ValueError("planes is None, a {name: element size} dict or \"manifest\"")
         n = len(picks)
         sizes = [int(r.file_entries[i].uncomp_size) for i in picks]
+        pnames = [r.file_entries[i].filename.decode() for i in picks]
+        wins = _windows_of(pnames, sizes, planes, window)
+        if wins is not None:
+            for nm, w in zip(pnames, wins):
+                if w.row_bytes and nm in base and check_base and recorded_hash is not None:
+                    raise ValueError("%s: the archive records the hash of its WHOLE base, which the reader of a window does not hold; read it with check_base=False" % nm)
+            sizes = [int(w.rows * w.cols) if w.row_bytes else s for w, s in zip(wins, sizes)]      # (what the buffers and the bases hold)
         starts, total = [], 0
         for s in sizes:
             starts.append(total)
@@ -329,7 +386,6 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
         dev = torch.device("cuda", device)
         backing = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         tensors = [backing[a:a + s] for a, s in zip(starts, sizes)]
-        pnames = [r.file_entries[i].filename.decode() for i in picks]
         bases = [_base_bytes(nm, base[nm], s) if nm in base else None for nm, s in zip(pnames, sizes)]
         out = list(tensors)
         if inplace:
@@ -342,7 +398,20 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
         res = (C.c_int * max(n, 1))()
         _settle(dev)
         elem = None if planes is None else (C.c_uint8 * max(n, 1))(*[int(planes.get(nm, 1)) for nm in pnames])
-        if any(b is not None for b in bases):
+        if wins is not None:
+            d_bases = want = None
+            if any(b is not None for b in bases):
+                for b in bases:
+                    if b is not None:
+                        _settle(b.device)
+                d_bases = (C.c_void_p * max(n, 1))(*[b.data_ptr() if b is not None and b.numel() else None for b in bases])
+                if check_base and recorded_hash is not None:                        # (no windowed entry has a base here: the entries read whole are checked as ever)
+                    unlisted = [k for k, (nm, b) in enumerate(zip(pnames, bases)) if b is not None and nm not in recorded_hash]
+                    own = dict(zip(unlisted, _hash_flat(L, [bases[k] for k in unlisted])))
+                    want = (C.c_uint64 * max(n, 1))(*[own[k] if k in own else recorded_hash.get(nm, 0) for k, nm in enumerate(pnames)])
+            _check(L.zpack_amd_read_files_device_windows(C.byref(r), ents, n, bufs, caps, elem, d_bases, want, (Window * max(n, 1))(*wins), res, None),
+                   "zpack_amd_read_files_device_windows")
+        elif any(b is not None for b in bases):
             for b in bases:
                 if b is not None:
                     _settle(b.device)
