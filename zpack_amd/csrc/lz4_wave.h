@@ -80,6 +80,10 @@ static_assert(LZ4W_SEG <= 64u, "the visited-position mask of a segment is one 64
 #define LZ4W_FIX_CONT 1                           // developer A/B: 0 = fix-up rounds without the one-successor continuation
 #endif
 
+#ifndef LZ4W_LEAN_HOPS
+#define LZ4W_LEAN_HOPS 1                          // developer A/B: 0 = the hop loops of lz4_walk with a carried live flag (profiles/r35)
+#endif
+
 #ifndef LZ4W_SPLIT_FIRST
 #define LZ4W_SPLIT_FIRST 0
 #endif
@@ -209,9 +213,52 @@ __device__ __forceinline__ Lz4Walk lz4_walk(const Lz4Bytes& B, bool on, u32 from
     const lds_cp8 base = B.S + (seg_start - B.cbase);
     const bool start_in = on && (i32)(from - seg_start) < seg_len;
     i32 rp = start_in ? (i32)(from - seg_start) : seg_len;
-    bool live = start_in;
     u32 flags = 0, exit_far = from, far = on && !start_in ? 1u : 0u;
     u64 m = 0;
+    if constexpr (LZ4W_LEAN_HOPS != 0) {
+    // NO BOOLEAN IS CARRIED round the loop.  A lane is live exactly while rp < seg_len and, in a re-walk, the previous walk did not
+    // visit rp: a lane that is not `on`, did not start, finished or left through the slow path has rp >= seg_len, and a re-walk that
+    // lands on a visited position stays there, before seg_len, and finds the same bit again.  Both tests are compares, so the exit
+    // test is the `and` of two ballots, a scalar instruction (the ballot of a carried flag, or of an `&&`, costs a v_cndmask and a
+    // v_cmp_ne to turn the flag into a lane mask again).  The visit bit is 1 << rp, an inline constant shifted: no zero moved into
+    // place for a high half, no `& 63` (the compiler drops it here), and the old-mask test reads the same shifted bit.  It goes into
+    // the mask under an all-ones / zero select in two v_and_or.  Per iteration without the slow path: 22 vector instructions in the
+    // first walk and 24 in the re-walk, where the carried flag had 25 and 27 (profiles/r35).
+    // (`live && rp >= 0` in the first walk, not the single unsigned compare rp < seg_len: with the latter the compiler takes the
+    // block pointer out of its scalar registers for the whole batch loop, 54 lane accesses of scalar spills instead of 42.)
+    u32 mlo = 0, mhi = 0;
+    for (;;) {
+        const u64 bit = 1ull << (rp & 63);
+        const bool inr = rp < seg_len, fresh = FIRST || (old.m & bit) == 0;    // (a first walk has nothing to merge with)
+        if ((__builtin_amdgcn_ballot_w64(inr) & __builtin_amdgcn_ballot_w64(fresh)) == 0) break;
+        const bool live = inr && fresh;                             // a hit ends the walk where it stands: before seg_len
+        SEQ_STAT(if (FIRST) stt.hops_first++; else stt.hops_fix++);
+        const bool inseg = FIRST ? rp >= 0 : true;
+        u32 sel = (live && inseg) ? ~0u : 0u;
+        asm("" : "+v"(sel));                                        // (opaque: `bit & sel` must not become two selects)
+        mlo |= (u32)bit & sel; mhi |= (u32)(bit >> 32) & sel;
+        // the common shapes, without a branch (see lz4_quick)
+        const lds_cp8 at = base + rp;
+        const u32 tok = lds_ld8(at), b1 = lds_ld8(at + 1);
+        const u32 lit4 = tok >> 4, mlc = tok & 15;
+        const bool l15 = lit4 == 15, m15 = mlc == 15;
+        const u32 q = lit4 + 1 + (l15 ? b1 + 1 : 0u);               // the offset field, relative to the token
+        const u32 b2 = lds_ld8(at + q + 2);
+        const i32 n2 = rp + (i32)q + 2;
+        i32 nx = n2 + (m15 ? 1 : 0);
+        const bool slow = (l15 && b1 == 255) || (m15 && b2 == 255) || n2 >= lim_rel;
+        if (live && slow) {                                         // rare, divergent
+            SEQ_STAT(stt.slow_hops++);
+            const Lz4Tok tt = lz4_token_at(B, seg_start + (u32)rp, C, false);
+            nx = (i32)(tt.next - seg_start);
+            if (tt.flags && !inseg) nx = 0;                         // an odd run-in gives up: walk from the segment boundary
+            else if (tt.flags || nx >= seg_len) { flags |= tt.flags; far = 1; exit_far = tt.next; nx = seg_len; }
+        }
+        rp = live ? nx : rp;
+    }
+    m = ((u64)mhi << 32) | mlo;
+    } else {
+    bool live = start_in;
     for (;;) {
         live = live && rp < seg_len;
         const bool inseg = FIRST ? rp >= 0 : true;
@@ -239,6 +286,7 @@ __device__ __forceinline__ Lz4Walk lz4_walk(const Lz4Bytes& B, bool on, u32 from
             else if (tt.flags || nx >= seg_len) { flags |= tt.flags; far = 1; exit_far = tt.next; nx = seg_len; }
         }
         rp = live ? nx : rp;
+    }
     }
     Lz4Walk w; w.m = m; w.flags = flags; w.exit = far ? exit_far : seg_start + (u32)rp;
     // merged: a re-walk that stopped before seg_len stopped on a visited position (one that did not start has rp == seg_len).  Derived here,
