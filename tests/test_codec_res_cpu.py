@@ -43,14 +43,17 @@ def test_code_object_report_of_the_built_library_against_itself():
     """tools/code_objects.py, the recipe behind profiles/r25/r25_code_objects.md: the library build() made has one gfx950 code object per
     .hip file, each with kernels, and compares identical to itself"""
     so = os.path.join(ROOT, "zpack_amd", "libzpk_codec.so")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "code_objects.py"), so, so, "--names", "zpk_codec.hip", "span_copy.hip", "sink_commit.hip"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "code_objects.py"), so, so, "--names", "zpk_codec.hip", "row_copy.hip", "sink_commit.hip"],
                        capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
     rows = [l for l in p.stdout.split("\n") if l.startswith("| ") and ".hip |" in l]
-    assert [r.split("|")[1].strip() for r in rows] == ["zpk_codec.hip", "span_copy.hip", "sink_commit.hip"], p.stdout[:1500]
+    assert [r.split("|")[1].strip() for r in rows] == ["zpk_codec.hip", "row_copy.hip", "sink_commit.hip"], p.stdout[:1500]
     for r in rows:
         f = [x.strip() for x in r.split("|")]
         assert int(f[2]) > 0 and f[3] == f[4] and int(f[5]) > 0 and f[6] == f[7], r
     for k in ("k_lz4_wave", "k_span_copy", "k_sink_place"):
         assert k in p.stdout
+    for k in ("k_span_copy", "k_plane_copy", "k_delta_copy", "k_window_copy"):    # the four row copies, all of row_copy.hip
+        assert k in p.stdout
+    assert "twin" not in p.stdout and b"twin" not in open(so, "rb").read()         # no kernel compiled a second time under another name: no symbol, device or host
     assert p.stdout.strip().endswith("RESULT: identical")

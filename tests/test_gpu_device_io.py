@@ -1,5 +1,5 @@
 """GPU: the plaintext in DEVICE memory through the library API (include/zpack_amd.h: zpack_amd_read_files_device, _packed,
-zpack_amd_write_files_device), the codec calls behind it and the kernel that moves the bytes (k_span_copy, zpack_amd/csrc/span_copy.h).
+zpack_amd_write_files_device), the codec calls behind it and the kernel that moves the bytes (k_span_copy, zpack_amd/csrc/row_copy.hip).
 
 The reference of every read is zpack_read_files of the same library with host buffers and the same arguments: same results, same bytes
 in all of [buffer, buffer + max_size) — host and device buffers start out as 0xA5, so a byte the host path does not write must not be

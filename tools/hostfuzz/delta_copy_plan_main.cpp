@@ -1,5 +1,5 @@
 // zpack_amd/csrc/delta_copy_plan.h, the header the codec compiles, under ASan + UBSan: the layout of a delta entry and the row table of
-// k_delta_copy.  Every item is walked the way the kernel walks it (dc_item, delta_copy.h) — whole groups of 16 elements against 16 bytes
+// k_delta_copy.  Every item is walked the way the kernel walks it (pc_item, row_copy.h) — whole groups of 16 elements against 16 bytes
 // in each plane with the base beside the plain side, the rest byte by byte through the index map —:
 //   split then join with the same base is the identity, and the stored side is split_k(plain XOR base) as the header states it;
 //   the items tile the bytes of all three sides once;
@@ -27,10 +27,10 @@ struct Walk { u64 items = 0, wide = 0; };
 static Walk run_row(u64 n, u32 k, u32 join, const u8* src, u8* dst, const u8* base, bool reverse_items)
 {
     DeltaCopyRow rows[2];
-    PlaneCopyPlan p = { 0, 0 };
+    CopyPlan p = { 0, 0 };
     CHECK(delta_copy_emit(0x1000, 0x2000, 0x3000, 0, k, join, rows, p) && p.nrows == 0 && p.items == 0);       // no bytes: no row, no item
     CHECK(delta_copy_emit((u64)src, (u64)dst, (u64)base, n, k, join, rows, p));
-    CHECK(p.nrows == (n ? 1u : 0u) && p.items == plane_copy_items(n));
+    CHECK(p.nrows == (n ? 1u : 0u) && p.items == copy_items(n));
     Walk w;
     w.items = p.items;
     const bool inplace = base == dst;
@@ -40,11 +40,11 @@ static Walk run_row(u64 n, u32 k, u32 join, const u8* src, u8* dst, const u8* ba
     u64 covered = 0;
     for (u64 tt = 0; tt < p.items; tt++) {
         const u64 t = reverse_items ? p.items - 1 - tt : tt;
-        CHECK(delta_copy_row_of(rows, p.nrows, t) == 0);
+        CHECK(copy_row_of(rows, p.nrows, t) == 0);
         const DeltaCopyRow& r = rows[0];
         CHECK(r.src == (u64)src && r.dst == (u64)dst && r.base == (u64)base && r.len == n && r.elem == k && r.join == (join ? PLANE_JOIN : PLANE_SPLIT));
         const PlanePiece P = plane_piece(n, k, t - r.item_base);
-        CHECK(P.from < P.to && P.to <= n && P.from % ZPK_PC_PIECE == 0 && P.wide_end <= m * k);
+        CHECK(P.from < P.to && P.to <= n && P.from % ZPK_COPY_PIECE == 0 && P.wide_end <= m * k);
         covered += P.to - P.from;
         // what the item does to plain byte i / stored byte j: reads src, reads base[i], writes dst
         auto one = [&](u64 i, u64 j) {
@@ -80,18 +80,18 @@ int main()
     {
         DeltaCopyRow one[1]; memset(one, 0xA5, sizeof(one));
         const DeltaCopyRow before = one[0];
-        PlaneCopyPlan p = { 0, 0 };
+        CopyPlan p = { 0, 0 };
         for (u32 k : { 0u, 3u, 5u, 6u, 7u, 9u, 16u }) CHECK(!delta_copy_emit(1, 2, 3, 64, k, 0, one, p) && !delta_copy_emit(1, 2, 3, 0, k, 0, one, p));
         CHECK(!delta_copy_emit(1, 2, 0, 64, 2, 0, one, p));                                                    // bytes and no base: not a row of this table
         CHECK(delta_copy_emit(1, 2, 0, 0, 2, 0, one, p));                                                      // (no bytes pass)
         CHECK(p.nrows == 0 && p.items == 0 && memcmp(one, &before, sizeof(before)) == 0);
-        PlaneCopyPlan full = { ZPK_PC_MAX_ROWS, 77 };
-        CHECK(!delta_copy_emit(1, 2, 3, 4, 2, 0, one, full) && full.nrows == ZPK_PC_MAX_ROWS && full.items == 77 && memcmp(one, &before, sizeof(before)) == 0);
+        CopyPlan full = { ZPK_COPY_MAX_ROWS, 77 };
+        CHECK(!delta_copy_emit(1, 2, 3, 4, 2, 0, one, full) && full.nrows == ZPK_COPY_MAX_ROWS && full.items == 77 && memcmp(one, &before, sizeof(before)) == 0);
         DeltaCopyRow three[3];
-        PlaneCopyPlan q = { 0, 0 };
+        CopyPlan q = { 0, 0 };
         CHECK(delta_copy_emit(10, 20, 30, 16385, 4, 1, three, q) && delta_copy_emit(11, 21, 31, 0, 4, 1, three, q) && delta_copy_emit(12, 22, 32, 5, 1, 0, three, q));
         CHECK(q.nrows == 2 && q.items == 3 && three[0].item_base == 0 && three[1].item_base == 2 && three[1].base == 32 && three[0].join == PLANE_JOIN && three[1].join == PLANE_SPLIT);
-        CHECK(delta_copy_row_of(three, 2, 0) == 0 && delta_copy_row_of(three, 2, 1) == 0 && delta_copy_row_of(three, 2, 2) == 1);
+        CHECK(copy_row_of(three, 2, 0) == 0 && copy_row_of(three, 2, 1) == 0 && copy_row_of(three, 2, 2) == 1);
         printf("rows: as given with base, element size and direction; none for the empty row, none without a base; item_base ascending\n");
     }
     // ---- base against destination ----

@@ -1,6 +1,6 @@
 #!/bin/bash
 # CPU, AddressSanitizer + UBSan: the layout of a delta entry and the row table of k_delta_copy, every item walked as the kernel walks it,
-# in place too (zpack_amd/csrc/delta_copy_plan.h: the very header the codec compiles).  tools/hostfuzz/run_delta_copy_plan.sh
+# in place too (zpack_amd/csrc/delta_copy_plan.h over copy_rows_plan.h: the very headers the codec compiles).  tools/hostfuzz/run_delta_copy_plan.sh
 set -e
 cd "$(dirname "$0")/../.."
 work=$(mktemp -d -t zpk_deltacopyplan.XXXXXX)    # private to this run: a directory left by another user cannot block it

@@ -1,6 +1,6 @@
 #!/bin/bash
 # CPU, AddressSanitizer + UBSan: the layout of a byte-plane entry, the row table, work items and launches of k_plane_copy
-# (zpack_amd/csrc/plane_copy_plan.h: the very header the codec compiles).  Arguments go to the program (`dump`: the stored side of every
+# (zpack_amd/csrc/plane_copy_plan.h over copy_rows_plan.h: the very headers the codec compiles).  Arguments go to the program (`dump`: the stored side of every
 # case, for a model to compare with).  tools/hostfuzz/run_plane_copy_plan.sh
 set -e
 cd "$(dirname "$0")/../.."

@@ -20,12 +20,12 @@ int main()
     std::vector<SpanCopyRow> rows(nlens + 1);
     memset(rows.data(), 0xA5, rows.size() * sizeof(SpanCopyRow));
     const SpanCopyRow guard = rows[nlens];
-    SpanCopyPlan p = { 0, 0 };
+    CopyPlan p = { 0, 0 };
     std::vector<u64> in_src, in_dst, in_len;
     u64 src_at = 0x7f0000000003ull, dst_at = 0x7e000000000dull, items = 0;
     for (u64 k = 0; k < nlens; k++) {
-        CHECK(span_copy_items(lens[k]) == want_items[k]);
-        const SpanCopyPlan before = p;
+        CHECK(copy_items(lens[k]) == want_items[k]);
+        const CopyPlan before = p;
         CHECK(span_copy_emit(src_at, dst_at, lens[k], rows.data(), p));
         if (lens[k] == 0) CHECK(p.nrows == before.nrows && p.items == before.items);               // no row, no item
         else { in_src.push_back(src_at); in_dst.push_back(dst_at); in_len.push_back(lens[k]); items += want_items[k]; }
@@ -35,7 +35,7 @@ int main()
     CHECK(p.nrows == nlens - 1 && p.items == 1 + 1 + 1 + 2 + (1ull << 18) + 1);
     CHECK(memcmp(&rows[p.nrows], &guard, sizeof(guard)) == 0 && memcmp(&rows[nlens], &guard, sizeof(guard)) == 0);      // nothing behind the last row
     for (u64 k = 0; k < p.nrows; k++) CHECK(rows[k].src == in_src[k] && rows[k].dst == in_dst[k] && rows[k].len == in_len[k]);
-    CHECK(span_copy_items(~0ull) == (1ull << 50));                                                 // (nothing wraps)
+    CHECK(copy_items(~0ull) == (1ull << 50));                                                 // (nothing wraps)
     printf("rows: %llu spans of the lengths 0, 1, 16383, 16384, 16385, 2^32 + 5 are %llu rows and %llu items: rows as given, none for the empty span\n",
            (unsigned long long)nlens, (unsigned long long)p.nrows, (unsigned long long)p.items);
 
@@ -43,44 +43,44 @@ int main()
     u64 next = 0, searched = 0;
     for (u64 k = 0; k < p.nrows; k++) {
         CHECK(rows[k].item_base == next);                                                          // ascending, disjoint, no gap
-        const u64 n = span_copy_items(rows[k].len);
-        CHECK(n >= 1 && (n - 1) * ZPK_SC_PIECE < rows[k].len && rows[k].len <= n * ZPK_SC_PIECE);  // the last item holds 1..16384 bytes
+        const u64 n = copy_items(rows[k].len);
+        CHECK(n >= 1 && (n - 1) * ZPK_COPY_PIECE < rows[k].len && rows[k].len <= n * ZPK_COPY_PIECE);  // the last item holds 1..16384 bytes
         next += n;
-        for (u64 t : { rows[k].item_base, rows[k].item_base + n / 2, next - 1 }) { CHECK(span_copy_row_of(rows.data(), p.nrows, t) == k); searched++; }
+        for (u64 t : { rows[k].item_base, rows[k].item_base + n / 2, next - 1 }) { CHECK(copy_row_of(rows.data(), p.nrows, t) == k); searched++; }
     }
     CHECK(next == p.items);
     {   // a full table takes no further row
         SpanCopyRow one[1]; memset(one, 0xA5, sizeof(one));
         const SpanCopyRow before = one[0];
-        SpanCopyPlan full = { ZPK_SC_MAX_ROWS, 77 };
-        CHECK(!span_copy_emit(1, 2, 3, one, full) && full.nrows == ZPK_SC_MAX_ROWS && full.items == 77 && memcmp(one, &before, sizeof(before)) == 0);
+        CopyPlan full = { ZPK_COPY_MAX_ROWS, 77 };
+        CHECK(!span_copy_emit(1, 2, 3, one, full) && full.nrows == ZPK_COPY_MAX_ROWS && full.items == 77 && memcmp(one, &before, sizeof(before)) == 0);
         CHECK(span_copy_emit(1, 2, 0, one, full));
     }
     printf("item_base: ascending and disjoint without a gap, %llu items searched for land in their own rows\n", (unsigned long long)searched);
 
     // ---- the launches ----
     {
-        CHECK(span_copy_launches(0) == 0 && span_copy_launches(1) == 1 && span_copy_launches(ZPK_SC_MAX_ITEMS) == 1 && span_copy_launches(ZPK_SC_MAX_ITEMS + 1) == 2);
-        SpanCopyLaunch L = span_copy_launch(ZPK_SC_MAX_ITEMS, 0);
-        CHECK(L.item0 == 0 && L.items == ZPK_SC_MAX_ITEMS && L.grid == 0x7FFFFFFFu);
-        L = span_copy_launch(ZPK_SC_MAX_ITEMS + 1, 0);
-        CHECK(L.item0 == 0 && L.items == ZPK_SC_MAX_ITEMS && L.grid == 0x7FFFFFFFu);
-        L = span_copy_launch(ZPK_SC_MAX_ITEMS + 1, 1);
-        CHECK(L.item0 == ZPK_SC_MAX_ITEMS && L.items == 1 && L.grid == 1);
-        L = span_copy_launch(5, 0);
+        CHECK(copy_launches(0) == 0 && copy_launches(1) == 1 && copy_launches(ZPK_COPY_MAX_ITEMS) == 1 && copy_launches(ZPK_COPY_MAX_ITEMS + 1) == 2);
+        CopyLaunch L = copy_launch(ZPK_COPY_MAX_ITEMS, 0);
+        CHECK(L.item0 == 0 && L.items == ZPK_COPY_MAX_ITEMS && L.grid == 0x7FFFFFFFu);
+        L = copy_launch(ZPK_COPY_MAX_ITEMS + 1, 0);
+        CHECK(L.item0 == 0 && L.items == ZPK_COPY_MAX_ITEMS && L.grid == 0x7FFFFFFFu);
+        L = copy_launch(ZPK_COPY_MAX_ITEMS + 1, 1);
+        CHECK(L.item0 == ZPK_COPY_MAX_ITEMS && L.items == 1 && L.grid == 1);
+        L = copy_launch(5, 0);
         CHECK(L.item0 == 0 && L.items == 5 && L.grid == 2);
         // a small grid limit: the launches tile the items exactly, each grid holds its items and fewer than four to spare
         const u64 total = p.items, cap = 1000;
         u64 at = 0;
-        const u64 nl = span_copy_launches(total, cap);
+        const u64 nl = copy_launches(total, cap);
         for (u64 j = 0; j < nl; j++) {
-            L = span_copy_launch(total, j, cap);
+            L = copy_launch(total, j, cap);
             CHECK(L.item0 == at && L.items >= 1 && L.items <= cap && (u64)L.grid * 4 >= L.items && (u64)L.grid * 4 < L.items + 4);
             at += L.items;
         }
         CHECK(at == total && nl == (total + cap - 1) / cap);
         printf("launches: one grid holds %llu items, one more is a second launch of 1; %llu items at 1000 a grid are %llu launches that tile them\n",
-               (unsigned long long)ZPK_SC_MAX_ITEMS, (unsigned long long)total, (unsigned long long)nl);
+               (unsigned long long)ZPK_COPY_MAX_ITEMS, (unsigned long long)total, (unsigned long long)nl);
     }
 
     // ---- the staging slots ----

@@ -1,5 +1,5 @@
 // zpack_amd/csrc/window_copy_plan.h, the header the codec compiles, under ASan + UBSan: the window, its rule, the row table of
-// k_window_copy and what an item covers.  Every item is walked the way the kernel walks it (wc_item, window_copy.h) — the groups of 16
+// k_window_copy and what an item covers.  Every item is walked the way the kernel walks it (wc_item, row_copy.h) — the groups of 16
 // elements inside one window row against 16 bytes in each plane, the loose bytes through the map, both numbered through the whole item —
 // over edge and randomized geometries:
 //   the items tile [0, window_bytes) exactly once;
@@ -26,10 +26,10 @@ struct Walk { u64 items = 0, wide = 0, bytes = 0; };
 static Walk run_row(u64 n, u32 k, const Window& w, const u8* stored, u8* dst, const u8* base, bool reverse_items)
 {
     WindowCopyRow rows[1];
-    PlaneCopyPlan p = { 0, 0 };
+    CopyPlan p = { 0, 0 };
     CHECK(window_copy_emit((u64)stored, (u64)dst, (u64)base, n, w, k, rows, p));
     const u64 len = window_bytes(w);
-    CHECK(p.nrows == (len ? 1u : 0u) && p.items == plane_copy_items(len));
+    CHECK(p.nrows == (len ? 1u : 0u) && p.items == copy_items(len));
     Walk out;
     out.items = p.items; out.bytes = len;
     const bool inplace = base && base == dst;
@@ -39,12 +39,12 @@ static Walk run_row(u64 n, u32 k, const Window& w, const u8* stored, u8* dst, co
     u64 covered = 0;
     for (u64 tt = 0; tt < p.items; tt++) {
         const u64 t = reverse_items ? p.items - 1 - tt : tt;
-        CHECK(window_copy_row_of(rows, p.nrows, t) == 0);
+        CHECK(copy_row_of(rows, p.nrows, t) == 0);
         const WindowCopyRow& r = rows[0];
         CHECK(r.src == (u64)stored && r.dst == (u64)dst && r.base == (u64)base && r.n == n && r.len == len && r.elem == k && r.item_base == 0);
         CHECK(r.row_bytes == w.row_bytes && r.row0 == w.row0 && r.col0 == w.col0 && r.cols == w.cols);
         const WindowPiece P = window_piece(len, w.cols, k, t);
-        CHECK(P.from < P.to && P.to <= len && P.from % ZPK_PC_PIECE == 0 && P.to - P.from <= ZPK_PC_PIECE);
+        CHECK(P.from < P.to && P.to <= len && P.from % ZPK_COPY_PIECE == 0 && P.to - P.from <= ZPK_COPY_PIECE);
         CHECK((u64)P.groups * 16u * k + P.loose == P.to - P.from);                                              // groups and loose bytes make up the item
         covered += P.to - P.from;
         auto one = [&](u64 d, u64 i) {
@@ -118,16 +118,16 @@ int main()
         CHECK(window_valid(0, 2, Window{ 64, 0, 0, 0, 64 }));                                                   // an entry of no bytes: no rows
         WindowCopyRow one[1]; memset(one, 0xA5, sizeof(one));
         const WindowCopyRow before = one[0];
-        PlaneCopyPlan p = { 0, 0 };
+        CopyPlan p = { 0, 0 };
         CHECK(!window_copy_emit(1, 2, 3, 256, Window{ 64, 3, 2, 8, 16 }, 4, one, p) && window_copy_emit(1, 2, 3, 256, Window{ 64, 1, 0, 8, 16 }, 4, one, p));
         CHECK(p.nrows == 0 && p.items == 0 && memcmp(one, &before, sizeof(before)) == 0);
-        PlaneCopyPlan full = { ZPK_PC_MAX_ROWS, 5 };
+        CopyPlan full = { ZPK_COPY_MAX_ROWS, 5 };
         CHECK(!window_copy_emit(1, 2, 3, 256, ok, 4, one, full) && memcmp(one, &before, sizeof(before)) == 0);
         WindowCopyRow two[2];
-        PlaneCopyPlan q = { 0, 0 };
+        CopyPlan q = { 0, 0 };
         CHECK(window_copy_emit(1, 2, 0, 1 << 20, Window{ 1 << 10, 0, 1 << 10, 0, 32 }, 2, two, q) && window_copy_emit(4, 5, 6, 256, ok, 4, two, q));
         CHECK(q.nrows == 2 && q.items == 3 && two[1].item_base == 2 && two[0].base == 0 && two[1].len == 32);
-        CHECK(window_copy_row_of(two, 2, 1) == 0 && window_copy_row_of(two, 2, 2) == 1);
+        CHECK(copy_row_of(two, 2, 1) == 0 && copy_row_of(two, 2, 2) == 1);
         CHECK(window_overlap_ok(100, 100, ok) && window_overlap_ok(100, 132, ok) && !window_overlap_ok(100, 131, ok) && !window_overlap_ok(131, 100, ok));
         printf("rule: every clause of window_valid, wrap-around included; rows as given, none for the empty window; overlap over window_bytes\n");
     }

@@ -54,6 +54,10 @@ def _hipcc():
     return h
 
 
+# the compile line of the codec, product and developer build alike: one gfx950 code object per file, in this order
+CODEC_HIP = [os.path.join(CSRC, f) for f in ("zpk_codec.hip", "row_copy.hip", "sink_commit.hip", "stored_hash.hip", "span_hash.hip")]
+
+
 def build_codec(force=False, verbose=False):
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", "zpack_codec.h")]
     flags = (os.environ.get("ZPK_STATS") or "") + "|" + os.environ.get("ZPK_DEFINES", "")
@@ -62,7 +66,7 @@ def build_codec(force=False, verbose=False):
         return CODEC_SO
     dig = dig or _digest(srcs, flags)
     cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
-           "-Wno-unused-function", "-o", CODEC_SO, os.path.join(CSRC, "zpk_codec.hip"), os.path.join(CSRC, "span_copy.hip"), os.path.join(CSRC, "sink_commit.hip"), os.path.join(CSRC, "stored_hash.hip"), os.path.join(CSRC, "plane_copy.hip"), os.path.join(CSRC, "delta_copy.hip"), os.path.join(CSRC, "span_hash.hip"), os.path.join(CSRC, "window_copy.hip")]
+           "-Wno-unused-function", "-o", CODEC_SO] + CODEC_HIP
     if os.environ.get("ZPK_STATS"):          # developer build: per-phase cycle counters in the decode kernels
         cmd.insert(1, "-DZPK_STATS=1")
     for d in os.environ.get("ZPK_DEFINES", "").split():      # developer build: A/B variants (-D names)
@@ -85,7 +89,7 @@ def build_codec_dev(force=False, verbose=False):
     dig = dig or _digest(srcs, "dev")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-DZPK_DEVELOPER",
-           "-o", out, os.path.join(CSRC, "zpk_codec.hip"), os.path.join(CSRC, "span_copy.hip"), os.path.join(CSRC, "sink_commit.hip"), os.path.join(CSRC, "stored_hash.hip"), os.path.join(CSRC, "plane_copy.hip"), os.path.join(CSRC, "delta_copy.hip"), os.path.join(CSRC, "span_hash.hip"), os.path.join(CSRC, "window_copy.hip")]
+           "-o", out] + CODEC_HIP
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -1,10 +1,10 @@
 // delta_copy_plan.h — DELTA entries: a tensor stored as its XOR against a BASE in device memory (the previous checkpoint, which the caller
 // holds anyway), grouped into byte planes.  Most weights of a float tensor do not change in a step and those that do change in their low
 // mantissa bits, so `new XOR old` is mostly zero bytes, and after the split the high planes are almost all zero.  The XOR rides on the
-// copy that carries the plaintext between the caller's device buffers and the codec's staging anyway (k_delta_copy, delta_copy.h, beside
+// copy that carries the plaintext between the caller's device buffers and the codec's staging anyway (k_delta_copy, row_copy.hip, beside
 // k_plane_copy): one more read stream, no further pass over the plaintext, no second copy of it.  Decided here, in one place: the layout
-// and the row table the kernel reads.  The index map (plane_stored_index), the 16 KiB item and its pieces (plane_piece), the launch split
-// (plane_copy_launch) and the element sizes (plane_elem_valid) are those of plane_copy_plan.h and are not restated.
+// and the row table the kernel reads.  The index map (plane_stored_index), what an item covers (plane_piece) and the element sizes
+// (plane_elem_valid) are those of plane_copy_plan.h, the 16 KiB item, the search and the launches those of copy_rows_plan.h.
 // Plain C++17 like that header: tools/hostfuzz builds this file with g++ under ASan + UBSan.
 #pragma once
 #include "plane_copy_plan.h"
@@ -20,30 +20,24 @@ namespace zpk {
 ZPK_HD static inline u8 delta_byte(u8 a, u8 base) { return (u8)(a ^ base); }
 
 // ---- the row table ---------------------------------------------------------------------------------------------------------------------
-// PlaneCopyRow with the base beside the two ends; items, item_base and the search are plane_copy_plan.h's.  SPLIT: src plain, dst stored.
+// PlaneCopyRow with the base beside the two ends; items, item_base and the search are copy_rows_plan.h's.  SPLIT: src plain, dst stored.
 // JOIN: src stored, dst plain.  The base lies beside the PLAIN side either way.
 struct DeltaCopyRow { u64 src, dst, base, len, item_base; u32 elem, join; };
 // Appends the row.  false: the table is full, the element size is none, or a row with bytes has no base — nothing is written.
-static inline bool delta_copy_emit(u64 src, u64 dst, u64 base, u64 len, u32 elem, u32 join, DeltaCopyRow* rows, PlaneCopyPlan& p)
+static inline bool delta_copy_emit(u64 src, u64 dst, u64 base, u64 len, u32 elem, u32 join, DeltaCopyRow* rows, CopyPlan& p)
 {
     if (!plane_elem_valid(elem)) return false;
     if (len == 0) return true;
-    if (base == 0 || p.nrows >= ZPK_PC_MAX_ROWS) return false;
+    if (base == 0 || p.nrows >= ZPK_COPY_MAX_ROWS) return false;
     rows[p.nrows] = DeltaCopyRow{ src, dst, base, len, p.items, elem, join ? PLANE_JOIN : PLANE_SPLIT };
-    p.nrows++; p.items += plane_copy_items(len);
+    p.nrows++; p.items += copy_items(len);
     return true;
-}
-static inline u64 delta_copy_row_of(const DeltaCopyRow* rows, u64 nrows, u64 t)
-{
-    u64 lo = 0, hi = nrows;
-    while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (rows[mid].item_base <= t) lo = mid; else hi = mid; }
-    return lo;
 }
 
 // ---- base and destination ----------------------------------------------------------------------------------------------------------------
 // JOIN with base == dst EXACTLY is legal (the buffer that holds the previous checkpoint becomes the new one): item t reads
 // base[from, to) and writes dst[from, to), the same plain range; the items tile the plain side, so no item writes what another reads; and
-// inside an item a lane loads the base bytes of its groups before it stores to the same addresses (delta_copy.h).  Any OTHER overlap of
+// inside an item a lane loads the base bytes of its groups before it stores to the same addresses (pc_item, row_copy.h).  Any OTHER overlap of
 // [base, base + len) with [dst, dst + len) is refused: an item would read base bytes that another item has written or not.
 static inline bool delta_overlap_ok(u64 base, u64 dst, u64 len)
 {

@@ -1,22 +1,13 @@
 // plane_copy_plan.h — BYTE-PLANE entries: the plaintext of an entry whose elements are k bytes wide (k in {2, 4, 8}: a float tensor),
 // stored with byte 0 of every element first, then byte 1 of every element, and so on.  The bytes of a float that compress (sign and
 // exponent) then lie together and those that are noise (mantissa) lie together.  The transposition happens inside the copies that move
-// the plaintext between the caller's device buffers and the codec's staging anyway (k_plane_copy, plane_copy.h, beside k_span_copy):
-// SPLIT on the way in, JOIN on the way out.  Decided here, in one place: the layout, the row table the kernel reads, its work items and
-// launches, and which element sizes there are.
+// the plaintext between the caller's device buffers and the codec's staging anyway (k_plane_copy, row_copy.hip, beside k_span_copy):
+// SPLIT on the way in, JOIN on the way out.  Decided here, in one place: the layout, the row table the kernel reads, what an item of it
+// covers, and which element sizes there are.  The 16 KiB item, the search and the launches: copy_rows_plan.h.
 // Plain C++17, pj_types.h and standard headers only: tools/hostfuzz builds this file with g++ under ASan + UBSan (g++ knows no HIP),
 // which keeps it so.  The index map is also device code (k_plane_copy): ZPK_HD is empty on a CPU build.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include "pj_types.h"                            // (the typedefs)
-#ifndef ZPK_HD
-#ifdef __HIPCC__
-#define ZPK_HD __host__ __device__
-#else
-#define ZPK_HD
-#endif
-#endif
+#include "copy_rows_plan.h"
 
 namespace zpk {
 
@@ -37,30 +28,18 @@ ZPK_HD static inline u64 plane_stored_index(u64 n, u32 k, u64 i)
 // ---- the row table ---------------------------------------------------------------------------------------------------------------------
 // A WORK ITEM is 16 KiB of a row's INTERLEAVED (plain) side, one wave's — the source of a split, the destination of a join —, so it is
 // 16384 / k whole elements, a multiple of the 1024 a wave takes in one step, except in the last item of a row, which also owns the tail.
-// Row r owns the items [item_base, item_base + plane_copy_items(len)); item_base ascends without gaps, so the wave of item t finds its
-// row as the LAST one with item_base <= t (the search of k_span_copy).  A row of no bytes takes no row and no item.
-#define ZPK_PC_PIECE (16u << 10)
+// A row of no bytes takes no row and no item.
 enum : u32 { PLANE_SPLIT = 0, PLANE_JOIN = 1 };
 struct PlaneCopyRow { u64 src, dst, len, item_base; u32 elem, join; };               // src, dst: device addresses; elem in {1, 2, 4, 8}
-struct PlaneCopyPlan { u64 nrows, items; };
-#define ZPK_PC_MAX_ROWS 0xFFFFFFFFull                // the kernel searches with 32-bit row numbers
-ZPK_HD static inline u64 plane_copy_items(u64 len) { return len / ZPK_PC_PIECE + (len % ZPK_PC_PIECE ? 1 : 0); }      // (no sum that could wrap)
-// Appends the row to the table.  false: the table is full (ZPK_PC_MAX_ROWS) or the element size is none — nothing is written.
-static inline bool plane_copy_emit(u64 src, u64 dst, u64 len, u32 elem, u32 join, PlaneCopyRow* rows, PlaneCopyPlan& p)
+// Appends the row to the table.  false: the table is full (ZPK_COPY_MAX_ROWS) or the element size is none — nothing is written.
+static inline bool plane_copy_emit(u64 src, u64 dst, u64 len, u32 elem, u32 join, PlaneCopyRow* rows, CopyPlan& p)
 {
     if (!plane_elem_valid(elem)) return false;
     if (len == 0) return true;
-    if (p.nrows >= ZPK_PC_MAX_ROWS) return false;
+    if (p.nrows >= ZPK_COPY_MAX_ROWS) return false;
     rows[p.nrows] = PlaneCopyRow{ src, dst, len, p.items, elem, join ? PLANE_JOIN : PLANE_SPLIT };
-    p.nrows++; p.items += plane_copy_items(len);
+    p.nrows++; p.items += copy_items(len);
     return true;
-}
-// the row of item t, as the kernel finds it
-static inline u64 plane_copy_row_of(const PlaneCopyRow* rows, u64 nrows, u64 t)
-{
-    u64 lo = 0, hi = nrows;
-    while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (rows[mid].item_base <= t) lo = mid; else hi = mid; }
-    return lo;
 }
 // What item `piece` of a row of `len` bytes with element size k covers: the plain bytes [from, to), of which [from, wide_end) are whole
 // groups of 16 elements — the kernel's wide path, 16 * k plain bytes against 16 bytes in each of the k planes — and [wide_end, to) go
@@ -69,27 +48,12 @@ struct PlanePiece { u64 from, wide_end, to; };
 ZPK_HD static inline PlanePiece plane_piece(u64 len, u32 k, u64 piece)
 {
     PlanePiece P;
-    P.from = piece * ZPK_PC_PIECE;
-    P.to = len - P.from < ZPK_PC_PIECE ? len : P.from + ZPK_PC_PIECE;
+    P.from = piece * ZPK_COPY_PIECE;
+    P.to = len - P.from < ZPK_COPY_PIECE ? len : P.from + ZPK_COPY_PIECE;
     const u64 m = len / k;
     const u64 e1 = P.to / k < m ? P.to / k : m;                                       // whole elements end here
     P.wide_end = P.from + ((e1 * k - P.from) / (16u * k)) * (16u * k);
     return P;
-}
-
-// ---- the launches ----------------------------------------------------------------------------------------------------------------------
-// Four items per workgroup; a grid holds at most max_items of them (the x limit of a grid), a table with more goes in several launches
-// over the SAME table: launch j takes the items [j * max_items, ...), the kernel adds that base to its wave number (as k_span_copy).
-#define ZPK_PC_MAX_ITEMS (4ull * 0x7FFFFFFFull)
-struct PlaneCopyLaunch { u64 item0, items; u32 grid; };
-static inline u64 plane_copy_launches(u64 items, u64 max_items = ZPK_PC_MAX_ITEMS) { return items / max_items + (items % max_items ? 1 : 0); }
-static inline PlaneCopyLaunch plane_copy_launch(u64 items, u64 j, u64 max_items = ZPK_PC_MAX_ITEMS)
-{
-    PlaneCopyLaunch L;
-    L.item0 = j * max_items;
-    L.items = items - L.item0 < max_items ? items - L.item0 : max_items;
-    L.grid = (u32)((L.items + 3) / 4);
-    return L;
 }
 
 }  // namespace zpk

@@ -1,6 +1,6 @@
 // sink_commit.hip — k_sink_cut and k_sink_place (sink_commit.h) as a code object of their own, and the one host function that launches
 // them.  zpk_codec.hip stages, encodes and scans a sub-batch and calls sink_commit_launch; keeping the kernels out of that file keeps its
-// code object, and where every other kernel lies in it, unchanged (as span_copy.hip does for k_span_copy).
+// code object, and where every other kernel lies in it, unchanged (as row_copy.hip does for the four row copies).
 #include <hip/hip_runtime.h>
 #include "sink_commit.h"
 

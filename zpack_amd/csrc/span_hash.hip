@@ -1,6 +1,6 @@
 // span_hash.hip — k_span_hash (span_hash.h) and the chip-wide pair it hands its long rows to, as a code object of its own, and the one
 // host function that launches them.  zpk_codec.hip builds the tables and calls span_hash_launch; keeping the kernels out of that file
-// keeps its code object, and those of span_copy.hip, sink_commit.hip, stored_hash.hip, plane_copy.hip and delta_copy.hip, unchanged.
+// keeps its code object, and those of row_copy.hip, sink_commit.hip and stored_hash.hip, unchanged.
 #include <hip/hip_runtime.h>
 // xxh3_span.h, which span_hash.h includes as it is, defines the kernels k_xxh3_partials and k_xxh3_chain, and zpk_codec.hip owns those
 // names: a second definition would not link.  The copies compiled here are the ones this file launches, under names of their own.

@@ -1,6 +1,6 @@
 // stored_hash.hip — k_stored_hash (stored_hash.h) as a code object of its own, and the one host function that launches it.  decode_launch
 // (zpk_codec.hip) calls stored_hash_launch in place of k_stored when the batch has no destination; keeping the kernel out of that file
-// keeps its code object, and where every other kernel lies in it, unchanged (as span_copy.hip does for k_span_copy).
+// keeps its code object, and where every other kernel lies in it, unchanged (as row_copy.hip does for the four row copies).
 #include <hip/hip_runtime.h>
 #include "stored_hash.h"
 

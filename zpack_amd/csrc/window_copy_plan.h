@@ -1,11 +1,11 @@
 // window_copy_plan.h — WINDOW reads: a 2-D sub-block of an entry, seen as a matrix of rows x row_bytes, delivered densely into a
 // destination of window size.  A reader that owns part of every tensor (a tensor-parallel rank, a pipeline stage) otherwise needs a
 // full-size scratch tensor per entry and a second pass over the plaintext to cut its part out; every device read already moves each
-// plaintext byte once, from the codec's staging to the caller's buffer, and the cut rides on that copy (k_window_copy, window_copy.h,
+// plaintext byte once, from the codec's staging to the caller's buffer, and the cut rides on that copy (k_window_copy, row_copy.hip,
 // beside k_plane_copy and k_delta_copy).  The byte planes are joined and the base is XORed on the way.  Decided here, in one place: the
 // window, the rule it has to pass, the map, the row table the kernel reads and what an item of it covers.  The index map of the stored
-// side (plane_stored_index), the element sizes (plane_elem_valid), the 16 KiB item and the launch split (plane_copy_launch) are those of
-// plane_copy_plan.h, the overlap rule is delta_copy_plan.h's, and none is restated.
+// side (plane_stored_index) and the element sizes (plane_elem_valid) are those of plane_copy_plan.h, the 16 KiB item, the search and the
+// launches those of copy_rows_plan.h, the overlap rule is delta_copy_plan.h's, and none is restated.
 // Plain C++17 like those headers: tools/hostfuzz builds this file with g++ under ASan + UBSan.
 #pragma once
 #include "delta_copy_plan.h"
@@ -38,24 +38,18 @@ ZPK_HD static inline u64 window_plain_index(const Window& w, u64 d) { return (w.
 
 // ---- the row table ---------------------------------------------------------------------------------------------------------------------
 // src: the entry's stored bytes, n of them; dst, base: len = window_bytes bytes each (base 0: none).  A WORK ITEM is 16 KiB of the row's
-// DESTINATION; items, item_base and the search are plane_copy_plan.h's.
+// DESTINATION; items, item_base and the search are copy_rows_plan.h's.
 struct WindowCopyRow { u64 src, dst, base, n, row_bytes, row0, col0, cols, len, item_base; u32 elem, pad; };
 // Appends the row.  false: the table is full or the window fails window_valid — nothing is written.  A window of no bytes takes no row.
-static inline bool window_copy_emit(u64 src, u64 dst, u64 base, u64 n, const Window& w, u32 elem, WindowCopyRow* rows, PlaneCopyPlan& p)
+static inline bool window_copy_emit(u64 src, u64 dst, u64 base, u64 n, const Window& w, u32 elem, WindowCopyRow* rows, CopyPlan& p)
 {
     if (!window_valid(n, elem, w)) return false;
     const u64 len = window_bytes(w);
     if (len == 0) return true;
-    if (p.nrows >= ZPK_PC_MAX_ROWS) return false;
+    if (p.nrows >= ZPK_COPY_MAX_ROWS) return false;
     rows[p.nrows] = WindowCopyRow{ src, dst, base, n, w.row_bytes, w.row0, w.col0, w.cols, len, p.items, elem, 0 };
-    p.nrows++; p.items += plane_copy_items(len);
+    p.nrows++; p.items += copy_items(len);
     return true;
-}
-static inline u64 window_copy_row_of(const WindowCopyRow* rows, u64 nrows, u64 t)
-{
-    u64 lo = 0, hi = nrows;
-    while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (rows[mid].item_base <= t) lo = mid; else hi = mid; }
-    return lo;
 }
 
 // ---- what an item covers ---------------------------------------------------------------------------------------------------------------
@@ -75,8 +69,8 @@ ZPK_HD static inline WindowPiece window_piece(u64 len, u64 cols, u32 k, u64 piec
 {
     WindowPiece P;
     const u32 gb = 16u * k;
-    P.from = piece * ZPK_PC_PIECE;
-    P.to = len - P.from < ZPK_PC_PIECE ? len : P.from + ZPK_PC_PIECE;
+    P.from = piece * ZPK_COPY_PIECE;
+    P.to = len - P.from < ZPK_COPY_PIECE ? len : P.from + ZPK_COPY_PIECE;
     P.r0 = P.from / cols; P.c0 = P.from % cols;
     const u64 span = P.to - P.from;
     P.seg0 = cols - P.c0 < span ? cols - P.c0 : span;

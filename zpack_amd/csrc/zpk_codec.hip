@@ -42,19 +42,19 @@
 #include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
 #include "stored_plan.h"                         // the large stored entries of a device-resident batch: which are taken, their span table, the verdict (plain C++, likewise)
 #include "stored_span.h"                         // k_stored_span: their copy fused with the XXH3 partial sums, across the chip
-#include "span_copy_plan.h"                      // plaintext in the caller's DEVICE memory: the row table, items and launches of k_span_copy, the staging slots, the pointer test (plain C++, likewise)
-// k_span_copy (span_copy.h) is compiled in a file of its own, span_copy.hip: this file's code object stays the one it was, kernel for
-// kernel at the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
-namespace zpk { void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
-#include "plane_copy_plan.h"                     // byte-plane entries: the layout, the row table, items and launches of k_plane_copy (plain C++, likewise)
-// k_plane_copy (plane_copy.h) is compiled in plane_copy.hip, for the same reason
-namespace zpk { void plane_copy_launch(const PlaneCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
+#include "copy_rows_plan.h"                      // the four row copies below: the 16 KiB item, the row search and the launch split they share (plain C++, likewise)
+#include "span_copy_plan.h"                      // plaintext in the caller's DEVICE memory: the row table of k_span_copy, the staging slots, the pointer test (plain C++, likewise)
+#include "plane_copy_plan.h"                     // byte-plane entries: the layout and the row table of k_plane_copy (plain C++, likewise)
 #include "delta_copy_plan.h"                     // delta entries: a tensor stored as its XOR against a base in device memory, and the row table of k_delta_copy (plain C++, likewise)
-// k_delta_copy (delta_copy.h) is compiled in delta_copy.hip, for the same reason
-namespace zpk { void delta_copy_launch(const DeltaCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
 #include "window_copy_plan.h"                    // window reads: a 2-D sub-block of an entry delivered densely, the rule, the map and the row table of k_window_copy (plain C++, likewise)
-// k_window_copy (window_copy.h) is compiled in window_copy.hip, for the same reason
-namespace zpk { void window_copy_launch(const WindowCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st); }
+// The four kernels are compiled in a file of their own, row_copy.hip: this file's code object stays the one it was, kernel for kernel at
+// the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
+namespace zpk {
+void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
+void plane_copy_launch(const PlaneCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
+void delta_copy_launch(const DeltaCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
+void window_copy_launch(const WindowCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
+}
 #include "span_hash_plan.h"                      // XXH3 of arbitrary device spans (the bases of delta entries): one-wave and chip-wide rows, their tables, launches and loads (plain C++, likewise)
 // k_span_hash (span_hash.h) and its copies of the chip-wide pair are compiled in span_hash.hip, for the same reason
 namespace zpk { u32 span_hash_launch(u8* d_block, const SpanHashPlan& p, const SpanHashLayout& L, u64 max_wave_rows, u64 max_groups, u64 max_chains, hipStream_t st); }
@@ -706,6 +706,10 @@ struct LastCall {
     int  totals_valid = 0;
 };
 
+// The row table of one of the row copies (row_table_enqueue): on the device, and pinned going up — the event says that the upload has
+// run, the pinned block is written again only behind it.
+struct RowTable { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; };
+
 // Every HIP resource below is owned by the member that names it (codec_res.h): deleting the codec releases all of them.
 // A growable pinned block (PinBuf) is regrown only while nothing on a stream still reads or writes it: a call that uses one drains the
 // stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk, sh.h: hipStreamSynchronize behind the copy home; sspan.h: the
@@ -791,16 +795,10 @@ struct zpk_codec {
         SideStream side;                         // the second stream of the forked form (created on first use)
     } sspan;
 
-    // plaintext in the caller's device memory (span_copy_plan.h / span_copy.h): the row table of k_span_copy, pinned going up — the event
-    // says that the upload has run, the block is written again only behind it
-    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } sc;
-    // ... and the row table of k_plane_copy (plane_copy_plan.h / plane_copy.h), a block of its own under the same rule: a call with
-    // byte-plane entries fills both tables before either kernel has run
-    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } pc;
-    // ... and that of k_delta_copy (delta_copy_plan.h / delta_copy.h), a third block under the same rule
-    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } dc;
-    // ... and that of k_window_copy (window_copy_plan.h / window_copy.h), a fourth block under the same rule
-    struct { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; } wc;
+    // plaintext in the caller's device memory: the row tables of k_span_copy, k_plane_copy, k_delta_copy and k_window_copy (row_copy.hip;
+    // span_copy_plan.h, plane_copy_plan.h, delta_copy_plan.h, window_copy_plan.h).  FOUR tables, not one that takes turns: a call with
+    // entries of several kinds fills several of them before any of their kernels has run (rows_enqueue).
+    RowTable sc, pc, dc, wc;
     // the spans k_span_hash and the chip-wide pair hash (span_hash_plan.h / span_hash.h): tables | hashes | partial sums on the device,
     // the tables going up and the hashes coming home through a pinned block of its own — a call that hashes spans waits for its stream
     // behind the copy home, so the block is idle whenever the next call writes it
@@ -924,7 +922,7 @@ int zpk_codec_device(const zpk_codec* c) { return c ? c->device : -1; }
 #define ZPK_WD_ARG
 #endif
 
-// ---- memory of the caller's ON THE DEVICE: the pointer rule, the checked copy, k_span_copy's table (span_copy_plan.h, span_copy.h) -------------
+// ---- memory of the caller's ON THE DEVICE: the pointer rule, the checked copy, the row copies' tables (copy_rows_plan.h, row_copy.hip) -----------
 // THE QUERY, the one place that asks HIP about a caller's address: which device it lies on and which allocation [base, base + size) holds it.
 // ZPK_OK: *r says so; ZPK_E_INVALID: NULL, host memory (HIP may never have seen it: its last error is cleared), memory of another device
 // than `only` (that device is not entered; DEV_ANY: every device will do, DEV_NONE: none, the caller wants r->device alone), or no
@@ -1015,138 +1013,87 @@ int zpk_codec_store_device(void* d_dst, const void* host_src, uint64_t bytes) { 
 // the device whose memory `ptr` is, -1 for anything else: the memory's kind alone decides, as a host must not read through such a pointer
 int zpk_codec_pointer_device(const void* ptr) { DevRange r; (void)device_range_of(ptr, &r, DEV_NONE); return r.device; }
 
-// Entries [0, n), entry i the span row(i) (a zpk_span_copy; no bytes: no row), in ONE k_span_copy on `st` (a table past one grid: several,
-// over the same table); returns when the table's upload and the kernel are enqueued.  The rows are written straight into the pinned
-// table: row() is asked twice per entry, once for the count.  The pointers have been checked by the caller, or are the codec's own.
+// The skeleton of the four row copies: the entries [0, n) of which takes(i) says whether entry i takes a row of table `t`, in ONE kernel
+// on `st` (a table past one grid: several, over the same table); returns when the table's upload and the kernel are enqueued.  The rows
+// are written straight into the pinned table by emit(i, rows, p) — false: ZPK_E_INVALID, nothing is uploaded or launched —, so an entry
+// is asked twice, once for the count; launch(d_rows, nrows, L) enqueues one launch.  No rows: nothing is touched.
 extern "C++" {
+template <class Row, class TakesFn, class EmitFn, class LaunchFn>
+static int row_table_enqueue(zpk_codec* c, RowTable& t, const char* what, u64 n, TakesFn takes, EmitFn emit, LaunchFn launch, hipStream_t st)
+{
+    u64 nz = 0;
+    for (u64 i = 0; i < n; i++) nz += takes(i) ? 1 : 0;
+    if (nz == 0) return ZPK_OK;
+    if (nz > ZPK_COPY_MAX_ROWS) return ZPK_E_INVALID;
+    if (t.pending) { HIPCHK(c, hipEventSynchronize(t.ev)); t.pending = false; }                         // the pinned block's last upload has run
+    if (t.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "%s: no event", what); return ZPK_E_LAUNCH; }
+    if (!t.h.grow(nz * sizeof(Row))) { snprintf(c->err, sizeof(c->err), "%s: out of pinned memory", what); return ZPK_E_NOMEM; }
+    int rc;
+    if ((rc = grow(c, t.d, nz * sizeof(Row)))) return rc;
+    Row* const rows = (Row*)t.h.p;
+    CopyPlan p = { 0, 0 };
+    for (u64 i = 0; i < n; i++) if (!emit(i, rows, p)) return ZPK_E_INVALID;
+    HIPCHK(c, hipMemcpyAsync(t.d, rows, p.nrows * sizeof(Row), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(t.ev, st));
+    t.pending = true;
+    const u64 nl = copy_launches(p.items);
+    for (u64 j = 0; j < nl; j++) launch((const Row*)(const u8*)t.d, (u32)p.nrows, copy_launch(p.items, j));
+    HIPCHK(c, hipGetLastError());
+    return ZPK_OK;
+}
+// k_span_copy: entry i the span row(i) (a zpk_span_copy; no bytes: no row).  The pointers have been checked by the caller, or are the
+// codec's own.
 template <class RowFn>
 static int span_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
 {
-    u64 nz = 0;
-    for (u64 i = 0; i < n; i++) nz += row(i).len != 0;
-    if (nz == 0) return ZPK_OK;
-    if (nz > ZPK_SC_MAX_ROWS) return ZPK_E_INVALID;
-    if (c->sc.pending) { HIPCHK(c, hipEventSynchronize(c->sc.ev)); c->sc.pending = false; }             // the pinned block's last upload has run
-    if (c->sc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "span copy: no event"); return ZPK_E_LAUNCH; }
-    if (!c->sc.h.grow(nz * sizeof(SpanCopyRow))) { snprintf(c->err, sizeof(c->err), "span copy: out of pinned memory"); return ZPK_E_NOMEM; }
-    int rc;
-    if ((rc = grow(c, c->sc.d, nz * sizeof(SpanCopyRow)))) return rc;
-    SpanCopyRow* const rows = (SpanCopyRow*)c->sc.h.p;
-    SpanCopyPlan p = { 0, 0 };
-    for (u64 i = 0; i < n; i++) { const zpk_span_copy s = row(i); (void)span_copy_emit(s.src, s.dst, s.len, rows, p); }
-    HIPCHK(c, hipMemcpyAsync(c->sc.d, rows, p.nrows * sizeof(SpanCopyRow), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->sc.ev, st));
-    c->sc.pending = true;
-    const u64 nl = span_copy_launches(p.items);
-    for (u64 j = 0; j < nl; j++) {
-        const SpanCopyLaunch L = span_copy_launch(p.items, j);
-        span_copy_launch((const SpanCopyRow*)(const u8*)c->sc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
-        c->last.sc++;
-    }
-    HIPCHK(c, hipGetLastError());
-    return ZPK_OK;
+    return row_table_enqueue<SpanCopyRow>(c, c->sc, "span copy", n, [&](u64 i) { return row(i).len != 0; },
+        [&](u64 i, SpanCopyRow* rows, CopyPlan& p) { const zpk_span_copy s = row(i); return span_copy_emit(s.src, s.dst, s.len, rows, p); },
+        [&](const SpanCopyRow* d, u32 nrows, const CopyLaunch& L) { span_copy_launch(d, nrows, L.item0, L.items, L.grid, st); c->last.sc++; }, st);
 }
-// The same for k_plane_copy: entry i the row row(i) (a zpk_plane_copy; no bytes: no row), through the codec's second pinned table.  The
-// element sizes have been checked by the caller (planes_check).
+// k_plane_copy: entry i the row row(i) (a zpk_plane_copy; no bytes: no row).  The element sizes have been checked by the caller
+// (planes_check).
 template <class RowFn>
 static int plane_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
 {
-    u64 nz = 0;
-    for (u64 i = 0; i < n; i++) nz += row(i).len != 0;
-    if (nz == 0) return ZPK_OK;
-    if (nz > ZPK_PC_MAX_ROWS) return ZPK_E_INVALID;
-    if (c->pc.pending) { HIPCHK(c, hipEventSynchronize(c->pc.ev)); c->pc.pending = false; }             // the pinned block's last upload has run
-    if (c->pc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "plane copy: no event"); return ZPK_E_LAUNCH; }
-    if (!c->pc.h.grow(nz * sizeof(PlaneCopyRow))) { snprintf(c->err, sizeof(c->err), "plane copy: out of pinned memory"); return ZPK_E_NOMEM; }
-    int rc;
-    if ((rc = grow(c, c->pc.d, nz * sizeof(PlaneCopyRow)))) return rc;
-    PlaneCopyRow* const rows = (PlaneCopyRow*)c->pc.h.p;
-    PlaneCopyPlan p = { 0, 0 };
-    for (u64 i = 0; i < n; i++) {
-        const zpk_plane_copy s = row(i);
-        if (!plane_copy_emit(s.src, s.dst, s.len, s.elem, s.join, rows, p)) return ZPK_E_INVALID;
-        if (s.len) c->last.planes[s.join ? 1 : 0]++;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->pc.d, rows, p.nrows * sizeof(PlaneCopyRow), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->pc.ev, st));
-    c->pc.pending = true;
-    const u64 nl = plane_copy_launches(p.items);
-    for (u64 j = 0; j < nl; j++) {
-        const PlaneCopyLaunch L = plane_copy_launch(p.items, j);
-        plane_copy_launch((const PlaneCopyRow*)(const u8*)c->pc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
-        c->last.planes[2]++;
-    }
-    HIPCHK(c, hipGetLastError());
-    return ZPK_OK;
+    return row_table_enqueue<PlaneCopyRow>(c, c->pc, "plane copy", n, [&](u64 i) { return row(i).len != 0; },
+        [&](u64 i, PlaneCopyRow* rows, CopyPlan& p) {
+            const zpk_plane_copy s = row(i);
+            if (!plane_copy_emit(s.src, s.dst, s.len, s.elem, s.join, rows, p)) return false;
+            if (s.len) c->last.planes[s.join ? 1 : 0]++;
+            return true;
+        },
+        [&](const PlaneCopyRow* d, u32 nrows, const CopyLaunch& L) { plane_copy_launch(d, nrows, L.item0, L.items, L.grid, st); c->last.planes[2]++; }, st);
 }
-// The same for k_delta_copy: entry i the row row(i) (a zpk_delta_copy; no bytes: no row), through the codec's third pinned table.  Element
-// sizes, bases and their overlap with the destinations have been checked by the caller.
+// k_delta_copy: entry i the row row(i) (a zpk_delta_copy; no bytes: no row).  Element sizes, bases and their overlap with the
+// destinations have been checked by the caller.
 template <class RowFn>
 static int delta_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
 {
-    u64 nz = 0;
-    for (u64 i = 0; i < n; i++) nz += row(i).len != 0;
-    if (nz == 0) return ZPK_OK;
-    if (nz > ZPK_PC_MAX_ROWS) return ZPK_E_INVALID;
-    if (c->dc.pending) { HIPCHK(c, hipEventSynchronize(c->dc.ev)); c->dc.pending = false; }             // the pinned block's last upload has run
-    if (c->dc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "delta copy: no event"); return ZPK_E_LAUNCH; }
-    if (!c->dc.h.grow(nz * sizeof(DeltaCopyRow))) { snprintf(c->err, sizeof(c->err), "delta copy: out of pinned memory"); return ZPK_E_NOMEM; }
-    int rc;
-    if ((rc = grow(c, c->dc.d, nz * sizeof(DeltaCopyRow)))) return rc;
-    DeltaCopyRow* const rows = (DeltaCopyRow*)c->dc.h.p;
-    PlaneCopyPlan p = { 0, 0 };
-    for (u64 i = 0; i < n; i++) {
-        const zpk_delta_copy s = row(i);
-        if (!delta_copy_emit(s.src, s.dst, s.base, s.len, s.elem, s.join, rows, p)) return ZPK_E_INVALID;
-        if (s.len) c->last.delta[s.join ? 1 : 0]++;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->dc.d, rows, p.nrows * sizeof(DeltaCopyRow), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->dc.ev, st));
-    c->dc.pending = true;
-    const u64 nl = plane_copy_launches(p.items);
-    for (u64 j = 0; j < nl; j++) {
-        const PlaneCopyLaunch L = plane_copy_launch(p.items, j);
-        delta_copy_launch((const DeltaCopyRow*)(const u8*)c->dc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
-        c->last.delta[2]++;
-    }
-    HIPCHK(c, hipGetLastError());
-    return ZPK_OK;
+    return row_table_enqueue<DeltaCopyRow>(c, c->dc, "delta copy", n, [&](u64 i) { return row(i).len != 0; },
+        [&](u64 i, DeltaCopyRow* rows, CopyPlan& p) {
+            const zpk_delta_copy s = row(i);
+            if (!delta_copy_emit(s.src, s.dst, s.base, s.len, s.elem, s.join, rows, p)) return false;
+            if (s.len) c->last.delta[s.join ? 1 : 0]++;
+            return true;
+        },
+        [&](const DeltaCopyRow* d, u32 nrows, const CopyLaunch& L) { delta_copy_launch(d, nrows, L.item0, L.items, L.grid, st); c->last.delta[2]++; }, st);
 }
-// The same for k_window_copy: entry i the row row(i) (a zpk_window_copy; an entry or a window of no bytes: no row), through the codec's
-// fourth pinned table.  Element sizes, windows (window_valid), bases and their overlap with the destinations have been checked by the
-// caller; a window that fails the rule all the same: ZPK_E_INVALID and nothing is launched.
+// k_window_copy: entry i the row row(i) (a zpk_window_copy; an entry or a window of no bytes: no row).  Element sizes, windows
+// (window_valid), bases and their overlap with the destinations have been checked by the caller; a window that fails the rule all the
+// same: ZPK_E_INVALID and nothing is launched.
 template <class RowFn>
 static int window_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
 {
     auto bytes = [](const zpk_window_copy& s) { return s.n ? s.win.rows * s.win.cols : 0ull; };
-    u64 nz = 0;
-    for (u64 i = 0; i < n; i++) nz += bytes(row(i)) != 0;
-    if (nz == 0) return ZPK_OK;
-    if (nz > ZPK_PC_MAX_ROWS) return ZPK_E_INVALID;
-    if (c->wc.pending) { HIPCHK(c, hipEventSynchronize(c->wc.ev)); c->wc.pending = false; }             // the pinned block's last upload has run
-    if (c->wc.ev.ready(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, sizeof(c->err), "window copy: no event"); return ZPK_E_LAUNCH; }
-    if (!c->wc.h.grow(nz * sizeof(WindowCopyRow))) { snprintf(c->err, sizeof(c->err), "window copy: out of pinned memory"); return ZPK_E_NOMEM; }
-    int rc;
-    if ((rc = grow(c, c->wc.d, nz * sizeof(WindowCopyRow)))) return rc;
-    WindowCopyRow* const rows = (WindowCopyRow*)c->wc.h.p;
-    PlaneCopyPlan p = { 0, 0 };
-    for (u64 i = 0; i < n; i++) {
-        const zpk_window_copy s = row(i);
-        if (!bytes(s)) continue;
-        if (!window_copy_emit(s.src, s.dst, s.base, s.n, Window{ s.win.row_bytes, s.win.row0, s.win.rows, s.win.col0, s.win.cols }, s.elem, rows, p)) return ZPK_E_INVALID;
-        c->last.window[0]++;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->wc.d, rows, p.nrows * sizeof(WindowCopyRow), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->wc.ev, st));
-    c->wc.pending = true;
-    const u64 nl = plane_copy_launches(p.items);
-    for (u64 j = 0; j < nl; j++) {
-        const PlaneCopyLaunch L = plane_copy_launch(p.items, j);
-        window_copy_launch((const WindowCopyRow*)(const u8*)c->wc.d, (u32)p.nrows, L.item0, L.items, L.grid, st);
-        c->last.window[1]++;
-    }
-    HIPCHK(c, hipGetLastError());
-    return ZPK_OK;
+    return row_table_enqueue<WindowCopyRow>(c, c->wc, "window copy", n, [&](u64 i) { return bytes(row(i)) != 0; },
+        [&](u64 i, WindowCopyRow* rows, CopyPlan& p) {
+            const zpk_window_copy s = row(i);
+            if (!bytes(s)) return true;
+            if (!window_copy_emit(s.src, s.dst, s.base, s.n, Window{ s.win.row_bytes, s.win.row0, s.win.rows, s.win.col0, s.win.cols }, s.elem, rows, p)) return false;
+            c->last.window[0]++;
+            return true;
+        },
+        [&](const WindowCopyRow* d, u32 nrows, const CopyLaunch& L) { window_copy_launch(d, nrows, L.item0, L.items, L.grid, st); c->last.window[1]++; }, st);
 }
 // The spans row(i) of a batch with element sizes, bases and windows `pl`, all of one direction (join: PLANE_SPLIT / PLANE_JOIN), split
 // FOUR ways: those with a window in ONE k_window_copy, whatever their element size or base (row(i).len is the entry's plain size there,
@@ -1169,10 +1116,16 @@ static int rows_enqueue(zpk_codec* c, u64 n, RowFn row, const Planes& pl, u32 jo
     }, st);
 }
 }  // extern "C++"
+// false, with the message: `elem` is no element size (plane_elem_valid) — of entry i of a batch, or row i of a table (`noun`)
+static bool elem_size_ok(zpk_codec* c, const char* noun, u64 i, u32 elem)
+{
+    if (plane_elem_valid(elem)) return true;
+    snprintf(c->err, sizeof(c->err), "%s %llu: an element size of %u (1, 2, 4 or 8)", noun, (unsigned long long)i, (unsigned)elem);
+    return false;
+}
 static int planes_check(zpk_codec* c, const u8* elem, u64 n)
 {
-    for (u64 i = 0; elem && i < n; i++)
-        if (!plane_elem_valid(elem[i])) { snprintf(c->err, sizeof(c->err), "entry %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)elem[i]); return ZPK_E_INVALID; }
+    for (u64 i = 0; elem && i < n; i++) if (!elem_size_ok(c, "entry", i, elem[i])) return ZPK_E_INVALID;
     return ZPK_OK;
 }
 // ZPK_E_INVALID, before anything is enqueued: a base (those that are not NULL) that fails the pointer rule over len(i) bytes, or — where
@@ -2509,8 +2462,7 @@ int zpk_codec_plane_copy_device(zpk_codec* c, const zpk_plane_copy* rows, uint64
     c->last.no_planes();
     if (n == 0) return ZPK_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    for (u64 i = 0; i < n; i++)
-        if (!plane_elem_valid(rows[i].elem)) { snprintf(c->err, sizeof(c->err), "row %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
+    for (u64 i = 0; i < n; i++) if (!elem_size_ok(c, "row", i, rows[i].elem)) return ZPK_E_INVALID;
     PtrRule rule(c);
     auto len = [&](u64 i) { return (u64)rows[i].len; };
     if (rule.batch("plane source", n, [&](u64 i) { return (const void*)rows[i].src; }, len) ||
@@ -2528,7 +2480,7 @@ int zpk_codec_delta_copy_device(zpk_codec* c, const zpk_delta_copy* rows, uint64
     if (n == 0) return ZPK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     for (u64 i = 0; i < n; i++) {
-        if (!plane_elem_valid(rows[i].elem)) { snprintf(c->err, sizeof(c->err), "row %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
+        if (!elem_size_ok(c, "row", i, rows[i].elem)) return ZPK_E_INVALID;
         if (rows[i].len && !rows[i].base) { snprintf(c->err, sizeof(c->err), "row %llu has no base: a row of zpk_codec_plane_copy_device", (unsigned long long)i); return ZPK_E_INVALID; }
     }
     PtrRule rule(c);
@@ -2566,7 +2518,7 @@ int zpk_codec_window_copy_device(zpk_codec* c, const zpk_window_copy* rows, uint
     HIPCHK(c, hipSetDevice(c->device));
     auto win = [&](u64 i) { const zpk_window& w = rows[i].win; return Window{ w.row_bytes, w.row0, w.rows, w.col0, w.cols }; };
     for (u64 i = 0; i < n; i++) {
-        if (!plane_elem_valid(rows[i].elem)) { snprintf(c->err, sizeof(c->err), "row %llu: an element size of %u (1, 2, 4 or 8)", (unsigned long long)i, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
+        if (!elem_size_ok(c, "row", i, rows[i].elem)) return ZPK_E_INVALID;
         if (!window_valid(rows[i].n, rows[i].elem, win(i))) { snprintf(c->err, sizeof(c->err), "row %llu: its window does not lie in %llu bytes of %u-byte elements", (unsigned long long)i, (unsigned long long)rows[i].n, (unsigned)rows[i].elem); return ZPK_E_INVALID; }
     }
     PtrRule rule(c);
