@@ -222,7 +222,9 @@ int  zpk_codec_decode_big_batch_device(zpk_codec* c, const uint8_t* d_archive, u
 
 /* Host form: host pointers, synchronous.  Stages [min src_offset, max src_offset+comp_size) of
  * `archive` to the device, decodes, and copies each slot back to dst_ptrs[i] (desc[i].dst_offset is
- * ignored; desc[i].dst_capacity is the size of dst_ptrs[i]).  zpack_read_file is a batch of one. */
+ * ignored; desc[i].dst_capacity is the size of dst_ptrs[i]).  zpack_read_file is a batch of one.
+ * A compressed entry whose dst_capacity lies within 255 bytes of 2^64 has a staging slot no device holds: the call returns
+ * ZPK_E_NOMEM ("a staging slot of ... bytes") before anything is enqueued for it; the sub-batches in front of it have run. */
 int zpk_codec_decode_batch_host(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
                                 const zpk_decode_desc* desc, uint64_t n,
                                 uint8_t* const* dst_ptrs, zpk_decode_result* results);

@@ -389,6 +389,44 @@ def test_sub_batches_by_the_chunk_option_on_both_calls(codec, torch, synth):
         codec.set_option(zpack_amd.OPT_DEC_SPLIT_MIN, 256 << 10)
 
 
+def _cut_model(slots, chunk):
+    """the sub-batches of staging slots at `chunk`: a sub-batch closes when the next slot would take it past the chunk, its first
+    entry always joins (host_plan.h / dimage_plan.h state this; the count here comes from this loop alone)"""
+    subs, total, count = [], 0, 0
+    for s in slots:
+        if count and (total > chunk or s > chunk - total):
+            subs.append((count, total))
+            total = count = 0
+        total, count = total + s, count + 1
+    return subs + ([(count, total)] if count else [])
+
+
+def test_both_calls_cut_the_same_sub_batches_and_an_entry_above_the_chunk_goes_alone(codec, torch):
+    """12 entries of 4 KiB to 96 KiB, stored, LZ4 and Zstandard in turn, at a chunk of 64 KiB: the slot of the 96 KiB LZ4 entry exceeds it"""
+    sizes = [4 << 10, 96 << 10, 8 << 10, 20000, 40 << 10, 4097, 64 << 10, 12 << 10, 33333, 16 << 10, 50 << 10, 24 << 10]
+    specs = [METHODS[i % 3] + (_plain(i, n),) for i, n in enumerate(sizes)]
+    arc = _build(specs)
+    desc = _desc_of(arc)
+    image = _image(torch, arc, 6)[6:6 + len(arc)]
+    chunk = 64 << 10
+    slots = [0 if m == dg.NONE else (n + 255) & ~255 for (m, _, _), n in zip(specs, sizes)]      # (no destination: a stored entry has no slot)
+    want = _cut_model(slots, chunk)
+    assert (1, (96 << 10)) in want and len(want) > 2, want
+    read, _ = codec.decode_batch_host(arc, desc)
+    assert (read["status"] == 0).all() and [int(h) for h in read["hash"]] == [oracle().xxh3(s[2]) for s in specs]
+    codec.set_option(zpack_amd.OPT_DIMAGE_CHUNK, chunk)
+    try:
+        subs = {}
+        for name, call, src in (("host", codec.verify_batch_host, arc), ("dimage", codec.verify_batch_dimage, image)):
+            res = call(src, desc)
+            subs[name] = codec.verify_stats()["sub_batches"]
+            assert res.tobytes() == read.tobytes(), name
+        print("sub-batches: %s, the model: %s" % (subs, want))
+        assert subs["host"] == subs["dimage"] == len(want)
+    finally:
+        codec.set_option(zpack_amd.OPT_DIMAGE_CHUNK, 0)
+
+
 # ------------------------------------------------------------------------------------------------ 7. the pipelined upload is kept
 
 def test_a_large_host_batch_keeps_its_pipelined_upload(codec):

@@ -61,6 +61,7 @@ namespace zpk { u32 span_hash_launch(u8* d_block, const SpanHashPlan& p, const S
 // ... and so is k_stored_hash (stored_hash.h, stored_hash.hip): k_stored without the copy, for a batch that has no destination
 namespace zpk { void stored_hash_launch(const u8* src, const zpk_decode_desc* desc, zpk_decode_result* res, const u32* list, const u32* counters, u32 grid, hipStream_t st); }
 #include "dimage_plan.h"                         // a batch out of an archive image in DEVICE memory: its sub-batches and their staging slots (plain C++, likewise)
+#include "host_plan.h"                           // the host-pointer read path: slot and sub-batch, staged image, pipeline pieces, copy shares, frame-parallel groups, delivery rules (plain C++, likewise)
 #include "dsink_plan.h"                          // a batch compressed into a bounded sink in DEVICE memory: the cut, the span table, room and chaining, the staging (plain C++, likewise); the kernels: sink_commit.hip
 #include "stream_plan.h"                        // the bounded steps of the stream reader: intake, go rule, hash sections, history carry, layouts, verdict (plain C++, likewise)
 #include "codec_res.h"                           // what a codec or a stream context holds, each owned by its member: DevBuf, PinBuf / PinBlock, Event, Stream (plain C++ over the HIP runtime, likewise)
@@ -673,12 +674,7 @@ static inline u64 planes_join_len(const zpk_decode_desc& d, const zpk_decode_res
 // (base_verdicts_mark, once the call's results are final); every other status stays the entry's own.  The verdicts are complete before
 // the call's first row reaches rows_enqueue (base_verdicts runs in front of the routing), so all four delivery sites see them.
 inline u64 Planes::join_len(u64 i, const zpk_decode_desc& d, const zpk_decode_result& r) const { return refused_at(i) ? 0ull : planes_join_len(d, r); }
-// the staging slot of an entry under destination `to` (span_copy_plan.h states the layout for the two kinds that have one)
-static inline u64 staging_slot(Dst to, const zpk_decode_desc& d)
-{
-    const bool stored = d.method == ZPK_METHOD_NONE;
-    return to == Dst::None ? (stored ? 0ull : span_copy_read_slot(false, d.uncomp_size, d.uncomp_size)) : span_copy_read_slot(stored, d.uncomp_size, d.dst_capacity);
-}
+// (the staging slot of an entry under either kind of destination, and under none: read_slot, host_plan.h)
 
 // The words the stats calls report of the most recent call.  begin_decode_call zeroes the decode words; dimage, dsink and enc_big are
 // zeroed by the one call that counts them; totals_valid by every launch, fell_back_fused by the launch that decides it.
@@ -1481,8 +1477,7 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
 {
     for (u64 i = 0; i < n; i++) {
         zpk_decode_result& r = results[i];
-        if ((r.status != 0 && r.status != 15) || r.produced >= desc[i].uncomp_size || desc[i].uncomp_size > desc[i].dst_capacity ||
-            desc[i].comp_size == 0 /* :328: OK before anything is read */ || desc[i].method == ZPK_METHOD_NONE) continue;
+        if (!host_short_decode(desc[i], r)) continue;
         int rc;
         if ((rc = grow(c, c->d_xpart, 64))) return rc;
         const u64 tail = desc[i].uncomp_size - r.produced;
@@ -1496,7 +1491,7 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
         HIPCHK(c, hipMemcpyAsync(&h, m + 2, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         r.hash = h;
-        r.status = (h == desc[i].expect_hash || (desc[i].flags & ZPK_DF_SKIP_HASH)) ? 0 : 15;
+        r.status = dec_hash_verdict(desc[i], h).status;
     }
     return ZPK_OK;
 }
@@ -1504,16 +1499,10 @@ static int rehash_short_entries(zpk_codec* c, const zpk_decode_desc* hd, const z
 // One sub-batch of the host path: entries [0, n) of hd/desc, whose slots (hd[i].dst_offset, already laid out) total
 // out_total bytes.  `image` is what gets staged: either the archive itself (span mode, src_offset = archive offsets,
 // staged range [lo, hi)) or a packed copy of just these payloads (gather mode: hd[i].src_offset already rewritten).
-#ifndef ZPK_PIN_CHUNK
-#define ZPK_PIN_CHUNK (32ull << 20)
-#endif
 // The pinned staging buffers are touched by copy engines and host threads only, never by kernels: non-coherent host memory
 // (measured, tools/micro/pinned_copy.hip: H2D 47.8 vs 40.5 GB/s, D2H 55.9 vs 47.4 GB/s against the default, coherent kind)
 #ifndef ZPK_PIN_FLAGS
 #define ZPK_PIN_FLAGS hipHostMallocNonCoherent
-#endif
-#ifndef ZPK_SCATTER_THREADS
-#define ZPK_SCATTER_THREADS 4u
 #endif
 static int pin_ready(zpk_codec* c)
 {
@@ -1528,31 +1517,15 @@ static int pin_ready(zpk_codec* c)
 
 // One piece [p0, p1) of a staged range, moved between its pinned buffer and the buffers of those of the n entries that reach into it (entry
 // i owns bytes [off(i), off(i) + len(i)) of the range, ascending in i; ei: the first that may, kept from piece to piece) by a few host
-// threads: one thread copies at ~22 GB/s, the bus brings ~50.
-// move(i, in_entry, in_piece, bytes) copies `bytes` bytes, at in_entry of entry i and at in_piece of the piece, whichever way the caller goes.
-// Eight entries or more are dealt out by count; of a few large entries the piece's BYTES are cut among the threads (one entry of 256 MiB
-// came home at one thread's rate).  A piece below 4 MiB is one thread's.
+// threads.  Which entries reach into the piece, how many threads it gets and what each of them moves: host_plan.h (staged_reach,
+// staged_threads, staged_share); move(i, in_entry, in_piece, bytes) copies, whichever way the caller goes.
 extern "C++" {
 template <class OffFn, class LenFn, class MoveFn>
 static void staged_piece_copy(u64 p0, u64 p1, u64 n, u64& ei, OffFn off, LenFn len, MoveFn move)
 {
-    while (ei < n && off(ei) + len(ei) <= p0) ei++;
-    u64 ej = ei;
-    while (ej < n && off(ej) < p1) ej++;
-    const u64 cnt = ej - ei, span = p1 - p0;
-    const unsigned T = span >= (4u << 20) ? ZPK_SCATTER_THREADS : 1u;
-    auto cut = [&](unsigned t) { return t >= T ? p1 : p0 + ((span * t / T) & ~(u64)4095); };
-    // share t of T: entries [lo_i, hi_i), of each what lies in bytes [lo_b, hi_b)
-    auto share = [&](unsigned t) {
-        const bool by_bytes = cnt < 8;
-        const u64 lo_i = by_bytes ? ei : ei + cnt * t / T, hi_i = by_bytes ? ej : ei + cnt * (t + 1) / T;
-        const u64 lo_b = by_bytes ? cut(t) : p0, hi_b = by_bytes ? cut(t + 1) : p1;
-        for (u64 i = lo_i; i < hi_i; i++) {
-            const u64 o = off(i), l = len(i);
-            const u64 a = o > lo_b ? o : lo_b, z = o + l < hi_b ? o + l : hi_b;
-            if (z > a) move(i, a - o, a - p0, z - a);
-        }
-    };
+    const u64 ej = staged_reach(p0, p1, n, ei, off, len);
+    const unsigned T = staged_threads(p0, p1);
+    auto share = [&](unsigned t) { staged_share_move(staged_share(p0, p1, ei, ej, t, T), p0, off, len, move); };
     // (a thread that cannot be started must not unwind through the C ABI: its share is copied inline instead)
     std::thread th[ZPK_SCATTER_THREADS - 1];
     bool started[ZPK_SCATTER_THREADS - 1] = {};
@@ -1576,24 +1549,22 @@ static int d2h_scatter(zpk_codec* c, const u8* d_base, u64 total, u64 n, uint8_t
     if (rc) return rc;
     if (total == 0) return ZPK_OK;
     if (!st) st = c->stream;
-    const u64 npieces = (total + ZPK_PIN_CHUNK - 1) / ZPK_PIN_CHUNK;
+    const u64 npieces = staged_pieces(total);
     u64 ei = 0;                                                                       // first entry that may still reach into the current piece
-    e = pre(total < ZPK_PIN_CHUNK ? total : ZPK_PIN_CHUNK);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->pipe.h_pin[0], d_base, total < ZPK_PIN_CHUNK ? total : ZPK_PIN_CHUNK, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipEventRecord(c->pipe.pin_ev[0], st);
+    auto fetch = [&](u64 j) {                                                         // piece j sets out for its buffer
+        const StagedPiece q = staged_piece(j, total);
+        e = pre(q.p1);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->pipe.h_pin[j & 1], d_base + q.p0, q.p1 - q.p0, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipEventRecord(c->pipe.pin_ev[j & 1], st);
+    };
+    fetch(0);
     for (u64 j = 0; j < npieces && e == hipSuccess; j++) {
         const int k = (int)(j & 1);
-        const u64 p0 = j * ZPK_PIN_CHUNK, p1 = p0 + ZPK_PIN_CHUNK < total ? p0 + ZPK_PIN_CHUNK : total;
-        if (j + 1 < npieces) {
-            const u64 q0 = p1, q1 = q0 + ZPK_PIN_CHUNK < total ? q0 + ZPK_PIN_CHUNK : total;
-            e = pre(q1);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->pipe.h_pin[k ^ 1], d_base + q0, q1 - q0, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipEventRecord(c->pipe.pin_ev[k ^ 1], st);
-            if (e != hipSuccess) break;
-        }
+        const StagedPiece p = staged_piece(j, total);
+        if (j + 1 < npieces) { fetch(j + 1); if (e != hipSuccess) break; }
         e = hipEventSynchronize(c->pipe.pin_ev[k]);
         if (e != hipSuccess) break;
-        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(dst_ptrs[i] + in_entry, c->pipe.h_pin[k] + in_piece, bytes); });
+        staged_piece_copy(p.p0, p.p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(dst_ptrs[i] + in_entry, c->pipe.h_pin[k] + in_piece, bytes); });
     }
     return ZPK_OK;
 }
@@ -1611,15 +1582,15 @@ static int h2d_gather(zpk_codec* c, u8* d_base, u64 total, u64 n, const uint8_t*
     Event* const evs = c->pipe.pin_ev;
     e = hipSuccess;
     if (total == 0) return ZPK_OK;
-    const u64 npieces = (total + ZPK_PIN_CHUNK - 1) / ZPK_PIN_CHUNK;
+    const u64 npieces = staged_pieces(total);
     u64 ei = 0;
     bool used[2] = { false, false };
     for (u64 j = 0; j < npieces && e == hipSuccess; j++) {
         const int k = (int)(j & 1);
-        const u64 p0 = j * ZPK_PIN_CHUNK, p1 = p0 + ZPK_PIN_CHUNK < total ? p0 + ZPK_PIN_CHUNK : total;
+        const StagedPiece p = staged_piece(j, total);
         if (used[k]) { e = hipEventSynchronize(evs[k]); if (e != hipSuccess) break; }      // the buffer's previous piece has left
-        staged_piece_copy(p0, p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(pin[k] + in_piece, src_ptrs[i] + in_entry, bytes); });
-        e = hipMemcpyAsync(d_base + p0, pin[k], p1 - p0, hipMemcpyHostToDevice, st);
+        staged_piece_copy(p.p0, p.p1, n, ei, off, len, [&](u64 i, u64 in_entry, u64 in_piece, u64 bytes) { memcpy(pin[k] + in_piece, src_ptrs[i] + in_entry, bytes); });
+        e = hipMemcpyAsync(d_base + p.p0, pin[k], p.p1 - p.p0, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipEventRecord(evs[k], st);
         used[k] = true;
     }
@@ -1643,10 +1614,7 @@ static int stage_sources(zpk_codec* c, const uint8_t* const* src_ptrs, bool dsrc
 }
 }  // extern "C++"
 
-// the staged image is followed by ZPK_SRC_SLACK bytes of the codec's own: the kernels may READ ZPK_SRC_READ_SLACK bytes past its
-// logical end (wide loads next to an entry's last byte; the two-stage LZ4 parser fetches whole 64-byte groups) — never interpret them
-#define ZPK_SRC_SLACK 192u
-#define ZPK_SRC_READ_SLACK 128u
+// (the staged image is followed by ZPK_SRC_SLACK bytes of the codec's own, of which the kernels may read ZPK_SRC_READ_SLACK: host_plan.h)
 static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs,
                          zpk_decode_result* results, Dst to, u64* home = nullptr, const Planes& pl = Planes());
 static int decode_host_chunk(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
@@ -1684,7 +1652,7 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
     u64 produced_total = 0;
     if (home) *home = 0;
     for (u64 i = 0; i < n; i++) {
-        if (results[i].produced > desc[i].dst_capacity) results[i].produced = desc[i].dst_capacity;     // (cannot happen)
+        results[i].produced = host_delivered(desc[i], results[i]);
         produced_total += results[i].produced;
     }
     if (to == Dst::None) return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to);
@@ -1694,19 +1662,19 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
         auto row = [&](u64 i) { return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? pl.join_len(i, desc[i], results[i]) : (u64)results[i].produced }; };
         if ((rc = rows_enqueue(c, n, row, pl, PLANE_JOIN, c->stream))) return rc;
         e = hipStreamSynchronize(c->stream);
-    } else if (n > 1 && produced_total && produced_total * 2 >= out_total) {
+    } else if (host_deliver_dense(n, produced_total, out_total)) {
         // dense: the slots come back in pieces of ZPK_PIN_CHUNK bytes through two PINNED staging buffers — piece j + 1 is on the bus
         // while piece j is scattered into the caller's (pageable) buffers.  (One hipMemcpy of everything into a fresh malloc, then
         // the scatter, ran at 6.7 GB/s: page faults + the driver's own staging of pageable memory.)
         rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; }, [&](u64 i) { return (u64)results[i].produced; }, e);
         if (rc) return rc;
         if (home) *home = out_total;
-        c->last.home = out_total > ~0ull - c->last.home ? ~0ull : c->last.home + out_total;
+        sat_add(c->last.home, out_total);
     } else {
         for (u64 i = 0; i < n && e == hipSuccess; i++)
             if (results[i].produced) e = hipMemcpy(dst_ptrs[i], c->d_dst + hd[i].dst_offset, results[i].produced, hipMemcpyDeviceToHost);
         if (home) *home = produced_total;
-        c->last.home = produced_total > ~0ull - c->last.home ? ~0ull : c->last.home + produced_total;
+        sat_add(c->last.home, produced_total);
     }
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "D2H: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     return rehash_short_entries(c, hd, desc, n, dst_ptrs, results, to, pl);
@@ -1715,17 +1683,19 @@ static int deliver_slots(zpk_codec* c, const zpk_decode_desc* hd, const zpk_deco
 // ---- the same chunk as a three-stage pipeline (round 3) ------------------------------------------------------------------------
 // decode_host_chunk runs upload -> decode -> download one after the other: 0.71 GB up, 2 ms of kernels and 1.31 GB down took 40 ms
 // for 20 000 x 64 KiB LZ4 entries, i.e. 30 GiB/s of decoded bytes where the bus alone allows ~47 (PCIe is full duplex).  Here the
-// chunk is cut into pieces (at least ZPK_PIPE_PIECE output bytes and enough entries to fill the device: one wave per LZ4 entry,
-// 48 Zstandard streams per CU): an UPLOADER thread sends the compressed span of piece after piece (pageable memory, its own
+// chunk is cut into pieces (host_pieces, host_plan.h): an UPLOADER thread sends the compressed span of piece after piece (pageable memory, its own
 // stream), a LAUNCHER thread starts the decode of piece k as soon as its upload has been enqueued (the codec's stream waits for
 // the upload's event), and this thread brings the output range back as ONE continuous double-buffered stream through the pinned
 // buffers (download stream; before a range is copied that stream is told to wait for the decode of the pieces it covers) and
 // scatters it.  Entries must lie in the archive roughly in batch order (each piece uploads the span of its own entries);
 // anything else, or a chunk too small to be worth it, takes decode_host_chunk.
-#ifndef ZPK_PIPE_PIECE
-#define ZPK_PIPE_PIECE (64ull << 20)
-#endif
-struct HostPiece { u64 e0, e1, clo, chi, olo, ohi; };
+// A stage's progress: pieces ENQUEUED with their event recorded, -1 = the stage failed.  -> once it is past piece k: true; failed: false
+static bool stage_past(const std::atomic<int>& done, int k)
+{
+    int v;
+    while ((v = done.load()) >= 0 && v <= k) std::this_thread::yield();
+    return v >= 0;
+}
 
 static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, u64 lo, u64 hi, zpk_decode_desc* hd,
                                  const zpk_decode_desc* desc, u64 n, u64 out_total, uint8_t* const* dst_ptrs, zpk_decode_result* results,
@@ -1735,32 +1705,9 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     // events — and the verdicts come home in one copy behind the last piece
     const bool ddst = to == Dst::Device, none = to == Dst::None;
     taken = false;
-    const u64 min_entries = holds.zstd ? 12288 : 4096;
-    if (out_total < 3 * ZPK_PIPE_PIECE || n < 3 * min_entries) return ZPK_OK;
-    // ---- pieces ----
-    HostPiece pc[64];
-    int np = 0;
-    u64 span_sum = 0;
-    for (u64 i = 0; i < n; ) {
-        if (np == 64) return ZPK_OK;
-        HostPiece& P = pc[np];
-        P.e0 = i; P.olo = hd[i].dst_offset; P.clo = ~0ull; P.chi = 0;
-        u64 out = 0;
-        while (i < n && (out < ZPK_PIPE_PIECE || i - P.e0 < min_entries || n - i < min_entries / 2)) {
-            const zpk_decode_desc& d = hd[i];
-            const bool ok = d.comp_size && d.src_offset <= image_size && d.comp_size <= image_size - d.src_offset;
-            if (ok) { if (d.src_offset < P.clo) P.clo = d.src_offset; if (d.src_offset + d.comp_size > P.chi) P.chi = d.src_offset + d.comp_size; }
-            const u64 next = i + 1 < n ? hd[i + 1].dst_offset : out_total;
-            out += next - d.dst_offset;
-            i++;
-        }
-        P.e1 = i; P.ohi = i < n ? hd[i].dst_offset : out_total;
-        if (P.clo > P.chi) { P.clo = lo; P.chi = lo; }
-        if (P.clo < lo || P.chi > hi) return ZPK_OK;
-        span_sum += P.chi - P.clo;
-        np++;
-    }
-    if (np < 3 || span_sum > (hi - lo) + (hi - lo) / 4 + (1u << 20)) return ZPK_OK;      // entries not in archive order: the spans would be uploaded many times over
+    HostPiece pc[ZPK_HOST_MAX_PIECES];
+    const int np = host_pieces(hd, n, image_size, lo, hi, out_total, host_pipe_min_entries(holds.zstd != 0), pc);
+    if (np == 0) return ZPK_OK;
     int rc;
     if ((rc = grow(c, c->d_src, hi - lo + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, out_total + 16)) ||
         (rc = grow(c, c->d_desc, n * sizeof(zpk_decode_desc))) ||
@@ -1789,9 +1736,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     auto launcher = [&]() {
         if (hipSetDevice(device) != hipSuccess) { launch_rc.store(ZPK_E_LAUNCH); launched.store(-1); return; }
         for (int k = 0; k < np; k++) {
-            int u;
-            while ((u = uploaded.load()) >= 0 && u <= k) std::this_thread::yield();
-            int lrc = u < 0 ? (int)ZPK_E_LAUNCH : (int)ZPK_OK;
+            int lrc = stage_past(uploaded, k) ? (int)ZPK_OK : (int)ZPK_E_LAUNCH;
             if (lrc == ZPK_OK && hipStreamWaitEvent(c->stream, c->pipe.ev[2 * k], 0) != hipSuccess) lrc = ZPK_E_LAUNCH;
             const HostPiece& P = pc[k];
             if (lrc == ZPK_OK)
@@ -1811,19 +1756,17 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     try { t_launch = std::thread(launcher); } catch (...) { launch_threaded = false; }
     if (!launch_threaded) launcher();
     // ---- download: one continuous stream over the chunk's output range ----
+    // the results of piece k come home on the download stream, once its decode has been enqueued and behind it
+    auto results_home = [&](int k) -> hipError_t {
+        if (!stage_past(launched, k)) return hipErrorUnknown;
+        const HostPiece& P = pc[k];
+        hipError_t pe = hipStreamWaitEvent(c->pipe.s_dn, c->pipe.ev[2 * k + 1], 0);
+        if (pe == hipSuccess) pe = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->pipe.s_dn);
+        return pe;
+    };
     int next = 0;                                // first piece the download stream has not been told to wait for
-    auto pre = [&](u64 q1) -> hipError_t {
-        while (next < np && pc[next].olo < q1) {
-            int l;
-            while ((l = launched.load()) >= 0 && l <= next) std::this_thread::yield();
-            if (l < 0) return hipErrorUnknown;
-            hipError_t pe = hipStreamWaitEvent(c->pipe.s_dn, c->pipe.ev[2 * next + 1], 0);
-            const HostPiece& P = pc[next];
-            if (pe == hipSuccess) pe = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result),
-                                                      hipMemcpyDeviceToHost, c->pipe.s_dn);      // in stream order before the bytes: there when they are scattered
-            if (pe != hipSuccess) return pe;
-            next++;
-        }
+    auto pre = [&](u64 q1) -> hipError_t {       // (the results in stream order before the bytes: there when they are scattered)
+        for (; next < np && pc[next].olo < q1; next++) { const hipError_t pe = results_home(next); if (pe != hipSuccess) return pe; }
         return hipSuccess;
     };
     if (none) {
@@ -1833,23 +1776,18 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
         // verdicts come home and ONE k_span_copy on the download stream moves the piece's slots to their pointers — [slot, slot + produced),
         // the bytes the scatter below copies — while the upload and the decode of the pieces behind it go on.
         for (int k = 0; k < np && rc == ZPK_OK && e == hipSuccess; k++) {
-            int l;
-            while ((l = launched.load()) >= 0 && l <= k) std::this_thread::yield();
-            if (l < 0) { e = hipErrorUnknown; break; }
             const HostPiece& P = pc[k];
-            e = hipStreamWaitEvent(c->pipe.s_dn, c->pipe.ev[2 * k + 1], 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(results + P.e0, (const zpk_decode_result*)c->d_res + P.e0, (P.e1 - P.e0) * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->pipe.s_dn);
+            e = results_home(k);
             if (e == hipSuccess) e = hipStreamSynchronize(c->pipe.s_dn);
             if (e != hipSuccess) break;
             rc = rows_enqueue(c, P.e1 - P.e0, [&](u64 k2) {
-                const u64 i = P.e0 + k2, p = results[i].produced > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : (u64)results[i].produced;
-                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? pl.join_len(i, desc[i], results[i]) : p };
+                const u64 i = P.e0 + k2;
+                return zpk_span_copy{ (u64)(c->d_dst + hd[i].dst_offset), (u64)dst_ptrs[i], pl.grouped(i) ? pl.join_len(i, desc[i], results[i]) : host_delivered(desc[i], results[i]) };
             }, pl.from(P.e0), PLANE_JOIN, c->pipe.s_dn);
         }
     } else
-    rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; },
-                     [&](u64 i) { const u64 p = results[i].produced; return p > desc[i].dst_capacity ? (u64)desc[i].dst_capacity : p; }, e, c->pipe.s_dn, pre);
-    if (!ddst && !none && rc == ZPK_OK) c->last.home = out_total > ~0ull - c->last.home ? ~0ull : c->last.home + out_total;
+    rc = d2h_scatter(c, c->d_dst, out_total, n, dst_ptrs, [&](u64 i) { return (u64)hd[i].dst_offset; }, [&](u64 i) { return host_delivered(desc[i], results[i]); }, e, c->pipe.s_dn, pre);
+    if (!ddst && !none && rc == ZPK_OK) sat_add(c->last.home, out_total);
     if (up_threaded) t_up.join();
     if (launch_threaded) t_launch.join();
     if (none && launch_rc.load() == ZPK_OK) {                                   // every piece is enqueued: the verdicts, behind the last one
@@ -1861,7 +1799,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
     if (launch_rc.load() != ZPK_OK) rc = launch_rc.load();
     else if (rc == ZPK_OK && e != hipSuccess) { snprintf(c->err, sizeof(c->err), "host decode pipeline: %s", hipGetErrorString(e)); rc = ZPK_E_LAUNCH; }
     if (rc != ZPK_OK) { (void)hipStreamSynchronize(c->pipe.s_up); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->pipe.s_dn); }
-    for (u64 i = 0; i < n && rc == ZPK_OK; i++) if (results[i].produced > desc[i].dst_capacity) results[i].produced = desc[i].dst_capacity;     // (cannot happen)
+    for (u64 i = 0; i < n && rc == ZPK_OK; i++) results[i].produced = host_delivered(desc[i], results[i]);
     if (rc == ZPK_OK && hipStreamSynchronize(c->stream) == hipSuccess) {
         memset(c->last.host_totals, 0, sizeof(c->last.host_totals));
         for (int k = 0; k < np; k++) for (int w = 0; w < N_COUNTERS; w++) c->last.host_totals[w] += c->pipe.piece_counters[k][w];
@@ -1872,7 +1810,7 @@ static int decode_host_pipelined(zpk_codec* c, const u8* image, u64 image_size, 
 }
 
 // ---- entries that are SEQUENCES OF FRAMES, decoded frame-parallel (host path): host_walk.h finds the frames (walk_lz4_frames, walk_zstd_frames) ----
-struct BigEntry { u64 idx, first_sub, nsub; };
+// (struct BigEntry, the cut of such entries into groups and the staging of a group: host_plan.h)
 
 // The common second half of the block-parallel readers (lz4_pj.h, zstd_pj.h): the blocks' references exist per chunk through `init`, the
 // block table `hb` (output offsets) is on the host.  Chunks of ZPK_PJ_CHUNK_BLOCKS blocks are resolved one after the other, hashed and
@@ -1974,7 +1912,7 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
     const hipError_t e2 = hipStreamSynchronize(sh), e3 = hipStreamSynchronize(st);
     if (e == hipSuccess) e = e2 != hipSuccess ? e2 : e3;
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "large frame: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    if (dst_ptr) c->last.home = n > ~0ull - c->last.home ? ~0ull : c->last.home + n;
+    if (dst_ptr) sat_add(c->last.home, n);
     if ((u32)c->pj.h_words[1] != 0) return ZPK_OK;                                                      // PJ_ERR: something was irregular after all
     const zpk_decode_result v = dec_hash_verdict(d, c->pj.h_words[0]);
     if (v.status != DEC_R_OK && !accept_mismatch) return ZPK_OK;                                   // (the one-wave decoder gives this entry's verdict)
@@ -2111,34 +2049,16 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
                             const Planes& pl = Planes())
 {
     const u64 ng = g1 - g0;
-    const bool src_only = to == Dst::None && desc[be[g0].idx].method == ZPK_METHOD_NONE;
-    u64 nsub = 0;
-    for (u64 k = g0; k < g1 && !src_only; k++) nsub += be[k].nsub;
     std::vector<u64> coff(ng + 1), ooff(ng + 1);
-    std::vector<zpk_span> spans(ng);
+    std::vector<StoredSpanRow> spans(ng);                                              // (the zpk_span of xxh3_span.h, field for field: stored_span.h asserts it)
     std::vector<u64> h_hash(ng);
-    std::vector<zpk_decode_desc> hd(nsub);
+    std::vector<zpk_decode_desc> hd;
+    const HostGroup G = host_group_layout(desc, be, g0, g1, subs.data(), to == Dst::None, coff.data(), ooff.data(), spans.data(), hd);
+    const bool src_only = G.src_only;
+    const u64 nsub = G.nsub, ct = G.ct, ot = G.ot;
     std::vector<zpk_decode_result> hr(nsub);
     std::vector<const uint8_t*> cptr(ng);
-    u64 ct = 0, ot = 0, part_blocks = 0, j = 0;
-    int has_zstd = 0, has_lz4 = 0;
-    for (u64 k = 0; k < ng; k++) {
-        const BigEntry& E = be[g0 + k];
-        const zpk_decode_desc& d = desc[E.idx];
-        coff[k] = ct; ooff[k] = ot; cptr[k] = archive + d.src_offset;
-        for (u64 f = 0; f < E.nsub && !src_only; f++, j++) {
-            const BigSub& S = subs[E.first_sub + f];
-            zpk_decode_desc& x = hd[j];
-            x.src_offset = ct + S.src_off; x.comp_size = S.comp; x.uncomp_size = S.size; x.expect_hash = 0;
-            x.dst_offset = ot + S.out_off; x.dst_capacity = S.size; x.method = d.method; x.flags = ZPK_DF_SKIP_HASH;
-        }
-        spans[k].off = src_only ? ct : ot; spans[k].len = d.uncomp_size; spans[k].part_base = part_blocks;
-        part_blocks += xxh3_span_blocks(d.uncomp_size);
-        ct += (d.comp_size + 255) & ~255ull; if (!src_only) ot += (d.uncomp_size + 255) & ~255ull;
-        if (d.method == ZPK_METHOD_ZSTD) has_zstd = 1;
-        if (d.method == ZPK_METHOD_LZ4) has_lz4 = 1;
-    }
-    coff[ng] = ct; ooff[ng] = ot;
+    for (u64 k = 0; k < ng; k++) cptr[k] = archive + desc[be[g0 + k].idx].src_offset;
     int rc;
     if ((rc = grow(c, c->d_src, ct + ZPK_SRC_SLACK)) || (rc = grow(c, c->d_dst, ot + 16)) ||
         (rc = grow(c, c->d_desc, nsub * sizeof(zpk_decode_desc))) ||
@@ -2152,15 +2072,14 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     if (e == hipSuccess && nsub) e = hipMemcpyAsync(c->d_desc, hd.data(), nsub * sizeof(zpk_decode_desc), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "H2D: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
     // (image size = the staged bytes + 1: the last frame still passes the `offset + comp_size < file_size` guard of :331)
-    rc = decode_launch(c, BatchMethods{ has_zstd, has_lz4 }, c->d_src, ct + 1, c->d_src, c->d_src + ct + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, nsub,
+    rc = decode_launch(c, BatchMethods{ G.zstd, G.lz4 }, c->d_src, ct + 1, c->d_src, c->d_src + ct + ZPK_SRC_READ_SLACK, (const zpk_decode_desc*)c->d_desc, nsub,
                        c->d_dst, ot, (zpk_decode_result*)c->d_res, c->stream);
     if (rc) return rc;
-    if ((rc = xxh3_spans_launch(c, src_only ? c->d_src : c->d_dst, spans.data(), ng, part_blocks, h_hash.data(), c->stream))) return rc;
+    if ((rc = xxh3_spans_launch(c, src_only ? c->d_src : c->d_dst, (const zpk_span*)spans.data(), ng, G.part_blocks, h_hash.data(), c->stream))) return rc;
     if (nsub) e = hipMemcpyAsync(hr.data(), c->d_res, nsub * sizeof(zpk_decode_result), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "decode: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    j = 0;
-    for (u64 k = 0; k < ng; k++) {
+    for (u64 k = 0, j = 0; k < ng; k++) {
         const BigEntry& E = be[g0 + k];
         const zpk_decode_desc& d = desc[E.idx];
         bool ok = true;
@@ -2188,7 +2107,7 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
     rc = d2h_scatter(c, c->d_dst, ot, ng, optr.data(), [&](u64 k) { return ooff[k]; }, [&](u64 k) { return redo[g0 + k] ? 0ull : (u64)desc[be[g0 + k].idx].uncomp_size; }, e);
     if (rc) return rc;
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "D2H: %s", hipGetErrorString(e)); return ZPK_E_LAUNCH; }
-    c->last.home = ot > ~0ull - c->last.home ? ~0ull : c->last.home + ot;
+    sat_add(c->last.home, ot);
     return ZPK_OK;
 }
 
@@ -2230,55 +2149,40 @@ static int decode_batch_host_plain(zpk_codec* c, const uint8_t* archive, uint64_
     if (n == 0) return ZPK_OK;
     // (no destination: the sub-batches are cut by ZPK_OPT_DIMAGE_CHUNK, as those of a device image are — a caller can force several cheaply)
     const u64 chunk_bytes = to == Dst::None ? dimage_chunk(c->opt.dimage_chunk) : ZPK_HOST_CHUNK_BYTES;
-    zpk_decode_desc* hd = (zpk_decode_desc*)malloc(n * sizeof(zpk_decode_desc));
-    if (!hd) return ZPK_E_NOMEM;
     int rc = ZPK_OK;
     u8* gathered = nullptr; u64 gathered_cap = 0;
-    for (u64 first = 0; first < n && rc == ZPK_OK; ) {
-        // ---- cut a sub-batch by the size of its output slots ----
-        u64 out_total = 0, cnt = 0, lo = ~0ull, hi = 0, comp_sum = 0;
-        int has_zstd = 0, has_lz4 = 0;
-        while (first + cnt < n) {
-            const zpk_decode_desc& d = desc[first + cnt];
-            // stored entries copy exactly uncomp_size bytes (lib/zpack_read.c:366); the decoders may fill all of max_size
-            const u64 slot = staging_slot(to, d);                                             // (span_copy_plan.h states the layout for both kinds of destination; none: a stored entry has no slot)
-            if (cnt && (out_total + slot > chunk_bytes || cnt >= 0x7FFFFFF0ull)) break;
-            hd[first + cnt] = span_copy_staged_desc(d, d.method == ZPK_METHOD_NONE, out_total);
-            out_total += slot;
-            if (dec_has_payload(d) && dec_src_in_image(d, archive_size)) { if (d.src_offset < lo) lo = d.src_offset; if (d.src_offset + d.comp_size > hi) hi = d.src_offset + d.comp_size; comp_sum += d.comp_size; }
-            if (d.method == ZPK_METHOD_ZSTD) has_zstd = 1;
-            if (d.method == ZPK_METHOD_LZ4) has_lz4 = 1;
-            cnt++;
-        }
-        if (lo > hi) { lo = 0; hi = 0; }
-        const BatchMethods holds = { has_zstd, has_lz4 };
-        const u8* image = archive; u64 image_size = archive_size;
-        if (hi - lo > 2 * comp_sum + (1u << 20)) {
-            // sparse picks out of a large archive: stage only the payloads.  Entries that pass the reference's offset guard
-            // (lib/zpack_read.c:331) are packed behind each other, followed by one pad byte so that the guard still passes;
-            // the others get an offset that still fails it — the device evaluates the same guards in the same order.
-            const u64 total = comp_sum + 1;
-            if (total + 1 > gathered_cap) { free(gathered); gathered = (u8*)malloc(total + 1); gathered_cap = gathered ? total + 1 : 0; }
-            if (!gathered) { rc = ZPK_E_NOMEM; break; }
-            u64 pos = 0;
-            for (u64 i = first; i < first + cnt; i++) {
-                const zpk_decode_desc& d = desc[i];
-                if (dec_has_payload(d) && dec_src_passes(d, archive_size)) { memcpy(gathered + pos, archive + d.src_offset, d.comp_size); hd[i].src_offset = pos; pos += d.comp_size; }
-                else hd[i].src_offset = total + 1;
+    try {
+        std::vector<zpk_decode_desc> hd;
+        std::vector<u64> at(n);                                                       // entry i lies at at[i] of ITS sub-batch's staging
+        for (u64 first = 0; first < n && rc == ZPK_OK; ) {
+            // ---- the sub-batch, cut by the size of its output slots (host_plan.h: read_slot; dimage_cut, as a device image's are) ----
+            const DimageCut cut = dimage_cut(first, n, chunk_bytes, [&](u64 i) { return read_slot(to == Dst::None, desc[i]); }, at.data() + first);
+            const u64 cnt = cut.count, out_total = cut.out_total;
+            if (host_staging_refused(out_total)) { snprintf(c->err, sizeof(c->err), "a staging slot of %llu bytes", (unsigned long long)out_total); rc = ZPK_E_NOMEM; break; }
+            hd.resize(cnt);
+            for (u64 k = 0; k < cnt; k++) hd[k] = span_copy_staged_desc(desc[first + k], desc[first + k].method == ZPK_METHOD_NONE, at[first + k]);
+            const HostSub sub = host_sub(desc + first, cnt, archive_size);
+            const u8* image = archive; u64 image_size = archive_size, lo = sub.lo, hi = sub.hi;
+            if (host_image_sparse(sub.lo, sub.hi, sub.comp_sum)) {
+                // sparse picks out of a large archive: stage only the payloads, gathered into an image of their own (host_gather_layout)
+                const HostGather G = host_gather_layout(desc + first, cnt, archive_size, hd.data());
+                if (G.image_size + 1 > gathered_cap) { free(gathered); gathered = (u8*)malloc(G.image_size + 1); gathered_cap = gathered ? G.image_size + 1 : 0; }
+                if (!gathered) { rc = ZPK_E_NOMEM; break; }
+                for (u64 k = 0; k < cnt; k++) if (hd[k].src_offset != G.fail_offset) memcpy(gathered + hd[k].src_offset, archive + desc[first + k].src_offset, desc[first + k].comp_size);
+                gathered[G.pad_at] = 0;
+                image = gathered; image_size = G.image_size; lo = 0; hi = G.pad_at;
             }
-            gathered[pos] = 0;
-            image = gathered; image_size = total; lo = 0; hi = pos;
+            const BatchMethods holds = { sub.zstd, sub.lz4 };
+            bool piped = false;
+            uint8_t* const* const sub_ptrs = dst_ptrs ? dst_ptrs + first : nullptr;
+            c->last.subs++;
+            rc = decode_host_pipelined(c, image, image_size, lo, hi, hd.data(), desc + first, cnt, out_total, sub_ptrs, results + first, piped, holds, to, pl.from(first));
+            if (rc == ZPK_OK && !piped)
+                rc = decode_host_chunk(c, image, image_size, lo, hi, hd.data(), desc + first, cnt, out_total, sub_ptrs, results + first, holds, to, pl.from(first));
+            first += cnt;
         }
-        bool piped = false;
-        uint8_t* const* const sub_ptrs = dst_ptrs ? dst_ptrs + first : nullptr;
-        c->last.subs++;
-        rc = decode_host_pipelined(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, piped, holds, to, pl.from(first));
-        if (rc == ZPK_OK && !piped)
-            rc = decode_host_chunk(c, image, image_size, lo, hi, hd + first, desc + first, cnt, out_total, sub_ptrs, results + first, holds, to, pl.from(first));
-        first += cnt;
-    }
+    } catch (...) { rc = ZPK_E_NOMEM; }
     free(gathered);
-    free(hd);
     return rc;
 }
 
@@ -2351,10 +2255,7 @@ static int decode_batch_host_routed(zpk_codec* c, const uint8_t* archive, uint64
     try {
         std::vector<u8> redo(be.size(), 0), is_big(n, 0);
         for (u64 g0 = 0; g0 < be.size() && rc == ZPK_OK; ) {                          // groups by the size of their output
-            u64 g1 = g0, out = 0;
-            // (no destination: stored entries and compressed ones in groups of their own — the stored ones are hashed in the staged source)
-            auto same_kind = [&](u64 g) { return to != Dst::None || (desc[be[g].idx].method == ZPK_METHOD_NONE) == (desc[be[g0].idx].method == ZPK_METHOD_NONE); };
-            while (g1 < be.size() && (g1 == g0 || (same_kind(g1) && out + desc[be[g1].idx].uncomp_size <= ZPK_HOST_CHUNK_BYTES))) { out += (desc[be[g1].idx].uncomp_size + 255) & ~255ull; g1++; }
+            const u64 g1 = host_group_cut(desc, be.data(), be.size(), g0, to == Dst::None);
             rc = decode_big_group(c, archive, desc, be.data(), g0, g1, subs, dst_ptrs, results, redo.data(), to, pl);
             g0 = g1;
         }
@@ -2836,10 +2737,7 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
     if (!staged.empty()) desc = staged.data();
     const Planes pl = { pl_given.elem, pl_given.base, refused.empty() ? nullptr : refused.data(), pl_given.win };
     const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
-    auto slot = [&](u64 i) {                                                          // (no destination: a stored entry has no slot)
-        const bool stored = desc[i].method == ZPK_METHOD_NONE;
-        return none && stored ? 0ull : dimage_slot(stored, desc[i].uncomp_size, desc[i].dst_capacity);
-    };
+    auto slot = [&](u64 i) { return read_slot(none, desc[i]); };                      // (host_plan.h: the host path's slot)
     int rc = ZPK_OK;
     u64 home_total = 0;
     try {
@@ -2854,7 +2752,7 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
             if ((rc = decode_big_batch_body(c, d_archive, archive_size, hd.data(), cut.count, c->d_dst, cut.out_total, results + first, none ? Dst::None : Dst::Device))) break;
             u64 home = 0;
             if ((rc = deliver_slots(c, hd.data(), desc + first, cut.count, cut.out_total, dst_ptrs ? dst_ptrs + first : nullptr, results + first, to, &home, pl.from(first)))) break;
-            home_total = home > ~0ull - home_total ? ~0ull : home_total + home;
+            sat_add(home_total, home);
             c->last.dimage[0]++; c->last.subs++;
             first += cut.count;
         }

@@ -474,7 +474,8 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
         image = span; image_size = span_size;
     } else if (reader->file) {
         /* pack the payloads of the entries that pass the reference's guards behind a 1-byte pad, so that
-         * the device sees the same `offset + comp_size >= file_size` verdicts (lib/zpack_read.c:331) */
+         * the device sees the same `offset + comp_size >= file_size` verdicts (lib/zpack_read.c:331); the codec's statement of this
+         * image for a reader in memory: host_gather_layout, csrc/host_plan.h */
         zpack_u64 total = 1;
         for (zpack_u64 i = 0; i < count; i++)
             if (entries[i]->comp_size && entries[i]->offset + entries[i]->comp_size < reader->file_size) total += entries[i]->comp_size;
