@@ -5,7 +5,7 @@ of at most 64 KiB of output whose first batch is 64 literal-heavy sequences, so 
 batch against the oracle's bytes) and tests/test_gpu_lz4_asm_overlap.py (the device).  Not a test module."""
 import numpy as np
 
-from tests.test_gpu_lz4_asm_batches import Block, M
+from tests.lz4_asm import Block, M
 
 LENGTHS = (4, 5, 16, 17, 31, 32, 33)                 # 33: still the direct path
 OFFSETS = (1, 2, 3, 7, 8, 15, 16, 17, 31)            # and length - 1

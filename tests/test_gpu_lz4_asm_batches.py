@@ -3,9 +3,7 @@ dead part runs up to the NEXT batch's first token (the chain's exit for a chunk'
 own tokens and literals in the stage.  Hand-built plain frames put batches on both sides of every edge of that rule — tools/sim/
 lz4_asm_share.py (the CPU model of the chunking and of the rule) says where each batch of a block sits, and the tests assert that the
 blocks sit where they mean to.  What is right is decided by the oracle: bytes, status and produced size of every entry."""
-import importlib.util
 import os
-import struct
 
 import numpy as np
 import pytest
@@ -13,87 +11,11 @@ import pytest
 import zpack_amd
 from benchdata import datagen as dg
 from tests._libs import oracle
+from tests.lz4_asm import Block, M, _frame, _model        # (the assembler lives there now; these names are used by other test modules)
 from tests.test_gpu_lz4_lean import _assemble, _device_batch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _model():
-    spec = importlib.util.spec_from_file_location("lz4_asm_share", os.path.join(ROOT, "tools", "sim", "lz4_asm_share.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-M = _model()
-
-
-class Block:
-    """one LZ4 block written sequence by sequence; only the LENGTH of the output is tracked (the oracle supplies the bytes)"""
-
-    def __init__(self, seed, history=0):
-        self.rng = np.random.default_rng(seed)
-        self.d = bytearray()
-        self.n = 0                    # output bytes of this block so far
-        self.hist = history           # output bytes a match may reach in front of the block (linked blocks)
-        self.off_pos = []             # block position of every offset field
-        self.nseq = 0
-
-    def seq(self, ll, ml, off=None):
-        assert ml >= 4
-        if off is None:               # a plain match somewhere in what exists, mostly near (so that batches depend on themselves)
-            have = self.n + ll + self.hist
-            off = int(self.rng.integers(ml, max(ml + 1, min(have, 300) + 1)))
-            off = min(off, have)
-        assert 1 <= off <= self.n + ll + self.hist, (off, self.n, ll)
-        self.d.append((min(ll, 15) << 4) | min(ml - 4, 15))
-        self._ext(ll)
-        self.d += self.rng.integers(0, 256, ll, dtype=np.uint8).tobytes()
-        self.off_pos.append(len(self.d))
-        self.d += struct.pack("<H", off)
-        self._ext(ml - 4)
-        self.n += ll + ml
-        self.nseq += 1
-        return self
-
-    def _ext(self, v):
-        if v >= 15:
-            v -= 15
-            while v >= 255:
-                self.d.append(255); v -= 255
-            self.d.append(v)
-
-    def fill(self, count, ll=(0, 6), ml=(4, 10)):
-        for _ in range(count):
-            self.seq(int(self.rng.integers(ll[0], ll[1] + 1)), int(self.rng.integers(ml[0], ml[1] + 1)))
-        return self
-
-    def run(self):
-        """a long byte run: the entry then compresses below 1/8 and k_classify routes it to k_lz4_left"""
-        self.seq(1, 9 * (len(self.d) + 40), 1)
-        return self
-
-    def done(self, tail=16):
-        self.d.append(min(tail, 15) << 4)
-        self._ext(tail)
-        self.d += self.rng.integers(0, 256, tail, dtype=np.uint8).tobytes()
-        self.n += tail
-        return bytes(self.d)
-
-
-def _frame(blocks, linked=False):
-    """blocks: [("c" | "s", bytes)] -> (frame, frame position of every block's payload)"""
-    o = oracle()
-    desc = bytes([0x40 if linked else 0x60, 0x40])
-    f = bytearray(b"\x04\x22\x4d\x18" + desc + bytes([(o.xxh32(desc) >> 8) & 0xFF]))
-    at = []
-    for kind, data in blocks:
-        f += struct.pack("<I", len(data) | (0x80000000 if kind == "s" else 0))
-        at.append(len(f))
-        f += data
-    f += struct.pack("<I", 0)
-    return bytes(f), at
 
 
 def _case(label, blk, data, left=False):

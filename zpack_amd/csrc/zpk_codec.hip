@@ -1877,6 +1877,7 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
     // ---- every chunk: references, PJ_MAX_ROUNDS rounds of pointer doubling (a round behind the last one that changed anything returns at
     // once: no host round trip), the gather; an event behind each chunk lets its bytes be hashed and go home while the next is resolved ----
     bool launch_failed = false;
+    const bool short_hash = n <= 240;
     u64 g_lo = 0;
     for (u64 k = 0; k < nchunks; k++) {
         const u32 b0 = (u32)(k * chunk_blocks), b1 = (u32)(b0 + chunk_blocks < nb ? b0 + chunk_blocks : nb);
@@ -1893,6 +1894,9 @@ static int pj_finish(zpk_codec* c, const zpk_decode_desc& d, const std::vector<P
         enqueued.store(k + 1, std::memory_order_release);
         const bool last = k + 1 == nchunks;
         const u64 g_hi = last ? ngroups : (hi >> 10) / XS_GROUP;                       // groups of 64 blocks that are final now
+        // (an output of at most 240 bytes: XXH3's short-input forms, not the chain — its tail reads the stripe at end - 64 and ends in the
+        // avalanche of the long form.  One wave of k_hash behind the last chunk, the span's own off / len words as its one-row table)
+        if (short_hash) { if (last) hipLaunchKernelGGL(k_hash, dim3(1), dim3(64), 0, sh, (const u8*)d_out, (const u64*)&d_span->off, (const u64*)&d_span->len, (u64)1, d_hash); continue; }
         if (g_hi > g_lo) hipLaunchKernelGGL(k_xxh3_partials, dim3((u32)((g_hi - g_lo + 3) / 4)), dim3(256), 0, sh, (const u8*)d_out, (const zpk_span*)d_span, 1u, g_lo, g_hi, d_part);
         if (g_hi > g_lo || last)
             hipLaunchKernelGGL(k_xxh3_chain, dim3(1), dim3(64), 0, sh, (const u8*)d_out, (const zpk_span*)d_span, (const u64*)d_part, d_hash, d_state, g_lo * XS_GROUP, g_hi * XS_GROUP, last ? 1 : 0);
