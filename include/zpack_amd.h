@@ -173,6 +173,43 @@ ZPACK_EXPORT int zpack_amd_read_files_device_windows(zpack_reader* reader, zpack
                                                      const void* const* d_bases, const zpack_u64* base_hashes,
                                                      const zpack_amd_window* windows, int* results, void* dctx);
 
+/* ---- PLACED reads: an entry delivered into a sub-block of a device tensor -------------------------------------------------------------------
+ * The opposite direction.  A checkpoint written by 8 tensor-parallel ranks holds 8 shard entries per weight; a loader at another width —
+ * an inference server, an evaluation job — puts several shards side by side in ONE tensor.  Along dimension 0 that is a pointer offset;
+ * along any other each shard is a strided sub-block of the destination, and the calls above make the caller read every shard into a
+ * scratch buffer and concatenate: a second pass over every plaintext byte and a scratch copy of the checkpoint.  A PLACED entry has a
+ * window and a destination ROW PITCH in bytes; the copy that delivers the entry writes window row r at byte r * pitch of the buffer.
+ * An entry read whole is the window row0 = 0, col0 = 0, cols = row_bytes, rows = uncomp_size / row_bytes.
+ * A placement is VALID when the window is, pitch >= cols, and place_extent = (rows - 1) * pitch + cols (0 when rows * cols == 0) does
+ *   not wrap; the pitch needs no alignment to the element size.  Window byte d, d in [0, window_bytes), lands at buffer byte
+ *   (d / cols) * pitch + d % cols, XOR that same byte of the base when there is one: the base is the caller's previous checkpoint in
+ *   the MERGED layout.  The bytes of the extent in the gaps [cols, pitch) of every row are never written and never read from the base.
+ * The slice [start, start + length) along dimension `dim` of a contiguous destination of `shape` and `itemsize` is
+ *   rows = prod(shape[:dim]), cols = length * inner, pitch = shape[dim] * inner, and d_buffers[i] = the tensor + start * inner,
+ *   with inner = prod(shape[dim + 1:]) * itemsize.
+ *
+ * zpack_amd_read_files_device_placed.  zpack_amd_read_files_device_windows with dst_pitches[i], the pitch of entry i (host memory, count
+ *   values).  dst_pitches == NULL IS that call, the same code; dst_pitches[i] == 0: entry i as that call treats it.  Every kind of
+ *   reader.  For a placed entry:
+ *   d_buffers[i] points at the FIRST BYTE of the sub-block: the caller adds the column offset.  max_sizes[i], d_bases[i] and the pointer
+ *     rule are about place_extent bytes; d_bases[i] == d_buffers[i] exactly is legal, any other overlap of the two extents is not.
+ *   max_sizes[i] < place_extent: results[i] is ZPACK_ERROR_BUFFER_TOO_SMALL as in the _windows call, and nothing is written.
+ *   Otherwise results[i], the return value and reader->last_return are the _windows call's.  The bytes are delivered only when the entry
+ *     decoded to all of its uncomp_size bytes (ZPACK_OK or ZPACK_ERROR_FILE_HASH_MISMATCH) and its base was accepted; otherwise no byte
+ *     of the buffer is touched.  The gap bytes are never touched.
+ *   The extents of different entries may interleave — that is the point.  Two entries whose PLACED bytes overlap are the caller's
+ *     error and are not diagnosed.
+ *   base_hashes[i] is the hash of a contiguous span, and a placed base is not one: a placed entry with a base in a call whose
+ *     base_hashes is not NULL is refused (below) unless its extent equals its window bytes (rows <= 1 or pitch == cols), which is
+ *     checked as ever.  Hash the whole merged base with zpack_amd_hash_device instead and read with base_hashes NULL.
+ * A placement that is not valid, a pitch on an entry without a window, a base of a placed entry that overlaps its buffer other than by
+ *   being it, or that base-hash case is ZPACK_ERROR_STREAM_INVALID, judged before any context is created or anything is enqueued: no
+ *   result is set. */
+ZPACK_EXPORT int zpack_amd_read_files_device_placed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                                    void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes,
+                                                    const void* const* d_bases, const zpack_u64* base_hashes,
+                                                    const zpack_amd_window* windows, const zpack_u64* dst_pitches, int* results, void* dctx);
+
 /* ---- the archive IMAGE in DEVICE memory -------------------------------------------------------------------------------------------
  * A third kind of reader beside the memory-backed and the file-backed one: the archive lies in device memory — a data set or checkpoint
  * kept compressed in HBM, an archive that arrived by a device-to-device transfer — and its compressed bytes never cross the bus.

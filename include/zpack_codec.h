@@ -62,7 +62,9 @@ extern "C" {
                                         zpk_codec_hash_spans_device, ZPK_OPT_SPAN_HASH_MIN, the _delta_checked forms of the two reads that take bases, ZPK_R_BASE_MISMATCH,
                                         zpk_codec_base_check_stats: the base of a delta entry is hashed on the device before it is applied.
                                         zpk_codec_window_copy_device, the _windows forms of the same two reads, zpk_codec_window_stats: a 2-D sub-block of an entry
-                                        delivered densely to device memory.) */
+                                        delivered densely to device memory.
+                                        zpk_codec_place_copy_device, the _placed forms of the same two reads, zpk_codec_place_stats: that sub-block delivered into a
+                                        sub-block of a larger device tensor, several entries side by side.) */
 
 /* return codes of the zpk_* entry points themselves (not per-entry statuses) */
 enum {
@@ -529,6 +531,57 @@ int zpk_codec_decode_batch_dimage_windows(zpk_codec* c, const uint8_t* d_archive
  * out[2] entries that decoded into the staging only because they had a window (element size 1, no base).  zpk_codec_planes_stats and
  * zpk_codec_delta_stats keep their meaning: they count the rows of k_plane_copy and k_delta_copy, which are those without a window. */
 int zpk_codec_window_stats(zpk_codec* c, uint32_t out[3]);
+
+/* ---- PLACED reads: an entry, or a window of it, delivered into a sub-block of a larger device tensor (k_place_copy) --------------------
+ * A checkpoint written by 8 tensor-parallel ranks holds 8 shard entries per weight; a loader at another width puts several of them side
+ * by side in one tensor, which along any dimension but the first makes each shard a strided sub-block of the destination.  A PLACED
+ * entry has a valid window and a PITCH != 0, in bytes: window row r begins at byte r * pitch of the destination, and of the base.  An
+ * entry read whole is the window row0 = 0, col0 = 0, cols = row_bytes, rows = n / row_bytes.  The placement is valid when the window is,
+ * pitch >= cols, and place_extent = (rows - 1) * pitch + cols (0 when rows * cols == 0) does not wrap; the pitch needs no alignment to
+ * the element size.  For window byte d in [0, window_bytes):
+ *     o(d)      = (d / cols) * pitch + d % cols
+ *     dst[o(d)] = plain[(row0 + d / cols) * row_bytes + col0 + d % cols] ^ (base ? base[o(d)] : 0)
+ * The base is indexed by the same byte as the destination: it is the caller's previous checkpoint in the MERGED layout.  The bytes of
+ * the extent in the gaps [cols, pitch) of every row are never written and never read from the base: they belong to the neighbouring
+ * shards, and the extents of different rows may interleave.  The slice [start, start + length) along dimension `dim` of a contiguous
+ * destination of `shape` and `itemsize` is rows = prod(shape[:dim]), cols = length * inner, pitch = shape[dim] * inner at the byte
+ * offset start * inner, inner = prod(shape[dim + 1:]) * itemsize.
+ * zpk_codec_place_copy_device: the kernel on its own.  rows[0, n) is HOST memory, consumed before the call returns; src is the entry's
+ * n stored bytes, dst and base (0: none) span place_extent bytes; DEVICE addresses on the codec's device, any alignment.  base == dst
+ * exactly is legal; any other overlap of the two ranges of place_extent bytes is not.  A placement that is not valid, an element size
+ * outside {1, 2, 4, 8}, such an overlap, or a pointer that fails the rule over those lengths: ZPK_E_INVALID and NOTHING has run, the
+ * good rows beside the bad one included.  A row of no bytes (n == 0 or rows * cols == 0) passes wherever it points. */
+typedef struct zpk_place_copy { uint64_t src, dst, base, n; zpk_window win; uint64_t pitch; uint32_t elem, pad; } zpk_place_copy;
+int zpk_codec_place_copy_device(zpk_codec* c, const zpk_place_copy* rows, uint64_t n, void* stream);
+/* the rule on its own, instance-free, no device needed: 1 = `win` at `pitch` is a valid placement of an entry of n plain bytes with
+ * element size elem (*extent, when not NULL, becomes place_extent), 0 = it is not (pitch == 0 and row_bytes == 0 included) */
+int zpk_codec_place_valid(uint64_t n, uint32_t elem, const zpk_window* win, uint64_t pitch, uint64_t* extent);
+/* ... and the overlap rule of a valid placement: 1 = base == dst or the two ranges of place_extent bytes are disjoint */
+int zpk_codec_place_overlap_ok(uint64_t base, uint64_t dst, const zpk_window* win, uint64_t pitch);
+/* The two _windows reads with one more argument: pitch[i] is the pitch of entry i (HOST memory, n values).  pitch == NULL IS the
+ * _windows call, the same body; pitch[i] == 0: entry i as that call treats it.  A non-zero pitch on an entry without a window, a
+ * placement that is not valid against desc[i].uncomp_size and elem[i], or one with host destinations: ZPK_E_INVALID and nothing has
+ * run.  A placed entry decodes into the codec's staging exactly as a windowed one does and is delivered through k_place_copy — even
+ * where pitch == cols — under the rule of the _windows call: only when it decoded to all of uncomp_size and its base was accepted,
+ * else no byte of its buffer is written.  For a placed entry the destination, the base and the pointer rule are about place_extent
+ * bytes, and desc[i].dst_capacity is the room at the destination: with less than place_extent the entry is BUFFER_TOO_SMALL where the
+ * guards, in their order, say so, and nothing is written.
+ * BASE HASHES.  base_hash[i] is the XXH3 of a contiguous span, and the base of a placed entry is not one: a placed entry with a base in
+ * a call whose base_hash is not NULL is ZPK_E_INVALID before anything runs — unless its extent equals its window bytes (rows <= 1 or
+ * pitch == cols), which is checked as ever.  The caller hashes its whole merged base itself (zpk_codec_hash_spans_device;
+ * zpack_amd_hash_device) and reads with base_hash NULL. */
+int zpk_codec_decode_batch_host_dptr_placed(zpk_codec* c, const uint8_t* archive, uint64_t archive_size,
+                                            const zpk_decode_desc* desc, uint64_t n,
+                                            uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                            const uint64_t* base_hash, const zpk_window* win, const uint64_t* pitch);
+int zpk_codec_decode_batch_dimage_placed(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size,
+                                         const zpk_decode_desc* desc, uint64_t n,
+                                         uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                         const uint64_t* base_hash, const zpk_window* win, const uint64_t* pitch);
+/* the most recent of the three calls above (or of a call that could split, join or cut): out[0] rows placed, out[1] k_place_copy
+ * launches.  zpk_codec_window_stats keeps its meaning: out[0] and out[1] count the rows of k_window_copy, which are the windowed rows
+ * without a pitch; out[2] counts a placed entry that was staged only because it had a window as it counts any other. */
+int zpk_codec_place_stats(zpk_codec* c, uint32_t out[2]);
 
 /* zpk_codec_encode_batch_device for batches that hold LARGE entries: d_src, d_dst and d_results are DEVICE pointers, `desc` is HOST memory
  * (consumed before the call returns).  An entry with size >= ZPK_OPT_ENC_SPLIT_MIN, size > 512 KiB and a valid method is compressed as

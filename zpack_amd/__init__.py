@@ -42,6 +42,8 @@ assert HASH_SPAN.itemsize == 16
 WINDOW = np.dtype([("row_bytes", "<u8"), ("row0", "<u8"), ("rows", "<u8"), ("col0", "<u8"), ("cols", "<u8")])           # zpk_window (and zpack_amd_window)
 WINDOW_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("base", "<u8"), ("n", "<u8"), ("win", WINDOW), ("elem", "<u4"), ("pad", "<u4")])   # zpk_window_copy
 assert WINDOW.itemsize == 40 and WINDOW_COPY.itemsize == 80
+PLACE_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("base", "<u8"), ("n", "<u8"), ("win", WINDOW), ("pitch", "<u8"), ("elem", "<u4"), ("pad", "<u4")])   # zpk_place_copy
+assert PLACE_COPY.itemsize == 88
 
 
 def slice_window(shape, dim, start, stop, itemsize=1):
@@ -62,6 +64,28 @@ def slice_window(shape, dim, start, stop, itemsize=1):
         inner *= s
     inner *= int(itemsize)
     return (shape[dim] * inner, 0, outer, start * inner, (stop - start) * inner)
+
+
+def place_of(dest_shape, dim, start, length, itemsize=1):
+    """Where the slice [start, start + length) along dimension `dim` of a contiguous destination tensor of `dest_shape` lies, as
+    (rows, cols, pitch, byte_offset), all but rows in bytes: the placement of a placed read (include/zpack_codec.h states the formula) —
+    `rows` rows of `cols` bytes, row r at byte_offset + r * pitch of the tensor.  ValueError: dim, start or length out of range."""
+    shape = [int(s) for s in dest_shape]
+    if not shape or any(s < 0 for s in shape):
+        raise ValueError("shape %r" % (shape,))
+    if not -len(shape) <= dim < len(shape):
+        raise ValueError("dim %d of a %d-d shape" % (dim, len(shape)))
+    dim %= len(shape)
+    if not (0 <= start and 0 <= length and start + length <= shape[dim]):
+        raise ValueError("[%d, %d + %d) of %d along dim %d" % (start, start, length, shape[dim], dim))
+    rows = inner = 1
+    for s in shape[:dim]:
+        rows *= s
+    for s in shape[dim + 1:]:
+        inner *= s
+    inner *= int(itemsize)
+    return (rows, length * inner, shape[dim] * inner, start * inner)
+
 
 _lib = None
 
@@ -116,6 +140,11 @@ def lib():
             L.zpk_codec_window_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
             L.zpk_codec_window_valid.argtypes = [u64, C.c_uint32, vp, C.POINTER(u64)]
             L.zpk_codec_window_overlap_ok.argtypes = [u64, u64, vp]
+        if hasattr(L, "zpk_codec_place_copy_device"):         # (likewise: placed reads)
+            L.zpk_codec_place_copy_device.argtypes = [vp, vp, u64, vp]
+            L.zpk_codec_place_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
+            L.zpk_codec_place_valid.argtypes = [u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+            L.zpk_codec_place_overlap_ok.argtypes = [u64, u64, vp, u64]
         L.zpk_codec_pack_batch_device.argtypes = [vp, u8p, vp, vp, u64, u8p, u64, vp, u64, vp]
         L.zpk_codec_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
         L.zpk_codec_compress_bound.restype = C.c_size_t
@@ -477,6 +506,23 @@ class Codec:
         a = (C.c_uint32 * 3)()
         self._chk(self.L.zpk_codec_window_stats(self.h, a), "zpk_codec_window_stats")
         return dict(rows=a[0], launches=a[1], staged=a[2])
+
+    def place_copy_device(self, rows, stream=None):
+        """rows: PLACE_COPY array of (src address, dst address, base address or 0, n, window, pitch, elem): one k_place_copy launch — the
+        window of the n stored bytes at src, joined and XORed with the base, window row r at r * pitch of dst (include/zpack_codec.h
+        states the map); the gaps between the rows are not touched, so several rows may share one destination tensor; base == dst is
+        legal.  Asynchronous on `stream` (None: the codec's own; synchronise the device before reading the destinations).  Raises on
+        ZPK_E_INVALID (a placement, a pointer or an overlap the check turned down: nothing has run)."""
+        self._settle(stream)
+        rows = np.ascontiguousarray(rows, dtype=PLACE_COPY)
+        self._chk(self.L.zpk_codec_place_copy_device(self.h, rows.ctypes.data, len(rows), C.c_void_p(stream) if stream else None),
+                  "zpk_codec_place_copy_device")
+
+    def place_stats(self):
+        """The most recent call that could split, join, cut or place: rows placed, k_place_copy launches."""
+        a = (C.c_uint32 * 2)()
+        self._chk(self.L.zpk_codec_place_stats(self.h, a), "zpk_codec_place_stats")
+        return dict(rows=a[0], launches=a[1])
 
     def hash_spans_device(self, rows, stream=None):
         """rows: HASH_SPAN array of (device address, len), any alignment: the XXH3-64 (seed 0) of each span as a uint64 array — rows below

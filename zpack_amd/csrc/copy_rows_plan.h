@@ -1,8 +1,8 @@
-// copy_rows_plan.h — what the four ROW COPIES share: k_span_copy, k_plane_copy, k_delta_copy and k_window_copy (row_copy.hip) each read a
-// table of rows, one wave per 16 KiB work item of a row, and a table past one grid goes in several launches.  Decided here, in one place:
+// copy_rows_plan.h — what the five ROW COPIES share: k_span_copy, k_plane_copy, k_delta_copy, k_window_copy and k_place_copy (row_copy.hip)
+// each read a table of rows, one wave per 16 KiB work item of a row, and a table past one grid goes in several launches.  Decided here, in one place:
 // the piece, the limits, the count of a row's items, the search a wave finds its row by, and the launch split.  What a row IS — its
 // struct, its emit, what an item of it covers — belongs to the table's own header: span_copy_plan.h, plane_copy_plan.h,
-// delta_copy_plan.h, window_copy_plan.h.
+// delta_copy_plan.h, window_copy_plan.h, place_copy_plan.h.
 // Plain C++17, pj_types.h and standard headers only: tools/hostfuzz builds this file with g++ under ASan + UBSan (g++ knows no HIP),
 // which keeps it so.  copy_items is also device code: ZPK_HD is empty on a CPU build.
 #pragma once

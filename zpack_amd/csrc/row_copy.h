@@ -1,11 +1,11 @@
 // row_copy.h — the device parts the four ROW COPIES share (the kernels themselves: row_copy.hip): how a wave finds its row and its piece
 // (copy_item_of), the dispatch on a row's element size (copy_dispatch), the byte permutes (pc_group) and the 16-byte accesses (pc_ld,
 // pc_st), and the two item bodies that use them — pc_item, one 16 KiB piece of a byte-plane or delta row, and wc_item, one of a window
-// row.  The tables, the items and the launches: copy_rows_plan.h and the four *_copy_plan.h.
+// row or, PITCHED, of a placed row.  The tables, the items and the launches: copy_rows_plan.h and the five *_copy_plan.h.
 #pragma once
 #include <type_traits>
 #include "zpk_device.h"
-#include "window_copy_plan.h"                    // (... and delta_copy_plan.h, plane_copy_plan.h, copy_rows_plan.h through it)
+#include "place_copy_plan.h"                     // (... and window_copy_plan.h, delta_copy_plan.h, plane_copy_plan.h, copy_rows_plan.h through it)
 
 namespace zpk {
 
@@ -171,8 +171,8 @@ template <u32 K, bool JOIN, bool BASE> __device__ __forceinline__ void pc_item(c
     }
 }
 
-// the geometry of a window row, uniform over the wave
-struct WcGeom { u64 n, row_bytes, row0, col0, cols; };
+// the geometry of a window row, uniform over the wave; pitch: a placed row's (place_copy_plan.h), not looked at otherwise
+struct WcGeom { u64 n, row_bytes, row0, col0, cols, pitch; };
 
 // One item of a window row with element size K.  Group G of the item — 16 elements of ONE window row — is 16 * K destination bytes at
 // window_dst_of, the same 16 * K bytes of the base, and 16 bytes in each plane at p * m + e, e the group's first plain element; lane l
@@ -185,7 +185,13 @@ struct WcGeom { u64 n, row_bytes, row0, col0, cols; };
 // base bytes of its groups before it stores to the same addresses, and lanes own disjoint groups — with U > 1 every load of a step
 // stands before its first store.  So `base` and `dst` are NOT __restrict__, as in pc_item.  Any other overlap the host refuses
 // (window_overlap_ok).
-template <u32 K, bool BASE> __device__ __forceinline__ void wc_item(const u8* src, u8* dst, const u8* base, WcGeom g, WindowPiece P, int lane)
+//
+// PITCHED: one item of a PLACED row (k_place_copy).  The item is the same 16 KiB of window bytes, the same groups and loose bytes and the
+// same plain indices; only where a place lies in `dst` and `base` differs — place_dst_of, window row r at r * pitch — so the rows of an
+// item lie apart and the gaps between them are neither written nor read.  The in-place argument holds over the placed bytes
+// (place_copy_plan.h); any other overlap of the two extents the host refuses (place_overlap_ok).  Without PITCHED g.pitch is not looked
+// at and the instructions are those the item had before there was one.
+template <u32 K, bool BASE, bool PITCHED = false> __device__ __forceinline__ void wc_item(const u8* src, u8* dst, const u8* base, WcGeom g, WindowPiece P, int lane)
 {
     constexpr u32 U = K == 1 ? 4 : K == 2 ? 2 : 1;
     const u64 m = g.n / K;
@@ -198,7 +204,7 @@ template <u32 K, bool BASE> __device__ __forceinline__ void wc_item(const u8* sr
         #pragma unroll
         for (u32 t = 0; t < U; t++) {
             const WindowAt a = window_group_at(P, K, G + t * WAVE);
-            d[t] = d_row0 + (u64)a.row * g.cols + a.col;
+            d[t] = PITCHED ? place_dst_of(P, g.pitch, a) : d_row0 + (u64)a.row * g.cols + a.col;
             const u64 e = (i_row0 + (u64)a.row * g.row_bytes + a.col) / K;
             #pragma unroll
             for (u32 p = 0; p < K; p++) {
@@ -223,7 +229,7 @@ template <u32 K, bool BASE> __device__ __forceinline__ void wc_item(const u8* sr
         for (; G < P.groups; G += WAVE) {
             v4u32 x[K], b[K], y[K];
             const WindowAt a = window_group_at(P, K, G);
-            const u64 d = d_row0 + (u64)a.row * g.cols + a.col;
+            const u64 d = PITCHED ? place_dst_of(P, g.pitch, a) : d_row0 + (u64)a.row * g.cols + a.col;
             const u64 e = (i_row0 + (u64)a.row * g.row_bytes + a.col) / K;
             #pragma unroll
             for (u32 p = 0; p < K; p++) {
@@ -241,7 +247,7 @@ template <u32 K, bool BASE> __device__ __forceinline__ void wc_item(const u8* sr
     // what does not fill a group at the end of a window-row segment: byte by byte through the map, dealt over the whole item likewise
     for (u32 B = (u32)lane; B < P.loose; B += WAVE) {
         const WindowAt a = window_loose_at(P, K, B);
-        const u64 d = d_row0 + (u64)a.row * g.cols + a.col;
+        const u64 d = PITCHED ? place_dst_of(P, g.pitch, a) : d_row0 + (u64)a.row * g.cols + a.col;
         const u64 i = i_row0 + (u64)a.row * g.row_bytes + a.col;
         const u8 v = ld8(src + (i % K) * m + i / K);                                   // plane_stored_index of an entry without a tail (window_valid)
         st8(dst + d, BASE ? delta_byte(v, ld8(base + d)) : v);

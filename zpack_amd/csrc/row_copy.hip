@@ -1,8 +1,8 @@
-// row_copy.hip — the four ROW COPIES that move plaintext between the codec's staging and the caller's device buffers, as one code object:
-// k_span_copy (plain bytes), k_plane_copy (byte planes), k_delta_copy (byte planes XORed against a base) and k_window_copy (a 2-D cut of
-// a decoded entry), each with the one host function that launches it.  zpk_codec.hip builds the row tables and calls the launchers;
+// row_copy.hip — the five ROW COPIES that move plaintext between the codec's staging and the caller's device buffers, as one code object:
+// k_span_copy (plain bytes), k_plane_copy (byte planes), k_delta_copy (byte planes XORed against a base), k_window_copy (a 2-D cut of
+// a decoded entry) and k_place_copy (that cut set into a sub-block of a larger tensor), each with the one host function that launches it.  zpk_codec.hip builds the row tables and calls the launchers;
 // keeping the kernels out of that file keeps its code object, and where every other kernel lies in it, unchanged.  What the kernels
-// share: row_copy.h; the tables, the items and the launches: copy_rows_plan.h and the four *_copy_plan.h.
+// share: row_copy.h; the tables, the items and the launches: copy_rows_plan.h and the five *_copy_plan.h.
 #include <hip/hip_runtime.h>
 #include "row_copy.h"
 #include "seq_exec.h"                            // gcopy_upto16
@@ -96,9 +96,33 @@ __global__ __launch_bounds__(256) void k_window_copy(const WindowCopyRow* __rest
     const u8* const s = uni_ptr((const u8*)r.src);
     u8* const d = uni_ptr((u8*)r.dst);
     const u8* const b = uni_ptr((const u8*)r.base);
-    const WcGeom g = { uni64(r.n), uni64(r.row_bytes), uni64(r.row0), uni64(r.col0), uni64(r.cols) };
+    const WcGeom g = { uni64(r.n), uni64(r.row_bytes), uni64(r.row0), uni64(r.col0), uni64(r.cols), 0 };
     const WindowPiece P = window_piece(len, g.cols, k, piece);
     copy_dispatch(k, b != nullptr, [&](auto K, auto BASE) { wc_item<decltype(K)::value, decltype(BASE)::value>(s, d, b, g, P, lane); });
+}
+
+// k_place_copy: k_window_copy for PLACED reads — the window of each row is written into a sub-block of a larger tensor, window row r at
+// r * pitch of the destination, so that several entries land side by side in one buffer; the base, where the row has one, is the
+// caller's previous checkpoint in that merged layout and is read at the very bytes that are written.  The pitch, the rule, the map and
+// the placed offset: place_copy_plan.h; an item is 16 KiB of the row's WINDOW bytes, cut as k_window_copy's are.  IN PLACE: wc_item.
+// Source, destination, base, pitch and every plane start may have any alignment.  Nothing outside [src, src + n) is read; of
+// [dst, dst + place_extent) and [base, base + place_extent) only the placed bytes are touched, each destination byte written once — the
+// gaps [cols, pitch) of every row belong to the neighbours.  No LDS, no scratch.
+__global__ __launch_bounds__(256) void k_place_copy(const PlaceCopyRow* __restrict__ rows, u32 nrows, u64 item0, u64 nitems)
+{
+    const int lane = lane_id();
+    PlaceCopyRow r;
+    u64 piece;
+    if (!copy_item_of(rows, nrows, item0, nitems, r, piece)) return;
+    const u64 len = uni64(r.len);
+    const u32 k = uni(r.elem);
+    if (piece >= copy_items(len)) return;                                             // (not an item of this table)
+    const u8* const s = uni_ptr((const u8*)r.src);
+    u8* const d = uni_ptr((u8*)r.dst);
+    const u8* const b = uni_ptr((const u8*)r.base);
+    const WcGeom g = { uni64(r.n), uni64(r.row_bytes), uni64(r.row0), uni64(r.col0), uni64(r.cols), uni64(r.pitch) };
+    const WindowPiece P = window_piece(len, g.cols, k, piece);
+    copy_dispatch(k, b != nullptr, [&](auto K, auto BASE) { wc_item<decltype(K)::value, decltype(BASE)::value, true>(s, d, b, g, P, lane); });
 }
 
 void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st)
@@ -116,6 +140,11 @@ void delta_copy_launch(const DeltaCopyRow* d_rows, u32 nrows, u64 item0, u64 nit
 void window_copy_launch(const WindowCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st)
 {
     hipLaunchKernelGGL(k_window_copy, dim3(grid), dim3(256), 0, st, d_rows, nrows, item0, nitems);
+}
+
+void place_copy_launch(const PlaceCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_place_copy, dim3(grid), dim3(256), 0, st, d_rows, nrows, item0, nitems);
 }
 
 }  // namespace zpk

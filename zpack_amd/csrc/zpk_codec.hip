@@ -42,18 +42,20 @@
 #include "enc_plan.h"                            // an entry written in pieces: split rule, piece descriptors, frame envelope, verdict (plain C++, likewise)
 #include "stored_plan.h"                         // the large stored entries of a device-resident batch: which are taken, their span table, the verdict (plain C++, likewise)
 #include "stored_span.h"                         // k_stored_span: their copy fused with the XXH3 partial sums, across the chip
-#include "copy_rows_plan.h"                      // the four row copies below: the 16 KiB item, the row search and the launch split they share (plain C++, likewise)
+#include "copy_rows_plan.h"                      // the five row copies below: the 16 KiB item, the row search and the launch split they share (plain C++, likewise)
 #include "span_copy_plan.h"                      // plaintext in the caller's DEVICE memory: the row table of k_span_copy, the staging slots, the pointer test (plain C++, likewise)
 #include "plane_copy_plan.h"                     // byte-plane entries: the layout and the row table of k_plane_copy (plain C++, likewise)
 #include "delta_copy_plan.h"                     // delta entries: a tensor stored as its XOR against a base in device memory, and the row table of k_delta_copy (plain C++, likewise)
 #include "window_copy_plan.h"                    // window reads: a 2-D sub-block of an entry delivered densely, the rule, the map and the row table of k_window_copy (plain C++, likewise)
-// The four kernels are compiled in a file of their own, row_copy.hip: this file's code object stays the one it was, kernel for kernel at
+#include "place_copy_plan.h"                     // placed reads: that sub-block set into a sub-block of a larger tensor — the pitch, its rule, the extent and the row table of k_place_copy (plain C++, likewise)
+// The five kernels are compiled in a file of their own, row_copy.hip: this file's code object stays the one it was, kernel for kernel at
 // the same place (a 46th kernel among them cost c4_mixed 1.3 % in alternating pairs: profiles/r20/README.md)
 namespace zpk {
 void span_copy_launch(const SpanCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
 void plane_copy_launch(const PlaneCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
 void delta_copy_launch(const DeltaCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
 void window_copy_launch(const WindowCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
+void place_copy_launch(const PlaceCopyRow* d_rows, u32 nrows, u64 item0, u64 nitems, u32 grid, hipStream_t st);
 }
 #include "span_hash_plan.h"                      // XXH3 of arbitrary device spans (the bases of delta entries): one-wave and chip-wide rows, their tables, launches and loads (plain C++, likewise)
 // k_span_hash (span_hash.h) and its copies of the chip-wide pair are compiled in span_hash.hip, for the same reason
@@ -642,21 +644,28 @@ enum class Dst : int { Host = 0, Device = 1, None = 2 };
 // densely, to a destination — and against a base — of window_bytes bytes; none (or row_bytes == 0 for an entry) = the entry whole.  An
 // entry with a window is treated wherever a grouped entry is, whatever its element size or base.  The fourth column, cut and gathered
 // with the other three.
+// ... and their PITCHES (place_copy_plan.h; the _placed reads): pitch[i] != 0 = the window of entry i is PLACED — window row r at byte
+// r * pitch[i] of the destination, and of the base — so destination and base hold place_extent bytes of which only the placed ones are
+// touched; none (or 0 for an entry) = the window lies densely.  Only an entry with a window has one (placed_check).  The fifth column,
+// cut and gathered with the other four.
 struct Planes {
     const u8* elem = nullptr;
     const u8* const* base = nullptr;
     const u8* refused = nullptr;
     const zpk_window* win = nullptr;
+    const u64* pitch = nullptr;
     u32 of(u64 i) const { return elem ? elem[i] : 1u; }
     const u8* base_of(u64 i) const { return base ? base[i] : nullptr; }
     bool refused_at(u64 i) const { return refused && refused[i] && base_of(i) != nullptr; }
     bool windowed(u64 i) const { return win && win[i].row_bytes != 0; }
     Window window_of(u64 i) const { return windowed(i) ? Window{ win[i].row_bytes, win[i].row0, win[i].rows, win[i].col0, win[i].cols } : Window{ 0, 0, 0, 0, 0 }; }
     bool grouped(u64 i) const { return of(i) > 1 || base_of(i) != nullptr || windowed(i); }        // not a plain copy: k_plane_copy's, k_delta_copy's or k_window_copy's
-    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr, base ? base + first : nullptr, refused ? refused + first : nullptr, win ? win + first : nullptr }; }
+    u64 pitch_of(u64 i) const { return pitch ? pitch[i] : 0ull; }
+    bool placed(u64 i) const { return windowed(i) && pitch_of(i) != 0; }
+    Planes from(u64 first) const { return Planes{ elem ? elem + first : nullptr, base ? base + first : nullptr, refused ? refused + first : nullptr, win ? win + first : nullptr, pitch ? pitch + first : nullptr }; }
     bool any() const { return elem != nullptr || base != nullptr || win != nullptr; }
-    // what the caller's buffer and the base of entry i hold: the window's bytes, or those given
-    u64 dst_len(u64 i, u64 whole) const { return windowed(i) ? window_bytes(window_of(i)) : whole; }
+    // what the caller's buffer and the base of entry i hold: the placement's extent, the window's bytes, or those given
+    u64 dst_len(u64 i, u64 whole) const { return placed(i) ? place_extent(window_of(i), pitch[i]) : windowed(i) ? window_bytes(window_of(i)) : whole; }
     // what of the caller's buffer of `cap` bytes the call may write: all of it, of a window's no more than the window (too small a one: cap)
     u64 room(u64 i, u64 cap) const { const u64 w = dst_len(i, cap); return w < cap ? w : cap; }
     inline u64 join_len(u64 i, const zpk_decode_desc& d, const zpk_decode_result& r) const;
@@ -693,7 +702,8 @@ struct LastCall {
     u32  delta[4] = {0, 0, 0, 0};                // zpk_codec_delta_stats: rows split with a base, rows joined with a base, k_delta_copy launches, entries staged only because they had a base
     u32  base_check[4] = {0, 0, 0, 0};           // zpk_codec_base_check_stats: rows hashed by one wave, rows hashed chip-wide, entries refused for their base, launches of the hash pass
     u32  window[3] = {0, 0, 0};                  // zpk_codec_window_stats: rows windowed, k_window_copy launches, entries staged only because they had a window
-    void no_planes() { for (int k = 0; k < 4; k++) planes[k] = delta[k] = base_check[k] = 0; window[0] = window[1] = window[2] = 0; }      // (a call that could split or join begins with this)
+    u32  place[2] = {0, 0};                      // zpk_codec_place_stats: rows placed, k_place_copy launches
+    void no_planes() { for (int k = 0; k < 4; k++) planes[k] = delta[k] = base_check[k] = 0; window[0] = window[1] = window[2] = 0; place[0] = place[1] = 0; }      // (a call that could split or join begins with this)
     u32  planes[4] = {0, 0, 0, 0};               // zpk_codec_planes_stats: rows split, rows joined, k_plane_copy launches, entries staged only because they were grouped
     int  fell_back_fused = 0;                    // the last decode batch could not get its sequence arena and ran the fused decoder only
     // the host-path pipeline decodes one call in several launches: their counters are brought back piece by piece and summed, so that
@@ -710,7 +720,7 @@ struct RowTable { DevBuf<u8> d; PinBuf h; Event ev; bool pending = false; };
 // A growable pinned block (PinBuf) is regrown only while nothing on a stream still reads or writes it: a call that uses one drains the
 // stream it put the copies on before it returns (walk.h_bigsrc, walk.h_bigwalk, sh.h: hipStreamSynchronize behind the copy home; sspan.h: the
 // run waits for its stream on every way out, ~StoredSpanRun), or waits for the event behind its last upload before the block's next turn
-// (bigenc.h, sc.h, pc.h, dc.h, wc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
+// (bigenc.h, sc.h, pc.h, dc.h, wc.h, plc.h).  A call that FAILED may leave a copy behind: zpk_codec_reset waits for the codec's stream.
 struct zpk_codec {
     int device = 0;
     Stream stream;
@@ -791,10 +801,10 @@ struct zpk_codec {
         SideStream side;                         // the second stream of the forked form (created on first use)
     } sspan;
 
-    // plaintext in the caller's device memory: the row tables of k_span_copy, k_plane_copy, k_delta_copy and k_window_copy (row_copy.hip;
-    // span_copy_plan.h, plane_copy_plan.h, delta_copy_plan.h, window_copy_plan.h).  FOUR tables, not one that takes turns: a call with
-    // entries of several kinds fills several of them before any of their kernels has run (rows_enqueue).
-    RowTable sc, pc, dc, wc;
+    // plaintext in the caller's device memory: the row tables of k_span_copy, k_plane_copy, k_delta_copy, k_window_copy and k_place_copy
+    // (row_copy.hip; span_copy_plan.h, plane_copy_plan.h, delta_copy_plan.h, window_copy_plan.h, place_copy_plan.h).  FIVE tables, not one
+    // that takes turns: a call with entries of several kinds fills several of them before any of their kernels has run (rows_enqueue).
+    RowTable sc, pc, dc, wc, plc;
     // the spans k_span_hash and the chip-wide pair hash (span_hash_plan.h / span_hash.h): tables | hashes | partial sums on the device,
     // the tables going up and the hashes coming home through a pinned block of its own — a call that hashes spans waits for its stream
     // behind the copy home, so the block is idle whenever the next call writes it
@@ -1009,7 +1019,7 @@ int zpk_codec_store_device(void* d_dst, const void* host_src, uint64_t bytes) { 
 // the device whose memory `ptr` is, -1 for anything else: the memory's kind alone decides, as a host must not read through such a pointer
 int zpk_codec_pointer_device(const void* ptr) { DevRange r; (void)device_range_of(ptr, &r, DEV_NONE); return r.device; }
 
-// The skeleton of the four row copies: the entries [0, n) of which takes(i) says whether entry i takes a row of table `t`, in ONE kernel
+// The skeleton of the five row copies: the entries [0, n) of which takes(i) says whether entry i takes a row of table `t`, in ONE kernel
 // on `st` (a table past one grid: several, over the same table); returns when the table's upload and the kernel are enqueued.  The rows
 // are written straight into the pinned table by emit(i, rows, p) — false: ZPK_E_INVALID, nothing is uploaded or launched —, so an entry
 // is asked twice, once for the count; launch(d_rows, nrows, L) enqueues one launch.  No rows: nothing is touched.
@@ -1091,8 +1101,26 @@ static int window_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
         },
         [&](const WindowCopyRow* d, u32 nrows, const CopyLaunch& L) { window_copy_launch(d, nrows, L.item0, L.items, L.grid, st); c->last.window[1]++; }, st);
 }
-// The spans row(i) of a batch with element sizes, bases and windows `pl`, all of one direction (join: PLANE_SPLIT / PLANE_JOIN), split
-// FOUR ways: those with a window in ONE k_window_copy, whatever their element size or base (row(i).len is the entry's plain size there,
+// k_place_copy: entry i the row row(i) (a zpk_place_copy; an entry or a window of no bytes: no row).  Element sizes, placements
+// (place_valid), bases and their overlap with the destinations have been checked by the caller; a placement that fails the rule all the
+// same: ZPK_E_INVALID and nothing is launched.
+template <class RowFn>
+static int place_copy_enqueue(zpk_codec* c, u64 n, RowFn row, hipStream_t st)
+{
+    auto bytes = [](const zpk_place_copy& s) { return s.n ? s.win.rows * s.win.cols : 0ull; };
+    return row_table_enqueue<PlaceCopyRow>(c, c->plc, "place copy", n, [&](u64 i) { return bytes(row(i)) != 0; },
+        [&](u64 i, PlaceCopyRow* rows, CopyPlan& p) {
+            const zpk_place_copy s = row(i);
+            if (!bytes(s)) return true;
+            if (!place_copy_emit(s.src, s.dst, s.base, s.n, Window{ s.win.row_bytes, s.win.row0, s.win.rows, s.win.col0, s.win.cols }, s.pitch, s.elem, rows, p)) return false;
+            c->last.place[0]++;
+            return true;
+        },
+        [&](const PlaceCopyRow* d, u32 nrows, const CopyLaunch& L) { place_copy_launch(d, nrows, L.item0, L.items, L.grid, st); c->last.place[1]++; }, st);
+}
+// The spans row(i) of a batch with element sizes, bases, windows and pitches `pl`, all of one direction (join: PLANE_SPLIT / PLANE_JOIN),
+// split FIVE ways: those with a window and a pitch in ONE k_place_copy, even where pitch == cols; those with a window and none in ONE
+// k_window_copy, whatever their element size or base (row(i).len is the entry's plain size there,
 // or 0: nothing is delivered); of the others those with a base in ONE k_delta_copy, those without a base and with an element size above 1
 // in ONE k_plane_copy, the rest in ONE k_span_copy as ever.  No element sizes, bases or windows: span_copy_enqueue and nothing else; no
 // windows: what it was before there were any.
@@ -1106,9 +1134,14 @@ static int rows_enqueue(zpk_codec* c, u64 n, RowFn row, const Planes& pl, u32 jo
     if (rc) return rc;
     if (pl.base) rc = delta_copy_enqueue(c, n, [&](u64 i) { const zpk_span_copy s = row(i); const u8* const b = pl.base_of(i); return zpk_delta_copy{ s.src, s.dst, (u64)b, b && !pl.windowed(i) ? s.len : 0ull, pl.of(i), join }; }, st);
     if (rc || !pl.win) return rc;
-    return window_copy_enqueue(c, n, [&](u64 i) {
+    rc = window_copy_enqueue(c, n, [&](u64 i) {
         const zpk_span_copy s = row(i);
-        return zpk_window_copy{ s.src, s.dst, (u64)pl.base_of(i), pl.windowed(i) ? s.len : 0ull, pl.win[i], pl.of(i), 0u };
+        return zpk_window_copy{ s.src, s.dst, (u64)pl.base_of(i), pl.windowed(i) && !pl.placed(i) ? s.len : 0ull, pl.win[i], pl.of(i), 0u };
+    }, st);
+    if (rc || !pl.pitch) return rc;
+    return place_copy_enqueue(c, n, [&](u64 i) {
+        const zpk_span_copy s = row(i);
+        return zpk_place_copy{ s.src, s.dst, (u64)pl.base_of(i), pl.placed(i) ? s.len : 0ull, pl.win[i], pl.pitch[i], pl.of(i), 0u };
     }, st);
 }
 }  // extern "C++"
@@ -1141,15 +1174,25 @@ static int bases_check(zpk_codec* c, PtrRule& rule, const Planes& pl, u64 n, Len
 }
 
 }  // extern "C++"
-// The windows of a batch, before anything is enqueued.  ZPK_E_INVALID: a window that fails window_valid against its entry's uncomp_size
-// and element size, or one on a batch whose destinations are not device memory.  `staged` becomes the descriptors as the routing is to
+// The windows of a batch and the pitches of those that are placed, before anything is enqueued.  ZPK_E_INVALID: a window that fails
+// window_valid against its entry's uncomp_size and element size, a pitch on an entry without a window or one that fails place_valid with
+// it, or either on a batch whose destinations are not device memory.  `staged` becomes the descriptors as the routing is to
 // see them when an entry has a window (else it stays empty): such an entry decodes into the codec's staging with a slot of uncomp_size
-// — its dst_capacity counts as that; the caller's says what room its buffer has, window_bytes is all the delivery needs of it, and with
+// — its dst_capacity counts as that; the caller's says what room its buffer has, window_bytes (of a placed entry place_extent:
+// Planes::dst_len) is all the delivery needs of it, and with
 // less the capacity counts as 0: the entry earns BUFFER_TOO_SMALL from the kernels' guards, in their order, and nothing is delivered.
 static int windows_check(zpk_codec* c, const Planes& pl, const zpk_decode_desc* desc, u64 n, bool ddst, std::vector<zpk_decode_desc>& staged)
 {
     staged.clear();
     bool any = false;
+    for (u64 i = 0; pl.pitch && i < n; i++) {                                          // the placements: a pitch belongs to a window, and the pair passes place_valid
+        if (!pl.pitch[i]) continue;
+        if (!ddst || !pl.windowed(i) || !place_valid(desc[i].uncomp_size, pl.of(i), pl.window_of(i), pl.pitch[i])) {
+            snprintf(c->err, sizeof(c->err), "entry %llu: a pitch of %llu %s", (unsigned long long)i, (unsigned long long)pl.pitch[i],
+                     !ddst ? "(placements belong to device destinations)" : !pl.windowed(i) ? "without a window" : "that its window does not fit, or an extent that wraps");
+            return ZPK_E_INVALID;
+        }
+    }
     for (u64 i = 0; pl.win && i < n; i++) {
         if (!pl.windowed(i)) continue;
         if (!ddst || !window_valid(desc[i].uncomp_size, pl.of(i), pl.window_of(i))) {
@@ -1161,7 +1204,19 @@ static int windows_check(zpk_codec* c, const Planes& pl, const zpk_decode_desc* 
     }
     if (!any) return ZPK_OK;
     try { staged.assign(desc, desc + n); } catch (...) { return ZPK_E_NOMEM; }
-    for (u64 i = 0; i < n; i++) if (pl.windowed(i)) staged[i].dst_capacity = desc[i].dst_capacity < window_bytes(pl.window_of(i)) ? 0 : desc[i].uncomp_size;
+    for (u64 i = 0; i < n; i++) if (pl.windowed(i)) staged[i].dst_capacity = desc[i].dst_capacity < pl.dst_len(i, 0) ? 0 : desc[i].uncomp_size;     // (a placed one: place_extent)
+    return ZPK_OK;
+}
+// base_hash[i] is the XXH3 of a contiguous span, and the base of a placed entry is not one: ZPK_E_INVALID, before anything runs, for a
+// placed entry with a base in a call that checks bases — unless its extent IS its window's bytes (one row, or pitch == cols), which is
+// checked as ever.  (The caller hashes its whole merged base once: zpk_codec_hash_spans_device.)
+static int placed_hash_check(zpk_codec* c, const Planes& pl, const u64* base_hash, u64 n)
+{
+    for (u64 i = 0; pl.pitch && pl.base && base_hash && i < n; i++)
+        if (pl.placed(i) && pl.base[i] && place_extent(pl.window_of(i), pl.pitch[i]) != window_bytes(pl.window_of(i))) {
+            snprintf(c->err, sizeof(c->err), "entry %llu: a placed base is no contiguous span, there is no hash to check it by", (unsigned long long)i);
+            return ZPK_E_INVALID;
+        }
     return ZPK_OK;
 }
 extern "C++" {
@@ -2102,7 +2157,9 @@ static int decode_big_group(zpk_codec* c, const u8* archive, const zpk_decode_de
         if (pl.base) { gbase.resize(ng); for (u64 k = 0; k < ng; k++) gbase[k] = pl.base_of(be[g0 + k].idx); }
         std::vector<zpk_window> gwin;                                                  // (... and its windows)
         if (pl.win) { gwin.resize(ng); for (u64 k = 0; k < ng; k++) gwin[k] = pl.win[be[g0 + k].idx]; }
-        if ((rc = rows_enqueue(c, ng, row, Planes{ pl.any() ? gelem.data() : nullptr, pl.base ? gbase.data() : nullptr, nullptr, pl.win ? gwin.data() : nullptr }, PLANE_JOIN, c->stream))) return rc;
+        std::vector<u64> gpitch;                                                       // (... and their pitches)
+        if (pl.pitch) { gpitch.resize(ng); for (u64 k = 0; k < ng; k++) gpitch[k] = pl.pitch[be[g0 + k].idx]; }
+        if ((rc = rows_enqueue(c, ng, row, Planes{ pl.any() ? gelem.data() : nullptr, pl.base ? gbase.data() : nullptr, nullptr, pl.win ? gwin.data() : nullptr, pl.pitch ? gpitch.data() : nullptr }, PLANE_JOIN, c->stream))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return ZPK_OK;
     }
@@ -2206,7 +2263,8 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
     if (planes_check(c, pl.elem, n)) return ZPK_E_INVALID;
     std::vector<zpk_decode_desc> staged;                                              // (the windows: their rule, and the slots of the entries that have one)
     if (const int wrc = windows_check(c, pl, desc, n, ddst, staged)) return wrc;
-    // the pointer rule (PtrRule): before anything is enqueued.  (A window's destination and base hold window_bytes bytes: Planes::dst_len.)
+    if (placed_hash_check(c, pl, base_hash, n)) return ZPK_E_INVALID;
+    // the pointer rule (PtrRule): before anything is enqueued.  (A window's destination and base hold window_bytes bytes, a placed one's place_extent: Planes::dst_len.)
     PtrRule rule(c);
     if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return pl.room(i, desc[i].dst_capacity); })) return ZPK_E_INVALID;
     if (bases_check(c, rule, pl, n, [&](u64 i) { return pl.dst_len(i, desc[i].uncomp_size); }, dst_ptrs)) return ZPK_E_INVALID;
@@ -2216,7 +2274,7 @@ static int decode_batch_host_any(zpk_codec* c, const uint8_t* archive, uint64_t 
     int rc = base_verdicts(c, pl, base_hash, n, [&](u64 i) { return pl.dst_len(i, desc[i].uncomp_size); }, refused);
     if (rc) return rc;
     if (!staged.empty()) desc = staged.data();
-    rc = decode_batch_host_routed(c, archive, archive_size, desc, n, dst_ptrs, results, to, Planes{ pl.elem, pl.base, refused.empty() ? nullptr : refused.data(), pl.win });
+    rc = decode_batch_host_routed(c, archive, archive_size, desc, n, dst_ptrs, results, to, Planes{ pl.elem, pl.base, refused.empty() ? nullptr : refused.data(), pl.win, pl.pitch });
     if (rc == ZPK_OK) base_verdicts_mark(refused, desc, results, n);
     return rc;
 }
@@ -2279,7 +2337,8 @@ static int decode_batch_host_routed(zpk_codec* c, const uint8_t* archive, uint64
                 if (k1 > 1) c->last.planes[3]++; else if (b1) c->last.delta[3]++; else c->last.window[2]++;     // (staged because it was grouped; staged only because it had a base; ... a window)
                 const zpk_span_copy row = { (u64)(u8*)c->d_dst, (u64)dst_ptrs[idx], pl.join_len(idx, desc[idx], results[idx]) };
                 const zpk_window w1 = pl.win ? pl.win[idx] : zpk_window{ 0, 0, 0, 0, 0 };
-                if ((rc = rows_enqueue(c, 1, [&](u64) { return row; }, Planes{ &k1, pl.base ? &b1 : nullptr, nullptr, pl.win ? &w1 : nullptr }, PLANE_JOIN, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
+                const u64 p1 = pl.pitch_of(idx);
+                if ((rc = rows_enqueue(c, 1, [&](u64) { return row; }, Planes{ &k1, pl.base ? &b1 : nullptr, nullptr, pl.win ? &w1 : nullptr, pl.pitch ? &p1 : nullptr }, PLANE_JOIN, c->stream)) == ZPK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPK_E_LAUNCH;
             }
             if (rc == ZPK_OK && !again) is_big[idx] = 1;
         }
@@ -2293,15 +2352,17 @@ static int decode_batch_host_routed(zpk_codec* c, const uint8_t* archive, uint64
             std::vector<const u8*> rb(pl.base ? rest.size() : 0);
             std::vector<u8> rf(pl.refused ? rest.size() : 0);
             std::vector<zpk_window> rw(pl.win ? rest.size() : 0);
+            std::vector<u64> rpitch(pl.pitch ? rest.size() : 0);
             for (u64 k = 0; k < rest.size(); k++) {
                 rd[k] = desc[rest[k]]; rp[k] = to == Dst::None ? nullptr : dst_ptrs[rest[k]];
                 if (pl.any()) re[k] = (u8)pl.of(rest[k]);
                 if (pl.base) rb[k] = pl.base_of(rest[k]);
                 if (pl.refused) rf[k] = pl.refused[rest[k]];
                 if (pl.win) rw[k] = pl.win[rest[k]];
+                if (pl.pitch) rpitch[k] = pl.pitch[rest[k]];
             }
             rc = decode_batch_host_plain(c, archive, archive_size, rd.data(), rest.size(), rp.data(), rr.data(), to,
-                                         Planes{ pl.any() ? re.data() : nullptr, pl.base ? rb.data() : nullptr, pl.refused ? rf.data() : nullptr, pl.win ? rw.data() : nullptr });
+                                         Planes{ pl.any() ? re.data() : nullptr, pl.base ? rb.data() : nullptr, pl.refused ? rf.data() : nullptr, pl.win ? rw.data() : nullptr, pl.pitch ? rpitch.data() : nullptr });
             if (rc == ZPK_OK) for (u64 k = 0; k < rest.size(); k++) results[rest[k]] = rr[k];
         }
     } catch (...) { rc = ZPK_E_NOMEM; }
@@ -2320,11 +2381,18 @@ int zpk_codec_decode_batch_host_dptr(zpk_codec* c, const uint8_t* archive, uint6
     return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device);
 }
 
+int zpk_codec_decode_batch_host_dptr_placed(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                            uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                            const uint64_t* base_hash, const zpk_window* win, const uint64_t* pitch)
+{
+    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem, d_base, nullptr, win, pitch }, base_hash);
+}
+
 int zpk_codec_decode_batch_host_dptr_windows(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                              uint8_t* const* d_dst_ptrs, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
                                              const uint64_t* base_hash, const zpk_window* win)
 {
-    return decode_batch_host_any(c, archive, archive_size, desc, n, d_dst_ptrs, results, Dst::Device, Planes{ elem, d_base, nullptr, win }, base_hash);
+    return zpk_codec_decode_batch_host_dptr_placed(c, archive, archive_size, desc, n, d_dst_ptrs, results, elem, d_base, base_hash, win, nullptr);
 }
 
 int zpk_codec_decode_batch_host_dptr_delta_checked(zpk_codec* c, const uint8_t* archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
@@ -2460,6 +2528,61 @@ int zpk_codec_window_stats(zpk_codec* c, uint32_t out[3])
     if (!c || !out) return ZPK_E_INVALID;
     CodecLock lk(c);
     for (int k = 0; k < 3; k++) out[k] = c->last.window[k];
+    return ZPK_OK;
+}
+
+// rows of k_place_copy on their own: element size, window, pitch, both ends and the base (0: none) per row; place_valid, the pointer rule
+// on all three ends of every row — the source over n bytes, destination and base over place_extent — and the overlap rule between base
+// and destination (place_overlap_ok) — on refusal nothing has run
+int zpk_codec_place_copy_device(zpk_codec* c, const zpk_place_copy* rows, uint64_t n, void* stream)
+{
+    if (!c || (n && !rows)) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    c->last.no_planes();
+    if (n == 0) return ZPK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto win = [&](u64 i) { const zpk_window& w = rows[i].win; return Window{ w.row_bytes, w.row0, w.rows, w.col0, w.cols }; };
+    for (u64 i = 0; i < n; i++) {
+        if (!elem_size_ok(c, "row", i, rows[i].elem)) return ZPK_E_INVALID;
+        if (!place_valid(rows[i].n, rows[i].elem, win(i), rows[i].pitch)) {
+            snprintf(c->err, sizeof(c->err), "row %llu: its window does not lie in %llu bytes of %u-byte elements, or not at a pitch of %llu", (unsigned long long)i, (unsigned long long)rows[i].n,
+                     (unsigned)rows[i].elem, (unsigned long long)rows[i].pitch);
+            return ZPK_E_INVALID;
+        }
+    }
+    PtrRule rule(c);
+    auto ext = [&](u64 i) { return place_extent(win(i), rows[i].pitch); };
+    if (rule.batch("place source", n, [&](u64 i) { return (const void*)rows[i].src; }, [&](u64 i) { return ext(i) ? (u64)rows[i].n : 0ull; }) ||
+        rule.batch("place destination", n, [&](u64 i) { return (const void*)rows[i].dst; }, ext) ||
+        rule.batch("place base", n, [&](u64 i) { return (const void*)rows[i].base; }, [&](u64 i) { return rows[i].base ? ext(i) : 0ull; })) return ZPK_E_INVALID;
+    for (u64 i = 0; i < n; i++)
+        if (rows[i].base && !place_overlap_ok(rows[i].base, rows[i].dst, win(i), rows[i].pitch)) {
+            snprintf(c->err, sizeof(c->err), "row %llu: the base overlaps the destination without being it", (unsigned long long)i);
+            return ZPK_E_INVALID;
+        }
+    return place_copy_enqueue(c, n, [&](u64 i) { return rows[i]; }, stream ? (hipStream_t)stream : c->stream);
+}
+
+// place_valid and place_overlap_ok (place_copy_plan.h) for the callers that judge a placement before they have a codec
+int zpk_codec_place_valid(uint64_t n, uint32_t elem, const zpk_window* win, uint64_t pitch, uint64_t* extent)
+{
+    if (!win) return 0;
+    const Window w = { win->row_bytes, win->row0, win->rows, win->col0, win->cols };
+    if (!place_valid(n, elem, w, pitch)) return 0;
+    if (extent) *extent = place_extent(w, pitch);
+    return 1;
+}
+int zpk_codec_place_overlap_ok(uint64_t base, uint64_t dst, const zpk_window* win, uint64_t pitch)
+{
+    return win && place_overlap_ok(base, dst, Window{ win->row_bytes, win->row0, win->rows, win->col0, win->cols }, pitch) ? 1 : 0;
+}
+
+// the most recent call that could split, join, cut or place: out[0] rows placed, out[1] k_place_copy launches
+int zpk_codec_place_stats(zpk_codec* c, uint32_t out[2])
+{
+    if (!c || !out) return ZPK_E_INVALID;
+    CodecLock lk(c);
+    out[0] = c->last.place[0]; out[1] = c->last.place[1];
     return ZPK_OK;
 }
 
@@ -2731,6 +2854,7 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
     if (rule.batch("archive image", 1, [&](u64) { return d_archive; }, [&](u64) { return (u64)archive_size; })) return ZPK_E_INVALID;
     std::vector<zpk_decode_desc> staged;                                              // (the windows: their rule, and the slots of the entries that have one)
     if (const int wrc = windows_check(c, pl_given, desc, n, ddst, staged)) return wrc;
+    if (placed_hash_check(c, pl_given, base_hash, n)) return ZPK_E_INVALID;
     if (ddst && rule.batch("destination", n, [&](u64 i) { return dst_ptrs[i]; }, [&](u64 i) { return pl_given.room(i, desc[i].dst_capacity); })) return ZPK_E_INVALID;
     if (bases_check(c, rule, pl_given, n, [&](u64 i) { return pl_given.dst_len(i, desc[i].uncomp_size); }, dst_ptrs)) return ZPK_E_INVALID;
     begin_decode_call(c);
@@ -2739,7 +2863,7 @@ static int decode_batch_dimage_any(zpk_codec* c, const uint8_t* d_archive, uint6
     std::vector<u8> refused;
     if (const int vrc = base_verdicts(c, pl_given, base_hash, n, [&](u64 i) { return pl_given.dst_len(i, desc[i].uncomp_size); }, refused)) return vrc;
     if (!staged.empty()) desc = staged.data();
-    const Planes pl = { pl_given.elem, pl_given.base, refused.empty() ? nullptr : refused.data(), pl_given.win };
+    const Planes pl = { pl_given.elem, pl_given.base, refused.empty() ? nullptr : refused.data(), pl_given.win, pl_given.pitch };
     const u64 chunk = dimage_chunk(c->opt.dimage_chunk);
     auto slot = [&](u64 i) { return read_slot(none, desc[i]); };                      // (host_plan.h: the host path's slot)
     int rc = ZPK_OK;
@@ -2774,14 +2898,21 @@ int zpk_codec_decode_batch_dimage(zpk_codec* c, const uint8_t* d_archive, uint64
 }
 
 // (element sizes and bases belong to DEVICE destinations: with host destinations every element size has to be 1 and no entry has a base)
-// (... and so do windows: with host destinations no entry has one)
+// (... and so do windows and pitches: with host destinations no entry has one)
+int zpk_codec_decode_batch_dimage_placed(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
+                                         uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
+                                         const uint64_t* base_hash, const zpk_window* win, const uint64_t* pitch)
+{
+    if (!dst_on_device) for (u64 i = 0; i < n; i++) if ((elem && elem[i] != 1) || (d_base && d_base[i]) || (win && win[i].row_bytes) || (pitch && pitch[i])) return ZPK_E_INVALID;
+    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results,
+                                   Planes{ dst_on_device ? elem : nullptr, dst_on_device ? d_base : nullptr, nullptr, dst_on_device ? win : nullptr, dst_on_device ? pitch : nullptr }, base_hash);
+}
+
 int zpk_codec_decode_batch_dimage_windows(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,
                                           uint8_t* const* dst_ptrs, int dst_on_device, zpk_decode_result* results, const uint8_t* elem, const uint8_t* const* d_base,
                                           const uint64_t* base_hash, const zpk_window* win)
 {
-    if (!dst_on_device) for (u64 i = 0; i < n; i++) if ((elem && elem[i] != 1) || (d_base && d_base[i]) || (win && win[i].row_bytes)) return ZPK_E_INVALID;
-    return decode_batch_dimage_any(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device ? Dst::Device : Dst::Host, results,
-                                   Planes{ dst_on_device ? elem : nullptr, dst_on_device ? d_base : nullptr, nullptr, dst_on_device ? win : nullptr }, base_hash);
+    return zpk_codec_decode_batch_dimage_placed(c, d_archive, archive_size, desc, n, dst_ptrs, dst_on_device, results, elem, d_base, base_hash, win, nullptr);
 }
 
 int zpk_codec_decode_batch_dimage_delta_checked(zpk_codec* c, const uint8_t* d_archive, uint64_t archive_size, const zpk_decode_desc* desc, uint64_t n,

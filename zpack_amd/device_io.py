@@ -49,6 +49,18 @@ of the previous checkpoint, of the slice's size, and inplace=True reads into it.
 
     mine, statuses = read_files_device(image, planes="manifest", window={"w": ((4096, 4096), 1, 0, 512)})    # columns [0, 512) of w
 
+Placed reads (include/zpack_amd.h: zpack_amd_read_files_device_placed).  The opposite direction: a checkpoint written by several
+tensor-parallel ranks holds one shard entry per rank and weight, and a loader at another width puts shards side by side in one tensor.
+With place={name: (dest_tensor, dim, start)} the entry — or its `window` slice — lands at [start, start + length) along `dim` of the
+caller's contiguous `dest_tensor`, placed inside the copy that delivers the entry: no scratch tensor per shard and no torch.cat.  The
+tensor returned for such an entry is `dest_tensor`.  Four column shards of a (4096, 4096) bf16 weight merged by one read:
+
+    w = torch.empty(4096, 4096, dtype=torch.bfloat16, device="cuda")
+    shards = ["w.tp0", "w.tp1", "w.tp2", "w.tp3"]                                       # each (4096, 1024)
+    _, statuses = read_files_device(image, names=shards, planes="manifest", place={nm: (w, 1, 1024 * r) for r, nm in enumerate(shards)})
+
+With base= and inplace=True the destination is its own base: the previous checkpoint in the merged layout becomes the new one.
+
 The library works with the devices of ZPACK_AMD_DEVICES (default: ZPACK_AMD_DEVICE, else LOCAL_RANK, else 0); tensors on another device
 are ZPACK_ERROR_NOT_AVAILABLE.
 """
@@ -119,6 +131,8 @@ def lib():
                                                                 C.POINTER(u64), C.POINTER(C.c_int), vp]
         L.zpack_amd_read_files_device_windows.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(vp),
                                                           C.POINTER(u64), C.POINTER(Window), C.POINTER(C.c_int), vp]
+        L.zpack_amd_read_files_device_placed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), C.POINTER(vp),
+                                                         C.POINTER(u64), C.POINTER(Window), C.POINTER(u64), C.POINTER(C.c_int), vp]
         L.zpack_amd_hash_device.argtypes = [C.POINTER(vp), C.POINTER(C.c_size_t), u64, C.POINTER(u64), vp]
         L.zpack_read_file.argtypes = [R, C.POINTER(FileEntry), vp, C.c_size_t, vp]
         L.zpack_amd_read_files_device_packed.argtypes = [R, C.POINTER(C.POINTER(FileEntry)), u64, vp, C.c_size_t, C.POINTER(u64), C.POINTER(C.c_int), vp]
@@ -326,7 +340,48 @@ def _windows_of(pnames, sizes, planes, window):
     return out
 
 
-def read_files_device(archive, names=None, device=0, planes=None, base=None, inplace=False, base_id=None, check_base=True, window=None):
+def _places_of(pnames, sizes, wins, place, dev):
+    """the `place` argument of read_files_device against the entries read: (wins, pitches, offsets, extents) — the windows with one for
+    every placed entry (an entry placed whole becomes the window that is all of it), its pitch (0: not placed), the byte offset of its
+    sub-block in its destination tensor and the bytes from that offset to the sub-block's last; ValueError naming the entry for a
+    destination that is not a contiguous tensor on `dev`, a size that does not divide into the destination's rows, or a slice past it"""
+    from . import place_of
+    unknown = [nm for nm in place if nm not in pnames]
+    if unknown:
+        raise KeyError("place names no entry of this read: %s" % ", ".join(unknown))
+    wins = list(wins) if wins is not None else [Window(0, 0, 0, 0, 0) for _ in pnames]
+    pitches, offsets, extents = [0] * len(pnames), [0] * len(pnames), [0] * len(pnames)
+    for k, (nm, size) in enumerate(zip(pnames, sizes)):
+        if nm not in place:
+            continue
+        try:
+            dest, dim, start = place[nm]
+            dim, start = int(dim), int(start)
+            if not (dest.is_cuda and dest.is_contiguous() and dest.device == dev):
+                raise ValueError("the destination is a contiguous CUDA tensor on %s" % (dev,))
+            w = wins[k]
+            n = int(w.rows * w.cols) if w.row_bytes else size                           # the bytes delivered
+            rows, unit, pitch, _ = place_of(dest.shape, dim, 0, 1, dest.element_size())   # (unit: the bytes of one step along dim, in one row)
+            if rows * unit == 0 or n % (rows * unit):
+                raise ValueError("%d bytes do not divide into %d rows of %d-byte steps along dim %d of %r" % (n, rows, unit, dim, tuple(dest.shape)))
+            rows, cols, pitch, offset = place_of(dest.shape, dim, start, n // (rows * unit), dest.element_size())
+            if n == 0:
+                continue                                                                # (nothing to deliver: no placement)
+            if not w.row_bytes:
+                w = Window(cols, 0, rows, 0, cols)                                      # the entry whole, seen as the sub-block's rows
+            elif (w.rows, w.cols) != (rows, cols):
+                # a window that is one contiguous run of the entry (whole rows, or part of one row) is that run seen as the sub-block's rows
+                first = w.row0 * w.row_bytes + w.col0
+                if not (w.rows == 1 or w.cols == w.row_bytes) or first % cols or size % cols:
+                    raise ValueError("its window has %d rows of %d bytes, the destination %d of %d" % (w.rows, w.cols, rows, cols))
+                w = Window(cols, first // cols, rows, 0, cols)
+            wins[k], pitches[k], offsets[k], extents[k] = w, pitch, offset, (rows - 1) * pitch + cols
+        except (TypeError, ValueError) as err:
+            raise ValueError("place of %s: %s" % (nm, err)) from None
+    return wins, pitches, offsets, extents
+
+
+def read_files_device(archive, names=None, device=0, planes=None, base=None, inplace=False, base_id=None, check_base=True, window=None, place=None):
     """`archive`: a path, the archive's bytes, or the archive image as a contiguous uint8 CUDA tensor (zpack_amd_init_reader_device: the
     compressed bytes are decoded where they lie, nothing crosses the bus; `device` is then the tensor's).  `names`: the entries to read,
     in that order (None: all, in archive order).  `planes`: None — the entries' bytes as they are stored; {name: element size} — those
@@ -347,6 +402,14 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
     that size.  A shape that does not multiply out to the entry's size, or a dim, start or stop out of range, raises ValueError naming
     the entry before anything is decoded.  A recorded "base_xxh3" is the hash of the WHOLE base, which the reader of a window does not
     hold: a windowed entry with a base in such an archive raises ValueError unless check_base=False.  None: no entry has a window.
+    `place`: {name: (dest_tensor, dim, start)} — those entries, or their `window` slices, land at [start, start + length) along dimension
+    `dim` of the caller's contiguous `dest_tensor` on the read's device (zpack_amd_read_files_device_placed: the placement rides on the
+    copy that delivers the entry; several entries may share one destination, side by side).  `length` follows from the entry's size —
+    the bytes delivered over the destination's rows and the bytes of one step along `dim`; a size that does not divide, or a slice past
+    the destination, raises ValueError naming the entry before anything is decoded.  The tensor returned for such an entry is
+    `dest_tensor`; what the read does not place in it stays as it was.  Its base is a tensor in the destination's layout and of its
+    size, read at the bytes that are written; with inplace=True it is `dest_tensor` itself: the destination is its own base.  A recorded
+    "base_xxh3" is handled as for a windowed entry: ValueError unless check_base=False.  None: no entry is placed.
     Returns (tensors, statuses): one uint8 CUDA tensor of uncomp_size bytes per entry on cuda:`device` — views of one allocation, each at
     a multiple of 256 — and the zpack_result of each (0 = decoded and its XXH3 verified; anything else: the tensor's bytes are not the entry)."""
     import torch
@@ -379,19 +442,40 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
                 if w.row_bytes and nm in base and check_base and recorded_hash is not None:
                     raise ValueError("%s: the archive records the hash of its WHOLE base, which the reader of a window does not hold; read it with check_base=False" % nm)
             sizes = [int(w.rows * w.cols) if w.row_bytes else s for w, s in zip(wins, sizes)]      # (what the buffers and the bases hold)
+        dev = torch.device("cuda", device)
+        pitches = None
+        if place:
+            whole = [int(r.file_entries[i].uncomp_size) for i in picks]
+            wins, pitches, offsets, extents = _places_of(pnames, whole, wins, place, dev)
+            for k, nm in enumerate(pnames):
+                if pitches[k] and nm in base and check_base and recorded_hash is not None:
+                    raise ValueError("%s: the archive records the hash of its base as one span, which a placed base is not; read it with check_base=False" % nm)
+            sizes = [0 if p else s for p, s in zip(pitches, sizes)]                                # (a placed entry takes nothing of the backing)
         starts, total = [], 0
         for s in sizes:
             starts.append(total)
             total += (s + 255) & ~255
-        dev = torch.device("cuda", device)
         backing = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         tensors = [backing[a:a + s] for a, s in zip(starts, sizes)]
-        bases = [_base_bytes(nm, base[nm], s) if nm in base else None for nm, s in zip(pnames, sizes)]
+        bases = [_base_bytes(nm, base[nm], s) if nm in base and not (pitches and pitches[k]) else None for k, (nm, s) in enumerate(zip(pnames, sizes))]
         out = list(tensors)
         if inplace:
             for k, b in enumerate(bases):
                 if b is not None:
                     tensors[k], out[k] = b, base[pnames[k]]
+        if pitches:
+            # a placed entry: its buffer is its sub-block of the destination, its base the same bytes of a tensor in the destination's layout
+            for k, nm in enumerate(pnames):
+                if not pitches[k]:
+                    continue
+                dest = place[nm][0]
+                flat = dest.reshape(-1).view(dtype=_u8())
+                tensors[k], out[k], sizes[k] = flat[offsets[k]:offsets[k] + extents[k]], dest, extents[k]
+                if nm in base:
+                    b = _base_bytes(nm, base[nm], flat.numel())
+                    if inplace and b.data_ptr() != flat.data_ptr():
+                        raise ValueError("place of %s: with inplace=True the destination is its own base" % nm)
+                    bases[k] = b[offsets[k]:offsets[k] + extents[k]]
         ents = (C.POINTER(FileEntry) * max(n, 1))(*[C.pointer(r.file_entries[i]) for i in picks])
         bufs = (C.c_void_p * max(n, 1))(*[t.data_ptr() if s else None for t, s in zip(tensors, sizes)])
         caps = (C.c_size_t * max(n, 1))(*sizes)
@@ -409,8 +493,12 @@ def read_files_device(archive, names=None, device=0, planes=None, base=None, inp
                     unlisted = [k for k, (nm, b) in enumerate(zip(pnames, bases)) if b is not None and nm not in recorded_hash]
                     own = dict(zip(unlisted, _hash_flat(L, [bases[k] for k in unlisted])))
                     want = (C.c_uint64 * max(n, 1))(*[own[k] if k in own else recorded_hash.get(nm, 0) for k, nm in enumerate(pnames)])
-            _check(L.zpack_amd_read_files_device_windows(C.byref(r), ents, n, bufs, caps, elem, d_bases, want, (Window * max(n, 1))(*wins), res, None),
-                   "zpack_amd_read_files_device_windows")
+            if pitches:
+                _check(L.zpack_amd_read_files_device_placed(C.byref(r), ents, n, bufs, caps, elem, d_bases, want, (Window * max(n, 1))(*wins),
+                                                            (C.c_uint64 * max(n, 1))(*pitches), res, None), "zpack_amd_read_files_device_placed")
+            else:
+                _check(L.zpack_amd_read_files_device_windows(C.byref(r), ents, n, bufs, caps, elem, d_bases, want, (Window * max(n, 1))(*wins), res, None),
+                       "zpack_amd_read_files_device_windows")
         elif any(b is not None for b in bases):
             for b in bases:
                 if b is not None:

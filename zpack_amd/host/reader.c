@@ -424,19 +424,19 @@ static zpack_u64 entry_weight(const void* entries, zpack_u64 i)
 static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                           zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                           const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int dest, const zpack_u8* elem,
-                          const zpack_u8* const* bases, const zpack_u64* base_hashes, const zpk_window* win);
+                          const zpack_u8* const* bases, const zpack_u64* base_hashes, const zpk_window* win, const zpack_u64* pitch);
 
 int zi_decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                       zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                       const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size)
 {
-    return decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, span, span_lo, span_size, ZI_DST_HOST, NULL, NULL, NULL, NULL);
+    return decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, span, span_lo, span_size, ZI_DST_HOST, NULL, NULL, NULL, NULL, NULL);
 }
 
 int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                              zpack_u8* const* d_buffers, const size_t* max_sizes, zpk_decode_result* res)
 {
-    return decode_entries(reader, ctx, entries, count, d_buffers, max_sizes, res, NULL, 0, 0, ZI_DST_DEVICE, NULL, NULL, NULL, NULL);
+    return decode_entries(reader, ctx, entries, count, d_buffers, max_sizes, res, NULL, 0, 0, ZI_DST_DEVICE, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* ZI_DST_DEVICE: buffers[i] are DEVICE pointers — the plaintext stays there, only the compressed bytes cross the bus: the batch is one
@@ -447,11 +447,13 @@ int zi_decode_entries_device(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry
  * bases (likewise): the entries' bases in device memory, NULL for an entry that has none — XORed in on the same way
  * base_hashes (likewise): what each base has to hash to before it is applied (the codec's _delta_checked calls); NULL: no check
  * win (likewise): the entries' windows, row_bytes 0 for an entry read whole (the codec's _windows calls) — max_sizes[i] is then the room
- * for window_bytes bytes; NULL: no entry has one */
+ * for window_bytes bytes; NULL: no entry has one
+ * pitch (likewise): the destination row pitches of the placed entries, 0 for an entry that is not (the codec's _placed calls) — max_sizes[i]
+ * is then the room for place_extent bytes; NULL: no entry is placed */
 static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* const* entries, zpack_u64 count,
                           zpack_u8* const* buffers, const size_t* max_sizes, zpk_decode_result* res,
                           const zpack_u8* span, zpack_u64 span_lo, zpack_u64 span_size, int dest, const zpack_u8* elem,
-                          const zpack_u8* const* bases, const zpack_u64* base_hashes, const zpk_window* win)
+                          const zpack_u8* const* bases, const zpack_u64* base_hashes, const zpk_window* win, const zpack_u64* pitch)
 {
     const int on_device = dest == ZI_DST_DEVICE, none = dest == ZI_DST_NONE;
 #define ZI_CAP(i) (none ? (size_t)entries[i]->uncomp_size : max_sizes[i])
@@ -506,11 +508,11 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
         zpk_codec* codec = zi_ctx_codec_on(ctx, d_device);
         if (!codec) rc = ZPACK_ERROR_NOT_AVAILABLE;
         else if (none) rc = test_rc_of_codec(zpk_codec_verify_batch_dimage(codec, d_image, image_size, desc, count, res));
-        else rc = zi_rc_of_codec(zpk_codec_decode_batch_dimage_windows(codec, d_image, image_size, desc, count, buffers, on_device, res, elem, bases, base_hashes, win));
+        else rc = zi_rc_of_codec(zpk_codec_decode_batch_dimage_placed(codec, d_image, image_size, desc, count, buffers, on_device, res, elem, bases, base_hashes, win, pitch));
     } else if (rc == ZPACK_OK && on_device) {
         zpk_codec* codec = zi_ctx_codec_of(ctx, buffers, sizeof(*buffers), max_sizes, sizeof(*max_sizes), sizeof(size_t) == 8, count, &rc);
         if (!codec && rc == ZPACK_OK) codec = ctx->dev[0];                           /* (nothing has bytes: verdicts only) */
-        if (codec) rc = zi_rc_of_codec(zpk_codec_decode_batch_host_dptr_windows(codec, image, image_size, desc, count, buffers, res, elem, bases, base_hashes, win));
+        if (codec) rc = zi_rc_of_codec(zpk_codec_decode_batch_host_dptr_placed(codec, image, image_size, desc, count, buffers, res, elem, bases, base_hashes, win, pitch));
     } else if (rc == ZPACK_OK) {
         read_job job = { ctx, image, image_size, desc, buffers, res, {0}, {0} };
         /* static shard: contiguous ranges of the batch balanced by comp + uncomp bytes, one host thread
@@ -526,7 +528,7 @@ static int decode_entries(zpack_reader* reader, zi_ctx* ctx, zpack_file_entry* c
 
 static int read_batch_planes(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
                              zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int dest, const zpack_u8* elem,
-                             const zpack_u8* const* bases, const zpack_u64* base_hashes, const zpk_window* win)
+                             const zpack_u8* const* bases, const zpack_u64* base_hashes, const zpk_window* win, const zpack_u64* pitch)
 {
     if (count == 0) return ZPACK_OK;
     if (zi_reader_source(reader, NULL, NULL) == ZI_SRC_NONE) return ZPACK_ERROR_ARCHIVE_NOT_LOADED;
@@ -535,7 +537,7 @@ static int read_batch_planes(zpack_reader* reader, zpack_file_entry* const* entr
     if (!ctx) return ZPACK_ERROR_NOT_AVAILABLE;              /* no HIP device: there is no CPU fallback */
     zpk_decode_result* res = (zpk_decode_result*)calloc((size_t)count, sizeof(*res));
     if (!res) return ZPACK_ERROR_MALLOC_FAILED;
-    const int rc = decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0, dest, elem, bases, base_hashes, win);
+    const int rc = decode_entries(reader, ctx, entries, count, buffers, max_sizes, res, NULL, 0, 0, dest, elem, bases, base_hashes, win, pitch);
     if (rc == ZPACK_OK)
         for (zpack_u64 i = 0; i < count; i++) {
             results[i] = res[i].status;
@@ -548,7 +550,7 @@ static int read_batch_planes(zpack_reader* reader, zpack_file_entry* const* entr
 static int read_batch(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
                       zpack_u8* const* buffers, const size_t* max_sizes, int* results, void* dctx, int dest)
 {
-    return read_batch_planes(reader, entries, count, buffers, max_sizes, results, dctx, dest, NULL, NULL, NULL, NULL);
+    return read_batch_planes(reader, entries, count, buffers, max_sizes, results, dctx, dest, NULL, NULL, NULL, NULL, NULL);
 }
 
 int zpack_read_file(zpack_reader* reader, zpack_file_entry* entry, zpack_u8* buffer, size_t max_size, void* dctx)
@@ -628,21 +630,44 @@ _Static_assert(ZPACK_AMD_ERROR_BASE_MISMATCH > ZPACK_ERROR_NOT_AVAILABLE, "disti
  * The windows' rule and the overlap of a windowed entry's base with its buffer are judged here, by the codec's statement of both, before
  * any context is created; NULL: the _delta_checked call */
 _Static_assert(sizeof(zpack_amd_window) == sizeof(zpk_window) && offsetof(zpack_amd_window, cols) == offsetof(zpk_window, cols), "windows[] is handed to the codec as it is");
-int zpack_amd_read_files_device_windows(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
-                                        void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes, const void* const* d_bases,
-                                        const zpack_u64* base_hashes, const zpack_amd_window* windows, int* results, void* dctx)
+/* ... some of which are PLACED: dst_pitches[i] != 0 = the window of entry i lands in a sub-block of a larger tensor, window row r at
+ * r * dst_pitches[i] of d_buffers[i].  The placements' rule, a pitch without a window, the overlap of a placed entry's base with its
+ * buffer and a placed base in a call that checks hashes are judged here too, by the codec's statement of each; NULL: the _windows call */
+int zpack_amd_read_files_device_placed(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                       void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes, const void* const* d_bases,
+                                       const zpack_u64* base_hashes, const zpack_amd_window* windows, const zpack_u64* dst_pitches, int* results, void* dctx)
 {
     if (!reader || (count && (!entries || !d_buffers || !max_sizes || !results))) return ZPACK_ERROR_STREAM_INVALID;
     if (!zi_elem_sizes_valid(elem_sizes, count)) return ZPACK_ERROR_STREAM_INVALID;  /* before any context is created */
     const zpk_window* const win = (const zpk_window*)windows;
-    for (zpack_u64 i = 0; win && i < count; i++) {
-        if (!win[i].row_bytes) continue;
-        if (!entries[i] || !zpk_codec_window_valid(entries[i]->uncomp_size, elem_sizes ? elem_sizes[i] : 1u, &win[i], NULL)) return ZPACK_ERROR_STREAM_INVALID;
-        if (d_bases && d_bases[i] && !zpk_codec_window_overlap_ok((zpack_u64)(uintptr_t)d_bases[i], (zpack_u64)(uintptr_t)d_buffers[i], &win[i])) return ZPACK_ERROR_STREAM_INVALID;
+    for (zpack_u64 i = 0; i < count; i++) {
+        const zpack_u64 pitch = dst_pitches ? dst_pitches[i] : 0;
+        const zpack_u64 base = d_bases ? (zpack_u64)(uintptr_t)d_bases[i] : 0, dst = (zpack_u64)(uintptr_t)d_buffers[i];
+        if (!win || !win[i].row_bytes) {
+            if (pitch) return ZPACK_ERROR_STREAM_INVALID;                           /* a pitch belongs to a window */
+            continue;
+        }
+        const zpack_u32 k = elem_sizes ? elem_sizes[i] : 1u;
+        if (!entries[i] || !zpk_codec_window_valid(entries[i]->uncomp_size, k, &win[i], NULL)) return ZPACK_ERROR_STREAM_INVALID;
+        if (!pitch) {
+            if (base && !zpk_codec_window_overlap_ok(base, dst, &win[i])) return ZPACK_ERROR_STREAM_INVALID;
+            continue;
+        }
+        zpack_u64 extent = 0;
+        if (!zpk_codec_place_valid(entries[i]->uncomp_size, k, &win[i], pitch, &extent)) return ZPACK_ERROR_STREAM_INVALID;
+        if (base && !zpk_codec_place_overlap_ok(base, dst, &win[i], pitch)) return ZPACK_ERROR_STREAM_INVALID;
+        if (base && base_hashes && extent != win[i].rows * win[i].cols) return ZPACK_ERROR_STREAM_INVALID;       /* no hash of a pitched base */
     }
     if (zpk_codec_device_count() <= 0) return ZPACK_ERROR_NOT_AVAILABLE;           /* no HIP device: there is no CPU fallback */
     return read_batch_planes(reader, entries, count, (zpack_u8* const*)d_buffers, max_sizes, results, dctx, ZI_DST_DEVICE, elem_sizes,
-                             (const zpack_u8* const*)d_bases, base_hashes, win);
+                             (const zpack_u8* const*)d_bases, base_hashes, win, dst_pitches);
+}
+
+int zpack_amd_read_files_device_windows(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
+                                        void* const* d_buffers, const size_t* max_sizes, const zpack_u8* elem_sizes, const void* const* d_bases,
+                                        const zpack_u64* base_hashes, const zpack_amd_window* windows, int* results, void* dctx)
+{
+    return zpack_amd_read_files_device_placed(reader, entries, count, d_buffers, max_sizes, elem_sizes, d_bases, base_hashes, windows, NULL, results, dctx);
 }
 
 int zpack_amd_read_files_device_delta_checked(zpack_reader* reader, zpack_file_entry* const* entries, zpack_u64 count,
